@@ -13,7 +13,12 @@ Inputs are synthetic and generated ON THE DEVICE before the timed region (QPSK t
 txWaveform, Philox AWGN inside the kernels).  Prints one JSON line on rank 0.
 
 `--gpus N` without a torchrun environment launches N ranks itself (one per GPU, RCCL); under torchrun the
-launcher's RANK / LOCAL_RANK / WORLD_SIZE are used.  `roofline` quotes the dominant HBM-bound kernel (the fused
+launcher's RANK / LOCAL_RANK / WORLD_SIZE are used.
+
+A plain run sets up, primes and warms up, times the K steps and prints the line; `--dump-outputs DIR` also writes
+what the last timed step computed (dump_outputs).  Everything else is measured with `--full` only: `roofline`,
+`pipeline.blocking_cpi_ms`, the `cold` block and `cpu_baseline`, all after the timed region.
+`--full`: `roofline` quotes the dominant HBM-bound kernel (the fused
 echo-synthesis + range-stage kernel: the largest share of the wide kernels' time and of the bytes), timed with HIP
 events inside the run; `roofline.top_by_time` names whichever kernel has the largest time share in the committed
 rocprofv3 single-stream summary (profiles/rNN_kernel_stats_single_stream.csv), and `roofline.traffic` is read from the
@@ -155,6 +160,7 @@ class SlotPool:
             for c in self.ctxs[1:]:
                 c.share_streams(self.ctxs[0])
         self.owner = [None] * len(self.ctxs)
+        self.last_cell = [None] * len(self.ctxs)     # the cell whose CPI each context ran last
         self.k = 0
         self.timeline = None          # list of (collect_s, enqueue_s) per submit while recording (host-side stalls show up here)
         self.pace_s = 0.0             # minimum spacing of consecutive submissions (0 = none): see --pace-ms
@@ -163,6 +169,8 @@ class SlotPool:
 
     def collect(self, slot):
         cell, self.owner[slot] = self.owner[slot], None
+        if cell is not None:
+            self.last_cell[slot] = cell
         return cell.finish(self.ctxs[slot]) if cell is not None else None
 
     def submit(self, cell):
@@ -249,12 +257,14 @@ class Cell:
         self.seed = 0x5EED0002 + cell_id
         self.n_sub = 0
         self.last = None
+        self.last_ctx = None          # the context the last collected CPI ran on
         self.profile_sink = None      # list: per-launch durations of the fused kernel (HIP events recorded by the library)
         ctx.sync()
 
     def finish(self, ctx):
         """Collect the CPI this cell enqueued on `ctx`."""
         est = None
+        self.last_ctx = ctx
         if self.profile_sink is not None and self.fuse:
             ms = C.c_double(0.0)
             if ctx.lib.isac_profile_last_kernel_ms(ctx.handle, C.byref(ms)) == 0:
@@ -630,52 +640,59 @@ def run_config5(args, pkg, rank, world, local_rank, dist, torch):
     on_gpu = dist is not None and dist.get_backend() == "nccl"
     allr = d.gather_records(recs, dist, torch.device("cuda", local_rank) if on_gpu else None)
     dt_max = float(np.nanmax(allr[:, 6])) if allr.size else dt
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, mine, sense, records=recs)
     if rank != 0:
         return
-    # ---- the contraction kernel with the device to itself: 10 launches of the larger group's batch, HIP events around exactly that launch
     cc = comm[0]
-    gi, n_jobs, flops, n_paths = cc.gemm_launch()
-    ctx_cdl.check(ctx_cdl.lib.isac_profile_enable(ctx_cdl.handle, 1))
-    ms_k, ms_call = [], []
-    # (the batch the frame loop issues: SLOTS_PER_CALL consecutive slots x the UEs of the group -- the persistent grid of the fused kernel is priced on the
-    #  launch shape it actually runs with; a one-slot batch would spend a quarter of its tiles on warm-up)
-    n_slots = min(CommCell.SLOTS_PER_CALL, CommCell.DL_SLOTS)
-    n_jobs, flops = n_jobs * n_slots, flops * n_slots
-    for i in range(11):
-        ctx_cdl.sync(); ctx_cdl.timer_start()
-        cc.CM.applyCDLBatch([cc.chans[u] for s_ in range(n_slots) for u in cc.groups[gi]], [cc.waves[(i + s_) % cc.DL_SLOTS] for s_ in range(n_slots) for u in cc.groups[gi]],
-                            ctx=ctx_cdl, outs=cc.rx[gi][:n_jobs], gains=cc.gains[gi])
-        v = C.c_double(0.0)
-        ctx_cdl.check(ctx_cdl.lib.isac_profile_last_kernel_ms(ctx_cdl.handle, C.byref(v)))
-        ms_call.append(ctx_cdl.timer_stop_ms()); ms_k.append(v.value)
-    ms_k, ms_call = float(np.mean(ms_k[1:])), float(np.mean(ms_call[1:]))
-    t1 = time.perf_counter()
-    for _ in range(3):
-        cc.csi_reports()
-    ms_csi = 1e3 * (time.perf_counter() - t1) / (3 * cc.CSI_OCCASIONS * cc.n_ues)
     n_applies = sum(c_.n_ues for c_ in comm) * CommCell.DL_SLOTS
-    time_domain = bool(os.environ.get("ISAC_CDL_TIME_DOMAIN") or os.environ.get("ISAC_CDL_UNFUSED")) or args.ants != 64
-    if time_domain:
-        roof = {"bound": "mfma", "kernel": "cdl_fused_kernel<NCT,NSLOT> (DL apply of a batch in one persistent launch: contraction X [T x Nt] against the path gains of every job, 3M form on "
-                                           "v_mfma_f64_16x16x4_f64, + 16-tap delay filters + integer delays on the CU; Z never in HBM)" if not os.environ.get("ISAC_CDL_UNFUSED") else
-                                           "cdl_gemm_kernel<NCT,false> (DL contraction of a batch; ISAC_CDL_UNFUSED: the delay filter is a second launch, Z through HBM)",
-                "achieved": round(flops / 1e12 / (ms_k / 1e3), 2), "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(flops / 1e12 / (ms_k / 1e3) / FP64_MFMA_PEAK_TFLOPS, 4),
-                "traffic": None, "avg_launch_ms": round(ms_k, 4), "launches_averaged": 10, "jobs_per_launch": n_jobs, "paths": n_paths,
-                "issued_flops_per_launch": flops, "flops_note": "contraction only (the launch also runs the delay filters on the VALU: + 16 % flops, not counted): 3 real MFMAs x 2 flops per complex multiply-add, padded to 16-column tiles: 6 T cols Nt per job",
-                "whole_batch_call_ms": round(ms_call, 4), "whole_batch_note": "path gains + apply of the same batch, HIP events around the call",
-                "timing": "HIP events recorded by the library around the apply launch (isac_profile_*), device otherwise idle"}
-    else:
-        fa, fb, n_seg = cc.os_mix_flops(gi, n_jobs)
-        roof = {"bound": "mfma", "kernel": "cdl_os_mix_mfma_kernel (overlap-save DL apply, the arithmetic of the path: per 16-bin tile C(f) = sum_n H_n E_n(f) on v_mfma_f64_16x16x4_f64 -- 3M complex form --, "
-                                           "then Y(f) = C(f) X(f) for every 4096-sample window on the fp64 VALU; forward / inverse transforms are separate HBM-bound launches)",
-                "achieved": round((fa + fb) / 1e12 / (ms_k / 1e3), 2), "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round((fa + fb) / 1e12 / (ms_k / 1e3) / FP64_MFMA_PEAK_TFLOPS, 4),
-                "traffic": None, "avg_launch_ms": round(ms_k, 4), "launches_averaged": 10, "jobs_per_launch": n_jobs, "paths": n_paths, "windows": n_seg,
-                "issued_flops_per_launch": fa + fb, "mfma_flops": fa, "valu_flops": fb,
-                "flops_note": "matrix-pipe flops of C(f) (three real MFMAs per complex product, paths padded to a multiple of four) + vector flops of Y(f) (8 per complex multiply-add), one gain "
-                              "block per job (a lower bound); the part's fp64 vector and matrix peaks are the same 78.6 TFLOP/s.  The time-domain formulation of rounds 4-5 issued 1.09 GF per "
-                              "job on the matrix pipe for the same result: this launch needs %.2f GF per job" % ((fa + fb) / n_jobs / 1e9),
-                "whole_batch_call_ms": round(ms_call, 4), "whole_batch_note": "path gains + forward transforms + mix + inverse transforms of the same batch, HIP events around the call",
-                "timing": "HIP events recorded by the library around the mix launch (isac_profile_*), device otherwise idle"}
+    roof = seams = None
+    # ---- --full: the contraction kernel with the device to itself (10 launches of the larger group's batch, HIP events around exactly that launch)
+    #      and the CSI reports with the device otherwise idle
+    if args.full:
+        gi, n_jobs, flops, n_paths = cc.gemm_launch()
+        ctx_cdl.check(ctx_cdl.lib.isac_profile_enable(ctx_cdl.handle, 1))
+        ms_k, ms_call = [], []
+        # (the batch the frame loop issues: SLOTS_PER_CALL consecutive slots x the UEs of the group -- the persistent grid of the fused kernel is priced on the
+        #  launch shape it actually runs with; a one-slot batch would spend a quarter of its tiles on warm-up)
+        n_slots = min(CommCell.SLOTS_PER_CALL, CommCell.DL_SLOTS)
+        n_jobs, flops = n_jobs * n_slots, flops * n_slots
+        for i in range(11):
+            ctx_cdl.sync(); ctx_cdl.timer_start()
+            cc.CM.applyCDLBatch([cc.chans[u] for s_ in range(n_slots) for u in cc.groups[gi]], [cc.waves[(i + s_) % cc.DL_SLOTS] for s_ in range(n_slots) for u in cc.groups[gi]],
+                                ctx=ctx_cdl, outs=cc.rx[gi][:n_jobs], gains=cc.gains[gi])
+            v = C.c_double(0.0)
+            ctx_cdl.check(ctx_cdl.lib.isac_profile_last_kernel_ms(ctx_cdl.handle, C.byref(v)))
+            ms_call.append(ctx_cdl.timer_stop_ms()); ms_k.append(v.value)
+        ms_k, ms_call = float(np.mean(ms_k[1:])), float(np.mean(ms_call[1:]))
+        t1 = time.perf_counter()
+        for _ in range(3):
+            cc.csi_reports()
+        ms_csi = 1e3 * (time.perf_counter() - t1) / (3 * cc.CSI_OCCASIONS * cc.n_ues)
+        time_domain = bool(os.environ.get("ISAC_CDL_TIME_DOMAIN") or os.environ.get("ISAC_CDL_UNFUSED")) or args.ants != 64
+        if time_domain:
+            roof = {"bound": "mfma", "kernel": "cdl_fused_kernel<NCT,NSLOT> (DL apply of a batch in one persistent launch: contraction X [T x Nt] against the path gains of every job, 3M form on "
+                                               "v_mfma_f64_16x16x4_f64, + 16-tap delay filters + integer delays on the CU; Z never in HBM)" if not os.environ.get("ISAC_CDL_UNFUSED") else
+                                               "cdl_gemm_kernel<NCT,false> (DL contraction of a batch; ISAC_CDL_UNFUSED: the delay filter is a second launch, Z through HBM)",
+                    "achieved": round(flops / 1e12 / (ms_k / 1e3), 2), "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(flops / 1e12 / (ms_k / 1e3) / FP64_MFMA_PEAK_TFLOPS, 4),
+                    "traffic": None, "avg_launch_ms": round(ms_k, 4), "launches_averaged": 10, "jobs_per_launch": n_jobs, "paths": n_paths,
+                    "issued_flops_per_launch": flops, "flops_note": "contraction only (the launch also runs the delay filters on the VALU: + 16 % flops, not counted): 3 real MFMAs x 2 flops per complex multiply-add, padded to 16-column tiles: 6 T cols Nt per job",
+                    "whole_batch_call_ms": round(ms_call, 4), "whole_batch_note": "path gains + apply of the same batch, HIP events around the call",
+                    "timing": "HIP events recorded by the library around the apply launch (isac_profile_*), device otherwise idle"}
+        else:
+            fa, fb, n_seg = cc.os_mix_flops(gi, n_jobs)
+            roof = {"bound": "mfma", "kernel": "cdl_os_mix_mfma_kernel (overlap-save DL apply, the arithmetic of the path: per 16-bin tile C(f) = sum_n H_n E_n(f) on v_mfma_f64_16x16x4_f64 -- 3M complex form --, "
+                                               "then Y(f) = C(f) X(f) for every 4096-sample window on the fp64 VALU; forward / inverse transforms are separate HBM-bound launches)",
+                    "achieved": round((fa + fb) / 1e12 / (ms_k / 1e3), 2), "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round((fa + fb) / 1e12 / (ms_k / 1e3) / FP64_MFMA_PEAK_TFLOPS, 4),
+                    "traffic": None, "avg_launch_ms": round(ms_k, 4), "launches_averaged": 10, "jobs_per_launch": n_jobs, "paths": n_paths, "windows": n_seg,
+                    "issued_flops_per_launch": fa + fb, "mfma_flops": fa, "valu_flops": fb,
+                    "flops_note": "matrix-pipe flops of C(f) (three real MFMAs per complex product, paths padded to a multiple of four) + vector flops of Y(f) (8 per complex multiply-add), one gain "
+                                  "block per job (a lower bound); the part's fp64 vector and matrix peaks are the same 78.6 TFLOP/s.  The time-domain formulation of rounds 4-5 issued 1.09 GF per "
+                                  "job on the matrix pipe for the same result: this launch needs %.2f GF per job" % ((fa + fb) / n_jobs / 1e9),
+                    "whole_batch_call_ms": round(ms_call, 4), "whole_batch_note": "path gains + forward transforms + mix + inverse transforms of the same batch, HIP events around the call",
+                    "timing": "HIP events recorded by the library around the mix launch (isac_profile_*), device otherwise idle"}
+        seams = {"cdl_apply_ms_per_job": round(ms_call / n_jobs, 4), "csi_report_ms_per_ue": round(ms_csi, 4),
+                 "csi_note": "host wall per UE of the batched report (one synchronisation per cell and occasion), device otherwise idle"}
     res = {"metric": "sensing slots/sec (CDL echo->2D-FFT->2D-CFAR)", "value": round(n_cells * 20 * args.steps / dt_max, 2), "unit": "slots/sec (whole cells: sensing CPI + CDL applies + CSI reports)",
            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * dt_max / args.steps, 3), "higher_is_better": True, "scaling": "strong",
            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
@@ -692,12 +709,11 @@ def run_config5(args, pkg, rank, world, local_rank, dist, torch):
                                   "ul_applies": sum(c_.n_ues for c_ in comm) * CommCell.UL_SLOTS if CommCell.WITH_UL else 0, "precoded": True,
                                   "csi_h": "device, per occasion" if CommCell.DEVICE_CSI else "host, once at set-up",
                                   "rank_selection": CommCell.WITH_RI, "srs_reports": sum(c_.n_ues for c_ in comm) if CommCell.WITH_UL and CommCell.WITH_SRS else 0},
-           "roofline": roof,
-           "comm_seams": {"cdl_apply_ms_per_job": round(ms_call / n_jobs, 4), "csi_report_ms_per_ue": round(ms_csi, 4),
-                          "csi_note": "host wall per UE of the batched report (one synchronisation per cell and occasion), device otherwise idle"},
            "cells": [d.record_json(r) for r in allr[:64]],
            "cells_note": "gathered from every rank (one all_gather of fixed-size records, _dist.py): every cell's whole estResults (fft2D.m:102,114-115) and every UE's last "
                          "CSI report of the frame (wideband CQI, subband CQIs, PMI i1 / i2: networkSimulation.m:173-232)"}
+    if args.full:
+        res["roofline"], res["comm_seams"] = roof, seams
     print(json.dumps(res))
 
 
@@ -884,6 +900,60 @@ def roofline_entry(cell, args, ms_timed, ms_iso, n_launches, stages, cpi_bytes, 
             "other_stages": stages, "whole_cpi": whole}
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6          # every .npy file counted whole, header included
+
+
+def dump_outputs(out_dir, cell_ids, cells, records=None):
+    """`--dump-outputs DIR`: what the timed path computed in its last step, one float64 DIR/cell<id>_<name>.npy per array -- the estResults the
+    caller of each cell's last CPI received (rngEst, velEst, aziEst, eleEst; none where the library reported NO_DETECTION) and the fft2D state of
+    that CPI a caller reads back (fft2D_debug: covariance Ra as [A x A x 2] real / imaginary parts, the |rdm|^2 window around the CUTs, the MUSIC
+    spectrum in dB; left out for a cell whose context ran another cell's CPI after it).  `records` (config5): each cell's gathered record with
+    the CSI / SRS reports of its UEs, elapsed time zeroed.  The inputs are seeded and the timed steps restart every cell's seed sequence, so the
+    same arguments give the same arrays.  Every value written is finite: the library and the record mark "no value" with NaN (eleEst of a ULA, which
+    has no elevation scan; the unused slots of a record), so an array with such entries is written as its finite entries (flattened) with their flat
+    indices in cell<id>_<name>_finite_idx.npy, and an array with no finite entry, or none at all, is left out.  At most 64 MB in all: beyond that
+    the largest arrays are replaced by a fixed, seeded sample of their elements (cell<id>_<name>_sample.npy, the flat indices in
+    cell<id>_<name>_sample_idx.npy)."""
+    dbg_fn = importlib.import_module(PKG + ".sensing.estimation.fft2D").fft2D_debug
+    arrays = {}
+    for cid, cell in zip(cell_ids, cells):
+        est = cell.last
+        for k in ("rngEst", "velEst", "aziEst", "eleEst"):
+            arrays[f"cell{cid}_{k}"] = np.asarray(getattr(est, k) if est is not None else [], dtype=np.float64).reshape(-1)
+        slot = next((s for s, c in enumerate(cell.pool.ctxs) if c is cell.last_ctx), None)
+        if slot is not None and cell.pool.last_cell[slot] is cell:          # (the fft2D state of that CPI is still on its context)
+            dbg = dbg_fn(cell.last_ctx, cell.A)
+            arrays[f"cell{cid}_Ra"] = np.stack([dbg.Ra.real, dbg.Ra.imag], axis=-1)
+            arrays[f"cell{cid}_power_window"] = np.asarray(dbg.power_window, dtype=np.float64)
+            arrays[f"cell{cid}_music_spectrum_db"] = np.asarray(dbg.spectrum_db, dtype=np.float64)
+    for r in (records if records is not None else []):
+        r = np.array(r, dtype=np.float64)
+        r[6] = 0.0
+        arrays[f"cell{int(r[0])}_record"] = r
+    finite = {}
+    for name, a in arrays.items():
+        ok = np.isfinite(a)
+        if ok.all() and a.size:
+            finite[name] = a
+        elif ok.any():
+            finite[name], finite[name + "_finite_idx"] = a[ok], np.flatnonzero(ok).astype(np.float64)
+    arrays = finite
+    # fit the 64 MB: smallest arrays first, each at most an equal share of what is left (128-byte .npy header per file, two files for a sample)
+    left, out = DUMP_LIMIT_BYTES - 256 * len(arrays), {}
+    for i, (name, a) in enumerate(sorted(arrays.items(), key=lambda kv: kv[1].nbytes)):
+        share = left // (len(arrays) - i)
+        if a.nbytes <= share:
+            out[name] = a
+            left -= a.nbytes
+        else:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // 16, replace=False))
+            out[name + "_sample"], out[name + "_sample_idx"] = a.reshape(-1)[idx], idx.astype(np.float64)
+            left -= 16 * idx.size
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
 def cold_probe(args, pkg):
     """`--cold-probe MODE` (internal; run by the main bench in a FRESH process): what the drop-in's real caller sees.  The reference runs the sensing chain
     once per cell and simulation (cellSimulation.m:189-202, one worker per cell: networkSimulation.m:47-60), so the first calls of a process matter.
@@ -956,8 +1026,13 @@ def respawn_under_torchrun(n_gpus):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=100)
-    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 100; config5: 3 frames)")
+    ap.add_argument("--warmup", type=int, default=None, help="warm-up steps before the timed ones (default 10; config5: 1 frame)")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: the roofline entry (isolated kernel launches, committed "
+                                                        "profile facts), the per-stage table, the blocking-CPI latency, the cold-start probes and the CPU baseline; "
+                                                        "config5: the isolated CDL launch and the CSI report times")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what their last step computed as DIR/<name>.npy "
+                                                                        "(float64, at most 64 MB; see dump_outputs)")
     ap.add_argument("--ants", type=int, default=64)
     ap.add_argument("--slots", type=int, default=16)
     ap.add_argument("--targets", type=int, default=1)
@@ -981,8 +1056,8 @@ def main():
     ap.add_argument("--schedule", choices=("ordered", "free"), default="free",
                     help="ordered: all in-flight contexts enqueue on ONE pair of streams (isac_ctx_share_streams + ISAC_OPT_WIDE_ORDER) -- the wide kernels of "
                          "consecutive CPIs run back to back, never side by side, no pacing; free: two streams per context, the device interleaves the CPIs")
-    ap.add_argument("--trace-only", action="store_true", help="profiling aid: nothing after the timed region (no isolated-kernel / blocking-CPI / stage / CPU legs), "
-                                                              "so that a rocprofv3 trace holds priming + warm-up + the timed steps only")
+    ap.add_argument("--trace-only", action="store_true", help="profiling aid: with --full, nothing after the timed region (no isolated-kernel / blocking-CPI / stage / "
+                                                              "CPU legs), so that a rocprofv3 trace holds priming + warm-up + the timed steps only")
     ap.add_argument("--workload", choices=("config2", "config5"), default="config2",
                     help="config2 (default): the sensing CPI BASELINE's metric is quoted on; config5: BASELINE configs[4] -- per frame and cell one sensing CPI + every "
                          "DL slot through every UE's CDL channel + every UE's CSI reports (--cells, default 21; --ues)")
@@ -1025,11 +1100,11 @@ def main():
             local_rank = local_rank % max(n_dev, 1)
             dist.init_process_group(backend)
     pkg = importlib.import_module(PKG)
+    if args.steps is None:
+        args.steps = 3 if args.workload == "config5" else 100
+    if args.warmup is None:
+        args.warmup = 1 if args.workload == "config5" else 10
     if args.workload == "config5":
-        if "--steps" not in sys.argv:
-            args.steps = 3
-        if "--warmup" not in sys.argv:
-            args.warmup = 1
         run_config5(args, pkg, rank, world, local_rank, dist, torch)
         if dist is not None:
             dist.destroy_process_group()
@@ -1099,12 +1174,15 @@ def main():
             pool.drain(); pool.sync()
             n1_in_run = args.steps * len(cells) * args.slots / (time.perf_counter() - t1)
         barrier()
-    sink = [] if (rank == 0 and args.fuse) else None
+    sink = [] if (rank == 0 and args.fuse and args.full) else None    # (--full: per-launch events of the fused kernel for `roofline`)
     if sink is not None:
         for c_ in pool.ctxs:
             c_.check(c_.lib.isac_profile_enable(c_.handle, 1))
         for cell in cells:
             cell.profile_sink = sink
+    pool.k = 0                                               # the timed steps' seeds, buffers and contexts do not depend on how many priming steps ran
+    for cell in cells:
+        cell.n_sub = 0
     barrier()
     pool.timeline = []
     pool.next_t, pool.spin_run = 0.0, 0
@@ -1125,17 +1203,20 @@ def main():
     tl, pool.timeline = np.array(pool.timeline).reshape(-1, 2), None
     for cell in cells:
         cell.profile_sink = None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, my_cells, cells)
+    extra = args.full and not args.trace_only                # the legs after the timed region: --full only
     dom_ms_timed = float(np.mean(sink)) if sink else None                       # fused kernel, launches of the timed region (other CPIs co-running)
-    dom_ms_iso = cells[0].time_dominant_kernel_isolated() if (rank == 0 and args.fuse and not args.trace_only) else None
-    cov_ms_iso = cells[0].time_covariance_kernel_isolated() if (rank == 0 and args.fuse and not args.trace_only) else None
+    dom_ms_iso = cells[0].time_dominant_kernel_isolated() if (rank == 0 and args.fuse and extra) else None
+    cov_ms_iso = cells[0].time_covariance_kernel_isolated() if (rank == 0 and args.fuse and extra) else None
     blocking_ms = None
-    if rank == 0 and not args.trace_only:                    # latency of one blocking CPI (submit + collect, nothing else in flight)
+    if rank == 0 and extra:                                  # latency of one blocking CPI (submit + collect, nothing else in flight)
         cells[0].step()
         tb = time.perf_counter()
         for _ in range(3):
             cells[0].step()
         blocking_ms = 1e3 * (time.perf_counter() - tb) / 3
-    stages = stage_table(cells[0]) if (rank == 0 and not args.trace_only) else []
+    stages = stage_table(cells[0]) if (rank == 0 and extra) else []
     # per-cell result record gather -- the only collective (KB-scale, RCCL over xGMI); max over ranks of the timed region
     recs = np.array([d.make_record(cid, cell.last, dt) for cid, cell in zip(my_cells, cells)]).reshape(-1, d.RECORD_LEN)
     on_gpu = dist is not None and dist.get_backend() == "nccl"
@@ -1179,8 +1260,9 @@ def main():
                                    + ("echo grid LAZY (kept inside the context as a descriptor: never written to HBM, the covariance kernel re-forms its operands from the same D, a, seed -- identical CFAR lists and estimates, isac.h 'LAZY echo grid'), " if args.lazy else "echo grid materialised (written by monoStaticSensing, read back by the covariance), ")
                                    + f"{args.inflight} CPIs in flight",
                        "parallelism": f"cells sharded over {world} GPU(s)"},
-            "roofline": roofline_entry(cells[0], args, dom_ms_timed, dom_ms_iso, len(sink or []), stages, echo_b + rdm_b, per_cpi_ms, cov_ms_iso),
         }
+        if args.full:
+            res["roofline"] = roofline_entry(cells[0], args, dom_ms_timed, dom_ms_iso, len(sink or []), stages, echo_b + rdm_b, per_cpi_ms, cov_ms_iso)
         res["cells"] = [d.record_json(r) for r in allr[:64]]                      # every cell's whole estResults, gathered from every rank
         if world > 1:
             n1 = n1_in_run if n1_in_run is not None else args.n1_value
@@ -1190,9 +1272,9 @@ def main():
                                     "efficiency_vs_n1": None if n1 is None else round(res["value"] / (world * n1), 4),
                                     "note": f"efficiency = value / (N x N=1 value of {per_gpu}); no multi-GPU scaling curve has been measured on hardware yet "
                                             "(DESIGN.md section 7) -- the driver computes its own from the per-N lines"}
-        if world == 1 and not args.trace_only and not args.no_cold and args.workload == "config2":
+        if world == 1 and extra and not args.no_cold and args.workload == "config2":
             res["cold"] = cold_block(args)
-        if not args.no_cpu_baseline and world == 1 and not args.trace_only:
+        if not args.no_cpu_baseline and world == 1 and extra:
             res["cpu_baseline"] = cpu_baseline(cells[0])
             res["gpu_vs_cpu_baseline"] = round(res["value"] / res["cpu_baseline"]["value"], 1)
         print(json.dumps(res))

@@ -7,7 +7,7 @@ ROOT=$(pwd); OUT=$ROOT/gpurun_out/prof_$TAG; mkdir -p $OUT
 export TMPDIR=/tmp; cd /tmp
 PS="python $ROOT/tools/prof_summary.py"
 db() { find "$1" -name "*.db" | head -1; }
-B="python $ROOT/bench.py --no-cpu-baseline --prime-ms 0 --inflight 1 $*"
+B="python $ROOT/bench.py --full --no-cpu-baseline --prime-ms 0 --inflight 1 $*"
 rm -rf /tmp/q1 && ISAC_SINGLE_STREAM=1 rocprofv3 --kernel-trace -d /tmp/q1 -- $B --steps 10 --warmup 2 > /dev/null 2>&1
 $PS $(db /tmp/q1) --csv $OUT/${TAG}_kernel_stats_single_stream.csv > $OUT/${TAG}_kernel_stats_single_stream.txt
 for c in FETCH_SIZE WRITE_SIZE; do

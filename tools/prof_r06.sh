@@ -8,7 +8,7 @@ export TMPDIR=/tmp; cd /tmp
 PS="python $ROOT/tools/prof_summary.py"
 db() { find "$1" -name "*.db" | head -1; }
 for MODE in ${MODES:-lazy array}; do
-  B="python $ROOT/bench.py --no-cpu-baseline --no-cold --prime-ms 0 --inflight 1 --echo $MODE $*"
+  B="python $ROOT/bench.py --full --no-cpu-baseline --no-cold --prime-ms 0 --inflight 1 --echo $MODE $*"
   rm -rf /tmp/q1 && ISAC_SINGLE_STREAM=1 rocprofv3 --kernel-trace -d /tmp/q1 -- $B --steps 20 --warmup 3 > /dev/null 2>&1
   $PS $(db /tmp/q1) --csv $OUT/${TAG}_${MODE}_kernel_stats_single_stream.csv > $OUT/${TAG}_${MODE}_kernel_stats_single_stream.txt
   for c in FETCH_SIZE WRITE_SIZE; do

@@ -12,7 +12,7 @@ export TMPDIR=/tmp
 cd /tmp
 PS="python $ROOT/tools/prof_summary.py"
 db() { find "$1" -name "*.db" | head -1; }
-B="python $ROOT/bench.py"
+B="python $ROOT/bench.py --full"
 
 # ---- bench lines: the driver's invocation, the longer run, and the variants
 $B --gpus 1 --steps 20 --warmup 5 > $OUT/${TAG}_bench_driver_invocation.json 2> $OUT/bench.err
