@@ -393,7 +393,7 @@ struct DevPool {
   std::map<void*, Blk> size_of[16];                // every block the pool has handed out or holds
   size_t parked_bytes[16] = {0};
   size_t cap = 16384ull << 20;
-  DevPool() { if (const char* e = std::getenv("ISAC_DEV_POOL_MB")) cap = (size_t)std::strtoull(e, nullptr, 10) << 20; }
+  DevPool() { if (const char* e = std::getenv("ISAC_DEV_POOL_MB")) cap = (size_t)std::strtoull(e, nullptr, 10) << 20; }   // configuration (isac.h)
 };
 DevPool& dev_pool() { static DevPool p; return p; }
 }  // namespace
@@ -618,7 +618,7 @@ static int fft2d_submit(isac_ctx* ctx, const isac_est_params* ep, const isac_cfa
     ISAC_TRY(get_sind_table(ctx, ep, &d_sind, &n_steps));
     ISAC_TRY(ensure(ctx, ctx->spec, sizeof(double) * (size_t)n_steps));
   }
-  static const bool single_stream = std::getenv("ISAC_SINGLE_STREAM") != nullptr;   // profiling aid: isolate kernel times
+  static const bool single_stream = std::getenv("ISAC_SINGLE_STREAM") != nullptr;   // diagnostic: one stream, isolated kernel times
   hipStream_t s2 = single_stream ? ctx->stream : ctx->stream2;
   // ISAC_OPT_WIDE_ORDER: the covariance (a wide kernel) stays on the main stream, behind the echo synthesis / range stage; everything
   // narrow -- Doppler, CFAR, the MUSIC chain, pack, the D2H copy -- runs on the second stream in one sequence.  With contexts that share
@@ -940,7 +940,7 @@ extern "C" int isac_eigh(isac_ctx* ctx, const isac_c64* H, int32_t A, double* w,
   ISAC_TRY(copy_d2h(ctx, vv.data(), ctx->eig_v.p, sizeof(c64) * (size_t)A * A));
   ISAC_HIP(hipStreamSynchronize(ctx->stream));
   ISAC_TRY(eig_status(ctx, A));
-  if (std::getenv("ISAC_DEBUG")) {
+  if (std::getenv("ISAC_DEBUG")) {                 // diagnostic: eigensolver phase counters on stderr
     int inf[16] = {-1, 0, 0, 0, 0, 0};
     ISAC_TRY(copy_d2h(ctx, inf, (char*)ctx->eig_w.p + sizeof(double) * (size_t)A, sizeof(inf)));
     if (A > 64 && A <= 256)
@@ -1024,7 +1024,7 @@ extern "C" int isac_eigh_top(isac_ctx* ctx, const isac_c64* H, int32_t A, int32_
   ISAC_TRY(copy_d2h(ctx, ctl, isac_music_ctl(ctx), sizeof(ctl)));
   ISAC_HIP(hipStreamSynchronize(ctx->stream));
   ISAC_TRY(eig_status(ctx, A, ctl[0] != 1));
-  if (std::getenv("ISAC_DEBUG")) {
+  if (std::getenv("ISAC_DEBUG")) {                 // diagnostic: eigensolver phase counters on stderr
     int inf[15] = {0};
     ISAC_TRY(copy_d2h(ctx, inf, (char*)ctx->eig_w.p + sizeof(double) * (size_t)A, sizeof(inf)));
     std::fprintf(stderr, "[isac] eigh_top A=%d n_top=%d phases(x64 clk): tridiag=%d (n <= 64: reflector=%d matvec=%d matvec+update=%d) | subspace: set-up=%d solves=%d "

@@ -340,14 +340,12 @@ __device__ __forceinline__ void lds_barrier() {
 // rows are XOR-swizzled inside aligned groups of eight: the 16 lanes of a filter task column read rows 8 g + m -- (g & 1, (g >> 1) ^ m) is a different bank quad for every g
 __device__ __forceinline__ int fz_swz(int p) { return p ^ ((p >> 4) & 7); }
 
-template <int NCT, int NSLOT, bool PROF = false>
+template <int NCT, int NSLOT>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void cdl_fused_kernel(const CdlSeg* __restrict__ segs, const CdlWork* __restrict__ works, const int* __restrict__ wg_first, long long lda, long long ldy, int Nt,
                       int n_paths, const double* __restrict__ taps16 /* [n_paths][16], zero padded */,
                       const int* __restrict__ pmeta /* [NCT][8]: per column tile its paths in delay order, packed local path | (delay & 127) << 8 | (delay >> 7) << 16 | valid << 24 */,
-                      double scale, long long* __restrict__ prof /* PROF: [workgroup][8] cycles per phase (development: ISAC_CDL_FUSED_PROF) */) {
-  long long pc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, pt = 0;
-  auto stamp = [&](int i) { if constexpr (PROF) { const long long t = (long long)__builtin_readcyclecounter(); pc[i] += t - pt; pt = t; } };
+                      double scale) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   constexpr int KS = 16, Nr = 2;
   const int Nc = n_paths * Nr;
@@ -407,11 +405,9 @@ void cdl_fused_kernel(const CdlSeg* __restrict__ segs, const CdlWork* __restrict
     unsigned ro_cur = row_off(sg.r0 + (long long)wk.tile0 * kFzRows), ro_nxt;
 #pragma unroll
     for (int s_ = 0; s_ < kFzPf; ++s_) xq[s_] = load_a(ro_cur, s_);
-    stamp(6);                                                                // (bucket 6: everything outside the tile loop, incl. the first reading)
     for (int tile = wk.tile0; tile < wk.tile1; ++tile) {
       const long long row0 = sg.r0 + (long long)tile * kFzRows;
       ro_nxt = row_off(row0 + kFzRows);
-      stamp(7);
       // ---- 1. contraction: 16 k-steps x (NCT column tiles x 3 forms) MFMAs on this wave's 16 rows
       v4f64 p1[NCT], p2[NCT], p3[NCT];
 #pragma unroll
@@ -436,7 +432,6 @@ void cdl_fused_kernel(const CdlSeg* __restrict__ segs, const CdlWork* __restrict
         __builtin_amdgcn_sched_barrier(0);
       });
       ro_cur = ro_nxt;
-      stamp(0);
       static_for<0, NCT>([&](auto ctc) {
         constexpr int ct = decltype(ctc)::value;
         // ---- 2. Z of this column tile -> LDS (f64 MFMA C/D layout: lane (li, kq) holds rows kq + 4 r of column li), history rows in front.
@@ -448,7 +443,6 @@ void cdl_fused_kernel(const CdlSeg* __restrict__ segs, const CdlWork* __restrict
         }
         if (tid < 256) zbuf[(tid >> 4) * kFzLd + fz_swz(tid & 15)] = hk[ct];
         lds_barrier();
-        stamp(1);
         // ---- 3. delay filters in Z space: 23 window samples (one component) in registers, 8 independent accumulation chains
         {
           const double* zc = zre + 2 * (fc * kFzLd);
@@ -477,9 +471,7 @@ void cdl_fused_kernel(const CdlSeg* __restrict__ segs, const CdlWork* __restrict
 #pragma unroll
           for (int r = 0; r < 8; ++r) fo[2 * (po + (r ^ xo))] = a[r];         // (the previous tile's gather of fbuf lies in front of the barrier above)
         }
-        stamp(2);
         lds_barrier();
-        stamp(3);
         // ---- 4. integer delays: for every path of this column tile, the one row of the tile that lands on a row = rho (mod 128)
         {
           int pm[kFzPpt], h0[kFzPpt], h1[kFzPpt];
@@ -508,7 +500,6 @@ void cdl_fused_kernel(const CdlSeg* __restrict__ segs, const CdlWork* __restrict
             }
           }
         }
-        stamp(4);
       });
       {
         const long long row = row0 + rho;
@@ -519,12 +510,7 @@ void cdl_fused_kernel(const CdlSeg* __restrict__ segs, const CdlWork* __restrict
         for (int j = 0; j + 1 < NSLOT; ++j) slot[j] = slot[j + 1];
         slot[NSLOT - 1] = 0.0;
       }
-      stamp(5);
     }
-  }
-  if constexpr (PROF) {
-    if (tid == 0)
-      for (int i = 0; i < 8; ++i) prof[blockIdx.x * 8 + i] = pc[i];
   }
 }
 
@@ -607,7 +593,7 @@ __global__ __launch_bounds__(256) void cdl_freq_response_kernel(const c64* __res
 //      parts; 23 window samples in registers) write XF into the swizzled LDS tile in A-operand order, then 4 k-steps x NCT column tiles x 3 (3M) MFMAs per wave accumulate;
 //   3. y is stored straight from the accumulators (the eight waves of a column tile complete 2 KB runs per column together).
 // Tiles are independent (the filter is a gather on x, which is in memory): no ring, no warm-up; sums of an output run chunk-major, k ascending -- a fixed order.
-template <int NCT, bool PROF = false>
+template <int NCT>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void cdl_fused_ul_kernel(const CdlSeg* __restrict__ segs, const CdlWork* __restrict__ works, const int* __restrict__ wg_first, long long ldx, long long ldy, int Nr, int n_paths,
                          const double* __restrict__ taps16 /* [n_paths][16], zero padded */, const int* __restrict__ shift, int hist /* H */, double scale) {
@@ -814,7 +800,7 @@ int launch_gemm(isac_ctx* ctx, const CdlSeg* d_segs, int n_segs, long long max_r
 // Fused downlink apply: does the shape fit the kernel's envelope?  (Everything else -- uplink, more than 64 transmit elements, more than two receive
 // antennas (or one), more than 24 paths, filters longer than 16 taps, delays beyond 895 samples -- takes the unfused kernels.)
 bool cdl_fused_ok(long long T, int Nt, int Nr, int n_paths, int n_taps, int max_shift) {
-  static const bool off = std::getenv("ISAC_CDL_UNFUSED") != nullptr;        // development switch: contraction + filter as separate launches (Z through HBM)
+  static const bool off = std::getenv("ISAC_CDL_UNFUSED") != nullptr;        // test hook: contraction + filter as separate launches (Z through HBM)
   return !off && Nr == 2 && Nt >= 2 && Nt <= 64 && n_paths <= 3 * kFzPpt && n_taps <= kFzTaps && max_shift < 128 * 7 && (long long)T * Nr < (1ll << 28);
 }
 
@@ -863,7 +849,7 @@ int launch_fused(isac_ctx* ctx, const std::vector<CdlSeg>& segs, long long T, in
   long long total = 0;
   for (size_t i = 0; i < segs.size(); ++i) { seg_tiles[i] = segs[i].o1 > segs[i].o0 ? (segs[i].r1 - segs[i].r0 + kFzRows - 1) / kFzRows : 0; total += seg_tiles[i]; }
   if (total == 0) return ISAC_OK;
-  static const int wgs_env = std::getenv("ISAC_CDL_FUSED_WGS") ? std::atoi(std::getenv("ISAC_CDL_FUSED_WGS")) : 0;   // development switch: workgroups of the persistent grid
+  static const int wgs_env = std::getenv("ISAC_CDL_FUSED_WGS") ? std::atoi(std::getenv("ISAC_CDL_FUSED_WGS")) : 0;   // test hook: workgroups of the persistent grid
   const int n_wg = (int)std::min<long long>(wgs_env > 0 ? wgs_env : ctx->n_cus, total);
   std::vector<CdlWork> works;
   std::vector<int> wg_first;
@@ -888,29 +874,8 @@ int launch_fused(isac_ctx* ctx, const std::vector<CdlSeg>& segs, long long T, in
     auto kern = cdl_fused_kernel<NCT, NSLOT>;                                                                                                               \
     ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(kern), lds_bytes));                                                                               \
     hipLaunchKernelGGL(kern, dim3((unsigned)n_wg), dim3(512), lds_bytes, ctx->stream, (const CdlSeg*)(dm + o_seg), (const CdlWork*)(dm + o_wk),            \
-                       (const int*)(dm + o_wf), (long long)T, (long long)T, Nt, n_paths, (const double*)(dm + o_tap), (const int*)(dm + o_pm), out_scale,  \
-                       (long long*)nullptr);                                                                                                                \
+                       (const int*)(dm + o_wf), (long long)T, (long long)T, Nt, n_paths, (const double*)(dm + o_tap), (const int*)(dm + o_pm), out_scale);   \
   } while (0)
-  static const bool prof_on = std::getenv("ISAC_CDL_FUSED_PROF") != nullptr;   // development switch: cycles per phase of every workgroup on stderr (synchronises)
-  if (prof_on && nslot == 4 && nct >= 2) {
-    ISAC_TRY(ensure(ctx, ctx->misc, sizeof(long long) * 8 * (size_t)n_wg));
-    auto launch = [&](auto kern) -> int {
-      ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(kern), lds_bytes));
-      hipLaunchKernelGGL(kern, dim3((unsigned)n_wg), dim3(512), lds_bytes, ctx->stream, (const CdlSeg*)(dm + o_seg), (const CdlWork*)(dm + o_wk), (const int*)(dm + o_wf), (long long)T,
-                         (long long)T, Nt, n_paths, (const double*)(dm + o_tap), (const int*)(dm + o_pm), out_scale, (long long*)ctx->misc.p);
-      return ISAC_OK;
-    };
-    if (nct == 2) ISAC_TRY(launch(cdl_fused_kernel<2, 4, true>)); else ISAC_TRY(launch(cdl_fused_kernel<3, 4, true>));
-    std::vector<long long> h(8 * (size_t)n_wg);
-    ISAC_HIP(hipMemcpyAsync(h.data(), ctx->misc.p, sizeof(long long) * h.size(), hipMemcpyDeviceToHost, ctx->stream));
-    ISAC_HIP(hipStreamSynchronize(ctx->stream));
-    double sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int w = 0; w < n_wg; ++w) for (int i = 0; i < 8; ++i) sum[i] += (double)h[8 * (size_t)w + i];
-    const double tiles_wg = (double)total / n_wg;
-    std::fprintf(stderr, "CDLPROF wgs %d tiles/wg %.1f (+%d warm-up) | cycles per workgroup: mfma %.0f  z-write+barrier %.0f  filter+f-write %.0f  barrier %.0f  gather %.0f  store %.0f  tile-head %.0f\n", n_wg, tiles_wg, warm,
-                 sum[0] / n_wg, sum[1] / n_wg, sum[2] / n_wg, sum[3] / n_wg, sum[4] / n_wg, sum[5] / n_wg, sum[7] / n_wg);
-    return ISAC_OK;
-  }
   if (nslot == 4) { switch (nct) { case 1: ISAC_CDL_FUSED(1, 4); break; case 2: ISAC_CDL_FUSED(2, 4); break; default: ISAC_CDL_FUSED(3, 4); break; } }
   else { switch (nct) { case 1: ISAC_CDL_FUSED(1, 8); break; case 2: ISAC_CDL_FUSED(2, 8); break; default: ISAC_CDL_FUSED(3, 8); break; } }
 #undef ISAC_CDL_FUSED
@@ -921,7 +886,7 @@ int launch_fused(isac_ctx* ctx, const std::vector<CdlSeg>& segs, long long T, in
 
 // Fused uplink apply: two transmit elements into an array of up to 64 elements, <= 24 paths, <= 16 taps, delays that keep the x window within LDS.
 bool cdl_fused_ul_ok(long long T, int Nt, int Nr, int n_paths, int n_taps, int max_shift) {
-  static const bool off = std::getenv("ISAC_CDL_UNFUSED") != nullptr;
+  static const bool off = std::getenv("ISAC_CDL_UNFUSED") != nullptr;        // test hook (as above)
   return !off && Nt == 2 && Nr > Nt && Nr <= 64 && n_paths <= 3 * kFzPpt && n_taps <= kFzTaps && max_shift + kFzTaps <= 896 && (long long)T * Nr < (1ll << 28);
 }
 
@@ -940,7 +905,7 @@ int launch_fused_ul(isac_ctx* ctx, const std::vector<CdlSeg>& segs, long long T,
   long long total = 0;
   for (size_t i = 0; i < segs.size(); ++i) { seg_tiles[i] = segs[i].o1 > segs[i].o0 ? (segs[i].o1 - segs[i].o0 + kFzRows - 1) / kFzRows : 0; total += seg_tiles[i]; }
   if (total == 0) return ISAC_OK;
-  static const int wgs_env = std::getenv("ISAC_CDL_FUSED_WGS") ? std::atoi(std::getenv("ISAC_CDL_FUSED_WGS")) : 0;
+  static const int wgs_env = std::getenv("ISAC_CDL_FUSED_WGS") ? std::atoi(std::getenv("ISAC_CDL_FUSED_WGS")) : 0;   // test hook (as above)
   const int n_wg = (int)std::min<long long>(wgs_env > 0 ? wgs_env : ctx->n_cus, total);
   std::vector<CdlWork> works;
   std::vector<int> wg_first;
@@ -1061,7 +1026,7 @@ int cdl_apply_jobs(isac_ctx* ctx, const isac_cdl_job* jobs, int n_jobs, long lon
   char* dm = (char*)ctx->stage_c.p;
   ISAC_TRY(stage_upload(ctx, dm, host.data(), meta));
   const CdlSeg* d_segs = (const CdlSeg*)dm;
-  static const bool fir1 = std::getenv("ISAC_CDL_FIR1") != nullptr;     // development switch: the one-output-per-thread filter kernel for every tap count
+  static const bool fir1 = std::getenv("ISAC_CDL_FIR1") != nullptr;     // test hook: the one-output-per-thread filter kernel for every tap count
   const bool fir4 = n_taps == 16 && !fir1;
   const double* d_taps = (const double*)(dm + seg_bytes);
   const int* d_shift = (const int*)(dm + seg_bytes + tap_bytes);

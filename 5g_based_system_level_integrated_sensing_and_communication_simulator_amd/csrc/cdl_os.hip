@@ -19,7 +19,7 @@
 //   inverse transform's registers; no mix launch, no Y spectra.
 // Per CDL-A downlink job at config 5's shape 0.15 GF (matrix + vector pipe) + 36 inverse transforms + a fifth of the waveform's forward transforms -- against 1.09 GF of MFMA issue
 // + 0.18 GF of filter FMAs.  Every output sample is produced by exactly one (pair, window): no accumulation across launches, results independent of the batch composition.
-// Envelope: T >= 2 windows, Mpad <= 1024; everything else (and ISAC_CDL_TIME_DOMAIN=1 / ISAC_CDL_UL_TIME_DOMAIN=1) stays on the time-domain kernels.  Against the oracle <= 1e-10
+// Envelope: T >= 2 windows, Mpad <= 1024; everything else (and ISAC_CDL_TIME_DOMAIN=1) stays on the time-domain kernels.  Against the oracle <= 1e-10
 // (tests/test_gpu_cdl_config5.py), against the time-domain kernels <= 1e-12.
 #include <algorithm>
 #include <cstring>
@@ -430,13 +430,13 @@ __global__ __launch_bounds__(FFT::NT, MINW) void cdl_os_ul_kernel(const OsPair* 
 using namespace isac;
 
 bool cdl_os_ok(long long T, int Nt, int Nr, int n_paths, int n_taps, int max_shift) {
-  static const bool off = std::getenv("ISAC_CDL_TIME_DOMAIN") != nullptr;       // development switch: the time-domain kernels for every shape
+  static const bool off = std::getenv("ISAC_CDL_TIME_DOMAIN") != nullptr;       // test hook: the time-domain kernels for every shape
   const int Mpad = (max_shift + n_taps - 1 + 7) / 8 * 8;
   return !off && Nr == 2 && (Nt == 8 || Nt == 16 || Nt == 32 || Nt == 64) && n_paths >= 1 && n_paths <= 64 && Mpad <= kOsN / 4 && T >= 2 * (kOsN - Mpad);
 }
 
 bool cdl_os_ul_ok(long long T, int Nt, int Nr, int n_paths, int n_taps, int max_shift) {
-  static const bool off = std::getenv("ISAC_CDL_TIME_DOMAIN") != nullptr || std::getenv("ISAC_CDL_UL_TIME_DOMAIN") != nullptr;   // development switches
+  static const bool off = std::getenv("ISAC_CDL_TIME_DOMAIN") != nullptr;       // test hook (as above)
   const int Mpad = (max_shift + n_taps - 1 + 7) / 8 * 8;
   return !off && (Nt == 1 || Nt == 2) && Nr > Nt && Nr <= 65535 && n_paths >= 1 && n_paths <= 64 && Mpad <= kOsN / 4 && T >= 2 * (kOsN - Mpad);
 }
@@ -450,9 +450,8 @@ int cdl_os_apply(isac_ctx* ctx, const isac_cdl_job* jobs, int n_jobs, long long 
   if (ctx->cdl_share_spectra && Nr <= Nt && Mpad <= 512) Mpad = 512;
   const int S = kOsN - Mpad;
   const int n_seg = (int)((T + S - 1) / S);
-  static const bool no_mfma = std::getenv("ISAC_CDL_OS_VALU") != nullptr;       // development switch: the first (all-VALU) mix kernel for every shape
   const bool ul = Nr > Nt;                                                      // uplink form: cdl_os_ul_kernel, no mix launch, no Y spectra
-  const bool mfma_mix = !ul && Nt == 64 && !no_mfma;
+  const bool mfma_mix = !ul && Nt == 64;
   const size_t per_chunk = mfma_mix ? kOsMPairs : kOsPairs;
   // ---- distinct waveforms, (job, gain block) pairs, chunks of up to eight pairs on one waveform, (pair, window) tasks
   std::vector<const c64*> waves;

@@ -312,7 +312,7 @@ extern "C" int isac_precoded_sinr_cqi_dev(isac_ctx* ctx, const isac_c64* d_H, in
     ISAC_HIP(hipMemcpyAsync(ctx->pinned_csi, d_mean, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     ISAC_HIP(hipStreamSynchronize(ctx->stream));
     const double m = *(const double*)ctx->pinned_csi;
-    static const bool dbg_mean = std::getenv("ISAC_DEBUG_MEAN") != nullptr;     // development switch: re-read the per-RE values, recompute the mean on the host, report a disagreement
+    static const bool dbg_mean = std::getenv("ISAC_DEBUG_MEAN") != nullptr;     // diagnostic: re-read the per-RE values, recompute the mean on the host, report a disagreement
     if (dbg_mean) {
       std::vector<double> hv((size_t)n_re);
       ISAC_TRY(copy_d2h(ctx, hv.data(), out, sizeof(double) * (size_t)n_re));

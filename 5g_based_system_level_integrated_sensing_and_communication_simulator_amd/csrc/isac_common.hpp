@@ -195,7 +195,7 @@ inline int allow_lds(isac_ctx* ctx, const void* kernel, size_t bytes) {
 
 hipEvent_t timeline_base(hipStream_t st);   // capi.hip
 inline void timeline_mark(isac_ctx* ctx, int i, hipStream_t st) {
-  static const bool on = std::getenv("ISAC_TIMELINE") != nullptr;
+  static const bool on = std::getenv("ISAC_TIMELINE") != nullptr;   // diagnostic: per-stage event timeline
   if (!on) return;
   if (!ctx->tl_on) {
     for (auto& e : ctx->tl) (void)hipEventCreate(&e);

@@ -65,7 +65,7 @@ __device__ __forceinline__ double wave_sum_dpp(double x) {
 // Three real MFMAs per tile and k-step instead of four (3M / Gauss form, see cov_group_body): 30 instead of 40 per four samples
 // at A = 64.  Measured at A = 64 (733 824 samples): 4M, interleaved sample map, 3 workgroups per CU 276 us / 1.37 GB fetched;
 // 3M + line map, 2 workgroups per CU 209 us / 1.05 GB; + a workgroup barrier every 8 slabs 215 us / 0.73 GB (= the input, once).
-constexpr int kCovSyncSlabs = 8;                                // power of two (1, 2, 4: +3-9 %; 16 .. none: within the noise of 8 -- ISAC_COV_WGTIMES spans)
+constexpr int kCovSyncSlabs = 8;                                // power of two (1, 2, 4: +3-9 %; 16 .. none: within the noise of 8 in per-workgroup spans)
 template <int NB>
 struct CovPlan {
   static constexpr int kTiles = NB * (NB + 1) / 2;
@@ -224,10 +224,8 @@ __device__ __forceinline__ void cov_group_body(const c64* __restrict__ G, long l
 template <int NB, int NBUF = 3>
 __global__ __launch_bounds__(256, 2) void cov_mfma_small_kernel(const c64* __restrict__ G, long long N, int A,
                                                                 long long slabs_per_wg,
-                                                                double* __restrict__ part /* [gridX*kPhases][kTiles][2][256] */,
-                                                                long long* __restrict__ dbg /* dev: (start, end, xcc) per workgroup, or null */) {
+                                                                double* __restrict__ part /* [gridX*kPhases][kTiles][2][256] */) {
   using P = CovPlan<NB>;
-  const long long dbg_t0 = dbg ? (long long)wall_clock64() : 0;
   const int lane = threadIdx.x & 63;
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int grp = wid / P::kPhases, phase = wid % P::kPhases;
@@ -239,14 +237,6 @@ __global__ __launch_bounds__(256, 2) void cov_mfma_small_kernel(const c64* __res
   if (grp == 0) cov_group_body<NB, 0, NBUF>(G, N, A, P::kTiles, phase, lane, s_begin, 1, s_end - s_begin, s_end, pidx, part);
   if constexpr (P::kGroups > 1) {
     if (grp == 1) cov_group_body<NB, 1, NBUF>(G, N, A, P::kTiles, phase, lane, s_begin, 1, s_end - s_begin, s_end, pidx, part);
-  }
-  if (dbg) {
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      unsigned xcc = 0;
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-      dbg[3 * blockIdx.x] = dbg_t0; dbg[3 * blockIdx.x + 1] = (long long)wall_clock64(); dbg[3 * blockIdx.x + 2] = xcc & 15;
-    }
   }
 }
 
@@ -809,7 +799,7 @@ __global__ __launch_bounds__(256, 2) void cov_mfma_lds_kernel(const c64* __restr
 //   * thread (p = tid & 7, r0 = tid >> 3) makes TWO Philox calls per slab -- antennas r0 and r0 + 32 -- i.e. four elements, and two 16-byte loads of D (from L2: the lanes of a
 //     wave share 8 subcarriers) per target, issued two slabs ahead;
 //   * the generator is cut into 19 pieces (counter set-up + 10 Philox rounds, 4 Box-Muller transforms, 4 x (synthesis + mask + LDS store), the D loads) that sit in the gaps of the
-//     step's 30 MFMAs like the staging instructions did (SCHED picks the placement).
+//     step's 30 MFMAs like the staging instructions did, spread evenly (lazy_piece_gap).
 // Bound: fp64 MFMA issue + the generator's VALU (v_mfma_f64 and VALU of one wave overlap only inside the 64-cycle shadow of the wave's own MFMA, section 3d of DESIGN_HISTORY.md).
 struct LazyCovArgs {
   const c64* D;               // [K x L_whole x QT] per-target demodulated coefficient grids
@@ -820,12 +810,11 @@ struct LazyCovArgs {
   int s_col;                  // slabs per symbol column
 };
 constexpr int kLazyPieces = 19;
-template <int SCHED>
 __host__ __device__ constexpr int lazy_piece_gap(int i) {       // MFMA gap (0..29) that carries generator piece i
-  return SCHED == 0 ? i : SCHED == 1 ? 8 + i : (i * 30) / kLazyPieces;
+  return (i * 30) / kLazyPieces;
 }
 
-template <int GRP, int QT, int SCHED>
+template <int GRP, int QT>
 __device__ __forceinline__ void cov_lazy_body(const LazyCovArgs& a, int phase, long long s_begin, long long s_end, int part_index, double* __restrict__ part,
                                               c64* __restrict__ lds) {
   constexpr int NB = 4;
@@ -944,7 +933,7 @@ __device__ __forceinline__ void cov_lazy_body(const LazyCovArgs& a, int phase, l
         nxt[b][e] = img[b * kBlk + r_off[e]];        // (blocks no tile of this group touches: dead reads, dropped by the compiler)
       }
       static_for<0, kLazyPieces>([&](auto ic) {
-        if constexpr (lazy_piece_gap<SCHED>(decltype(ic)::value) == k) piece(ic);
+        if constexpr (lazy_piece_gap(decltype(ic)::value) == k) piece(ic);
       });
       __builtin_amdgcn_sched_barrier(0);
     };
@@ -1037,7 +1026,7 @@ __device__ __forceinline__ void cov_lazy_body(const LazyCovArgs& a, int phase, l
   }
 }
 
-template <int QT, int SCHED>
+template <int QT>
 __global__ __launch_bounds__(256, 2) void cov_lazy_kernel(LazyCovArgs a, long long n_slabs, long long slabs_per_wg, double* __restrict__ part /* [gridX][kTiles][2][256] */) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   c64* lds = reinterpret_cast<c64*>(smem_raw);      // [kCovLdsBufs][4 * 16 * kCovPitch]
@@ -1046,8 +1035,8 @@ __global__ __launch_bounds__(256, 2) void cov_lazy_kernel(LazyCovArgs a, long lo
   const long long s_begin = (long long)blockIdx.x * slabs_per_wg;
   long long s_end = s_begin + slabs_per_wg;
   if (s_end > n_slabs) s_end = n_slabs;
-  if (grp == 0) cov_lazy_body<0, QT, SCHED>(a, phase, s_begin, s_end, blockIdx.x, part, lds);
-  else cov_lazy_body<1, QT, SCHED>(a, phase, s_begin, s_end, blockIdx.x, part, lds);
+  if (grp == 0) cov_lazy_body<0, QT>(a, phase, s_begin, s_end, blockIdx.x, part, lds);
+  else cov_lazy_body<1, QT>(a, phase, s_begin, s_end, blockIdx.x, part, lds);
 }
 
 __global__ __launch_bounds__(256, 2) void cov_mfma_block_kernel(const c64* __restrict__ G, long long N, int A, int n_blk,
@@ -1200,7 +1189,7 @@ __device__ __forceinline__ double eigh_safe_scale(const c64* __restrict__ Hin, i
 
 // ---------------------------------------------------------------- Hermitian eigensolver: one-workgroup cyclic Jacobi in LDS
 // Round-robin (tournament) ordering: A/2 disjoint rotations per round, A-1 rounds per sweep.
-constexpr int kJacobiMaxA = 64;
+constexpr int kJacobiMaxA = 16;    // isac_eigh_dev: Jacobi up to this order, the tridiagonal pipeline beyond (the kernel's LDS carve holds up to 64)
 
 __device__ __forceinline__ void rr_pair(int round, int k, int n /* even */, int& p, int& q) {
   // circle method: position 0 fixed, others rotate
@@ -1339,7 +1328,8 @@ __global__ __launch_bounds__(1024) void jacobi_eigh_kernel(const c64* __restrict
 // ---------------------------------------------------------------- Hermitian eigensolver II: Householder tridiagonalisation + implicit QL
 // eig(Ra) of music.m:19 the LAPACK way (zhetd2 -> zungtr -> tql2), two launches on one stream, state in an L2-resident
 // global scratch (working matrix in LDS while n <= 64):
-//   K1  eigh_tridiag_kernel   one workgroup: n-1 Householder reflectors reduce H to a REAL symmetric tridiagonal (d, e)
+//   K1  n-1 Householder reflectors reduce H to a REAL symmetric tridiagonal (d, e): eigh_tridiag_small_kernel (n <= 64),
+//       eigh_tridiag_dist_kernel (n <= kTdMaxN) or eigh_tridiag_fused_kernel, see launch_tridiag
 //   K2  eigh_formq_ql_kernel  independent workgroups side by side:
 //         block 0: Q = H_0 ... H_{n-2} formed explicitly in Z (zungtr)
 //         block 1: one wavefront runs the strictly sequential implicit-shift QL recurrence on (d, e) ALONE -- one
@@ -1381,144 +1371,13 @@ struct EighScratch {   // carve of ctx->eig_scratch for order n
   }
 };
 
-// MLDS: the working matrix lives in LDS (n <= 64: 64 KB) instead of the L2-resident scratch -- every step is a handful of
-// dependent round trips to it (column norm, matrix-vector product, rank-2 update), 100 instead of 700 cycles each.
-template <bool MLDS>
-__global__ __launch_bounds__(1024) void eigh_tridiag_kernel(const c64* __restrict__ Hin, int n, void* scratch, int* __restrict__ info) {
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  EighScratch S(scratch, n);
-  // [n x n] column-major working matrix (reflectors end up below the subdiagonal)
-  c64* M = MLDS ? reinterpret_cast<c64*>(smem_raw) + 6 * n + 16 : S.M;  // (LDS copy placed after the vectors and the 32-double reduction scratch)
-  c64* sv = reinterpret_cast<c64*>(smem_raw);       // [n] current reflector
-  c64* sp = sv + n;                                 // [n] p / w vector
-  c64* spart = sp + n;                              // [4][n] partial matrix-vector products
-  double* sred = reinterpret_cast<double*>(spart + 4 * n);   // [2 x 16] block-reduction scratch
-  const int tid = threadIdx.x, nt = blockDim.x, lane = tid & 63, wid = tid >> 6, nw = nt >> 6;
-
-  auto block_sum2 = [&](double a, double b, double& oa, double& ob) {   // sum over the workgroup of two values
-    for (int o = 32; o > 0; o >>= 1) { a += __shfl_down(a, o); b += __shfl_down(b, o); }
-    __syncthreads();
-    if (lane == 0) { sred[wid] = a; sred[16 + wid] = b; }
-    __syncthreads();
-    double ta = 0.0, tb = 0.0;
-    for (int w = 0; w < nw; ++w) { ta += sred[w]; tb += sred[16 + w]; }
-    oa = ta; ob = tb;
-  };
-
-  constexpr int RWU = MLDS ? 64 : 256;              // row tile of the rank-2 update
-  const long long t_start = clock64();
-  const double scl = eigh_safe_scale(Hin, n * n, sred);
-  for (int i = tid; i < n * n; i += nt) M[i] = Hin[i] * scl;
-  if (tid == 0) *S.scale = scl;
-  if (tid < 8) S.cnt[tid] = 0;                      // publication counters of the next two stages
-  __syncthreads();
-  for (int k = 0; k < n - 1; ++k) {                 // zhetd2, lower
-    const int m = n - k - 1;                        // trailing size, rows/cols k+1 .. n-1
-    double xn2 = 0.0, dummy = 0.0;
-    for (int i = k + 2 + tid; i < n; i += nt) { const c64 x = M[i + n * k]; xn2 += x.re * x.re + x.im * x.im; }
-    double xnorm2, unused;
-    block_sum2(xn2, dummy, xnorm2, unused);
-    const c64 alpha = M[k + 1 + n * k];
-    c64 tau = mk(0.0, 0.0), scale = mk(0.0, 0.0);
-    double beta = alpha.re;
-    if (xnorm2 != 0.0 || alpha.im != 0.0) {         // zlarfg
-      beta = -copysign(sqrt(alpha.re * alpha.re + alpha.im * alpha.im + xnorm2), alpha.re);
-      tau = mk((beta - alpha.re) / beta, -alpha.im / beta);
-      const c64 dlt = mk(alpha.re - beta, alpha.im);
-      const double dn = dlt.re * dlt.re + dlt.im * dlt.im;
-      scale = mk(dlt.re / dn, -dlt.im / dn);        // 1 / (alpha - beta)
-    }
-    for (int i = k + 1 + tid; i < n; i += nt) {
-      const c64 vi = (i == k + 1) ? mk(1.0, 0.0) : M[i + n * k] * scale;
-      sv[i] = vi;
-      if (i > k + 1) M[i + n * k] = vi;             // keep the reflector for zungtr
-    }
-    if (tid == 0) { S.d[k] = M[k + n * k].re; S.e[k] = beta; S.tau[k] = tau; }
-    __syncthreads();
-    if (tau.re != 0.0 || tau.im != 0.0) {
-      // p = tau * A22 * v: thread (row i, column quarter jq); rows are coalesced across lanes, the four quarters of a
-      // row are summed through LDS.  (One thread per row left 3/4 of the workgroup idle and walked the m columns as one
-      // dependent chain of L2 round trips.)
-      {
-        // row tile RW (64 rows when the matrix is that small, else 256), G = blockDim / RW column groups
-        const int rw_shift = MLDS ? 6 : 8, RW = 1 << rw_shift;
-        const int rows_pt = (m + RW - 1) >> rw_shift;
-        const int G = nt >> rw_shift;
-        const int jq = tid >> rw_shift, il = tid & (RW - 1);
-        const int jlen = (m + G - 1) / G;
-        const int j0 = k + 1 + jq * jlen, j1 = min(n, j0 + jlen);
-        for (int rr = 0; rr < rows_pt; ++rr) {
-          const int i = k + 1 + il + RW * rr;
-          c64 a0 = mk(0.0, 0.0), a1 = a0, a2 = a0, a3 = a0;
-          if (i < n) {
-            int j = j0;
-            for (; j + 8 <= j1; j += 8) {                    // eight independent loads in flight
-              c64 m[8];
-#pragma unroll
-              for (int u = 0; u < 8; ++u) m[u] = M[i + n * (j + u)];
-              a0 = fma(m[0], sv[j], a0); a1 = fma(m[1], sv[j + 1], a1); a2 = fma(m[2], sv[j + 2], a2); a3 = fma(m[3], sv[j + 3], a3);
-              a0 = fma(m[4], sv[j + 4], a0); a1 = fma(m[5], sv[j + 5], a1); a2 = fma(m[6], sv[j + 6], a2); a3 = fma(m[7], sv[j + 7], a3);
-            }
-            for (; j + 4 <= j1; j += 4) {
-              const c64 m0 = M[i + n * j], m1 = M[i + n * (j + 1)], m2 = M[i + n * (j + 2)], m3 = M[i + n * (j + 3)];
-              a0 = fma(m0, sv[j], a0); a1 = fma(m1, sv[j + 1], a1); a2 = fma(m2, sv[j + 2], a2); a3 = fma(m3, sv[j + 3], a3);
-            }
-            for (; j < j1; ++j) a0 = fma(M[i + n * j], sv[j], a0);
-            spart[jq * n + i] = (a0 + a1) + (a2 + a3);
-          }
-        }
-        __syncthreads();
-        for (int i = k + 1 + tid; i < n; i += nt) {
-          c64 acc = spart[i];
-          for (int gq = 1; gq < G; ++gq) acc = acc + spart[gq * n + i];
-          sp[i] = tau * acc;
-        }
-      }
-      __syncthreads();
-      // alpha2 = -1/2 tau (p^H v);  w = p + alpha2 v
-      double pr = 0.0, pi = 0.0;
-      for (int i = k + 1 + tid; i < n; i += nt) { const c64 t = mul_conj(sv[i], sp[i]); pr += t.re; pi += t.im; }
-      double sr, si;
-      block_sum2(pr, pi, sr, si);
-      const c64 a2 = mk(-0.5, 0.0) * (tau * mk(sr, si));
-      __syncthreads();
-      for (int i = k + 1 + tid; i < n; i += nt) sp[i] = sp[i] + a2 * sv[i];
-      __syncthreads();
-      // A22 -= v w^H + w v^H   (thread = row slot x column phase: rows coalesced, no per-element division).  Four columns per trip with
-      // their loads issued together: the one-element loop waited an L2 round trip per element (the stores to M keep the compiler from
-      // overlapping trips by itself) -- with the matrix in L2 (n > 64) that latency was most of the kernel.
-      for (int i = k + 1 + (tid & (RWU - 1)); i < n; i += RWU) {
-        const c64 vi = sv[i], wi = sp[i];
-        const int js = nt / RWU;
-        int j = k + 1 + tid / RWU;
-        for (; j + 3 * js < n; j += 4 * js) {
-          c64 m[4];
-#pragma unroll
-          for (int u = 0; u < 4; ++u) m[u] = M[i + n * (j + u * js)];
-#pragma unroll
-          for (int u = 0; u < 4; ++u) M[i + n * (j + u * js)] = m[u] - mul_conj(vi, sp[j + u * js]) - mul_conj(wi, sv[j + u * js]);
-        }
-        for (; j < n; j += js) M[i + n * j] = M[i + n * j] - mul_conj(vi, sp[j]) - mul_conj(wi, sv[j]);
-      }
-    }
-    __syncthreads();
-  }
-  if (MLDS) {                                       // the reflectors go where zungtr expects them
-    for (int i = tid; i < n * n; i += nt) S.M[i] = M[i];
-  }
-  if (tid == 0) {
-    S.d[n - 1] = M[n - 1 + n * (n - 1)].re; S.e[n - 1] = 0.0;
-    if (info) { info[1] = (int)((clock64() - t_start) >> 6); info[6] = 0; }
-  }
-}
-
 // ---- n > 64, one pass over the trailing matrix per reflector instead of two.  zhetd2 reads A22 for p = tau A22 v and then reads AND writes it for
 // A22 -= v w' + w v'; the matrix (1 MB at n = 256) streams from L2 through one CU, and that traffic is half of the kernel.  Here the rank-2
 // update of step k - 1 is carried as a PENDING pair (v, w) and applied while the matrix-vector product of step k walks the matrix:
 //   (a) column k gets the pending update by itself (O(n)) -> d[k], the new reflector v', tau';
 //   (b) one pass over rows / columns > k:  a' = a - v_i conj(w_j) - w_i conj(v_j);  store a';  acc_i += a' v'_j   (one read + one write per element);
 //   (c) w' = tau' acc + alpha v'  becomes the pending pair of step k + 1.
-// Element for element the arithmetic is that of eigh_tridiag_kernel (same update expression, same partial-sum order of the product): d, e,
+// Element for element the arithmetic is that of the two-pass form (same update expression, same partial-sum order of the product): d, e,
 // tau and the reflectors come out bit-identical.
 __global__ __launch_bounds__(1024) void eigh_tridiag_fused_kernel(const c64* __restrict__ Hin, int n, void* scratch, int* __restrict__ info) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -2805,8 +2664,7 @@ static int launch_cov_small(isac_ctx* ctx, hipStream_t st, const c64* G, long lo
   long long gx = NB == 4 ? 512 : 768;       // NB = 4: 2 workgroups per CU (register-limited occupancy)
   if (gx > total) gx = total;
   long long per = (total + gx - 1) / gx;
-  static const bool reg_operands = std::getenv("ISAC_COV_REG_OPERANDS") != nullptr;   // development switch: the register-operand kernel for every A <= 64
-  const bool staged = (NB >= 3) && !reg_operands && N * 256 < (1ll << 31);           // two tile groups: fetch each slab once per workgroup, through LDS
+  const bool staged = (NB >= 3) && N * 256 < (1ll << 31);           // two tile groups: fetch each slab once per workgroup, through LDS
   if (staged) { gx = 512 < total ? 512 : total; per = (total + gx - 1) / gx; per = (per + 1) & ~1ll; }   // (the staged kernel walks slabs in pairs)
   gx = (total + per - 1) / per;
   const int n_part = (int)gx * (staged ? 1 : P::kPhases);       // (the staged kernel sums its two sample phases itself)
@@ -2822,33 +2680,10 @@ static int launch_cov_small(isac_ctx* ctx, hipStream_t st, const c64* G, long lo
     }
   }
   if (!staged) {
-  static const bool wg_times = std::getenv("ISAC_COV_WGTIMES") != nullptr;       // dev probe: per-workgroup wall-clock spans, printed per launch
-  static long long* d_dbg = nullptr;
-  if (wg_times && !d_dbg) ISAC_HIP(hipMalloc(&d_dbg, sizeof(long long) * 3 * 4096));
-  ISAC_PROF_COV0(st);
-  hipLaunchKernelGGL((cov_mfma_small_kernel<NB>), dim3((unsigned)gx), dim3(256), 0, st, G, N, A, per, (double*)ctx->cov_part.p, wg_times ? d_dbg : nullptr);
-  ISAC_HIP(hipGetLastError());
-  ISAC_PROF_COV1(st);
-  if (wg_times) {
-    std::vector<long long> h((size_t)3 * gx);
-    ISAC_HIP(hipStreamSynchronize(st));
-    ISAC_HIP(hipMemcpy(h.data(), d_dbg, sizeof(long long) * h.size(), hipMemcpyDeviceToHost));
-    long long t0 = h[0], t1 = h[1];
-    for (long long b = 0; b < gx; ++b) { t0 = std::min(t0, h[3 * b]); t1 = std::max(t1, h[3 * b + 1]); }
-    double sum[16] = {0}, mx[16] = {0}, mn[16]; int cnt[16] = {0};
-    for (int x = 0; x < 16; ++x) mn[x] = 1e30;
-    double end_sum = 0, start_max = 0;
-    for (long long b = 0; b < gx; ++b) {
-      const int x = (int)h[3 * b + 2];
-      const double d = 0.01 * (double)(h[3 * b + 1] - h[3 * b]);       // 100 MHz ticks -> us
-      sum[x] += d; mx[x] = std::max(mx[x], d); mn[x] = std::min(mn[x], d); ++cnt[x];
-      end_sum += 0.01 * (double)(h[3 * b + 1] - t0);
-      start_max = std::max(start_max, 0.01 * (double)(h[3 * b] - t0));
-    }
-    std::fprintf(stderr, "COVWG span %.1f us, last start +%.1f us, mean end +%.1f us |", 0.01 * (double)(t1 - t0), start_max, end_sum / (double)gx);
-    for (int x = 0; x < 16; ++x) if (cnt[x]) std::fprintf(stderr, " xcc%d n=%d %.0f/%.0f/%.0f", x, cnt[x], mn[x], sum[x] / cnt[x], mx[x]);
-    std::fprintf(stderr, "\n");
-  }
+    ISAC_PROF_COV0(st);
+    hipLaunchKernelGGL((cov_mfma_small_kernel<NB>), dim3((unsigned)gx), dim3(256), 0, st, G, N, A, per, (double*)ctx->cov_part.p);
+    ISAC_HIP(hipGetLastError());
+    ISAC_PROF_COV1(st);
   }
   const int S = 32;
   double* part2 = (double*)ctx->cov_part.p + (size_t)n_part * P::kTiles * 2 * 256;
@@ -2864,17 +2699,10 @@ static int launch_cov_small(isac_ctx* ctx, hipStream_t st, const c64* G, long lo
 // Ra of the context's NATIVE lazy echo grid (ctx->lazy: isac_mono_static_sensing_fused_dev with d_echo_grid == NULL) -- fft2D.m:106-107 without the array.
 template <int QT>
 static int launch_cov_lazy(isac_ctx* ctx, hipStream_t st, const LazyCovArgs& a, long long n_slabs, long long per, long long gx, double* part) {
-  static const int sched = std::getenv("ISAC_COV_LAZY_SCHED") ? std::atoi(std::getenv("ISAC_COV_LAZY_SCHED")) : 2;   // development switch: placement of the generator pieces
   const size_t lds = sizeof(c64) * kCovLdsBufs * 4 * 16 * kCovPitch;
-#define ISAC_LAZY(S)                                                                                                       \
-  do {                                                                                                                     \
-    auto kern = cov_lazy_kernel<QT, S>;                                                                                    \
-    ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(kern), lds));                                                    \
-    hipLaunchKernelGGL(kern, dim3((unsigned)gx), dim3(256), lds, st, a, n_slabs, per, part);                               \
-  } while (0)
+  ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(cov_lazy_kernel<QT>), lds));
   ISAC_PROF_COV0(st);
-  if (sched == 0) ISAC_LAZY(0); else if (sched == 1) ISAC_LAZY(1); else ISAC_LAZY(2);
-#undef ISAC_LAZY
+  hipLaunchKernelGGL((cov_lazy_kernel<QT>), dim3((unsigned)gx), dim3(256), lds, st, a, n_slabs, per, part);
   ISAC_HIP(hipGetLastError());
   ISAC_PROF_COV1(st);
   return ISAC_OK;
@@ -2932,9 +2760,8 @@ int isac_covariance_on(isac_ctx* ctx, hipStream_t st, const isac_c64* d_grid, in
     per = (per + 1) & ~1ll;                           // the kernel walks slabs in pairs
     n_chunks = (total + per - 1) / per;
     ISAC_TRY(ensure(ctx, ctx->cov_part, sizeof(double) * (size_t)n_chunks * n_pairs * 16 * 2 * 256));
-    static const bool burst_form = std::getenv("ISAC_COV_BLOCK_BURST") != nullptr;    // development switch: cov_mfma_block_kernel for every N
     ISAC_PROF_COV0(st);
-    if (!burst_form && N * 512 < (1ll << 31)) {       // (32 antennas per staging descriptor: 32-bit offsets up to N x 31 x 16 B)
+    if (N * 512 < (1ll << 31)) {       // (32 antennas per staging descriptor: 32-bit offsets up to N x 31 x 16 B)
       const size_t lds = sizeof(c64) * kCovUImgs * kCovUImg;
       ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(cov_mfma_block_pl_kernel), (size_t)(lds)));
       hipLaunchKernelGGL(cov_mfma_block_pl_kernel, dim3((unsigned)(n_chunks * n_pairs)), dim3(256), lds, st, (const c64*)d_grid, (long long)N, A,
@@ -2968,17 +2795,15 @@ static int launch_tridiag(isac_ctx* ctx, const c64* d_H, int n, hipStream_t st, 
       ISAC_HIP(hipMemsetAsync(ctx->eig_scratch.p, 0, ctx->eig_scratch.cap, st));
   }
   void* gs = ctx->eig_scratch.p;
-  const size_t lds1 = sizeof(c64) * 6 * (size_t)n + sizeof(double) * 32 + 64;
   if (n <= 64) {       // four waves, two barriers per step, matrix in LDS (the general kernel with its matrix in LDS: 222 us at n = 64; this one ~120)
     const size_t ldss = sizeof(c64) * ((size_t)n * n + kTriWaves * 64 + kTriWaves * 2 * 64) + sizeof(double) * 32 + 64;
     ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(eigh_tridiag_small_kernel), (size_t)(112 * 1024)));
     hipLaunchKernelGGL(eigh_tridiag_small_kernel, dim3(1), dim3(64 * kTriWaves), ldss, st, d_H, n, gs, info);
   } else {
-    static const bool unfused = std::getenv("ISAC_EIG_TRIDIAG_UNFUSED") != nullptr;   // development switch: the two-pass zhetd2 kernel
-    static const char* td_env = std::getenv("ISAC_EIG_TRIDIAG_DIST");   // development switch: "0" the one-workgroup kernels for every n; "far" write-through exchange at stride 8; "s1" stride 1
+    static const char* td_env = std::getenv("ISAC_EIG_TRIDIAG_DIST");   // test hook: "0" the one-workgroup kernels for every n; "far" write-through exchange at stride 8; "s1" stride 1
     const bool td_off = td_env && td_env[0] == '0';
     const int td_stride = td_env && td_env[0] == 's' ? std::max(1, std::atoi(td_env + 1)) : 8, td_far = td_env && td_env[0] == 'f';
-    const bool dist = n <= kTdMaxN && !unfused && !td_off;
+    const bool dist = n <= kTdMaxN && !td_off;
     if (dist) {
       if (((++ctx->eig_epoch) & 0xFFFFF) == 0) {                                      // the 20-bit epoch of the tags wraps: start over from a clean area
         ++ctx->eig_epoch;
@@ -2990,8 +2815,7 @@ static int launch_tridiag(isac_ctx* ctx, const c64* d_H, int n, hipStream_t st, 
       ISAC_HIP(hipMemsetAsync(info + 6, 0, sizeof(int), st));                        // the sticky time-out word (the one-workgroup kernels clear it themselves)
       hipLaunchKernelGGL(eigh_tridiag_dist_kernel, dim3((unsigned)(((n + 15) / 16) * td_stride)), dim3(256), 0, st, d_H, n, gs, info,
                          (unsigned)((ctx->eig_epoch & 0xFFFFF) << 12), td_stride, (int)(td_launches.fetch_add(1) % (unsigned)td_stride), td_far, force_to ? 1 : 0);
-    } else if (unfused) hipLaunchKernelGGL(eigh_tridiag_kernel<false>, dim3(1), dim3(1024), lds1, st, d_H, n, gs, info);
-    else {
+    } else {
       const size_t ldsf = sizeof(c64) * 7 * (size_t)n + sizeof(double) * 32 + 64;
       ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(eigh_tridiag_fused_kernel), ldsf));
       hipLaunchKernelGGL(eigh_tridiag_fused_kernel, dim3(1), dim3(1024), ldsf, st, d_H, n, gs, info);
@@ -3029,11 +2853,10 @@ static int launch_ql(isac_ctx* ctx, int n, hipStream_t st, int* info, const int*
   const size_t rows3 = (size_t)bt * n * sizeof(double), stage3 = sizeof(c64) * 2 * (size_t)n;
   const size_t lds3 = rows3 + stage3;
   const bool lds_replay = rows3 <= 150 * 1024 && n <= 8 * bt;
-  static const bool no_overlap = std::getenv("ISAC_EIG_NO_OVERLAP") != nullptr;   // development switch
   // Replay blocks ride along with zungtr and the recurrence (they spin on flags of the same launch: co-resident workgroups are a speed
   // assumption, a bounded spin turns a violation into an error) -- except when this is the in-stream fallback of the subspace route
   // (ctl != null): there the replay is its own launch behind the recurrence, so the rare large-numDets CPI cannot fail on a spin time-out
-  const bool live = lds_replay && !no_overlap && ctl == nullptr && allow_live;
+  const bool live = lds_replay && ctl == nullptr && allow_live;
   const int n_replay = (2 * n + bt - 1) / bt;
   ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(eigh_formq_ql_kernel), (size_t)(160 * 1024)));
   // (as the in-stream fallback it almost always returns at its first instruction: 256 threads then -- a 1024-thread workgroup of ~110 VGPRs needs a
@@ -3058,8 +2881,7 @@ int isac_eigh_replay_recover(isac_ctx* ctx, int n, hipStream_t st) {
 // ---- MUSIC's signal-subspace route (eigensolver III above): supported orders, and the two halves around the wait for numDets
 static int* music_ctl(isac_ctx* ctx) { return reinterpret_cast<int*>((char*)ctx->misc.p + 256); }   // (ctx->misc: >= 512 bytes here)
 bool isac_music_subspace_ok(isac_ctx* ctx, int A) {
-  static const bool env_full = std::getenv("ISAC_MUSIC_FULL_EIG") != nullptr;      // development switch: always the full eigendecomposition
-  return !env_full && ctx->music_route == 0 && A >= 3 && A <= 256;
+  return ctx->music_route == 0 && A >= 3 && A <= 256;
 }
 // first half: reflectors + all eigenvalues (ascending, ctx->eig_w); independent of numDets
 int isac_music_tridiag_bisect_dev(isac_ctx* ctx, const c64* d_H, int A, hipStream_t st) {
@@ -3109,16 +2931,10 @@ int isac_eigh_dev(isac_ctx* ctx, const c64* d_H, int A, hipStream_t st, bool liv
   if (A > 1024) return fail(ctx, ISAC_ERR_UNSUPPORTED, "device eigensolver supports up to 1024 antennas");
   // measured host-call times (tools/_eig_sizes.py): Jacobi 0.10 / 0.16 / 0.26 / 0.35 / 0.78 / 1.41 ms at A = 8 / 16 / 24 / 32 / 48 /
   // 64, the tridiagonal pipeline 0.10 / 0.17 / 0.24 / 0.33 / 0.57 / 0.86 ms: Jacobi up to 16 antennas, the pipeline beyond
-  // ISAC_EIG_JACOBI_MAX=64 selects the throughput trade-off instead: the pipeline occupies up to five CUs (1024-thread zungtr
-  // block, recurrence, spinning replay blocks), Jacobi one -- with several CPIs in flight per GPU its 1.4 ms are hidden and
-  // the sensing rate is ~3-5 % higher (bench.py sets it when --inflight > 1)
-  static const int jacobi_max = std::getenv("ISAC_EIG_JACOBI_MAX") ? std::min(kJacobiMaxA, std::atoi(std::getenv("ISAC_EIG_JACOBI_MAX"))) : 16;
-  const bool big = A > jacobi_max;
   ISAC_TRY(ensure(ctx, ctx->eig_w, sizeof(double) * (size_t)A + 64));
   ISAC_TRY(ensure(ctx, ctx->eig_v, sizeof(c64) * (size_t)A * A));
   int* info = reinterpret_cast<int*>((char*)ctx->eig_w.p + sizeof(double) * (size_t)A);
-  static const bool force_ql = std::getenv("ISAC_EIG_QL") != nullptr;             // development switch: A <= 64 through the pipeline
-  if (A >= 3 && (big || force_ql)) {
+  if (A > kJacobiMaxA) {
     ISAC_TRY(launch_tridiag(ctx, d_H, A, st, info));
     return launch_ql(ctx, A, st, info, nullptr, live_replay);
   }

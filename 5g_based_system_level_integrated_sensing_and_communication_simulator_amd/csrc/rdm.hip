@@ -550,8 +550,7 @@ static int launch_range(isac_ctx* ctx, hipStream_t st, const c64* rx, const c64*
 // The panel detector (cfar_panel_kernel + cfar_merge_kernel) applies when the CUT half-window fits a 48-row panel and the bookkeeping fits
 // the LDS carves; anything else -- or ISAC_OPT_TAIL_FUSION = 0 -- takes memset + cfar_window_kernel + count.
 static bool tail_fusable(isac_ctx* ctx, const isac_est_params* ep, const isac_cfar_config* cf, TailGeom* out) {
-  static const bool off = std::getenv("ISAC_TAIL_UNFUSED") != nullptr;
-  if (off || !ctx->tail_fusion) return false;
+  if (!ctx->tail_fusion) return false;
   TailGeom g{};
   g.gr = cf->guard[0]; g.gc = cf->guard[1];
   g.hr = cf->guard[0] + cf->train[0]; g.hc = cf->guard[1] + cf->train[1];
@@ -605,7 +604,7 @@ int isac_rdm_power_window(isac_ctx* ctx, const isac_est_params* ep, const isac_c
                                                             (c64*)ctx->ymid.p))));
   }
   const int Lu = L < n_fft ? L : n_fft;
-  if (n_fft == 256 && !std::getenv("ISAC_DOPPLER_DIRECT")) {
+  if (n_fft == 256) {
     size_t lds = sizeof(c64) * (256 + std::max((size_t)Lu * (kDopRows + 1), (size_t)kDopRows * 16 * 17));
     ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(doppler_fft256_kernel), lds));
     hipLaunchKernelGGL(doppler_fft256_kernel, dim3(cdiv(nr, kDopRows), A), dim3(256), lds, ctx->stream, (const c64*)ctx->ymid.p, nr, L,

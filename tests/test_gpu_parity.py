@@ -359,10 +359,10 @@ print("recovered")
 def test_eigh_live_replay_timeout_is_recovered():
     """A live replay block that gives up waiting (info[0] = -2) must not fail the call: the recorded rotations are replayed by a launch of its own.
     ISAC_EIG_FORCE_REPLAY_TIMEOUT (read once per process, hence the subprocess) destroys the eigenvectors of every QL-pipeline call and takes
-    that path; ISAC_EIG_QL sends A <= 64 through the pipeline too."""
+    that path (every order of the snippet is above the Jacobi limit of 16)."""
     import subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, ISAC_EIG_FORCE_REPLAY_TIMEOUT="1", ISAC_EIG_QL="1")
+    env = dict(os.environ, ISAC_EIG_FORCE_REPLAY_TIMEOUT="1")
     r = subprocess.run([sys.executable, "-c", _RECOVER_SNIPPET % (root, PKG_NAME)], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "recovered" in r.stdout, r.stdout + r.stderr
 

@@ -24,4 +24,4 @@ ts = np.array(ts)
 G = g.numpy().reshape(N, A, order="F")
 ref = (G.conj().T @ G) / N
 err = np.abs(ra.numpy() - ref).max() / np.abs(ref).max()
-print(f"A {A}: covariance min {ts.min():.4f} ms median {np.median(ts):.4f} ms; rel err vs NumPy {err:.2e}; {len(hs)} distinct result(s) over {args.reps} runs; env {os.environ.get('ISAC_COV_REG_OPERANDS')}")
+print(f"A {A}: covariance min {ts.min():.4f} ms median {np.median(ts):.4f} ms; rel err vs NumPy {err:.2e}; {len(hs)} distinct result(s) over {args.reps} runs")
