@@ -14,7 +14,7 @@ _LIB_PATH = os.path.join(_HERE, "libisac_hip.so")
 _lib = None
 _lock = threading.Lock()
 
-ISAC_ABI_VERSION = 7          # include/isac.h ISAC_ABI_VERSION this binding was written against (checked at load)
+ISAC_ABI_VERSION = 8          # include/isac.h ISAC_ABI_VERSION this binding was written against (checked at load)
 ISAC_MAX_EST = 4096
 NOISE_NONE, NOISE_INJECTED, NOISE_PHILOX, NOISE_PHILOX_SPECTRAL, NOISE_INJECTED_SPECTRAL = 0, 1, 2, 3, 4
 
@@ -107,7 +107,7 @@ EXPORTS = [
     "isac_mono_static_sensing", "isac_mono_static_sensing_fused_dev", "isac_echo_grid_materialize_dev", "isac_ofdm_symbol_count", "isac_ofdm_demodulate_dev", "isac_ofdm_modulate_dev", "isac_ofdm_modulate_windowed_dev", "isac_sentx_append_dev",
     "isac_ofdm_waveform_length", "isac_cfar2d_ca", "isac_fft2d_dev", "isac_fft2d", "isac_fft2d_submit_dev", "isac_fft2d_submit_cached_dev", "isac_fft2d_collect", "isac_sensing_submit_n", "isac_sensing_collect_n", "isac_fft2d_range_stage_dev", "isac_fft2d_get_detections",
     "isac_fft2d_get_power_window", "isac_fft2d_get_covariance", "isac_fft2d_get_music_spectrum",
-    "isac_rdm_plane_dev", "isac_covariance_dev", "isac_music_doa", "isac_ctx_set_option", "isac_ctx_share_streams", "isac_ctx_reserve", "isac_eigh_top", "isac_beamscan_doa", "isac_music2d_dev", "isac_eigh", "isac_cdl_apply_dev", "isac_cdl_apply_batch_dev", "isac_cdl_path_gains_dev", "isac_cdl_freq_response_dev", "isac_cdl_csi_estimate_batch_dev", "isac_prg_precode_dev", "isac_precoded_sinr_cqi_dev", "isac_type1sp_codebook", "isac_csi_report_dev", "isac_csi_report_batch_dev", "isac_pusch_codebook", "isac_srs_pmi_select_batch_dev", "isac_los_check_dev", "isac_winding_number_dev", "isac_synth_qpsk_grid_dev",
+    "isac_rdm_plane_dev", "isac_covariance_dev", "isac_music_doa", "isac_ctx_set_option", "isac_ctx_share_streams", "isac_ctx_reserve", "isac_eigh_top", "isac_beamscan_doa", "isac_get_angular_spectrum2d", "isac_find2d_peaks", "isac_music2d_dev", "isac_eigh", "isac_cdl_apply_dev", "isac_cdl_apply_batch_dev", "isac_cdl_path_gains_dev", "isac_cdl_freq_response_dev", "isac_cdl_csi_estimate_batch_dev", "isac_prg_precode_dev", "isac_precoded_sinr_cqi_dev", "isac_type1sp_codebook", "isac_csi_report_dev", "isac_csi_report_batch_dev", "isac_pusch_codebook", "isac_srs_pmi_select_batch_dev", "isac_los_check_dev", "isac_winding_number_dev", "isac_synth_qpsk_grid_dev",
 ]
 
 
@@ -262,6 +262,19 @@ class Context:
     def set_wide_order(self, on: bool):
         """ISAC_OPT_WIDE_ORDER: fft2D's covariance on the main stream, every narrow kernel on the second (see include/isac.h)."""
         self.check(self.lib.isac_ctx_set_option(self.handle, C.c_int32(2), C.c_int32(1 if on else 0)))
+
+    def set_upa_doa(self, on: bool):
+        """ISAC_OPT_UPA_DOA: DoA of a uniform planar array through the 2-D (elevation x azimuth) scan and find2DPeaks; off (default) = the
+        reference's own failure, IsacError(UNSUPPORTED) (see include/isac.h)."""
+        self.check(self.lib.isac_ctx_set_option(self.handle, C.c_int32(4), C.c_int32(1 if on else 0)))
+
+    def angular_spectrum2d(self) -> np.ndarray:
+        """The [eSteps x aSteps] dB map of this context's last UPA DoA (isac_get_angular_spectrum2d)."""
+        dims = (C.c_int32 * 2)()
+        self.check(self.lib.isac_get_angular_spectrum2d(self.handle, None, C.c_int64(0), dims))
+        out = np.zeros((dims[0], dims[1]), dtype=np.float64, order="F")
+        self.check(self.lib.isac_get_angular_spectrum2d(self.handle, out.ctypes.data_as(C.c_void_p), C.c_int64(out.size), dims))
+        return out
 
     def share_streams(self, owner: "Context | None"):
         """Enqueue on `owner`'s two streams from now on (None: back to this context's own): isac_ctx_share_streams."""

@@ -47,6 +47,13 @@ int isac_music_subspace_dev(isac_ctx* ctx, int A, const int* d_num_dets, int num
 const int* isac_music_ctl(isac_ctx* ctx);
 int isac_covariance_on(isac_ctx* ctx, hipStream_t st, const isac_c64* d_grid, int64_t N, int32_t A, isac_c64* d_Ra);
 int isac_covariance_lazy_on(isac_ctx* ctx, hipStream_t st, isac_c64* d_Ra);   // music.hip: Ra of the context's native lazy echo grid
+// UPA DoA (doa2d.hip): the 2-D scan, the column normalisation + peak candidates, the host half of find2DPeaks
+int isac_doa2d_peak_cap(int rows, int cols);
+int isac_doa2d_cand_doubles(int cap);
+int isac_doa2d_scan_dev(isac_ctx* ctx, int mode, int nV, int nH, int eS, int aS, const double* d_tab, const int* d_num_dets, int num_dets_host,
+                        const int* ctl, hipStream_t st);
+int isac_doa2d_norm_peaks_dev(isac_ctx* ctx, bool normalise, const double* d_db, int rows, int cols, double* d_cand, int cap, hipStream_t st);
+int isac_doa2d_select(isac_ctx* ctx, const double* cand, int count, int cap, int rows, int L, std::vector<int>& ele, std::vector<int>& azi);
 
 namespace {
 
@@ -92,6 +99,10 @@ double sind_deg(double x) {  // degree-domain reduction: exact at multiples of 9
   if (ax <= 45.0) return std::sin(x * k);
   const double c = std::cos((90.0 - ax) * k);
   return x < 0 ? -c : c;
+}
+
+double cosd_deg(double x) {  // cosd via sind(90 - |x|) (oracle/matlab_compat.py): even, exact zeros at +-90, cosd(p - 180) == -cosd(p) bitwise
+  return sind_deg(90.0 - std::fmod(std::fabs(x), 360.0));
 }
 
 // findpeaks(y,'NPeaks',L,'SortStr','descend'): strict maxima, first sample of plateaus, no end points,
@@ -155,6 +166,41 @@ int get_sind_table(isac_ctx* ctx, const isac_est_params* ep, const double** out,
   }
   *out = (const double*)it->second.p;
   *n_steps = n;
+  return ISAC_OK;
+}
+
+// UPA scan grid (music.m:36-53): eSteps x aSteps points, row e at elevation (e-1) eGran - eMax/2, column a at azimuth (a-1) aGran - aMax/2.
+// Device table [sind(ele) eSteps | cosd(azi) aSteps | sind(azi) aSteps], made on the host once per grid.
+int get_doa2d_tables(isac_ctx* ctx, const isac_est_params* ep, const double** out, int* e_steps, int* a_steps) {
+  const double ag = ep->azimuth_scan_granularity, am = ep->azimuth_scan_scale, eg = ep->elevation_scan_granularity, em = ep->elevation_scan_scale;
+  if (!(ag > 0.0) || !(eg > 0.0) || !std::isfinite(am) || !std::isfinite(em)) return fail(ctx, ISAC_ERR_INVALID_ARG, "UPA DoA: scan scales / granularities");
+  const double ne = std::floor((em + 1.0) / eg), na = std::floor((am + 1.0) / ag);                     // music.m:42-43
+  if (!(ne >= 1.0) || !(na >= 1.0) || ne * na > (double)(1 << 26)) return fail(ctx, ISAC_ERR_INVALID_ARG, "UPA DoA: empty or oversized scan grid");
+  const int n_e = (int)ne, n_a = (int)na;
+  const std::vector<long long> key = {std::llround(am * 1e6), std::llround(ag * 1e6), std::llround(em * 1e6), std::llround(eg * 1e6)};
+  auto it = ctx->doa2d_tab.find(key);
+  if (it == ctx->doa2d_tab.end()) {
+    std::vector<double> t((size_t)n_e + 2 * (size_t)n_a);
+    for (int e = 0; e < n_e; ++e) t[(size_t)e] = sind_deg(e * eg - em / 2.0);                         // music.m:47,44
+    for (int a = 0; a < n_a; ++a) {
+      const double ph = a * ag - am / 2.0;                                                              // music.m:48
+      t[(size_t)n_e + a] = cosd_deg(ph);
+      t[(size_t)n_e + n_a + a] = sind_deg(ph);
+    }
+    DevBuf b;
+    ISAC_TRY(upload(ctx, b, t.data(), sizeof(double) * t.size()));
+    it = ctx->doa2d_tab.emplace(key, b).first;
+  }
+  *out = (const double*)it->second.p;
+  *e_steps = n_e;
+  *a_steps = n_a;
+  return ISAC_OK;
+}
+
+int check_upa_dims(isac_ctx* ctx, const isac_est_params* ep, int A) {   // radarParams.m:90,99 reshape to nTxAnts
+  if (ep->n_ants_x <= 0 || ep->n_ants_y <= 0 || (long long)ep->n_ants_x * ep->n_ants_y != A)
+    return fail(ctx, ISAC_ERR_INVALID_ARG, "UPA DoA: n_ants_x * n_ants_y must equal the number of antennas");
+  if (A > 256) return fail(ctx, ISAC_ERR_UNSUPPORTED, "UPA DoA: the 2-D scan supports up to 256 elements");
   return ISAC_OK;
 }
 
@@ -334,7 +380,9 @@ extern "C" int isac_ctx_destroy(isac_ctx* ctx) {
   for (auto& kv : ctx->twiddles) (void)hipFree(kv.second.p);
   for (auto& kv : ctx->kaiser3) (void)hipFree(kv.second.p);
   for (auto& kv : ctx->sind) (void)hipFree(kv.second.p);
-  DevBuf* bufs[] = {&ctx->beam, &ctx->coef, &ctx->phase_rx, &ctx->steer, &ctx->dgrid,
+  for (auto& kv : ctx->doa2d_tab) (void)hipFree(kv.second.p);
+  DevBuf* bufs[] = {&ctx->doa2d_p, &ctx->doa2d_db, &ctx->doa2d_cand, &ctx->doa2d_w, &ctx->doa2d_user,
+                    &ctx->beam, &ctx->coef, &ctx->phase_rx, &ctx->steer, &ctx->dgrid,
                     &ctx->ymid, &ctx->pwin, &ctx->flags, &ctx->det_cut, &ctx->det_pow, &ctx->det_cnt, &ctx->cov_part,
                     &ctx->cov, &ctx->eig_w, &ctx->eig_v, &ctx->eig_scratch, &ctx->spec, &ctx->misc, &ctx->stage_a, &ctx->stage_b, &ctx->seg,
                     &ctx->stage_c, &ctx->sind_tab, &ctx->cdl_h, &ctx->echo_own, &ctx->os_x};
@@ -613,11 +661,25 @@ static int fft2d_submit(isac_ctx* ctx, const isac_est_params* ep, const isac_cfa
   //   stream2: covariance (fp64 MFMA) -> eig (one CU)      stream: range IFFT -> Doppler -> CFAR
   ISAC_TRY(ensure(ctx, ctx->cov, sizeof(c64) * (size_t)A * A));
   ISAC_TRY(ensure(ctx, ctx->misc, 512));
-  const bool sub = !upa && isac_music_subspace_ok(ctx, A);      // MUSIC needs the numDets signal vectors only (music.m:27-29)
+  const bool upa2d = upa && ctx->upa_doa != 0;                  // ISAC_OPT_UPA_DOA: the 2-D scan + find2DPeaks
+  const bool sub = (!upa || upa2d) && isac_music_subspace_ok(ctx, A);      // MUSIC needs the numDets signal vectors only (music.m:27-29)
   if (!upa) {
     ISAC_TRY(get_sind_table(ctx, ep, &d_sind, &n_steps));
     ISAC_TRY(ensure(ctx, ctx->spec, sizeof(double) * (size_t)n_steps));
   }
+  const double* d_tab2d = nullptr;
+  int e_steps = 0, a_steps = 0, cap2d = 0, first2d = 0;
+  if (upa2d) {                                                  // every buffer of the 2-D tail sized here, before anything is enqueued
+    ISAC_TRY(check_upa_dims(ctx, ep, A));
+    ISAC_TRY(get_doa2d_tables(ctx, ep, &d_tab2d, &e_steps, &a_steps));
+    cap2d = isac_doa2d_peak_cap(e_steps, a_steps);
+    first2d = std::min(cap2d, 256);                             // candidates that travel in the result copy; more: a second copy at collect
+    ISAC_TRY(ensure(ctx, ctx->doa2d_p, sizeof(double) * (size_t)e_steps * a_steps));
+    ISAC_TRY(ensure(ctx, ctx->doa2d_db, sizeof(double) * (size_t)e_steps * a_steps));
+    ISAC_TRY(ensure(ctx, ctx->doa2d_cand, sizeof(double) * (size_t)isac_doa2d_cand_doubles(cap2d)));
+    ISAC_TRY(ensure(ctx, ctx->doa2d_w, sizeof(double) * (size_t)A));
+  }
+  const int n_spec = upa2d ? isac_doa2d_cand_doubles(first2d) : n_steps;   // doubles of the pack's spectrum slot: the ULA spectrum, or [counter | first candidates]
   static const bool single_stream = std::getenv("ISAC_SINGLE_STREAM") != nullptr;   // diagnostic: one stream, isolated kernel times
   hipStream_t s2 = single_stream ? ctx->stream : ctx->stream2;
   // ISAC_OPT_WIDE_ORDER: the covariance (a wide kernel) stays on the main stream, behind the echo synthesis / range stage; everything
@@ -648,7 +710,7 @@ static int fft2d_submit(isac_ctx* ctx, const isac_est_params* ep, const isac_cfa
     timeline_mark(ctx, 5, s2);
   }
   auto eig_first_half = [&]() -> int {                                                           // music.m:19
-    if (upa) return ISAC_OK;
+    if (upa && !upa2d) return ISAC_OK;
     if (sub) return isac_music_tridiag_bisect_dev(ctx, (const c64*)ctx->cov.p, A, s2);           // reflectors + eigenvalues: independent of numDets
     return isac_eigh_dev(ctx, (const c64*)ctx->cov.p, A, s2, /*live_replay=*/false);   // (collect cannot run the replay time-out recovery before the scan)
   };
@@ -668,6 +730,10 @@ static int fft2d_submit(isac_ctx* ctx, const isac_est_params* ep, const isac_cfa
   if (!upa) {   // numDets comes from the CFAR branch, still on the device                   music.m:12,82-91
     if (sub) ISAC_TRY(isac_music_subspace_dev(ctx, A, (const int*)ctx->misc.p, 0, s2));          // the numDets signal vectors (or the QL fallback)
     ISAC_TRY(isac_music_scan_dev(ctx, A, (const int*)ctx->misc.p, 0, d_sind, n_steps, 0.5, (double*)ctx->spec.p, s2, 0, sub ? isac_music_ctl(ctx) : nullptr));
+  } else if (upa2d) {   // music.m:31-63 on the 2-D grid + the device half of find2DPeaks, numDets still on the device
+    if (sub) ISAC_TRY(isac_music_subspace_dev(ctx, A, (const int*)ctx->misc.p, 0, s2));
+    ISAC_TRY(isac_doa2d_scan_dev(ctx, 0, ep->n_ants_x, ep->n_ants_y, e_steps, a_steps, d_tab2d, (const int*)ctx->misc.p, 0, sub ? isac_music_ctl(ctx) : nullptr, s2));
+    ISAC_TRY(isac_doa2d_norm_peaks_dev(ctx, true, (const double*)ctx->doa2d_db.p, e_steps, a_steps, (double*)ctx->doa2d_cand.p, cap2d, s2));
   }
   ISAC_HIP(hipEventRecord(ctx->ev_join, s2));
   ISAC_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
@@ -675,7 +741,7 @@ static int fft2d_submit(isac_ctx* ctx, const isac_est_params* ep, const isac_cfa
   const int pack_first = 4096;
   const size_t hdr_ints = 3 + (size_t)A + 1;
   const size_t off_spec = (hdr_ints * sizeof(int) + 15) & ~(size_t)15;
-  const size_t off_pow = off_spec + sizeof(double) * (size_t)(n_steps > 0 ? n_steps : 1);
+  const size_t off_pow = off_spec + sizeof(double) * (size_t)(n_spec > 0 ? n_spec : 1);
   const size_t off_cut = off_pow + sizeof(double) * (size_t)pack_first;
   const size_t first_bytes = off_cut + sizeof(int) * (size_t)pack_first;
   const size_t pack_cap = (size_t)A * cap;
@@ -691,8 +757,8 @@ static int fft2d_submit(isac_ctx* ctx, const isac_est_params* ep, const isac_cfa
   int* d_pcut_full = (int*)((char*)ctx->stage_b.p + sizeof(double) * pack_cap);
   hipLaunchKernelGGL(pack_kernel, dim3(1), dim3(256), 0, ctx->stream, (const int*)ctx->det_cnt.p, (const int*)ctx->det_cut.p,
                      (const double*)ctx->det_pow.p, (const int*)ctx->misc.p, A, cap, (int*)dbase, d_pcut_full, d_ppow_full,
-                     pack_first, d_pcut_first, d_ppow_first, (const double*)ctx->spec.p, n_steps, (double*)(dbase + off_spec),
-                     upa ? nullptr : (const int*)((const char*)ctx->eig_w.p + sizeof(double) * (size_t)A));
+                     pack_first, d_pcut_first, d_ppow_first, upa2d ? (const double*)ctx->doa2d_cand.p : (const double*)ctx->spec.p, n_spec,
+                     (double*)(dbase + off_spec), (upa && !upa2d) ? nullptr : (const int*)((const char*)ctx->eig_w.p + sizeof(double) * (size_t)A));
   ISAC_HIP(hipGetLastError());
   char* h = (char*)ctx->pinned;
   ISAC_HIP(hipMemcpyAsync(h, dbase, first_bytes, hipMemcpyDeviceToHost, ctx->stream));
@@ -705,6 +771,7 @@ static int fft2d_submit(isac_ctx* ctx, const isac_est_params* ep, const isac_cfa
   pd.A = A; pd.nr = nr; pd.nc = nc; pd.n_steps = n_steps; pd.pack_first = pack_first;
   pd.off_spec = off_spec; pd.off_pow = off_pow; pd.off_cut = off_cut;
   pd.d_pcut_full = d_pcut_full; pd.d_ppow_full = d_ppow_full;
+  pd.upa2d = upa2d; pd.e_steps = e_steps; pd.a_steps = a_steps; pd.cap2d = cap2d; pd.first2d = first2d;
   pd.active = true;
   return ISAC_OK;
 }
@@ -796,7 +863,30 @@ extern "C" int isac_fft2d_collect(isac_ctx* ctx, isac_est_result* out) {
   for (size_t i = 0; i < ucol.size(); ++i) out->vel_est[i] = ((double)ucol[i] - ep->n_fft / 2.0 - 1.0) * ep->v_res;   // :78,:82
   last.valid = true;
   last.spectrum_db.clear();
-  if (upa) return fail(ctx, ISAC_ERR_UNSUPPORTED, "UPA DoA: music.m:69 calls tools.find2DPeaks, which the reference does not define");
+  if (upa && !pd.upa2d) return fail(ctx, ISAC_ERR_UNSUPPORTED, "UPA DoA: music.m:69 calls tools.find2DPeaks, which the reference does not define");
+  if (upa) {   // ---- 2-D DoA, music.m:65-71 (ISAC_OPT_UPA_DOA)
+    const double* cand = (const double*)(h + off_spec);
+    const int count = (int)*(const unsigned*)cand;
+    if (count > pd.cap2d) return fail(ctx, ISAC_ERR_HIP, "find2DPeaks: candidate count beyond the 2 x 2 bound (internal error)");
+    std::vector<double> full;
+    if (count > pd.first2d) {
+      full.resize((size_t)isac_doa2d_cand_doubles(count));
+      ISAC_TRY(copy_d2h(ctx, full.data(), ctx->doa2d_cand.p, sizeof(double) * full.size()));
+      cand = full.data();
+    }
+    ctx->doa2d_rows = pd.e_steps;
+    ctx->doa2d_cols = pd.a_steps;
+    if (out->num_dets == 0)
+      return fail(ctx, ISAC_ERR_NO_DETECTION, "no CFAR detection: find2DPeaks needs a positive number of peaks (music.m:69)");
+    std::vector<int> ele, azi;
+    ISAC_TRY(isac_doa2d_select(ctx, cand, count, pd.cap2d, pd.e_steps, out->num_dets, ele, azi));
+    out->n_azi = (int)std::min<size_t>(azi.size(), ISAC_MAX_EST);
+    for (int i = 0; i < out->n_azi; ++i) {
+      out->ele_est[i] = (ele[(size_t)i] - 1) * ep->elevation_scan_granularity - ep->elevation_scan_scale / 2.0;   // music.m:70
+      out->azi_est[i] = (azi[(size_t)i] - 1) * ep->azimuth_scan_granularity - ep->azimuth_scan_scale / 2.0;       // music.m:71
+    }
+    return ISAC_OK;
+  }
   // ---- DoA, music.m:94-104
   const double* spec = (const double*)(h + off_spec);
   double mx = 0.0;
@@ -969,7 +1059,9 @@ static int doa_scan(isac_ctx* ctx, int mode, int32_t num_dets, const isac_est_pa
   *n_est = 0;
   ISAC_TRY(ensure(ctx, ctx->stage_c, sizeof(c64) * (size_t)A * A));
   ISAC_TRY(copy_h2d(ctx, ctx->stage_c.p, Ra, sizeof(c64) * (size_t)A * A));
-  const bool sub = mode == 0 && !ep->array_is_upa && isac_music_subspace_ok(ctx, A);   // MUSIC: the L signal vectors are enough
+  const bool upa2d = ep->array_is_upa && ctx->upa_doa;                                            // ISAC_OPT_UPA_DOA
+  if (upa2d) ISAC_TRY(check_upa_dims(ctx, ep, A));
+  const bool sub = mode == 0 && (!ep->array_is_upa || upa2d) && isac_music_subspace_ok(ctx, A);   // MUSIC: the L signal vectors are enough
   if (sub) ISAC_TRY(isac_music_tridiag_bisect_dev(ctx, (const c64*)ctx->stage_c.p, A, nullptr));
   else ISAC_TRY(isac_eigh_dev(ctx, (const c64*)ctx->stage_c.p, A, nullptr));                               // music.m:19
   int L = num_dets;
@@ -982,7 +1074,36 @@ static int doa_scan(isac_ctx* ctx, int mode, int32_t num_dets, const isac_est_pa
   }
   if (sub) ISAC_TRY(isac_music_subspace_dev(ctx, A, nullptr, L, nullptr));
   if (L_out) *L_out = L;
-  if (ep->array_is_upa) return fail(ctx, ISAC_ERR_UNSUPPORTED, "UPA DoA: music.m:69 calls tools.find2DPeaks, which the reference does not define");
+  if (ep->array_is_upa && !upa2d) return fail(ctx, ISAC_ERR_UNSUPPORTED, "UPA DoA: music.m:69 calls tools.find2DPeaks, which the reference does not define");
+  if (upa2d) {   // music.m:31-71 / digitalBF.m:13-53 / mvdrBF.m:13-53
+    const double* d_tab = nullptr;
+    int e_steps = 0, a_steps = 0;
+    ISAC_TRY(get_doa2d_tables(ctx, ep, &d_tab, &e_steps, &a_steps));
+    const int cap2d = isac_doa2d_peak_cap(e_steps, a_steps);
+    ISAC_TRY(ensure(ctx, ctx->doa2d_db, sizeof(double) * (size_t)e_steps * a_steps));
+    ISAC_TRY(ensure(ctx, ctx->doa2d_cand, sizeof(double) * (size_t)isac_doa2d_cand_doubles(cap2d)));
+    ISAC_TRY(isac_doa2d_scan_dev(ctx, mode, ep->n_ants_x, ep->n_ants_y, e_steps, a_steps, d_tab, nullptr, L, sub ? isac_music_ctl(ctx) : nullptr, nullptr));
+    ISAC_TRY(isac_doa2d_norm_peaks_dev(ctx, true, (const double*)ctx->doa2d_db.p, e_steps, a_steps, (double*)ctx->doa2d_cand.p, cap2d, nullptr));
+    unsigned count = 0;
+    ISAC_TRY(copy_d2h(ctx, &count, ctx->doa2d_cand.p, sizeof(count)));
+    ISAC_HIP(hipStreamSynchronize(ctx->stream));
+    ISAC_TRY(eig_status(ctx, A));
+    ctx->doa2d_rows = e_steps;
+    ctx->doa2d_cols = a_steps;
+    if (L <= 0) return fail(ctx, ISAC_ERR_NO_DETECTION, "find2DPeaks needs a positive number of peaks (music.m:69)");
+    if ((int)count > cap2d) return fail(ctx, ISAC_ERR_HIP, "find2DPeaks: candidate count beyond the 2 x 2 bound (internal error)");
+    std::vector<double> cand((size_t)isac_doa2d_cand_doubles((int)count));
+    ISAC_TRY(copy_d2h(ctx, cand.data(), ctx->doa2d_cand.p, sizeof(double) * cand.size()));
+    std::vector<int> ele, azi;
+    ISAC_TRY(isac_doa2d_select(ctx, cand.data(), (int)count, cap2d, e_steps, L, ele, azi));
+    if ((int)azi.size() > cap) return fail(ctx, ISAC_ERR_CAPACITY, "more peaks than capacity");
+    *n_est = (int)azi.size();
+    for (size_t i = 0; i < azi.size(); ++i) {
+      if (ele_est) ele_est[i] = (ele[i] - 1) * ep->elevation_scan_granularity - ep->elevation_scan_scale / 2.0;   // music.m:70
+      if (azi_est) azi_est[i] = (azi[i] - 1) * ep->azimuth_scan_granularity - ep->azimuth_scan_scale / 2.0;       // music.m:71
+    }
+    return ISAC_OK;
+  }
   int n_steps = 0;
   const double* d_sind = nullptr;
   ISAC_TRY(get_sind_table(ctx, ep, &d_sind, &n_steps));
@@ -1110,6 +1231,7 @@ extern "C" int isac_ctx_set_option(isac_ctx* ctx, int32_t option, int32_t value)
     case ISAC_OPT_TAIL_FUSION: ctx->tail_fusion = value; return ISAC_OK;          // 1 = one Doppler + CFAR launch (default), 0 = separate kernels
     case ISAC_OPT_WIDE_ORDER: ctx->wide_order = value; return ISAC_OK;            // 1 = covariance on the main stream, the narrow kernels on the second
     case ISAC_OPT_CDL_SHARE_SPECTRA: ctx->cdl_share_spectra = value; ctx->os_valid = false; return ISAC_OK;   // 1 = consecutive downlink batches on the same waveforms share their forward transforms
+    case ISAC_OPT_UPA_DOA: ctx->upa_doa = value; return ISAC_OK;                  // 1 = UPA DoA through the 2-D scan + find2DPeaks, 0 = ISAC_ERR_UNSUPPORTED
     default: return fail(ctx, ISAC_ERR_INVALID_ARG, "unknown option");
   }
 }
@@ -1144,6 +1266,45 @@ extern "C" int isac_beamscan_doa(isac_ctx* ctx, int32_t method, int32_t num_dets
   if (method != 1 && method != 2) return fail(ctx, ISAC_ERR_INVALID_ARG, "method: 1 = digitalBF, 2 = mvdrBF");
   if (num_dets < 0) return fail(ctx, ISAC_ERR_INVALID_ARG, "digitalBF / mvdrBF need numDets (digitalBF.m:84, mvdrBF.m:84)");
   return doa_scan(ctx, method, num_dets, ep, Ra, A, nullptr, azi_est, ele_est, cap, n_est);
+}
+
+// ------------------------------------------------------------------ UPA angular spectrum / find2DPeaks (include/isac.h)
+extern "C" int isac_get_angular_spectrum2d(isac_ctx* ctx, double* p_db, int64_t cap, int32_t dims[2]) {
+  ISAC_ENTER(ctx);
+  if (ctx->doa2d_rows <= 0 || ctx->doa2d_cols <= 0) return fail(ctx, ISAC_ERR_INVALID_ARG, "no UPA DoA has run on this context");
+  if (dims) { dims[0] = ctx->doa2d_rows; dims[1] = ctx->doa2d_cols; }
+  if (!p_db) return ISAC_OK;
+  const long long n = (long long)ctx->doa2d_rows * ctx->doa2d_cols;
+  if (cap < n) return fail(ctx, ISAC_ERR_CAPACITY, "angular spectrum larger than capacity");
+  ISAC_TRY(copy_d2h(ctx, p_db, ctx->doa2d_db.p, sizeof(double) * (size_t)n));
+  return ISAC_OK;
+}
+
+extern "C" int isac_find2d_peaks(isac_ctx* ctx, const double* p_db, int32_t rows, int32_t cols, int32_t n_peaks, int32_t* ele, int32_t* azi,
+                                 int32_t* n_found) {
+  ISAC_ENTER(ctx);
+  if (!p_db || rows <= 0 || cols <= 0 || !n_found || (n_peaks > 0 && (!ele || !azi))) return fail(ctx, ISAC_ERR_INVALID_ARG, "bad arguments");
+  *n_found = 0;
+  const long long n = (long long)rows * cols;
+  if (n > (1ll << 26)) return fail(ctx, ISAC_ERR_INVALID_ARG, "find2DPeaks: matrix too large");
+  if (n_peaks <= 0) return fail(ctx, ISAC_ERR_NO_DETECTION, "find2DPeaks needs a positive number of peaks (music.m:69)");
+  const int cap = isac_doa2d_peak_cap(rows, cols);
+  const size_t map_doubles = ((size_t)n + 1) & ~(size_t)1;                 // (candidates 16-byte aligned behind the map)
+  ISAC_TRY(ensure(ctx, ctx->doa2d_user, sizeof(double) * (map_doubles + (size_t)isac_doa2d_cand_doubles(cap))));
+  double* d_map = (double*)ctx->doa2d_user.p;
+  double* d_cand = d_map + map_doubles;
+  ISAC_TRY(copy_h2d(ctx, d_map, p_db, sizeof(double) * (size_t)n));
+  ISAC_TRY(isac_doa2d_norm_peaks_dev(ctx, false, d_map, rows, cols, d_cand, cap, nullptr));
+  unsigned count = 0;
+  ISAC_TRY(copy_d2h(ctx, &count, d_cand, sizeof(count)));
+  if ((int)count > cap) return fail(ctx, ISAC_ERR_HIP, "find2DPeaks: candidate count beyond the 2 x 2 bound (internal error)");
+  std::vector<double> cand((size_t)isac_doa2d_cand_doubles((int)count));
+  ISAC_TRY(copy_d2h(ctx, cand.data(), d_cand, sizeof(double) * cand.size()));
+  std::vector<int> e, a;
+  ISAC_TRY(isac_doa2d_select(ctx, cand.data(), (int)count, cap, rows, n_peaks, e, a));
+  for (size_t i = 0; i < e.size(); ++i) { ele[i] = e[i]; azi[i] = a[i]; }
+  *n_found = (int)e.size();
+  return ISAC_OK;
 }
 
 // ------------------------------------------------------------------ music2D (music2D.m:1-123)

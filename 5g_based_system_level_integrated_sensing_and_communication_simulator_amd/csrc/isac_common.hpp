@@ -123,6 +123,8 @@ struct Fft2dPending {  // state between isac_fft2d_submit_dev and isac_fft2d_col
   size_t off_spec = 0, off_pow = 0, off_cut = 0;
   int* d_pcut_full = nullptr;
   double* d_ppow_full = nullptr;
+  bool upa2d = false;                      // ISAC_OPT_UPA_DOA: the pack's spectrum slot holds [counter | first2d find2DPeaks candidates]
+  int e_steps = 0, a_steps = 0, cap2d = 0, first2d = 0;
 };
 
 }  // namespace isac
@@ -170,6 +172,11 @@ struct isac_ctx {
   long long os_T = 0; int os_nt = 0, os_mpad = 0, os_tb = 0; bool os_valid = false;
   int cdl_share_spectra = 0;
   isac::DevBuf echo_own;             // ... and its storage when it has to exist in memory (LazyEcho::native == false)
+  // ISAC_OPT_UPA_DOA (doa2d.hip): the 2-D (elevation x azimuth) scan of a UPA
+  int upa_doa = 0;                   // 0 = UPA DoA returns ISAC_ERR_UNSUPPORTED (default), 1 = 2-D scan + find2DPeaks
+  std::map<std::vector<long long>, isac::DevBuf> doa2d_tab;          // (scales, granularities) -> [sind(ele) | cosd(azi) | sind(azi)]
+  isac::DevBuf doa2d_p, doa2d_db, doa2d_cand, doa2d_w, doa2d_user;  // raw spectrum, dB map, peak candidates, eigen weights, a caller's map
+  int doa2d_rows = 0, doa2d_cols = 0;   // dims of the dB map in doa2d_db (0: none yet)
   isac::StageSlot stage_ring[isac::kStageSlots];   // pinned->device parameter uploads (stage_acquire / stage_commit)
   int stage_next = 0;
 };

@@ -1,5 +1,6 @@
 """sensing.estimation.doaEstimation.digitalBF / mvdrBF (+sensing/+estimation/+doaEstimation/digitalBF.m:55-86,
-mvdrBF.m:55-86), ULA branch.  No caller in the reference; they reuse the MUSIC eigendecomposition + scan kernel."""
+mvdrBF.m:55-86) and, with ``ctx.set_upa_doa(True)``, their UPA branch (digitalBF.m:13-53, mvdrBF.m:13-53: the 2-D scan + find2DPeaks;
+IsacError(UNSUPPORTED) otherwise).  No caller in the reference; they reuse the MUSIC eigendecomposition + scan kernels."""
 from __future__ import annotations
 
 import ctypes as C

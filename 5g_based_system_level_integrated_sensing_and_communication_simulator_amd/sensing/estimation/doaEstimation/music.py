@@ -1,5 +1,7 @@
-"""sensing.estimation.doaEstimation.music (+sensing/+estimation/+doaEstimation/music.m:1-125), ULA branch.
-The UPA branch of the reference ends in the undefined ``tools.find2DPeaks`` (music.m:69) and errors."""
+"""sensing.estimation.doaEstimation.music (+sensing/+estimation/+doaEstimation/music.m:1-125).
+ULA branch always; the UPA branch (music.m:31-71) ends in ``tools.find2DPeaks``, which the reference never defines: it raises
+IsacError(UNSUPPORTED) unless the context has ``set_upa_doa(True)``, and then returns finite ``eleEst`` from the 2-D scan and the
+project's find2DPeaks (include/isac.h)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -12,7 +14,8 @@ from ..._marshal import est_block
 
 def music(numDets, radarEstParams, Ra, *, ctx=None):
     """[L, aziEst, eleEst] = music(numDets, radarEstParams, Ra).  ``numDets`` None/[] -> model order
-    from determineNumTargets (music.m:21-22,109-125)."""
+    from determineNumTargets (music.m:21-22,109-125).  ULA: eleEst is NaN (music.m:104); UPA (ctx.set_upa_doa(True)): the
+    elevations of the find2DPeaks peaks (music.m:70), the dB map in ``ctx.angular_spectrum2d()``."""
     ctx = ctx or L.default_context()
     ra = L.as_c128_f(Ra)
     A = ra.shape[0]

@@ -44,7 +44,10 @@ def fft2D(radarEstParams, cfar, rxGrid, txGrid, *, ctx=None, return_debug=False,
     reference's caller turns any error into ``senResults = NaN`` (cellSimulation.m:196-202).
     Plotting (fft2D.m:119) is not part of the hot path.
     ``reuse_range=True`` (device grids): consume the range rows the preceding ``monoStaticSensing(..., fuse_fft2d=...)``
-    call cached on this context (isac_fft2d_submit_cached_dev); an error if there are none."""
+    call cached on this context (isac_fft2d_submit_cached_dev); an error if there are none.
+    A UPA (radarEstParams.antennaType.kind == "upa") raises IsacError(UNSUPPORTED) after the range / velocity stages, as the reference fails
+    at music.m:69, unless the context has ``set_upa_doa(True)``: then aziEst / eleEst come from the 2-D scan and find2DPeaks, and
+    ``return_debug`` adds ``spectrum_db_2d`` (the [eSteps x aSteps] dB map)."""
     lazy = hasattr(rxGrid, "materialize")                 # LazyEchoGrid of monoStaticSensing(..., lazy=True): rxGrid goes to the library as NULL
     if lazy and not reuse_range:
         raise ValueError("a lazy echo grid is consumed with reuse_range=True (the fused call has already run its range stage)")
@@ -77,7 +80,10 @@ def fft2D(radarEstParams, cfar, rxGrid, txGrid, *, ctx=None, return_debug=False,
     est = SimpleNamespace(rngEst=np.array(res.rng_est[: res.n_rng]), velEst=np.array(res.vel_est[: res.n_vel]),
                           aziEst=np.array(res.azi_est[: res.n_azi]), eleEst=np.array(res.ele_est[: res.n_azi]))
     if return_debug:
-        return est, fft2D_debug(ctx, A)
+        dbg = fft2D_debug(ctx, A)
+        if ep.array_is_upa:
+            dbg.spectrum_db_2d = ctx.angular_spectrum2d()
+        return est, dbg
     return est
 
 

@@ -32,10 +32,10 @@ extern "C" {
 #endif
 
 /* Bumped on EVERY change of a struct layout, enum value or entry-point signature below (1: round 1; 2: ISAC_MAX_EST 1024 -> 4096,
- * noise modes 3 / 4, the fused / cached / windowed / CDL / CSI entry points; 3: isac_abi_sizeof, isac_ctx_set_option, isac_eigh_top; 4: ISAC_OPT_WIDE_ORDER, isac_ctx_share_streams; 5: isac_cdl_apply_batch_dev, isac_cdl_path_gains_dev, isac_csi_report_batch_dev; 6: isac_ctx_reserve, isac_prg_precode_dev, isac_cdl_freq_response_dev, isac_cdl_csi_estimate_batch_dev; 7: the lazy echo grid -- d_echo_grid / d_rx_grid may be NULL --, isac_echo_grid_materialize_dev, isac_sensing_submit_n / isac_sensing_collect_n, isac_csi_report.ri_total_sinr, isac_pusch_codebook, isac_srs_pmi_select_batch_dev, ISAC_OPT_CDL_SHARE_SPECTRA).  A host must
+ * noise modes 3 / 4, the fused / cached / windowed / CDL / CSI entry points; 3: isac_abi_sizeof, isac_ctx_set_option, isac_eigh_top; 4: ISAC_OPT_WIDE_ORDER, isac_ctx_share_streams; 5: isac_cdl_apply_batch_dev, isac_cdl_path_gains_dev, isac_csi_report_batch_dev; 6: isac_ctx_reserve, isac_prg_precode_dev, isac_cdl_freq_response_dev, isac_cdl_csi_estimate_batch_dev; 7: the lazy echo grid -- d_echo_grid / d_rx_grid may be NULL --, isac_echo_grid_materialize_dev, isac_sensing_submit_n / isac_sensing_collect_n, isac_csi_report.ri_total_sinr, isac_pusch_codebook, isac_srs_pmi_select_batch_dev, ISAC_OPT_CDL_SHARE_SPECTRA; 8: ISAC_OPT_UPA_DOA, isac_get_angular_spectrum2d, isac_find2d_peaks).  A host must
  * compare isac_abi_version() with the ISAC_ABI_VERSION it was compiled against AND isac_abi_sizeof() with its own sizeof of every
  * struct it passes: the library writes whole structs (isac_est_result is 128 KB) into caller memory. */
-#define ISAC_ABI_VERSION 7
+#define ISAC_ABI_VERSION 8
 #define ISAC_MAX_EST 4096 /* capacity of the estimate vectors in isac_est_result: unique range bins <= nIFFT (<= 4096 for every
                              * NR numerology), unique velocity bins <= nFFT, azimuth peaks <= 180 -- never the binding limit */
 
@@ -52,7 +52,7 @@ typedef enum {
                                 cellSimulation.m:196-202 maps it to senResults = NaN */
   ISAC_ERR_CFAR_WINDOW = 5,  /* a CUT's training window leaves the map (phased.CFARDetector2D error) */
   ISAC_ERR_CAPACITY = 6,     /* more results than the caller's capacity */
-  ISAC_ERR_UNSUPPORTED = 7,  /* e.g. UPA DoA: music.m:69 calls the non-existent tools.find2DPeaks */
+  ISAC_ERR_UNSUPPORTED = 7,  /* e.g. UPA DoA unless ISAC_OPT_UPA_DOA: music.m:69 calls the non-existent tools.find2DPeaks */
   ISAC_ERR_SHORT_WAVEFORM = 8 /* waveform shorter than one OFDM symbol (nrOFDMDemodulate error) */
 } isac_status;
 
@@ -357,7 +357,17 @@ int isac_eigh_top(isac_ctx* ctx, const isac_c64* H, int32_t A, int32_t n_top, do
  *                profile's call of a cell-slot skips a third of the path.  All profiles then share one window step (Mpad = 512 samples where they need no more).  The CALLER
  *                promises that those waveforms were not rewritten between the two calls; any other call pattern simply transforms again.  Same results to rounding (the window
  *                boundaries move: <= 1e-12 against the default). */
-enum { ISAC_OPT_MUSIC_ROUTE = 0, ISAC_OPT_TAIL_FUSION = 1, ISAC_OPT_WIDE_ORDER = 2, ISAC_OPT_CDL_SHARE_SPECTRA = 3 };
+/* ISAC_OPT_UPA_DOA  DoA of a uniform planar array (isac_est_params.array_is_upa) in isac_fft2d_submit*_dev / isac_fft2d_collect (and so isac_fft2d[_dev],
+ *                   isac_sensing_submit_n / collect_n), isac_music_doa and isac_beamscan_doa (methods 1 and 2):
+ *   0 (default)  ISAC_ERR_UNSUPPORTED, as the reference fails at music.m:69 (tools.find2DPeaks is not defined there); range and velocity are still reported;
+ *   1            the 2-D scan of music.m:31-71 / digitalBF.m:13-53 / mvdrBF.m:13-53 over eSteps = floor((eMax+1)/eGran) elevations x aSteps = floor((aMax+1)/aGran)
+ *                azimuths, steering a[n + nH m] = exp(-2j pi sind(th) (m d cosd(ph) + n d sind(ph))), d = 0.5, m < nV = n_ants_x, n < nH = n_ants_y
+ *                (n_ants_x * n_ants_y must equal A, at most 256), the column normalisation of music.m:61-63 (below) and find2DPeaks (isac_find2d_peaks);
+ *                ele_est / aziEst = (ele-1) eGran - eMax/2, (azi-1) aGran - aMax/2 (music.m:70-71).  The dB map stays on the device: isac_get_angular_spectrum2d.
+ *                Normalisation quirk kept: P = -abs(P); P ./ max(P) takes COLUMN maxima of a matrix, so every azimuth column is divided by its own
+ *                least-magnitude value -- every column's minimum is exactly 0 dB.  Mirror twins (ph -+ 180, -th) have bitwise equal steering vectors and values.
+ * isac_music2d_dev stays ULA-only (ISAC_ERR_UNSUPPORTED for a UPA) whatever this option says. */
+enum { ISAC_OPT_MUSIC_ROUTE = 0, ISAC_OPT_TAIL_FUSION = 1, ISAC_OPT_WIDE_ORDER = 2, ISAC_OPT_CDL_SHARE_SPECTRA = 3, ISAC_OPT_UPA_DOA = 4 };
 int isac_ctx_set_option(isac_ctx* ctx, int32_t option, int32_t value);
 
 /* A host that keeps several CPIs in flight on one device uses one context per CPI (buffers, scratch, pending result).  By default each
@@ -380,17 +390,29 @@ int isac_ctx_share_streams(isac_ctx* ctx, isac_ctx* owner);
 int isac_ctx_reserve(isac_ctx* ctx, int64_t T, int32_t tx_dim_l, const isac_carrier* carrier, const isac_radar_channel_params* rp,
                      const isac_est_params* ep, const isac_cfar_config* cfar, double warm_ms, double* elapsed_ms);
 
-/* sensing.estimation.doaEstimation.music(numDets, radarEstParams, Ra) (music.m:1), ULA branch.
+/* sensing.estimation.doaEstimation.music(numDets, radarEstParams, Ra) (music.m:1): ULA branch; UPA branch with ISAC_OPT_UPA_DOA (above), else ISAC_ERR_UNSUPPORTED.
  * num_dets < 0 means [] (model order from determineNumTargets, music.m:109-125). */
 int isac_music_doa(isac_ctx* ctx, int32_t num_dets, const isac_est_params* ep, const isac_c64* Ra,
                    int32_t A, int32_t* L_out, double* azi_est, double* ele_est, int32_t cap, int32_t* n_est);
 
 /* sensing.estimation.doaEstimation.digitalBF (method 1, digitalBF.m:55-86: |a' Ra a|) and .mvdrBF (method 2,
- * mvdrBF.m:55-86: 1/(a' Ra^-1 a + eps)), ULA branch; same scan/findpeaks tail as music. */
+ * mvdrBF.m:55-86: 1/(a' Ra^-1 a + eps)), ULA branch; same scan/findpeaks tail as music.  UPA branch (digitalBF.m:13-53, mvdrBF.m:13-53) with ISAC_OPT_UPA_DOA. */
 int isac_beamscan_doa(isac_ctx* ctx, int32_t method, int32_t num_dets, const isac_est_params* ep, const isac_c64* Ra,
                       int32_t A, double* azi_est, double* ele_est, int32_t cap, int32_t* n_est);
 
-/* sensing.estimation.music2D(rdrEstParams, bsParams, rxGrid, txGrid) (+sensing/+estimation/music2D.m:1-123):
+/* UPA DoA introspection and the project's find2DPeaks (ISAC_OPT_UPA_DOA above).
+ * isac_get_angular_spectrum2d: the [eSteps x aSteps] column-major dB map of the context's last UPA DoA (isac_music_doa / isac_beamscan_doa / fft2D);
+ *   dims = {eSteps, aSteps}; p_db == NULL: size query only.
+ * isac_find2d_peaks: tools.find2DPeaks(PdB, L), which the reference calls (music.m:69, digitalBF.m:51, mvdrBF.m:51) but never defines, on a caller's
+ *   p_db [rows x cols] column-major, through the same device kernel and host sort as the DoA calls.  Definition:
+ *     1. a candidate is an INTERIOR cell (1 < e < rows, 1 < a < cols) strictly greater than all 8 neighbours -- no wrap-around, border cells are never
+ *        peaks (findpeaks' "no end points" in 2-D), a plateau gives no peak, NaN is never a peak;
+ *     2. candidates sorted by value, descending, ties by ascending column-major index e + rows (a-1) (a stable sort of find(isPeak));
+ *     3. the first min(n_peaks, #candidates) as 1-based ele [n_peaks] / azi [n_peaks], *n_found of them.  n_peaks <= 0: ISAC_ERR_NO_DETECTION. */
+int isac_get_angular_spectrum2d(isac_ctx* ctx, double* p_db, int64_t cap, int32_t dims[2]);
+int isac_find2d_peaks(isac_ctx* ctx, const double* p_db, int32_t rows, int32_t cols, int32_t n_peaks, int32_t* ele, int32_t* azi, int32_t* n_found);
+
+/* sensing.estimation.music2D(rdrEstParams, bsParams, rxGrid, txGrid) (+sensing/+estimation/music2D.m:1-123), ULA only (a UPA: ISAC_ERR_UNSUPPORTED):
  * MUSIC DoA with the model order from determineNumTargets, then MUSIC range and velocity spectra from
  * H = rxGrid(:,:,1).*conj(txGrid(:,:,1)).  The K x K eigenproblem of Rr = H H'/nSym (music2D.m:71,77) is solved
  * through the nSym x nSym Gram matrix H'H (same non-zero spectrum; the signal vectors are H v / sqrt(K mu)), so a

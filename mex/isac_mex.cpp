@@ -189,15 +189,16 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     if (it != g_arrays.end()) { check(isac_dev_free(ctx(), it->second.p)); g_arrays.erase(it); }
   // ------------------------------------------------------------------ context preparation
   } else if (fn == "setOption") {
-    // isac_mex('setOption', name, value): 'musicRoute' | 'tailFusion' | 'wideOrder' | 'cdlShareSpectra' -> isac_ctx_set_option (include/isac.h: per-context algorithm switches;
-    // 'cdlShareSpectra' = 1 lets consecutive applyCDLBatch calls on the same waveform handles share their forward transforms)
+    // isac_mex('setOption', name, value): 'musicRoute' | 'tailFusion' | 'wideOrder' | 'cdlShareSpectra' | 'upaDoA' -> isac_ctx_set_option (include/isac.h: per-context
+    // algorithm switches; 'cdlShareSpectra' = 1 lets consecutive applyCDLBatch calls on the same waveform handles share their forward transforms; 'upaDoA' = 1 gives a UPA
+    // its angles through the 2-D scan and find2DPeaks instead of ISAC:UNSUPPORTED)
     if (nrhs < 3) mexErrMsgIdAndTxt("isac:INVALID_ARG", "usage: isac_mex('setOption', name, value)");
     char* nm = mxArrayToString(prhs[1]);
     const std::string name = nm ? nm : "";
     mxFree(nm);
     int opt = -1;
     if (name == "musicRoute") opt = ISAC_OPT_MUSIC_ROUTE; else if (name == "tailFusion") opt = ISAC_OPT_TAIL_FUSION; else if (name == "wideOrder") opt = ISAC_OPT_WIDE_ORDER;
-    else if (name == "cdlShareSpectra") opt = ISAC_OPT_CDL_SHARE_SPECTRA;
+    else if (name == "cdlShareSpectra") opt = ISAC_OPT_CDL_SHARE_SPECTRA; else if (name == "upaDoA") opt = ISAC_OPT_UPA_DOA;
     if (opt < 0) mexErrMsgIdAndTxt("isac:INVALID_ARG", "setOption: unknown option name");
     check(isac_ctx_set_option(ctx(), opt, (int32_t)mxGetScalar(prhs[2])));
   } else if (fn == "reserve") {
