@@ -7,21 +7,13 @@
 #include <mutex>
 #include <numeric>
 
-#include "isac_common.hpp"
+#include "isac_internal.hpp"
 
 using namespace isac;
 
-// kernels / stages implemented in the other translation units
-int isac_rdm_power_window(isac_ctx* ctx, const isac_est_params* ep, const isac_cfar_config* cf, const c64* d_rx, const c64* d_tx,
-                          int K, int L, int A, int* nr_out, int* nc_out, bool use_cached_range);
-int isac_cfar_window(isac_ctx* ctx, const isac_est_params* ep, const isac_cfar_config* cf, int nr, int nc, int A, int cap);
-int isac_eigh_dev(isac_ctx* ctx, const c64* d_H, int A, hipStream_t st, bool live_replay = true);
-// status word the device eigensolver leaves behind the eigenvalues (ctx->eig_w [A] | info[0..5]): negative = the QL
-// recurrence ran out of rotation storage (-1) or a replay block gave up waiting (-2).  Call after the stream is idle.
-int isac_eigh_replay_recover(isac_ctx* ctx, int n, hipStream_t st);   // music.hip
 static int eig_status(isac_ctx* ctx, int A, bool ql_ran = true /* false: the signal-subspace kernel delivered, the QL pipeline returned at once */) {
   int sweeps = 0;
-  ISAC_TRY(copy_d2h(ctx, &sweeps, (const char*)ctx->eig_w.p + sizeof(double) * (size_t)A, sizeof(int)));
+  ISAC_TRY(copy_d2h(ctx, &sweeps, eig_info(ctx, A), sizeof(int)));
   static const bool force = std::getenv("ISAC_EIG_FORCE_REPLAY_TIMEOUT") != nullptr;   // test hook: take the recovery path on every call ...
   if (force && ql_ran && sweeps >= 0 && A > 16 && ctx->eig_scratch.p) {
     ISAC_HIP(hipMemset(ctx->eig_v.p, 0xFF, sizeof(c64) * (size_t)A * A));               // ... with the eigenvectors destroyed first
@@ -30,7 +22,7 @@ static int eig_status(isac_ctx* ctx, int A, bool ql_ran = true /* false: the sig
   if (sweeps == -2) {                                // live replay blocks gave up waiting: Z and the rotations are intact, replay them offline
     ISAC_TRY(isac_eigh_replay_recover(ctx, A, ctx->stream));
     ISAC_HIP(hipStreamSynchronize(ctx->stream));
-    ISAC_TRY(copy_d2h(ctx, &sweeps, (const char*)ctx->eig_w.p + sizeof(double) * (size_t)A, sizeof(int)));
+    ISAC_TRY(copy_d2h(ctx, &sweeps, eig_info(ctx, A), sizeof(int)));
   }
   if (sweeps < 0) return isac::fail(ctx, ISAC_ERR_HIP, sweeps == -1 ? "eigensolver: QL recurrence exceeded its rotation storage (no convergence)"
                                                      : sweeps == -3 ? "eigensolver: the signal-subspace vectors are not finite (NaN / Inf in the covariance)"
@@ -38,22 +30,6 @@ static int eig_status(isac_ctx* ctx, int A, bool ql_ran = true /* false: the sig
                                                                      : "eigensolver: a replay block timed out waiting for the recurrence");
   return ISAC_OK;
 }
-int isac_music_scan_dev(isac_ctx* ctx, int A, const int* d_num_dets, int num_dets_host, const double* d_sind, int n_steps,
-                        double d_ratio, double* d_spec, hipStream_t st, int mode = 0, const int* ctl = nullptr);
-// MUSIC's signal-subspace eigensolver (music.hip): usable for this order?  first half (before numDets), second half (after), its control block
-bool isac_music_subspace_ok(isac_ctx* ctx, int A);
-int isac_music_tridiag_bisect_dev(isac_ctx* ctx, const c64* d_H, int A, hipStream_t st);
-int isac_music_subspace_dev(isac_ctx* ctx, int A, const int* d_num_dets, int num_dets_host, hipStream_t st);
-const int* isac_music_ctl(isac_ctx* ctx);
-int isac_covariance_on(isac_ctx* ctx, hipStream_t st, const isac_c64* d_grid, int64_t N, int32_t A, isac_c64* d_Ra);
-int isac_covariance_lazy_on(isac_ctx* ctx, hipStream_t st, isac_c64* d_Ra);   // music.hip: Ra of the context's native lazy echo grid
-// UPA DoA (doa2d.hip): the 2-D scan, the column normalisation + peak candidates, the host half of find2DPeaks
-int isac_doa2d_peak_cap(int rows, int cols);
-int isac_doa2d_cand_doubles(int cap);
-int isac_doa2d_scan_dev(isac_ctx* ctx, int mode, int nV, int nH, int eS, int aS, const double* d_tab, const int* d_num_dets, int num_dets_host,
-                        const int* ctl, hipStream_t st);
-int isac_doa2d_norm_peaks_dev(isac_ctx* ctx, bool normalise, const double* d_db, int rows, int cols, double* d_cand, int cap, hipStream_t st);
-int isac_doa2d_select(isac_ctx* ctx, const double* cand, int count, int cap, int rows, int L, std::vector<int>& ele, std::vector<int>& azi);
 
 namespace {
 
@@ -142,7 +118,7 @@ int determine_num_targets(const std::vector<double>& v_ascending) {  // music.m:
 
 int upload(isac_ctx* ctx, DevBuf& b, const void* src, size_t bytes) {
   ISAC_TRY(ensure(ctx, b, bytes));
-  ISAC_TRY(upload_now(ctx, b.p, src, bytes));         // (not hipMemcpy: see upload_now)
+  ISAC_TRY(copy_h2d(ctx, b.p, src, bytes));           // (not hipMemcpy: see copy_h2d)
   return ISAC_OK;
 }
 
@@ -227,7 +203,6 @@ int isac_get_twiddles(isac_ctx* ctx, int n, const c64** out) {
   *out = (const c64*)it->second.p;
   return ISAC_OK;
 }
-int isac_get_twiddles2(isac_ctx* ctx, int n, const c64** out) { return isac_get_twiddles(ctx, n, out); }
 
 // {W512^0..511, W4096^0..7}: the LDS tables of Fft4096W in one contiguous run (bit-identical to entries 8 i / i of the 4096 table)
 int isac_get_w512_pack(isac_ctx* ctx, const c64** out) {
@@ -758,7 +733,7 @@ static int fft2d_submit(isac_ctx* ctx, const isac_est_params* ep, const isac_cfa
   hipLaunchKernelGGL(pack_kernel, dim3(1), dim3(256), 0, ctx->stream, (const int*)ctx->det_cnt.p, (const int*)ctx->det_cut.p,
                      (const double*)ctx->det_pow.p, (const int*)ctx->misc.p, A, cap, (int*)dbase, d_pcut_full, d_ppow_full,
                      pack_first, d_pcut_first, d_ppow_first, upa2d ? (const double*)ctx->doa2d_cand.p : (const double*)ctx->spec.p, n_spec,
-                     (double*)(dbase + off_spec), (upa && !upa2d) ? nullptr : (const int*)((const char*)ctx->eig_w.p + sizeof(double) * (size_t)A));
+                     (double*)(dbase + off_spec), (upa && !upa2d) ? nullptr : eig_info(ctx, A));
   ISAC_HIP(hipGetLastError());
   char* h = (char*)ctx->pinned;
   ISAC_HIP(hipMemcpyAsync(h, dbase, first_bytes, hipMemcpyDeviceToHost, ctx->stream));
@@ -961,7 +936,7 @@ extern "C" int isac_fft2d(isac_ctx* ctx, const isac_est_params* ep, const isac_c
   ISAC_HIP(hipMalloc(&d_rx, bytes));
   if (hipMalloc(&d_tx, bytes) != hipSuccess) { (void)hipFree(d_rx); return fail(ctx, ISAC_ERR_HIP, "hipMalloc failed"); }
   int st = ISAC_OK;
-  if (upload_now(ctx, d_rx, rx_grid, bytes) != ISAC_OK || upload_now(ctx, d_tx, tx_grid, bytes) != ISAC_OK)      // (on the context's stream and waited for: see upload_now)
+  if (copy_h2d(ctx, d_rx, rx_grid, bytes) != ISAC_OK || copy_h2d(ctx, d_tx, tx_grid, bytes) != ISAC_OK)      // (on the context's stream and waited for: see copy_h2d)
     st = fail(ctx, ISAC_ERR_HIP, "host->device copy failed");
   if (st == ISAC_OK) st = isac_fft2d_dev(ctx, ep, cfar, (const isac_c64*)d_rx, (const isac_c64*)d_tx, K, L, A, out);
   (void)hipStreamSynchronize(ctx->stream);
@@ -1032,7 +1007,7 @@ extern "C" int isac_eigh(isac_ctx* ctx, const isac_c64* H, int32_t A, double* w,
   ISAC_TRY(eig_status(ctx, A));
   if (std::getenv("ISAC_DEBUG")) {                 // diagnostic: eigensolver phase counters on stderr
     int inf[16] = {-1, 0, 0, 0, 0, 0};
-    ISAC_TRY(copy_d2h(ctx, inf, (char*)ctx->eig_w.p + sizeof(double) * (size_t)A, sizeof(inf)));
+    ISAC_TRY(copy_d2h(ctx, inf, eig_info(ctx, A), sizeof(inf)));
     if (A > 64 && A <= 256)
       std::fprintf(stderr, "[isac] eigh A=%d distributed tridiagonalisation, phases(x64 clk): column + p published=%d exchange wait=%d vector work=%d rank-2 update=%d\n", A,
                    inf[12], inf[13], inf[14], inf[15]);
@@ -1147,7 +1122,7 @@ extern "C" int isac_eigh_top(isac_ctx* ctx, const isac_c64* H, int32_t A, int32_
   ISAC_TRY(eig_status(ctx, A, ctl[0] != 1));
   if (std::getenv("ISAC_DEBUG")) {                 // diagnostic: eigensolver phase counters on stderr
     int inf[15] = {0};
-    ISAC_TRY(copy_d2h(ctx, inf, (char*)ctx->eig_w.p + sizeof(double) * (size_t)A, sizeof(inf)));
+    ISAC_TRY(copy_d2h(ctx, inf, eig_info(ctx, A), sizeof(inf)));
     std::fprintf(stderr, "[isac] eigh_top A=%d n_top=%d phases(x64 clk): tridiag=%d (n <= 64: reflector=%d matvec=%d matvec+update=%d) | subspace: set-up=%d solves=%d "
                  "gram-schmidt=%d back-transform=%d\n", A, n_top, inf[1], inf[12], inf[13], inf[14], inf[8], inf[9], inf[10], inf[11]);
   }
@@ -1256,7 +1231,6 @@ hipEvent_t isac::timeline_base(hipStream_t st) {
   return base;
 }
 
-
 extern "C" int isac_music_doa(isac_ctx* ctx, int32_t num_dets, const isac_est_params* ep, const isac_c64* Ra, int32_t A,
                               int32_t* L_out, double* azi_est, double* ele_est, int32_t cap, int32_t* n_est) {
   return doa_scan(ctx, 0, num_dets, ep, Ra, A, L_out, azi_est, ele_est, cap, n_est);
@@ -1308,10 +1282,6 @@ extern "C" int isac_find2d_peaks(isac_ctx* ctx, const double* p_db, int32_t rows
 }
 
 // ------------------------------------------------------------------ music2D (music2D.m:1-123)
-int isac_music2d_plane(isac_ctx* ctx, const c64* d_rx, const c64* d_tx, long long n, c64* d_h);
-int isac_music2d_signal_vectors(isac_ctx* ctx, const c64* d_h, int K, int Ls, const int* d_top, int Lsig, c64* d_U);
-int isac_music2d_scan(isac_ctx* ctx, const c64* d_U, int N, int ldU, const int* d_cols, int Lsig, int conj_u, double coef, double den,
-                      double x0, double dx, int n_steps, double* d_p);
 
 extern "C" int isac_music2d_dev(isac_ctx* ctx, const isac_est_params* ep, const isac_music2d_params* mp, const isac_c64* d_rx_grid,
                                 const isac_c64* d_tx_grid, int32_t K, int32_t L, int32_t A, isac_est_result* out) {
@@ -1412,10 +1382,10 @@ extern "C" int isac_basic_radar_channel(isac_ctx* ctx, const isac_c64* tx_wave, 
   int st = ISAC_OK;
   if (hipMalloc(&d_tx, bytes) != hipSuccess || hipMalloc(&d_rx, bytes) != hipSuccess) st = fail(ctx, ISAC_ERR_HIP, "hipMalloc failed");
   if (st == ISAC_OK && noise_mode == ISAC_NOISE_INJECTED && noise_unit) {
-    if (hipMalloc(&d_nz, bytes) != hipSuccess || upload_now(ctx, d_nz, noise_unit, bytes) != ISAC_OK)
+    if (hipMalloc(&d_nz, bytes) != hipSuccess || copy_h2d(ctx, d_nz, noise_unit, bytes) != ISAC_OK)
       st = fail(ctx, ISAC_ERR_HIP, "noise upload failed");
   }
-  if (st == ISAC_OK && upload_now(ctx, d_tx, tx_wave, bytes) != ISAC_OK) st = fail(ctx, ISAC_ERR_HIP, "upload failed");
+  if (st == ISAC_OK && copy_h2d(ctx, d_tx, tx_wave, bytes) != ISAC_OK) st = fail(ctx, ISAC_ERR_HIP, "upload failed");
   if (st == ISAC_OK)
     st = isac_basic_radar_channel_dev(ctx, (const isac_c64*)d_tx, T, rp, los, noise_mode, (const isac_c64*)d_nz, seed, (isac_c64*)d_rx);
   if (st == ISAC_OK && copy_d2h(ctx, rx_wave, d_rx, bytes) != ISAC_OK)
@@ -1440,10 +1410,10 @@ extern "C" int isac_mono_static_sensing(isac_ctx* ctx, const isac_c64* tx_wave, 
   if (hipMalloc(&d_tx, wbytes) != hipSuccess || hipMalloc(&d_g, gbytes) != hipSuccess) st = fail(ctx, ISAC_ERR_HIP, "hipMalloc failed");
   if (st == ISAC_OK && (noise_mode == ISAC_NOISE_INJECTED || noise_mode == ISAC_NOISE_INJECTED_SPECTRAL) && noise_unit) {
     const size_t nbytes = noise_mode == ISAC_NOISE_INJECTED ? wbytes : gbytes;   // [T x A] samples or [n_sc x L_out x A] grid elements
-    if (hipMalloc(&d_nz, nbytes) != hipSuccess || upload_now(ctx, d_nz, noise_unit, nbytes) != ISAC_OK)
+    if (hipMalloc(&d_nz, nbytes) != hipSuccess || copy_h2d(ctx, d_nz, noise_unit, nbytes) != ISAC_OK)
       st = fail(ctx, ISAC_ERR_HIP, "noise upload failed");
   }
-  if (st == ISAC_OK && upload_now(ctx, d_tx, tx_wave, wbytes) != ISAC_OK) st = fail(ctx, ISAC_ERR_HIP, "upload failed");
+  if (st == ISAC_OK && copy_h2d(ctx, d_tx, tx_wave, wbytes) != ISAC_OK) st = fail(ctx, ISAC_ERR_HIP, "upload failed");
   if (st == ISAC_OK)
     st = isac_mono_static_sensing_dev(ctx, (const isac_c64*)d_tx, T, tx_dim_l, carrier, rp, los, noise_mode,
                                       (const isac_c64*)d_nz, seed, (isac_c64*)d_g, l_out);

@@ -20,7 +20,7 @@
 #include <type_traits>
 #include <vector>
 
-#include "isac_common.hpp"
+#include "isac_internal.hpp"
 
 namespace isac {
 
@@ -939,13 +939,6 @@ int launch_fused_ul(isac_ctx* ctx, const std::vector<CdlSeg>& segs, long long T,
   return ISAC_OK;
 }
 
-}  // namespace
-// cdl_os.hip: the downlink apply in the frequency domain (overlap-save, 4096-point windows) for long waveforms into two receive elements
-bool cdl_os_ok(long long T, int Nt, int Nr, int n_paths, int n_taps, int max_shift);
-bool cdl_os_ul_ok(long long T, int Nt, int Nr, int n_paths, int n_taps, int max_shift);   // uplink: one or two transmit elements into many receive elements
-int cdl_os_apply(isac_ctx* ctx, const isac_cdl_job* jobs, int n_jobs, long long T, int Nt, int Nr, int n_paths, const double* taps, int n_taps, const int32_t* shift, int max_shift,
-                 double out_scale);
-namespace {
 
 int cdl_apply_jobs(isac_ctx* ctx, const isac_cdl_job* jobs, int n_jobs, long long T, int Nt, int Nr, int n_paths, const double* taps, int n_taps,
                    const int32_t* shift, double out_scale) {

@@ -26,10 +26,8 @@
 #include <map>
 #include <vector>
 
+#include "isac_internal.hpp"
 #include "fft_lds.hpp"
-
-int isac_get_twiddles(isac_ctx* ctx, int n, const isac::c64** out);  // capi.hip
-int isac_get_w512_pack(isac_ctx* ctx, const isac::c64** out);        // capi.hip
 
 namespace isac {
 

@@ -5,7 +5,7 @@
 // M = G^H G + sigma^2 I, Gauss-Jordan inverse in registers, sinr = sum_l 1/(sigma^2 (M^-1)_ll) - 1.
 #include <cstring>
 
-#include "isac_common.hpp"
+#include "isac_internal.hpp"
 
 namespace isac {
 

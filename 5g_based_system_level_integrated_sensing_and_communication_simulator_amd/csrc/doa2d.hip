@@ -6,7 +6,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "isac_common.hpp"
+#include "isac_internal.hpp"
 
 using namespace isac;
 
@@ -16,8 +16,8 @@ constexpr int kThreads = 256;
 constexpr int kCandHdr = 2;          // doubles in front of the candidate pairs: [0] holds the 32-bit candidate counter
 constexpr double kD = 0.5;           // element spacing / wavelength (music.m:12)
 
-// the L signal vectors of music_subspace_kernel are delivered when ctl[0] == 1 (ctl[1] of them); same block as music.hip's MusicCtl
-__device__ __forceinline__ bool subspace_delivered(const int* ctl) { return ctl && ctl[0] == 1; }
+// the L signal vectors of music_subspace_kernel are delivered when ctl[kRoute] == 1 (ctl[kLsub] of them)
+__device__ __forceinline__ bool subspace_delivered(const int* ctl) { return ctl && ctl[MusicCtl::kRoute] == 1; }
 
 // per-eigenpair weight: MUSIC (mode 0) 1 for the noise subspace (descending rank >= L, ties in index order, as music_scan_kernel),
 // 0 for the signal subspace; DBF (mode 1) lambda; MVDR (mode 2) 1 / lambda
@@ -77,7 +77,7 @@ __global__ __launch_bounds__(kThreads) void doa2d_scan_kernel(const double* __re
   __syncthreads();
   double t_out = 0.0;
   if (mode == 0 && subspace_delivered(ctl)) {
-    const int Ls = ctl[1];
+    const int Ls = ctl[MusicCtl::kLsub];
     if (Ls < A) {                                                    // (Ls >= A: empty noise space, the quadratic form is 0)
       const int pg = tid % PG, vg = tid / PG, i0 = 4 * vg;
       if (i0 < Ls) {

@@ -19,6 +19,7 @@
 #include <cstring>
 #include <type_traits>
 
+#include "isac_internal.hpp"
 #include "fft_lds.hpp"
 #include "echo_dev.hpp"
 
@@ -306,7 +307,7 @@ __global__ __launch_bounds__(Fft4096W::NT, kEchoRangeWavesPerSimd) void echo_ran
 // stores of the group before -- and neither sched_barrier nor a compiler fence holds it.  With three or four targets the straight-line form
 // holds 2 x GROUP x (6 + 4 Q) load registers beside the generator and spills: those counts stay on the kernel above, as measured.)
 // STORE = false (round 6, "lazy" echo grid: isac_mono_static_sensing_fused_dev with d_echo_grid == NULL): the echoGrid store is left out -- the grid is a function of (D, a, seed)
-// that the covariance kernel re-forms for itself (cov_lazy_kernel, music.hip), so that 0.75 GB written here and 0.75 GB read back there per CPI never cross the HBM.
+// that the covariance kernel re-forms for itself (cov_lazy_kernel, cov.hip), so that 0.75 GB written here and 0.75 GB read back there per CPI never cross the HBM.
 template <int QT, int NZ, bool STORE = true, int GROUP = (QT <= 1 ? 4 : 2)>
 __global__ __launch_bounds__(Fft4096W::NT, kEchoRangeWavesPerSimd) void echo_range_sl_kernel(int K, int L_whole, int L_out, int A, const c64* D,
                                                             const c64* __restrict__ steer_rq, double sig, uint64_t seed,
@@ -505,10 +506,6 @@ __global__ __launch_bounds__(256) void synth_qpsk_kernel(c64* __restrict__ grid,
 
 // ================================================================= host side
 using namespace isac;
-
-int isac_get_twiddles(isac_ctx* ctx, int n, const c64** out);  // capi.hip
-int isac_get_logtab(isac_ctx* ctx, const c64** out);           // capi.hip
-int isac_get_w512_pack(isac_ctx* ctx, const c64** out);        // capi.hip
 
 static int check_carrier(isac_ctx* ctx, const isac_carrier* c) {
   if (!c) return fail(ctx, ISAC_ERR_INVALID_ARG, "carrier is NULL");
@@ -759,10 +756,6 @@ extern "C" int isac_mono_static_sensing_dev(isac_ctx* ctx, const isac_c64* d_tx_
   return ISAC_OK;
 }
 
-int isac_get_windows(isac_ctx* ctx, int K, int n_ifft, const double** win_k, const double** win_r);   // capi.hip
-
-int isac_range_stage_into_cache(isac_ctx* ctx, const isac_est_params* ep, const isac_cfar_config* cf, const c64* d_rx, const c64* d_tx, int K, int L, int A);   // rdm.hip
-
 extern "C" int isac_mono_static_sensing_fused_dev(isac_ctx* ctx, const isac_c64* d_tx_wave, int64_t T, int32_t tx_dim_l,
                                                   const isac_carrier* carrier, const isac_radar_channel_params* rp,
                                                   const uint8_t* los, int noise_mode, const isac_c64* d_noise_unit,
@@ -942,8 +935,6 @@ extern "C" int isac_ofdm_demodulate_dev(isac_ctx* ctx, const isac_c64* d_wave, i
                                                                (const c64*)d_wave, (c64*)d_grid))));
   return ISAC_OK;
 }
-
-int isac_get_rise_window(isac_ctx* ctx, int n_win, const double** out);   // capi.hip
 
 template <class FFT>
 static int launch_mod(isac_ctx* ctx, const OfdmGeom& g, const ModIo& io, int A, int L, const c64* tw, const c64* grid,

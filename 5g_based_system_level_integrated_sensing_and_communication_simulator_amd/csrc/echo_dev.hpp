@@ -148,7 +148,7 @@ __device__ __forceinline__ c64 box_muller32_hw(uint32_t ur, uint32_t ua) {
   return c64{(double)(rad * __builtin_amdgcn_cosf(turns)), (double)(rad * __builtin_amdgcn_sinf(turns))};
 }
 
-// The same transform with the two products still in single precision (what box_muller32_hw widens): the lazy covariance kernel (music.hip) keeps the unit noise of a slab in
+// The same transform with the two products still in single precision (what box_muller32_hw widens): the lazy covariance kernel (cov.hip) keeps the unit noise of a slab in
 // flight as floats -- (double)re, (double)im are bit for bit box_muller32_hw's result.
 __device__ __forceinline__ void box_muller32_hw_f32(uint32_t ur, uint32_t ua, float& re, float& im) {
   const float u = __builtin_fmaf((float)ur, 0x1.0p-32f, 0x1.0p-33f);

@@ -200,18 +200,6 @@ inline int allow_lds(isac_ctx* ctx, const void* kernel, size_t bytes) {
   return ISAC_OK;
 }
 
-hipEvent_t timeline_base(hipStream_t st);   // capi.hip
-inline void timeline_mark(isac_ctx* ctx, int i, hipStream_t st) {
-  static const bool on = std::getenv("ISAC_TIMELINE") != nullptr;   // diagnostic: per-stage event timeline
-  if (!on) return;
-  if (!ctx->tl_on) {
-    for (auto& e : ctx->tl) (void)hipEventCreate(&e);
-    ctx->tl_on = true;
-    (void)timeline_base(st);
-  }
-  (void)hipEventRecord(ctx->tl[i], st);
-}
-
 #define ISAC_HIP(call)                                                                     \
   do {                                                                                     \
     hipError_t e__ = (call);                                                               \
@@ -331,7 +319,6 @@ inline int copy_d2h(isac_ctx* ctx, void* dst, const void* src, size_t bytes) {  
   for (int h = 0; h < 2; ++h) if (pend_n[h]) std::memcpy((char*)dst + pend_off[h], (char*)ctx->bounce + (size_t)h * kBounceChunk, pend_n[h]);
   return ISAC_OK;
 }
-inline int upload_now(isac_ctx* ctx, void* dst, const void* src, size_t bytes) { return copy_h2d(ctx, dst, src, bytes); }
 
 // Small host block -> device scratch through the context's pinned staging ring: asynchronous, no stream synchronisation; the host waits only when the
 // ring wraps onto a slot whose copy has not left it yet.  stage_acquire hands out the next slot's host memory, stage_commit enqueues its copy.

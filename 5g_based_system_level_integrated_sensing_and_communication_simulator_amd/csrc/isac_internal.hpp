@@ -1,0 +1,82 @@
+// The interface between the translation units of libisac_hip: every function that one .hip file defines and another calls is declared here, once (default arguments
+// included), and every .hip file includes this header -- the defining unit too, so the compiler sees both.  extern "C" entry points: include/isac.h, not here.
+#pragma once
+#include "isac_common.hpp"
+
+// ---------------------------------------------------------------- capi.hip: cached device tables
+int isac_get_twiddles(isac_ctx* ctx, int n, const isac::c64** out);
+int isac_get_w512_pack(isac_ctx* ctx, const isac::c64** out);
+int isac_get_logtab(isac_ctx* ctx, const isac::c64** out);
+int isac_get_rise_window(isac_ctx* ctx, int n_win, const double** out);
+int isac_get_windows(isac_ctx* ctx, int K, int n_ifft, const double** win_k, const double** win_r);
+// ---------------------------------------------------------------- rdm.hip
+int isac_rdm_power_window(isac_ctx* ctx, const isac_est_params* ep, const isac_cfar_config* cf, const isac::c64* d_rx, const isac::c64* d_tx, int K, int L, int A, int* nr_out, int* nc_out, bool use_cached_range);
+int isac_cfar_window(isac_ctx* ctx, const isac_est_params* ep, const isac_cfar_config* cf, int nr, int nc, int A, int cap);
+int isac_range_stage_into_cache(isac_ctx* ctx, const isac_est_params* ep, const isac_cfar_config* cf, const isac::c64* d_rx, const isac::c64* d_tx, int K, int L, int A);
+// ---------------------------------------------------------------- cov.hip
+int isac_covariance_on(isac_ctx* ctx, hipStream_t st, const isac_c64* d_grid, int64_t N, int32_t A, isac_c64* d_Ra);
+int isac_covariance_lazy_on(isac_ctx* ctx, hipStream_t st, isac_c64* d_Ra);   // Ra of the context's native lazy echo grid
+// ---------------------------------------------------------------- music.hip
+// device eig: H [A x A] (device) -> ctx->eig_w [A], ctx->eig_v [A x A] (unsorted); live_replay: see the definition
+int isac_eigh_dev(isac_ctx* ctx, const isac::c64* d_H, int A, hipStream_t st, bool live_replay = true);
+int isac_eigh_replay_recover(isac_ctx* ctx, int n, hipStream_t st);
+// MUSIC's signal-subspace eigensolver: usable for this order?  first half (before numDets), second half (after), its control block
+bool isac_music_subspace_ok(isac_ctx* ctx, int A);
+int isac_music_tridiag_bisect_dev(isac_ctx* ctx, const isac::c64* d_H, int A, hipStream_t st);
+int isac_music_subspace_dev(isac_ctx* ctx, int A, const int* d_num_dets, int num_dets_host, hipStream_t st);
+const int* isac_music_ctl(isac_ctx* ctx);
+int isac_music_scan_dev(isac_ctx* ctx, int A, const int* d_num_dets, int num_dets_host, const double* d_sind, int n_steps, double d_ratio, double* d_spec, hipStream_t st, int mode = 0, const int* ctl = nullptr);
+// music2D stages (host side: capi.hip)
+int isac_music2d_plane(isac_ctx* ctx, const isac::c64* d_rx, const isac::c64* d_tx, long long n, isac::c64* d_h);
+int isac_music2d_signal_vectors(isac_ctx* ctx, const isac::c64* d_h, int K, int Ls, const int* d_top, int Lsig, isac::c64* d_U);
+int isac_music2d_scan(isac_ctx* ctx, const isac::c64* d_U, int N, int ldU, const int* d_cols, int Lsig, int conj_u, double coef, double den, double x0, double dx, int n_steps, double* d_p);
+// ---------------------------------------------------------------- doa2d.hip: UPA DoA -- the 2-D scan, the column normalisation + peak candidates, the host half of find2DPeaks
+int isac_doa2d_peak_cap(int rows, int cols);
+int isac_doa2d_cand_doubles(int cap);
+int isac_doa2d_scan_dev(isac_ctx* ctx, int mode, int nV, int nH, int eS, int aS, const double* d_tab, const int* d_num_dets, int num_dets_host, const int* ctl, hipStream_t st);
+int isac_doa2d_norm_peaks_dev(isac_ctx* ctx, bool normalise, const double* d_db, int rows, int cols, double* d_cand, int cap, hipStream_t st);
+int isac_doa2d_select(isac_ctx* ctx, const double* cand, int count, int cap, int rows, int L, std::vector<int>& ele, std::vector<int>& azi);
+// ---------------------------------------------------------------- cdl_os.hip: the CDL apply in the frequency domain (overlap-save, 4096-point windows) for long waveforms
+bool cdl_os_ok(long long T, int Nt, int Nr, int n_paths, int n_taps, int max_shift);      // downlink: into two receive elements
+bool cdl_os_ul_ok(long long T, int Nt, int Nr, int n_paths, int n_taps, int max_shift);   // uplink: one or two transmit elements into many receive elements
+int cdl_os_apply(isac_ctx* ctx, const isac_cdl_job* jobs, int n_jobs, long long T, int Nt, int Nr, int n_paths, const double* taps, int n_taps, const int32_t* shift, int max_shift, double out_scale);
+
+// Status words the device eigensolver leaves behind the eigenvalues (ctx->eig_w [A] | info[0..6]).  info[0] negative: the QL recurrence ran out of rotation storage (-1), a live replay
+// block gave up waiting (-2; isac_eigh_replay_recover, once the stream is idle), the signal-subspace vectors are not finite (-3), the distributed tridiagonalisation saw no progress (-4; sticky in info[6]).
+inline int* eig_info(isac_ctx* ctx, int A) { return reinterpret_cast<int*>((char*)ctx->eig_w.p + sizeof(double) * (size_t)A); }
+namespace isac {
+hipEvent_t timeline_base(hipStream_t st);   // capi.hip
+inline void timeline_mark(isac_ctx* ctx, int i, hipStream_t st) {
+  static const bool on = std::getenv("ISAC_TIMELINE") != nullptr;   // diagnostic: per-stage event timeline
+  if (!on) return;
+  if (!ctx->tl_on) {
+    for (auto& e : ctx->tl) (void)hipEventCreate(&e);
+    ctx->tl_on = true;
+    (void)timeline_base(st);
+  }
+  (void)hipEventRecord(ctx->tl[i], st);
+}
+
+struct MusicCtl { enum { kRoute = 0, kLsub = 1 }; };     // MUSIC's control block (isac_music_ctl): ctl[kRoute]: 1 = subspace vectors delivered (kLsub of them; >= n: empty noise space)
+
+// Sum over the 64 lanes of a wavefront through DPP row operations (quad_perm, row_ror, row_bcast15 / 31 + one readlane): six short VALU
+// steps.  The __shfl_xor butterfly goes through the LDS crossbar (ds_bpermute: ~100 cycles per step, six dependent steps) -- for the
+// one-reduction-per-Householder-step kernels of music.hip that latency WAS the kernel (two of them per reflector: 37 of the 83 us of the subspace
+// kernel at n = 64).  Returns the total in every lane (wave-uniform).
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ double dpp_move(double x) {
+  const int lo = __double2loint(x), hi = __double2hiint(x);
+  const int l2 = __builtin_amdgcn_update_dpp(0, lo, CTRL, ROW_MASK, 0xf, false);    // rows outside ROW_MASK receive 0: the add leaves them unchanged
+  const int h2 = __builtin_amdgcn_update_dpp(0, hi, CTRL, ROW_MASK, 0xf, false);
+  return __hiloint2double(h2, l2);
+}
+__device__ __forceinline__ double wave_sum_dpp(double x) {
+  x += dpp_move<0xB1, 0xf>(x);                       // quad_perm [1,0,3,2]
+  x += dpp_move<0x4E, 0xf>(x);                       // quad_perm [2,3,0,1]
+  x += dpp_move<0x124, 0xf>(x);                      // row_ror:4
+  x += dpp_move<0x128, 0xf>(x);                      // row_ror:8   -> every lane: the sum of its row of 16
+  x += dpp_move<0x142, 0xa>(x);                      // row_bcast15 -> rows 1, 3 += rows 0, 2
+  x += dpp_move<0x143, 0xc>(x);                      // row_bcast31 -> rows 2, 3 += rows 0 + 1: lane 63 holds the total
+  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(x), 63), __builtin_amdgcn_readlane(__double2loint(x), 63));
+}
+}  // namespace isac

@@ -5,7 +5,7 @@
 // One thread per (link, wall) pair, walls fastest so that a wavefront shares its link and streams the wall table
 // (a few hundred KB, L2 resident); blocked links are flagged with one atomicOr.  fp64 throughout; the decision
 // |sum of angles| > 0.1 separates ~0 from ~2*pi, so it does not depend on the last bits of atan2.
-#include "isac_common.hpp"
+#include "isac_internal.hpp"
 
 namespace isac {
 

@@ -1,1172 +1,11 @@
-// Array covariance on fp64 MFMA, Hermitian eigendecomposition and MUSIC angle scan (gfx950).
-//
+// Hermitian eigendecomposition and MUSIC angle scan (gfx950).  The array covariance they consume: cov.hip.
 // Reference path: fft2D.m:106-111 -> doaEstimation.music (+sensing/+estimation/+doaEstimation/music.m).
-//   Ra   = X*X'/N,  X = reshape(rxGrid, N, A)'   -- the ' is a CONJUGATE transpose, so
-//   Ra[a,b] = (1/N) sum_n conj(G[n,a]) G[n,b],   G[n,a] = rxGrid(n + N*a)
 //   [Ua,Sa] = eig(Ra); descending sort; Uan = Ua(:,L+1:end); P(phi) = 1/(a' Uan Uan' a + eps)
-//
-// Covariance: each 16x16 output tile is a real-MFMA triple on v_mfma_f64_16x16x4_f64
-//   Re += Gr_I^T Gr_J + Gi_I^T Gi_J ,  Im += Gr_I^T Gi_J - Gi_I^T Gr_J
-// Only tiles I <= J are formed (Hermitian).  The long sample axis n is contiguous per
-// antenna column, so lane (i = lane&15, kq = lane>>4) streams 64 contiguous bytes
-// (4 complex samples) of column a0+i per macro-step and feeds them to 4 consecutive MFMA
-// k-steps; the k index is only a summation label, so no transposition is needed.
-// Per-workgroup partial tiles are reduced in a fixed order (deterministic).
-#include <type_traits>
-
 #include <algorithm>
 #include <atomic>
-#include "isac_common.hpp"
-#include "echo_dev.hpp"
+#include "isac_internal.hpp"
 
 namespace isac {
-
-typedef double v4f64 __attribute__((ext_vector_type(4)));
-
-
-__device__ __forceinline__ void tile_ij(int t, int nb, int& I, int& J) {
-  // t-th upper-triangular tile in row-major order
-  int i = 0;
-  int rem = t;
-  while (rem >= nb - i) { rem -= nb - i; ++i; }
-  I = i;
-  J = i + rem;
-}
-
-// Sum over the 64 lanes of a wavefront through DPP row operations (quad_perm, row_ror, row_bcast15 / 31 + one readlane): six short VALU
-// steps.  The __shfl_xor butterfly goes through the LDS crossbar (ds_bpermute: ~100 cycles per step, six dependent steps) -- for the
-// one-reduction-per-Householder-step kernels below that latency WAS the kernel (two of them per reflector: 37 of the 83 us of the subspace
-// kernel at n = 64).  Returns the total in every lane (wave-uniform).
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double dpp_move(double x) {
-  const int lo = __double2loint(x), hi = __double2hiint(x);
-  const int l2 = __builtin_amdgcn_update_dpp(0, lo, CTRL, ROW_MASK, 0xf, false);    // rows outside ROW_MASK receive 0: the add leaves them unchanged
-  const int h2 = __builtin_amdgcn_update_dpp(0, hi, CTRL, ROW_MASK, 0xf, false);
-  return __hiloint2double(h2, l2);
-}
-__device__ __forceinline__ double wave_sum_dpp(double x) {
-  x += dpp_move<0xB1, 0xf>(x);                       // quad_perm [1,0,3,2]
-  x += dpp_move<0x4E, 0xf>(x);                       // quad_perm [2,3,0,1]
-  x += dpp_move<0x124, 0xf>(x);                      // row_ror:4
-  x += dpp_move<0x128, 0xf>(x);                      // row_ror:8   -> every lane: the sum of its row of 16
-  x += dpp_move<0x142, 0xa>(x);                      // row_bcast15 -> rows 1, 3 += rows 0, 2
-  x += dpp_move<0x143, 0xc>(x);                      // row_bcast31 -> rows 2, 3 += rows 0 + 1: lane 63 holds the total
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(x), 63), __builtin_amdgcn_readlane(__double2loint(x), 63));
-}
-
-// ---- specialised schedule for A <= 64 (NB = ceil(A/16) <= 4 antenna blocks): every wave keeps ALL blocks'
-// operands of its samples in registers and owns a static group of <= 5 output tiles, so the four waves of a
-// workgroup issue exactly the same number of MFMAs (balanced SIMDs), and the next slab is prefetched under the
-// current slab's MFMAs.
-//   wave = (tile group g, sample phase p):  NB=4: 2 groups x 2 phases,  NB=3: 2 x 2,  NB=2: 1 x 4,  NB=1: 1 x 4
-//   phase p owns the contiguous samples [16 p / kPhases, 16 (p + 1) / kPhases) of a 16-sample slab -- at two phases one whole
-//   128-byte line per antenna, requested by the two tile groups of that phase only; lane (i = lane&15, kq = lane>>4) holds
-//   kSamplesPerLane consecutive samples of antenna 16 b + i in every block b.
-// Three real MFMAs per tile and k-step instead of four (3M / Gauss form, see cov_group_body): 30 instead of 40 per four samples
-// at A = 64.  Measured at A = 64 (733 824 samples): 4M, interleaved sample map, 3 workgroups per CU 276 us / 1.37 GB fetched;
-// 3M + line map, 2 workgroups per CU 209 us / 1.05 GB; + a workgroup barrier every 8 slabs 215 us / 0.73 GB (= the input, once).
-constexpr int kCovSyncSlabs = 8;                                // power of two (1, 2, 4: +3-9 %; 16 .. none: within the noise of 8 in per-workgroup spans)
-template <int NB>
-struct CovPlan {
-  static constexpr int kTiles = NB * (NB + 1) / 2;
-  static constexpr int kGroups = (kTiles + 4) / 5;              // <= 5 tiles per wave
-  static constexpr int kPerGroup = (kTiles + kGroups - 1) / kGroups;
-  static constexpr int kPhases = 4 / kGroups;                   // waves per workgroup = kGroups * kPhases = 4
-  static constexpr int kSamplesPerLane = 4 / kPhases;           // k-steps a wave runs per 16-sample slab
-};
-
-constexpr int cov_tile_i(int nb, int t) {
-  int i = 0;
-  while (t >= nb - i) { t -= nb - i; ++i; }
-  return i;
-}
-constexpr int cov_tile_j(int nb, int t) {
-  int i = 0;
-  while (t >= nb - i) { t -= nb - i; ++i; }
-  return i + t;
-}
-template <int U, int NT, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (U < NT) {
-    f(std::integral_constant<int, U>{});
-    static_for<U + 1, NT>(f);
-  }
-}
-
-template <int NB, int GRP, int NBUF = 3>
-__device__ __forceinline__ void cov_group_body(const c64* __restrict__ G, long long N, int A, int n_tiles, int phase, int lane,
-                                               long long s0, long long s_step, long long s_cnt, long long s_lim, int part_index,
-                                               double* __restrict__ part) {
-  // this wave's i-th slab (16 samples) is slab s0 + i s_step of the grid, i = 0 .. s_cnt - 1; slabs >= s_lim contribute nothing
-  using P = CovPlan<NB>;
-  constexpr int T0 = GRP * P::kPerGroup;
-  constexpr int NT = (T0 + P::kPerGroup <= P::kTiles) ? P::kPerGroup : (P::kTiles - T0);
-  constexpr int SPL = P::kSamplesPerLane;
-  const int li = lane & 15, kq = lane >> 4;
-  // 3M form: three real products per tile and k-step --
-  //   off-diagonal tile:  S1 += Gr_I Gr_J,  S2 += Gi_I Gi_J,  S3 += (Gr_I - Gi_I)(Gr_J + Gi_J)  =>  Re = S1 + S2,  Im = (S3 - S1) + S2
-  //   diagonal tile    :  Re += Gr Gr + Gi Gi,  M += Gr Gi  =>  Im = M - M^T, formed by the reducer (exactly antisymmetric)
-  // re = S1 (or Re), im = S2 (or M), s3 = S3 (off-diagonal tiles only; the unused ones are dead code).  The cancellation in Im is
-  // against terms of the size of the tile's own entries (|S1|, |S2| <~ |Re|): errors stay at a few ulp of the matrix norm.
-  v4f64 re[NT], im[NT], s3[NT];
-#pragma unroll
-  for (int u = 0; u < NT; ++u) re[u] = im[u] = s3[u] = v4f64{0.0, 0.0, 0.0, 0.0};
-  // One raw-buffer descriptor per 16-antenna block (uniform: scalar registers), ending with the array's last antenna: padding antennas read as
-  // zero by the bounds check, and per thread the address of all NB x SPL loads of a slab is ONE 32-bit offset (+ immediates) -- the 64-bit
-  // pointer arithmetic and index clamps of a pointer-per-block form were ~30 of the ~40 VALU instructions of a slab, every one of them paid in
-  // full beside the 30 v_mfma_f64 (MFMA and VALU do not co-issue).
-  __amdgpu_buffer_rsrc_t rs[NB];
-  bool colok[NB];
-#pragma unroll
-  for (int b = 0; b < NB; ++b) {
-    int n_ant = A - 16 * b;
-    n_ant = n_ant < 0 ? 0 : (n_ant > 16 ? 16 : n_ant);
-    colok[b] = li < n_ant;
-    rs[b] = buffer_of(G + N * (long long)(n_ant > 0 ? 16 * b : 0), (unsigned)(N * n_ant * (long long)sizeof(c64)));
-  }
-  const long long lane_off = (16 / P::kPhases) * phase + SPL * kq;   // first sample of this lane inside a slab (see above)
-  const unsigned lane_byte = (unsigned)((N * li + lane_off) * (long long)sizeof(c64));
-  // Loads are unconditional (clamped indices) and the out-of-range mask is applied when a slab is CONSUMED, not when it is loaded: a
-  // select at load time makes the compiler predicate the loads (branches + `s_waitcnt vmcnt(0)` before the MFMAs), a multiply at load time
-  // waits for the data right away -- either way the prefetch of the next slab would not fly under the current slab's MFMAs (ISA-checked).
-  // (samples past N of the last slab read the next antenna's first samples or, behind the last antenna, zero: masked at consumption)
-  auto load_raw = [&](c64 (&dst)[NB][SPL], long long slab) {
-    const unsigned off = lane_byte + (unsigned)slab * (unsigned)(16 * sizeof(c64));
-#pragma unroll
-    for (int b = 0; b < NB; ++b)
-#pragma unroll
-      for (int e = 0; e < SPL; ++e) dst[b][e] = buffer_load_c64(rs[b], off + (unsigned)(e * sizeof(c64)));
-  };
-  auto mask = [&](c64 (&v)[NB][SPL], long long slab) {               // padding antennas and samples past N contribute 0
-    const long long n0 = slab * 16 + lane_off;
-#pragma unroll
-    for (int b = 0; b < NB; ++b)
-#pragma unroll
-      for (int e = 0; e < SPL; ++e) {
-        const double m = ((n0 + e < N) && colok[b] && slab < s_lim) ? 1.0 : 0.0;
-        v[b][e] = mk(v[b][e].re * m, v[b][e].im * m);
-      }
-  };
-  // Issue order: the four products of a k-step are issued tile by tile in four sweeps, so that two MFMAs into the same accumulator are
-  // 2 NT issues apart -- back-to-back dependent v_mfma_f64_16x16x4 stall for the 64-cycle pass of their predecessor.
-  auto mfmas = [&](const c64 (&cur)[NB][SPL]) {
-#pragma unroll
-    for (int e = 0; e < SPL; ++e) {
-      double dm[NB], sp[NB];                          // Gr - Gi (row operand), Gr + Gi (column operand)
-#pragma unroll
-      for (int b = 0; b < NB; ++b) { dm[b] = cur[b][e].re - cur[b][e].im; sp[b] = cur[b][e].re + cur[b][e].im; }
-      static_for<0, NT>([&](auto uc) {
-        constexpr int u = decltype(uc)::value;
-        constexpr int I = cov_tile_i(NB, T0 + u), J = cov_tile_j(NB, T0 + u);   // row-major upper-triangular tile order
-        re[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur[I][e].re, cur[J][e].re, re[u], 0, 0, 0);
-      });
-      static_for<0, NT>([&](auto uc) {
-        constexpr int u = decltype(uc)::value;
-        constexpr int I = cov_tile_i(NB, T0 + u), J = cov_tile_j(NB, T0 + u);
-        if constexpr (I == J) im[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur[I][e].re, cur[J][e].im, im[u], 0, 0, 0);
-        else                  im[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur[I][e].im, cur[J][e].im, im[u], 0, 0, 0);
-      });
-      static_for<0, NT>([&](auto uc) {
-        constexpr int u = decltype(uc)::value;
-        constexpr int I = cov_tile_i(NB, T0 + u), J = cov_tile_j(NB, T0 + u);
-        if constexpr (I == J) re[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur[I][e].im, cur[J][e].im, re[u], 0, 0, 0);
-        else                  s3[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(dm[I], sp[J], s3[u], 0, 0, 0);
-      });
-    }
-  };
-  {
-    // Three register buffers in rotation: the loads of slabs s+1 and s+2 fly under the MFMAs of slab s (one slab of MFMAs is ~0.8 us,
-    // less than a loaded HBM round trip: a single prefetched slab still stalled).  Loads are unconditional (indices clamped to the
-    // run's last slab): a branch around loads makes the compiler's vmcnt bookkeeping pessimistic.  Padding antennas / samples past N
-    // exist only when A is not a multiple of 16 or in the very last slab: the 0/1 mask multiply runs only then (wave-uniform branch) --
-    // VALU instructions do not overlap v_mfma_f64 on this hardware (tools/cobench.hip), every one of them is paid in full.
-    const bool ants_full = (A == 16 * NB);
-    const long long i_last = s_cnt - 1;
-    auto slab_at = [&](long long i) { return s0 + (i < i_last ? i : i_last) * s_step; };
-    c64 buf[NBUF][NB][SPL];                           // buffer r holds slab i with i mod NBUF == r; slabs i+1 .. i+NBUF-1 are in flight under slab i
-                                                      // (NBUF = 4 fits at 254 VGPRs since the buffer loads: the same 178-182 us as NBUF = 3 at A = 64)
-    auto step = [&](auto rc, long long i) {
-      constexpr int r = decltype(rc)::value, f = (r + NBUF - 1) % NBUF;
-      // every kCovSyncSlabs slabs the waves of the workgroup re-align, so that a line is still in L1 / L2 when the other tile group asks for
-      // it (a barrier on EVERY slab costs 9-11 % of the pipelined rate: one delayed wave then stalls the workgroup each time)
-      if ((i & (kCovSyncSlabs - 1)) == 0) __builtin_amdgcn_s_barrier();   // (workgroup-uniform: every wave runs s_cnt steps)
-      load_raw(buf[f], slab_at(i + NBUF - 1));
-      __builtin_amdgcn_sched_barrier(0);
-      const long long slab = s0 + i * s_step;
-      if (!ants_full || slab * 16 + 16 > N || slab >= s_lim) mask(buf[r], slab);          // (wave-uniform, rare)
-      mfmas(buf[r]);
-      __builtin_amdgcn_sched_barrier(0);              // waits for later slabs' data belong AFTER this slab's MFMAs have been issued
-    };
-    if (s_cnt > 0) static_for<0, NBUF - 1>([&](auto rc) { load_raw(buf[decltype(rc)::value], slab_at(decltype(rc)::value)); });
-    long long i = 0;
-    for (; i + NBUF <= s_cnt; i += NBUF) static_for<0, NBUF>([&](auto rc) { step(rc, i + decltype(rc)::value); });
-    static_for<0, NBUF - 1>([&](auto rc) {
-      if (i + decltype(rc)::value < s_cnt) step(rc, i + decltype(rc)::value);
-    });
-  }
-  static_for<0, NT>([&](auto uc) {
-    constexpr int u = decltype(uc)::value;
-    constexpr bool diag = cov_tile_i(NB, T0 + u) == cov_tile_j(NB, T0 + u);
-    double* o = part + (((long long)part_index * n_tiles + (T0 + u)) * 2) * 256;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      if constexpr (!diag) {
-        o[0 * 256 + r * 64 + lane] = re[u][r] + im[u][r];
-        o[1 * 256 + r * 64 + lane] = (s3[u][r] - re[u][r]) + im[u][r];
-      } else {
-        o[0 * 256 + r * 64 + lane] = re[u][r];
-        o[1 * 256 + r * 64 + lane] = im[u][r];             // diagonal tile: M, antisymmetrised by cov_reduce_kernel
-      }
-    }
-  });
-}
-
-template <int NB, int NBUF = 3>
-__global__ __launch_bounds__(256, 2) void cov_mfma_small_kernel(const c64* __restrict__ G, long long N, int A,
-                                                                long long slabs_per_wg,
-                                                                double* __restrict__ part /* [gridX*kPhases][kTiles][2][256] */) {
-  using P = CovPlan<NB>;
-  const int lane = threadIdx.x & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int grp = wid / P::kPhases, phase = wid % P::kPhases;
-  const long long total = (N + 15) / 16;
-  const long long s_begin = (long long)blockIdx.x * slabs_per_wg;
-  long long s_end = s_begin + slabs_per_wg;
-  if (s_end > total) s_end = total;
-  const int pidx = blockIdx.x * P::kPhases + phase;
-  if (grp == 0) cov_group_body<NB, 0, NBUF>(G, N, A, P::kTiles, phase, lane, s_begin, 1, s_end - s_begin, s_end, pidx, part);
-  if constexpr (P::kGroups > 1) {
-    if (grp == 1) cov_group_body<NB, 1, NBUF>(G, N, A, P::kTiles, phase, lane, s_begin, 1, s_end - s_begin, s_end, pidx, part);
-  }
-}
-
-// ---- arrays wider than 64 elements (config 4: 256-element ULA): Ra is cut into 64 x 64 blocks and every workgroup owns
-// one block pair (BI <= BJ) over a chunk of samples -- a classical LDS-staged GEMM step:
-//   * the 16-sample x (64 + 64)-antenna slab is fetched once per workgroup with line-friendly loads (16 consecutive lanes
-//     read the 256 contiguous bytes of one antenna) into a double-buffered LDS image [block][sample][antenna ^ g(sample)], 16-slot rows
-//     (kCovSwizzle below: the transposing writes and the MFMA operand reads are both conflict-free); the loads of slabs s+1, s+2
-//     fly under the MFMAs of slab s; one barrier per slab;
-//   * wave w computes up to four 16 x 16 tiles per slab from LDS operands: tile row w on off-diagonal blocks, a balanced
-//     3/3/2/2 split of the 10 upper-triangular tiles on diagonal blocks.
-// Workgroups of the same sample chunk are adjacent in the grid so that block pairs sharing an antenna block stream it
-// together (Infinity Cache).  (The generic kernel above re-reads its operands once per tile triple: 8.8 ms at A = 256;
-// a register-operand version of this kernel, 20 strided global loads per wave and slab: 6.4 ms.)
-// LDS image: slot(block, sample, antenna) = (16 block + sample) 16 + (antenna ^ g(sample)),  g(s) = (s & 3) | (s & 4 ? 12 : 0).
-//   * ds_write_b128 is served in groups of 8 contiguous lanes against 32 banks (8 slots): the lanes of a group hold samples 8h .. 8h+7 of
-//     one antenna, and g's low three bits run through 0..7 there;
-//   * ds_read_b128 is served in the lane groups {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31}, ... against 64 banks (16 slots): a group mixes
-//     antennas {0-3, 12-15} of sample quad kq with antennas {4-11} of quad kq + 1 (four samples on).  XOR with g keeps {0-3}, {4-7}, {8-11},
-//     {12-15} as sets; the 12 applied on every second quad swaps {0-3} <-> {12-15} and {4-7} <-> {8-11} -- the two halves of a group land
-//     on complementary slots.  (The 17-slot pitch of the first version served the writes but left every read group 2-way conflicted:
-//     SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE = 0.37 at A = 256.)
-constexpr int kCovPitch = 16;                                   // complex elements per (block, sample) row
-__host__ __device__ constexpr int kCovSwizzle(int smp) { return (smp & 3) | ((smp & 4) ? 12 : 0); }
-constexpr int kCovBufElems = 8 * 16 * kCovPitch;                // one slab image: 8 antenna blocks x 16 samples
-constexpr unsigned kCovOobOffset = 0x80000000u;                 // beyond every staging descriptor (N * 256 B < 2^31, checked by the launcher)
-__constant__ unsigned char kCovDiagTiles[4][4] = {              // 16*I + J per (wave, slot); 255 = idle.  Slot 0 = the wave's diagonal tile
-    {0x00, 0x01, 0x02, 255}, {0x11, 0x03, 0x12, 255}, {0x22, 0x13, 255, 255}, {0x33, 0x23, 255, 255}};
-
-// One block pair.  DIAG (BI == BJ) is a template parameter so that the staging loop has a compile-time trip count: with a run-time
-// `j < n_stage` around the loads the wait-count pass gave up at every join and each stash waited with vmcnt(0) -- for the slab it needs AND
-// for the one issued a trip later, i.e. the second slab in flight never was.  Off-diagonal pairs also lose the operand selects of the
-// diagonal-tile form (VALU instructions are paid in full beside v_mfma_f64).
-template <bool DIAG>
-__device__ __forceinline__ void cov_block_pair(const c64* __restrict__ G, long long N, int A, int BI, int BJ, int pair, int chunk, int n_pairs,
-                                               long long slabs_per_wg, double* __restrict__ part, c64* __restrict__ lds) {
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int li = lane & 15, kq = lane >> 4;
-  // tiles of this wave: (I, J) inside the 64 x 64 block
-  int tI[4], tJ[4];
-  bool tv[4];
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    const int code = DIAG ? (int)kCovDiagTiles[wid][u] : (16 * wid + u);
-    tv[u] = !DIAG || code != 255;
-    tI[u] = tv[u] ? (code >> 4) : 0;
-    tJ[u] = tv[u] ? (code & 15) : 0;
-  }
-  constexpr int jbase = DIAG ? 0 : 4;               // LDS blocks 0..3 = antenna block BI, 4..7 = BJ (absent on diagonal pairs)
-  // staging ownership: flat = j*256 + tid -> antenna slot flat/16 (0..127), sample flat%16
-  constexpr int NS = DIAG ? 4 : 8;                  // loads per thread and slab
-  const int s_smp = tid & 15, l16 = tid >> 4;
-  // Staging step j reads antennas 64 B + 16 (j & 3) + (0..15) of block B = (j < 4 ? BI : BJ): one raw-buffer descriptor per step (uniform:
-  // scalar registers) that ends with the array's last antenna, so that padding antennas read as zero by the bounds check -- per thread
-  // the address is ONE 32-bit offset (N l16 + n) for all NS loads, the LDS address one base + immediate offsets.
-  __amdgpu_buffer_rsrc_t s_rs[NS];
-#pragma unroll
-  for (int j = 0; j < NS; ++j) {
-    const int ant0 = 64 * (j < 4 ? BI : BJ) + 16 * (j & 3);
-    int n_ant = A - ant0;
-    n_ant = n_ant < 0 ? 0 : (n_ant > 16 ? 16 : n_ant);
-    s_rs[j] = buffer_of(G + N * (long long)(ant0 < A ? ant0 : 0), (unsigned)(N * n_ant * (long long)sizeof(c64)));
-  }
-  const int s_lds0 = s_smp * kCovPitch + (l16 ^ kCovSwizzle(s_smp));       // + j * 16 * kCovPitch
-  // 3M form, as in cov_group_body: off-diagonal tile re = S1, im = S2, s3 = S3; diagonal tile (slot 0 of every wave of a diagonal block
-  // pair: a compile-time property, so neither selects nor branch-dependent accumulator moves) re + s3 = Re, im = M.
-  v4f64 re[4], im[4], s3[4];
-#pragma unroll
-  for (int u = 0; u < 4; ++u) re[u] = im[u] = s3[u] = v4f64{0.0, 0.0, 0.0, 0.0};
-  const long long total = (N + 15) / 16;
-  const long long s_begin = (long long)chunk * slabs_per_wg;
-  long long s_end = s_begin + slabs_per_wg;
-  if (s_end > total) s_end = total;
-  // Two slabs of global loads in flight (register sets gA / gB in rotation): one slab of MFMAs is ~1.3 us, less than a loaded HBM round
-  // trip -- with a single prefetched slab (round 2) the stash of slab s + 1 still waited for its loads (0.52 of the MFMA peak at A = 256).
-  // Samples past N and whole slabs past the chunk's end are fetched at an offset beyond every descriptor: they read as zero without a
-  // select behind the load (a select is a use of the loaded value and puts the wait for it right there) and without memory traffic.
-  c64 gA[NS], gB[NS];
-  auto fetch = [&](c64 (&g)[NS], long long slab) {
-    const long long n = slab * 16 + s_smp;
-    const unsigned voff = (n < N && slab < s_end) ? (unsigned)((N * l16 + n) * (long long)sizeof(c64)) : kCovOobOffset;
-#pragma unroll
-    for (int j = 0; j < NS; ++j) g[j] = buffer_load_c64(s_rs[j], voff);
-  };
-  auto stash = [&](const c64 (&g)[NS], int buf) {
-    c64* d = lds + buf * kCovBufElems + s_lds0;
-#pragma unroll
-    for (int j = 0; j < NS; ++j) d[j * 16 * kCovPitch] = g[j];
-  };
-  int r_off[4];                                     // operand slot of this lane for sample 4 kq + e inside a (block, 16-sample) image
-#pragma unroll
-  for (int e = 0; e < 4; ++e) r_off[e] = (4 * kq + e) * kCovPitch + (li ^ kCovSwizzle(4 * kq + e));
-  auto mfmas = [&](int buf) {
-    const c64* cur = lds + buf * kCovBufElems;
-    if constexpr (!DIAG) {
-      // off-diagonal pair: wave w owns tile row w (tI = w, tJ = 0..3) -- the row operand is read once per sample quad and shared by
-      // the four tiles: 20 instead of 32 ds_read_b128 per slab, and the operand registers of one quad at a time
-      const c64* pa = cur + wid * 16 * kCovPitch;
-      const c64* pb = cur + jbase * 16 * kCovPitch;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const c64 xa = pa[r_off[e]];
-        const double dm = xa.re - xa.im;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const c64 xb = pb[u * 16 * kCovPitch + r_off[e]];
-          re[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(xa.re, xb.re, re[u], 0, 0, 0);
-          im[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(xa.im, xb.im, im[u], 0, 0, 0);
-          s3[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(dm, xb.re + xb.im, s3[u], 0, 0, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);          // operand reads of at most one quad ahead of their MFMAs (register budget)
-      }
-    } else {
-      {                                             // slot 0: the wave's diagonal tile -- Gr Gr', M = Gr Gi', Gi Gi'
-        const c64* pa = cur + tI[0] * 16 * kCovPitch;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const c64 xa = pa[r_off[e]];
-          re[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(xa.re, xa.re, re[0], 0, 0, 0);
-          im[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(xa.re, xa.im, im[0], 0, 0, 0);
-          s3[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(xa.im, xa.im, s3[0], 0, 0, 0);
-        }
-      }
-#pragma unroll
-      for (int u = 1; u < 3; ++u) {                 // slots 1, 2: off-diagonal tiles (slot 2 on waves 0 and 1 only; slot 3 is never used)
-        if (u == 2 && !tv[2]) continue;             // (wave-uniform)
-        const c64* pa = cur + tI[u] * 16 * kCovPitch;
-        const c64* pb = cur + tJ[u] * 16 * kCovPitch;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const c64 xa = pa[r_off[e]], xb = pb[r_off[e]];
-          re[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(xa.re, xb.re, re[u], 0, 0, 0);
-          im[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(xa.im, xb.im, im[u], 0, 0, 0);
-          s3[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(xa.re - xa.im, xb.re + xb.im, s3[u], 0, 0, 0);
-        }
-      }
-    }
-  };
-  // Two trips per iteration, no exit in the middle (an odd slab count runs one all-zero slab): the accumulators keep their registers
-  // over the back-edge -- with a mid-loop exit the compiler moved all twelve of them, 48 v_mov_b64 per trip, paid in full beside the MFMAs.
-  if (s_begin < s_end) {
-    fetch(gA, s_begin);
-    stash(gA, 0);
-    fetch(gA, s_begin + 1);
-    fetch(gB, s_begin + 2);
-  }
-  __syncthreads();
-  for (long long slab = s_begin; slab < s_end; slab += 2) {
-    // even trip: slab from buffer 0; gA holds slab + 1 (issued two trips ago), gB slab + 2 (in flight)
-    mfmas(0);
-    stash(gA, 1);
-    fetch(gA, slab + 3);
-    __syncthreads();
-    // odd trip: slab + 1 from buffer 1; gB holds slab + 2
-    mfmas(1);
-    stash(gB, 0);
-    fetch(gB, slab + 4);
-    __syncthreads();
-  }
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    if (DIAG && !tv[u]) continue;
-    const bool td = DIAG && u == 0;
-    double* o = part + ((((long long)chunk * n_pairs + pair) * 16 + (tI[u] * 4 + tJ[u])) * 2) * 256;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      o[r * 64 + lane] = td ? re[u][r] + s3[u][r] : re[u][r] + im[u][r];
-      o[256 + r * 64 + lane] = td ? im[u][r] /* M: antisymmetrised by cov_block_reduce_kernel */ : (s3[u][r] - re[u][r]) + im[u][r];
-    }
-  }
-}
-
-// ---- the same block pairs, software-pipelined inside the wave (round 4; the shipped kernel for A > 64, cov_block_pair above stays as the
-// fallback for sample counts beyond this kernel's 32-bit staging offsets).  cov_block_pair issues, per 16-sample slab and wave,
-// [5 ds_read, wait, 12 MFMAs] x 4, then 8 ds_write + 8 loads + barrier: on gfx950 a wave that wants to issue a v_mfma_f64 into the busy pipe
-// holds the SIMD's issue port, so nothing of the OTHER workgroup's wave hides those bursts (tools/cobench.hip: together = sum for LDS and
-// global-memory instructions too) -- 0.53 of the MFMA peak at A = 256.  Here the pipeline step is ONE k-step (4 samples: 12 MFMAs on an
-// off-diagonal pair) on operands read during the step before, and its gaps carry, one instruction each, the operand reads of the next k-step,
-// a quarter of the staging writes of the unit after next and the re-issue of those staging loads.  Unit = 8 samples (two k-steps); four
-// 16 KB images in rotation (the same 64 KB): unit u is read during u - 1 / u, unit u + 2 written during u, one barrier per unit.
-// Image of a unit: [antenna block 0..7][sample 0..7][antenna ^ g(sample)] (16-slot rows, kCovSwizzle): staging writes (8 lanes = the 8
-// samples of one antenna) and operand reads (sample 4 e + kq) are conflict-free as in the 16-sample image.
-constexpr int kCovUnit = 8;
-constexpr int kCovUBlk = kCovUnit * kCovPitch;                  // complex elements per (antenna block, unit)
-constexpr int kCovUImg = 8 * kCovUBlk;                          // one image (16 KB)
-constexpr int kCovUImgs = 4;
-template <bool DIAG, int NSLOT>                                 // NSLOT: tiles of this wave -- 4 on an off-diagonal pair, 3 / 2 on a diagonal one (waves 0, 1 / 2, 3)
-__device__ __forceinline__ void cov_block_pair_pl(const c64* __restrict__ G, long long N, int A, int BI, int BJ, int pair, int chunk, int n_pairs,
-                                                  long long units_per_wg, double* __restrict__ part, c64* __restrict__ lds) {
-  static_assert(DIAG ? (NSLOT == 2 || NSLOT == 3) : NSLOT == 4, "");
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int li = lane & 15, kq = lane >> 4;
-  int tI[NSLOT], tJ[NSLOT];
-#pragma unroll
-  for (int u = 0; u < NSLOT; ++u) {
-    const int code = DIAG ? (int)kCovDiagTiles[wid][u] : (16 * wid + u);
-    tI[u] = code >> 4;
-    tJ[u] = code & 15;
-  }
-  // operands of one k-step.  Off-diagonal pair: op 0 = the wave's row tile (LDS block wid), op 1 + u = column tile u (LDS block 4 + u).
-  // Diagonal pair: op 0 = the diagonal tile (slot 0), ops 2 u - 1, 2 u = row / column tile of slot u >= 1.
-  constexpr int NOP = DIAG ? 2 * NSLOT - 1 : 1 + NSLOT;
-  int a_off[NOP][2];                                // element offset of operand i, k-step e inside an image
-#pragma unroll
-  for (int i = 0; i < NOP; ++i) {
-    int blk;
-    if constexpr (DIAG) blk = i == 0 ? tI[0] : ((i & 1) ? tI[(i + 1) >> 1] : tJ[i >> 1]);
-    else blk = i == 0 ? wid : 3 + i;
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-      const int smp = 4 * e + kq;
-      a_off[i][e] = blk * kCovUBlk + smp * kCovPitch + (li ^ kCovSwizzle(smp));
-    }
-  }
-  // staging: load j of a unit covers antennas 32 j .. 32 j + 31 of the pair's 128 (64) x the unit's 8 samples -- thread -> (sample tid & 7,
-  // antenna tid >> 3); 8 consecutive lanes read one 128-byte line.  One descriptor per load (uniform), ending with the array's last antenna.
-  constexpr int NS = DIAG ? 2 : 4;
-  const int s_smp = tid & 7, l32 = tid >> 3;
-  __amdgpu_buffer_rsrc_t s_rs[NS];
-#pragma unroll
-  for (int j = 0; j < NS; ++j) {
-    const int ant0 = 64 * (j < 2 ? BI : BJ) + 32 * (j & 1);
-    int n_ant = A - ant0;
-    n_ant = n_ant < 0 ? 0 : (n_ant > 32 ? 32 : n_ant);
-    s_rs[j] = buffer_of(G + N * (long long)(ant0 < A ? ant0 : 0), (unsigned)(N * n_ant * (long long)sizeof(c64)));
-  }
-  const int s_lds0 = ((l32 >> 4) * kCovUnit + s_smp) * kCovPitch + ((l32 & 15) ^ kCovSwizzle(s_smp));   // + 2 j kCovUBlk: LDS block 2 j + (l32 >> 4)
-  const long long total = (N + kCovUnit - 1) / kCovUnit;
-  const long long u_begin = (long long)chunk * units_per_wg;
-  long long u_end = u_begin + units_per_wg;
-  if (u_end > total) u_end = total;
-  auto voff_of = [&](long long unit) {               // samples past N / units past the chunk: an offset beyond every descriptor reads zero
-    const long long n = unit * kCovUnit + s_smp;
-    return (n < N && unit < u_end) ? (unsigned)((N * l32 + n) * (long long)sizeof(c64)) : kCovOobOffset;
-  };
-  v4f64 re[NSLOT], im[NSLOT], s3[NSLOT];             // 3M form as in cov_block_pair: off-diagonal tile S1, S2, S3; diagonal tile (slot 0) Gr Gr', M, Gi Gi'
-#pragma unroll
-  for (int u = 0; u < NSLOT; ++u) re[u] = im[u] = s3[u] = v4f64{0.0, 0.0, 0.0, 0.0};
-  c64 g[2][NS];                                      // staging sets: during unit u, g[u & 1] holds unit u + 2 (then u + 4), the other u + 3
-  c64 ops[2][NOP];                                   // operand sets by k-step parity
-  // One k-step.  UQ = unit index mod 4 (its image), E = k-step of the unit: compile time, the loop below is unrolled over four units.
-  auto kstep = [&](auto uq_c, auto e_c, long long unit) {
-    constexpr int UQ = decltype(uq_c)::value, E = decltype(e_c)::value, SET = UQ & 1;
-    constexpr int IMG_RD = E == 0 ? UQ : ((UQ + 1) & 3), E_RD = E ^ 1, IMG_WR = (UQ + 2) & 3;
-    const c64 (&cur)[NOP] = ops[E];
-    c64 (&nxt)[NOP] = ops[E ^ 1];
-    const unsigned voff = voff_of(unit + 4);
-    double dm[NSLOT], sp[NSLOT];                     // Gr - Gi of the row operand, Gr + Gi of the column operand (slot 0 of a diagonal pair: unused)
-#pragma unroll
-    for (int u = DIAG ? 1 : 0; u < NSLOT; ++u) {
-      const c64 xa = DIAG ? cur[2 * u - 1] : cur[0], xb = DIAG ? cur[2 * u] : cur[1 + u];
-      dm[u] = xa.re - xa.im;
-      sp[u] = xb.re + xb.im;
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    // filler k sits in the gap behind the k-th MFMA of the k-step: the NOP operand reads of the next k-step, NS / 2 staging writes, NS / 2 staging loads
-    auto filler = [&](auto kc) {
-      constexpr int k = decltype(kc)::value;
-      if constexpr (k < NOP) {
-        nxt[k] = lds[IMG_RD * kCovUImg + a_off[k][E_RD]];
-        __builtin_amdgcn_sched_barrier(0);
-      } else if constexpr (k < NOP + NS / 2) {
-        constexpr int j = E * (NS / 2) + (k - NOP);
-        lds[IMG_WR * kCovUImg + s_lds0 + 2 * j * kCovUBlk] = g[SET][j];
-        __builtin_amdgcn_sched_barrier(0);
-      } else if constexpr (k < NOP + NS) {
-        constexpr int j = E * (NS / 2) + (k - NOP - NS / 2);
-        g[SET][j] = buffer_load_c64(s_rs[j], voff);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    };
-    static_assert(3 * NSLOT >= NOP + NS, "every filler has its gap");
-    static_for<0, NSLOT>([&](auto uc) {
-      constexpr int u = decltype(uc)::value;
-      if constexpr (DIAG && u == 0) re[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur[0].re, cur[0].re, re[0], 0, 0, 0);
-      else if constexpr (DIAG) re[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur[2 * u - 1].re, cur[2 * u].re, re[u], 0, 0, 0);
-      else re[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur[0].re, cur[1 + u].re, re[u], 0, 0, 0);
-      filler(std::integral_constant<int, u>{});
-    });
-    static_for<0, NSLOT>([&](auto uc) {
-      constexpr int u = decltype(uc)::value;
-      if constexpr (DIAG && u == 0) im[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur[0].re, cur[0].im, im[0], 0, 0, 0);
-      else if constexpr (DIAG) im[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur[2 * u - 1].im, cur[2 * u].im, im[u], 0, 0, 0);
-      else im[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur[0].im, cur[1 + u].im, im[u], 0, 0, 0);
-      filler(std::integral_constant<int, NSLOT + u>{});
-    });
-    static_for<0, NSLOT>([&](auto uc) {
-      constexpr int u = decltype(uc)::value;
-      if constexpr (DIAG && u == 0) s3[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur[0].im, cur[0].im, s3[0], 0, 0, 0);
-      else s3[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(dm[u], sp[u], s3[u], 0, 0, 0);
-      filler(std::integral_constant<int, 2 * NSLOT + u>{});
-    });
-    if constexpr (E == 1) __syncthreads();
-  };
-  auto fetch = [&](c64 (&gg)[NS], long long unit) {
-    const unsigned voff = voff_of(unit);
-#pragma unroll
-    for (int j = 0; j < NS; ++j) gg[j] = buffer_load_c64(s_rs[j], voff);
-  };
-  auto stash = [&](const c64 (&gg)[NS], int img) {
-#pragma unroll
-    for (int j = 0; j < NS; ++j) lds[img * kCovUImg + s_lds0 + 2 * j * kCovUBlk] = gg[j];
-  };
-  // prologue: units 0, 1 -> images 0, 1; units 2, 3 in flight; operands of (unit 0, k-step 0)
-  fetch(g[0], u_begin);
-  fetch(g[1], u_begin + 1);
-  stash(g[0], 0);
-  stash(g[1], 1);
-  fetch(g[0], u_begin + 2);
-  fetch(g[1], u_begin + 3);
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < NOP; ++i) ops[0][i] = lds[a_off[i][0]];
-  for (long long unit = u_begin; unit < u_end; unit += 4) {     // (a unit count that is no multiple of four runs all-zero units: no exit in the middle)
-    static_for<0, 4>([&](auto uq_c) {
-      kstep(uq_c, std::integral_constant<int, 0>{}, unit + decltype(uq_c)::value);
-      kstep(uq_c, std::integral_constant<int, 1>{}, unit + decltype(uq_c)::value);
-    });
-  }
-#pragma unroll
-  for (int u = 0; u < NSLOT; ++u) {
-    const bool td = DIAG && u == 0;
-    double* o = part + ((((long long)chunk * n_pairs + pair) * 16 + (tI[u] * 4 + tJ[u])) * 2) * 256;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      o[r * 64 + lane] = td ? re[u][r] + s3[u][r] : re[u][r] + im[u][r];
-      o[256 + r * 64 + lane] = td ? im[u][r] /* M: antisymmetrised by cov_block_reduce_kernel */ : (s3[u][r] - re[u][r]) + im[u][r];
-    }
-  }
-}
-
-__global__ __launch_bounds__(256, 2) void cov_mfma_block_pl_kernel(const c64* __restrict__ G, long long N, int A, int n_blk, int n_pairs,
-                                                                   long long units_per_wg, double* __restrict__ part /* [chunk][pair][16][2][256] */) {
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  c64* lds = reinterpret_cast<c64*>(smem_raw);      // [kCovUImgs][kCovUImg]
-  const int pair = blockIdx.x % n_pairs, chunk = blockIdx.x / n_pairs;
-  int BI = 0, BJ = 0;
-  {
-    int rem = pair;                                 // pair-th (BI <= BJ) in row-major order
-    while (rem >= n_blk - BI) { rem -= n_blk - BI; ++BI; }
-    BJ = BI + rem;
-  }
-  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  if (BI != BJ) cov_block_pair_pl<false, 4>(G, N, A, BI, BJ, pair, chunk, n_pairs, units_per_wg, part, lds);
-  else if (wid < 2) cov_block_pair_pl<true, 3>(G, N, A, BI, BJ, pair, chunk, n_pairs, units_per_wg, part, lds);
-  else cov_block_pair_pl<true, 2>(G, N, A, BI, BJ, pair, chunk, n_pairs, units_per_wg, part, lds);
-}
-
-// ---- 33..64 antennas (NB = 3, 4: two tile groups), LDS-staged and software-pipelined INSIDE the wave (round 4).
-// Two measurements of this round decide the shape (profiles/r04_cobench.txt, r04_gbench.txt, r04_cov_probe_variants.txt):
-//  * cov_mfma_small_kernel feeds the MFMAs from registers: lane (i, kq) loads its own operand, i.e. 16 consecutive lanes read 16 different
-//    antenna columns, 16 bytes each.  The texture path serves such a gather at about one lane per cycle (64 cycles per wave instruction where a
-//    coalesced 1 KB load takes 16), and with two tile groups both waves of a sample phase load (nearly) every block: the loads alone take
-//    152-173 us of that kernel's 190.  Here a slab (16 samples x 64 antennas = 16 KB) is fetched ONCE per workgroup with coalesced loads
-//    (16 lanes read 256 contiguous bytes of one antenna, 4 loads per thread), transposed through the block kernel's swizzled LDS image, and
-//    every wave reads its operands with ds_read_b128 (conflict-free, 6-8 per slab).
-//  * A wave that wants to issue a v_mfma_f64 into the busy pipe holds the SIMD's issue port: beside a wave that streams MFMAs, ANOTHER wave's
-//    ds_read / ds_write / global loads cost their full stand-alone time (cobench: together = sum for every instruction kind, not only VALU).  A
-//    kernel whose waves alternate "burst of memory instructions" / "run of 30 MFMAs" therefore leaves the pipe idle while both waves of a SIMD do
-//    their bursts one after the other -- the first staged version of this kernel (burst form) ran 193 us; without its barriers 180, without its
-//    staging instructions 170, as a bare MFMA stream 159.  The fix is to hide every non-MFMA instruction in the 64-cycle shadow of the wave's OWN
-//    MFMAs: each slab step issues its 30 MFMAs on operands already in registers and, one instruction per MFMA gap, reads the NEXT slab's operands
-//    from LDS, writes the slab after that into LDS and re-issues the global loads (sched_barrier pins the positions).
-// Three LDS images in rotation (operands of slab s + 1 are read while slab s + 2 is written: one barrier per slab covers both hazards), two
-// staging register sets (two slabs of global loads in flight), two operand register sets.  Same tile groups / sample phases / 3M accumulators /
-// partial layout as cov_group_body, so the reducers are shared; a phase owns the k-steps e = 2 p, 2 p + 1 of the image (samples {e, 4 + e, 8 + e, 12 + e}).
-constexpr int kCovLdsBufs = 3;
-template <int NB, int GRP>
-__device__ __forceinline__ void cov_lds_body(const c64* __restrict__ G, long long N, int A, int phase, long long s_begin, long long s_end,
-                                             int part_index, double* __restrict__ part, c64* __restrict__ lds) {
-  using P = CovPlan<NB>;
-  static_assert(P::kGroups == 2 && P::kPhases == 2, "two tile groups x two sample phases");
-  constexpr int T0 = GRP * P::kPerGroup;
-  constexpr int NT = (T0 + P::kPerGroup <= P::kTiles) ? P::kPerGroup : (P::kTiles - T0);
-  constexpr int kBuf = NB * 16 * kCovPitch;         // one slab image
-  constexpr int kBlk = 16 * kCovPitch;              // one 16-antenna block of it
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int li = lane & 15, kq = lane >> 4;
-  v4f64 re[NT], im[NT], s3[NT];
-#pragma unroll
-  for (int u = 0; u < NT; ++u) re[u] = im[u] = s3[u] = v4f64{0.0, 0.0, 0.0, 0.0};
-  // staging: thread -> (sample tid & 15, antenna 16 j + (tid >> 4)), j = 0 .. NB - 1; one descriptor per 16-antenna block that ends with the
-  // array's last antenna (padding antennas read as zero by the bounds check)
-  const int s_smp = tid & 15, l16 = tid >> 4;
-  __amdgpu_buffer_rsrc_t s_rs[NB];
-#pragma unroll
-  for (int j = 0; j < NB; ++j) {
-    int n_ant = A - 16 * j;
-    n_ant = n_ant < 0 ? 0 : (n_ant > 16 ? 16 : n_ant);
-    s_rs[j] = buffer_of(G + N * (long long)(n_ant > 0 ? 16 * j : 0), (unsigned)(N * n_ant * (long long)sizeof(c64)));
-  }
-  const int s_lds0 = s_smp * kCovPitch + (l16 ^ kCovSwizzle(s_smp));
-  auto voff_of = [&](long long slab) {               // samples past N / slabs past the chunk: an offset beyond every descriptor reads zero
-    const long long n = slab * 16 + s_smp;
-    return (n < N && slab < s_end) ? (unsigned)((N * l16 + n) * (long long)sizeof(c64)) : kCovOobOffset;
-  };
-  int r_off[2];
-#pragma unroll
-  for (int e = 0; e < 2; ++e) {
-    const int smp = 4 * kq + 2 * phase + e;
-    r_off[e] = smp * kCovPitch + (li ^ kCovSwizzle(smp));
-  }
-  c64 g[2][NB];                                      // staging sets: at the top of the step for slab s, g[s & 1] holds slab s + 2, the other s + 3
-  c64 ops[2][NB][2];                                 // operand sets: ops[s & 1] holds slab s
-  // One slab step.  PAR = parity of the step (compile time: register sets), rd / wr = LDS images of slab + 1 (complete) and slab + 2 (free).
-  auto step = [&](auto par_c, long long slab, int rd, int wr) {
-    constexpr int PAR = decltype(par_c)::value;
-    const c64 (&cur)[NB][2] = ops[PAR];
-    c64 (&nxt)[NB][2] = ops[PAR ^ 1];
-    c64 (&gs)[NB] = g[PAR];
-    const c64* img = lds + rd * kBuf;
-    c64* dst = lds + wr * kBuf + s_lds0;
-    const unsigned voff = voff_of(slab + 4);
-    double dm[2][NB], sp[2][NB];                     // Gr - Gi (row operand), Gr + Gi (column operand) of the 3M form
-#pragma unroll
-    for (int e = 0; e < 2; ++e)
-#pragma unroll
-      for (int b = 0; b < NB; ++b) { dm[e][b] = cur[b][e].re - cur[b][e].im; sp[e][b] = cur[b][e].re + cur[b][e].im; }
-    __builtin_amdgcn_sched_barrier(0);
-    // filler k goes into the gap behind the k-th MFMA of the step (6 NT MFMAs: 30 at NB = 4): gaps 0 .. 2 NB - 1 the operand reads of the
-    // next slab, then the NB staging writes, then the NB staging loads into the registers just written out
-    auto filler = [&](auto kc) {
-      constexpr int k = decltype(kc)::value;
-      if constexpr (k < 2 * NB) {
-        constexpr int e = k / NB, b = k % NB;
-        nxt[b][e] = img[b * kBlk + r_off[e]];        // (blocks no tile of this group touches: dead reads, dropped by the compiler)
-        __builtin_amdgcn_sched_barrier(0);
-      } else if constexpr (k < 3 * NB) {
-        constexpr int j = k - 2 * NB;
-        dst[j * kBlk] = gs[j];
-        __builtin_amdgcn_sched_barrier(0);
-      } else if constexpr (k < 4 * NB) {
-        constexpr int j = k - 3 * NB;
-        gs[j] = buffer_load_c64(s_rs[j], voff);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    };
-    static_for<0, 2>([&](auto ec) {
-      constexpr int e = decltype(ec)::value;
-      static_for<0, NT>([&](auto uc) {
-        constexpr int u = decltype(uc)::value;
-        constexpr int I = cov_tile_i(NB, T0 + u), J = cov_tile_j(NB, T0 + u);
-        re[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur[I][e].re, cur[J][e].re, re[u], 0, 0, 0);
-        filler(std::integral_constant<int, e * 3 * NT + u>{});
-      });
-      static_for<0, NT>([&](auto uc) {
-        constexpr int u = decltype(uc)::value;
-        constexpr int I = cov_tile_i(NB, T0 + u), J = cov_tile_j(NB, T0 + u);
-        if constexpr (I == J) im[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur[I][e].re, cur[J][e].im, im[u], 0, 0, 0);
-        else                  im[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur[I][e].im, cur[J][e].im, im[u], 0, 0, 0);
-        filler(std::integral_constant<int, e * 3 * NT + NT + u>{});
-      });
-      static_for<0, NT>([&](auto uc) {
-        constexpr int u = decltype(uc)::value;
-        constexpr int I = cov_tile_i(NB, T0 + u), J = cov_tile_j(NB, T0 + u);
-        if constexpr (I == J) re[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur[I][e].im, cur[J][e].im, re[u], 0, 0, 0);
-        else                  s3[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(dm[e][I], sp[e][J], s3[u], 0, 0, 0);
-        filler(std::integral_constant<int, e * 3 * NT + 2 * NT + u>{});
-      });
-    });
-    static_assert(6 * NT >= 4 * NB, "every filler has its gap");
-    __syncthreads();
-  };
-  auto fetch = [&](c64 (&gg)[NB], long long slab) {
-    const unsigned voff = voff_of(slab);
-#pragma unroll
-    for (int j = 0; j < NB; ++j) gg[j] = buffer_load_c64(s_rs[j], voff);
-  };
-  auto stash = [&](const c64 (&gg)[NB], int buf) {
-    c64* d = lds + buf * kBuf + s_lds0;
-#pragma unroll
-    for (int j = 0; j < NB; ++j) d[j * kBlk] = gg[j];
-  };
-  // prologue: slab 0 -> image 0 -> ops[0]; slab 1 -> image 1; slabs 2, 3 in flight
-  fetch(g[0], s_begin);
-  fetch(g[1], s_begin + 1);
-  stash(g[0], 0);
-  stash(g[1], 1);
-  fetch(g[0], s_begin + 2);
-  fetch(g[1], s_begin + 3);
-  __syncthreads();
-#pragma unroll
-  for (int e = 0; e < 2; ++e)
-#pragma unroll
-    for (int b = 0; b < NB; ++b) ops[0][b][e] = lds[b * kBlk + r_off[e]];
-  int rd = 1, wr = 2;                                // (uniform) image of slab + 1, image for slab + 2
-  auto rot = [&]() { rd = wr; wr = wr == kCovLdsBufs - 1 ? 0 : wr + 1; };
-  for (long long slab = s_begin; slab < s_end; slab += 2) {       // (an odd slab count runs one all-zero slab: no exit in the middle)
-    step(std::integral_constant<int, 0>{}, slab, rd, wr);
-    rot();
-    step(std::integral_constant<int, 1>{}, slab + 1, rd, wr);
-    rot();
-  }
-  // the two sample phases of a tile group are summed inside the workgroup (through the now idle slab images) before anything goes to memory: one partial per
-  // workgroup and tile instead of two -- half the partial-sum traffic of this kernel and of the reducers behind it (20 instead of 41 MB per launch at A = 64)
-  double* x = reinterpret_cast<double*>(lds) + GRP * (P::kPerGroup * 2 * 256);
-  static_assert(sizeof(c64) * kCovLdsBufs * kBuf >= sizeof(double) * 2 * P::kPerGroup * 2 * 256, "the phase exchange fits the slab images");
-  double o0[NT][4], o1[NT][4];
-  static_for<0, NT>([&](auto uc) {
-    constexpr int u = decltype(uc)::value;
-    constexpr bool diag = cov_tile_i(NB, T0 + u) == cov_tile_j(NB, T0 + u);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      if constexpr (!diag) {
-        o0[u][r] = re[u][r] + im[u][r];
-        o1[u][r] = (s3[u][r] - re[u][r]) + im[u][r];
-      } else {
-        o0[u][r] = re[u][r];
-        o1[u][r] = im[u][r];                                 // diagonal tile: M, antisymmetrised by cov_reduce_kernel
-      }
-    }
-  });
-  if (phase == 1) {
-#pragma unroll
-    for (int u = 0; u < NT; ++u)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) { x[(u * 2 + 0) * 256 + r * 64 + lane] = o0[u][r]; x[(u * 2 + 1) * 256 + r * 64 + lane] = o1[u][r]; }
-  }
-  __syncthreads();
-  if (phase == 0) {
-#pragma unroll
-    for (int u = 0; u < NT; ++u) {
-      double* o = part + (((long long)part_index * P::kTiles + (T0 + u)) * 2) * 256;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        o[0 * 256 + r * 64 + lane] = o0[u][r] + x[(u * 2 + 0) * 256 + r * 64 + lane];
-        o[1 * 256 + r * 64 + lane] = o1[u][r] + x[(u * 2 + 1) * 256 + r * 64 + lane];
-      }
-    }
-  }
-}
-
-template <int NB>
-__global__ __launch_bounds__(256, 2) void cov_mfma_lds_kernel(const c64* __restrict__ G, long long N, int A, long long slabs_per_wg,
-                                                              double* __restrict__ part /* [gridX][kTiles][2][256] */) {
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  c64* lds = reinterpret_cast<c64*>(smem_raw);      // [kCovLdsBufs][NB * 16 * kCovPitch]
-  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int grp = wid >> 1, phase = wid & 1;
-  const long long total = (N + 15) / 16;
-  const long long s_begin = (long long)blockIdx.x * slabs_per_wg;
-  long long s_end = s_begin + slabs_per_wg;
-  if (s_end > total) s_end = total;
-  const int pidx = blockIdx.x;                       // (one partial per workgroup: the phases are summed in the kernel)
-  if (grp == 0) cov_lds_body<NB, 0>(G, N, A, phase, s_begin, s_end, pidx, part, lds);
-  else cov_lds_body<NB, 1>(G, N, A, phase, s_begin, s_end, pidx, part, lds);
-}
-
-// ---------------------------------------------------------------- covariance of a LAZY echo grid (round 6)
-// The fused monoStaticSensing call wrote echoGrid (0.75 GB at the bench shape) only so that this stage could read it back.  With the spectral noise route the grid is a function
-// of 12 MB of inputs:   e[k, l, r] = sum_q D_q[k, l] a_q[r] + sig W(seed; k, l, r),   W = float32 Box-Muller of one Philox4x32-10 call per element PAIR (k, k + 512)
-// (echo_dev.hpp).  cov_lazy_kernel is cov_mfma_lds_kernel<4> with the slab staging (four 16-byte global loads per thread and slab) replaced by a generator that re-forms the
-// slab's 16 x 64 elements with THE expression of the synthesis kernel (spectral_echo_value: the same bits) and writes them into the same swizzled LDS image:
-//   * a slab is 8 PAIR rows of one symbol column: samples k0 + p and k0 + p + 512 (p = 0..7) occupy sample slots p and p + 8, so that both halves of every Philox call are
-//     used -- the slab order is therefore (symbol, 1024-subcarrier block pair, 8-row group), not the flat n = k + K l of the array form; the sum is the same, its rounding
-//     differs in the last bits (tests: <= 1e-13 of the array form; every estimate identical).  K is not a multiple of 1024: the partner half of the last block pair is masked
-//     (218 instead of 204.75 slabs per column at K = 3276: 6 % more MFMA issue than the array form);
-//   * thread (p = tid & 7, r0 = tid >> 3) makes TWO Philox calls per slab -- antennas r0 and r0 + 32 -- i.e. four elements, and two 16-byte loads of D (from L2: the lanes of a
-//     wave share 8 subcarriers) per target, issued two slabs ahead;
-//   * the generator is cut into 19 pieces (counter set-up + 10 Philox rounds, 4 Box-Muller transforms, 4 x (synthesis + mask + LDS store), the D loads) that sit in the gaps of the
-//     step's 30 MFMAs like the staging instructions did, spread evenly (lazy_piece_gap).
-// Bound: fp64 MFMA issue + the generator's VALU (v_mfma_f64 and VALU of one wave overlap only inside the 64-cycle shadow of the wave's own MFMA, section 3d of DESIGN_HISTORY.md).
-struct LazyCovArgs {
-  const c64* D;               // [K x L_whole x QT] per-target demodulated coefficient grids
-  const c64* steer_rq;        // [A x QT]: a_q[r] at r QT + q
-  double sig;
-  unsigned long long seed;
-  int K, L_whole, L_out, A;
-  int s_col;                  // slabs per symbol column
-};
-constexpr int kLazyPieces = 19;
-__host__ __device__ constexpr int lazy_piece_gap(int i) {       // MFMA gap (0..29) that carries generator piece i
-  return (i * 30) / kLazyPieces;
-}
-
-template <int GRP, int QT>
-__device__ __forceinline__ void cov_lazy_body(const LazyCovArgs& a, int phase, long long s_begin, long long s_end, int part_index, double* __restrict__ part,
-                                              c64* __restrict__ lds) {
-  constexpr int NB = 4;
-  using P = CovPlan<NB>;
-  constexpr int T0 = GRP * P::kPerGroup;
-  constexpr int NT = (T0 + P::kPerGroup <= P::kTiles) ? P::kPerGroup : (P::kTiles - T0);
-  constexpr int kBuf = NB * 16 * kCovPitch;         // one slab image
-  constexpr int kBlk = 16 * kCovPitch;              // one 16-antenna block of it
-  static_assert(6 * NT == 30, "30 MFMA gaps per slab step");
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int li = lane & 15, kq = lane >> 4;
-  v4f64 re[NT], im[NT], s3[NT];
-#pragma unroll
-  for (int u = 0; u < NT; ++u) re[u] = im[u] = s3[u] = v4f64{0.0, 0.0, 0.0, 0.0};
-  // ---- generator: thread -> (pair row gp, antennas ga and ga + 32)
-  const int gp = tid & 7, ga = tid >> 3;
-  const int K = a.K;
-  const double sig = a.sig;
-  const uint32_t key0 = (uint32_t)a.seed, key1 = (uint32_t)(a.seed >> 32);
-  c64 st[2][QT];
-  bool ant_ok[2];
-  uint64_t colbase[2];
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int ant = ga + 32 * j;
-    ant_ok[j] = ant < a.A;
-    colbase[j] = (uint64_t)a.L_out * (uint64_t)ant;
-#pragma unroll
-    for (int q = 0; q < QT; ++q) st[j][q] = ant_ok[j] ? a.steer_rq[(long long)ant * QT + q] : mk(0.0, 0.0);
-  }
-  __amdgpu_buffer_rsrc_t rsD[QT];
-#pragma unroll
-  for (int q = 0; q < QT; ++q) rsD[q] = buffer_of(a.D + (long long)q * K * a.L_whole, (unsigned)((long long)K * a.L_whole * (long long)sizeof(c64)));
-  const int g_lds0 = (ga >> 4) * kBlk + gp * kCovPitch + ((ga & 15) ^ kCovSwizzle(gp));     // element (antenna ga, sample slot gp); + 2 j kBlk, + 8 h kCovPitch
-  // cursors (wave-uniform): the slab being generated and the slab whose D values are being fetched
-  struct Cur { int l, sc; long long g; };
-  auto cur_at = [&](long long g) { Cur c; c.g = g; c.l = (int)((unsigned)g / (unsigned)a.s_col); c.sc = (int)((unsigned)g - (unsigned)c.l * (unsigned)a.s_col); return c; };   // (slab counts fit 31 bits: checked by the launcher)
-  auto advance = [&](Cur& c) { ++c.g; if (++c.sc == a.s_col) { c.sc = 0; ++c.l; } };
-  auto k0_of = [&](const Cur& c) { return ((c.sc >> 6) << 10) + ((c.sc & 63) << 3) + gp; };      // subcarrier of half 0; half 1 = + 512
-  uint32_t pc[2][4];
-  float wf[2][2][2];
-  bool v_half[2];
-  c64 dl[2][QT][2];                                  // D values of two slabs in flight: dl[par][q][half]
-  auto gen_init = [&](const Cur& c) {
-    const int k0 = k0_of(c);
-    const bool in = c.g < s_end;
-    v_half[0] = in && k0 < K;
-    v_half[1] = in && k0 + 512 < K;
-    const uint32_t slot = (uint32_t)(((c.sc >> 6) << 9) + ((c.sc & 63) << 3) + gp);
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const uint64_t ctr = (uint64_t)slot + (uint64_t)kSpectralSlotsPerColumn * ((uint64_t)c.l + colbase[j]);
-      pc[j][0] = (uint32_t)ctr; pc[j][1] = (uint32_t)(ctr >> 32); pc[j][2] = kSpectralStream; pc[j][3] = 0u;
-    }
-  };
-  auto gen_round = [&](auto rc) {
-    constexpr uint32_t r = (uint32_t)decltype(rc)::value;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) philox4x32_round(pc[j], key0 + r * 0x9E3779B9u, key1 + r * 0xBB67AE85u);
-  };
-  auto gen_bm = [&](auto jc, auto hc) {
-    constexpr int j = decltype(jc)::value, h = decltype(hc)::value;
-    box_muller32_hw_f32(pc[j][2 * h], pc[j][2 * h + 1], wf[j][h][0], wf[j][h][1]);
-  };
-  auto gen_emit = [&](auto jc, auto hc, const c64 (&dv)[QT][2], c64* img) {
-    constexpr int j = decltype(jc)::value, h = decltype(hc)::value;
-    c64 d[QT];
-#pragma unroll
-    for (int q = 0; q < QT; ++q) d[q] = dv[q][h];
-    c64 v = spectral_echo_value<QT, true>(d, st[j], mk((double)wf[j][h][0], (double)wf[j][h][1]), sig);
-    const bool ok = v_half[h] && ant_ok[j];
-    v = mk(ok ? v.re : 0.0, ok ? v.im : 0.0);
-    img[g_lds0 + 2 * j * kBlk + 8 * h * kCovPitch] = v;
-  };
-  auto gen_loads = [&](c64 (&dv)[QT][2], const Cur& c) {
-    const int k0 = k0_of(c);
-    const bool in = c.g < s_end;
-    const unsigned base = (unsigned)(((long long)K * c.l + k0) * (long long)sizeof(c64));
-    const unsigned o0 = (in && k0 < K) ? base : kCovOobOffset, o1 = (in && k0 + 512 < K) ? base + 512u * (unsigned)sizeof(c64) : kCovOobOffset;
-#pragma unroll
-    for (int q = 0; q < QT; ++q) { dv[q][0] = buffer_load_c64(rsD[q], o0); dv[q][1] = buffer_load_c64(rsD[q], o1); }
-  };
-  int r_off[2];
-#pragma unroll
-  for (int e = 0; e < 2; ++e) {
-    const int smp = 4 * kq + 2 * phase + e;
-    r_off[e] = smp * kCovPitch + (li ^ kCovSwizzle(smp));
-  }
-  c64 ops[2][NB][2];                                 // operand sets: ops[s & 1] holds slab s
-  Cur cg = cur_at(s_begin), cd = cur_at(s_begin);
-  // One slab step.  PAR = parity of the step, rd / wr = LDS images of slab + 1 (complete) and slab + 2 (being generated here).
-  auto step = [&](auto par_c, int rd, int wr) {
-    constexpr int PAR = decltype(par_c)::value;
-    const c64 (&cur)[NB][2] = ops[PAR];
-    c64 (&nxt)[NB][2] = ops[PAR ^ 1];
-    const c64* img = lds + rd * kBuf;
-    c64* dst = lds + wr * kBuf;
-    double dm[2][NB], sp[2][NB];
-#pragma unroll
-    for (int e = 0; e < 2; ++e)
-#pragma unroll
-      for (int b = 0; b < NB; ++b) { dm[e][b] = cur[b][e].re - cur[b][e].im; sp[e][b] = cur[b][e].re + cur[b][e].im; }
-    __builtin_amdgcn_sched_barrier(0);
-    auto piece = [&](auto ic) {
-      constexpr int i = decltype(ic)::value;
-      if constexpr (i == 0) { gen_init(cg); gen_round(std::integral_constant<int, 0>{}); }
-      else if constexpr (i < 10) gen_round(std::integral_constant<int, i>{});
-      else if constexpr (i < 14) gen_bm(std::integral_constant<int, (i - 10) / 2>{}, std::integral_constant<int, (i - 10) % 2>{});
-      else if constexpr (i < 18) gen_emit(std::integral_constant<int, (i - 14) / 2>{}, std::integral_constant<int, (i - 14) % 2>{}, dl[PAR], dst);
-      else { gen_loads(dl[PAR], cd); advance(cg); advance(cd); }
-    };
-    auto filler = [&](auto kc) {
-      constexpr int k = decltype(kc)::value;
-      if constexpr (k < 2 * NB) {
-        constexpr int e = k / NB, b = k % NB;
-        nxt[b][e] = img[b * kBlk + r_off[e]];        // (blocks no tile of this group touches: dead reads, dropped by the compiler)
-      }
-      static_for<0, kLazyPieces>([&](auto ic) {
-        if constexpr (lazy_piece_gap(decltype(ic)::value) == k) piece(ic);
-      });
-      __builtin_amdgcn_sched_barrier(0);
-    };
-    static_for<0, 2>([&](auto ec) {
-      constexpr int e = decltype(ec)::value;
-      static_for<0, NT>([&](auto uc) {
-        constexpr int u = decltype(uc)::value;
-        constexpr int I = cov_tile_i(NB, T0 + u), J = cov_tile_j(NB, T0 + u);
-        re[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur[I][e].re, cur[J][e].re, re[u], 0, 0, 0);
-        filler(std::integral_constant<int, e * 3 * NT + u>{});
-      });
-      static_for<0, NT>([&](auto uc) {
-        constexpr int u = decltype(uc)::value;
-        constexpr int I = cov_tile_i(NB, T0 + u), J = cov_tile_j(NB, T0 + u);
-        if constexpr (I == J) im[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur[I][e].re, cur[J][e].im, im[u], 0, 0, 0);
-        else                  im[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur[I][e].im, cur[J][e].im, im[u], 0, 0, 0);
-        filler(std::integral_constant<int, e * 3 * NT + NT + u>{});
-      });
-      static_for<0, NT>([&](auto uc) {
-        constexpr int u = decltype(uc)::value;
-        constexpr int I = cov_tile_i(NB, T0 + u), J = cov_tile_j(NB, T0 + u);
-        if constexpr (I == J) re[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur[I][e].im, cur[J][e].im, re[u], 0, 0, 0);
-        else                  s3[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(dm[e][I], sp[e][J], s3[u], 0, 0, 0);
-        filler(std::integral_constant<int, e * 3 * NT + 2 * NT + u>{});
-      });
-    });
-    __syncthreads();
-  };
-  // prologue: slabs 0 and 1 generated outright into images 0 and 1; the D values of slabs 2 and 3 in flight
-  auto gen_whole = [&](c64 (&dv)[QT][2], int buf) {
-    gen_loads(dv, cg);
-    gen_init(cg);
-    static_for<0, 10>([&](auto rc) { gen_round(rc); });
-    static_for<0, 4>([&](auto ic) { gen_bm(std::integral_constant<int, decltype(ic)::value / 2>{}, std::integral_constant<int, decltype(ic)::value % 2>{}); });
-    static_for<0, 4>([&](auto ic) { gen_emit(std::integral_constant<int, decltype(ic)::value / 2>{}, std::integral_constant<int, decltype(ic)::value % 2>{}, dv, lds + buf * kBuf); });
-    advance(cg);
-  };
-  gen_whole(dl[0], 0);
-  gen_whole(dl[1], 1);
-  cd = cg;                                           // slab s_begin + 2
-  gen_loads(dl[0], cd); advance(cd);
-  gen_loads(dl[1], cd); advance(cd);
-  __syncthreads();
-#pragma unroll
-  for (int e = 0; e < 2; ++e)
-#pragma unroll
-    for (int b = 0; b < NB; ++b) ops[0][b][e] = lds[b * kBlk + r_off[e]];
-  int rd = 1, wr = 2;                                // (uniform) image of slab + 1, image for slab + 2
-  auto rot = [&]() { rd = wr; wr = wr == kCovLdsBufs - 1 ? 0 : wr + 1; };
-  for (long long slab = s_begin; slab < s_end; slab += 2) {       // (an odd slab count runs one all-zero slab: no exit in the middle)
-    step(std::integral_constant<int, 0>{}, rd, wr);
-    rot();
-    step(std::integral_constant<int, 1>{}, rd, wr);
-    rot();
-  }
-  // phase exchange + partial store: as cov_lds_body
-  double* x = reinterpret_cast<double*>(lds) + GRP * (P::kPerGroup * 2 * 256);
-  double o0[NT][4], o1[NT][4];
-  static_for<0, NT>([&](auto uc) {
-    constexpr int u = decltype(uc)::value;
-    constexpr bool diag = cov_tile_i(NB, T0 + u) == cov_tile_j(NB, T0 + u);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      if constexpr (!diag) {
-        o0[u][r] = re[u][r] + im[u][r];
-        o1[u][r] = (s3[u][r] - re[u][r]) + im[u][r];
-      } else {
-        o0[u][r] = re[u][r];
-        o1[u][r] = im[u][r];                                 // diagonal tile: M, antisymmetrised by cov_reduce_kernel
-      }
-    }
-  });
-  if (phase == 1) {
-#pragma unroll
-    for (int u = 0; u < NT; ++u)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) { x[(u * 2 + 0) * 256 + r * 64 + lane] = o0[u][r]; x[(u * 2 + 1) * 256 + r * 64 + lane] = o1[u][r]; }
-  }
-  __syncthreads();
-  if (phase == 0) {
-#pragma unroll
-    for (int u = 0; u < NT; ++u) {
-      double* o = part + (((long long)part_index * P::kTiles + (T0 + u)) * 2) * 256;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        o[0 * 256 + r * 64 + lane] = o0[u][r] + x[(u * 2 + 0) * 256 + r * 64 + lane];
-        o[1 * 256 + r * 64 + lane] = o1[u][r] + x[(u * 2 + 1) * 256 + r * 64 + lane];
-      }
-    }
-  }
-}
-
-template <int QT>
-__global__ __launch_bounds__(256, 2) void cov_lazy_kernel(LazyCovArgs a, long long n_slabs, long long slabs_per_wg, double* __restrict__ part /* [gridX][kTiles][2][256] */) {
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  c64* lds = reinterpret_cast<c64*>(smem_raw);      // [kCovLdsBufs][4 * 16 * kCovPitch]
-  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int grp = wid >> 1, phase = wid & 1;
-  const long long s_begin = (long long)blockIdx.x * slabs_per_wg;
-  long long s_end = s_begin + slabs_per_wg;
-  if (s_end > n_slabs) s_end = n_slabs;
-  if (grp == 0) cov_lazy_body<0, QT>(a, phase, s_begin, s_end, blockIdx.x, part, lds);
-  else cov_lazy_body<1, QT>(a, phase, s_begin, s_end, blockIdx.x, part, lds);
-}
-
-__global__ __launch_bounds__(256, 2) void cov_mfma_block_kernel(const c64* __restrict__ G, long long N, int A, int n_blk,
-                                                                int n_pairs, long long slabs_per_wg,
-                                                                double* __restrict__ part /* [chunk][pair][16][2][256] */) {
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  c64* lds = reinterpret_cast<c64*>(smem_raw);      // [2][kCovBufElems]
-  // (pinning the block pairs of one sample chunk to one XCD -- workgroup b runs on XCD b % 8 -- so that a chunk's slabs enter ONE L2: 3.71 ->
-  // 4.11 ms at A = 256, no change at A = 128: the diagonal pairs run 1.6x faster than the off-diagonal ones and drift out of the L2 window)
-  const int pair = blockIdx.x % n_pairs, chunk = blockIdx.x / n_pairs;
-  int BI = 0, BJ = 0;
-  {
-    int rem = pair;                                 // pair-th (BI <= BJ) in row-major order
-    while (rem >= n_blk - BI) { rem -= n_blk - BI; ++BI; }
-    BJ = BI + rem;
-  }
-  if (BI == BJ) cov_block_pair<true>(G, N, A, BI, BJ, pair, chunk, n_pairs, slabs_per_wg, part, lds);
-  else cov_block_pair<false>(G, N, A, BI, BJ, pair, chunk, n_pairs, slabs_per_wg, part, lds);
-}
-
-// fixed-order sum over the sample chunks of one tile + Hermitian fill + 1/N (block layout of cov_mfma_block_kernel)
-__global__ __launch_bounds__(1024) void cov_block_reduce_kernel(const double* __restrict__ part, int n_chunks, int n_blk, int n_pairs,
-                                                                int A, double inv_n, c64* __restrict__ Ra) {
-  __shared__ double s_sum[2][4][256];
-  const int tile = blockIdx.x, pair = blockIdx.y;
-  int BI = 0, BJ = 0;
-  {
-    int rem = pair;
-    while (rem >= n_blk - BI) { rem -= n_blk - BI; ++BI; }
-    BJ = BI + rem;
-  }
-  const int I = tile >> 2, J = tile & 3;
-  if (BI == BJ && J < I) return;                    // never computed
-  const int e = threadIdx.x, g = threadIdx.y;
-  const int per = (n_chunks + 3) / 4;
-  const int c0 = g * per, c1 = min(n_chunks, c0 + per);
-  double sr = 0.0, si = 0.0;
-  for (int c = c0; c < c1; ++c) {
-    const double* o = part + ((((long long)c * n_pairs + pair) * 16 + tile) * 2) * 256;
-    sr += o[e];
-    si += o[256 + e];
-  }
-  s_sum[0][g][e] = sr; s_sum[1][g][e] = si;
-  __syncthreads();
-  if (g != 0) return;
-  sr = ((s_sum[0][0][e] + s_sum[0][1][e]) + s_sum[0][2][e]) + s_sum[0][3][e];
-  si = ((s_sum[1][0][e] + s_sum[1][1][e]) + s_sum[1][2][e]) + s_sum[1][3][e];
-  const int r = e >> 6, lane = e & 63;
-  if (BI == BJ && I == J) {                         // diagonal tile: the partials hold M, Im = M - M^T
-    const int row = (lane >> 4) + 4 * r, col = lane & 15;
-    const int et = (col >> 2) * 64 + ((col & 3) << 4) + row;
-    si -= ((s_sum[1][0][et] + s_sum[1][1][et]) + s_sum[1][2][et]) + s_sum[1][3][et];
-  }
-  const int a = 64 * BI + 16 * I + (lane >> 4) + 4 * r;   // f64 MFMA C/D layout: row = (lane>>4) + 4*reg, col = lane&15
-  const int b = 64 * BJ + 16 * J + (lane & 15);
-  if (a >= A || b >= A) return;
-  c64 v = mk(sr * inv_n, si * inv_n);
-  if (a == b) v.im = 0.0;
-  if (BI == BJ && I == J && a > b) return;          // diagonal tile: keep the upper triangle, mirror it (exactly Hermitian)
-  Ra[a + (long long)A * b] = v;
-  if (a != b) Ra[b + (long long)A * a] = conj(v);
-}
-
-// first reduction level: slice s of S sums a contiguous run of workgroup partials (fixed order) into part2[s];
-// spreads the 60 MB of partial tiles over S x n_tiles workgroups instead of n_tiles (per-CU bandwidth bound)
-__global__ __launch_bounds__(256) void cov_reduce_slice_kernel(const double* __restrict__ part, int n_wg, int n_tiles, int S,
-                                                               double* __restrict__ part2 /* [S][n_tiles][2][256] */) {
-  const int t = blockIdx.x, sl = blockIdx.y, e = threadIdx.x;
-  const int per = (n_wg + S - 1) / S;
-  const int w0 = sl * per, w1 = min(n_wg, w0 + per);
-  double sr = 0.0, si = 0.0;
-#pragma unroll 8
-  for (int w = w0; w < w1; ++w) {
-    const double* o = part + (((long long)w * n_tiles + t) * 2) * 256;
-    sr += o[e];
-    si += o[256 + e];
-  }
-  double* d = part2 + (((long long)sl * n_tiles + t) * 2) * 256;
-  d[e] = sr; d[256 + e] = si;
-}
-
-// fixed-order reduction over workgroup partials + Hermitian fill + 1/N.
-__global__ __launch_bounds__(1024) void cov_reduce_kernel(const double* __restrict__ part, int n_wg, int n_tiles, int A,
-                                                          double inv_n, c64* __restrict__ Ra /* [A x A] column-major */,
-                                                          int diag_antisym /* diagonal tiles hold M: Im = M - M^T */) {
-  __shared__ double s_sum[2][4][256];
-  const int t = blockIdx.x;
-  const int nb = (A + 15) / 16;
-  int I, J;
-  tile_ij(t, nb, I, J);
-  const int e = threadIdx.x;            // r*64 + lane
-  const int g = threadIdx.y;
-  const int r = e >> 6, lane = e & 63;
-  const int row = (lane >> 4) + 4 * r;  // f64 MFMA C/D layout: row = (lane>>4) + 4*reg, col = lane&15
-  const int col = lane & 15;
-  const int per = (n_wg + 3) / 4;
-  const int w0 = g * per, w1 = min(n_wg, w0 + per);
-  double sr = 0.0, si = 0.0;
-#pragma unroll 8
-  for (int w = w0; w < w1; ++w) {
-    const double* o = part + (((long long)w * n_tiles + t) * 2) * 256;
-    sr += o[e];
-    si += o[256 + e];
-  }
-  s_sum[0][g][e] = sr; s_sum[1][g][e] = si;
-  __syncthreads();
-  if (g != 0) return;
-  sr = ((s_sum[0][0][e] + s_sum[0][1][e]) + s_sum[0][2][e]) + s_sum[0][3][e];
-  si = ((s_sum[1][0][e] + s_sum[1][1][e]) + s_sum[1][2][e]) + s_sum[1][3][e];
-  if (diag_antisym && I == J) {
-    const int et = (col >> 2) * 64 + ((col & 3) << 4) + row;          // the (col, row) entry of the same tile
-    si -= ((s_sum[1][0][et] + s_sum[1][1][et]) + s_sum[1][2][et]) + s_sum[1][3][et];
-  }
-  const int a = I * 16 + row, b = J * 16 + col;
-  if (a < A && b < A) {
-    c64 v = mk(sr * inv_n, si * inv_n);
-    if (I == J) {
-      if (a == b) v.im = 0.0;
-      // both triangles of a diagonal tile are computed; keep the upper one and mirror it so
-      // the matrix is exactly Hermitian (zherk-like), as MATLAB's X*X' is
-      if (a <= b) {
-        Ra[a + (long long)A * b] = v;
-        if (a != b) Ra[b + (long long)A * a] = conj(v);
-      }
-    } else {
-      Ra[a + (long long)A * b] = v;
-      Ra[b + (long long)A * a] = conj(v);
-    }
-  }
-}
 
 // zheev-style safe scaling: when the largest |entry| lies outside [2^-400, 2^400] (squares would under/overflow), the
 // matrix is multiplied by an exact power of two on load and the eigenvalues by its inverse on output.  Returns the factor
@@ -2216,7 +1055,6 @@ __global__ __launch_bounds__(256) void eigh_replay_kernel(int n, void* scratch, 
 //   K4  music_scan_kernel        a' Uan Uan' a = || a - Us Us' a ||^2  (a sum of squares: no cancellation at the peaks)
 // L >= A (empty noise space) and L <= 0 need no vectors; L beyond the LDS capacity of K3 falls back to the QL pipeline, whose kernels are
 // always enqueued behind K3 and return at once when K3 reports success in `ctl` (numDets lives on the device: no host decision).
-struct MusicCtl { enum { kRoute = 0, kLsub = 1 }; };     // ctl[kRoute]: 1 = subspace vectors delivered (kLsub of them; >= n: empty noise space)
 
 __device__ __forceinline__ double rcp_fast(double q) {   // 1/q: hardware estimate r0 + one third-order step  r0 (1 + h + h^2), h = 1 - q r0
   const double r0 = __builtin_amdgcn_rcp(q);
@@ -2648,139 +1486,6 @@ __global__ __launch_bounds__(256) void music2d_scan_kernel(const c64* __restrict
 // ================================================================= host side
 using namespace isac;
 
-int isac_covariance_on(isac_ctx* ctx, hipStream_t st, const isac_c64* d_grid, int64_t N, int32_t A, isac_c64* d_Ra);
-extern "C" int isac_covariance_dev(isac_ctx* ctx, const isac_c64* d_grid, int64_t N, int32_t A, isac_c64* d_Ra) {
-  ISAC_ENTER(ctx);
-  return isac_covariance_on(ctx, ctx->stream, d_grid, N, A, d_Ra);
-}
-// isac_profile_enable(ctx, 2): HIP events around exactly the wide covariance launch (bench.py's roofline entry when that launch is the longest of the CPI)
-#define ISAC_PROF_COV0(st) do { if (ctx->profile_cov) ISAC_HIP(hipEventRecord(ctx->ev_k0, st)); } while (0)
-#define ISAC_PROF_COV1(st) do { if (ctx->profile_cov) { ISAC_HIP(hipEventRecord(ctx->ev_k1, st)); ctx->profile_recorded = true; } } while (0)
-template <int NB>
-static int launch_cov_small(isac_ctx* ctx, hipStream_t st, const c64* G, long long N, int A, c64* Ra) {
-  using P = CovPlan<NB>;
-  const long long total = (N + 15) / 16;
-  if (N * 256 >= (1ll << 32)) return fail(ctx, ISAC_ERR_UNSUPPORTED, "covariance: at most 2^24 - 1 samples per antenna");
-  long long gx = NB == 4 ? 512 : 768;       // NB = 4: 2 workgroups per CU (register-limited occupancy)
-  if (gx > total) gx = total;
-  long long per = (total + gx - 1) / gx;
-  const bool staged = (NB >= 3) && N * 256 < (1ll << 31);           // two tile groups: fetch each slab once per workgroup, through LDS
-  if (staged) { gx = 512 < total ? 512 : total; per = (total + gx - 1) / gx; per = (per + 1) & ~1ll; }   // (the staged kernel walks slabs in pairs)
-  gx = (total + per - 1) / per;
-  const int n_part = (int)gx * (staged ? 1 : P::kPhases);       // (the staged kernel sums its two sample phases itself)
-  ISAC_TRY(ensure(ctx, ctx->cov_part, sizeof(double) * ((size_t)n_part + 32) * P::kTiles * 2 * 256));
-  if constexpr (NB >= 3) {
-    if (staged) {
-      const size_t lds = sizeof(c64) * kCovLdsBufs * NB * 16 * kCovPitch;
-      ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(cov_mfma_lds_kernel<NB>), lds));
-      ISAC_PROF_COV0(st);
-      hipLaunchKernelGGL((cov_mfma_lds_kernel<NB>), dim3((unsigned)gx), dim3(256), lds, st, G, N, A, per, (double*)ctx->cov_part.p);
-      ISAC_HIP(hipGetLastError());
-      ISAC_PROF_COV1(st);
-    }
-  }
-  if (!staged) {
-    ISAC_PROF_COV0(st);
-    hipLaunchKernelGGL((cov_mfma_small_kernel<NB>), dim3((unsigned)gx), dim3(256), 0, st, G, N, A, per, (double*)ctx->cov_part.p);
-    ISAC_HIP(hipGetLastError());
-    ISAC_PROF_COV1(st);
-  }
-  const int S = 32;
-  double* part2 = (double*)ctx->cov_part.p + (size_t)n_part * P::kTiles * 2 * 256;
-  hipLaunchKernelGGL(cov_reduce_slice_kernel, dim3(P::kTiles, S), dim3(256), 0, st, (const double*)ctx->cov_part.p, n_part, P::kTiles, S,
-                     part2);
-  ISAC_HIP(hipGetLastError());
-  hipLaunchKernelGGL(cov_reduce_kernel, dim3(P::kTiles), dim3(256, 4), 0, st, (const double*)part2, S, P::kTiles, A,
-                     1.0 / (double)N, Ra, 1);
-  ISAC_HIP(hipGetLastError());
-  return ISAC_OK;
-}
-
-// Ra of the context's NATIVE lazy echo grid (ctx->lazy: isac_mono_static_sensing_fused_dev with d_echo_grid == NULL) -- fft2D.m:106-107 without the array.
-template <int QT>
-static int launch_cov_lazy(isac_ctx* ctx, hipStream_t st, const LazyCovArgs& a, long long n_slabs, long long per, long long gx, double* part) {
-  const size_t lds = sizeof(c64) * kCovLdsBufs * 4 * 16 * kCovPitch;
-  ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(cov_lazy_kernel<QT>), lds));
-  ISAC_PROF_COV0(st);
-  hipLaunchKernelGGL((cov_lazy_kernel<QT>), dim3((unsigned)gx), dim3(256), lds, st, a, n_slabs, per, part);
-  ISAC_HIP(hipGetLastError());
-  ISAC_PROF_COV1(st);
-  return ISAC_OK;
-}
-
-int isac_covariance_lazy_on(isac_ctx* ctx, hipStream_t st, isac_c64* d_Ra) {
-  const LazyEcho& lz = ctx->lazy;
-  if (!lz.valid || !lz.native || !d_Ra) return fail(ctx, ISAC_ERR_INVALID_ARG, "no native lazy echo grid on this context");
-  if (lz.A <= 48 || lz.A > 64 || lz.Q < 1 || lz.Q > 2) return fail(ctx, ISAC_ERR_UNSUPPORTED, "lazy covariance: 49..64 antennas, one or two LoS targets");
-  if ((long long)lz.K * lz.L_whole * 16 >= (1ll << 31)) return fail(ctx, ISAC_ERR_UNSUPPORTED, "lazy covariance: per-target grid of 2 GB or more");
-  using P = CovPlan<4>;
-  int s_col = 0;
-  for (int k0 = 0; k0 < lz.K; k0 += 1024) s_col += (std::min(512, lz.K - k0) + 7) / 8;
-  const long long n_slabs = (long long)lz.L_whole * s_col;
-  if (n_slabs <= 0 || n_slabs >= (1ll << 31) - 4) return fail(ctx, ISAC_ERR_UNSUPPORTED, "lazy covariance: slab count out of range");
-  long long gx = 512 < n_slabs ? 512 : n_slabs;
-  long long per = (n_slabs + gx - 1) / gx;
-  per = (per + 1) & ~1ll;                             // the kernel walks slabs in pairs
-  gx = (n_slabs + per - 1) / per;
-  const int n_part = (int)gx;
-  ISAC_TRY(ensure(ctx, ctx->cov_part, sizeof(double) * ((size_t)n_part + 32) * P::kTiles * 2 * 256));
-  LazyCovArgs a{(const c64*)ctx->dgrid.p, (const c64*)ctx->steer.p + (size_t)lz.A * lz.Q, lz.sig, lz.seed, lz.K, lz.L_whole, lz.L_out, lz.A, s_col};
-  if (lz.Q == 1) ISAC_TRY(launch_cov_lazy<1>(ctx, st, a, n_slabs, per, gx, (double*)ctx->cov_part.p));
-  else ISAC_TRY(launch_cov_lazy<2>(ctx, st, a, n_slabs, per, gx, (double*)ctx->cov_part.p));
-  const int S = 32;
-  double* part2 = (double*)ctx->cov_part.p + (size_t)n_part * P::kTiles * 2 * 256;
-  hipLaunchKernelGGL(cov_reduce_slice_kernel, dim3(P::kTiles, S), dim3(256), 0, st, (const double*)ctx->cov_part.p, n_part, P::kTiles, S, part2);
-  ISAC_HIP(hipGetLastError());
-  hipLaunchKernelGGL(cov_reduce_kernel, dim3(P::kTiles), dim3(256, 4), 0, st, (const double*)part2, S, P::kTiles, lz.A,
-                     1.0 / ((double)lz.K * (double)lz.L_out), (c64*)d_Ra, 1);
-  ISAC_HIP(hipGetLastError());
-  return ISAC_OK;
-}
-
-int isac_covariance_on(isac_ctx* ctx, hipStream_t st, const isac_c64* d_grid, int64_t N, int32_t A, isac_c64* d_Ra) {
-  if (!d_grid || !d_Ra || N <= 0 || A <= 0) return fail(ctx, ISAC_ERR_INVALID_ARG, "bad arguments");
-  const int nb = (A + 15) / 16;
-  if (nb <= 4) {
-    switch (nb) {
-      case 1: return launch_cov_small<1>(ctx, st, (const c64*)d_grid, N, A, (c64*)d_Ra);
-      case 2: return launch_cov_small<2>(ctx, st, (const c64*)d_grid, N, A, (c64*)d_Ra);
-      case 3: return launch_cov_small<3>(ctx, st, (const c64*)d_grid, N, A, (c64*)d_Ra);
-      default: return launch_cov_small<4>(ctx, st, (const c64*)d_grid, N, A, (c64*)d_Ra);
-    }
-  }
-  {                                                  // 64 x 64 block pairs (any A > 64)
-    const int n_blk = (A + 63) / 64;
-    const int n_pairs = n_blk * (n_blk + 1) / 2;
-    const long long total = (N + 15) / 16;
-    long long n_chunks = 1024 / n_pairs;              // ~4 workgroups per CU over the launch, 2 resident
-    if (n_chunks < 1) n_chunks = 1;
-    if (n_chunks > total) n_chunks = total;
-    if (N * 256 >= (1ll << 31)) return fail(ctx, ISAC_ERR_UNSUPPORTED, "covariance of more than 64 antennas: at most 2^23 - 1 samples per antenna");
-    long long per = (total + n_chunks - 1) / n_chunks;
-    per = (per + 1) & ~1ll;                           // the kernel walks slabs in pairs
-    n_chunks = (total + per - 1) / per;
-    ISAC_TRY(ensure(ctx, ctx->cov_part, sizeof(double) * (size_t)n_chunks * n_pairs * 16 * 2 * 256));
-    ISAC_PROF_COV0(st);
-    if (N * 512 < (1ll << 31)) {       // (32 antennas per staging descriptor: 32-bit offsets up to N x 31 x 16 B)
-      const size_t lds = sizeof(c64) * kCovUImgs * kCovUImg;
-      ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(cov_mfma_block_pl_kernel), (size_t)(lds)));
-      hipLaunchKernelGGL(cov_mfma_block_pl_kernel, dim3((unsigned)(n_chunks * n_pairs)), dim3(256), lds, st, (const c64*)d_grid, (long long)N, A,
-                         n_blk, n_pairs, 2 * per, (double*)ctx->cov_part.p);
-    } else {
-      const size_t lds = sizeof(c64) * 2 * kCovBufElems;
-      ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(cov_mfma_block_kernel), (size_t)(lds)));
-      hipLaunchKernelGGL(cov_mfma_block_kernel, dim3((unsigned)(n_chunks * n_pairs)), dim3(256), lds, st, (const c64*)d_grid, (long long)N, A,
-                         n_blk, n_pairs, per, (double*)ctx->cov_part.p);
-    }
-    ISAC_HIP(hipGetLastError());
-    ISAC_PROF_COV1(st);
-    hipLaunchKernelGGL(cov_block_reduce_kernel, dim3(16, n_pairs), dim3(256, 4), 0, st, (const double*)ctx->cov_part.p, (int)n_chunks,
-                       n_blk, n_pairs, A, 1.0 / (double)N, (c64*)d_Ra);
-    ISAC_HIP(hipGetLastError());
-    return ISAC_OK;
-  }
-}
-
 // launches of eigh_tridiag_dist_kernel in this process: consecutive ones (of any context) go to consecutive XCDs, so that concurrent reductions of a
 // multi-context pipeline do not compete for the workgroup slots of one XCD (each needs its <= 16 workgroups resident together)
 static std::atomic<unsigned> td_launches{0};
@@ -2873,7 +1578,7 @@ static int launch_ql(isac_ctx* ctx, int n, hipStream_t st, int* info, const int*
 // zungtr blocks never wait for the replay blocks -- so the eigenvectors are formed by the offline replay, as on the fallback route.
 int isac_eigh_replay_recover(isac_ctx* ctx, int n, hipStream_t st) {
   if (!st) st = ctx->stream;
-  int* info = reinterpret_cast<int*>((char*)ctx->eig_w.p + sizeof(double) * (size_t)n);
+  int* info = eig_info(ctx, n);
   ISAC_HIP(hipMemsetAsync(info, 0, sizeof(int), st));                 // the time-out mark; the replay below cannot time out
   return launch_replay_offline(ctx, n, st, info, nullptr);
 }
@@ -2890,8 +1595,7 @@ int isac_music_tridiag_bisect_dev(isac_ctx* ctx, const c64* d_H, int A, hipStrea
   ISAC_TRY(ensure(ctx, ctx->eig_w, sizeof(double) * (size_t)A + 64));
   ISAC_TRY(ensure(ctx, ctx->eig_v, sizeof(c64) * (size_t)A * A));
   ISAC_TRY(ensure(ctx, ctx->misc, 512));
-  int* info = reinterpret_cast<int*>((char*)ctx->eig_w.p + sizeof(double) * (size_t)A);
-  ISAC_TRY(launch_tridiag(ctx, d_H, n, st, info));
+  ISAC_TRY(launch_tridiag(ctx, d_H, n, st, eig_info(ctx, A)));
   const size_t lds = sizeof(c64) * (size_t)n + sizeof(double) * 48 + 64;
   hipLaunchKernelGGL(eigh_bisect_kernel, dim3((unsigned)((n + kBisectWaves - 1) / kBisectWaves)), dim3(64 * kBisectWaves), lds, st, n, ctx->eig_scratch.p,
                      (double*)ctx->eig_w.p);
@@ -2903,7 +1607,7 @@ int isac_music_tridiag_bisect_dev(isac_ctx* ctx, const c64* d_H, int A, hipStrea
 int isac_music_subspace_dev(isac_ctx* ctx, int A, const int* d_num_dets, int num_dets_host, hipStream_t st) {
   if (!st) st = ctx->stream;
   const int n = A;
-  int* info = reinterpret_cast<int*>((char*)ctx->eig_w.p + sizeof(double) * (size_t)A);
+  int* info = eig_info(ctx, A);
   int* ctl = music_ctl(ctx);
   int lmax = (int)(122880 / (32 * (size_t)n));
   lmax = lmax > 32 ? 32 : (lmax < 1 ? 1 : lmax);
@@ -2933,7 +1637,7 @@ int isac_eigh_dev(isac_ctx* ctx, const c64* d_H, int A, hipStream_t st, bool liv
   // 64, the tridiagonal pipeline 0.10 / 0.17 / 0.24 / 0.33 / 0.57 / 0.86 ms: Jacobi up to 16 antennas, the pipeline beyond
   ISAC_TRY(ensure(ctx, ctx->eig_w, sizeof(double) * (size_t)A + 64));
   ISAC_TRY(ensure(ctx, ctx->eig_v, sizeof(c64) * (size_t)A * A));
-  int* info = reinterpret_cast<int*>((char*)ctx->eig_w.p + sizeof(double) * (size_t)A);
+  int* info = eig_info(ctx, A);
   if (A > kJacobiMaxA) {
     ISAC_TRY(launch_tridiag(ctx, d_H, A, st, info));
     return launch_ql(ctx, A, st, info, nullptr, live_replay);

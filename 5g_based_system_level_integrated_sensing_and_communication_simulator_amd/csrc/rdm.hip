@@ -16,9 +16,8 @@
 // kernel evaluates just the needed Doppler bins, and |.|^2 is written as a small power window.
 #include <type_traits>
 
+#include "isac_internal.hpp"
 #include "fft_lds.hpp"
-
-int isac_get_w512_pack(isac_ctx* ctx, const isac::c64** out);   // capi.hip
 
 namespace isac {
 
@@ -525,10 +524,6 @@ __global__ __launch_bounds__(256) void doppler_full_kernel(const c64* __restrict
 // ================================================================= host side
 using namespace isac;
 
-int isac_get_twiddles(isac_ctx* ctx, int n, const c64** out);        // capi.hip
-int isac_get_twiddles2(isac_ctx* ctx, int n, const c64** out);       // capi.hip (second slot)
-int isac_get_windows(isac_ctx* ctx, int K, int n_ifft, const double** win_k, const double** win_r);   // capi.hip
-
 static double cfar_alpha(int n_train, double pfa) { return n_train * (std::pow(pfa, -1.0 / n_train) - 1.0); }
 
 static unsigned fft_grid2(int n_cols) { return (unsigned)n_cols; }   // one column per workgroup
@@ -584,7 +579,7 @@ int isac_rdm_power_window(isac_ctx* ctx, const isac_est_params* ep, const isac_c
   const c64 *tw = nullptr, *twd = nullptr;
   const double *wk = nullptr, *wr = nullptr;
   ISAC_TRY(isac_get_twiddles(ctx, n_ifft, &tw));
-  ISAC_TRY(isac_get_twiddles2(ctx, n_fft, &twd));
+  ISAC_TRY(isac_get_twiddles(ctx, n_fft, &twd));
   ISAC_TRY(isac_get_windows(ctx, K, n_ifft, &wk, &wr));
   ISAC_TRY(ensure(ctx, ctx->ymid, sizeof(c64) * (size_t)nr * L * A));
   ISAC_TRY(ensure(ctx, ctx->pwin, sizeof(double) * (size_t)nr * nc * A));
@@ -783,7 +778,7 @@ extern "C" int isac_rdm_plane_dev(isac_ctx* ctx, const isac_est_params* ep, cons
   const c64 *tw = nullptr, *twd = nullptr;
   const double *wk = nullptr, *wr = nullptr;
   ISAC_TRY(isac_get_twiddles(ctx, n_ifft, &tw));
-  ISAC_TRY(isac_get_twiddles2(ctx, n_fft, &twd));
+  ISAC_TRY(isac_get_twiddles(ctx, n_fft, &twd));
   ISAC_TRY(isac_get_windows(ctx, K, n_ifft, &wk, &wr));
   ISAC_TRY(ensure(ctx, ctx->stage_a, sizeof(c64) * (size_t)n_ifft * L));
   const c64* rx = (const c64*)d_rx_grid + (size_t)K * L * ant;

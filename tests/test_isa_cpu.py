@@ -81,6 +81,11 @@ def music_co(tmp_path_factory):
     return CodeObject(str(tmp_path_factory.mktemp("isa_music")), "music")
 
 
+@pytest.fixture(scope="module")
+def cov_co(tmp_path_factory):
+    return CodeObject(str(tmp_path_factory.mktemp("isa_cov")), "cov")
+
+
 def vm_waits(asm):
     return [int(m.group(1)) for ln in asm for m in [re.search(r"s_waitcnt.*vmcnt\((\d+)\)", ln)] if m]
 
@@ -111,10 +116,10 @@ def test_lazy_fused_kernel_has_no_echo_grid_store(echo_co, q, group):
 
 
 @pytest.mark.parametrize("q", [1, 2])
-def test_lazy_covariance_kernel_shape(music_co, q):
+def test_lazy_covariance_kernel_shape(cov_co, q):
     """cov_lazy_kernel<Q>: two workgroups per CU (<= 256 registers, at most a handful of spilled registers at two targets), the 2 x 30 MFMAs of its two slab steps, no
     global load of the grid (only the D values: 2 Q per thread and slab), the generator's transcendentals between the MFMAs, no waterfall loop (uniform descriptors)."""
-    name, meta, asm = music_co.find("cov_lazy_kernel", f"ILi{q}E")
+    name, meta, asm = cov_co.find("cov_lazy_kernel", f"ILi{q}E")
     assert meta["vgpr_count"] <= 256 and meta["agpr_count"] == 0, meta
     assert meta["private_segment_fixed_size"] <= (0 if q == 1 else 32), meta
     mf = [i for i, ln in enumerate(asm) if ln.startswith("v_mfma_f64_16x16x4")]
@@ -133,8 +138,8 @@ def test_fused_kernel_fallback_forms_exist(echo_co):
         echo_co.find("echo_range_kernelILi%dELi1E" % q)
 
 
-def test_covariance_block_kernel_shape(music_co):
-    name, meta, asm = music_co.find("cov_mfma_block_kernel")
+def test_covariance_block_kernel_shape(cov_co):
+    name, meta, asm = cov_co.find("cov_mfma_block_kernel")
     assert meta["private_segment_fixed_size"] == 0 and meta["agpr_count"] == 0 and meta["vgpr_count"] <= 256, meta
     w = vm_waits(asm)
     assert sum(1 for x in w if x == 0) <= 4 and sum(1 for x in w if x > 0) >= 24, w   # staging loads stay in flight under the MFMAs
@@ -151,18 +156,18 @@ def test_covariance_block_kernel_shape(music_co):
     assert sum(1 for ln in asm if ln.startswith("v_mov_b64")) <= 220
 
 
-def test_covariance_small_kernel_budget(music_co):
-    name, meta, asm = music_co.find("cov_mfma_small_kernelILi4E")
+def test_covariance_small_kernel_budget(cov_co):
+    name, meta, asm = cov_co.find("cov_mfma_small_kernelILi4E")
     assert meta["private_segment_fixed_size"] == 0 and meta["agpr_count"] == 0 and meta["vgpr_count"] <= 240, meta   # two workgroups per CU
     w = vm_waits(asm)
     assert sum(1 for x in w if x == 0) <= 6 and len(w) >= 60, (len(w), sum(1 for x in w if x == 0))
 
 
-def test_covariance_staged_kernel_is_pipelined_inside_the_wave(music_co):
+def test_covariance_staged_kernel_is_pipelined_inside_the_wave(cov_co):
     """A = 33..64: on gfx950 every instruction of either wave of a SIMD waits while a v_mfma_f64 is pending (tools/cobench.hip), so the staged
     covariance kernel hides its LDS reads / staging writes / staging loads one by one behind its own MFMAs.  A scheduler change that regroups
     them into a burst in front of the MFMA run costs ~10 us per launch and no numerical test would notice."""
-    name, meta, asm = music_co.find("cov_mfma_lds_kernelILi4E")
+    name, meta, asm = cov_co.find("cov_mfma_lds_kernelILi4E")
     assert meta["private_segment_fixed_size"] == 0 and meta["agpr_count"] == 0 and meta["vgpr_count"] <= 248, meta   # two workgroups per CU
     mf = [i for i, ln in enumerate(asm) if ln.startswith("v_mfma_f64_16x16x4")]
     assert len(mf) == 120                                          # 2 tile groups x 2 unrolled slab steps x 30
@@ -176,10 +181,10 @@ def test_covariance_staged_kernel_is_pipelined_inside_the_wave(music_co):
         assert any(asm[j].startswith("v_mfma") for j in range(i - 3, i)) and any(asm[j].startswith("v_mfma") for j in range(i + 1, i + 4)), asm[i - 3:i + 4]
 
 
-def test_covariance_block_kernel_is_pipelined_inside_the_wave(music_co):
+def test_covariance_block_kernel_is_pipelined_inside_the_wave(cov_co):
     """cov_mfma_block_pl_kernel (A > 64): no scratch, <= 256 registers (two workgroups per CU), and the operand reads / staging writes / staging loads of a unit
     sit in the gaps of its MFMA stream -- at most a handful of instructions between two MFMAs except at the unit / diagonal-vs-off-diagonal seams."""
-    name, meta, asm = music_co.find("cov_mfma_block_pl_kernel")
+    name, meta, asm = cov_co.find("cov_mfma_block_pl_kernel")
     assert meta["private_segment_fixed_size"] == 0 and meta["vgpr_count"] <= 256, meta
     mf = [i for i, ln in enumerate(asm) if ln.startswith("v_mfma_f64_16x16x4")]
     assert len(mf) >= 200
@@ -211,10 +216,10 @@ def test_distributed_householder_kernel_exchange_code(music_co):
     assert sum(1 for ln in asm if ln.startswith("s_barrier")) <= 4
 
 
-def test_scratch_users_are_the_known_ones(echo_co, music_co):
+def test_scratch_users_are_the_known_ones(echo_co, music_co, cov_co):
     known = ("echo_range_kernelILi4E", "eigh_replay_kernel",       # spill a few registers by design
              "cov_lazy_kernelILi2E")                               # two targets, spread generator placement: 3 registers (16 B) beyond the 256 of two waves per SIMD
-    for co in (echo_co, music_co):
+    for co in (echo_co, music_co, cov_co):
         for n, m in co.meta.items():
             if m.get("private_segment_fixed_size", 0) > 0:
                 assert any(k in n for k in known), f"{n} uses {m['private_segment_fixed_size']} B of scratch"

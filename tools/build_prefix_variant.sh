@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B library for tools/stress_race.py: the tree's sources with the two round-5 fixes taken OUT again --
-#   (i)  upload_now = plain hipMemcpy on the NULL stream (before c98d090), (ii) the SINR mean copied back into a pageable stack variable (before c8f9239)
+#   (i)  copy_h2d = plain hipMemcpy on the NULL stream (before c98d090), (ii) the SINR mean copied back into a pageable stack variable (before c8f9239)
 # -> tools/_ab/libisac_hip_prefix.so (git-ignored; travels with gpurun).  Shows the NULL-stream race at a rate, or shows that it cannot be provoked.
 set -eu
 ROOT=$(cd "$(dirname "$0")/.." && pwd); PKG=$ROOT/5g_based_system_level_integrated_sensing_and_communication_simulator_amd
@@ -21,7 +21,7 @@ open(p, "w").write(s)
 PY
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -fno-gpu-rdc -Wno-unused-function -Wno-unused-variable -Wno-unused-value -Wno-unused-result -ffp-contract=on"
 cd $W/pkg/csrc
-for f in capi echo rdm music cdl cdl_os cqi los; do /opt/rocm/bin/hipcc $FLAGS -c $f.hip -o $f.o & done; wait
+for f in *.hip; do /opt/rocm/bin/hipcc $FLAGS -c $f -o ${f%.hip}.o & done; wait
 mkdir -p $ROOT/tools/_ab
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $ROOT/tools/_ab/libisac_hip_prefix.so *.o -Wl,-soname,libisac_hip.so -Wl,--no-undefined
 echo built tools/_ab/libisac_hip_prefix.so

@@ -9,7 +9,7 @@ W=/tmp/isac_var_$NAME; rm -rf $W; mkdir -p $W/pkg $W/include; cp -r $PKG/csrc $W
 if [ -n "$FILE" ]; then sed -i -E "$EXPR" $W/pkg/csrc/$FILE; else sed -i -E "$EXPR" $W/pkg/csrc/*.h* ; fi
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -fno-gpu-rdc -Wno-unused-function -Wno-unused-variable -Wno-unused-value -Wno-unused-result -ffp-contract=on"
 cd $W/pkg/csrc
-for f in capi echo rdm music cdl cdl_os cqi los; do /opt/rocm/bin/hipcc $FLAGS -c $f.hip -o $f.o & done; wait
+for f in *.hip; do /opt/rocm/bin/hipcc $FLAGS -c $f -o ${f%.hip}.o & done; wait
 mkdir -p $ROOT/tools/_ab
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $ROOT/tools/_ab/libisac_hip_$NAME.so *.o -Wl,-soname,libisac_hip.so -Wl,--no-undefined
 echo built tools/_ab/libisac_hip_$NAME.so

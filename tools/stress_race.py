@@ -2,7 +2,7 @@
 """Stress harness for the two single-case mismatches of the round-5 fuzz campaign (profiles/r05_fuzz_campaigns.txt):
 
   (i)  a host-array fft2D call whose |rdm|^2 window came back off by 1e-2 once in ~4 700 cases   -> attributed to hipMemcpy on the NULL stream racing the context's
-       non-blocking streams, fixed by upload_now (csrc/isac_common.hpp);
+       non-blocking streams, fixed by copy_h2d (csrc/isac_common.hpp);
   (ii) a cqiFromChannel call whose MEAN came back 60.88 instead of 69.06 once                      -> unexplained.
 
 N worker processes on ONE GPU, each with its own context, beside B CPU burner processes (host oversubscription, as in the 16-process xdist campaign), repeat
