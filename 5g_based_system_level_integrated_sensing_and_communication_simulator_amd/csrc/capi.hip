@@ -11,26 +11,6 @@
 
 using namespace isac;
 
-static int eig_status(isac_ctx* ctx, int A, bool ql_ran = true /* false: the signal-subspace kernel delivered, the QL pipeline returned at once */) {
-  int sweeps = 0;
-  ISAC_TRY(copy_d2h(ctx, &sweeps, eig_info(ctx, A), sizeof(int)));
-  static const bool force = std::getenv("ISAC_EIG_FORCE_REPLAY_TIMEOUT") != nullptr;   // test hook: take the recovery path on every call ...
-  if (force && ql_ran && sweeps >= 0 && A > 16 && ctx->eig_scratch.p) {
-    ISAC_HIP(hipMemset(ctx->eig_v.p, 0xFF, sizeof(c64) * (size_t)A * A));               // ... with the eigenvectors destroyed first
-    sweeps = -2;
-  }
-  if (sweeps == -2) {                                // live replay blocks gave up waiting: Z and the rotations are intact, replay them offline
-    ISAC_TRY(isac_eigh_replay_recover(ctx, A, ctx->stream));
-    ISAC_HIP(hipStreamSynchronize(ctx->stream));
-    ISAC_TRY(copy_d2h(ctx, &sweeps, eig_info(ctx, A), sizeof(int)));
-  }
-  if (sweeps < 0) return isac::fail(ctx, ISAC_ERR_HIP, sweeps == -1 ? "eigensolver: QL recurrence exceeded its rotation storage (no convergence)"
-                                                     : sweeps == -3 ? "eigensolver: the signal-subspace vectors are not finite (NaN / Inf in the covariance)"
-                                                     : sweeps == -4 ? "eigensolver: the distributed tridiagonalisation saw no progress for 2 s (its workgroups were not resident together)"
-                                                                     : "eigensolver: a replay block timed out waiting for the recurrence");
-  return ISAC_OK;
-}
-
 namespace {
 
 // ---- host math mirrors of the MATLAB helpers the reference calls (product code, not the oracle)
@@ -62,122 +42,6 @@ std::vector<double> kaiser_window(int n, double beta) {  // Signal Processing To
   for (int i = half - 1; i >= odd; --i) w[(size_t)o++] = h[(size_t)i];
   for (int i = 0; i < half; ++i) w[(size_t)o++] = h[(size_t)i];
   return w;
-}
-
-double sind_deg(double x) {  // degree-domain reduction: exact at multiples of 90, sind(180-p) == sind(p) bitwise
-  x = std::fmod(x, 360.0);
-  if (x > 180.0) x -= 360.0;
-  if (x < -180.0) x += 360.0;
-  if (x > 90.0) x = 180.0 - x;
-  if (x < -90.0) x = -180.0 - x;
-  const double ax = std::fabs(x);
-  const double k = M_PI / 180.0;
-  if (ax <= 45.0) return std::sin(x * k);
-  const double c = std::cos((90.0 - ax) * k);
-  return x < 0 ? -c : c;
-}
-
-double cosd_deg(double x) {  // cosd via sind(90 - |x|) (oracle/matlab_compat.py): even, exact zeros at +-90, cosd(p - 180) == -cosd(p) bitwise
-  return sind_deg(90.0 - std::fmod(std::fabs(x), 360.0));
-}
-
-// findpeaks(y,'NPeaks',L,'SortStr','descend'): strict maxima, first sample of plateaus, no end points,
-// stable descending sort (music.m:102).  Returns 0-based locations.
-std::vector<int> findpeaks_desc(const std::vector<double>& y, int npeaks) {
-  std::vector<int> idx;
-  const int n = (int)y.size();
-  for (int i = 0; i < n; ++i)
-    if (i == 0 || y[(size_t)i] != y[(size_t)i - 1]) idx.push_back(i);
-  std::vector<int> locs;
-  for (size_t k = 1; k + 1 < idx.size(); ++k) {
-    double a = y[(size_t)idx[k - 1]], b = y[(size_t)idx[k]], c = y[(size_t)idx[k + 1]];
-    if (b > a && b > c) locs.push_back(idx[k]);
-  }
-  std::stable_sort(locs.begin(), locs.end(), [&](int p, int q) { return y[(size_t)p] > y[(size_t)q]; });
-  if ((int)locs.size() > npeaks) locs.resize((size_t)npeaks);
-  return locs;
-}
-
-int determine_num_targets(const std::vector<double>& v_ascending) {  // music.m:109-125 (on eig()'s ascending order)
-  const int n = (int)v_ascending.size() - 1;
-  if (n < 1) return 1;
-  std::vector<double> delta((size_t)n);
-  for (int i = 0; i < n; ++i) delta[(size_t)i] = -(v_ascending[(size_t)i + 1] - v_ascending[(size_t)i]);
-  const int start = (int)std::ceil((n + 1) / 2.0) - 1;
-  double sum = 0.0;
-  for (int i = start; i < n; ++i) sum += delta[(size_t)i];
-  const double half_mean = sum / (double)(n - start);
-  int best = 0;
-  double bv = delta[0] - 2.0 * half_mean;
-  for (int i = 1; i < n; ++i) {
-    double v = delta[(size_t)i] - 2.0 * half_mean;
-    if (v > bv) { bv = v; best = i; }
-  }
-  return best + 1;
-}
-
-int upload(isac_ctx* ctx, DevBuf& b, const void* src, size_t bytes) {
-  ISAC_TRY(ensure(ctx, b, bytes));
-  ISAC_TRY(copy_h2d(ctx, b.p, src, bytes));           // (not hipMemcpy: see copy_h2d)
-  return ISAC_OK;
-}
-
-int scan_steps(const isac_est_params* ep) {
-  return (int)std::floor((ep->azimuth_scan_scale + 1.0) / ep->azimuth_scan_granularity);   // music.m:79
-}
-
-int get_sind_table(isac_ctx* ctx, const isac_est_params* ep, const double** out, int* n_steps) {
-  isac_ctx& t = *ctx;
-  auto key = std::make_pair((long long)std::llround(ep->azimuth_scan_scale * 1e6),
-                            (long long)std::llround(ep->azimuth_scan_granularity * 1e6));
-  const int n = scan_steps(ep);
-  if (n <= 0) return fail(ctx, ISAC_ERR_INVALID_ARG, "empty azimuth scan");
-  auto it = t.sind.find(key);
-  if (it == t.sind.end()) {
-    std::vector<double> s((size_t)n);
-    for (int a = 0; a < n; ++a) s[(size_t)a] = sind_deg(a * ep->azimuth_scan_granularity - ep->azimuth_scan_scale / 2.0);   // music.m:88
-    DevBuf b;
-    ISAC_TRY(upload(ctx, b, s.data(), sizeof(double) * s.size()));
-    it = t.sind.emplace(key, b).first;
-  }
-  *out = (const double*)it->second.p;
-  *n_steps = n;
-  return ISAC_OK;
-}
-
-// UPA scan grid (music.m:36-53): eSteps x aSteps points, row e at elevation (e-1) eGran - eMax/2, column a at azimuth (a-1) aGran - aMax/2.
-// Device table [sind(ele) eSteps | cosd(azi) aSteps | sind(azi) aSteps], made on the host once per grid.
-int get_doa2d_tables(isac_ctx* ctx, const isac_est_params* ep, const double** out, int* e_steps, int* a_steps) {
-  const double ag = ep->azimuth_scan_granularity, am = ep->azimuth_scan_scale, eg = ep->elevation_scan_granularity, em = ep->elevation_scan_scale;
-  if (!(ag > 0.0) || !(eg > 0.0) || !std::isfinite(am) || !std::isfinite(em)) return fail(ctx, ISAC_ERR_INVALID_ARG, "UPA DoA: scan scales / granularities");
-  const double ne = std::floor((em + 1.0) / eg), na = std::floor((am + 1.0) / ag);                     // music.m:42-43
-  if (!(ne >= 1.0) || !(na >= 1.0) || ne * na > (double)(1 << 26)) return fail(ctx, ISAC_ERR_INVALID_ARG, "UPA DoA: empty or oversized scan grid");
-  const int n_e = (int)ne, n_a = (int)na;
-  const std::vector<long long> key = {std::llround(am * 1e6), std::llround(ag * 1e6), std::llround(em * 1e6), std::llround(eg * 1e6)};
-  auto it = ctx->doa2d_tab.find(key);
-  if (it == ctx->doa2d_tab.end()) {
-    std::vector<double> t((size_t)n_e + 2 * (size_t)n_a);
-    for (int e = 0; e < n_e; ++e) t[(size_t)e] = sind_deg(e * eg - em / 2.0);                         // music.m:47,44
-    for (int a = 0; a < n_a; ++a) {
-      const double ph = a * ag - am / 2.0;                                                              // music.m:48
-      t[(size_t)n_e + a] = cosd_deg(ph);
-      t[(size_t)n_e + n_a + a] = sind_deg(ph);
-    }
-    DevBuf b;
-    ISAC_TRY(upload(ctx, b, t.data(), sizeof(double) * t.size()));
-    it = ctx->doa2d_tab.emplace(key, b).first;
-  }
-  *out = (const double*)it->second.p;
-  *e_steps = n_e;
-  *a_steps = n_a;
-  return ISAC_OK;
-}
-
-int check_upa_dims(isac_ctx* ctx, const isac_est_params* ep, int A) {   // radarParams.m:90,99 reshape to nTxAnts
-  if (ep->n_ants_x <= 0 || ep->n_ants_y <= 0 || (long long)ep->n_ants_x * ep->n_ants_y != A)
-    return fail(ctx, ISAC_ERR_INVALID_ARG, "UPA DoA: n_ants_x * n_ants_y must equal the number of antennas");
-  if (A > 256) return fail(ctx, ISAC_ERR_UNSUPPORTED, "UPA DoA: the 2-D scan supports up to 256 elements");
-  return ISAC_OK;
 }
 
 }  // namespace
@@ -597,18 +461,6 @@ extern "C" int isac_fft2d_dev(isac_ctx* ctx, const isac_est_params* ep, const is
 }
 
 static int fft2d_submit(isac_ctx* ctx, const isac_est_params* ep, const isac_cfar_config* cfar, const isac_c64* d_rx_grid,
-                        const isac_c64* d_tx_grid, int32_t K, int32_t L, int32_t A, bool use_cached_range);
-
-extern "C" int isac_fft2d_submit_dev(isac_ctx* ctx, const isac_est_params* ep, const isac_cfar_config* cfar,
-                                     const isac_c64* d_rx_grid, const isac_c64* d_tx_grid, int32_t K, int32_t L, int32_t A) {
-  return fft2d_submit(ctx, ep, cfar, d_rx_grid, d_tx_grid, K, L, A, false);
-}
-extern "C" int isac_fft2d_submit_cached_dev(isac_ctx* ctx, const isac_est_params* ep, const isac_cfar_config* cfar,
-                                            const isac_c64* d_rx_grid, const isac_c64* d_tx_grid, int32_t K, int32_t L, int32_t A) {
-  return fft2d_submit(ctx, ep, cfar, d_rx_grid, d_tx_grid, K, L, A, true);
-}
-
-static int fft2d_submit(isac_ctx* ctx, const isac_est_params* ep, const isac_cfar_config* cfar, const isac_c64* d_rx_grid,
                         const isac_c64* d_tx_grid, int32_t K, int32_t L, int32_t A, bool use_cached_range) {
   ISAC_ENTER(ctx);
   ctx->pending.active = false;
@@ -629,32 +481,14 @@ static int fft2d_submit(isac_ctx* ctx, const isac_est_params* ep, const isac_cfa
   ctx->last.valid = false;
   const c64* rx = (const c64*)d_rx_grid;
   const c64* tx = (const c64*)d_tx_grid;
-  const bool upa = ep->array_is_upa != 0;
-  int n_steps = 0;
-  const double* d_sind = nullptr;
   // MUSIC branch on the second stream, concurrent with the range-Doppler/CFAR branch:
   //   stream2: covariance (fp64 MFMA) -> eig (one CU)      stream: range IFFT -> Doppler -> CFAR
   ISAC_TRY(ensure(ctx, ctx->cov, sizeof(c64) * (size_t)A * A));
   ISAC_TRY(ensure(ctx, ctx->misc, 512));
-  const bool upa2d = upa && ctx->upa_doa != 0;                  // ISAC_OPT_UPA_DOA: the 2-D scan + find2DPeaks
-  const bool sub = (!upa || upa2d) && isac_music_subspace_ok(ctx, A);      // MUSIC needs the numDets signal vectors only (music.m:27-29)
-  if (!upa) {
-    ISAC_TRY(get_sind_table(ctx, ep, &d_sind, &n_steps));
-    ISAC_TRY(ensure(ctx, ctx->spec, sizeof(double) * (size_t)n_steps));
-  }
-  const double* d_tab2d = nullptr;
-  int e_steps = 0, a_steps = 0, cap2d = 0, first2d = 0;
-  if (upa2d) {                                                  // every buffer of the 2-D tail sized here, before anything is enqueued
-    ISAC_TRY(check_upa_dims(ctx, ep, A));
-    ISAC_TRY(get_doa2d_tables(ctx, ep, &d_tab2d, &e_steps, &a_steps));
-    cap2d = isac_doa2d_peak_cap(e_steps, a_steps);
-    first2d = std::min(cap2d, 256);                             // candidates that travel in the result copy; more: a second copy at collect
-    ISAC_TRY(ensure(ctx, ctx->doa2d_p, sizeof(double) * (size_t)e_steps * a_steps));
-    ISAC_TRY(ensure(ctx, ctx->doa2d_db, sizeof(double) * (size_t)e_steps * a_steps));
-    ISAC_TRY(ensure(ctx, ctx->doa2d_cand, sizeof(double) * (size_t)isac_doa2d_cand_doubles(cap2d)));
-    ISAC_TRY(ensure(ctx, ctx->doa2d_w, sizeof(double) * (size_t)A));
-  }
-  const int n_spec = upa2d ? isac_doa2d_cand_doubles(first2d) : n_steps;   // doubles of the pack's spectrum slot: the ULA spectrum, or [counter | first candidates]
+  DoaPlan pl;                                                   // tables and every buffer of the DoA tail, before anything is enqueued
+  ISAC_TRY(doa_plan(ctx, ep, A, /*mode: MUSIC*/ 0, &pl));
+  const int first2d = std::min(pl.cap2d, 256);                  // UPA: candidates that travel in the result copy; more: a second copy at collect
+  const int n_spec = pl.upa2d ? isac_doa2d_cand_doubles(first2d) : pl.n_steps;   // doubles of the pack's spectrum slot: the ULA spectrum, or [counter | first candidates]
   static const bool single_stream = std::getenv("ISAC_SINGLE_STREAM") != nullptr;   // diagnostic: one stream, isolated kernel times
   hipStream_t s2 = single_stream ? ctx->stream : ctx->stream2;
   // ISAC_OPT_WIDE_ORDER: the covariance (a wide kernel) stays on the main stream, behind the echo synthesis / range stage; everything
@@ -684,11 +518,8 @@ static int fft2d_submit(isac_ctx* ctx, const isac_est_params* ep, const isac_cfa
     else ISAC_TRY(isac_covariance_on(ctx, s2, d_rx_grid, (int64_t)K * L, A, (isac_c64*)ctx->cov.p));   // fft2D.m:106-107
     timeline_mark(ctx, 5, s2);
   }
-  auto eig_first_half = [&]() -> int {                                                           // music.m:19
-    if (upa && !upa2d) return ISAC_OK;
-    if (sub) return isac_music_tridiag_bisect_dev(ctx, (const c64*)ctx->cov.p, A, s2);           // reflectors + eigenvalues: independent of numDets
-    return isac_eigh_dev(ctx, (const c64*)ctx->cov.p, A, s2, /*live_replay=*/false);   // (collect cannot run the replay time-out recovery before the scan)
-  };
+  // music.m:19; nothing for a UPA that collect will refuse; no live replay: collect cannot run the replay time-out recovery before the scan
+  auto eig_first_half = [&] { return pl.refused() ? ISAC_OK : doa_eig_first_half(ctx, pl, (const c64*)ctx->cov.p, s2, /*live_replay=*/false); };
   // (wide order: the many-workgroup narrow kernels -- Doppler, CFAR panels, merge -- first, while the next CPI's beam-sum holds the main stream and
   // leaves registers free; the one-workgroup eigensolver kernels then sit under the next fused kernel, where they cost one CU each)
   if (!wide) ISAC_TRY(eig_first_half());
@@ -702,14 +533,7 @@ static int fft2d_submit(isac_ctx* ctx, const isac_est_params* ep, const isac_cfa
   ISAC_HIP(hipEventRecord(ctx->ev_cfar, ctx->stream));
   ISAC_HIP(hipStreamWaitEvent(s2, ctx->ev_cfar, 0));
   if (wide) ISAC_TRY(eig_first_half());
-  if (!upa) {   // numDets comes from the CFAR branch, still on the device                   music.m:12,82-91
-    if (sub) ISAC_TRY(isac_music_subspace_dev(ctx, A, (const int*)ctx->misc.p, 0, s2));          // the numDets signal vectors (or the QL fallback)
-    ISAC_TRY(isac_music_scan_dev(ctx, A, (const int*)ctx->misc.p, 0, d_sind, n_steps, 0.5, (double*)ctx->spec.p, s2, 0, sub ? isac_music_ctl(ctx) : nullptr));
-  } else if (upa2d) {   // music.m:31-63 on the 2-D grid + the device half of find2DPeaks, numDets still on the device
-    if (sub) ISAC_TRY(isac_music_subspace_dev(ctx, A, (const int*)ctx->misc.p, 0, s2));
-    ISAC_TRY(isac_doa2d_scan_dev(ctx, 0, ep->n_ants_x, ep->n_ants_y, e_steps, a_steps, d_tab2d, (const int*)ctx->misc.p, 0, sub ? isac_music_ctl(ctx) : nullptr, s2));
-    ISAC_TRY(isac_doa2d_norm_peaks_dev(ctx, true, (const double*)ctx->doa2d_db.p, e_steps, a_steps, (double*)ctx->doa2d_cand.p, cap2d, s2));
-  }
+  ISAC_TRY(doa_enqueue(ctx, pl, (const int*)ctx->misc.p, 0, s2));   // numDets comes from the CFAR branch, still on the device   music.m:12
   ISAC_HIP(hipEventRecord(ctx->ev_join, s2));
   ISAC_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
   // pack + one device->host copy
@@ -732,8 +556,8 @@ static int fft2d_submit(isac_ctx* ctx, const isac_est_params* ep, const isac_cfa
   int* d_pcut_full = (int*)((char*)ctx->stage_b.p + sizeof(double) * pack_cap);
   hipLaunchKernelGGL(pack_kernel, dim3(1), dim3(256), 0, ctx->stream, (const int*)ctx->det_cnt.p, (const int*)ctx->det_cut.p,
                      (const double*)ctx->det_pow.p, (const int*)ctx->misc.p, A, cap, (int*)dbase, d_pcut_full, d_ppow_full,
-                     pack_first, d_pcut_first, d_ppow_first, upa2d ? (const double*)ctx->doa2d_cand.p : (const double*)ctx->spec.p, n_spec,
-                     (double*)(dbase + off_spec), (upa && !upa2d) ? nullptr : eig_info(ctx, A));
+                     pack_first, d_pcut_first, d_ppow_first, pl.upa2d ? (const double*)ctx->doa2d_cand.p : (const double*)ctx->spec.p, n_spec,
+                     (double*)(dbase + off_spec), pl.refused() ? nullptr : eig_info(ctx, A));
   ISAC_HIP(hipGetLastError());
   char* h = (char*)ctx->pinned;
   ISAC_HIP(hipMemcpyAsync(h, dbase, first_bytes, hipMemcpyDeviceToHost, ctx->stream));
@@ -743,12 +567,21 @@ static int fft2d_submit(isac_ctx* ctx, const isac_est_params* ep, const isac_cfa
   // everything the host half needs later
   Fft2dPending& pd = ctx->pending;
   pd.ep = *ep; pd.cfar = *cfar;
-  pd.A = A; pd.nr = nr; pd.nc = nc; pd.n_steps = n_steps; pd.pack_first = pack_first;
+  pd.A = A; pd.nr = nr; pd.nc = nc; pd.pack_first = pack_first;
   pd.off_spec = off_spec; pd.off_pow = off_pow; pd.off_cut = off_cut;
   pd.d_pcut_full = d_pcut_full; pd.d_ppow_full = d_ppow_full;
-  pd.upa2d = upa2d; pd.e_steps = e_steps; pd.a_steps = a_steps; pd.cap2d = cap2d; pd.first2d = first2d;
+  pd.doa = pl; pd.first2d = first2d;
   pd.active = true;
   return ISAC_OK;
+}
+
+extern "C" int isac_fft2d_submit_dev(isac_ctx* ctx, const isac_est_params* ep, const isac_cfar_config* cfar,
+                                     const isac_c64* d_rx_grid, const isac_c64* d_tx_grid, int32_t K, int32_t L, int32_t A) {
+  return fft2d_submit(ctx, ep, cfar, d_rx_grid, d_tx_grid, K, L, A, false);
+}
+extern "C" int isac_fft2d_submit_cached_dev(isac_ctx* ctx, const isac_est_params* ep, const isac_cfar_config* cfar,
+                                            const isac_c64* d_rx_grid, const isac_c64* d_tx_grid, int32_t K, int32_t L, int32_t A) {
+  return fft2d_submit(ctx, ep, cfar, d_rx_grid, d_tx_grid, K, L, A, true);
 }
 
 extern "C" int isac_fft2d_collect(isac_ctx* ctx, isac_est_result* out) {
@@ -760,11 +593,10 @@ extern "C" int isac_fft2d_collect(isac_ctx* ctx, isac_est_result* out) {
   std::memset(out, 0, sizeof(*out));
   const isac_est_params* ep = &pd.ep;
   const isac_cfar_config* cfar = &pd.cfar;
-  const int A = pd.A, nr = pd.nr, nc = pd.nc, n_steps = pd.n_steps, pack_first = pd.pack_first;
+  const int A = pd.A, nr = pd.nr, nc = pd.nc, pack_first = pd.pack_first;
   const size_t off_spec = pd.off_spec, off_pow = pd.off_pow, off_cut = pd.off_cut;
   int* d_pcut_full = pd.d_pcut_full;
   double* d_ppow_full = pd.d_ppow_full;
-  const bool upa = ep->array_is_upa != 0;
   const int n_cut_rows = cfar->row1 - cfar->row0 + 1;
   char* h = (char*)ctx->pinned;
   ISAC_HIP(hipEventSynchronize(ctx->ev_done));      // (not the stream: contexts that share streams have later CPIs queued behind this one)
@@ -838,44 +670,12 @@ extern "C" int isac_fft2d_collect(isac_ctx* ctx, isac_est_result* out) {
   for (size_t i = 0; i < ucol.size(); ++i) out->vel_est[i] = ((double)ucol[i] - ep->n_fft / 2.0 - 1.0) * ep->v_res;   // :78,:82
   last.valid = true;
   last.spectrum_db.clear();
-  if (upa && !pd.upa2d) return fail(ctx, ISAC_ERR_UNSUPPORTED, "UPA DoA: music.m:69 calls tools.find2DPeaks, which the reference does not define");
-  if (upa) {   // ---- 2-D DoA, music.m:65-71 (ISAC_OPT_UPA_DOA)
-    const double* cand = (const double*)(h + off_spec);
-    const int count = (int)*(const unsigned*)cand;
-    if (count > pd.cap2d) return fail(ctx, ISAC_ERR_HIP, "find2DPeaks: candidate count beyond the 2 x 2 bound (internal error)");
-    std::vector<double> full;
-    if (count > pd.first2d) {
-      full.resize((size_t)isac_doa2d_cand_doubles(count));
-      ISAC_TRY(copy_d2h(ctx, full.data(), ctx->doa2d_cand.p, sizeof(double) * full.size()));
-      cand = full.data();
-    }
-    ctx->doa2d_rows = pd.e_steps;
-    ctx->doa2d_cols = pd.a_steps;
-    if (out->num_dets == 0)
-      return fail(ctx, ISAC_ERR_NO_DETECTION, "no CFAR detection: find2DPeaks needs a positive number of peaks (music.m:69)");
-    std::vector<int> ele, azi;
-    ISAC_TRY(isac_doa2d_select(ctx, cand, count, pd.cap2d, pd.e_steps, out->num_dets, ele, azi));
-    out->n_azi = (int)std::min<size_t>(azi.size(), ISAC_MAX_EST);
-    for (int i = 0; i < out->n_azi; ++i) {
-      out->ele_est[i] = (ele[(size_t)i] - 1) * ep->elevation_scan_granularity - ep->elevation_scan_scale / 2.0;   // music.m:70
-      out->azi_est[i] = (azi[(size_t)i] - 1) * ep->azimuth_scan_granularity - ep->azimuth_scan_scale / 2.0;       // music.m:71
-    }
-    return ISAC_OK;
-  }
-  // ---- DoA, music.m:94-104
-  const double* spec = (const double*)(h + off_spec);
-  double mx = 0.0;
-  for (int i = 0; i < n_steps; ++i) mx = std::max(mx, std::fabs(spec[i]));
-  last.spectrum_db.resize((size_t)n_steps);
-  for (int i = 0; i < n_steps; ++i) last.spectrum_db[(size_t)i] = 20.0 * std::log10(std::fabs(spec[i]) / mx);   // :94-96
-  if (out->num_dets == 0)
-    return fail(ctx, ISAC_ERR_NO_DETECTION, "no CFAR detection: findpeaks 'NPeaks' must be a positive integer (music.m:102)");
-  const std::vector<int> locs = findpeaks_desc(last.spectrum_db, out->num_dets);                             // :102
-  out->n_azi = (int)std::min<size_t>(locs.size(), ISAC_MAX_EST);
-  for (int i = 0; i < out->n_azi; ++i) {
-    out->azi_est[i] = locs[(size_t)i] * ep->azimuth_scan_granularity - ep->azimuth_scan_scale / 2.0;           // :103
-    out->ele_est[i] = NAN;                                                                                  // :104
-  }
+  if (pd.doa.refused()) return fail(ctx, ISAC_ERR_UNSUPPORTED, kUpaRefused);
+  // ---- DoA: music.m:94-104 (ULA), :65-71 (UPA) from the pack's spectrum slot
+  std::vector<double> ele, azi;
+  ISAC_TRY(doa_readout(ctx, pd.doa, ep, (const double*)(h + off_spec), pd.first2d, out->num_dets, "no CFAR detection: ", ele, azi));
+  out->n_azi = (int)std::min<size_t>(azi.size(), ISAC_MAX_EST);
+  doa_store(ele, azi, out->n_azi, out->ele_est, out->azi_est);
   return ISAC_OK;
 }
 
@@ -992,160 +792,6 @@ extern "C" int isac_fft2d_get_music_spectrum(isac_ctx* ctx, double* p_db, int32_
   return ISAC_OK;
 }
 
-// ------------------------------------------------------------------ stand-alone MUSIC / eig
-extern "C" int isac_eigh(isac_ctx* ctx, const isac_c64* H, int32_t A, double* w, isac_c64* V) {
-  ISAC_ENTER(ctx);
-  if (!H || !w || A <= 0) return fail(ctx, ISAC_ERR_INVALID_ARG, "bad arguments");
-  ISAC_TRY(ensure(ctx, ctx->stage_c, sizeof(c64) * (size_t)A * A));
-  ISAC_TRY(copy_h2d(ctx, ctx->stage_c.p, H, sizeof(c64) * (size_t)A * A));
-  ISAC_TRY(isac_eigh_dev(ctx, (const c64*)ctx->stage_c.p, A, nullptr));
-  std::vector<double> wv((size_t)A);
-  std::vector<c64> vv((size_t)A * A);
-  ISAC_TRY(copy_d2h(ctx, wv.data(), ctx->eig_w.p, sizeof(double) * (size_t)A));
-  ISAC_TRY(copy_d2h(ctx, vv.data(), ctx->eig_v.p, sizeof(c64) * (size_t)A * A));
-  ISAC_HIP(hipStreamSynchronize(ctx->stream));
-  ISAC_TRY(eig_status(ctx, A));
-  if (std::getenv("ISAC_DEBUG")) {                 // diagnostic: eigensolver phase counters on stderr
-    int inf[16] = {-1, 0, 0, 0, 0, 0};
-    ISAC_TRY(copy_d2h(ctx, inf, eig_info(ctx, A), sizeof(inf)));
-    if (A > 64 && A <= 256)
-      std::fprintf(stderr, "[isac] eigh A=%d distributed tridiagonalisation, phases(x64 clk): column + p published=%d exchange wait=%d vector work=%d rank-2 update=%d\n", A,
-                   inf[12], inf[13], inf[14], inf[15]);
-    if (inf[5] < 0)
-      std::fprintf(stderr, "[isac] eigh A=%d Jacobi sweeps=%d phases(x64 clk): rotation parameters=%d two-sided updates=%d\n", A, inf[0], inf[1], inf[2]);
-    else
-      std::fprintf(stderr, "[isac] eigh A=%d QL sweeps=%d rotations=%d phases(x64 clk): tridiag=%d formQ=%d ql-recurrence=%d replay=%d\n", A, inf[0],
-                   inf[5], inf[1], inf[2], inf[3], inf[4]);
-  }
-  std::vector<int> order((size_t)A);
-  std::iota(order.begin(), order.end(), 0);
-  std::stable_sort(order.begin(), order.end(), [&](int p, int q) { return wv[(size_t)p] < wv[(size_t)q]; });
-  for (int i = 0; i < A; ++i) {
-    w[i] = wv[(size_t)order[(size_t)i]];
-    if (V) std::memcpy(V + (size_t)A * i, vv.data() + (size_t)A * order[(size_t)i], sizeof(c64) * (size_t)A);
-  }
-  return ISAC_OK;
-}
-
-static int doa_scan(isac_ctx* ctx, int mode, int32_t num_dets, const isac_est_params* ep, const isac_c64* Ra, int32_t A,
-                    int32_t* L_out, double* azi_est, double* ele_est, int32_t cap, int32_t* n_est) {
-  ISAC_ENTER(ctx);
-  if (!ep || !Ra || A <= 0 || !n_est) return fail(ctx, ISAC_ERR_INVALID_ARG, "bad arguments");
-  *n_est = 0;
-  ISAC_TRY(ensure(ctx, ctx->stage_c, sizeof(c64) * (size_t)A * A));
-  ISAC_TRY(copy_h2d(ctx, ctx->stage_c.p, Ra, sizeof(c64) * (size_t)A * A));
-  const bool upa2d = ep->array_is_upa && ctx->upa_doa;                                            // ISAC_OPT_UPA_DOA
-  if (upa2d) ISAC_TRY(check_upa_dims(ctx, ep, A));
-  const bool sub = mode == 0 && (!ep->array_is_upa || upa2d) && isac_music_subspace_ok(ctx, A);   // MUSIC: the L signal vectors are enough
-  if (sub) ISAC_TRY(isac_music_tridiag_bisect_dev(ctx, (const c64*)ctx->stage_c.p, A, nullptr));
-  else ISAC_TRY(isac_eigh_dev(ctx, (const c64*)ctx->stage_c.p, A, nullptr));                               // music.m:19
-  int L = num_dets;
-  if (num_dets < 0) {                                                                              // music.m:21-22
-    std::vector<double> wv((size_t)A);
-    ISAC_TRY(copy_d2h(ctx, wv.data(), ctx->eig_w.p, sizeof(double) * (size_t)A));
-    ISAC_HIP(hipStreamSynchronize(ctx->stream));
-    std::sort(wv.begin(), wv.end());
-    L = determine_num_targets(wv);
-  }
-  if (sub) ISAC_TRY(isac_music_subspace_dev(ctx, A, nullptr, L, nullptr));
-  if (L_out) *L_out = L;
-  if (ep->array_is_upa && !upa2d) return fail(ctx, ISAC_ERR_UNSUPPORTED, "UPA DoA: music.m:69 calls tools.find2DPeaks, which the reference does not define");
-  if (upa2d) {   // music.m:31-71 / digitalBF.m:13-53 / mvdrBF.m:13-53
-    const double* d_tab = nullptr;
-    int e_steps = 0, a_steps = 0;
-    ISAC_TRY(get_doa2d_tables(ctx, ep, &d_tab, &e_steps, &a_steps));
-    const int cap2d = isac_doa2d_peak_cap(e_steps, a_steps);
-    ISAC_TRY(ensure(ctx, ctx->doa2d_db, sizeof(double) * (size_t)e_steps * a_steps));
-    ISAC_TRY(ensure(ctx, ctx->doa2d_cand, sizeof(double) * (size_t)isac_doa2d_cand_doubles(cap2d)));
-    ISAC_TRY(isac_doa2d_scan_dev(ctx, mode, ep->n_ants_x, ep->n_ants_y, e_steps, a_steps, d_tab, nullptr, L, sub ? isac_music_ctl(ctx) : nullptr, nullptr));
-    ISAC_TRY(isac_doa2d_norm_peaks_dev(ctx, true, (const double*)ctx->doa2d_db.p, e_steps, a_steps, (double*)ctx->doa2d_cand.p, cap2d, nullptr));
-    unsigned count = 0;
-    ISAC_TRY(copy_d2h(ctx, &count, ctx->doa2d_cand.p, sizeof(count)));
-    ISAC_HIP(hipStreamSynchronize(ctx->stream));
-    ISAC_TRY(eig_status(ctx, A));
-    ctx->doa2d_rows = e_steps;
-    ctx->doa2d_cols = a_steps;
-    if (L <= 0) return fail(ctx, ISAC_ERR_NO_DETECTION, "find2DPeaks needs a positive number of peaks (music.m:69)");
-    if ((int)count > cap2d) return fail(ctx, ISAC_ERR_HIP, "find2DPeaks: candidate count beyond the 2 x 2 bound (internal error)");
-    std::vector<double> cand((size_t)isac_doa2d_cand_doubles((int)count));
-    ISAC_TRY(copy_d2h(ctx, cand.data(), ctx->doa2d_cand.p, sizeof(double) * cand.size()));
-    std::vector<int> ele, azi;
-    ISAC_TRY(isac_doa2d_select(ctx, cand.data(), (int)count, cap2d, e_steps, L, ele, azi));
-    if ((int)azi.size() > cap) return fail(ctx, ISAC_ERR_CAPACITY, "more peaks than capacity");
-    *n_est = (int)azi.size();
-    for (size_t i = 0; i < azi.size(); ++i) {
-      if (ele_est) ele_est[i] = (ele[i] - 1) * ep->elevation_scan_granularity - ep->elevation_scan_scale / 2.0;   // music.m:70
-      if (azi_est) azi_est[i] = (azi[i] - 1) * ep->azimuth_scan_granularity - ep->azimuth_scan_scale / 2.0;       // music.m:71
-    }
-    return ISAC_OK;
-  }
-  int n_steps = 0;
-  const double* d_sind = nullptr;
-  ISAC_TRY(get_sind_table(ctx, ep, &d_sind, &n_steps));
-  ISAC_TRY(ensure(ctx, ctx->spec, sizeof(double) * (size_t)n_steps));
-  ISAC_TRY(isac_music_scan_dev(ctx, A, nullptr, L, d_sind, n_steps, 0.5, (double*)ctx->spec.p, nullptr, mode, sub ? isac_music_ctl(ctx) : nullptr));
-  std::vector<double> spec((size_t)n_steps);
-  ISAC_TRY(copy_d2h(ctx, spec.data(), ctx->spec.p, sizeof(double) * (size_t)n_steps));
-  ISAC_HIP(hipStreamSynchronize(ctx->stream));
-  ISAC_TRY(eig_status(ctx, A));
-  double mx = 0.0;
-  for (double v : spec) mx = std::max(mx, std::fabs(v));
-  std::vector<double> db((size_t)n_steps);
-  for (int i = 0; i < n_steps; ++i) db[(size_t)i] = 20.0 * std::log10(std::fabs(spec[(size_t)i]) / mx);
-  ctx->last.spectrum_db = db;
-  if (L <= 0) return fail(ctx, ISAC_ERR_NO_DETECTION, "findpeaks 'NPeaks' must be a positive integer (music.m:102)");
-  const std::vector<int> locs = findpeaks_desc(db, L);
-  if ((int)locs.size() > cap) return fail(ctx, ISAC_ERR_CAPACITY, "more peaks than capacity");
-  *n_est = (int)locs.size();
-  for (size_t i = 0; i < locs.size(); ++i) {
-    if (azi_est) azi_est[i] = locs[i] * ep->azimuth_scan_granularity - ep->azimuth_scan_scale / 2.0;
-    if (ele_est) ele_est[i] = NAN;
-  }
-  return ISAC_OK;
-}
-
-// eigenvalues (all, ascending) + the eigenvectors of the n_top largest, through MUSIC's signal-subspace route
-extern "C" int isac_eigh_top(isac_ctx* ctx, const isac_c64* H, int32_t A, int32_t n_top, double* w, isac_c64* U) {
-  ISAC_ENTER(ctx);
-  if (!H || !w || A <= 0 || n_top < 0 || n_top > A || (n_top > 0 && !U)) return fail(ctx, ISAC_ERR_INVALID_ARG, "bad arguments");
-  if (A < 3 || A > 256) return fail(ctx, ISAC_ERR_UNSUPPORTED, "isac_eigh_top: orders 3..256 (use isac_eigh)");
-  ISAC_TRY(ensure(ctx, ctx->stage_c, sizeof(c64) * (size_t)A * A));
-  ISAC_TRY(copy_h2d(ctx, ctx->stage_c.p, H, sizeof(c64) * (size_t)A * A));
-  ISAC_TRY(isac_music_tridiag_bisect_dev(ctx, (const c64*)ctx->stage_c.p, A, nullptr));
-  ISAC_TRY(copy_d2h(ctx, w, ctx->eig_w.p, sizeof(double) * (size_t)A));
-  ISAC_HIP(hipStreamSynchronize(ctx->stream));                      // (the fallback below overwrites eig_w with unsorted values)
-  if (n_top == 0) return ISAC_OK;
-  ISAC_TRY(isac_music_subspace_dev(ctx, A, nullptr, n_top, nullptr));
-  int ctl[2] = {0, 0};
-  ISAC_TRY(copy_d2h(ctx, ctl, isac_music_ctl(ctx), sizeof(ctl)));
-  ISAC_HIP(hipStreamSynchronize(ctx->stream));
-  ISAC_TRY(eig_status(ctx, A, ctl[0] != 1));
-  if (std::getenv("ISAC_DEBUG")) {                 // diagnostic: eigensolver phase counters on stderr
-    int inf[15] = {0};
-    ISAC_TRY(copy_d2h(ctx, inf, eig_info(ctx, A), sizeof(inf)));
-    std::fprintf(stderr, "[isac] eigh_top A=%d n_top=%d phases(x64 clk): tridiag=%d (n <= 64: reflector=%d matvec=%d matvec+update=%d) | subspace: set-up=%d solves=%d "
-                 "gram-schmidt=%d back-transform=%d\n", A, n_top, inf[1], inf[12], inf[13], inf[14], inf[8], inf[9], inf[10], inf[11]);
-  }
-  if (ctl[0] == 1 && n_top < A) {                                   // the subspace kernel delivered the vectors, descending eigenvalue order
-    ISAC_TRY(copy_d2h(ctx, U, ctx->eig_v.p, sizeof(c64) * (size_t)A * n_top));
-    ISAC_HIP(hipStreamSynchronize(ctx->stream));
-    return ISAC_OK;
-  }
-  // n_top beyond the subspace kernel's capacity (or the whole basis): the QL pipeline ran; pick the columns of the n_top largest
-  std::vector<double> wv((size_t)A);
-  std::vector<c64> vv((size_t)A * A);
-  if (n_top == A) ISAC_TRY(isac_eigh_dev(ctx, (const c64*)ctx->stage_c.p, A, nullptr));
-  ISAC_TRY(copy_d2h(ctx, wv.data(), ctx->eig_w.p, sizeof(double) * (size_t)A));   // (the context's streams are
-  ISAC_TRY(copy_d2h(ctx, vv.data(), ctx->eig_v.p, sizeof(c64) * (size_t)A * A));  //  non-blocking: stay on them)
-  ISAC_HIP(hipStreamSynchronize(ctx->stream));
-  ISAC_TRY(eig_status(ctx, A));
-  std::vector<int> order((size_t)A);
-  std::iota(order.begin(), order.end(), 0);
-  std::stable_sort(order.begin(), order.end(), [&](int p, int q) { return wv[(size_t)p] > wv[(size_t)q]; });
-  for (int i = 0; i < n_top; ++i) std::memcpy(U + (size_t)A * i, vv.data() + (size_t)A * order[(size_t)i], sizeof(c64) * (size_t)A);
-  return ISAC_OK;
-}
-
 extern "C" int isac_ctx_reserve(isac_ctx* ctx, int64_t T, int32_t tx_dim_l, const isac_carrier* carrier, const isac_radar_channel_params* rp,
                                 const isac_est_params* ep, const isac_cfar_config* cfar, double warm_ms, double* elapsed_ms) {
   ISAC_ENTER(ctx);
@@ -1229,146 +875,6 @@ hipEvent_t isac::timeline_base(hipStream_t st) {
   static hipEvent_t base = nullptr;
   if (!base) { (void)hipEventCreate(&base); (void)hipEventRecord(base, st); (void)hipEventSynchronize(base); }
   return base;
-}
-
-extern "C" int isac_music_doa(isac_ctx* ctx, int32_t num_dets, const isac_est_params* ep, const isac_c64* Ra, int32_t A,
-                              int32_t* L_out, double* azi_est, double* ele_est, int32_t cap, int32_t* n_est) {
-  return doa_scan(ctx, 0, num_dets, ep, Ra, A, L_out, azi_est, ele_est, cap, n_est);
-}
-extern "C" int isac_beamscan_doa(isac_ctx* ctx, int32_t method, int32_t num_dets, const isac_est_params* ep, const isac_c64* Ra,
-                                 int32_t A, double* azi_est, double* ele_est, int32_t cap, int32_t* n_est) {
-  if (method != 1 && method != 2) return fail(ctx, ISAC_ERR_INVALID_ARG, "method: 1 = digitalBF, 2 = mvdrBF");
-  if (num_dets < 0) return fail(ctx, ISAC_ERR_INVALID_ARG, "digitalBF / mvdrBF need numDets (digitalBF.m:84, mvdrBF.m:84)");
-  return doa_scan(ctx, method, num_dets, ep, Ra, A, nullptr, azi_est, ele_est, cap, n_est);
-}
-
-// ------------------------------------------------------------------ UPA angular spectrum / find2DPeaks (include/isac.h)
-extern "C" int isac_get_angular_spectrum2d(isac_ctx* ctx, double* p_db, int64_t cap, int32_t dims[2]) {
-  ISAC_ENTER(ctx);
-  if (ctx->doa2d_rows <= 0 || ctx->doa2d_cols <= 0) return fail(ctx, ISAC_ERR_INVALID_ARG, "no UPA DoA has run on this context");
-  if (dims) { dims[0] = ctx->doa2d_rows; dims[1] = ctx->doa2d_cols; }
-  if (!p_db) return ISAC_OK;
-  const long long n = (long long)ctx->doa2d_rows * ctx->doa2d_cols;
-  if (cap < n) return fail(ctx, ISAC_ERR_CAPACITY, "angular spectrum larger than capacity");
-  ISAC_TRY(copy_d2h(ctx, p_db, ctx->doa2d_db.p, sizeof(double) * (size_t)n));
-  return ISAC_OK;
-}
-
-extern "C" int isac_find2d_peaks(isac_ctx* ctx, const double* p_db, int32_t rows, int32_t cols, int32_t n_peaks, int32_t* ele, int32_t* azi,
-                                 int32_t* n_found) {
-  ISAC_ENTER(ctx);
-  if (!p_db || rows <= 0 || cols <= 0 || !n_found || (n_peaks > 0 && (!ele || !azi))) return fail(ctx, ISAC_ERR_INVALID_ARG, "bad arguments");
-  *n_found = 0;
-  const long long n = (long long)rows * cols;
-  if (n > (1ll << 26)) return fail(ctx, ISAC_ERR_INVALID_ARG, "find2DPeaks: matrix too large");
-  if (n_peaks <= 0) return fail(ctx, ISAC_ERR_NO_DETECTION, "find2DPeaks needs a positive number of peaks (music.m:69)");
-  const int cap = isac_doa2d_peak_cap(rows, cols);
-  const size_t map_doubles = ((size_t)n + 1) & ~(size_t)1;                 // (candidates 16-byte aligned behind the map)
-  ISAC_TRY(ensure(ctx, ctx->doa2d_user, sizeof(double) * (map_doubles + (size_t)isac_doa2d_cand_doubles(cap))));
-  double* d_map = (double*)ctx->doa2d_user.p;
-  double* d_cand = d_map + map_doubles;
-  ISAC_TRY(copy_h2d(ctx, d_map, p_db, sizeof(double) * (size_t)n));
-  ISAC_TRY(isac_doa2d_norm_peaks_dev(ctx, false, d_map, rows, cols, d_cand, cap, nullptr));
-  unsigned count = 0;
-  ISAC_TRY(copy_d2h(ctx, &count, d_cand, sizeof(count)));
-  if ((int)count > cap) return fail(ctx, ISAC_ERR_HIP, "find2DPeaks: candidate count beyond the 2 x 2 bound (internal error)");
-  std::vector<double> cand((size_t)isac_doa2d_cand_doubles((int)count));
-  ISAC_TRY(copy_d2h(ctx, cand.data(), d_cand, sizeof(double) * cand.size()));
-  std::vector<int> e, a;
-  ISAC_TRY(isac_doa2d_select(ctx, cand.data(), (int)count, cap, rows, n_peaks, e, a));
-  for (size_t i = 0; i < e.size(); ++i) { ele[i] = e[i]; azi[i] = a[i]; }
-  *n_found = (int)e.size();
-  return ISAC_OK;
-}
-
-// ------------------------------------------------------------------ music2D (music2D.m:1-123)
-
-extern "C" int isac_music2d_dev(isac_ctx* ctx, const isac_est_params* ep, const isac_music2d_params* mp, const isac_c64* d_rx_grid,
-                                const isac_c64* d_tx_grid, int32_t K, int32_t L, int32_t A, isac_est_result* out) {
-  ISAC_ENTER(ctx);
-  if (!ep || !mp || !d_rx_grid || !d_tx_grid || !out || K <= 0 || L <= 0 || A <= 0) return fail(ctx, ISAC_ERR_INVALID_ARG, "bad arguments");
-  std::memset(out, 0, sizeof(*out));
-  const double c0 = 299792458.0;                                        // physconst('LightSpeed')  music2D.m:35
-  const double lambda = c0 / mp->fc;                                    // :37
-  const double r_gran = 0.5, v_gran = 0.5;                              // :43-44
-  const int r_steps = (int)std::floor((mp->r_max + 1.0) / r_gran);      // :45
-  const int v_steps = (int)std::floor((mp->v_max + 1.0) / v_gran);      // :46
-  // ---- DoA: Ra -> eig -> determineNumTargets -> ULA scan                                   :57-63
-  ISAC_TRY(ensure(ctx, ctx->cov, sizeof(c64) * (size_t)std::max(A * A, L * L)));
-  ISAC_TRY(isac_covariance_on(ctx, ctx->stream, d_rx_grid, (int64_t)K * L, A, (isac_c64*)ctx->cov.p));
-  ISAC_TRY(isac_eigh_dev(ctx, (const c64*)ctx->cov.p, A, nullptr));
-  std::vector<double> wa((size_t)A);
-  ISAC_TRY(copy_d2h(ctx, wa.data(), ctx->eig_w.p, sizeof(double) * (size_t)A));
-  ISAC_HIP(hipStreamSynchronize(ctx->stream));
-  ISAC_TRY(eig_status(ctx, A));
-  std::sort(wa.begin(), wa.end());
-  const int Lsig = determine_num_targets(wa);                           // music.m:22 on ascending eigenvalues
-  out->num_dets = Lsig;
-  if (ep->array_is_upa) return fail(ctx, ISAC_ERR_UNSUPPORTED, "UPA DoA: music.m:69 calls tools.find2DPeaks, which the reference does not define");
-  int n_steps = 0;
-  const double* d_sind = nullptr;
-  ISAC_TRY(get_sind_table(ctx, ep, &d_sind, &n_steps));
-  ISAC_TRY(ensure(ctx, ctx->spec, sizeof(double) * (size_t)std::max(n_steps, std::max(r_steps, v_steps))));
-  ISAC_TRY(isac_music_scan_dev(ctx, A, nullptr, Lsig, d_sind, n_steps, 0.5, (double*)ctx->spec.p, nullptr));
-  std::vector<double> spec((size_t)n_steps);
-  ISAC_TRY(copy_d2h(ctx, spec.data(), ctx->spec.p, sizeof(double) * (size_t)n_steps));
-  ISAC_HIP(hipStreamSynchronize(ctx->stream));
-  auto to_db = [](std::vector<double>& v) {
-    double mx = 0.0;
-    for (double x : v) mx = std::max(mx, std::fabs(x));
-    for (double& x : v) x = 20.0 * std::log10(std::fabs(x) / mx);
-  };
-  to_db(spec);
-  if (Lsig <= 0) return fail(ctx, ISAC_ERR_NO_DETECTION, "findpeaks 'NPeaks' must be a positive integer");
-  {
-    const std::vector<int> locs = findpeaks_desc(spec, Lsig);
-    out->n_azi = (int)std::min<size_t>(locs.size(), ISAC_MAX_EST);
-    for (int i = 0; i < out->n_azi; ++i) {
-      out->azi_est[i] = locs[(size_t)i] * ep->azimuth_scan_granularity - ep->azimuth_scan_scale / 2.0;
-      out->ele_est[i] = NAN;
-    }
-  }
-  // ---- range / velocity: H = channelInfo(:,:,1); Gram matrix G/K = H^H H / K (= conj(Rv));  Rr's signal vectors u = H v / sqrt(K mu)
-  ISAC_TRY(ensure(ctx, ctx->stage_a, sizeof(c64) * (size_t)K * L));
-  c64* d_h = (c64*)ctx->stage_a.p;
-  ISAC_TRY(isac_music2d_plane(ctx, (const c64*)d_rx_grid, (const c64*)d_tx_grid, (long long)K * L, d_h));      // :67-68
-  ISAC_TRY(isac_covariance_on(ctx, ctx->stream, (const isac_c64*)d_h, (int64_t)K, L, (isac_c64*)ctx->cov.p));  // G/K        :71-72
-  ISAC_TRY(isac_eigh_dev(ctx, (const c64*)ctx->cov.p, L, nullptr));                                            // :77-89
-  std::vector<double> wg((size_t)L);
-  ISAC_TRY(copy_d2h(ctx, wg.data(), ctx->eig_w.p, sizeof(double) * (size_t)L));
-  ISAC_HIP(hipStreamSynchronize(ctx->stream));
-  ISAC_TRY(eig_status(ctx, L));
-  std::vector<int> order((size_t)L);
-  std::iota(order.begin(), order.end(), 0);
-  std::stable_sort(order.begin(), order.end(), [&](int p, int q) { return wg[(size_t)p] > wg[(size_t)q]; });    // sort(.,'descend')
-  const int Lu = std::min(Lsig, L);
-  std::vector<int> top(order.begin(), order.begin() + Lu);
-  ISAC_TRY(ensure(ctx, ctx->stage_b, sizeof(c64) * (size_t)K * Lu + sizeof(int) * (size_t)Lu + 64));
-  c64* d_U = (c64*)ctx->stage_b.p;
-  int* d_top = (int*)((char*)ctx->stage_b.p + sizeof(c64) * (size_t)K * Lu);
-  ISAC_TRY(copy_h2d(ctx, d_top, top.data(), sizeof(int) * (size_t)Lu));
-  ISAC_TRY(isac_music2d_signal_vectors(ctx, d_h, K, L, d_top, Lu, d_U));
-  // range scan  ar = exp(-2j*pi*scs*2*r*n/c)                                                :92,:98-102
-  const double coef_r = ((-2.0 * M_PI) * mp->scs_hz) * 2.0;
-  ISAC_TRY(isac_music2d_scan(ctx, d_U, K, K, nullptr, Lu, 0, coef_r, c0, 0.0, r_gran, r_steps, (double*)ctx->spec.p));
-  std::vector<double> pr((size_t)r_steps), pv((size_t)v_steps);
-  ISAC_TRY(copy_d2h(ctx, pr.data(), ctx->spec.p, sizeof(double) * (size_t)r_steps));
-  ISAC_HIP(hipStreamSynchronize(ctx->stream));
-  // velocity scan  av = exp(2j*pi*T*2*v*m/lambda), Uvs = conj(V(:,top))                       :93,:104-108
-  const double coef_v = ((2.0 * M_PI) * mp->t_sri) * 2.0;
-  ISAC_TRY(isac_music2d_scan(ctx, (const c64*)ctx->eig_v.p, L, L, d_top, Lu, 1, coef_v, lambda, -mp->v_max / 2.0, v_gran, v_steps,
-                             (double*)ctx->spec.p));
-  ISAC_TRY(copy_d2h(ctx, pv.data(), ctx->spec.p, sizeof(double) * (size_t)v_steps));
-  ISAC_HIP(hipStreamSynchronize(ctx->stream));
-  to_db(pr);                                                            // :111-117
-  to_db(pv);
-  const std::vector<int> rl = findpeaks_desc(pr, Lsig), vl = findpeaks_desc(pv, Lsig);                          // :120-121
-  out->n_rng = (int)std::min<size_t>(rl.size(), ISAC_MAX_EST);
-  out->n_vel = (int)std::min<size_t>(vl.size(), ISAC_MAX_EST);
-  for (int i = 0; i < out->n_rng; ++i) out->rng_est[i] = rl[(size_t)i] * r_gran;                               // :122
-  for (int i = 0; i < out->n_vel; ++i) out->vel_est[i] = vl[(size_t)i] * v_gran - mp->v_max / 2.0;             // :123
-  ctx->last.spectrum_db = pr;
-  return ISAC_OK;
 }
 
 // ------------------------------------------------------------------ host-pointer wrappers of the echo path

@@ -176,7 +176,7 @@ __global__ __launch_bounds__(kThreads) void doa2d_peaks_kernel(const double* __r
 
 }  // namespace
 
-// ------------------------------------------------------------------ host side (called from capi.hip)
+// ------------------------------------------------------------------ host side (called from doa.hip)
 // at most one strict maximum in every 2 x 2 block of the interior
 int isac_doa2d_peak_cap(int rows, int cols) {
   if (rows < 3 || cols < 3) return 0;

@@ -115,16 +115,25 @@ struct StageSlot {
 };
 constexpr int kStageSlots = 128;    // (a batched CDL call stages two or three blocks and a slot is free again only when the stream has REACHED its copy: with 8 slots the host ran 4 calls ahead of the device, with 32 about ten -- 5 ms of config 5's frame; 128: the host issues a frame's applies in 40 ms against 94 ms of GPU work)
 
+struct DoaPlan {  // the direction-finding tail of one covariance: what doa_plan (doa.hip) decides, looks up and sizes before anything is enqueued
+  int A = 0, mode = 0;                     // antennas; 0 = MUSIC, 1 = digitalBF, 2 = mvdrBF
+  bool upa = false, upa2d = false;         // planar array; ... with ISAC_OPT_UPA_DOA: the 2-D scan + find2DPeaks
+  bool sub = false;                        // MUSIC through the signal-subspace eigensolver (the numDets signal vectors are enough: music.m:27-29)
+  const double* d_sind = nullptr; int n_steps = 0;   // ULA: sind of the n_steps scan angles
+  const double* d_tab2d = nullptr;         // UPA: [sind(ele) e_steps | cosd(azi) a_steps | sind(azi) a_steps], at most cap2d peak candidates
+  int e_steps = 0, a_steps = 0, cap2d = 0, n_ants_x = 0, n_ants_y = 0;
+  bool refused() const { return upa && !upa2d; }   // music.m:69 without the option
+};
+
 struct Fft2dPending {  // state between isac_fft2d_submit_dev and isac_fft2d_collect
   bool active = false;
   isac_est_params ep{};
   isac_cfar_config cfar{};
-  int A = 0, nr = 0, nc = 0, n_steps = 0, pack_first = 0;
+  int A = 0, nr = 0, nc = 0, pack_first = 0;
   size_t off_spec = 0, off_pow = 0, off_cut = 0;
   int* d_pcut_full = nullptr;
   double* d_ppow_full = nullptr;
-  bool upa2d = false;                      // ISAC_OPT_UPA_DOA: the pack's spectrum slot holds [counter | first2d find2DPeaks candidates]
-  int e_steps = 0, a_steps = 0, cap2d = 0, first2d = 0;
+  DoaPlan doa; int first2d = 0;            // doa.upa2d: the pack's spectrum slot holds [counter | first2d find2DPeaks candidates]
 };
 
 }  // namespace isac
@@ -317,6 +326,12 @@ inline int copy_d2h(isac_ctx* ctx, void* dst, const void* src, size_t bytes) {  
   }
   ISAC_HIP(hipStreamSynchronize(ctx->stream));
   for (int h = 0; h < 2; ++h) if (pend_n[h]) std::memcpy((char*)dst + pend_off[h], (char*)ctx->bounce + (size_t)h * kBounceChunk, pend_n[h]);
+  return ISAC_OK;
+}
+
+inline int upload(isac_ctx* ctx, DevBuf& b, const void* src, size_t bytes) {            // size b, then copy_h2d into it
+  ISAC_TRY(ensure(ctx, b, bytes));
+  ISAC_TRY(copy_h2d(ctx, b.p, src, bytes));           // (not hipMemcpy: see copy_h2d)
   return ISAC_OK;
 }
 

@@ -26,16 +26,23 @@ int isac_music_tridiag_bisect_dev(isac_ctx* ctx, const isac::c64* d_H, int A, hi
 int isac_music_subspace_dev(isac_ctx* ctx, int A, const int* d_num_dets, int num_dets_host, hipStream_t st);
 const int* isac_music_ctl(isac_ctx* ctx);
 int isac_music_scan_dev(isac_ctx* ctx, int A, const int* d_num_dets, int num_dets_host, const double* d_sind, int n_steps, double d_ratio, double* d_spec, hipStream_t st, int mode = 0, const int* ctl = nullptr);
-// music2D stages (host side: capi.hip)
+// music2D stages (host side: doa.hip)
 int isac_music2d_plane(isac_ctx* ctx, const isac::c64* d_rx, const isac::c64* d_tx, long long n, isac::c64* d_h);
 int isac_music2d_signal_vectors(isac_ctx* ctx, const isac::c64* d_h, int K, int Ls, const int* d_top, int Lsig, isac::c64* d_U);
 int isac_music2d_scan(isac_ctx* ctx, const isac::c64* d_U, int N, int ldU, const int* d_cols, int Lsig, int conj_u, double coef, double den, double x0, double dx, int n_steps, double* d_p);
-// ---------------------------------------------------------------- doa2d.hip: UPA DoA -- the 2-D scan, the column normalisation + peak candidates, the host half of find2DPeaks
+// ---------------------------------------------------------------- doa2d.hip: UPA DoA -- the 2-D scan, the column normalisation + peak candidates, the host sort of find2DPeaks (callers: doa.hip)
 int isac_doa2d_peak_cap(int rows, int cols);
 int isac_doa2d_cand_doubles(int cap);
 int isac_doa2d_scan_dev(isac_ctx* ctx, int mode, int nV, int nH, int eS, int aS, const double* d_tab, const int* d_num_dets, int num_dets_host, const int* ctl, hipStream_t st);
 int isac_doa2d_norm_peaks_dev(isac_ctx* ctx, bool normalise, const double* d_db, int rows, int cols, double* d_cand, int cap, hipStream_t st);
 int isac_doa2d_select(isac_ctx* ctx, const double* cand, int count, int cap, int rows, int L, std::vector<int>& ele, std::vector<int>& azi);
+// ---------------------------------------------------------------- doa.hip: the host side of direction finding, one back end for the fft2D pipeline and the stand-alone calls
+int doa_plan(isac_ctx* ctx, const isac_est_params* ep, int A, int mode, isac::DoaPlan* pl);   // route, scan tables, every buffer of the tail; enqueues nothing
+constexpr const char* kUpaRefused = "UPA DoA: music.m:69 calls tools.find2DPeaks, which the reference does not define";   // ISAC_ERR_UNSUPPORTED where plan.refused()
+int doa_eig_first_half(isac_ctx* ctx, const isac::DoaPlan& pl, const isac::c64* d_H, hipStream_t st, bool live_replay);
+int doa_enqueue(isac_ctx* ctx, const isac::DoaPlan& pl, const int* d_num_dets, int num_dets_host, hipStream_t st);   // subspace -> scan (-> norm + peak candidates)
+int doa_readout(isac_ctx* ctx, const isac::DoaPlan& pl, const isac_est_params* ep, const double* host, int n_first, int L, const char* none_prefix, std::vector<double>& ele, std::vector<double>& azi);
+void doa_store(const std::vector<double>& ele, const std::vector<double>& azi, int n, double* ele_est, double* azi_est);   // the first n, NaN elevations for a ULA
 // ---------------------------------------------------------------- cdl_os.hip: the CDL apply in the frequency domain (overlap-save, 4096-point windows) for long waveforms
 bool cdl_os_ok(long long T, int Nt, int Nr, int n_paths, int n_taps, int max_shift);      // downlink: into two receive elements
 bool cdl_os_ul_ok(long long T, int Nt, int Nr, int n_paths, int n_taps, int max_shift);   // uplink: one or two transmit elements into many receive elements

@@ -1661,7 +1661,7 @@ int isac_music_scan_dev(isac_ctx* ctx, int A, const int* d_num_dets, int num_det
   return ISAC_OK;
 }
 
-// ---- music2D stages (host side lives in capi.hip)
+// ---- music2D stages (host side lives in doa.hip)
 int isac_music2d_plane(isac_ctx* ctx, const c64* d_rx, const c64* d_tx, long long n, c64* d_h) {
   hipLaunchKernelGGL(chan_plane_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ctx->stream, d_rx, d_tx, n, d_h);
   ISAC_HIP(hipGetLastError());
