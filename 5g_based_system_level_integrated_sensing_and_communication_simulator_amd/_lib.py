@@ -91,6 +91,14 @@ class SensingJob(C.Structure):
                 ("d_noise_unit", C.c_void_p), ("seed", C.c_uint64), ("noise_mode", C.c_int32), ("reserved", C.c_int32)]
 
 
+class RxFrontendJob(C.Structure):
+    _fields_ = [("d_y", C.c_void_p), ("d_noise_unit", C.c_void_p), ("path_scale", C.c_double), ("gain_scale", C.c_double), ("noise_power", C.c_double), ("seed", C.c_uint64)]
+
+
+class PathLossConfig(C.Structure):
+    _fields_ = [("building_height", C.c_double), ("street_width", C.c_double), ("environment_height", C.c_double), ("optional_model", C.c_int32), ("reserved", C.c_int32)]
+
+
 class EstResult(C.Structure):
     _fields_ = [("n_rng", C.c_int32), ("n_vel", C.c_int32), ("n_azi", C.c_int32), ("num_dets", C.c_int32),
                 ("total_detections", C.c_int32), ("reserved", C.c_int32),
@@ -108,6 +116,7 @@ EXPORTS = [
     "isac_ofdm_waveform_length", "isac_cfar2d_ca", "isac_fft2d_dev", "isac_fft2d", "isac_fft2d_submit_dev", "isac_fft2d_submit_cached_dev", "isac_fft2d_collect", "isac_sensing_submit_n", "isac_sensing_collect_n", "isac_fft2d_range_stage_dev", "isac_fft2d_get_detections",
     "isac_fft2d_get_power_window", "isac_fft2d_get_covariance", "isac_fft2d_get_music_spectrum",
     "isac_rdm_plane_dev", "isac_covariance_dev", "isac_music_doa", "isac_ctx_set_option", "isac_ctx_share_streams", "isac_ctx_reserve", "isac_eigh_top", "isac_beamscan_doa", "isac_get_angular_spectrum2d", "isac_find2d_peaks", "isac_music2d_dev", "isac_eigh", "isac_cdl_apply_dev", "isac_cdl_apply_batch_dev", "isac_cdl_path_gains_dev", "isac_cdl_freq_response_dev", "isac_cdl_csi_estimate_batch_dev", "isac_prg_precode_dev", "isac_precoded_sinr_cqi_dev", "isac_type1sp_codebook", "isac_csi_report_dev", "isac_csi_report_batch_dev", "isac_pusch_codebook", "isac_srs_pmi_select_batch_dev", "isac_los_check_dev", "isac_winding_number_dev", "isac_synth_qpsk_grid_dev",
+    "isac_path_loss_38901", "isac_path_loss_fspl", "isac_thermal_noise_power", "isac_dft_channel_matrix", "isac_rx_frontend_batch_dev", "isac_rx_frontend_dev",
 ]
 
 
@@ -145,7 +154,8 @@ def load():
             raise RuntimeError(f"{_LIB_PATH}: ABI version {lib.isac_abi_version()} but this binding was written for {ISAC_ABI_VERSION}; rebuild the library")
         for which, (name, cls) in enumerate((("isac_est_result", EstResult), ("isac_est_params", EstParams), ("isac_cfar_config", CfarConfig),
                                              ("isac_radar_channel_params", RadarChannelParams), ("isac_carrier", Carrier),
-                                             ("isac_music2d_params", Music2dParams), ("isac_csi_report", CsiReport), ("isac_sensing_job", SensingJob), ("isac_srs_report", SrsReport))):
+                                             ("isac_music2d_params", Music2dParams), ("isac_csi_report", CsiReport), ("isac_sensing_job", SensingJob), ("isac_srs_report", SrsReport),
+                                             ("isac_rx_frontend_job", RxFrontendJob), ("isac_path_loss_config", PathLossConfig))):
             if lib.isac_abi_sizeof(C.c_int32(which)) != C.sizeof(cls):
                 raise RuntimeError(f"{_LIB_PATH}: sizeof({name}) = {lib.isac_abi_sizeof(C.c_int32(which))} in the library, {C.sizeof(cls)} in the binding")
         _lib = lib

@@ -1,2 +1,2 @@
 """Mirror of the reference's ``+communication`` package (hot-path seams only)."""
-from . import channelModels, phyLayer  # noqa: F401
+from . import channelModels, pathlossModels, phyLayer  # noqa: F401

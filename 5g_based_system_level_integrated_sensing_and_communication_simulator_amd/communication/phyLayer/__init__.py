@@ -5,3 +5,4 @@ from .csiReport import cqiSelect, cqiSelectBatch, dlPMISelect, type1SinglePanelC
 from .prgPrecode import prgPrecode, prgPrecodeGrid  # noqa: F401,E402
 from .pmiSelect import pmiSelect, srsReportBatch, puschCodebook, maxPUSCHPrecodingMatrixIndicator  # noqa: F401,E402
 from .riSelect import riSelect, riSelectBatch  # noqa: F401,E402
+from .applyChannelModel import applyChannelModel, applyChannelModelBatch, rxFrontEndBatch, thermalNoisePower, dftChannelMatrix, pathLoss  # noqa: F401,E402

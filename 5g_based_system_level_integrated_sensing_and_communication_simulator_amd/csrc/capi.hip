@@ -164,6 +164,8 @@ extern "C" int isac_abi_sizeof(int32_t which) {
     case ISAC_SIZEOF_CSI_REPORT: return (int)sizeof(isac_csi_report);
     case ISAC_SIZEOF_SENSING_JOB: return (int)sizeof(isac_sensing_job);
     case ISAC_SIZEOF_SRS_REPORT: return (int)sizeof(isac_srs_report);
+    case ISAC_SIZEOF_RX_FRONTEND_JOB: return (int)sizeof(isac_rx_frontend_job);
+    case ISAC_SIZEOF_PATH_LOSS_CONFIG: return (int)sizeof(isac_path_loss_config);
     default: return -1;
   }
 }
@@ -224,7 +226,7 @@ extern "C" int isac_ctx_destroy(isac_ctx* ctx) {
                     &ctx->beam, &ctx->coef, &ctx->phase_rx, &ctx->steer, &ctx->dgrid,
                     &ctx->ymid, &ctx->pwin, &ctx->flags, &ctx->det_cut, &ctx->det_pow, &ctx->det_cnt, &ctx->cov_part,
                     &ctx->cov, &ctx->eig_w, &ctx->eig_v, &ctx->eig_scratch, &ctx->spec, &ctx->misc, &ctx->stage_a, &ctx->stage_b, &ctx->seg,
-                    &ctx->stage_c, &ctx->sind_tab, &ctx->cdl_h, &ctx->echo_own, &ctx->os_x};
+                    &ctx->stage_c, &ctx->sind_tab, &ctx->cdl_h, &ctx->rxfe_tab, &ctx->echo_own, &ctx->os_x};
   for (DevBuf* b : bufs)
     if (b->p) (void)hipFree(b->p);
   if (ctx->pinned) (void)hipHostFree(ctx->pinned);

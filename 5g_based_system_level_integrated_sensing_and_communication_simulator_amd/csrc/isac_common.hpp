@@ -166,7 +166,7 @@ struct isac_ctx {
   std::map<std::pair<long long, long long>, isac::DevBuf> sind;     // (scale, granularity) -> sind(scan angles)
   // scratch
   isac::DevBuf beam, coef, phase_rx, steer, dgrid, ymid, pwin, flags, det_cut, det_pow, det_cnt, cov_part, cov,
-      eig_w, eig_v, eig_scratch, spec, misc, stage_a, stage_b, stage_c, sind_tab, seg, cdl_h;
+      eig_w, eig_v, eig_scratch, spec, misc, stage_a, stage_b, stage_c, sind_tab, seg, cdl_h, rxfe_tab;
   void* pinned = nullptr; size_t pinned_cap = 0;                       // results of isac_fft2d_submit* (read by isac_fft2d_collect) -- no other entry point may touch it
   void* bounce = nullptr; size_t bounce_cap = 0; hipEvent_t ev_bounce[2] = {nullptr, nullptr};   // pinned bounce buffer of the host-array copies (copy_h2d / copy_d2h)
   void* pinned_csi = nullptr; size_t pinned_csi_cap = 0;               // results of isac_csi_report*: its own buffer, so a CSI call between submit and collect cannot clobber a pending CPI

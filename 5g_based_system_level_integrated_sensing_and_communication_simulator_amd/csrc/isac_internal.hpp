@@ -47,6 +47,9 @@ void doa_store(const std::vector<double>& ele, const std::vector<double>& azi, i
 bool cdl_os_ok(long long T, int Nt, int Nr, int n_paths, int n_taps, int max_shift);      // downlink: into two receive elements
 bool cdl_os_ul_ok(long long T, int Nt, int Nr, int n_paths, int n_taps, int max_shift);   // uplink: one or two transmit elements into many receive elements
 int cdl_os_apply(isac_ctx* ctx, const isac_cdl_job* jobs, int n_jobs, long long T, int Nt, int Nr, int n_paths, const double* taps, int n_taps, const int32_t* shift, int max_shift, double out_scale);
+// ---------------------------------------------------------------- rxfe.hip: the tail of applyChannelModel (path loss, Rx gain, thermal noise), one launch for a batch
+constexpr uint32_t kRxFrontEndStream = 3u;   // Philox stream word of its time-domain AWGN (0: the echo's time-domain noise, 1: isac_synth_qpsk_grid_dev, 2: kSpectralStream)
+int isac_rx_frontend_jobs(isac_ctx* ctx, const isac_rx_frontend_job* jobs, int n_jobs, long long T, int Nr, int noise_mode);
 
 // Status words the device eigensolver leaves behind the eigenvalues (ctx->eig_w [A] | info[0..6]).  info[0] negative: the QL recurrence ran out of rotation storage (-1), a live replay
 // block gave up waiting (-2; isac_eigh_replay_recover, once the stream is idle), the signal-subspace vectors are not finite (-3), the distributed tridiagonalisation saw no progress (-4; sticky in info[6]).

@@ -60,7 +60,8 @@ typedef enum {
 int isac_abi_version(void);
 /* sizeof() of the library's build of struct `which` (ISAC_SIZEOF_*), -1 for an unknown selector. */
 enum { ISAC_SIZEOF_EST_RESULT = 0, ISAC_SIZEOF_EST_PARAMS = 1, ISAC_SIZEOF_CFAR_CONFIG = 2, ISAC_SIZEOF_RADAR_CHANNEL_PARAMS = 3,
-       ISAC_SIZEOF_CARRIER = 4, ISAC_SIZEOF_MUSIC2D_PARAMS = 5, ISAC_SIZEOF_CSI_REPORT = 6, ISAC_SIZEOF_SENSING_JOB = 7, ISAC_SIZEOF_SRS_REPORT = 8 };
+       ISAC_SIZEOF_CARRIER = 4, ISAC_SIZEOF_MUSIC2D_PARAMS = 5, ISAC_SIZEOF_CSI_REPORT = 6, ISAC_SIZEOF_SENSING_JOB = 7, ISAC_SIZEOF_SRS_REPORT = 8,
+       ISAC_SIZEOF_RX_FRONTEND_JOB = 9, ISAC_SIZEOF_PATH_LOSS_CONFIG = 10 /* added under ABI 8: an older library answers -1 */ };
 int isac_abi_sizeof(int32_t which);
 int isac_device_count(int* count);
 int isac_ctx_create(int device, isac_ctx** out);
@@ -489,6 +490,63 @@ int isac_cdl_freq_response_dev(isac_ctx* ctx, const isac_c64* d_H, int32_t n_pat
 int isac_cdl_csi_estimate_batch_dev(isac_ctx* ctx, int32_t n_ue, const isac_c64* const* d_base, const double* const* d_rate, const isac_c64* const* d_los,
                                     const double* los_rate, const double* t, int32_t n_paths, int32_t n_rays, int32_t Nt, int32_t Nr, int32_t ports,
                                     const double* d_tau, const double* d_freq, int64_t n_re, isac_c64* const* d_Hf);
+/* ------------------------------------------------------------------ the rest of applyChannelModel: path loss, Rx gain, thermal noise
+ * What uePhy.m:724-755 (downlink) / gNBPhy.m:833-864 (uplink) do to the waveform AFTER the channel object (isac_cdl_apply*_dev above):
+ *   rxWaveform = db2mag(-pathLoss) * rxWaveform;                                  uePhy.m:742-748   gNBPhy.m:851-857
+ *   rxWaveform = rxWaveform .* 10.^(RxGain/20);                                   uePhy.m:935-940   gNBPhy.m:1064-1069
+ *   rxWaveform = rxWaveform + sqrt(Nt/2)*complex(randn, randn),  Nt = k (T + 290 (F - 1)) fs    uePhy.m:942-950   gNBPhy.m:1071-1080
+ * Added under ABI 8 (new symbols and new structs only).
+ *
+ * Host-side scalars first: plain C, no context, no GPU.
+ * isac_path_loss_38901 = nrPathLoss(nrPathLossConfig('Scenario', s), fc, los, bs, ue) as +communication/+pathlossModels/config5GNRModels.m calls it: TR 38.901 7.4.1, Table
+ *   7.4.1-1, mean path loss only (no shadow fading, no O2I terms), for ANY distance (no range-of-validity errors).  d2D / d3D from the two positions [x y z] in m; the third
+ *   coordinate of the FIRST position is h_BS, of the SECOND h_UT -- positions are taken in the order the caller passes them.  Quirk of the reference, kept by its callers and
+ *   not "fixed" here: uePhy.m:744 passes the UE's own position first, so the downlink evaluates the model with the two heights swapped; gNBPhy.m:853 passes the gNB first.
+ *   Equal positions give 0, not -Inf (config5GNRModels.m:32-33).  los != 0: the LoS formula; 0: max(LoS, NLoS') (InF-HH: the LoS formula either way).
+ *   cfg == NULL: nrPathLossConfig's defaults (BuildingHeight 5 m, StreetWidth 20 m, EnvironmentHeight 1 m, OptionalModel off).  optional_model != 0 selects the
+ *   optional NLoS formulas of UMa / UMi / InH (32.4 + 20 log10 f + {30, 31.9, 31.9} log10 d, taken as they stand, without the max).
+ *   The table is transcribed from the 3GPP document (nrPathLoss's source is not in the reference): parity with MATLAB is unpinned, DESIGN.md section 5.
+ * isac_path_loss_fspl = fspl(R, lambda) as configFreeSpaceModel.m calls it: 20 log10(4 pi R / lambda), lambda = c / fc; negative values (R < lambda / 4 pi, R = 0) give 0.
+ * isac_thermal_noise_power: Nt = 1.380649e-23 * (T + 290 (10^(F/10) - 1)) * fs  [W]   (uePhy.m:945-947).
+ * isac_dft_channel_matrix: the link without a CDL object (uePhy.m:732-740, gNBPhy.m:841-849): H = fft(eye(n)); H = H(1:Nt,1:Nr); H = H / norm(H), n = max(Nt, Nr),
+ *   H [Nt x Nr] column-major.  Apply it with isac_cdl_apply_dev (one path, one unit tap, shift 0, one gain block). */
+typedef enum {
+  ISAC_PL_UMA = 0, ISAC_PL_UMI = 1, ISAC_PL_RMA = 2, ISAC_PL_INH = 3,
+  ISAC_PL_INF_SL = 4, ISAC_PL_INF_DL = 5, ISAC_PL_INF_SH = 6, ISAC_PL_INF_DH = 7, ISAC_PL_INF_HH = 8
+} isac_path_loss_scenario;
+typedef struct {
+  double building_height;      /* nrPathLossConfig.BuildingHeight    (RMa), m, default 5   */
+  double street_width;         /* nrPathLossConfig.StreetWidth       (RMa), m, default 20  */
+  double environment_height;   /* nrPathLossConfig.EnvironmentHeight (UMa / UMi breakpoint), m, default 1 */
+  int32_t optional_model;      /* nrPathLossConfig.OptionalModel     (UMa / UMi / InH NLoS), default 0    */
+  int32_t reserved;
+} isac_path_loss_config;
+int isac_path_loss_38901(int32_t scenario, double fc_hz, int32_t los, const double bs_pos[3], const double ue_pos[3],
+                         const isac_path_loss_config* cfg, double* pl_db);
+int isac_path_loss_fspl(double fc_hz, const double bs_pos[3], const double ue_pos[3], double* pl_db);
+int isac_thermal_noise_power(double temperature_k, double noise_figure_db, double sample_rate_hz, double* nt_w);
+int isac_dft_channel_matrix(int32_t Nt, int32_t Nr, isac_c64* H);
+
+/* The three waveform lines on the device, in place and in the reference's order, per element:
+ *      y = (y * path_scale) * gain_scale + sqrt(noise_power / 2) * w          (two multiplies, not one folded factor; the sum is one fused multiply-add)
+ * for n_jobs arrays [T x Nr] in ONE launch, asynchronous on the context's stream; nothing synchronises (the job table goes through pinned staging, as the segment table
+ * of isac_cdl_apply_batch_dev does).  noise_mode (isac_noise_mode): ISAC_NOISE_NONE: scaling only;  ISAC_NOISE_INJECTED: w = d_noise_unit [T x Nr] (randn + 1j randn of the
+ * caller: parity mode);  ISAC_NOISE_PHILOX: w = the fp64 Box-Muller pair of Philox4x32-10 with counter e = t + T u, key = seed, stream word 3 (a stream of its own: 0 is the
+ * time-domain echo noise, 1 the QPSK grid generator, 2 the spectral echo noise) -- oracle.philox.philox_normal_pairs(e, seed, 3) restates it.  The two spectral modes are
+ * ISAC_ERR_INVALID_ARG.  Jobs must not overlap one another.  Like every call that writes device memory, it drops cached range rows a job's array overlaps.
+ * isac_rx_frontend_dev is the one-job form of the batch call. */
+typedef struct {
+  isac_c64* d_y;                  /* [T x Nr] column-major, modified IN PLACE                         */
+  const isac_c64* d_noise_unit;   /* ISAC_NOISE_INJECTED: randn + 1j randn, [T x Nr]; else NULL       */
+  double path_scale;              /* db2mag(-pathLoss)                                               */
+  double gain_scale;              /* 10^(RxGain/20)                                                  */
+  double noise_power;             /* Nt in W; the kernel adds sqrt(Nt/2) (re + j im)                 */
+  uint64_t seed;                  /* ISAC_NOISE_PHILOX                                               */
+} isac_rx_frontend_job;
+int isac_rx_frontend_batch_dev(isac_ctx* ctx, const isac_rx_frontend_job* jobs, int32_t n_jobs, int64_t T, int32_t Nr, int32_t noise_mode);
+int isac_rx_frontend_dev(isac_ctx* ctx, isac_c64* d_y, int64_t T, int32_t Nr, double path_scale, double gain_scale, double noise_power, int32_t noise_mode,
+                         const isac_c64* d_noise_unit, uint64_t seed);
+
 /* ------------------------------------------------------------------ SINR -> CQI (config 5)
  * precodedSINR(H, sigma, W) (+communication/+phyLayer/precodedSINR.m:11-17) for every resource element of a
  * channel estimate, its mean, and getCQI (+communication/+phyLayer/cqiSelect.m:697-722) against a SINR table

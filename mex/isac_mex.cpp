@@ -42,7 +42,7 @@ isac_ctx* ctx() {
         isac_abi_sizeof(ISAC_SIZEOF_EST_PARAMS) != (int)sizeof(isac_est_params) || isac_abi_sizeof(ISAC_SIZEOF_CFAR_CONFIG) != (int)sizeof(isac_cfar_config) ||
         isac_abi_sizeof(ISAC_SIZEOF_RADAR_CHANNEL_PARAMS) != (int)sizeof(isac_radar_channel_params) ||
         isac_abi_sizeof(ISAC_SIZEOF_CSI_REPORT) != (int)sizeof(isac_csi_report) || isac_abi_sizeof(ISAC_SIZEOF_CARRIER) != (int)sizeof(isac_carrier) ||
-        isac_abi_sizeof(ISAC_SIZEOF_MUSIC2D_PARAMS) != (int)sizeof(isac_music2d_params))
+        isac_abi_sizeof(ISAC_SIZEOF_MUSIC2D_PARAMS) != (int)sizeof(isac_music2d_params) || isac_abi_sizeof(ISAC_SIZEOF_RX_FRONTEND_JOB) != (int)sizeof(isac_rx_frontend_job))
       mexErrMsgIdAndTxt("isac:INVALID_ARG", "libisac_hip.so ABI %d does not match the gateway's isac.h (ABI %d): rebuild both", isac_abi_version(), ISAC_ABI_VERSION);
     const char* dev = std::getenv("ISAC_DEVICE");                    // parallel workers: one process per GPU (cellID mod nGPU)
     if (isac_ctx_create(dev ? std::atoi(dev) : 0, &g_ctx) != ISAC_OK) mexErrMsgIdAndTxt("isac:HIP", "no MI355X visible");
@@ -183,6 +183,11 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     DevArray& a = lookup(prhs[1]);
     plhs[0] = mxCreateNumericArray(3, a.dims, mxDOUBLE_CLASS, mxCOMPLEX);
     check(isac_memcpy_d2h(ctx(), mxGetComplexDoubles(plhs[0]), a.p, sizeof(isac_c64) * a.dims[0] * a.dims[1] * a.dims[2]));
+  } else if (fn == "size") {                                // d = isac_mex('size', h): [d0 d1] of a device array ([d0 d1 d2] when it has a third dimension)
+    DevArray& a = lookup(prhs[1]);
+    const mwSize nd = a.dims[2] > 1 ? 3 : 2;
+    plhs[0] = mxCreateDoubleMatrix(1, nd, mxREAL);
+    for (mwSize i = 0; i < nd; ++i) mxGetDoubles(plhs[0])[i] = (double)a.dims[i];
   } else if (fn == "free") {
     const uint64_t h = *mxGetUint64s(prhs[1]);
     auto it = g_arrays.find(h);
@@ -666,6 +671,78 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     check(isac_dev_alloc(ctx(), sizeof(isac_c64) * d0 * d1 * d2, &p));
     check(isac_memset_dev(ctx(), p, 0, sizeof(isac_c64) * d0 * d1 * d2));
     plhs[0] = make_handle(p, d0, d1, d2, true);
+  } else if (fn == "pathLoss") {
+    // pl = isac_mex('pathLoss', pathLossConfig, carrierFreq, losCondition, bsPosition, uePosition): 'fspl' -> configFreeSpaceModel.m (fspl), any of the nine
+    // nrPathLossConfig scenario names -> config5GNRModels.m (nrPathLoss, TR 38.901 7.4.1); positions [x y z] in the order passed (first: h_BS).   uePhy.m:742-747, gNBPhy.m:851-856
+    if (nrhs < 6) mexErrMsgIdAndTxt("isac:INVALID_ARG", "usage: isac_mex('pathLoss', pathLossConfig, carrierFreq, losCondition, bsPosition, uePosition)");
+    char* sc = mxArrayToString(prhs[1]);
+    const std::string scen = sc ? sc : "";
+    mxFree(sc);
+    if (mxGetNumberOfElements(prhs[4]) != 3 || mxGetNumberOfElements(prhs[5]) != 3) mexErrMsgIdAndTxt("isac:INVALID_ARG", "pathLoss: positions must be [x y z]");
+    const double fc = mxGetScalar(prhs[2]);
+    const int los = mxIsEmpty(prhs[3]) ? 0 : (mxGetScalar(prhs[3]) != 0.0);
+    double pl = 0.0;
+    int st = ISAC_ERR_INVALID_ARG;
+    if (scen == "fspl") {
+      st = isac_path_loss_fspl(fc, mxGetDoubles(prhs[4]), mxGetDoubles(prhs[5]), &pl);
+    } else {
+      static const char* names[] = {"UMa", "UMi", "RMa", "InH", "InF-SL", "InF-DL", "InF-SH", "InF-DH", "InF-HH"};
+      for (int i = 0; i < 9; ++i)
+        if (scen == names[i]) st = isac_path_loss_38901(i, fc, los, mxGetDoubles(prhs[4]), mxGetDoubles(prhs[5]), nullptr, &pl);
+    }
+    if (st != ISAC_OK) mexErrMsgIdAndTxt("isac:INVALID_ARG", "pathLoss: unknown scenario '%s' or a carrier frequency that is not positive", scen.c_str());
+    plhs[0] = mxCreateDoubleScalar(pl);
+  } else if (fn == "thermalNoisePower") {
+    // Nt = isac_mex('thermalNoisePower', temperature_K, noiseFigure_dB, sampleRate)                uePhy.m:945-947, gNBPhy.m:1074-1077
+    if (nrhs < 4) mexErrMsgIdAndTxt("isac:INVALID_ARG", "usage: isac_mex('thermalNoisePower', temperature, noiseFigure_dB, sampleRate)");
+    double nt = 0.0;
+    if (isac_thermal_noise_power(mxGetScalar(prhs[1]), mxGetScalar(prhs[2]), mxGetScalar(prhs[3]), &nt) != ISAC_OK) mexErrMsgIdAndTxt("isac:INVALID_ARG", "thermalNoisePower");
+    plhs[0] = mxCreateDoubleScalar(nt);
+  } else if (fn == "rxFrontEnd") {
+    // rx = isac_mex('rxFrontEnd', rxWaveform | handle, pathLoss_dB, rxGain_dB, Nt_W [, noise | handle | [] [, seed | []]])
+    // the three lines behind the channel in applyChannelModel: db2mag(-pathLoss), 10^(RxGain/20), + sqrt(Nt/2) noise (uePhy.m:748-754, gNBPhy.m:857-863).  A handle is
+    // modified IN PLACE and returned; a MATLAB array gives a MATLAB array.  noise = complex(randn(size), randn(size)): the reference's own stream (parity); noise empty
+    // and a seed: the library's Philox stream; neither: noiseless.
+    if (nrhs < 5) mexErrMsgIdAndTxt("isac:INVALID_ARG", "usage: isac_mex('rxFrontEnd', rxWaveform, pathLoss_dB, rxGain_dB, Nt [, noise [, seed]])");
+    const mxArray* wv = prhs[1];
+    const double s1 = std::pow(10.0, -mxGetScalar(prhs[2]) / 20.0), s2 = std::pow(10.0, mxGetScalar(prhs[3]) / 20.0), nt = mxGetScalar(prhs[4]);
+    const mxArray* noise = (nrhs > 5 && !mxIsEmpty(prhs[5])) ? prhs[5] : nullptr;
+    const bool seeded = !noise && nrhs > 6 && !mxIsEmpty(prhs[6]);
+    const int mode = noise ? ISAC_NOISE_INJECTED : (seeded ? ISAC_NOISE_PHILOX : ISAC_NOISE_NONE);
+    const uint64_t seed = seeded ? seed_of(prhs[6]) : 0;
+    if (is_handle(wv)) {
+      DevArray& a = lookup(wv);
+      const int64_t T = (int64_t)a.dims[0];
+      const mwSize Nr = a.dims[1] * a.dims[2];
+      int st;
+      {
+        DevIn* nz = noise ? new DevIn(noise) : nullptr;
+        if (nz && nz->d[0] * nz->d[1] * nz->d[2] != a.dims[0] * Nr) { delete nz; mexErrMsgIdAndTxt("isac:INVALID_ARG", "rxFrontEnd: noise and waveform sizes differ"); }
+        st = isac_rx_frontend_dev(ctx(), (isac_c64*)a.p, T, (int32_t)Nr, s1, s2, nt, mode, nz ? nz->p : nullptr, seed);
+        if (st == ISAC_OK && nz && nz->tmp) st = isac_sync(ctx());      // an uploaded noise array is released when this call returns
+        delete nz;
+      }
+      check(st);
+      plhs[0] = mxCreateNumericMatrix(1, 1, mxUINT64_CLASS, mxREAL);
+      *mxGetUint64s(plhs[0]) = *mxGetUint64s(wv);
+    } else {
+      const mwSize T = mxGetM(wv), Nr = mxGetN(wv);
+      if (noise && !is_handle(noise) && (mxGetM(noise) != T || mxGetN(noise) != Nr)) mexErrMsgIdAndTxt("isac:INVALID_ARG", "rxFrontEnd: noise and waveform sizes differ");
+      const size_t bytes = sizeof(isac_c64) * T * Nr;
+      void* d_y = nullptr;
+      check(isac_dev_alloc(ctx(), bytes, &d_y));
+      struct Guard3 { void* p; ~Guard3() { if (p) isac_dev_free(g_ctx, p); } } guard{d_y};
+      check(isac_memcpy_h2d(ctx(), d_y, mxGetComplexDoubles(wv), bytes));
+      int st;
+      {
+        DevIn* nz = noise ? new DevIn(noise) : nullptr;
+        st = isac_rx_frontend_dev(ctx(), (isac_c64*)d_y, (int64_t)T, (int32_t)Nr, s1, s2, nt, mode, nz ? nz->p : nullptr, seed);
+        plhs[0] = mxCreateDoubleMatrix(T, Nr, mxCOMPLEX);
+        if (st == ISAC_OK) st = isac_memcpy_d2h(ctx(), mxGetComplexDoubles(plhs[0]), d_y, bytes);   // (waits for the stream: the noise temporary is done with)
+        delete nz;
+      }
+      check(st);
+    }
   // ------------------------------------------------------------------ topology
   } else if (fn == "checkLoS") {
     // (wallTable, uePos [3 x n], antPos [3 x n]) -> logical [1 x n]                               openStreetMapCity.m:67-93

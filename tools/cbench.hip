@@ -4,8 +4,12 @@
 // lane and trip, plain vs nontemporal stores, destination offset against the source (0 / 256 B / 4 KB + 256 B), and the fused echo kernel's own shape (52 416-byte
 // columns: 3 276 x 16 B per (symbol, antenna) column, read and written).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/cbench.hip -o tools/cbench && tools/cbench
+//   tools/cbench <bytes> [<bytes> ...]: only the flat copy (one float4 per thread) of exactly these byte counts per direction, median of 30 -- the yardstick other
+//   streaming kernels are compared with in their own session (tools/rxfe_bench.py).
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cstdio>
+#include <cstdlib>
 #include <vector>
 typedef float f4 __attribute__((ext_vector_type(4)));
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e_)); return 1; } } while (0)
@@ -54,10 +58,28 @@ float best_ms(L launch, int reps = 7) {
   (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
   return best;
 }
-int main() {
+int main(int argc, char** argv) {
   const size_t cap = (size_t)4 << 30;
   char *src, *dst;
   CK(hipMalloc(&src, cap + (1 << 20))); CK(hipMalloc(&dst, cap + (1 << 20))); CK(hipMemset(src, 1, cap + (1 << 20))); CK(hipMemset(dst, 0, cap + (1 << 20)));
+  if (argc > 1) {                                             // flat copy of the given byte counts, median of 30 after 5 warm launches
+    hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+    for (int a = 1; a < argc; ++a) {
+      const size_t bytes = (size_t)std::strtoull(argv[a], nullptr, 10);
+      if (!bytes || bytes > cap) { printf("%s: byte count must be 1 .. %zu\n", argv[a], cap); return 1; }
+      const long long n = (long long)(bytes / 16);
+      std::vector<float> ms;
+      for (int r = 0; r < 35; ++r) {
+        CK(hipEventRecord(e0)); hipLaunchKernelGGL(copy_flat, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, (f4*)dst, (const f4*)src, n); CK(hipEventRecord(e1));
+        CK(hipEventSynchronize(e1));
+        float t; CK(hipEventElapsedTime(&t, e0, e1));
+        if (r >= 5) ms.push_back(t);
+      }
+      std::sort(ms.begin(), ms.end());
+      printf("flat_copy bytes_per_direction %zu median_us %.2f min_us %.2f TBps %.3f\n", bytes, ms[ms.size() / 2] * 1e3, ms[0] * 1e3, 2.0 * bytes / 1e9 / ms[ms.size() / 2]);
+    }
+    return 0;
+  }
   printf("# bytes per direction | shape | us | TB/s (read + written)\n");
   for (size_t mb : {32, 64, 128, 256, 512, 752, 1024, 2048, 4096}) {
     const size_t bytes = mb << 20;
