@@ -1,5 +1,5 @@
 // Array covariance on fp64 MFMA (gfx950).
-// Reference path: fft2D.m:106-111 (the eigensolvers and the MUSIC scan: music.hip).
+// Reference path: fft2D.m:106-111 (the eigensolvers: eigh.hip; the MUSIC scan: music.hip).
 //   Ra   = X*X'/N,  X = reshape(rxGrid, N, A)'   -- the ' is a CONJUGATE transpose, so
 //   Ra[a,b] = (1/N) sum_n conj(G[n,a]) G[n,b],   G[n,a] = rxGrid(n + N*a)
 // Covariance: each 16x16 output tile is a real-MFMA triple on v_mfma_f64_16x16x4_f64

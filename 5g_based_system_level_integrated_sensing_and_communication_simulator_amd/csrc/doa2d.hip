@@ -2,7 +2,7 @@
 // music.m:31-71, digitalBF.m:13-53, mvdrBF.m:13-53: every point of the [eSteps x aSteps] grid is
 //   P_j = sum_i w_i |v_i' a_j|^2          (eigenpairs (lambda_i, v_i) of Ra; DBF w = lambda, MVDR w = 1/lambda, MUSIC w = [rank >= L])
 // or, on MUSIC's signal-subspace route, || a_j - Us Us' a_j ||^2; then the column normalisation of music.m:61-63 and the strict
-// 8-neighbour maxima (include/isac.h, isac_find2d_peaks).  Own translation unit: the echo / music / cdl code objects stay as they are.
+// 8-neighbour maxima (include/isac.h, isac_find2d_peaks).  Own translation unit: the echo / eigh / music / cdl code objects stay as they are.
 #include <algorithm>
 #include <vector>
 

@@ -16,13 +16,15 @@ int isac_range_stage_into_cache(isac_ctx* ctx, const isac_est_params* ep, const 
 // ---------------------------------------------------------------- cov.hip
 int isac_covariance_on(isac_ctx* ctx, hipStream_t st, const isac_c64* d_grid, int64_t N, int32_t A, isac_c64* d_Ra);
 int isac_covariance_lazy_on(isac_ctx* ctx, hipStream_t st, isac_c64* d_Ra);   // Ra of the context's native lazy echo grid
-// ---------------------------------------------------------------- music.hip
+// ---------------------------------------------------------------- eigh.hip (the device code it shares with music.hip: eigh_dev.hpp)
 // device eig: H [A x A] (device) -> ctx->eig_w [A], ctx->eig_v [A x A] (unsorted); live_replay: see the definition
 int isac_eigh_dev(isac_ctx* ctx, const isac::c64* d_H, int A, hipStream_t st, bool live_replay = true);
 int isac_eigh_replay_recover(isac_ctx* ctx, int n, hipStream_t st);
-// MUSIC's signal-subspace eigensolver: usable for this order?  first half (before numDets), second half (after), its control block
+int isac_eigh_ql_dev(isac_ctx* ctx, int n, hipStream_t st, const int* ctl, bool allow_live = true);   // the QL pipeline on the tridiagonal form in ctx->eig_scratch; ctl: see the definition
+int isac_music_tridiag_bisect_dev(isac_ctx* ctx, const isac::c64* d_H, int A, hipStream_t st);           // first half of MUSIC's signal-subspace route (before numDets)
+// ---------------------------------------------------------------- music.hip
+// MUSIC's signal-subspace eigensolver: usable for this order?  second half (after numDets), its control block
 bool isac_music_subspace_ok(isac_ctx* ctx, int A);
-int isac_music_tridiag_bisect_dev(isac_ctx* ctx, const isac::c64* d_H, int A, hipStream_t st);
 int isac_music_subspace_dev(isac_ctx* ctx, int A, const int* d_num_dets, int num_dets_host, hipStream_t st);
 const int* isac_music_ctl(isac_ctx* ctx);
 int isac_music_scan_dev(isac_ctx* ctx, int A, const int* d_num_dets, int num_dets_host, const double* d_sind, int n_steps, double d_ratio, double* d_spec, hipStream_t st, int mode = 0, const int* ctl = nullptr);
@@ -68,25 +70,4 @@ inline void timeline_mark(isac_ctx* ctx, int i, hipStream_t st) {
 }
 
 struct MusicCtl { enum { kRoute = 0, kLsub = 1 }; };     // MUSIC's control block (isac_music_ctl): ctl[kRoute]: 1 = subspace vectors delivered (kLsub of them; >= n: empty noise space)
-
-// Sum over the 64 lanes of a wavefront through DPP row operations (quad_perm, row_ror, row_bcast15 / 31 + one readlane): six short VALU
-// steps.  The __shfl_xor butterfly goes through the LDS crossbar (ds_bpermute: ~100 cycles per step, six dependent steps) -- for the
-// one-reduction-per-Householder-step kernels of music.hip that latency WAS the kernel (two of them per reflector: 37 of the 83 us of the subspace
-// kernel at n = 64).  Returns the total in every lane (wave-uniform).
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double dpp_move(double x) {
-  const int lo = __double2loint(x), hi = __double2hiint(x);
-  const int l2 = __builtin_amdgcn_update_dpp(0, lo, CTRL, ROW_MASK, 0xf, false);    // rows outside ROW_MASK receive 0: the add leaves them unchanged
-  const int h2 = __builtin_amdgcn_update_dpp(0, hi, CTRL, ROW_MASK, 0xf, false);
-  return __hiloint2double(h2, l2);
-}
-__device__ __forceinline__ double wave_sum_dpp(double x) {
-  x += dpp_move<0xB1, 0xf>(x);                       // quad_perm [1,0,3,2]
-  x += dpp_move<0x4E, 0xf>(x);                       // quad_perm [2,3,0,1]
-  x += dpp_move<0x124, 0xf>(x);                      // row_ror:4
-  x += dpp_move<0x128, 0xf>(x);                      // row_ror:8   -> every lane: the sum of its row of 16
-  x += dpp_move<0x142, 0xa>(x);                      // row_bcast15 -> rows 1, 3 += rows 0, 2
-  x += dpp_move<0x143, 0xc>(x);                      // row_bcast31 -> rows 2, 3 += rows 0 + 1: lane 63 holds the total
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(x), 63), __builtin_amdgcn_readlane(__double2loint(x), 63));
-}
 }  // namespace isac

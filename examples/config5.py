@@ -9,7 +9,7 @@ only collective is the final gather of the per-cell records (RCCL on GPUs).
 Per cell (simulation/cellSimulation.m order):
   1. layout: a seeded block of buildings around the gNB, UEs and targets dropped in the cell
   2. line of sight for every UE / target link        networkTopology.blockages.city.checkLoS      (los.hip)
-  3. sensing CPI                                      sensing.monoStaticSensing -> estimation.fft2D (echo/rdm/cov/music.hip)
+  3. sensing CPI                                      sensing.monoStaticSensing -> estimation.fft2D (echo/rdm/cov/eigh/music.hip)
   4. per UE: CDL-D (LoS) or CDL-A (NLoS) downlink channel over one slot   communication.channelModels (cdl.hip)
   5. per UE: CSI report of a 4-port CSI-RS channel estimate -- Type-I single-panel PMI search + wideband / subband CQI
      (uePhy.m:901-908 -> cqiSelect -> dlPMISelect, setupCSIRS.m:5-23 configuration)              communication.phyLayer (cqi.hip)

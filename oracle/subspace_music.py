@@ -1,5 +1,5 @@
 """NumPy restatement of the SIGNAL-SUBSPACE route the HIP library takes for doaEstimation.music on a ULA
-(csrc/music.hip: eigh_tridiag_* -> eigh_bisect_kernel -> music_subspace_kernel -> music_scan_kernel mode 3).
+(csrc/eigh.hip: eigh_tridiag_* -> eigh_bisect_kernel; csrc/music.hip: music_subspace_kernel -> music_scan_kernel mode 3).
 
 music.m:19-29 forms the noise projector Uan*Uan' from a full eig(Ra).  MUSIC only needs
     a' Uan Uan' a  =  || a - Us Us' a ||^2 ,   Us = the L eigenvectors of the L largest eigenvalues,
@@ -56,7 +56,7 @@ def householder_tridiag(h):
 
 
 def householder_tridiag_one_pass(h):
-    """The same reduction the way eigh_tridiag_fused_kernel (csrc/music.hip, n > 64) walks the matrix: the rank-2 update of reflector k - 1 is
+    """The same reduction the way eigh_tridiag_fused_kernel (csrc/eigh.hip, n > 64) walks the matrix: the rank-2 update of reflector k - 1 is
     carried as a pending pair (v, w) and applied element by element while the matrix-vector product of reflector k is accumulated -- column
     k first (it defines the reflector), then one pass over the trailing rows / columns.  Returns what householder_tridiag returns."""
     a = np.array(h, dtype=np.complex128)
@@ -98,7 +98,7 @@ def householder_tridiag_one_pass(h):
 
 
 def householder_tridiag_distributed(h, cols_per_owner=4):
-    """The same reduction the way eigh_tridiag_dist_kernel (csrc/music.hip, 64 < n <= 256) distributes it: the matrix is held COLUMN-wise by owners of
+    """The same reduction the way eigh_tridiag_dist_kernel (csrc/eigh.hip, 64 < n <= 256) distributes it: the matrix is held COLUMN-wise by owners of
     `cols_per_owner` columns each (full columns, both triangles); per reflector every owner forms its entries of p from its own columns only
     (p_j = tau sum_i conj(a_ij) v_i -- the matrix is Hermitian, no row access), ONE exchange makes p and the next column (as the owner holds it, the
     current update not yet applied) known to everybody, and everybody derives w, the updated next column and the next reflector redundantly before

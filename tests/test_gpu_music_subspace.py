@@ -1,4 +1,4 @@
-"""MUSIC's default eigensolver route on the device (csrc/music.hip, "eigensolver III"): Householder tridiagonalisation -> all eigenvalues by
+"""MUSIC's default eigensolver route on the device (csrc/eigh.hip "eigensolver III" + csrc/music.hip): Householder tridiagonalisation -> all eigenvalues by
 Sturm-count bisection -> the L = numDets signal eigenvectors by block inverse iteration -> a' Uan Uan' a = ||a - Us Us' a||^2
 (music.m:19-29,82-91), against (1) SciPy's eigh for the operator itself (isac_eigh_top), (2) the full-eigendecomposition route of the same
 library (isac_ctx_set_option(ISAC_OPT_MUSIC_ROUTE, 1)) and (3) the oracle's music_doa / fft2d for the estimates.  Tolerances: eigenvalues <= 1e-13 ||H||,

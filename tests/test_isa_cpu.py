@@ -77,6 +77,11 @@ def echo_co(tmp_path_factory):
 
 
 @pytest.fixture(scope="module")
+def eigh_co(tmp_path_factory):
+    return CodeObject(str(tmp_path_factory.mktemp("isa_eigh")), "eigh")
+
+
+@pytest.fixture(scope="module")
 def music_co(tmp_path_factory):
     return CodeObject(str(tmp_path_factory.mktemp("isa_music")), "music")
 
@@ -193,20 +198,20 @@ def test_covariance_block_kernel_is_pipelined_inside_the_wave(cov_co):
     assert sum(1 for g in gaps if g > 16) <= 2, sorted(gaps)[-6:]       # (the two code paths: diagonal and off-diagonal block pairs)
 
 
-def test_one_pass_householder_kernel_budget(music_co):
+def test_one_pass_householder_kernel_budget(eigh_co):
     """1024-thread workgroup: 128 VGPRs is all a wave gets; the fused pass keeps four matrix loads in flight per thread (eight spilled)."""
-    name, meta, asm = music_co.find("eigh_tridiag_fused_kernel")
+    name, meta, asm = eigh_co.find("eigh_tridiag_fused_kernel")
     assert meta["private_segment_fixed_size"] == 0 and meta["vgpr_count"] <= 128, meta
     loads = sum(1 for ln in asm if ln.startswith("global_load_dwordx4"))
     stores = sum(1 for ln in asm if ln.startswith("global_store_dwordx4"))
     assert loads >= 4 and stores >= 4
 
 
-def test_distributed_householder_kernel_exchange_code(music_co):
+def test_distributed_householder_kernel_exchange_code(eigh_co):
     """eigh_tridiag_dist_kernel: the matrix stays in registers (no scratch, one wave per SIMD), the exchange is tagged 16-byte granules -- write-through (sc1)
     and L2-resident stores both present, every polling load sc1 (never served by the CU's L1) -- with no release / acquire fence anywhere (no L2 write-back or
     L1 invalidate per reflector) and ONE workgroup barrier per reflector besides the two of the prologue."""
-    name, meta, asm = music_co.find("eigh_tridiag_dist_kernel")
+    name, meta, asm = eigh_co.find("eigh_tridiag_dist_kernel")
     assert meta["private_segment_fixed_size"] == 0 and meta["vgpr_count"] <= 256, meta
     assert not any(ln.startswith(("buffer_wbl2", "buffer_inv")) for ln in asm)
     st = [ln for ln in asm if ln.startswith("buffer_store_dwordx4")]
@@ -216,10 +221,10 @@ def test_distributed_householder_kernel_exchange_code(music_co):
     assert sum(1 for ln in asm if ln.startswith("s_barrier")) <= 4
 
 
-def test_scratch_users_are_the_known_ones(echo_co, music_co, cov_co):
+def test_scratch_users_are_the_known_ones(echo_co, eigh_co, music_co, cov_co):
     known = ("echo_range_kernelILi4E", "eigh_replay_kernel",       # spill a few registers by design
              "cov_lazy_kernelILi2E")                               # two targets, spread generator placement: 3 registers (16 B) beyond the 256 of two waves per SIMD
-    for co in (echo_co, music_co, cov_co):
+    for co in (echo_co, eigh_co, music_co, cov_co):
         for n, m in co.meta.items():
             if m.get("private_segment_fixed_size", 0) > 0:
                 assert any(k in n for k in known), f"{n} uses {m['private_segment_fixed_size']} B of scratch"
