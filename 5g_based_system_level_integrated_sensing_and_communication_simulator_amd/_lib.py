@@ -17,6 +17,7 @@ _lock = threading.Lock()
 ISAC_ABI_VERSION = 8          # include/isac.h ISAC_ABI_VERSION this binding was written against (checked at load)
 ISAC_MAX_EST = 4096
 NOISE_NONE, NOISE_INJECTED, NOISE_PHILOX, NOISE_PHILOX_SPECTRAL, NOISE_INJECTED_SPECTRAL = 0, 1, 2, 3, 4
+OPT_MUSIC_ROUTE, OPT_TAIL_FUSION, OPT_WIDE_ORDER, OPT_CDL_SHARE_SPECTRA, OPT_UPA_DOA = 0, 1, 2, 3, 4   # ISAC_OPT_* of isac_ctx_set_option
 
 STATUS_NAMES = {0: "OK", 1: "INVALID_ARG", 2: "HIP", 3: "NO_LOS", 4: "NO_DETECTION", 5: "CFAR_WINDOW",
                 6: "CAPACITY", 7: "UNSUPPORTED", 8: "SHORT_WAVEFORM"}
@@ -106,18 +107,100 @@ class EstResult(C.Structure):
                 ("azi_est", C.c_double * ISAC_MAX_EST), ("ele_est", C.c_double * ISAC_MAX_EST)]
 
 
-# every symbol include/isac.h declares (tests check the library exports all of them)
-EXPORTS = [
-    "isac_abi_version", "isac_abi_sizeof", "isac_device_count", "isac_ctx_create", "isac_ctx_destroy", "isac_last_error",
-    "isac_ctx_get_stream", "isac_sync", "isac_dev_alloc", "isac_dev_free", "isac_memcpy_h2d", "isac_memcpy_d2h", "isac_memcpy_d2d",
-    "isac_memset_dev", "isac_timer_start", "isac_timer_stop_ms", "isac_profile_enable", "isac_profile_last_kernel_ms",
-    "isac_basic_radar_channel_dev", "isac_basic_radar_channel", "isac_mono_static_sensing_dev",
-    "isac_mono_static_sensing", "isac_mono_static_sensing_fused_dev", "isac_echo_grid_materialize_dev", "isac_ofdm_symbol_count", "isac_ofdm_demodulate_dev", "isac_ofdm_modulate_dev", "isac_ofdm_modulate_windowed_dev", "isac_sentx_append_dev",
-    "isac_ofdm_waveform_length", "isac_cfar2d_ca", "isac_fft2d_dev", "isac_fft2d", "isac_fft2d_submit_dev", "isac_fft2d_submit_cached_dev", "isac_fft2d_collect", "isac_sensing_submit_n", "isac_sensing_collect_n", "isac_fft2d_range_stage_dev", "isac_fft2d_get_detections",
-    "isac_fft2d_get_power_window", "isac_fft2d_get_covariance", "isac_fft2d_get_music_spectrum",
-    "isac_rdm_plane_dev", "isac_covariance_dev", "isac_music_doa", "isac_ctx_set_option", "isac_ctx_share_streams", "isac_ctx_reserve", "isac_eigh_top", "isac_beamscan_doa", "isac_get_angular_spectrum2d", "isac_find2d_peaks", "isac_music2d_dev", "isac_eigh", "isac_cdl_apply_dev", "isac_cdl_apply_batch_dev", "isac_cdl_path_gains_dev", "isac_cdl_freq_response_dev", "isac_cdl_csi_estimate_batch_dev", "isac_prg_precode_dev", "isac_precoded_sinr_cqi_dev", "isac_type1sp_codebook", "isac_csi_report_dev", "isac_csi_report_batch_dev", "isac_pusch_codebook", "isac_srs_pmi_select_batch_dev", "isac_los_check_dev", "isac_winding_number_dev", "isac_synth_qpsk_grid_dev",
-    "isac_path_loss_38901", "isac_path_loss_fspl", "isac_thermal_noise_power", "isac_dft_channel_matrix", "isac_rx_frontend_batch_dev", "isac_rx_frontend_dev",
-]
+# The structs isac_abi_sizeof() knows, in ISAC_SIZEOF_* index order: (C name, mirror).  load() compares every size with the library's.
+ABI_STRUCTS = (("isac_est_result", EstResult), ("isac_est_params", EstParams), ("isac_cfar_config", CfarConfig),
+               ("isac_radar_channel_params", RadarChannelParams), ("isac_carrier", Carrier), ("isac_music2d_params", Music2dParams),
+               ("isac_csi_report", CsiReport), ("isac_sensing_job", SensingJob), ("isac_srs_report", SrsReport),
+               ("isac_rx_frontend_job", RxFrontendJob), ("isac_path_loss_config", PathLossConfig))
+
+# Every function include/isac.h declares, in the header's order: name -> (restype, argtypes).  load() sets both, so a call with a missing
+# argument (TypeError) or a float for an integer (ctypes.ArgumentError) fails instead of reaching the library, a 64-bit value arrives whole,
+# and call sites pass plain Python numbers, DeviceArrays and None.  ONE typing rule, no exceptions (tests/test_abi_cpu.py re-derives it from the header):
+#   int, int32_t -> c_int32    int64_t -> c_int64    uint64_t -> c_uint64    size_t -> c_size_t    double -> c_double
+#   pointer to a struct that has a mirror above (isac_c64 excepted: it is array data) -> POINTER(mirror): takes byref(x), an array of the mirror, None
+#   every other pointer (data, out-scalars, T[] parameters, isac_ctx*, void*, pointer to pointer) -> c_void_p: takes byref(x), ctypes arrays,
+#       ndarray.ctypes.data_as(c_void_p), a DeviceArray, ctx.handle, None
+#   returns: c_char_p for isac_last_error, c_int (an isac_status) for everything else.
+_INT, _I32, _I64, _U64, _SZ, _F64, _P, _ptr = C.c_int, C.c_int32, C.c_int64, C.c_uint64, C.c_size_t, C.c_double, C.c_void_p, C.POINTER
+PROTOTYPES = {
+    "isac_abi_version": (_INT, ()),
+    "isac_abi_sizeof": (_INT, (_I32,)),
+    "isac_device_count": (_INT, (_P,)),
+    "isac_ctx_create": (_INT, (_I32, _P)),
+    "isac_ctx_destroy": (_INT, (_P,)),
+    "isac_last_error": (C.c_char_p, (_P,)),
+    "isac_ctx_get_stream": (_INT, (_P, _P)),
+    "isac_sync": (_INT, (_P,)),
+    "isac_dev_alloc": (_INT, (_P, _SZ, _P)),
+    "isac_dev_free": (_INT, (_P, _P)),
+    "isac_memcpy_h2d": (_INT, (_P, _P, _P, _SZ)),
+    "isac_memcpy_d2h": (_INT, (_P, _P, _P, _SZ)),
+    "isac_memcpy_d2d": (_INT, (_P, _P, _P, _SZ)),
+    "isac_memset_dev": (_INT, (_P, _P, _I32, _SZ)),
+    "isac_timer_start": (_INT, (_P,)),
+    "isac_timer_stop_ms": (_INT, (_P, _P)),
+    "isac_profile_enable": (_INT, (_P, _I32)),
+    "isac_profile_last_kernel_ms": (_INT, (_P, _P)),
+    "isac_basic_radar_channel_dev": (_INT, (_P, _P, _I64, _ptr(RadarChannelParams), _P, _I32, _P, _U64, _P)),
+    "isac_basic_radar_channel": (_INT, (_P, _P, _I64, _ptr(RadarChannelParams), _P, _I32, _P, _U64, _P)),
+    "isac_mono_static_sensing_dev": (_INT, (_P, _P, _I64, _I32, _ptr(Carrier), _ptr(RadarChannelParams), _P, _I32, _P, _U64, _P, _P)),
+    "isac_mono_static_sensing": (_INT, (_P, _P, _I64, _I32, _ptr(Carrier), _ptr(RadarChannelParams), _P, _I32, _P, _U64, _P, _P)),
+    "isac_mono_static_sensing_fused_dev": (_INT, (_P, _P, _I64, _I32, _ptr(Carrier), _ptr(RadarChannelParams), _P, _I32, _P, _U64, _P, _P, _ptr(EstParams), _ptr(CfarConfig), _P)),
+    "isac_echo_grid_materialize_dev": (_INT, (_P, _P, _P)),
+    "isac_ofdm_symbol_count": (_INT, (_ptr(Carrier), _I64, _P)),
+    "isac_ofdm_demodulate_dev": (_INT, (_P, _P, _I64, _I32, _ptr(Carrier), _P, _I32)),
+    "isac_ofdm_modulate_dev": (_INT, (_P, _P, _I32, _I32, _ptr(Carrier), _F64, _P, _I64)),
+    "isac_ofdm_waveform_length": (_INT, (_ptr(Carrier), _I32, _P)),
+    "isac_ofdm_modulate_windowed_dev": (_INT, (_P, _P, _I32, _I32, _ptr(Carrier), _F64, _I32, _I32, _P, _I64)),
+    "isac_sentx_append_dev": (_INT, (_P, _ptr(Carrier), _I32, _I32, _I32, _P, _F64, _I32, _P, _I32, _I32, _P, _I64, _I64, _P)),
+    "isac_cfar2d_ca": (_INT, (_P, _P, _I32, _I32, _P, _I32, _P, _P, _F64, _P, _I32, _P)),
+    "isac_fft2d_dev": (_INT, (_P, _ptr(EstParams), _ptr(CfarConfig), _P, _P, _I32, _I32, _I32, _ptr(EstResult))),
+    "isac_fft2d": (_INT, (_P, _ptr(EstParams), _ptr(CfarConfig), _P, _P, _I32, _I32, _I32, _ptr(EstResult))),
+    "isac_fft2d_submit_dev": (_INT, (_P, _ptr(EstParams), _ptr(CfarConfig), _P, _P, _I32, _I32, _I32)),
+    "isac_fft2d_collect": (_INT, (_P, _ptr(EstResult))),
+    "isac_fft2d_submit_cached_dev": (_INT, (_P, _ptr(EstParams), _ptr(CfarConfig), _P, _P, _I32, _I32, _I32)),
+    "isac_sensing_submit_n": (_INT, (_P, _I32, _ptr(SensingJob), _I64, _I32, _ptr(Carrier), _ptr(EstParams), _ptr(CfarConfig), _F64, _P)),
+    "isac_sensing_collect_n": (_INT, (_P, _I32, _ptr(EstResult), _P)),
+    "isac_fft2d_range_stage_dev": (_INT, (_P, _ptr(EstParams), _ptr(CfarConfig), _P, _P, _I32, _I32, _I32)),
+    "isac_fft2d_get_detections": (_INT, (_P, _P, _P, _I32, _P, _P)),
+    "isac_fft2d_get_power_window": (_INT, (_P, _P, _I64, _P, _P, _P)),
+    "isac_fft2d_get_covariance": (_INT, (_P, _P, _I32)),
+    "isac_fft2d_get_music_spectrum": (_INT, (_P, _P, _I32, _P)),
+    "isac_rdm_plane_dev": (_INT, (_P, _ptr(EstParams), _P, _P, _I32, _I32, _I32, _I32, _P)),
+    "isac_covariance_dev": (_INT, (_P, _P, _I64, _I32, _P)),
+    "isac_eigh_top": (_INT, (_P, _P, _I32, _I32, _P, _P)),
+    "isac_ctx_set_option": (_INT, (_P, _I32, _I32)),
+    "isac_ctx_share_streams": (_INT, (_P, _P)),
+    "isac_ctx_reserve": (_INT, (_P, _I64, _I32, _ptr(Carrier), _ptr(RadarChannelParams), _ptr(EstParams), _ptr(CfarConfig), _F64, _P)),
+    "isac_music_doa": (_INT, (_P, _I32, _ptr(EstParams), _P, _I32, _P, _P, _P, _I32, _P)),
+    "isac_beamscan_doa": (_INT, (_P, _I32, _I32, _ptr(EstParams), _P, _I32, _P, _P, _I32, _P)),
+    "isac_get_angular_spectrum2d": (_INT, (_P, _P, _I64, _P)),
+    "isac_find2d_peaks": (_INT, (_P, _P, _I32, _I32, _I32, _P, _P, _P)),
+    "isac_music2d_dev": (_INT, (_P, _ptr(EstParams), _ptr(Music2dParams), _P, _P, _I32, _I32, _I32, _ptr(EstResult))),
+    "isac_eigh": (_INT, (_P, _P, _I32, _P, _P)),
+    "isac_cdl_apply_dev": (_INT, (_P, _P, _I64, _I32, _I32, _I32, _P, _I32, _P, _P, _I32, _P, _F64, _P)),
+    "isac_cdl_apply_batch_dev": (_INT, (_P, _ptr(CdlJob), _I32, _I64, _I32, _I32, _I32, _P, _I32, _P, _F64)),
+    "isac_cdl_path_gains_dev": (_INT, (_P, _P, _P, _I32, _I32, _I32, _I32, _P, _F64, _P, _I32, _P)),
+    "isac_prg_precode_dev": (_INT, (_P, _P, _I32, _I32, _I32, _P, _I32, _I32, _I32, _P)),
+    "isac_cdl_freq_response_dev": (_INT, (_P, _P, _I32, _I32, _I32, _I32, _P, _P, _I64, _P)),
+    "isac_cdl_csi_estimate_batch_dev": (_INT, (_P, _I32, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _I64, _P)),
+    "isac_path_loss_38901": (_INT, (_I32, _F64, _I32, _P, _P, _ptr(PathLossConfig), _P)),
+    "isac_path_loss_fspl": (_INT, (_F64, _P, _P, _P)),
+    "isac_thermal_noise_power": (_INT, (_F64, _F64, _F64, _P)),
+    "isac_dft_channel_matrix": (_INT, (_I32, _I32, _P)),
+    "isac_rx_frontend_batch_dev": (_INT, (_P, _ptr(RxFrontendJob), _I32, _I64, _I32, _I32)),
+    "isac_rx_frontend_dev": (_INT, (_P, _P, _I64, _I32, _F64, _F64, _F64, _I32, _P, _U64)),
+    "isac_precoded_sinr_cqi_dev": (_INT, (_P, _P, _I64, _I32, _I32, _P, _I32, _F64, _P, _I32, _P, _P, _P)),
+    "isac_type1sp_codebook": (_INT, (_I32, _I32, _I32, _I32, _I32, _P, _I64, _P)),
+    "isac_csi_report_dev": (_INT, (_P, _P, _I64, _I32, _I32, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _I32, _P, _F64, _P, _I32, _ptr(CsiReport), _P, _P)),
+    "isac_csi_report_batch_dev": (_INT, (_P, _I32, _P, _I64, _I32, _I32, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _I32, _P, _P, _P, _I32, _ptr(CsiReport), _P)),
+    "isac_pusch_codebook": (_INT, (_I32, _I32, _P, _I64, _P)),
+    "isac_srs_pmi_select_batch_dev": (_INT, (_P, _I32, _P, _I64, _I32, _I32, _P, _I32, _I32, _I32, _P, _P, _I32, _ptr(SrsReport))),
+    "isac_los_check_dev": (_INT, (_P, _P, _P, _I64, _P, _P, _P, _P, _I32, _P, _P)),
+    "isac_winding_number_dev": (_INT, (_P, _P, _I64, _P, _P, _P, _I32, _P)),
+    "isac_synth_qpsk_grid_dev": (_INT, (_P, _P, _I32, _I32, _I32, _U64, _I32)),
+}
+EXPORTS = list(PROTOTYPES)
 
 
 def library_path() -> str:
@@ -144,20 +227,15 @@ def load():
             except Exception:
                 pass
         lib = C.CDLL(_LIB_PATH, mode=C.RTLD_GLOBAL)
-        lib.isac_last_error.restype = C.c_char_p
-        for name in EXPORTS:
+        for name, (restype, argtypes) in PROTOTYPES.items():
             fn = getattr(lib, name)  # AttributeError here = ABI drift between isac.h and the .so
-            if name != "isac_last_error":
-                fn.restype = C.c_int
+            fn.restype, fn.argtypes = restype, argtypes
         # the library writes whole structs into caller memory: version AND struct sizes must match this binding's mirrors
         if lib.isac_abi_version() != ISAC_ABI_VERSION:
             raise RuntimeError(f"{_LIB_PATH}: ABI version {lib.isac_abi_version()} but this binding was written for {ISAC_ABI_VERSION}; rebuild the library")
-        for which, (name, cls) in enumerate((("isac_est_result", EstResult), ("isac_est_params", EstParams), ("isac_cfar_config", CfarConfig),
-                                             ("isac_radar_channel_params", RadarChannelParams), ("isac_carrier", Carrier),
-                                             ("isac_music2d_params", Music2dParams), ("isac_csi_report", CsiReport), ("isac_sensing_job", SensingJob), ("isac_srs_report", SrsReport),
-                                             ("isac_rx_frontend_job", RxFrontendJob), ("isac_path_loss_config", PathLossConfig))):
-            if lib.isac_abi_sizeof(C.c_int32(which)) != C.sizeof(cls):
-                raise RuntimeError(f"{_LIB_PATH}: sizeof({name}) = {lib.isac_abi_sizeof(C.c_int32(which))} in the library, {C.sizeof(cls)} in the binding")
+        for which, (name, cls) in enumerate(ABI_STRUCTS):
+            if lib.isac_abi_sizeof(which) != C.sizeof(cls):
+                raise RuntimeError(f"{_LIB_PATH}: sizeof({name}) = {lib.isac_abi_sizeof(which)} in the library, {C.sizeof(cls)} in the binding")
         _lib = lib
         return lib
 
@@ -173,17 +251,22 @@ class DeviceArray:
         self.ctx, self.ptr, self.shape, self.dtype, self._owner = ctx, int(ptr), tuple(int(s) for s in shape), np.dtype(dtype), owner
 
     @property
+    def _as_parameter_(self):
+        """What ctypes passes for this array: its device pointer (NULL once freed)."""
+        return C.c_void_p(self.ptr)
+
+    @property
     def nbytes(self) -> int:
         return int(np.prod(self.shape, dtype=np.int64)) * self.dtype.itemsize
 
     def numpy(self) -> np.ndarray:
         out = np.empty(self.shape, dtype=self.dtype, order="F")
-        self.ctx.check(self.ctx.lib.isac_memcpy_d2h(self.ctx.handle, _np_ptr(out), C.c_void_p(self.ptr), C.c_size_t(self.nbytes)))
+        self.ctx.check(self.ctx.lib.isac_memcpy_d2h(self.ctx.handle, _np_ptr(out), self, self.nbytes))
         return out
 
     def free(self):
         if self._owner and self.ptr:
-            self.ctx.lib.isac_dev_free(self.ctx.handle, C.c_void_p(self.ptr))
+            self.ctx.lib.isac_dev_free(self.ctx.handle, self)
             self.ptr = 0
 
     def __del__(self):
@@ -206,7 +289,7 @@ class Context:
         if st != 0 or n.value <= 0:
             raise IsacError(2, "no HIP device visible: the sensing hot path needs an MI355X (no CPU fallback)")
         h = C.c_void_p()
-        st = self.lib.isac_ctx_create(C.c_int(device % n.value), C.byref(h))
+        st = self.lib.isac_ctx_create(device % n.value, C.byref(h))
         if st != 0:
             raise IsacError(st, f"isac_ctx_create(device={device}) failed")
         self.handle = h
@@ -246,44 +329,44 @@ class Context:
         dt = np.dtype(dtype)
         nbytes = int(np.prod(shape, dtype=np.int64)) * dt.itemsize
         p = C.c_void_p()
-        self.check(self.lib.isac_dev_alloc(self.handle, C.c_size_t(nbytes), C.byref(p)))
+        self.check(self.lib.isac_dev_alloc(self.handle, nbytes, C.byref(p)))
         return DeviceArray(self, p.value, shape, dt)
 
     def to_device(self, a: np.ndarray) -> DeviceArray:
         a = np.asfortranarray(a)
         d = self.empty(a.shape, a.dtype)
-        self.check(self.lib.isac_memcpy_h2d(self.handle, C.c_void_p(d.ptr), _np_ptr(a), C.c_size_t(a.nbytes)))
+        self.check(self.lib.isac_memcpy_h2d(self.handle, d, _np_ptr(a), a.nbytes))
         return d
 
     def set_music_route(self, route: int):
         """0 = MUSIC through the signal-subspace eigensolver (default), 1 = always the full eigendecomposition (ISAC_OPT_MUSIC_ROUTE)."""
-        self.check(self.lib.isac_ctx_set_option(self.handle, C.c_int32(0), C.c_int32(int(route))))
+        self.check(self.lib.isac_ctx_set_option(self.handle, OPT_MUSIC_ROUTE, int(route)))
 
     def set_tail_fusion(self, on: bool):
         """True (default) = panel CFAR (antenna x 42-CUT-row workgroups) + per-antenna merge that also forms numDets, where the zone allows;
         False = memset of the row flags + one CFAR workgroup per antenna + a separate count kernel (ISAC_OPT_TAIL_FUSION, include/isac.h)."""
-        self.check(self.lib.isac_ctx_set_option(self.handle, C.c_int32(1), C.c_int32(1 if on else 0)))
+        self.check(self.lib.isac_ctx_set_option(self.handle, OPT_TAIL_FUSION, 1 if on else 0))
 
     def set_cdl_share_spectra(self, on: bool):
         """ISAC_OPT_CDL_SHARE_SPECTRA: consecutive overlap-save downlink batches on the SAME waveform arrays share their forward transforms (the caller promises the
         waveforms are not rewritten in between; see include/isac.h)."""
-        self.check(self.lib.isac_ctx_set_option(self.handle, C.c_int32(3), C.c_int32(1 if on else 0)))
+        self.check(self.lib.isac_ctx_set_option(self.handle, OPT_CDL_SHARE_SPECTRA, 1 if on else 0))
 
     def set_wide_order(self, on: bool):
         """ISAC_OPT_WIDE_ORDER: fft2D's covariance on the main stream, every narrow kernel on the second (see include/isac.h)."""
-        self.check(self.lib.isac_ctx_set_option(self.handle, C.c_int32(2), C.c_int32(1 if on else 0)))
+        self.check(self.lib.isac_ctx_set_option(self.handle, OPT_WIDE_ORDER, 1 if on else 0))
 
     def set_upa_doa(self, on: bool):
         """ISAC_OPT_UPA_DOA: DoA of a uniform planar array through the 2-D (elevation x azimuth) scan and find2DPeaks; off (default) = the
         reference's own failure, IsacError(UNSUPPORTED) (see include/isac.h)."""
-        self.check(self.lib.isac_ctx_set_option(self.handle, C.c_int32(4), C.c_int32(1 if on else 0)))
+        self.check(self.lib.isac_ctx_set_option(self.handle, OPT_UPA_DOA, 1 if on else 0))
 
     def angular_spectrum2d(self) -> np.ndarray:
         """The [eSteps x aSteps] dB map of this context's last UPA DoA (isac_get_angular_spectrum2d)."""
         dims = (C.c_int32 * 2)()
-        self.check(self.lib.isac_get_angular_spectrum2d(self.handle, None, C.c_int64(0), dims))
+        self.check(self.lib.isac_get_angular_spectrum2d(self.handle, None, 0, dims))
         out = np.zeros((dims[0], dims[1]), dtype=np.float64, order="F")
-        self.check(self.lib.isac_get_angular_spectrum2d(self.handle, out.ctypes.data_as(C.c_void_p), C.c_int64(out.size), dims))
+        self.check(self.lib.isac_get_angular_spectrum2d(self.handle, _np_ptr(out), out.size, dims))
         return out
 
     def share_streams(self, owner: "Context | None"):
@@ -297,7 +380,7 @@ class Context:
         a = h.shape[0]
         w = np.zeros(a)
         u = np.zeros((a, max(int(n_top), 1)), dtype=np.complex128, order="F")
-        self.check(self.lib.isac_eigh_top(self.handle, _np_ptr(h), C.c_int32(a), C.c_int32(int(n_top)), _np_ptr(w), _np_ptr(u)))
+        self.check(self.lib.isac_eigh_top(self.handle, _np_ptr(h), a, int(n_top), _np_ptr(w), _np_ptr(u)))
         return w, u[:, : int(n_top)]
 
     def timer_start(self):

@@ -221,9 +221,8 @@ class CDLChannel:
         n_paths, n_rays, nt, nr = st.base.shape
         t = np.ascontiguousarray(np.asarray(t_snaps, dtype=np.float64).reshape(-1))
         d_h = out if out is not None else ctx.empty((t.size * n_paths * nt * nr,))
-        ctx.check(ctx.lib.isac_cdl_path_gains_dev(ctx.handle, C.c_void_p(d_base.ptr), C.c_void_p(d_rate.ptr), C.c_int32(n_paths), C.c_int32(n_rays), C.c_int32(nt),
-                                                  C.c_int32(nr), C.c_void_p(d_los.ptr if d_los is not None else 0), C.c_double(los_rate),
-                                                  t.ctypes.data_as(C.c_void_p), C.c_int32(t.size), C.c_void_p(d_h.ptr)))
+        ctx.check(ctx.lib.isac_cdl_path_gains_dev(ctx.handle, d_base, d_rate, n_paths, n_rays, nt, nr, d_los, los_rate,
+                                                  t.ctypes.data_as(C.c_void_p), t.size, d_h))
         return d_h
 
 
@@ -256,8 +255,7 @@ class CDLChannel:
         d_tau, d_f, n_re = self._fr_tables(ctx, k_sub, n_sc, scs_hz)
         if out is None:
             out = ctx.empty((n_re, nr, int(ports)))
-        ctx.check(ctx.lib.isac_cdl_freq_response_dev(ctx.handle, C.c_void_p(d_h.ptr), C.c_int32(n_paths), C.c_int32(nt), C.c_int32(nr), C.c_int32(int(ports)),
-                                                     C.c_void_p(d_tau.ptr), C.c_void_p(d_f.ptr), C.c_int64(n_re), C.c_void_p(out.ptr)))
+        ctx.check(ctx.lib.isac_cdl_freq_response_dev(ctx.handle, d_h, n_paths, nt, nr, int(ports), d_tau, d_f, n_re, out))
         return out
 
 
@@ -288,8 +286,7 @@ def csiEstimateBatch(channels, k_sub, n_sc, scs_hz, ports, *, ctx, times=None, o
     los_rate = (C.c_double * n)(*[st[3] for st in statics])
     t = (C.c_double * n)(*[ch.snap_time(None if times is None else times[j]) for j, ch in enumerate(channels)])
     hf = vp(*[o.ptr for o in outs])
-    ctx.check(ctx.lib.isac_cdl_csi_estimate_batch_dev(ctx.handle, C.c_int32(n), base, rate, los, los_rate, t, C.c_int32(n_paths), C.c_int32(n_rays), C.c_int32(nt), C.c_int32(nr),
-                                                      C.c_int32(int(ports)), C.c_void_p(d_tau.ptr), C.c_void_p(d_f.ptr), C.c_int64(n_re), hf))
+    ctx.check(ctx.lib.isac_cdl_csi_estimate_batch_dev(ctx.handle, n, base, rate, los, los_rate, t, n_paths, n_rays, nt, nr, int(ports), d_tau, d_f, n_re, hf))
     return outs
 
 
@@ -355,8 +352,8 @@ def applyCDLBatch(channels, waveforms, *, ctx=None, outs=None, gains=None):
             jobs[i].block_start = st.ctypes.data_as(C.c_void_p).value
             jobs[i].n_blocks = st.size
             off += st.size
-    ctx.check(ctx.lib.isac_cdl_apply_batch_dev(ctx.handle, jobs, C.c_int32(len(channels)), C.c_int64(T), C.c_int32(nt), C.c_int32(nr), C.c_int32(n_paths),
-                                               g.ctypes.data_as(C.c_void_p), C.c_int32(FILTER_TAPS), shift.ctypes.data_as(C.c_void_p), C.c_double(scale)))
+    ctx.check(ctx.lib.isac_cdl_apply_batch_dev(ctx.handle, jobs, len(channels), T, nt, nr, n_paths,
+                                               g.ctypes.data_as(C.c_void_p), FILTER_TAPS, shift.ctypes.data_as(C.c_void_p), scale))
     if gains is None:
         for o in outs:
             o._cdl_keep = d_h_all                   # the gains stay alive until the outputs are dropped (the launches are asynchronous)
@@ -379,9 +376,7 @@ def applyCDL(channel: CDLChannel, waveform, *, ctx=None):
     scale = 1.0 / math.sqrt(nr) if channel.NormalizeChannelOutputs else 1.0
     d_x = waveform if dev else ctx.to_device(L.as_c128_f(waveform))
     d_y = ctx.empty((T, nr))
-    ctx.check(ctx.lib.isac_cdl_apply_dev(ctx.handle, C.c_void_p(d_x.ptr), C.c_int64(T), C.c_int32(nt), C.c_int32(nr), C.c_int32(h.shape[1]),
-                                         h.ctypes.data_as(C.c_void_p), C.c_int32(len(t_snap)), starts.ctypes.data_as(C.c_void_p),
-                                         g.ctypes.data_as(C.c_void_p), C.c_int32(FILTER_TAPS), shift.ctypes.data_as(C.c_void_p),
-                                         C.c_double(scale), C.c_void_p(d_y.ptr)))
+    ctx.check(ctx.lib.isac_cdl_apply_dev(ctx.handle, d_x, T, nt, nr, h.shape[1], h.ctypes.data_as(C.c_void_p), len(t_snap), starts.ctypes.data_as(C.c_void_p),
+                                         g.ctypes.data_as(C.c_void_p), FILTER_TAPS, shift.ctypes.data_as(C.c_void_p), scale, d_y))
     channel.time += T / channel.SampleRate
     return d_y if dev else d_y.numpy()

@@ -30,7 +30,7 @@ def config5GNRModels(pathLossConfig, carrierFreq, losCondition, bsPosition, uePo
     cfg = L.PathLossConfig(float(BuildingHeight), float(StreetWidth), float(EnvironmentHeight), 1 if OptionalModel else 0, 0)
     bs, ue = _pos(bsPosition), _pos(uePosition)
     out = C.c_double(0.0)
-    st = L.load().isac_path_loss_38901(C.c_int32(SCENARIOS[pathLossConfig]), C.c_double(float(carrierFreq)), C.c_int32(1 if losCondition else 0),
+    st = L.load().isac_path_loss_38901(SCENARIOS[pathLossConfig], float(carrierFreq), 1 if losCondition else 0,
                                        bs.ctypes.data_as(C.c_void_p), ue.ctypes.data_as(C.c_void_p), C.byref(cfg), C.byref(out))
     if st != 0:
         raise L.IsacError(st, "isac_path_loss_38901: carrier frequency must be positive")

@@ -15,7 +15,7 @@ from ..pathlossModels import config5GNRModels, configFreeSpaceModel
 def thermalNoisePower(temperature_k, noise_figure_db, sample_rate):
     """Nt [W] = k (T + 290 (10^(F/10) - 1)) fs   (uePhy.m:942-950, gNBPhy.m:1071-1080) -- isac_thermal_noise_power."""
     out = C.c_double(0.0)
-    st = L.load().isac_thermal_noise_power(C.c_double(float(temperature_k)), C.c_double(float(noise_figure_db)), C.c_double(float(sample_rate)), C.byref(out))
+    st = L.load().isac_thermal_noise_power(float(temperature_k), float(noise_figure_db), float(sample_rate), C.byref(out))
     if st != 0:
         raise L.IsacError(st, "isac_thermal_noise_power")
     return out.value
@@ -24,7 +24,7 @@ def thermalNoisePower(temperature_k, noise_figure_db, sample_rate):
 def dftChannelMatrix(n_tx, n_rx):
     """H [n_tx x n_rx] = fft(eye(n)); H = H(1:n_tx, 1:n_rx); H = H / norm(H), n = max(n_tx, n_rx)   (uePhy.m:732-740) -- isac_dft_channel_matrix."""
     h = np.zeros((int(n_tx), int(n_rx)), dtype=np.complex128, order="F")
-    st = L.load().isac_dft_channel_matrix(C.c_int32(int(n_tx)), C.c_int32(int(n_rx)), h.ctypes.data_as(C.c_void_p))
+    st = L.load().isac_dft_channel_matrix(int(n_tx), int(n_rx), h.ctypes.data_as(C.c_void_p))
     if st != 0:
         raise L.IsacError(st, "isac_dft_channel_matrix: antenna counts must be positive")
     return h
@@ -61,7 +61,7 @@ def rxFrontEndBatch(arrays, path_scales, gain_scales, noise_powers, *, seeds=Non
                 raise ValueError("rxFrontEndBatch: `noises` must be DeviceArrays [T x Nr]")
         jobs[j] = L.RxFrontendJob(a.ptr, w.ptr if w is not None else None, float(path_scales[j]), float(gain_scales[j]), float(noise_powers[j]),
                                   int(seeds[j]) & 0xFFFFFFFFFFFFFFFF if seeds is not None else 0)
-    ctx.check(ctx.lib.isac_rx_frontend_batch_dev(ctx.handle, jobs, C.c_int32(n), C.c_int64(T), C.c_int32(nr), C.c_int32(mode)))
+    ctx.check(ctx.lib.isac_rx_frontend_batch_dev(ctx.handle, jobs, n, T, nr, mode))
     if noises is not None:
         for a, w in zip(arrays, noises):
             a._rxfe_keep = w                        # the launch is asynchronous: the noise stays alive as long as the output does
@@ -82,9 +82,8 @@ def _dft_apply(d_x, n_rx, ctx):
     tap = np.ones(1, dtype=np.float64)
     shift = np.zeros(1, dtype=np.int32)
     d_y = ctx.empty((T, int(n_rx)))
-    ctx.check(ctx.lib.isac_cdl_apply_dev(ctx.handle, C.c_void_p(d_x.ptr), C.c_int64(T), C.c_int32(nt), C.c_int32(int(n_rx)), C.c_int32(1), hb.ctypes.data_as(C.c_void_p),
-                                         C.c_int32(1), start.ctypes.data_as(C.c_void_p), tap.ctypes.data_as(C.c_void_p), C.c_int32(1), shift.ctypes.data_as(C.c_void_p),
-                                         C.c_double(1.0), C.c_void_p(d_y.ptr)))
+    ctx.check(ctx.lib.isac_cdl_apply_dev(ctx.handle, d_x, T, nt, int(n_rx), 1, hb.ctypes.data_as(C.c_void_p), 1, start.ctypes.data_as(C.c_void_p),
+                                         tap.ctypes.data_as(C.c_void_p), 1, shift.ctypes.data_as(C.c_void_p), 1.0, d_y))
     return d_y
 
 

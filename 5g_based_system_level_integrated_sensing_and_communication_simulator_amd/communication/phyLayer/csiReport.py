@@ -19,14 +19,13 @@ def type1SinglePanelCodebook(reportConfig, nLayers: int, nPorts: int):
     lib = L.load()
     n1, n2 = (int(v) for v in getattr(reportConfig, "PanelDimensions", (1, 1))) if nPorts > 2 else (1, 1)
     dims = (C.c_int32 * 4)()
-    st = lib.isac_type1sp_codebook(C.c_int32(nPorts), C.c_int32(n1), C.c_int32(n2), C.c_int32(int(getattr(reportConfig, "CodebookMode", 1))),
-                                   C.c_int32(int(nLayers)), None, C.c_int64(0), dims)
+    st = lib.isac_type1sp_codebook(nPorts, n1, n2, int(getattr(reportConfig, "CodebookMode", 1)), int(nLayers), None, 0, dims)
     if st != 0:
         raise L.IsacError(st, "isac_type1sp_codebook: unsupported rank / panel configuration (ranks 1-2 of TS 38.214 Table 5.2.2.2.1-2)")
     shape = (nPorts, int(nLayers), dims[0], dims[1], dims[2], dims[3])
     w = np.zeros(shape, dtype=np.complex128, order="F")
-    st = lib.isac_type1sp_codebook(C.c_int32(nPorts), C.c_int32(n1), C.c_int32(n2), C.c_int32(int(getattr(reportConfig, "CodebookMode", 1))),
-                                   C.c_int32(int(nLayers)), w.ctypes.data_as(C.c_void_p), C.c_int64(w.size), dims)
+    st = lib.isac_type1sp_codebook(nPorts, n1, n2, int(getattr(reportConfig, "CodebookMode", 1)),
+                                   int(nLayers), w.ctypes.data_as(C.c_void_p), w.size, dims)
     if st != 0:
         raise L.IsacError(st, "isac_type1sp_codebook failed")
     return w
@@ -57,11 +56,11 @@ def cqiSelect(carrier, csirs, reportConfig, nLayers, H, nVar, SINRTable, *, ctx=
     tot = np.zeros(int(np.prod(w.shape[2:])), dtype=np.float64)
     n_size = int(getattr(reportConfig, "NSizeBWP", None) or carrier.NSizeGrid)
     n_start = int(getattr(reportConfig, "NStartBWP", 0) or 0)
-    ctx.check(ctx.lib.isac_csi_report_dev(ctx.handle, C.c_void_p(d_h.ptr if d_h is not None else 0), C.c_int64(n_re), C.c_int32(nr), C.c_int32(p),
-                                          k.ctypes.data_as(C.c_void_p), l.ctypes.data_as(C.c_void_p), C.c_int32(n_size), C.c_int32(n_start),
-                                          C.c_int32(int(reportConfig.SubbandSize)), C.c_int32(1 if str(reportConfig.PMIMode).lower() == "subband" else 0),
-                                          C.c_int32(1 if str(reportConfig.CQIMode).lower() == "subband" else 0), w.ctypes.data_as(C.c_void_p),
-                                          C.c_int32(int(nLayers)), dims, C.c_double(float(nVar)), table.ctypes.data_as(C.c_void_p), C.c_int32(table.size),
+    ctx.check(ctx.lib.isac_csi_report_dev(ctx.handle, d_h, n_re, nr, p,
+                                          k.ctypes.data_as(C.c_void_p), l.ctypes.data_as(C.c_void_p), n_size, n_start,
+                                          int(reportConfig.SubbandSize), 1 if str(reportConfig.PMIMode).lower() == "subband" else 0,
+                                          1 if str(reportConfig.CQIMode).lower() == "subband" else 0, w.ctypes.data_as(C.c_void_p),
+                                          int(nLayers), dims, float(nVar), table.ctypes.data_as(C.c_void_p), table.size,
                                           C.byref(rep), tot.ctypes.data_as(C.c_void_p), None))
     pmi = SimpleNamespace(i1=np.array(rep.i1[:3]), i2=np.array(rep.i2[: rep.n_subbands_pmi]))
     cqi = np.array(rep.cqi[: rep.n_cqi])
@@ -95,12 +94,12 @@ def cqiSelectBatch(carrier, csirs, reportConfig, nLayers, H_list, nVar_list, SIN
     reps = (L.CsiReport * n_ue)()
     n_size = int(getattr(reportConfig, "NSizeBWP", None) or carrier.NSizeGrid)
     n_start = int(getattr(reportConfig, "NStartBWP", 0) or 0)
-    ctx.check(ctx.lib.isac_csi_report_batch_dev(ctx.handle, C.c_int32(n_ue), ptrs, C.c_int64(n_re), C.c_int32(nr), C.c_int32(p), k.ctypes.data_as(C.c_void_p),
-                                                l.ctypes.data_as(C.c_void_p), C.c_int32(n_size), C.c_int32(n_start), C.c_int32(int(reportConfig.SubbandSize)),
-                                                C.c_int32(1 if str(reportConfig.PMIMode).lower() == "subband" else 0),
-                                                C.c_int32(1 if str(reportConfig.CQIMode).lower() == "subband" else 0), w.ctypes.data_as(C.c_void_p),
-                                                C.c_int32(int(nLayers)), dims, nvar.ctypes.data_as(C.c_void_p), table.ctypes.data_as(C.c_void_p),
-                                                C.c_int32(table.size), reps, None))
+    ctx.check(ctx.lib.isac_csi_report_batch_dev(ctx.handle, n_ue, ptrs, n_re, nr, p, k.ctypes.data_as(C.c_void_p),
+                                                l.ctypes.data_as(C.c_void_p), n_size, n_start, int(reportConfig.SubbandSize),
+                                                1 if str(reportConfig.PMIMode).lower() == "subband" else 0,
+                                                1 if str(reportConfig.CQIMode).lower() == "subband" else 0, w.ctypes.data_as(C.c_void_p),
+                                                int(nLayers), dims, nvar.ctypes.data_as(C.c_void_p), table.ctypes.data_as(C.c_void_p),
+                                                table.size, reps, None))
     out = []
     for rep in reps:
         pmi = SimpleNamespace(i1=np.array(rep.i1[:3]), i2=np.array(rep.i2[: rep.n_subbands_pmi]))

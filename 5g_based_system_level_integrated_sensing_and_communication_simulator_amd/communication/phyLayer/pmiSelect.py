@@ -28,11 +28,11 @@ def puschCodebook(nlayers: int, nports: int):
     """nrPUSCHCodebook(nlayers, nports, tpmi).' for every TPMI: W [nports x nlayers x (maxTPMI + 1)]."""
     lib = L.load()
     n = C.c_int32(0)
-    st = lib.isac_pusch_codebook(C.c_int32(int(nlayers)), C.c_int32(int(nports)), None, C.c_int64(0), C.byref(n))
+    st = lib.isac_pusch_codebook(int(nlayers), int(nports), None, 0, C.byref(n))
     if st != 0:
         raise L.IsacError(st, "isac_pusch_codebook: one or two antenna ports, layers <= ports")
     w = np.zeros((int(nports), int(nlayers), n.value), dtype=np.complex128, order="F")
-    st = lib.isac_pusch_codebook(C.c_int32(int(nlayers)), C.c_int32(int(nports)), w.ctypes.data_as(C.c_void_p), C.c_int64(w.size), C.byref(n))
+    st = lib.isac_pusch_codebook(int(nlayers), int(nports), w.ctypes.data_as(C.c_void_p), w.size, C.byref(n))
     if st != 0:
         raise L.IsacError(st, "isac_pusch_codebook failed")
     return w
@@ -57,9 +57,9 @@ def srsReportBatch(nlayers, H_list, re_k, nVar_list, bandSize, NRBsUL, SINRTable
         raise ValueError("srsReportBatch: one noise variance per UE")
     table = np.ascontiguousarray(np.asarray(SINRTable, dtype=np.float64))
     reps = (L.SrsReport * n_ue)()
-    ctx.check(ctx.lib.isac_srs_pmi_select_batch_dev(ctx.handle, C.c_int32(n_ue), ptrs, C.c_int64(n_re), C.c_int32(r), C.c_int32(p), k.ctypes.data_as(C.c_void_p),
-                                                    C.c_int32(int(NRBsUL)), C.c_int32(int(bandSize)), C.c_int32(int(nlayers)), nvar.ctypes.data_as(C.c_void_p),
-                                                    table.ctypes.data_as(C.c_void_p), C.c_int32(table.size), reps))
+    ctx.check(ctx.lib.isac_srs_pmi_select_batch_dev(ctx.handle, n_ue, ptrs, n_re, r, p, k.ctypes.data_as(C.c_void_p),
+                                                    int(NRBsUL), int(bandSize), int(nlayers), nvar.ctypes.data_as(C.c_void_p),
+                                                    table.ctypes.data_as(C.c_void_p), table.size, reps))
     return [(np.array(rep.pmi[: rep.n_subbands]), np.array(rep.sinr_subband_pmi[: rep.n_subbands]), np.array(rep.cqi_rb[: rep.n_rb])) for rep in reps]
 
 

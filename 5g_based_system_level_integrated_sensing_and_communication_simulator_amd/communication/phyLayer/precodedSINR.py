@@ -28,10 +28,10 @@ def _run(H, sigma, W, table, want_per_re, ctx):
     per = ctx.empty((n_re,), np.float64) if want_per_re else None
     mean, cqi = C.c_double(0), C.c_int32(0)
     tab = None if table is None else np.ascontiguousarray(table, dtype=np.float64)
-    ctx.check(ctx.lib.isac_precoded_sinr_cqi_dev(ctx.handle, C.c_void_p(d_h.ptr), C.c_int64(n_re), C.c_int32(nr), C.c_int32(p),
-                                                 w.ctypes.data_as(C.c_void_p), C.c_int32(w.shape[1]), C.c_double(float(sigma)),
+    ctx.check(ctx.lib.isac_precoded_sinr_cqi_dev(ctx.handle, d_h, n_re, nr, p,
+                                                 w.ctypes.data_as(C.c_void_p), w.shape[1], float(sigma),
                                                  tab.ctypes.data_as(C.c_void_p) if tab is not None else None,
-                                                 C.c_int32(0 if tab is None else tab.size), C.c_void_p(per.ptr if per is not None else 0),
+                                                 0 if tab is None else tab.size, per,
                                                  C.byref(mean), C.byref(cqi)))
     if _DEBUG_UPLOAD and not isinstance(H, L.DeviceArray):      # development switch (ISAC_DEBUG_UPLOAD=1): read the channel estimate back and compare it with what was uploaded
         import sys

@@ -25,8 +25,7 @@ def prgPrecodeGrid(layers, F, nstartgrid=0, *, ctx=None, out=None):
     if out is None:
         out = ctx.empty((K, Ls, P))
     Ff = np.asfortranarray(F)
-    ctx.check(ctx.lib.isac_prg_precode_dev(ctx.handle, C.c_void_p(d_l.ptr), C.c_int32(K), C.c_int32(Ls), C.c_int32(nu), Ff.ctypes.data_as(C.c_void_p), C.c_int32(P),
-                                           C.c_int32(nprg), C.c_int32(int(nstartgrid)), C.c_void_p(out.ptr)))
+    ctx.check(ctx.lib.isac_prg_precode_dev(ctx.handle, d_l, K, Ls, nu, Ff.ctypes.data_as(C.c_void_p), P, nprg, int(nstartgrid), out))
     return out if dev else out.numpy()
 
 

@@ -35,12 +35,11 @@ def nrOFDMModulate(carrierInfo, grid, *, nSlot=0, windowing=0, amplitude=1.0, nf
     spf = int(carrierInfo.SubcarrierSpacing) // 15
     sym0 = (int(nSlot) % spf) * 14
     t0, t1 = C.c_int64(0), C.c_int64(0)
-    ctx.lib.isac_ofdm_waveform_length(C.byref(car), C.c_int32(sym0 + l), C.byref(t1))
-    ctx.lib.isac_ofdm_waveform_length(C.byref(car), C.c_int32(sym0), C.byref(t0))
+    ctx.lib.isac_ofdm_waveform_length(C.byref(car), sym0 + l, C.byref(t1))
+    ctx.lib.isac_ofdm_waveform_length(C.byref(car), sym0, C.byref(t0))
     t_len = int(t1.value - t0.value)
     d_w = ctx.empty((t_len, a))
-    ctx.check(ctx.lib.isac_ofdm_modulate_windowed_dev(ctx.handle, C.c_void_p(d_g.ptr), C.c_int32(l), C.c_int32(a), C.byref(car), C.c_double(amplitude),
-                                                      C.c_int32(int(nSlot)), C.c_int32(int(windowing)), C.c_void_p(d_w.ptr), C.c_int64(t_len)))
+    ctx.check(ctx.lib.isac_ofdm_modulate_windowed_dev(ctx.handle, d_g, l, a, C.byref(car), amplitude, int(nSlot), int(windowing), d_w, t_len))
     return d_w if dev else d_w.numpy()
 
 
@@ -58,7 +57,7 @@ class SenTx:
         # capacity in samples: a slot's length depends on its position in the subframe only through the long CPs; the longest possible slot bounds it
         spf = int(carrierInfo.SubcarrierSpacing) // 15
         t = C.c_int64(0)
-        self.ctx.lib.isac_ofdm_waveform_length(C.byref(self.car), C.c_int32(14 * spf), C.byref(t))
+        self.ctx.lib.isac_ofdm_waveform_length(C.byref(self.car), 14 * spf, C.byref(t))
         self._t_cap = (int(t.value) // spf + self.car.nfft) * self.maxSlots
         self._grid = self.ctx.empty((self.K, 14 * self.maxSlots, self.A))
         self._wave = self.ctx.empty((self._t_cap, self.A))
@@ -75,10 +74,8 @@ class SenTx:
         is_dl = 1 if determineSlotType(self.tdd, int(currSlot)) == "D" else 0
         amp = signalAmp(self.txPower, self.car.nfft, self.K, self.A)
         t_len = C.c_int64(0)
-        ctx.check(ctx.lib.isac_sentx_append_dev(ctx.handle, C.byref(self.car), C.c_int32(self.A), C.c_int32(int(currSlot)), C.c_int32(is_dl),
-                                                C.c_void_p(g.ptr), C.c_double(amp), C.c_int32(self.windowing), C.c_void_p(self._grid.ptr),
-                                                C.c_int32(14 * self.maxSlots), C.c_int32(14 * self.nSlots), C.c_void_p(self._wave.ptr),
-                                                C.c_int64(self._t_cap), C.c_int64(self.T), C.byref(t_len)))
+        ctx.check(ctx.lib.isac_sentx_append_dev(ctx.handle, C.byref(self.car), self.A, int(currSlot), is_dl, g, amp, self.windowing, self._grid,
+                                                14 * self.maxSlots, 14 * self.nSlots, self._wave, self._t_cap, self.T, C.byref(t_len)))
         self.nSlots += 1
         self.T += int(t_len.value)
 
@@ -100,5 +97,5 @@ class SenTx:
         w = self.ctx.empty((self.T, self.A))                  # compact the waveform planes to T rows
         for a in range(self.A):
             src = self._wave.ptr + 16 * self._t_cap * a
-            self.ctx.check(self.ctx.lib.isac_memcpy_d2d(self.ctx.handle, C.c_void_p(w.ptr + 16 * self.T * a), C.c_void_p(src), C.c_size_t(16 * self.T)))
+            self.ctx.check(self.ctx.lib.isac_memcpy_d2d(self.ctx.handle, w.ptr + 16 * self.T * a, src, 16 * self.T))
         return self._grid, w

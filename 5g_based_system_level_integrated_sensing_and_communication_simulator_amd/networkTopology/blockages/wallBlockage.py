@@ -5,8 +5,6 @@ The plane of the wall (normVec, normDist) is host-side scalar prep exactly as in
 (csrc/los.hip via isac_los_check_dev / isac_winding_number_dev).  No CPU fallback."""
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
 from ... import _lib as L
@@ -49,9 +47,6 @@ class WallTable:
         self.normals = self.ctx.to_device(normals) if normals.size else None
         self.dist = self.ctx.to_device(dist) if dist.size else None
 
-    def _p(self, d):
-        return C.c_void_p(d.ptr if d is not None else 0)
-
     def check_los(self, ue, ant, return_counts=False):
         """ue, ant [3 x n] paired -> bool [n] (True = line of sight) and optionally the number of blocking walls."""
         ue = np.asfortranarray(np.asarray(ue, dtype=np.float64).reshape(3, -1))
@@ -67,10 +62,7 @@ class WallTable:
         d_ue, d_ant = ctx.to_device(ue), ctx.to_device(ant)
         d_los = ctx.empty((n,), np.uint8)
         d_cnt = ctx.empty((n,), np.int32)
-        ctx.check(ctx.lib.isac_los_check_dev(ctx.handle, C.c_void_p(d_ue.ptr), C.c_void_p(d_ant.ptr), C.c_int64(n),
-                                             self._p(self.corners), self._p(self.offsets), self._p(self.normals),
-                                             self._p(self.dist), C.c_int32(self.n_walls), C.c_void_p(d_los.ptr),
-                                             C.c_void_p(d_cnt.ptr)))
+        ctx.check(ctx.lib.isac_los_check_dev(ctx.handle, d_ue, d_ant, n, self.corners, self.offsets, self.normals, self.dist, self.n_walls, d_los, d_cnt))
         los = d_los.numpy().astype(bool)
         return (los, d_cnt.numpy()) if return_counts else los
 
@@ -83,9 +75,7 @@ class WallTable:
         ctx = self.ctx
         d_pts = ctx.to_device(pts)
         out = ctx.empty((n, self.n_walls), np.float64)
-        ctx.check(ctx.lib.isac_winding_number_dev(ctx.handle, C.c_void_p(d_pts.ptr), C.c_int64(n), self._p(self.corners),
-                                                  self._p(self.offsets), self._p(self.normals), C.c_int32(self.n_walls),
-                                                  C.c_void_p(out.ptr)))
+        ctx.check(ctx.lib.isac_winding_number_dev(ctx.handle, d_pts, n, self.corners, self.offsets, self.normals, self.n_walls, out))
         return out.numpy()
 
 

@@ -31,16 +31,11 @@ def basicRadarChannel(txWaveform, radarParams, targetLoSConditions, *, noise=Non
     if dev:
         nz = noise if (noise is None or isinstance(noise, L.DeviceArray)) else ctx.to_device(L.as_c128_f(noise))
         out = ctx.empty((T, A))
-        ctx.check(lib.isac_basic_radar_channel_dev(ctx.handle, C.c_void_p(txWaveform.ptr), C.c_int64(T), C.byref(cb.block),
-                                                   los.ctypes.data_as(C.c_void_p), C.c_int(mode),
-                                                   C.c_void_p(nz.ptr if nz is not None else 0), C.c_uint64(seed or 0),
-                                                   C.c_void_p(out.ptr)))
+        ctx.check(lib.isac_basic_radar_channel_dev(ctx.handle, txWaveform, T, C.byref(cb.block), los.ctypes.data_as(C.c_void_p), mode, nz, seed or 0, out))
         return out
     tx = L.as_c128_f(txWaveform)
     nz = None if noise is None else L.as_c128_f(noise)
     out = np.empty((T, A), dtype=np.complex128, order="F")
-    ctx.check(lib.isac_basic_radar_channel(ctx.handle, tx.ctypes.data_as(C.c_void_p), C.c_int64(T), C.byref(cb.block),
-                                           los.ctypes.data_as(C.c_void_p), C.c_int(mode),
-                                           nz.ctypes.data_as(C.c_void_p) if nz is not None else C.c_void_p(0),
-                                           C.c_uint64(seed or 0), out.ctypes.data_as(C.c_void_p)))
+    ctx.check(lib.isac_basic_radar_channel(ctx.handle, tx.ctypes.data_as(C.c_void_p), T, C.byref(cb.block), los.ctypes.data_as(C.c_void_p), mode,
+                                           None if nz is None else nz.ctypes.data_as(C.c_void_p), seed or 0, out.ctypes.data_as(C.c_void_p)))
     return out

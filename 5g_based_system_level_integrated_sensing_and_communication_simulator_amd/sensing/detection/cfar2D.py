@@ -32,10 +32,8 @@ class CFARDetector2D:
         n_det = C.c_int32(0)
         g = (C.c_int32 * 2)(*self.GuardBandSize)
         t = (C.c_int32 * 2)(*self.TrainingBandSize)
-        ctx.check(ctx.lib.isac_cfar2d_ca(ctx.handle, p.ctypes.data_as(C.c_void_p), C.c_int32(p.shape[0]), C.c_int32(p.shape[1]),
-                                         cut.ctypes.data_as(C.c_void_p), C.c_int32(n_cut), g, t,
-                                         C.c_double(self.ProbabilityFalseAlarm), det.ctypes.data_as(C.c_void_p),
-                                         C.c_int32(max(n_cut, 1)), C.byref(n_det)))
+        ctx.check(ctx.lib.isac_cfar2d_ca(ctx.handle, p.ctypes.data_as(C.c_void_p), p.shape[0], p.shape[1], cut.ctypes.data_as(C.c_void_p), n_cut, g, t,
+                                         self.ProbabilityFalseAlarm, det.ctypes.data_as(C.c_void_p), max(n_cut, 1), C.byref(n_det)))
         return det[:, : n_det.value].astype(np.int64)
 
 

@@ -18,9 +18,8 @@ def _scan(method, numDets, radarEstParams, Ra, ctx):
     ep = est_block(radarEstParams)
     cap = 4096
     azi, ele, n = np.zeros(cap), np.zeros(cap), C.c_int32(0)
-    ctx.check(ctx.lib.isac_beamscan_doa(ctx.handle, C.c_int32(method), C.c_int32(int(numDets)), C.byref(ep), ra.ctypes.data_as(C.c_void_p),
-                                        C.c_int32(A), azi.ctypes.data_as(C.c_void_p), ele.ctypes.data_as(C.c_void_p), C.c_int32(cap),
-                                        C.byref(n)))
+    ctx.check(ctx.lib.isac_beamscan_doa(ctx.handle, method, int(numDets), C.byref(ep), ra.ctypes.data_as(C.c_void_p),
+                                        A, azi.ctypes.data_as(C.c_void_p), ele.ctypes.data_as(C.c_void_p), cap, C.byref(n)))
     return azi[: n.value].copy(), ele[: n.value].copy()
 
 

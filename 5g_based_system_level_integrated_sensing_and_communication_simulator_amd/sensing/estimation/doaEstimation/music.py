@@ -27,8 +27,7 @@ def music(numDets, radarEstParams, Ra, *, ctx=None):
     azi = np.zeros(cap)
     ele = np.zeros(cap)
     l_out, n_est = C.c_int32(0), C.c_int32(0)
-    ctx.check(ctx.lib.isac_music_doa(ctx.handle, C.c_int32(nd), C.byref(ep), ra.ctypes.data_as(C.c_void_p), C.c_int32(A),
-                                     C.byref(l_out), azi.ctypes.data_as(C.c_void_p), ele.ctypes.data_as(C.c_void_p),
-                                     C.c_int32(cap), C.byref(n_est)))
+    ctx.check(ctx.lib.isac_music_doa(ctx.handle, nd, C.byref(ep), ra.ctypes.data_as(C.c_void_p), A,
+                                     C.byref(l_out), azi.ctypes.data_as(C.c_void_p), ele.ctypes.data_as(C.c_void_p), cap, C.byref(n_est)))
     n = n_est.value
     return int(l_out.value), azi[:n].copy(), ele[:n].copy()

@@ -63,19 +63,17 @@ def fft2D(radarEstParams, cfar, rxGrid, txGrid, *, ctx=None, return_debug=False,
     res = L.EstResult()
     lib = ctx.lib
     if dev and reuse_range:
-        st = lib.isac_fft2d_submit_cached_dev(ctx.handle, C.byref(ep), C.byref(cf), C.c_void_p(rxGrid.ptr or None), C.c_void_p(txGrid.ptr),
-                                              C.c_int32(K), C.c_int32(Lsym), C.c_int32(A))
+        st = lib.isac_fft2d_submit_cached_dev(ctx.handle, C.byref(ep), C.byref(cf), rxGrid, txGrid, K, Lsym, A)
         if st == 0:
             st = lib.isac_fft2d_collect(ctx.handle, C.byref(res))
     elif reuse_range:
         raise ValueError("reuse_range needs the DeviceArray grids of a monoStaticSensing(fuse_fft2d=...) call")
     elif dev:
-        st = lib.isac_fft2d_dev(ctx.handle, C.byref(ep), C.byref(cf), C.c_void_p(rxGrid.ptr), C.c_void_p(txGrid.ptr),
-                                C.c_int32(K), C.c_int32(Lsym), C.c_int32(A), C.byref(res))
+        st = lib.isac_fft2d_dev(ctx.handle, C.byref(ep), C.byref(cf), rxGrid, txGrid, K, Lsym, A, C.byref(res))
     else:
         rx, tx = L.as_c128_f(rxGrid), L.as_c128_f(txGrid)
         st = lib.isac_fft2d(ctx.handle, C.byref(ep), C.byref(cf), rx.ctypes.data_as(C.c_void_p), tx.ctypes.data_as(C.c_void_p),
-                            C.c_int32(K), C.c_int32(Lsym), C.c_int32(A), C.byref(res))
+                            K, Lsym, A, C.byref(res))
     ctx.check(st)
     est = SimpleNamespace(rngEst=np.array(res.rng_est[: res.n_rng]), velEst=np.array(res.vel_est[: res.n_vel]),
                           aziEst=np.array(res.azi_est[: res.n_azi]), eleEst=np.array(res.ele_est[: res.n_azi]))
@@ -100,7 +98,7 @@ def fft2D_submit(radarEstParams, cfar, rxGrid, txGrid, *, ctx=None, reuse_range=
     cf = _cfar_block(cfar)
     ep = est_block(radarEstParams)
     fn = ctx.lib.isac_fft2d_submit_cached_dev if reuse_range else ctx.lib.isac_fft2d_submit_dev
-    ctx.check(fn(ctx.handle, C.byref(ep), C.byref(cf), C.c_void_p(rxGrid.ptr or None), C.c_void_p(txGrid.ptr), C.c_int32(K), C.c_int32(Lsym), C.c_int32(A)))
+    ctx.check(fn(ctx.handle, C.byref(ep), C.byref(cf), rxGrid, txGrid, K, Lsym, A))
     return ctx
 
 
@@ -118,23 +116,23 @@ def fft2D_debug(ctx, A):
     lib = ctx.lib
     n_total = C.c_int32(0)
     off = np.zeros(A + 1, dtype=np.int32)
-    ctx.check(lib.isac_fft2d_get_detections(ctx.handle, None, None, C.c_int32(1 << 30), off.ctypes.data_as(C.c_void_p), C.byref(n_total)))
+    ctx.check(lib.isac_fft2d_get_detections(ctx.handle, None, None, 1 << 30, off.ctypes.data_as(C.c_void_p), C.byref(n_total)))
     n = int(n_total.value)
     idx = np.zeros((2, max(n, 1)), dtype=np.int32, order="F")
     pw = np.zeros(max(n, 1), dtype=np.float64)
     ctx.check(lib.isac_fft2d_get_detections(ctx.handle, idx.ctypes.data_as(C.c_void_p), pw.ctypes.data_as(C.c_void_p),
-                                            C.c_int32(max(n, 1)), off.ctypes.data_as(C.c_void_p), C.byref(n_total)))
+                                            max(n, 1), off.ctypes.data_as(C.c_void_p), C.byref(n_total)))
     dets = [idx[:, off[a]:off[a + 1]].astype(np.int64) for a in range(A)]
     dims = (C.c_int32 * 3)()
     fr, fc = C.c_int32(0), C.c_int32(0)
-    ctx.check(lib.isac_fft2d_get_power_window(ctx.handle, None, C.c_int64(0), dims, C.byref(fr), C.byref(fc)))
+    ctx.check(lib.isac_fft2d_get_power_window(ctx.handle, None, 0, dims, C.byref(fr), C.byref(fc)))
     pwin = np.zeros(tuple(dims), dtype=np.float64, order="F")
-    ctx.check(lib.isac_fft2d_get_power_window(ctx.handle, pwin.ctypes.data_as(C.c_void_p), C.c_int64(pwin.size), dims, C.byref(fr), C.byref(fc)))
+    ctx.check(lib.isac_fft2d_get_power_window(ctx.handle, pwin.ctypes.data_as(C.c_void_p), pwin.size, dims, C.byref(fr), C.byref(fc)))
     ra = np.zeros((A, A), dtype=np.complex128, order="F")
-    ctx.check(lib.isac_fft2d_get_covariance(ctx.handle, ra.ctypes.data_as(C.c_void_p), C.c_int32(A)))
+    ctx.check(lib.isac_fft2d_get_covariance(ctx.handle, ra.ctypes.data_as(C.c_void_p), A))
     ns = C.c_int32(0)
-    ctx.check(lib.isac_fft2d_get_music_spectrum(ctx.handle, None, C.c_int32(0), C.byref(ns)))
+    ctx.check(lib.isac_fft2d_get_music_spectrum(ctx.handle, None, 0, C.byref(ns)))
     spec = np.zeros(max(ns.value, 1), dtype=np.float64)
-    ctx.check(lib.isac_fft2d_get_music_spectrum(ctx.handle, spec.ctypes.data_as(C.c_void_p), C.c_int32(spec.size), C.byref(ns)))
+    ctx.check(lib.isac_fft2d_get_music_spectrum(ctx.handle, spec.ctypes.data_as(C.c_void_p), spec.size, C.byref(ns)))
     return SimpleNamespace(detections=dets, det_pow=[pw[off[a]:off[a + 1]] for a in range(A)], power_window=pwin,
                            first_row=int(fr.value), first_col=int(fc.value), Ra=ra, spectrum_db=spec[: ns.value])

@@ -23,7 +23,6 @@ def music2D(rdrEstParams, bsParams, rxGrid, txGrid, *, ctx=None):
     mp = L.Music2dParams(float(rdrEstParams.fc), float(rdrEstParams.Tsri), float(bsParams.scs) * 1e3, float(zone[0, 1]), float(zone[1, 1]) * 2.0)
     ep = est_block(rdrEstParams)
     res = L.EstResult()
-    ctx.check(ctx.lib.isac_music2d_dev(ctx.handle, C.byref(ep), C.byref(mp), C.c_void_p(d_rx.ptr), C.c_void_p(d_tx.ptr),
-                                       C.c_int32(K), C.c_int32(Ls), C.c_int32(A), C.byref(res)))
+    ctx.check(ctx.lib.isac_music2d_dev(ctx.handle, C.byref(ep), C.byref(mp), d_rx, d_tx, K, Ls, A, C.byref(res)))
     return SimpleNamespace(aziEst=np.array(res.azi_est[: res.n_azi]), eleEst=np.array(res.ele_est[: res.n_azi]),
                            rngEst=np.array(res.rng_est[: res.n_rng]), velEst=np.array(res.vel_est[: res.n_vel]), L=int(res.num_dets))

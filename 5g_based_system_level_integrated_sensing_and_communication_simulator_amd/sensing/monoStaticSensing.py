@@ -14,8 +14,10 @@ class LazyEchoGrid:
     ``fft2D(..., reuse_range=True)`` as rxGrid, or call ``.materialize()`` for the array (monoStaticSensing.m:1 returns it; cellSimulation.m:194-197 only passes it on to fft2D).
     Valid until the next echo call on the same context."""
 
+    _as_parameter_ = None       # passed to the library it is d_echo_grid / d_rx_grid == NULL: the grid the context keeps
+
     def __init__(self, ctx, shape):
-        self.ctx, self.shape, self.ptr = ctx, tuple(int(v) for v in shape), 0
+        self.ctx, self.shape = ctx, tuple(int(v) for v in shape)
 
     def materialize(self, out=None):
         """The grid as a DeviceArray [nSc x nSym x nAnts] -- bit for bit what the non-lazy call stores (isac_echo_grid_materialize_dev)."""
@@ -25,7 +27,7 @@ class LazyEchoGrid:
             raise L.IsacError(1, "the context's lazy echo grid has been replaced by a later call")
         if out is None:
             out = self.ctx.empty(self.shape)
-        self.ctx.check(self.ctx.lib.isac_echo_grid_materialize_dev(self.ctx.handle, C.c_void_p(out.ptr), dims))
+        self.ctx.check(self.ctx.lib.isac_echo_grid_materialize_dev(self.ctx.handle, out, dims))
         return out
 
     def numpy(self):
@@ -75,44 +77,40 @@ def monoStaticSensing(txWaveform, txDimension, carrierInfo, radarParams, targetL
         mode = L.NOISE_NONE
     lib = ctx.lib
     lw = C.c_int32(0)
-    st = lib.isac_ofdm_symbol_count(C.byref(car), C.c_int64(T), C.byref(lw))
+    st = lib.isac_ofdm_symbol_count(C.byref(car), T, C.byref(lw))
     if st != 0:
         raise L.IsacError(st, "isac_ofdm_symbol_count failed")
     l_out = max(int(lw.value), int(txDimension[1]))
     lo = C.c_int32(0)
     if dev:
+        tx = txWaveform
         nz = noise if (noise is None or isinstance(noise, L.DeviceArray)) else ctx.to_device(L.as_c128_f(noise))
-        shape = (car.n_sc, max(l_out, 1), A)
-        if lazy:
-            if fuse_fft2d is None or out is not None:
-                raise ValueError("lazy=True needs fuse_fft2d=(radarEstParams, cfar, txGrid) and no `out` array")
-            out = LazyEchoGrid(ctx, shape)
-        elif out is None:
-            out = ctx.empty(shape)
-        elif tuple(out.shape) != shape:
-            raise ValueError(f"out must have shape {shape}")
-        if fuse_fft2d is not None:
-            from .estimation.fft2D import _cfar_block
-            from ._marshal import est_block
-            est_params, cfar, tx_grid = fuse_fft2d
-            if not isinstance(tx_grid, L.DeviceArray) or tuple(tx_grid.shape) != shape:
-                raise ValueError("fuse_fft2d needs a DeviceArray txGrid with the echo grid's shape")
-            ep, cf = est_block(est_params), _cfar_block(cfar)
-            ctx.check(lib.isac_mono_static_sensing_fused_dev(ctx.handle, C.c_void_p(txWaveform.ptr), C.c_int64(T), C.c_int32(int(txDimension[1])),
-                                                             C.byref(car), C.byref(cb.block), los.ctypes.data_as(C.c_void_p), C.c_int(mode),
-                                                             C.c_void_p(nz.ptr if nz is not None else 0), C.c_uint64(seed or 0),
-                                                             C.c_void_p(out.ptr or None), C.byref(lo), C.byref(ep), C.byref(cf), C.c_void_p(tx_grid.ptr)))
-            return out
-        ctx.check(lib.isac_mono_static_sensing_dev(ctx.handle, C.c_void_p(txWaveform.ptr), C.c_int64(T), C.c_int32(int(txDimension[1])),
-                                                   C.byref(car), C.byref(cb.block), los.ctypes.data_as(C.c_void_p), C.c_int(mode),
-                                                   C.c_void_p(nz.ptr if nz is not None else 0), C.c_uint64(seed or 0),
-                                                   C.c_void_p(out.ptr), C.byref(lo)))
+    else:
+        tx_h, nz_h = L.as_c128_f(txWaveform), None if noise is None else L.as_c128_f(noise)     # named: the host arrays must outlive the call
+        tx, nz = tx_h.ctypes.data_as(C.c_void_p), None if nz_h is None else nz_h.ctypes.data_as(C.c_void_p)
+    # what the three echo entry points share, in include/isac.h's order: ctx, tx_wave, T, tx_dim_l, carrier, rp, los, noise_mode, noise_unit, seed
+    echo_args = (ctx.handle, tx, T, int(txDimension[1]), C.byref(car), C.byref(cb.block), los.ctypes.data_as(C.c_void_p), mode, nz, seed or 0)
+    shape = (car.n_sc, max(l_out, 1), A)
+    if not dev:
+        out = np.empty(shape, dtype=np.complex128, order="F")
+        ctx.check(lib.isac_mono_static_sensing(*echo_args, out.ctypes.data_as(C.c_void_p), C.byref(lo)))
         return out
-    tx = L.as_c128_f(txWaveform)
-    nz = None if noise is None else L.as_c128_f(noise)
-    out = np.empty((car.n_sc, max(l_out, 1), A), dtype=np.complex128, order="F")
-    ctx.check(lib.isac_mono_static_sensing(ctx.handle, tx.ctypes.data_as(C.c_void_p), C.c_int64(T), C.c_int32(int(txDimension[1])),
-                                           C.byref(car), C.byref(cb.block), los.ctypes.data_as(C.c_void_p), C.c_int(mode),
-                                           nz.ctypes.data_as(C.c_void_p) if nz is not None else C.c_void_p(0),
-                                           C.c_uint64(seed or 0), out.ctypes.data_as(C.c_void_p), C.byref(lo)))
+    if lazy:
+        if fuse_fft2d is None or out is not None:
+            raise ValueError("lazy=True needs fuse_fft2d=(radarEstParams, cfar, txGrid) and no `out` array")
+        out = LazyEchoGrid(ctx, shape)
+    elif out is None:
+        out = ctx.empty(shape)
+    elif tuple(out.shape) != shape:
+        raise ValueError(f"out must have shape {shape}")
+    if fuse_fft2d is None:
+        ctx.check(lib.isac_mono_static_sensing_dev(*echo_args, out, C.byref(lo)))
+        return out
+    from .estimation.fft2D import _cfar_block
+    from ._marshal import est_block
+    est_params, cfar, tx_grid = fuse_fft2d
+    if not isinstance(tx_grid, L.DeviceArray) or tuple(tx_grid.shape) != shape:
+        raise ValueError("fuse_fft2d needs a DeviceArray txGrid with the echo grid's shape")
+    ep, cf = est_block(est_params), _cfar_block(cfar)
+    ctx.check(lib.isac_mono_static_sensing_fused_dev(*echo_args, out, C.byref(lo), C.byref(ep), C.byref(cf), tx_grid))
     return out

@@ -19,6 +19,6 @@ def reserve(waveformLength, txDimension, carrierInfo, radarParams, cfar, *, nfft
     car = carrier_block(carrierInfo, nfft)
     ep, cf = est_block(radarParams), _cfar_block(cfar)
     ms = C.c_double(0.0)
-    ctx.check(ctx.lib.isac_ctx_reserve(ctx.handle, C.c_int64(int(waveformLength)), C.c_int32(int(txDimension[1])), C.byref(car), C.byref(cb.block),
-                                       C.byref(ep), C.byref(cf), C.c_double(float(warm_ms)), C.byref(ms)))
+    ctx.check(ctx.lib.isac_ctx_reserve(ctx.handle, int(waveformLength), int(txDimension[1]), C.byref(car), C.byref(cb.block),
+                                       C.byref(ep), C.byref(cf), float(warm_ms), C.byref(ms)))
     return float(ms.value)

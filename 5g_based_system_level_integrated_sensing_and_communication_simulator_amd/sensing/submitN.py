@@ -45,8 +45,7 @@ class SensingBatch:
 
     def submit(self):
         lib = self.ctxs[0].lib
-        st = lib.isac_sensing_submit_n(self.handles, C.c_int32(self.n), self.jobs, C.c_int64(self.T), C.c_int32(self.tx_dim_l), C.byref(self.car), C.byref(self.ep),
-                                       C.byref(self.cf), C.c_double(self.pace_us), self.status)
+        st = lib.isac_sensing_submit_n(self.handles, self.n, self.jobs, self.T, self.tx_dim_l, C.byref(self.car), C.byref(self.ep), C.byref(self.cf), self.pace_us, self.status)
         if st != 0:
             raise L.IsacError(st, "isac_sensing_submit_n: malformed call")
         return self
@@ -54,7 +53,7 @@ class SensingBatch:
     def collect(self):
         """[estResults | IsacError] per job, in order (an error is returned, not raised: the reference maps a failed cell to senResults = NaN, cellSimulation.m:196-202)."""
         lib = self.ctxs[0].lib
-        st = lib.isac_sensing_collect_n(self.handles, C.c_int32(self.n), self.out, self.status)
+        st = lib.isac_sensing_collect_n(self.handles, self.n, self.out, self.status)
         if st != 0:
             raise L.IsacError(st, "isac_sensing_collect_n: malformed call")
         res = []

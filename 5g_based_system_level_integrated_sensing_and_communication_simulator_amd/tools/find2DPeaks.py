@@ -22,7 +22,7 @@ def find2DPeaks(PdB, numPeaks, *, ctx=None):
     ele = np.zeros(max(n, 1), dtype=np.int32)
     azi = np.zeros(max(n, 1), dtype=np.int32)
     found = C.c_int32(0)
-    ctx.check(ctx.lib.isac_find2d_peaks(ctx.handle, p.ctypes.data_as(C.c_void_p), C.c_int32(rows), C.c_int32(cols), C.c_int32(int(numPeaks)),
+    ctx.check(ctx.lib.isac_find2d_peaks(ctx.handle, p.ctypes.data_as(C.c_void_p), rows, cols, int(numPeaks),
                                         ele.ctypes.data_as(C.c_void_p), azi.ctypes.data_as(C.c_void_p), C.byref(found)))
     k = found.value
     return ele[:k].astype(np.int64), azi[:k].astype(np.int64)

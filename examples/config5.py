@@ -111,9 +111,8 @@ def main():
         wave = ctx.empty((slot_T, args.ants))
         car = pkg._lib.Carrier(cell.K, 4096, 30, 0)
         grid = ctx.empty((cell.K, 14, args.ants))
-        ctx.check(ctx.lib.isac_synth_qpsk_grid_dev(ctx.handle, bench.C.c_void_p(grid.ptr), cell.K, 14, args.ants, bench.C.c_uint64(0xD1 + c), 0))
-        ctx.check(ctx.lib.isac_ofdm_modulate_dev(ctx.handle, bench.C.c_void_p(grid.ptr), 14, args.ants, bench.C.byref(car), bench.C.c_double(1.0),
-                                                 bench.C.c_void_p(wave.ptr), bench.C.c_int64(slot_T)))
+        ctx.check(ctx.lib.isac_synth_qpsk_grid_dev(ctx.handle, grid, cell.K, 14, args.ants, 0xD1 + c, 0))
+        ctx.check(ctx.lib.isac_ofdm_modulate_dev(ctx.handle, grid, 14, args.ants, bench.C.byref(car), 1.0, wave, slot_T))
         cqis, pmis = [], []
         csi_k, csi_l = csirs_positions(273)
         report = SimpleNamespace(NSizeBWP=273, NStartBWP=0, PanelDimensions=(2, 1), CodebookMode=1, PMIMode="Subband", CQIMode="Subband",

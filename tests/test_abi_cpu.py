@@ -37,9 +37,94 @@ def test_header_symbols_all_exported(lib_path):
     assert lib.isac_abi_version() == int(m.group(1)) == pkg._lib.ISAC_ABI_VERSION >= 3
     # struct sizes as the library was built == the ctypes mirrors (the loader refuses a mismatch; ADVICE r2)
     L = pkg._lib
-    for which, cls in enumerate((L.EstResult, L.EstParams, L.CfarConfig, L.RadarChannelParams, L.Carrier, L.Music2dParams, L.CsiReport)):
-        assert lib.isac_abi_sizeof(ctypes.c_int32(which)) == ctypes.sizeof(cls)
+    selectors = {int(v): n for n, v in re.findall(r"\bISAC_SIZEOF_(\w+) = (\d+)", hdr)}
+    assert [name for name, _ in L.ABI_STRUCTS] == ["isac_" + selectors[i].lower() for i in range(len(selectors))] and len(selectors) == 11
+    for which, (name, cls) in enumerate(L.ABI_STRUCTS):
+        assert lib.isac_abi_sizeof(ctypes.c_int32(which)) == ctypes.sizeof(cls), name
     assert lib.isac_abi_sizeof(ctypes.c_int32(99)) == -1
+
+
+# ---- the prototype table of _lib.py against include/isac.h.  The typing rule is restated here, not imported from the binding:
+#      by-value scalars by their C type, a pointer to a struct the binding mirrors -> POINTER(mirror), every other pointer (T[] parameters included) -> c_void_p.
+_SCALARS = {"int": ctypes.c_int32, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64, "size_t": ctypes.c_size_t,
+            "double": ctypes.c_double}
+_MIRRORS = {"isac_carrier": "Carrier", "isac_est_params": "EstParams", "isac_cfar_config": "CfarConfig", "isac_radar_channel_params": "RadarChannelParams",
+            "isac_music2d_params": "Music2dParams", "isac_est_result": "EstResult", "isac_csi_report": "CsiReport", "isac_srs_report": "SrsReport",
+            "isac_cdl_job": "CdlJob", "isac_sensing_job": "SensingJob", "isac_rx_frontend_job": "RxFrontendJob", "isac_path_loss_config": "PathLossConfig"}
+_RETURNS = {"int": ctypes.c_int, "const char*": ctypes.c_char_p}
+
+
+def _header_without_comments():
+    hdr = open(os.path.join(ROOT, "include", "isac.h")).read()
+    return re.sub(r"//[^\n]*", " ", re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S))
+
+
+def _header_prototypes():
+    """[(return type, name, [parameter type, ...])] of every function include/isac.h declares; `T name[n]` is the pointer `T*`."""
+    out = []
+    for ret, name, params in re.findall(r"\b(int|const char\s*\*)\s+(isac_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", _header_without_comments()):
+        types = []
+        for p in ([] if params.strip() == "void" else params.split(",")):
+            m = re.fullmatch(r"(.*?)\s*\b\w+\s*(\[\d*\])?", " ".join(p.split()))
+            types.append(re.sub(r"\s*\*", "*", m.group(1)) + ("*" if m.group(2) else ""))
+        out.append((re.sub(r"\s*\*", "*", ret), name, types))
+    return out
+
+
+def _rule(c_type, L):
+    if "*" not in c_type:
+        return _SCALARS[c_type]
+    m = re.fullmatch(r"(?:const )?(isac_\w+)\*", c_type)
+    return ctypes.POINTER(getattr(L, _MIRRORS[m.group(1)])) if m and m.group(1) in _MIRRORS else ctypes.c_void_p
+
+
+def test_prototype_table_matches_the_header(lib_path):
+    L = load_pkg()._lib
+    protos = _header_prototypes()
+    hdr = open(os.path.join(ROOT, "include", "isac.h")).read()
+    assert len(protos) == 76 == len(set(re.findall(r"\b(isac_[a-z0-9_]+)\s*\(", hdr)) - {"isac_status"})      # the regex found every declaration
+    assert [name for _, name, _ in protos] == list(L.PROTOTYPES) == list(L.EXPORTS)                              # same names, in the header's order
+    for ret, name, types in protos:
+        restype, argtypes = L.PROTOTYPES[name]
+        assert restype is _RETURNS[ret], name
+        assert len(argtypes) == len(types), name
+        for i, (got, c_type) in enumerate(zip(argtypes, types)):
+            assert got is _rule(c_type, L), f"{name} argument {i}: {c_type}"
+    lib = L.load()
+    for name, (restype, argtypes) in L.PROTOTYPES.items():                                                       # and load() applied the table
+        fn = getattr(lib, name)
+        assert fn.restype is restype and tuple(fn.argtypes) == tuple(argtypes), name
+
+
+def test_option_and_status_constants_match_the_header():
+    L = load_pkg()._lib
+    hdr = _header_without_comments()
+    opts = {n: int(v) for n, v in re.findall(r"\bISAC_OPT_(\w+) = (\d+)", hdr)}
+    assert len(opts) == 5 and opts == {n[4:]: getattr(L, n) for n in dir(L) if n.startswith("OPT_")}
+    body = re.search(r"typedef enum \{([^}]*)\} isac_status;", hdr).group(1)
+    status = {int(v): n for n, v in re.findall(r"\bISAC_(?:ERR_)?(\w+) = (\d+)", body)}
+    assert len(status) == 9 and status == L.STATUS_NAMES
+
+
+def test_prototypes_reject_a_wrong_call_and_pass_64_bit_values(lib_path):
+    """Through load(), with plain Python arguments.  A float for int64_t T is a ctypes.ArgumentError; one argument too few is refused by
+    ctypes before the call as well, as a TypeError ("this function takes at least 3 arguments": ctypes raises ArgumentError for a
+    conversion only).  T = 2**33 reaches the library whole: the symbol count n it returns brackets T."""
+    L = load_pkg()._lib
+    lib = L.load()
+    car = L.Carrier(3276, 4096, 30, 0)
+    n = ctypes.c_int32(0)
+    with pytest.raises(ctypes.ArgumentError):
+        lib.isac_ofdm_symbol_count(ctypes.byref(car), 983040.0, ctypes.byref(n))
+    with pytest.raises(TypeError, match="at least 3 arguments"):
+        lib.isac_ofdm_symbol_count(ctypes.byref(car), 983040)
+    T = 2 ** 33
+    assert lib.isac_ofdm_symbol_count(ctypes.byref(car), T, ctypes.byref(n)) == 0
+    lo, hi = ctypes.c_int64(0), ctypes.c_int64(0)
+    assert lib.isac_ofdm_waveform_length(ctypes.byref(car), n.value, ctypes.byref(lo)) == 0
+    assert lib.isac_ofdm_waveform_length(ctypes.byref(car), n.value + 1, ctypes.byref(hi)) == 0
+    print(f"T = {T}: n = {n.value}, waveform_length(n) = {lo.value}, waveform_length(n + 1) = {hi.value}")
+    assert lo.value <= T < hi.value
 
 
 def test_size_queries_need_no_gpu(lib_path):

@@ -9,7 +9,7 @@ for A in (96, 128, 256):
     w = np.zeros(A); v = np.zeros((A, A), dtype=np.complex128, order="F")
     for _ in range(2):
         t0 = time.perf_counter()
-        ctx.check(lib.isac_eigh(ctx.handle, h.ctypes.data_as(C.c_void_p), C.c_int32(A), w.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p)))
+        ctx.check(lib.isac_eigh(ctx.handle, h.ctypes.data_as(C.c_void_p), A, w.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p)))
         dt = time.perf_counter() - t0
     wr = np.linalg.eigvalsh(h)
     print(A, "ms", round(dt * 1e3, 2), "err", np.abs(w - wr).max() / np.abs(wr).max(), "orth", np.abs(v.conj().T @ v - np.eye(A)).max())

@@ -9,7 +9,7 @@ pkg = importlib.import_module(bench.PKG)
 cell = bench.Cell(pkg, 0, 0, 64, 16, 1, inflight=1)
 c = cell.ctx
 d_w = c.empty((cell.K, cell.Lsym, cell.A))
-c.check(c.lib.isac_synth_qpsk_grid_dev(c.handle, C.c_void_p(d_w.ptr), cell.K, cell.Lsym, cell.A, C.c_uint64(77), 0))    # any unit-scale field
+c.check(c.lib.isac_synth_qpsk_grid_dev(c.handle, d_w, cell.K, cell.Lsym, cell.A, 77, 0))    # any unit-scale field
 c.check(c.lib.isac_profile_enable(c.handle, 1))
 for name, kw in (("Philox generator (NZ=1)", dict(seed=5, noise_domain="spectral")), ("injected field (NZ=2)", dict(spectral_noise=d_w))):
     out = []

@@ -26,9 +26,9 @@ ras = {id(c): c.empty((cell.A, cell.A)) for c in (c1, c2)}
 def mono(c, slot):
     pkg.sensing.monoStaticSensing(cell.tx_waves[slot], (cell.K, cell.Lsym, cell.A), cell.carrier, cell.rp, cell.los, seed=cell.seed, nfft=4096, out=cell.echo[slot], ctx=c)
 def rng(c, slot):
-    c.check(lib.isac_fft2d_range_stage_dev(c.handle, C.byref(ep), C.byref(cf), C.c_void_p(cell.echo[slot].ptr), C.c_void_p(cell.tx_grids[slot].ptr), cell.K, cell.Lsym, cell.A))
+    c.check(lib.isac_fft2d_range_stage_dev(c.handle, C.byref(ep), C.byref(cf), cell.echo[slot], cell.tx_grids[slot], cell.K, cell.Lsym, cell.A))
 def cov(c, slot):
-    c.check(lib.isac_covariance_dev(c.handle, C.c_void_p(cell.echo[slot].ptr), C.c_int64(cell.K * cell.Lsym), C.c_int32(cell.A), C.c_void_p(ras[id(c)].ptr)))
+    c.check(lib.isac_covariance_dev(c.handle, cell.echo[slot], cell.K * cell.Lsym, cell.A, ras[id(c)]))
 
 stages = {"mono": mono, "range": rng, "cov": cov}
 N = 20

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Development probe: isac_covariance_dev at the bench shapes (A = 64: 733 824 samples; --ants 256) -- GPU time (HIP events, kernel + the two
 reducers), max |Ra - G'G/N| against NumPy on a sub-sampled column set, run-to-run bit identity.   python tools/cov_probe.py [--ants 64]"""
-import argparse, ctypes as C, hashlib, importlib, os, sys
+import argparse, hashlib, importlib, os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -13,9 +13,9 @@ ctx = pkg.Context(0)
 K, L, A = 3276, 224, args.ants
 N = K * L
 g = ctx.empty((K, L, A))
-ctx.check(ctx.lib.isac_synth_qpsk_grid_dev(ctx.handle, C.c_void_p(g.ptr), K, L, A, C.c_uint64(5), 0))
+ctx.check(ctx.lib.isac_synth_qpsk_grid_dev(ctx.handle, g, K, L, A, 5, 0))
 ra = ctx.empty((A, A))
-def cov(): ctx.check(ctx.lib.isac_covariance_dev(ctx.handle, C.c_void_p(g.ptr), C.c_int64(N), C.c_int32(A), C.c_void_p(ra.ptr)))
+def cov(): ctx.check(ctx.lib.isac_covariance_dev(ctx.handle, g, N, A, ra))
 for _ in range(3): cov()
 ts, hs = [], set()
 for _ in range(args.reps):

@@ -2,7 +2,6 @@
 in the modes NONE and PHILOX, HIP events around the launch (isac_timer_start / isac_timer_stop_ms), warm, median of 30; then tools/cbench's flat copy of the same number
 of bytes in the same session.  Prints the text kept as profiles/rx_frontend_kernel_times.txt.
     python tools/rxfe_bench.py [out.txt]      (build tools/cbench first: see tools/cbench.hip)"""
-import ctypes as C
 import importlib
 import os
 import subprocess
@@ -26,7 +25,7 @@ def main():
     for name, n_jobs, nr in (("uplink   10 x [61909 x 64]", 10, 64), ("downlink 40 x [61909 x 2] ", 40, 2)):
         per = T * nr
         d_all = ctx.empty((n_jobs * per,))
-        ctx.check(ctx.lib.isac_memset_dev(ctx.handle, C.c_void_p(d_all.ptr), C.c_int(0), C.c_size_t(d_all.nbytes)))
+        ctx.check(ctx.lib.isac_memset_dev(ctx.handle, d_all, 0, d_all.nbytes))
         jobs = (L.RxFrontendJob * n_jobs)()
         for j in range(n_jobs):
             jobs[j] = L.RxFrontendJob(d_all.ptr + 16 * per * j, None, 1e-6, 2.0, NT, 1000 + j)
@@ -36,7 +35,7 @@ def main():
             ms = []
             for r in range(WARM + REPS):
                 ctx.timer_start()
-                ctx.check(ctx.lib.isac_rx_frontend_batch_dev(ctx.handle, jobs, C.c_int32(n_jobs), C.c_int64(T), C.c_int32(nr), C.c_int32(mode)))
+                ctx.check(ctx.lib.isac_rx_frontend_batch_dev(ctx.handle, jobs, n_jobs, T, nr, mode))
                 t = ctx.timer_stop_ms()
                 if r >= WARM:
                     ms.append(t)

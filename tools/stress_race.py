@@ -77,9 +77,8 @@ def _worker(rank, args):
         """One isac_precoded_sinr_cqi_dev call; host_h: upload the channel estimate through a fresh DeviceArray (alloc + pageable copy + free, as the fuzz did)."""
         d_h = ctx.to_device(h) if host_h else d_h_keep
         mean, cqi = C.c_double(0), C.c_int32(0)
-        ctx.check(ctx.lib.isac_precoded_sinr_cqi_dev(ctx.handle, C.c_void_p(d_h.ptr), C.c_int64(n_re), C.c_int32(nr), C.c_int32(p), w.ctypes.data_as(C.c_void_p),
-                                                     C.c_int32(nl), C.c_double(sigma), table.ctypes.data_as(C.c_void_p), C.c_int32(table.size),
-                                                     C.c_void_p(per.ptr if per is not None else 0), C.byref(mean), C.byref(cqi)))
+        ctx.check(ctx.lib.isac_precoded_sinr_cqi_dev(ctx.handle, d_h, n_re, nr, p, w.ctypes.data_as(C.c_void_p),
+                                                     nl, sigma, table.ctypes.data_as(C.c_void_p), table.size, per, C.byref(mean), C.byref(cqi)))
         return mean.value, cqi.value
 
     crng = np.random.default_rng(77 + rank)
