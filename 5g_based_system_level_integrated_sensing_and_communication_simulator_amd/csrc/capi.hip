@@ -1,4 +1,4 @@
-// C ABI of libisac_hip.so: context, tables, host glue of the fft2D pipeline (gfx950 only).
+// C ABI of libisac_hip.so: context, device memory, host glue of the fft2D pipeline (gfx950 only).
 // Declarations and the reference functions each entry point replaces: include/isac.h.
 #include <algorithm>
 #include <chrono>
@@ -10,146 +10,6 @@
 #include "isac_internal.hpp"
 
 using namespace isac;
-
-namespace {
-
-// ---- host math mirrors of the MATLAB helpers the reference calls (product code, not the oracle)
-double bessel_i0(double x) {  // power series, converges to < 1 ulp for |x| <= 10
-  double q = 0.25 * x * x, term = 1.0, sum = 1.0;
-  for (int k = 1; k < 200; ++k) {
-    term *= q / ((double)k * (double)k);
-    sum += term;
-    if (term < 1e-18 * sum) break;
-  }
-  return sum;
-}
-
-std::vector<double> kaiser_window(int n, double beta) {  // Signal Processing Toolbox kaiser(n, beta); fft2D.m:135
-  std::vector<double> w((size_t)n, 1.0);
-  if (n == 1) return w;
-  const int odd = n % 2;
-  const double xind = (double)(n - 1) * (double)(n - 1);
-  const int half = (n + 1) / 2;
-  const double den = bessel_i0(std::fabs(beta));
-  std::vector<double> h((size_t)half);
-  for (int i = 0; i < half; ++i) {
-    double xi = (double)i + 0.5 * (1 - odd);
-    xi = 4.0 * xi * xi;
-    h[(size_t)i] = std::fabs(bessel_i0(std::fabs(beta) * std::sqrt(1.0 - xi / xind)) / den);
-  }
-  // w = [h(half:-1:odd+1) h]
-  int o = 0;
-  for (int i = half - 1; i >= odd; --i) w[(size_t)o++] = h[(size_t)i];
-  for (int i = 0; i < half; ++i) w[(size_t)o++] = h[(size_t)i];
-  return w;
-}
-
-}  // namespace
-
-// ------------------------------------------------------------------ tables shared with the other TUs
-int isac_get_twiddles(isac_ctx* ctx, int n, const c64** out) {
-  isac_ctx& t = *ctx;
-  auto it = t.twiddles.find(n);
-  if (it == t.twiddles.end()) {
-    std::vector<c64> w((size_t)n);
-    for (int m = 0; m < n; ++m) {
-      // exact octant reduction in long double, rounded once
-      long double ang = -2.0L * 3.14159265358979323846264338327950288L * (long double)m / (long double)n;
-      w[(size_t)m] = mk((double)cosl(ang), (double)sinl(ang));
-    }
-    // exact values on the axes
-    w[0] = mk(1.0, 0.0);
-    if (n % 4 == 0) { w[(size_t)n / 4] = mk(0.0, -1.0); w[(size_t)n / 2] = mk(-1.0, 0.0); w[(size_t)3 * n / 4] = mk(0.0, 1.0); }
-    DevBuf b;
-    ISAC_TRY(upload(ctx, b, w.data(), sizeof(c64) * w.size()));
-    it = t.twiddles.emplace(n, b).first;
-  }
-  *out = (const c64*)it->second.p;
-  return ISAC_OK;
-}
-
-// {W512^0..511, W4096^0..7}: the LDS tables of Fft4096W in one contiguous run (bit-identical to entries 8 i / i of the 4096 table)
-int isac_get_w512_pack(isac_ctx* ctx, const c64** out) {
-  isac_ctx& t = *ctx;
-  const int key = -4096;                                 // lives in the same map under a key no FFT length uses
-  auto it = t.twiddles.find(key);
-  if (it == t.twiddles.end()) {
-    std::vector<c64> w(520);
-    const long double two_pi = 2.0L * 3.14159265358979323846264338327950288L;
-    for (int m = 0; m < 512; ++m) { const long double a = -two_pi * (long double)(8 * m) / 4096.0L; w[(size_t)m] = mk((double)cosl(a), (double)sinl(a)); }
-    for (int m = 0; m < 8; ++m) { const long double a = -two_pi * (long double)m / 4096.0L; w[(size_t)512 + m] = mk((double)cosl(a), (double)sinl(a)); }
-    w[0] = mk(1.0, 0.0); w[128] = mk(0.0, -1.0); w[256] = mk(-1.0, 0.0); w[384] = mk(0.0, 1.0); w[512] = mk(1.0, 0.0);
-    DevBuf b;
-    ISAC_TRY(upload(ctx, b, w.data(), sizeof(c64) * w.size()));
-    it = t.twiddles.emplace(key, b).first;
-  }
-  *out = (const c64*)it->second.p;
-  return ISAC_OK;
-}
-
-// (1 / c_i, ln c_i) for the kLogTabSize mantissa buckets of the table-driven Box-Muller radius (echo_dev.hpp); c_i is
-// the bucket centre in [0.5, 1); ln is taken of the reciprocal actually stored so that ln m = ln c_i + log1p(m / c_i - 1)
-// holds to rounding.  Kept in the twiddle map under a negative key (freed with the context).
-int isac_get_logtab(isac_ctx* ctx, const c64** out) {
-  isac_ctx& t = *ctx;
-  const int key = -128;
-  auto it = t.twiddles.find(key);
-  if (it == t.twiddles.end()) {
-    std::vector<c64> lt(128);
-    for (int i = 0; i < 128; ++i) {
-      const long double c = 0.5L * (1.0L + ((long double)i + 0.5L) / 128.0L);
-      const double inv = (double)(1.0L / c);
-      lt[(size_t)i] = mk(inv, (double)(-logl((long double)inv)));
-    }
-    DevBuf b;
-    ISAC_TRY(upload(ctx, b, lt.data(), sizeof(c64) * lt.size()));
-    it = t.twiddles.emplace(key, b).first;
-  }
-  *out = (const c64*)it->second.p;
-  return ISAC_OK;
-}
-
-// rising raised-cosine edge of the OFDM symbol window (toolbox form, oracle/ofdm.py raised_cosine_edge); kept in the Kaiser map
-// under the key (n, 2)
-int isac_get_rise_window(isac_ctx* ctx, int n_win, const double** out) {
-  isac_ctx& t = *ctx;
-  auto key = std::make_pair(n_win, 2);
-  auto it = t.kaiser3.find(key);
-  if (it == t.kaiser3.end()) {
-    std::vector<double> w((size_t)n_win);
-    for (int i = 1; i <= n_win; ++i) w[(size_t)i - 1] = 0.5 * (1.0 - std::sin(M_PI * (n_win + 1 - 2.0 * i) / (2.0 * n_win)));
-    DevBuf b;
-    ISAC_TRY(upload(ctx, b, w.data(), sizeof(double) * w.size()));
-    it = t.kaiser3.emplace(key, b).first;
-  }
-  *out = (const double*)it->second.p;
-  return ISAC_OK;
-}
-
-int isac_get_windows(isac_ctx* ctx, int K, int n_ifft, const double** win_k, const double** win_r) {
-  isac_ctx& t = *ctx;
-  auto get = [&](int n, int shifted, const double** out) -> int {
-    auto key = std::make_pair(n, shifted);
-    auto it = t.kaiser3.find(key);
-    if (it == t.kaiser3.end()) {
-      std::vector<double> w = kaiser_window(n, 3.0);            // fft2D.m:135 'kaiser', beta = 3
-      if (shifted) {                                            // fftshift: out[i] = in[(i + ceil(n/2)) mod n]
-        std::vector<double> s((size_t)n);
-        const int sh = (n + 1) / 2;
-        for (int i = 0; i < n; ++i) s[(size_t)i] = w[(size_t)((i + sh) % n)];
-        w.swap(s);
-      }
-      DevBuf b;
-      ISAC_TRY(upload(ctx, b, w.data(), sizeof(double) * w.size()));
-      it = t.kaiser3.emplace(key, b).first;
-    }
-    *out = (const double*)it->second.p;
-    return ISAC_OK;
-  };
-  ISAC_TRY(get(K, 0, win_k));
-  ISAC_TRY(get(n_ifft, 1, win_r));
-  return ISAC_OK;
-}
 
 // ------------------------------------------------------------------ context
 extern "C" int isac_abi_version(void) { return ISAC_ABI_VERSION; }
@@ -218,29 +78,13 @@ extern "C" int isac_ctx_destroy(isac_ctx* ctx) {
   if (borrowed) (void)hipEventSynchronize(ctx->ev_done);
   (void)hipStreamSynchronize(ctx->stream);
   (void)hipStreamSynchronize(ctx->stream2);
-  for (auto& kv : ctx->twiddles) (void)hipFree(kv.second.p);
-  for (auto& kv : ctx->kaiser3) (void)hipFree(kv.second.p);
-  for (auto& kv : ctx->sind) (void)hipFree(kv.second.p);
-  for (auto& kv : ctx->doa2d_tab) (void)hipFree(kv.second.p);
-  DevBuf* bufs[] = {&ctx->doa2d_p, &ctx->doa2d_db, &ctx->doa2d_cand, &ctx->doa2d_w, &ctx->doa2d_user,
-                    &ctx->beam, &ctx->coef, &ctx->phase_rx, &ctx->steer, &ctx->dgrid,
-                    &ctx->ymid, &ctx->pwin, &ctx->flags, &ctx->det_cut, &ctx->det_pow, &ctx->det_cnt, &ctx->cov_part,
-                    &ctx->cov, &ctx->eig_w, &ctx->eig_v, &ctx->eig_scratch, &ctx->spec, &ctx->misc, &ctx->stage_a, &ctx->stage_b, &ctx->seg,
-                    &ctx->stage_c, &ctx->sind_tab, &ctx->cdl_h, &ctx->rxfe_tab, &ctx->echo_own, &ctx->os_x};
-  for (DevBuf* b : bufs)
-    if (b->p) (void)hipFree(b->p);
-  if (ctx->pinned) (void)hipHostFree(ctx->pinned);
-  if (ctx->pinned_csi) (void)hipHostFree(ctx->pinned_csi);
-  if (ctx->bounce) (void)hipHostFree(ctx->bounce);
   for (auto& e : ctx->ev_bounce) if (e) (void)hipEventDestroy(e);
   (void)hipEventDestroy(ctx->ev_fork);
   (void)hipEventDestroy(ctx->ev_join);
   (void)hipEventDestroy(ctx->ev_cfar);
   (void)hipEventDestroy(ctx->ev_done);
-  for (auto& sl : ctx->stage_ring) {
+  for (auto& sl : ctx->stage_ring)
     if (sl.ev) (void)hipEventDestroy(sl.ev);
-    if (sl.p) (void)hipHostFree(sl.p);
-  }
   (void)hipEventDestroy(ctx->ev_t0);
   (void)hipEventDestroy(ctx->ev_t1);
   (void)hipEventDestroy(ctx->ev_k0);
@@ -249,7 +93,7 @@ extern "C" int isac_ctx_destroy(isac_ctx* ctx) {
     if (e) (void)hipEventDestroy(e);
   (void)hipStreamDestroy(ctx->stream);
   (void)hipStreamDestroy(ctx->stream2);
-  delete ctx;
+  delete ctx;                                         // every buffer and cached table goes with its owner (DevBuf / PinnedBuf); the context's device is current
   return ISAC_OK;
 }
 
@@ -561,7 +405,7 @@ static int fft2d_submit(isac_ctx* ctx, const isac_est_params* ep, const isac_cfa
                      pack_first, d_pcut_first, d_ppow_first, pl.upa2d ? (const double*)ctx->doa2d_cand.p : (const double*)ctx->spec.p, n_spec,
                      (double*)(dbase + off_spec), pl.refused() ? nullptr : eig_info(ctx, A));
   ISAC_HIP(hipGetLastError());
-  char* h = (char*)ctx->pinned;
+  char* h = (char*)ctx->pinned.p;
   ISAC_HIP(hipMemcpyAsync(h, dbase, first_bytes, hipMemcpyDeviceToHost, ctx->stream));
   timeline_mark(ctx, 6, ctx->stream);
   ISAC_HIP(hipEventRecord(ctx->ev_done, ctx->stream));
@@ -600,7 +444,7 @@ extern "C" int isac_fft2d_collect(isac_ctx* ctx, isac_est_result* out) {
   int* d_pcut_full = pd.d_pcut_full;
   double* d_ppow_full = pd.d_ppow_full;
   const int n_cut_rows = cfar->row1 - cfar->row0 + 1;
-  char* h = (char*)ctx->pinned;
+  char* h = (char*)ctx->pinned.p;
   ISAC_HIP(hipEventSynchronize(ctx->ev_done));      // (not the stream: contexts that share streams have later CPIs queued behind this one)
   ctx->tail_unjoined = false;                       // the narrow chain of this CPI has finished: nothing left for the main stream to wait for
   if (ctx->tl_on) {
@@ -734,16 +578,14 @@ extern "C" int isac_fft2d(isac_ctx* ctx, const isac_est_params* ep, const isac_c
   ISAC_ENTER(ctx);
   if (!rx_grid || !tx_grid) return fail(ctx, ISAC_ERR_INVALID_ARG, "NULL grid");
   const size_t bytes = sizeof(c64) * (size_t)K * L * A;
-  void *d_rx = nullptr, *d_tx = nullptr;
-  ISAC_HIP(hipMalloc(&d_rx, bytes));
-  if (hipMalloc(&d_tx, bytes) != hipSuccess) { (void)hipFree(d_rx); return fail(ctx, ISAC_ERR_HIP, "hipMalloc failed"); }
+  DevBuf d_rx, d_tx;
+  ISAC_TRY(ensure(ctx, d_rx, bytes));
+  ISAC_TRY(ensure(ctx, d_tx, bytes));
   int st = ISAC_OK;
-  if (copy_h2d(ctx, d_rx, rx_grid, bytes) != ISAC_OK || copy_h2d(ctx, d_tx, tx_grid, bytes) != ISAC_OK)      // (on the context's stream and waited for: see copy_h2d)
+  if (copy_h2d(ctx, d_rx.p, rx_grid, bytes) != ISAC_OK || copy_h2d(ctx, d_tx.p, tx_grid, bytes) != ISAC_OK)      // (on the context's stream and waited for: see copy_h2d)
     st = fail(ctx, ISAC_ERR_HIP, "host->device copy failed");
-  if (st == ISAC_OK) st = isac_fft2d_dev(ctx, ep, cfar, (const isac_c64*)d_rx, (const isac_c64*)d_tx, K, L, A, out);
-  (void)hipStreamSynchronize(ctx->stream);
-  (void)hipFree(d_rx);
-  (void)hipFree(d_tx);
+  if (st == ISAC_OK) st = isac_fft2d_dev(ctx, ep, cfar, (const isac_c64*)d_rx.p, (const isac_c64*)d_tx.p, K, L, A, out);
+  (void)hipStreamSynchronize(ctx->stream);            // before the grids go
   return st;
 }
 
@@ -808,12 +650,10 @@ extern "C" int isac_ctx_reserve(isac_ctx* ctx, int64_t T, int32_t tx_dim_l, cons
   const int K = carrier->n_sc, A = rp->n_ants, L = std::max<int>(l_whole, tx_dim_l);
   if (L <= 0) return fail(ctx, ISAC_ERR_SHORT_WAVEFORM, "isac_ctx_reserve: waveform shorter than one OFDM symbol");
   const size_t g_bytes = sizeof(c64) * (size_t)K * L * A, w_bytes = sizeof(c64) * (size_t)T * A;
-  void *d_grid = nullptr, *d_wave = nullptr, *d_echo = nullptr;
-  auto release = [&]() { if (d_grid) (void)hipFree(d_grid); if (d_wave) (void)hipFree(d_wave); if (d_echo) (void)hipFree(d_echo); };
-  if (hipMalloc(&d_grid, g_bytes) != hipSuccess || hipMalloc(&d_wave, w_bytes) != hipSuccess || hipMalloc(&d_echo, g_bytes) != hipSuccess) {
-    release();
+  DevBuf grid, wave, echo;
+  if (ensure(ctx, grid, g_bytes) != ISAC_OK || ensure(ctx, wave, w_bytes) != ISAC_OK || ensure(ctx, echo, g_bytes) != ISAC_OK)
     return fail(ctx, ISAC_ERR_HIP, "isac_ctx_reserve: no device memory for the dry run's grids (T A + 2 K L A elements)");
-  }
+  void *d_grid = grid.p, *d_wave = wave.p, *d_echo = echo.p;
   std::vector<uint8_t> los((size_t)rp->n_targets, 1);
   int st = isac_synth_qpsk_grid_dev(ctx, (isac_c64*)d_grid, K, L, A, 0x5EEDull, 0);
   if (st == ISAC_OK) st = isac_memset_dev(ctx, d_wave, 0, w_bytes);                     // (rows past the whole symbols stay zero)
@@ -840,7 +680,7 @@ extern "C" int isac_ctx_reserve(isac_ctx* ctx, int64_t T, int32_t tx_dim_l, cons
   ctx->last.valid = false;                                                                 // isac_fft2d_get_* must not hand out the dry run's detections / window / Ra
   ctx->last.pow_on_device = false;
   ctx->profile_recorded = false;                                                           // nor isac_profile_last_kernel_ms the dry run's kernel
-  release();
+  (void)grid.reset(); (void)wave.reset(); (void)echo.reset();
   if (elapsed_ms) *elapsed_ms = ms_since();
   if (st != ISAC_OK) { ctx->err = keep; return st; }
   return ISAC_OK;
@@ -886,20 +726,17 @@ extern "C" int isac_basic_radar_channel(isac_ctx* ctx, const isac_c64* tx_wave, 
   ISAC_ENTER(ctx);
   if (!tx_wave || !rp || !rx_wave || T <= 0) return fail(ctx, ISAC_ERR_INVALID_ARG, "bad arguments");
   const size_t bytes = sizeof(c64) * (size_t)T * rp->n_ants;
-  void *d_tx = nullptr, *d_nz = nullptr, *d_rx = nullptr;
-  int st = ISAC_OK;
-  if (hipMalloc(&d_tx, bytes) != hipSuccess || hipMalloc(&d_rx, bytes) != hipSuccess) st = fail(ctx, ISAC_ERR_HIP, "hipMalloc failed");
-  if (st == ISAC_OK && noise_mode == ISAC_NOISE_INJECTED && noise_unit) {
-    if (hipMalloc(&d_nz, bytes) != hipSuccess || copy_h2d(ctx, d_nz, noise_unit, bytes) != ISAC_OK)
-      st = fail(ctx, ISAC_ERR_HIP, "noise upload failed");
+  DevBuf d_tx, d_nz, d_rx;                            // (freed on every exit; hipFree waits for the device)
+  ISAC_TRY(ensure(ctx, d_tx, bytes));
+  ISAC_TRY(ensure(ctx, d_rx, bytes));
+  if (noise_mode == ISAC_NOISE_INJECTED && noise_unit) {
+    if (ensure(ctx, d_nz, bytes) != ISAC_OK || copy_h2d(ctx, d_nz.p, noise_unit, bytes) != ISAC_OK)
+      return fail(ctx, ISAC_ERR_HIP, "noise upload failed");
   }
-  if (st == ISAC_OK && copy_h2d(ctx, d_tx, tx_wave, bytes) != ISAC_OK) st = fail(ctx, ISAC_ERR_HIP, "upload failed");
-  if (st == ISAC_OK)
-    st = isac_basic_radar_channel_dev(ctx, (const isac_c64*)d_tx, T, rp, los, noise_mode, (const isac_c64*)d_nz, seed, (isac_c64*)d_rx);
-  if (st == ISAC_OK && copy_d2h(ctx, rx_wave, d_rx, bytes) != ISAC_OK)
-    st = fail(ctx, ISAC_ERR_HIP, "download failed");
-  (void)hipFree(d_tx); (void)hipFree(d_nz); (void)hipFree(d_rx);
-  return st;
+  if (copy_h2d(ctx, d_tx.p, tx_wave, bytes) != ISAC_OK) return fail(ctx, ISAC_ERR_HIP, "upload failed");
+  ISAC_TRY(isac_basic_radar_channel_dev(ctx, (const isac_c64*)d_tx.p, T, rp, los, noise_mode, (const isac_c64*)d_nz.p, seed, (isac_c64*)d_rx.p));
+  if (copy_d2h(ctx, rx_wave, d_rx.p, bytes) != ISAC_OK) return fail(ctx, ISAC_ERR_HIP, "download failed");
+  return ISAC_OK;
 }
 
 extern "C" int isac_mono_static_sensing(isac_ctx* ctx, const isac_c64* tx_wave, int64_t T, int32_t tx_dim_l,
@@ -913,20 +750,17 @@ extern "C" int isac_mono_static_sensing(isac_ctx* ctx, const isac_c64* tx_wave, 
   const int L_out = lw < tx_dim_l ? tx_dim_l : lw;
   const size_t wbytes = sizeof(c64) * (size_t)T * rp->n_ants;
   const size_t gbytes = sizeof(c64) * (size_t)carrier->n_sc * (size_t)(L_out > 0 ? L_out : 1) * rp->n_ants;
-  void *d_tx = nullptr, *d_nz = nullptr, *d_g = nullptr;
-  int st = ISAC_OK;
-  if (hipMalloc(&d_tx, wbytes) != hipSuccess || hipMalloc(&d_g, gbytes) != hipSuccess) st = fail(ctx, ISAC_ERR_HIP, "hipMalloc failed");
-  if (st == ISAC_OK && (noise_mode == ISAC_NOISE_INJECTED || noise_mode == ISAC_NOISE_INJECTED_SPECTRAL) && noise_unit) {
+  DevBuf d_tx, d_nz, d_g;                             // (freed on every exit; hipFree waits for the device)
+  ISAC_TRY(ensure(ctx, d_tx, wbytes));
+  ISAC_TRY(ensure(ctx, d_g, gbytes));
+  if ((noise_mode == ISAC_NOISE_INJECTED || noise_mode == ISAC_NOISE_INJECTED_SPECTRAL) && noise_unit) {
     const size_t nbytes = noise_mode == ISAC_NOISE_INJECTED ? wbytes : gbytes;   // [T x A] samples or [n_sc x L_out x A] grid elements
-    if (hipMalloc(&d_nz, nbytes) != hipSuccess || copy_h2d(ctx, d_nz, noise_unit, nbytes) != ISAC_OK)
-      st = fail(ctx, ISAC_ERR_HIP, "noise upload failed");
+    if (ensure(ctx, d_nz, nbytes) != ISAC_OK || copy_h2d(ctx, d_nz.p, noise_unit, nbytes) != ISAC_OK)
+      return fail(ctx, ISAC_ERR_HIP, "noise upload failed");
   }
-  if (st == ISAC_OK && copy_h2d(ctx, d_tx, tx_wave, wbytes) != ISAC_OK) st = fail(ctx, ISAC_ERR_HIP, "upload failed");
-  if (st == ISAC_OK)
-    st = isac_mono_static_sensing_dev(ctx, (const isac_c64*)d_tx, T, tx_dim_l, carrier, rp, los, noise_mode,
-                                      (const isac_c64*)d_nz, seed, (isac_c64*)d_g, l_out);
-  if (st == ISAC_OK && copy_d2h(ctx, echo_grid, d_g, gbytes) != ISAC_OK)
-    st = fail(ctx, ISAC_ERR_HIP, "download failed");
-  (void)hipFree(d_tx); (void)hipFree(d_nz); (void)hipFree(d_g);
-  return st;
+  if (copy_h2d(ctx, d_tx.p, tx_wave, wbytes) != ISAC_OK) return fail(ctx, ISAC_ERR_HIP, "upload failed");
+  ISAC_TRY(isac_mono_static_sensing_dev(ctx, (const isac_c64*)d_tx.p, T, tx_dim_l, carrier, rp, los, noise_mode,
+                                        (const isac_c64*)d_nz.p, seed, (isac_c64*)d_g.p, l_out));
+  if (copy_d2h(ctx, echo_grid, d_g.p, gbytes) != ISAC_OK) return fail(ctx, ISAC_ERR_HIP, "download failed");
+  return ISAC_OK;
 }

@@ -1077,11 +1077,11 @@ extern "C" int isac_cdl_path_gains_dev(isac_ctx* ctx, const isac_c64* d_base, co
   ISAC_ENTER(ctx);
   if (!d_base || !d_rate || !t_snap || !d_H) return fail(ctx, ISAC_ERR_INVALID_ARG, "NULL argument");
   if (n_paths <= 0 || n_rays <= 0 || Nt <= 0 || Nr <= 0 || n_snap <= 0 || n_snap > 65535) return fail(ctx, ISAC_ERR_INVALID_ARG, "bad dimensions");
-  ISAC_TRY(ensure(ctx, ctx->sind_tab, sizeof(double) * (size_t)n_snap));     // (scratch of this entry point only; stream order protects reuse)
-  ISAC_TRY(stage_upload(ctx, ctx->sind_tab.p, t_snap, sizeof(double) * (size_t)n_snap));
+  ISAC_TRY(ensure(ctx, ctx->cdl_par, sizeof(double) * (size_t)n_snap));     // (scratch of this entry point only; stream order protects reuse)
+  ISAC_TRY(stage_upload(ctx, ctx->cdl_par.p, t_snap, sizeof(double) * (size_t)n_snap));
   const int nsu = Nt * Nr;
   hipLaunchKernelGGL(cdl_path_gains_kernel, dim3((unsigned)cdiv((long long)n_paths * nsu, 256), (unsigned)n_snap), dim3(256), 0, ctx->stream, (const c64*)d_base,
-                     d_rate, n_paths, n_rays, nsu, (const c64*)d_los, los_rate, (const double*)ctx->sind_tab.p, (c64*)d_H);
+                     d_rate, n_paths, n_rays, nsu, (const c64*)d_los, los_rate, (const double*)ctx->cdl_par.p, (c64*)d_H);
   ISAC_HIP(hipGetLastError());
   return ISAC_OK;
 }
@@ -1114,9 +1114,9 @@ extern "C" int isac_cdl_csi_estimate_batch_dev(isac_ctx* ctx, int32_t n_ue, cons
     tab[j] = CdlCsiUe{(const c64*)d_base[j], d_rate[j], d_los ? (const c64*)d_los[j] : nullptr, los_rate ? los_rate[j] : 0.0, t[j], (c64*)d_Hf[j]};
     ctx->range_cache.touch(d_Hf[j], sizeof(c64) * (size_t)n_re * Nr * ports);
   }
-  ISAC_TRY(ensure(ctx, ctx->sind_tab, sizeof(CdlCsiUe) * tab.size()));     // (scratch of the CDL parameter entry points; stream order protects reuse)
-  ISAC_TRY(stage_upload(ctx, ctx->sind_tab.p, tab.data(), sizeof(CdlCsiUe) * tab.size()));
-  hipLaunchKernelGGL(cdl_csi_estimate_kernel, dim3(cdiv(n_re, 32), (unsigned)n_ue), dim3(256), lds, ctx->stream, (const CdlCsiUe*)ctx->sind_tab.p, n_paths, n_rays, Nt, Nr, ports,
+  ISAC_TRY(ensure(ctx, ctx->cdl_par, sizeof(CdlCsiUe) * tab.size()));     // (scratch of the CDL parameter entry points; stream order protects reuse)
+  ISAC_TRY(stage_upload(ctx, ctx->cdl_par.p, tab.data(), sizeof(CdlCsiUe) * tab.size()));
+  hipLaunchKernelGGL(cdl_csi_estimate_kernel, dim3(cdiv(n_re, 32), (unsigned)n_ue), dim3(256), lds, ctx->stream, (const CdlCsiUe*)ctx->cdl_par.p, n_paths, n_rays, Nt, Nr, ports,
                      d_tau, d_freq, (long long)n_re);
   ISAC_HIP(hipGetLastError());
   return ISAC_OK;

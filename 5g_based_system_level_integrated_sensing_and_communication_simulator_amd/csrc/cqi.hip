@@ -308,10 +308,10 @@ extern "C" int isac_precoded_sinr_cqi_dev(isac_ctx* ctx, const isac_c64* d_H, in
     ISAC_HIP(hipGetLastError());
     // (through pinned memory: an asynchronous copy into a pageable stack variable goes through the runtime's own staging -- one mean of ~1 900 fuzz cases under 16
     //  concurrent processes came back wrong once, unreproduced, profiles/r05_fuzz_campaigns.txt; pinned memory takes the runtime's staging out of the picture)
-    ISAC_TRY(ensure_pinned_buf(ctx, ctx->pinned_csi, ctx->pinned_csi_cap, 64));
-    ISAC_HIP(hipMemcpyAsync(ctx->pinned_csi, d_mean, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    ISAC_TRY(ensure_pinned_buf(ctx, ctx->pinned_csi, 64));
+    ISAC_HIP(hipMemcpyAsync(ctx->pinned_csi.p, d_mean, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     ISAC_HIP(hipStreamSynchronize(ctx->stream));
-    const double m = *(const double*)ctx->pinned_csi;
+    const double m = *(const double*)ctx->pinned_csi.p;
     static const bool dbg_mean = std::getenv("ISAC_DEBUG_MEAN") != nullptr;     // diagnostic: re-read the per-RE values, recompute the mean on the host, report a disagreement
     if (dbg_mean) {
       std::vector<double> hv((size_t)n_re);
@@ -697,10 +697,10 @@ static int csi_report_batch(isac_ctx* ctx, int n_ue, const isac_c64* const* d_H_
   ISAC_HIP(hipGetLastError());
   // ---- ONE copy back, ONE synchronisation for the whole batch
   const size_t res_bytes = sizeof(double) * res_stride * (size_t)n_ue;
-  ISAC_TRY(ensure_pinned_buf(ctx, ctx->pinned_csi, ctx->pinned_csi_cap, res_bytes));   // (its own buffer: ctx->pinned may hold a submitted CPI that has not been collected)
-  ISAC_HIP(hipMemcpyAsync(ctx->pinned_csi, d_res, res_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  ISAC_TRY(ensure_pinned_buf(ctx, ctx->pinned_csi, res_bytes));   // (its own buffer: ctx->pinned may hold a submitted CPI that has not been collected)
+  ISAC_HIP(hipMemcpyAsync(ctx->pinned_csi.p, d_res, res_bytes, hipMemcpyDeviceToHost, ctx->stream));
   ISAC_HIP(hipStreamSynchronize(ctx->stream));
-  const double* res = (const double*)ctx->pinned_csi;
+  const double* res = (const double*)ctx->pinned_csi.p;
   for (int u = 0; u < n_ue; ++u) {
     const double* r = res + res_stride * (size_t)u;
     if (total_sinr_out) std::memcpy(total_sinr_out + (size_t)u * nE, r, sizeof(double) * (size_t)nE);
@@ -831,10 +831,10 @@ extern "C" int isac_srs_pmi_select_batch_dev(isac_ctx* ctx, int32_t n_ue, const 
                      (long long)n_re, NL, nE, (const int*)(dm + o_ptr), (const int*)(dm + o_idx), n_sb, d_res);
   ISAC_HIP(hipGetLastError());
   const size_t res_bytes = sizeof(double) * res_stride * (size_t)n_ue;
-  ISAC_TRY(ensure_pinned_buf(ctx, ctx->pinned_csi, ctx->pinned_csi_cap, res_bytes));
-  ISAC_HIP(hipMemcpyAsync(ctx->pinned_csi, d_res, res_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  ISAC_TRY(ensure_pinned_buf(ctx, ctx->pinned_csi, res_bytes));
+  ISAC_HIP(hipMemcpyAsync(ctx->pinned_csi.p, d_res, res_bytes, hipMemcpyDeviceToHost, ctx->stream));
   ISAC_HIP(hipStreamSynchronize(ctx->stream));
-  const double* res = (const double*)ctx->pinned_csi;
+  const double* res = (const double*)ctx->pinned_csi.p;
   // ---- host half per UE: sinrPerSubband.m:33, pmiSelect.m:54-58, gNBPhy.m:1035-1058
   for (int u = 0; u < n_ue; ++u) {
     isac_srs_report& o = out[u];

@@ -87,22 +87,13 @@ int scan_steps(const isac_est_params* ep) {
 }
 
 int get_sind_table(isac_ctx* ctx, const isac_est_params* ep, const double** out, int* n_steps) {
-  isac_ctx& t = *ctx;
-  auto key = std::make_pair((long long)std::llround(ep->azimuth_scan_scale * 1e6),
-                            (long long)std::llround(ep->azimuth_scan_granularity * 1e6));
   const int n = scan_steps(ep);
   if (n <= 0) return fail(ctx, ISAC_ERR_INVALID_ARG, "empty azimuth scan");
-  auto it = t.sind.find(key);
-  if (it == t.sind.end()) {
-    std::vector<double> s((size_t)n);
-    for (int a = 0; a < n; ++a) s[(size_t)a] = sind_deg(a * ep->azimuth_scan_granularity - ep->azimuth_scan_scale / 2.0);   // music.m:88
-    DevBuf b;
-    ISAC_TRY(upload(ctx, b, s.data(), sizeof(double) * s.size()));
-    it = t.sind.emplace(key, b).first;
-  }
-  *out = (const double*)it->second.p;
   *n_steps = n;
-  return ISAC_OK;
+  return cached_table(ctx, {kSind, {std::llround(ep->azimuth_scan_scale * 1e6), std::llround(ep->azimuth_scan_granularity * 1e6)}}, out, [&](std::vector<double>& s) {
+    s.resize((size_t)n);
+    for (int a = 0; a < n; ++a) s[(size_t)a] = sind_deg(a * ep->azimuth_scan_granularity - ep->azimuth_scan_scale / 2.0);   // music.m:88
+  });
 }
 
 // UPA scan grid (music.m:36-53): eSteps x aSteps points, row e at elevation (e-1) eGran - eMax/2, column a at azimuth (a-1) aGran - aMax/2.
@@ -113,24 +104,17 @@ int get_doa2d_tables(isac_ctx* ctx, const isac_est_params* ep, const double** ou
   const double ne = std::floor((em + 1.0) / eg), na = std::floor((am + 1.0) / ag);                     // music.m:42-43
   if (!(ne >= 1.0) || !(na >= 1.0) || ne * na > (double)(1 << 26)) return fail(ctx, ISAC_ERR_INVALID_ARG, "UPA DoA: empty or oversized scan grid");
   const int n_e = (int)ne, n_a = (int)na;
-  const std::vector<long long> key = {std::llround(am * 1e6), std::llround(ag * 1e6), std::llround(em * 1e6), std::llround(eg * 1e6)};
-  auto it = ctx->doa2d_tab.find(key);
-  if (it == ctx->doa2d_tab.end()) {
-    std::vector<double> t((size_t)n_e + 2 * (size_t)n_a);
+  *e_steps = n_e;
+  *a_steps = n_a;
+  return cached_table(ctx, {kDoa2d, {std::llround(am * 1e6), std::llround(ag * 1e6), std::llround(em * 1e6), std::llround(eg * 1e6)}}, out, [&](std::vector<double>& t) {
+    t.resize((size_t)n_e + 2 * (size_t)n_a);
     for (int e = 0; e < n_e; ++e) t[(size_t)e] = sind_deg(e * eg - em / 2.0);                         // music.m:47,44
     for (int a = 0; a < n_a; ++a) {
       const double ph = a * ag - am / 2.0;                                                              // music.m:48
       t[(size_t)n_e + a] = cosd_deg(ph);
       t[(size_t)n_e + n_a + a] = sind_deg(ph);
     }
-    DevBuf b;
-    ISAC_TRY(upload(ctx, b, t.data(), sizeof(double) * t.size()));
-    it = ctx->doa2d_tab.emplace(key, b).first;
-  }
-  *out = (const double*)it->second.p;
-  *e_steps = n_e;
-  *a_steps = n_a;
-  return ISAC_OK;
+  });
 }
 
 int check_upa_dims(isac_ctx* ctx, const isac_est_params* ep, int A) {   // radarParams.m:90,99 reshape to nTxAnts

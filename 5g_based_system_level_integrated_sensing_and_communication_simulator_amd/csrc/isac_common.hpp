@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <array>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -10,6 +11,7 @@
 #include <cstring>
 #include <map>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -64,9 +66,35 @@ __device__ __forceinline__ void buffer_store_c64_nt(__amdgpu_buffer_rsrc_t rs, u
 }
 
 // ---------------------------------------------------------------- context
-struct DevBuf {
+// Device memory / pinned host memory with one owner: released when the owner goes (a member with its isac_ctx, a local at the end of its scope, a cached table with
+// the map that holds it).  Movable, not copyable.  Whoever destroys one has the allocation's device current and nothing in flight that still uses the memory.
+template <hipError_t (*Free)(void*)>
+struct OwnedBuf {
   void* p = nullptr;
   size_t cap = 0;
+  OwnedBuf() = default;
+  OwnedBuf(OwnedBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+  OwnedBuf& operator=(OwnedBuf&& o) noexcept { if (this != &o) { (void)reset(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; } return *this; }
+  OwnedBuf(const OwnedBuf&) = delete;
+  OwnedBuf& operator=(const OwnedBuf&) = delete;
+  ~OwnedBuf() { (void)reset(); }
+  hipError_t reset() {
+    const hipError_t e = p ? Free(p) : hipSuccess;
+    p = nullptr;
+    cap = 0;
+    return e;
+  }
+};
+using DevBuf = OwnedBuf<hipFree>;           // sized by ensure()
+using PinnedBuf = OwnedBuf<hipHostFree>;    // sized by ensure_pinned_buf()
+static_assert(!std::is_copy_constructible<DevBuf>::value && std::is_nothrow_move_constructible<DevBuf>::value, "one owner per allocation");
+
+// What a cached device table is and the parameters it was made for (isac_ctx::tables; cached_table, isac_internal.hpp)
+enum TableKind { kTwiddle, kW512Pack, kLogTab, kKaiser3, kKaiser3Shifted, kRiseWindow, kSind, kDoa2d };
+struct TableKey {
+  TableKind kind;
+  std::array<long long, 4> par{};
+  bool operator<(const TableKey& o) const { return kind != o.kind ? kind < o.kind : par < o.par; }
 };
 
 struct Fft2dLast {  // introspection of the last fft2D call (host copies)
@@ -108,8 +136,7 @@ struct LazyEcho {
 // pinned host -> device parameter staging: a small ring of slots, each guarded by its own event, so that a call's uploads do not wait for the
 // previous call's kernels to drain (one slot + one event did: every upload sat in stream order behind whatever was queued before it)
 struct StageSlot {
-  void* p = nullptr;
-  size_t cap = 0;
+  PinnedBuf mem;
   hipEvent_t ev = nullptr;
   bool busy = false;
 };
@@ -159,17 +186,14 @@ struct isac_ctx {
   int wide_order = 0;              // ISAC_OPT_WIDE_ORDER: 1 = fft2D's covariance on the main stream, everything narrow (Doppler, CFAR, MUSIC chain, pack, D2H) on the second
   int tail_fusion = 1;             // ISAC_OPT_TAIL_FUSION: 1 = panel CFAR + per-antenna merge / numDets where applicable (default), 0 = memset + per-antenna CFAR + count
   std::string err;
-  // cached device tables
   std::map<const void*, size_t> lds_allowed;                        // kernel -> dynamic LDS bytes enabled on this context's device
-  std::map<int, isac::DevBuf> twiddles;                             // n -> exp(-2 pi j m / n)
-  std::map<std::pair<int, int>, isac::DevBuf> kaiser3;              // (n, shifted) -> kaiser(n,3) / fftshift(kaiser(n,3))
-  std::map<std::pair<long long, long long>, isac::DevBuf> sind;     // (scale, granularity) -> sind(scan angles)
+  std::map<isac::TableKey, isac::DevBuf> tables;                    // cached device tables: made on first use, kept until the context goes
   // scratch
   isac::DevBuf beam, coef, phase_rx, steer, dgrid, ymid, pwin, flags, det_cut, det_pow, det_cnt, cov_part, cov,
-      eig_w, eig_v, eig_scratch, spec, misc, stage_a, stage_b, stage_c, sind_tab, seg, cdl_h, rxfe_tab;
-  void* pinned = nullptr; size_t pinned_cap = 0;                       // results of isac_fft2d_submit* (read by isac_fft2d_collect) -- no other entry point may touch it
-  void* bounce = nullptr; size_t bounce_cap = 0; hipEvent_t ev_bounce[2] = {nullptr, nullptr};   // pinned bounce buffer of the host-array copies (copy_h2d / copy_d2h)
-  void* pinned_csi = nullptr; size_t pinned_csi_cap = 0;               // results of isac_csi_report*: its own buffer, so a CSI call between submit and collect cannot clobber a pending CPI
+      eig_w, eig_v, eig_scratch, spec, misc, stage_a, stage_b, stage_c, cdl_par, seg, cdl_h, rxfe_tab;
+  isac::PinnedBuf pinned;       // results of isac_fft2d_submit* (read by isac_fft2d_collect) -- no other entry point may touch it
+  isac::PinnedBuf bounce; hipEvent_t ev_bounce[2] = {nullptr, nullptr};   // pinned bounce buffer of the host-array copies (copy_h2d / copy_d2h)
+  isac::PinnedBuf pinned_csi;   // results of isac_csi_report*: its own buffer, so a CSI call between submit and collect cannot clobber a pending CPI
   isac::Fft2dLast last;
   isac::Fft2dPending pending;
   isac::RangeCache range_cache;
@@ -183,7 +207,6 @@ struct isac_ctx {
   isac::DevBuf echo_own;             // ... and its storage when it has to exist in memory (LazyEcho::native == false)
   // ISAC_OPT_UPA_DOA (doa2d.hip): the 2-D (elevation x azimuth) scan of a UPA
   int upa_doa = 0;                   // 0 = UPA DoA returns ISAC_ERR_UNSUPPORTED (default), 1 = 2-D scan + find2DPeaks
-  std::map<std::vector<long long>, isac::DevBuf> doa2d_tab;          // (scales, granularities) -> [sind(ele) | cosd(azi) | sind(azi)]
   isac::DevBuf doa2d_p, doa2d_db, doa2d_cand, doa2d_w, doa2d_user;  // raw spectrum, dB map, peak candidates, eigen weights, a caller's map
   int doa2d_rows = 0, doa2d_cols = 0;   // dims of the dB map in doa2d_db (0: none yet)
   isac::StageSlot stage_ring[isac::kStageSlots];   // pinned->device parameter uploads (stage_acquire / stage_commit)
@@ -248,9 +271,7 @@ inline int ensure(isac_ctx* ctx, DevBuf& b, size_t bytes) {
   if (b.cap >= bytes && b.p) return ISAC_OK;
   if (b.p) {
     ISAC_HIP(hipStreamSynchronize(ctx->stream));
-    ISAC_HIP(hipFree(b.p));
-    b.p = nullptr;
-    b.cap = 0;
+    if (const hipError_t e = b.reset()) return fail(ctx, ISAC_ERR_HIP, std::string("hipFree(b.p): ") + hipGetErrorString(e));
   }
   size_t want = bytes < 256 ? 256 : bytes;
   ISAC_HIP(hipMalloc(&b.p, want));
@@ -258,19 +279,17 @@ inline int ensure(isac_ctx* ctx, DevBuf& b, size_t bytes) {
   return ISAC_OK;
 }
 
-inline int ensure_pinned_buf(isac_ctx* ctx, void*& p, size_t& cap, size_t bytes) {
-  if (cap >= bytes) return ISAC_OK;
-  if (p) ISAC_HIP(hipHostFree(p));
-  p = nullptr;
-  cap = 0;
-  ISAC_HIP(hipHostMalloc(&p, bytes, hipHostMallocDefault));
-  cap = bytes;
+inline int ensure_pinned_buf(isac_ctx* ctx, PinnedBuf& b, size_t bytes) {
+  if (b.cap >= bytes) return ISAC_OK;
+  ISAC_HIP(b.reset());
+  ISAC_HIP(hipHostMalloc(&b.p, bytes, hipHostMallocDefault));
+  b.cap = bytes;
   return ISAC_OK;
 }
 inline int ensure_pinned(isac_ctx* ctx, size_t bytes) {
-  if (ctx->pinned_cap >= bytes) return ISAC_OK;
-  if (ctx->pinned && ctx->ev_done) ISAC_HIP(hipEventSynchronize(ctx->ev_done));   // a submitted CPI's D2H copy may still be writing the old buffer
-  return ensure_pinned_buf(ctx, ctx->pinned, ctx->pinned_cap, bytes);
+  if (ctx->pinned.cap >= bytes) return ISAC_OK;
+  if (ctx->pinned.p && ctx->ev_done) ISAC_HIP(hipEventSynchronize(ctx->ev_done));   // a submitted CPI's D2H copy may still be writing the old buffer
+  return ensure_pinned_buf(ctx, ctx->pinned, bytes);
 }
 
 // Host -> device copy that is COMPLETE when it returns and ordered in front of everything enqueued on the context's streams afterwards.  hipMemcpy on the NULL stream
@@ -285,9 +304,9 @@ inline int ensure_pinned(isac_ctx* ctx, size_t bytes) {
 constexpr size_t kBounceChunk = 8u << 20;
 inline int bounce_ready(isac_ctx* ctx, size_t bytes) {
   const size_t want = bytes < kBounceChunk ? (bytes < 4096 ? 4096 : bytes) : 2 * kBounceChunk;
-  if (ctx->bounce_cap < want) {
+  if (ctx->bounce.cap < want) {
     ISAC_HIP(hipStreamSynchronize(ctx->stream));
-    ISAC_TRY(ensure_pinned_buf(ctx, ctx->bounce, ctx->bounce_cap, want));
+    ISAC_TRY(ensure_pinned_buf(ctx, ctx->bounce, want));
   }
   for (auto& e : ctx->ev_bounce) if (!e) ISAC_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   return ISAC_OK;
@@ -299,7 +318,7 @@ inline int copy_h2d(isac_ctx* ctx, void* dst, const void* src, size_t bytes) {  
   int half = 0;
   for (size_t off = 0; off < bytes; off += kBounceChunk, half ^= 1) {
     const size_t n = bytes - off < kBounceChunk ? bytes - off : kBounceChunk;
-    char* b = (char*)ctx->bounce + (ctx->bounce_cap >= 2 * kBounceChunk ? (size_t)half * kBounceChunk : 0);
+    char* b = (char*)ctx->bounce.p + (ctx->bounce.cap >= 2 * kBounceChunk ? (size_t)half * kBounceChunk : 0);
     if (used[half]) ISAC_HIP(hipEventSynchronize(ctx->ev_bounce[half]));          // the chunk's previous copy has left the bounce buffer
     std::memcpy(b, (const char*)src + off, n);
     ISAC_HIP(hipMemcpyAsync((char*)dst + off, b, n, hipMemcpyHostToDevice, ctx->stream));
@@ -312,20 +331,20 @@ inline int copy_h2d(isac_ctx* ctx, void* dst, const void* src, size_t bytes) {  
 inline int copy_d2h(isac_ctx* ctx, void* dst, const void* src, size_t bytes) {           // waits for the stream first: everything enqueued before is in the copy
   if (!bytes) return ISAC_OK;
   ISAC_TRY(bounce_ready(ctx, bytes));
-  const bool two = ctx->bounce_cap >= 2 * kBounceChunk;
+  const bool two = ctx->bounce.cap >= 2 * kBounceChunk;
   size_t pend_off[2] = {0, 0}, pend_n[2] = {0, 0};
   int half = 0;
   for (size_t off = 0; off < bytes; off += kBounceChunk, half ^= 1) {
     const size_t n = bytes - off < kBounceChunk ? bytes - off : kBounceChunk;
     const int h = two ? half : 0;
-    char* b = (char*)ctx->bounce + (size_t)h * kBounceChunk;
+    char* b = (char*)ctx->bounce.p + (size_t)h * kBounceChunk;
     if (pend_n[h]) { ISAC_HIP(hipEventSynchronize(ctx->ev_bounce[h])); std::memcpy((char*)dst + pend_off[h], b, pend_n[h]); pend_n[h] = 0; }
     ISAC_HIP(hipMemcpyAsync(b, (const char*)src + off, n, hipMemcpyDeviceToHost, ctx->stream));
     ISAC_HIP(hipEventRecord(ctx->ev_bounce[h], ctx->stream));
     pend_off[h] = off; pend_n[h] = n;
   }
   ISAC_HIP(hipStreamSynchronize(ctx->stream));
-  for (int h = 0; h < 2; ++h) if (pend_n[h]) std::memcpy((char*)dst + pend_off[h], (char*)ctx->bounce + (size_t)h * kBounceChunk, pend_n[h]);
+  for (int h = 0; h < 2; ++h) if (pend_n[h]) std::memcpy((char*)dst + pend_off[h], (char*)ctx->bounce.p + (size_t)h * kBounceChunk, pend_n[h]);
   return ISAC_OK;
 }
 
@@ -341,19 +360,13 @@ inline int stage_acquire(isac_ctx* ctx, size_t bytes, void** host) {
   StageSlot& sl = ctx->stage_ring[ctx->stage_next];
   if (!sl.ev) ISAC_HIP(hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming));
   if (sl.busy) { ISAC_HIP(hipEventSynchronize(sl.ev)); sl.busy = false; }    // the slot's previous upload has left it
-  if (sl.cap < bytes) {
-    if (sl.p) ISAC_HIP(hipHostFree(sl.p));
-    sl.p = nullptr; sl.cap = 0;
-    const size_t want = bytes < 65536 ? 65536 : bytes;
-    ISAC_HIP(hipHostMalloc(&sl.p, want, hipHostMallocDefault));
-    sl.cap = want;
-  }
-  *host = sl.p;
+  if (sl.mem.cap < bytes) ISAC_TRY(ensure_pinned_buf(ctx, sl.mem, bytes < 65536 ? 65536 : bytes));
+  *host = sl.mem.p;
   return ISAC_OK;
 }
 inline int stage_commit(isac_ctx* ctx, void* d_dst, size_t bytes) {
   StageSlot& sl = ctx->stage_ring[ctx->stage_next];
-  ISAC_HIP(hipMemcpyAsync(d_dst, sl.p, bytes, hipMemcpyHostToDevice, ctx->stream));
+  ISAC_HIP(hipMemcpyAsync(d_dst, sl.mem.p, bytes, hipMemcpyHostToDevice, ctx->stream));
   ISAC_HIP(hipEventRecord(sl.ev, ctx->stream));
   sl.busy = true;
   ctx->stage_next = (ctx->stage_next + 1) % kStageSlots;

@@ -3,7 +3,22 @@
 #pragma once
 #include "isac_common.hpp"
 
-// ---------------------------------------------------------------- capi.hip: cached device tables
+// ---------------------------------------------------------------- tables.hip: cached device tables
+// The one way a cached table comes to exist: `key` is looked up in ctx->tables; on a miss `build` fills a std::vector<T> on the host, which is uploaded and kept under
+// the key until the context goes.  *out: the device pointer.
+template <typename T, typename Build>
+int cached_table(isac_ctx* ctx, const isac::TableKey& key, const T** out, Build build) {
+  auto it = ctx->tables.find(key);
+  if (it == ctx->tables.end()) {
+    std::vector<T> v;
+    build(v);
+    isac::DevBuf b;
+    ISAC_TRY(isac::upload(ctx, b, v.data(), sizeof(T) * v.size()));
+    it = ctx->tables.emplace(key, std::move(b)).first;
+  }
+  *out = (const T*)it->second.p;
+  return ISAC_OK;
+}
 int isac_get_twiddles(isac_ctx* ctx, int n, const isac::c64** out);
 int isac_get_w512_pack(isac_ctx* ctx, const isac::c64** out);
 int isac_get_logtab(isac_ctx* ctx, const isac::c64** out);

@@ -14,7 +14,7 @@ assert a in s
 s = s.replace(a, "  ISAC_HIP(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));\n  return ISAC_OK;\n}")
 open(p, "w").write(s)
 p = d + "/cqi.hip"; s = open(p).read()
-a = "    ISAC_HIP(hipMemcpyAsync(ctx->pinned_csi, d_mean, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));\n    ISAC_HIP(hipStreamSynchronize(ctx->stream));\n    const double m = *(const double*)ctx->pinned_csi;"
+a = "    ISAC_HIP(hipMemcpyAsync(ctx->pinned_csi.p, d_mean, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));\n    ISAC_HIP(hipStreamSynchronize(ctx->stream));\n    const double m = *(const double*)ctx->pinned_csi.p;"
 assert a in s
 s = s.replace(a, "    double m_stack = 0.0;\n    ISAC_HIP(hipMemcpyAsync(&m_stack, d_mean, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));\n    ISAC_HIP(hipStreamSynchronize(ctx->stream));\n    const double m = m_stack;")
 open(p, "w").write(s)
