@@ -19,15 +19,6 @@ namespace isac {
 typedef double v4f64 __attribute__((ext_vector_type(4)));
 
 
-__device__ __forceinline__ void tile_ij(int t, int nb, int& I, int& J) {
-  // t-th upper-triangular tile in row-major order
-  int i = 0;
-  int rem = t;
-  while (rem >= nb - i) { rem -= nb - i; ++i; }
-  I = i;
-  J = i + rem;
-}
-
 // ---- specialised schedule for A <= 64 (NB = ceil(A/16) <= 4 antenna blocks): every wave keeps ALL blocks'
 // operands of its samples in registers and owns a static group of <= 5 output tiles, so the four waves of a
 // workgroup issue exactly the same number of MFMAs (balanced SIMDs), and the next slab is prefetched under the
@@ -36,7 +27,7 @@ __device__ __forceinline__ void tile_ij(int t, int nb, int& I, int& J) {
 //   phase p owns the contiguous samples [16 p / kPhases, 16 (p + 1) / kPhases) of a 16-sample slab -- at two phases one whole
 //   128-byte line per antenna, requested by the two tile groups of that phase only; lane (i = lane&15, kq = lane>>4) holds
 //   kSamplesPerLane consecutive samples of antenna 16 b + i in every block b.
-// Three real MFMAs per tile and k-step instead of four (3M / Gauss form, see cov_group_body): 30 instead of 40 per four samples
+// Three real MFMAs per tile and k-step instead of four (3M / Gauss form, see cov_3m_kstep): 30 instead of 40 per four samples
 // at A = 64.  Measured at A = 64 (733 824 samples): 4M, interleaved sample map, 3 workgroups per CU 276 us / 1.37 GB fetched;
 // 3M + line map, 2 workgroups per CU 209 us / 1.05 GB; + a workgroup barrier every 8 slabs 215 us / 0.73 GB (= the input, once).
 constexpr int kCovSyncSlabs = 8;                                // power of two (1, 2, 4: +3-9 %; 16 .. none: within the noise of 8 in per-workgroup spans)
@@ -47,8 +38,11 @@ struct CovPlan {
   static constexpr int kPerGroup = (kTiles + kGroups - 1) / kGroups;
   static constexpr int kPhases = 4 / kGroups;                   // waves per workgroup = kGroups * kPhases = 4
   static constexpr int kSamplesPerLane = 4 / kPhases;           // k-steps a wave runs per 16-sample slab
+  static constexpr int first_tile(int grp) { return grp * kPerGroup; }
+  static constexpr int tiles_of(int grp) { return first_tile(grp) + kPerGroup <= kTiles ? kPerGroup : kTiles - first_tile(grp); }
 };
 
+// t-th upper-triangular tile (I <= J) of an nb x nb tile grid in row-major order; the same order numbers the 64 x 64 block pairs
 constexpr int cov_tile_i(int nb, int t) {
   int i = 0;
   while (t >= nb - i) { t -= nb - i; ++i; }
@@ -67,22 +61,63 @@ __device__ __forceinline__ void static_for(F&& f) {
   }
 }
 
+// One k-step (4 samples) of a wave's tiles T0 .. T0 + NT - 1 in 3M form: three real products per tile and k-step --
+//   off-diagonal tile:  S1 += Gr_I Gr_J,  S2 += Gi_I Gi_J,  S3 += (Gr_I - Gi_I)(Gr_J + Gi_J)  =>  Re = S1 + S2,  Im = (S3 - S1) + S2
+//   diagonal tile    :  Re += Gr Gr + Gi Gi,  M += Gr Gi  =>  Im = M - M^T, formed by the reducer (exactly antisymmetric)
+// re = S1 (or Re), im = S2 (or M), s3 = S3 (off-diagonal tiles only; the unused ones are dead code).  The cancellation in Im is
+// against terms of the size of the tile's own entries (|S1|, |S2| <~ |Re|): errors stay at a few ulp of the matrix norm.
+// cur[b][E] is the operand of antenna block b, dm = Gr - Gi (row operand), sp = Gr + Gi (column operand).
+// Issue order: the products of a k-step are issued tile by tile in three sweeps, so that two MFMAs into the same accumulator are
+// >= 2 NT issues apart -- back-to-back dependent v_mfma_f64_16x16x4 stall for the 64-cycle pass of their predecessor.
+// filler(k) is placed in the gap behind the k-th MFMA of the k-step, k = 0 .. 3 NT - 1.
+template <int NB, int T0, int NT, int E, int SPL, class F>
+__device__ __forceinline__ void cov_3m_kstep(const c64 (&cur)[NB][SPL], const double (&dm)[NB], const double (&sp)[NB], v4f64 (&re)[NT], v4f64 (&im)[NT],
+                                             v4f64 (&s3)[NT], F&& filler) {
+  static_for<0, NT>([&](auto uc) {
+    constexpr int u = decltype(uc)::value;
+    constexpr int I = cov_tile_i(NB, T0 + u), J = cov_tile_j(NB, T0 + u);
+    re[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur[I][E].re, cur[J][E].re, re[u], 0, 0, 0);
+    filler(std::integral_constant<int, u>{});
+  });
+  static_for<0, NT>([&](auto uc) {
+    constexpr int u = decltype(uc)::value;
+    constexpr int I = cov_tile_i(NB, T0 + u), J = cov_tile_j(NB, T0 + u);
+    if constexpr (I == J) im[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur[I][E].re, cur[J][E].im, im[u], 0, 0, 0);
+    else                  im[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur[I][E].im, cur[J][E].im, im[u], 0, 0, 0);
+    filler(std::integral_constant<int, NT + u>{});
+  });
+  static_for<0, NT>([&](auto uc) {
+    constexpr int u = decltype(uc)::value;
+    constexpr int I = cov_tile_i(NB, T0 + u), J = cov_tile_j(NB, T0 + u);
+    if constexpr (I == J) re[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur[I][E].im, cur[J][E].im, re[u], 0, 0, 0);
+    else                  s3[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(dm[I], sp[J], s3[u], 0, 0, 0);
+    filler(std::integral_constant<int, 2 * NT + u>{});
+  });
+}
+
+// The two planes of a partial tile from one accumulator entry of the 3M form (see cov_3m_kstep): (Re, Im) of an off-diagonal tile, (Re, M) of a
+// diagonal one -- M is antisymmetrised by the reducers.
+template <bool DIAG>
+__device__ __forceinline__ void cov_3m_out(double re, double im, double s3, double& o0, double& o1) {
+  if constexpr (!DIAG) {
+    o0 = re + im;
+    o1 = (s3 - re) + im;
+  } else {
+    o0 = re;
+    o1 = im;
+  }
+}
+
 template <int NB, int GRP, int NBUF = 3>
 __device__ __forceinline__ void cov_group_body(const c64* __restrict__ G, long long N, int A, int n_tiles, int phase, int lane,
                                                long long s0, long long s_step, long long s_cnt, long long s_lim, int part_index,
                                                double* __restrict__ part) {
   // this wave's i-th slab (16 samples) is slab s0 + i s_step of the grid, i = 0 .. s_cnt - 1; slabs >= s_lim contribute nothing
   using P = CovPlan<NB>;
-  constexpr int T0 = GRP * P::kPerGroup;
-  constexpr int NT = (T0 + P::kPerGroup <= P::kTiles) ? P::kPerGroup : (P::kTiles - T0);
+  constexpr int T0 = P::first_tile(GRP), NT = P::tiles_of(GRP);
   constexpr int SPL = P::kSamplesPerLane;
   const int li = lane & 15, kq = lane >> 4;
-  // 3M form: three real products per tile and k-step --
-  //   off-diagonal tile:  S1 += Gr_I Gr_J,  S2 += Gi_I Gi_J,  S3 += (Gr_I - Gi_I)(Gr_J + Gi_J)  =>  Re = S1 + S2,  Im = (S3 - S1) + S2
-  //   diagonal tile    :  Re += Gr Gr + Gi Gi,  M += Gr Gi  =>  Im = M - M^T, formed by the reducer (exactly antisymmetric)
-  // re = S1 (or Re), im = S2 (or M), s3 = S3 (off-diagonal tiles only; the unused ones are dead code).  The cancellation in Im is
-  // against terms of the size of the tile's own entries (|S1|, |S2| <~ |Re|): errors stay at a few ulp of the matrix norm.
-  v4f64 re[NT], im[NT], s3[NT];
+  v4f64 re[NT], im[NT], s3[NT];                       // 3M accumulators (cov_3m_kstep)
 #pragma unroll
   for (int u = 0; u < NT; ++u) re[u] = im[u] = s3[u] = v4f64{0.0, 0.0, 0.0, 0.0};
   // One raw-buffer descriptor per 16-antenna block (uniform: scalar registers), ending with the array's last antenna: padding antennas read as
@@ -121,32 +156,14 @@ __device__ __forceinline__ void cov_group_body(const c64* __restrict__ G, long l
         v[b][e] = mk(v[b][e].re * m, v[b][e].im * m);
       }
   };
-  // Issue order: the four products of a k-step are issued tile by tile in four sweeps, so that two MFMAs into the same accumulator are
-  // 2 NT issues apart -- back-to-back dependent v_mfma_f64_16x16x4 stall for the 64-cycle pass of their predecessor.
   auto mfmas = [&](const c64 (&cur)[NB][SPL]) {
-#pragma unroll
-    for (int e = 0; e < SPL; ++e) {
-      double dm[NB], sp[NB];                          // Gr - Gi (row operand), Gr + Gi (column operand)
+    static_for<0, SPL>([&](auto ec) {
+      constexpr int e = decltype(ec)::value;
+      double dm[NB], sp[NB];
 #pragma unroll
       for (int b = 0; b < NB; ++b) { dm[b] = cur[b][e].re - cur[b][e].im; sp[b] = cur[b][e].re + cur[b][e].im; }
-      static_for<0, NT>([&](auto uc) {
-        constexpr int u = decltype(uc)::value;
-        constexpr int I = cov_tile_i(NB, T0 + u), J = cov_tile_j(NB, T0 + u);   // row-major upper-triangular tile order
-        re[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur[I][e].re, cur[J][e].re, re[u], 0, 0, 0);
-      });
-      static_for<0, NT>([&](auto uc) {
-        constexpr int u = decltype(uc)::value;
-        constexpr int I = cov_tile_i(NB, T0 + u), J = cov_tile_j(NB, T0 + u);
-        if constexpr (I == J) im[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur[I][e].re, cur[J][e].im, im[u], 0, 0, 0);
-        else                  im[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur[I][e].im, cur[J][e].im, im[u], 0, 0, 0);
-      });
-      static_for<0, NT>([&](auto uc) {
-        constexpr int u = decltype(uc)::value;
-        constexpr int I = cov_tile_i(NB, T0 + u), J = cov_tile_j(NB, T0 + u);
-        if constexpr (I == J) re[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur[I][e].im, cur[J][e].im, re[u], 0, 0, 0);
-        else                  s3[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(dm[I], sp[J], s3[u], 0, 0, 0);
-      });
-    }
+      cov_3m_kstep<NB, T0, NT, e>(cur, dm, sp, re, im, s3, [](auto) {});
+    });
   };
   {
     // Three register buffers in rotation: the loads of slabs s+1 and s+2 fly under the MFMAs of slab s (one slab of MFMAs is ~0.8 us,
@@ -183,15 +200,7 @@ __device__ __forceinline__ void cov_group_body(const c64* __restrict__ G, long l
     constexpr bool diag = cov_tile_i(NB, T0 + u) == cov_tile_j(NB, T0 + u);
     double* o = part + (((long long)part_index * n_tiles + (T0 + u)) * 2) * 256;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      if constexpr (!diag) {
-        o[0 * 256 + r * 64 + lane] = re[u][r] + im[u][r];
-        o[1 * 256 + r * 64 + lane] = (s3[u][r] - re[u][r]) + im[u][r];
-      } else {
-        o[0 * 256 + r * 64 + lane] = re[u][r];
-        o[1 * 256 + r * 64 + lane] = im[u][r];             // diagonal tile: M, antisymmetrised by cov_reduce_kernel
-      }
-    }
+    for (int r = 0; r < 4; ++r) cov_3m_out<diag>(re[u][r], im[u][r], s3[u][r], o[0 * 256 + r * 64 + lane], o[1 * 256 + r * 64 + lane]);
   });
 }
 
@@ -240,6 +249,30 @@ constexpr unsigned kCovOobOffset = 0x80000000u;                 // beyond every 
 __constant__ unsigned char kCovDiagTiles[4][4] = {              // 16*I + J per (wave, slot); 255 = idle.  Slot 0 = the wave's diagonal tile
     {0x00, 0x01, 0x02, 255}, {0x11, 0x03, 0x12, 255}, {0x22, 0x13, 255, 255}, {0x33, 0x23, 255, 255}};
 
+// pair-th block pair (BI <= BJ) of n_blk antenna blocks, in the row-major order of cov_tile_i / cov_tile_j
+__device__ __forceinline__ void cov_pair_blocks(int n_blk, int pair, int& BI, int& BJ) {
+  int i = 0, rem = pair;
+  while (rem >= n_blk - i) { rem -= n_blk - i; ++i; }
+  BI = i;
+  BJ = i + rem;
+}
+
+// Partial of tile (I, J) of a block pair -> part[chunk][pair][4 I + J][2][256].  td: the wave's diagonal tile of a diagonal pair, accumulated as
+// re = Gr Gr', im = M = Gr Gi', s3 = Gi Gi' (M is antisymmetrised by cov_block_reduce_kernel); every other tile is an off-diagonal tile of the 3M form.
+__device__ __forceinline__ void cov_block_tile_store(bool td, const v4f64& re, const v4f64& im, const v4f64& s3, double* __restrict__ part, int chunk,
+                                                     int n_pairs, int pair, int I, int J, int lane) {
+  double* o = part + ((((long long)chunk * n_pairs + pair) * 16 + (I * 4 + J)) * 2) * 256;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    if (td) {
+      o[r * 64 + lane] = re[r] + s3[r];
+      o[256 + r * 64 + lane] = im[r];
+    } else {
+      cov_3m_out<false>(re[r], im[r], s3[r], o[r * 64 + lane], o[256 + r * 64 + lane]);
+    }
+  }
+}
+
 // One block pair.  DIAG (BI == BJ) is a template parameter so that the staging loop has a compile-time trip count: with a run-time
 // `j < n_stage` around the loads the wait-count pass gave up at every join and each stash waited with vmcnt(0) -- for the slab it needs AND
 // for the one issued a trip later, i.e. the second slab in flight never was.  Off-diagonal pairs also lose the operand selects of the
@@ -276,7 +309,7 @@ __device__ __forceinline__ void cov_block_pair(const c64* __restrict__ G, long l
     s_rs[j] = buffer_of(G + N * (long long)(ant0 < A ? ant0 : 0), (unsigned)(N * n_ant * (long long)sizeof(c64)));
   }
   const int s_lds0 = s_smp * kCovPitch + (l16 ^ kCovSwizzle(s_smp));       // + j * 16 * kCovPitch
-  // 3M form, as in cov_group_body: off-diagonal tile re = S1, im = S2, s3 = S3; diagonal tile (slot 0 of every wave of a diagonal block
+  // 3M form, as in cov_3m_kstep: off-diagonal tile re = S1, im = S2, s3 = S3; diagonal tile (slot 0 of every wave of a diagonal block
   // pair: a compile-time property, so neither selects nor branch-dependent accumulator moves) re + s3 = Re, im = M.
   v4f64 re[4], im[4], s3[4];
 #pragma unroll
@@ -374,13 +407,7 @@ __device__ __forceinline__ void cov_block_pair(const c64* __restrict__ G, long l
 #pragma unroll
   for (int u = 0; u < 4; ++u) {
     if (DIAG && !tv[u]) continue;
-    const bool td = DIAG && u == 0;
-    double* o = part + ((((long long)chunk * n_pairs + pair) * 16 + (tI[u] * 4 + tJ[u])) * 2) * 256;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      o[r * 64 + lane] = td ? re[u][r] + s3[u][r] : re[u][r] + im[u][r];
-      o[256 + r * 64 + lane] = td ? im[u][r] /* M: antisymmetrised by cov_block_reduce_kernel */ : (s3[u][r] - re[u][r]) + im[u][r];
-    }
+    cov_block_tile_store(DIAG && u == 0, re[u], im[u], s3[u], part, chunk, n_pairs, pair, tI[u], tJ[u], lane);
   }
 }
 
@@ -533,15 +560,7 @@ __device__ __forceinline__ void cov_block_pair_pl(const c64* __restrict__ G, lon
     });
   }
 #pragma unroll
-  for (int u = 0; u < NSLOT; ++u) {
-    const bool td = DIAG && u == 0;
-    double* o = part + ((((long long)chunk * n_pairs + pair) * 16 + (tI[u] * 4 + tJ[u])) * 2) * 256;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      o[r * 64 + lane] = td ? re[u][r] + s3[u][r] : re[u][r] + im[u][r];
-      o[256 + r * 64 + lane] = td ? im[u][r] /* M: antisymmetrised by cov_block_reduce_kernel */ : (s3[u][r] - re[u][r]) + im[u][r];
-    }
-  }
+  for (int u = 0; u < NSLOT; ++u) cov_block_tile_store(DIAG && u == 0, re[u], im[u], s3[u], part, chunk, n_pairs, pair, tI[u], tJ[u], lane);
 }
 
 __global__ __launch_bounds__(256, 2) void cov_mfma_block_pl_kernel(const c64* __restrict__ G, long long N, int A, int n_blk, int n_pairs,
@@ -549,12 +568,8 @@ __global__ __launch_bounds__(256, 2) void cov_mfma_block_pl_kernel(const c64* __
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   c64* lds = reinterpret_cast<c64*>(smem_raw);      // [kCovUImgs][kCovUImg]
   const int pair = blockIdx.x % n_pairs, chunk = blockIdx.x / n_pairs;
-  int BI = 0, BJ = 0;
-  {
-    int rem = pair;                                 // pair-th (BI <= BJ) in row-major order
-    while (rem >= n_blk - BI) { rem -= n_blk - BI; ++BI; }
-    BJ = BI + rem;
-  }
+  int BI, BJ;
+  cov_pair_blocks(n_blk, pair, BI, BJ);
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if (BI != BJ) cov_block_pair_pl<false, 4>(G, N, A, BI, BJ, pair, chunk, n_pairs, units_per_wg, part, lds);
   else if (wid < 2) cov_block_pair_pl<true, 3>(G, N, A, BI, BJ, pair, chunk, n_pairs, units_per_wg, part, lds);
@@ -580,150 +595,24 @@ __global__ __launch_bounds__(256, 2) void cov_mfma_block_pl_kernel(const c64* __
 // staging register sets (two slabs of global loads in flight), two operand register sets.  Same tile groups / sample phases / 3M accumulators /
 // partial layout as cov_group_body, so the reducers are shared; a phase owns the k-steps e = 2 p, 2 p + 1 of the image (samples {e, 4 + e, 8 + e, 12 + e}).
 constexpr int kCovLdsBufs = 3;
-template <int NB, int GRP>
-__device__ __forceinline__ void cov_lds_body(const c64* __restrict__ G, long long N, int A, int phase, long long s_begin, long long s_end,
-                                             int part_index, double* __restrict__ part, c64* __restrict__ lds) {
+constexpr int kCovSlabBlk = 16 * kCovPitch;                     // one 16-antenna block of a slab image (an image: NB of them)
+
+// The phase exchange and partial store of a staged tile group: the two sample phases of a tile group are summed inside the workgroup (through the now idle
+// slab images) before anything goes to memory: one partial per workgroup and tile instead of two -- half the partial-sum traffic of the kernel and of the
+// reducers behind it (20 instead of 41 MB per launch at A = 64).
+template <int NB, int GRP, int NT>
+__device__ __forceinline__ void cov_phase_sum_store(const v4f64 (&re)[NT], const v4f64 (&im)[NT], const v4f64 (&s3)[NT], int phase, int lane, int part_index,
+                                                    double* __restrict__ part, c64* __restrict__ lds) {
   using P = CovPlan<NB>;
-  static_assert(P::kGroups == 2 && P::kPhases == 2, "two tile groups x two sample phases");
-  constexpr int T0 = GRP * P::kPerGroup;
-  constexpr int NT = (T0 + P::kPerGroup <= P::kTiles) ? P::kPerGroup : (P::kTiles - T0);
-  constexpr int kBuf = NB * 16 * kCovPitch;         // one slab image
-  constexpr int kBlk = 16 * kCovPitch;              // one 16-antenna block of it
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int li = lane & 15, kq = lane >> 4;
-  v4f64 re[NT], im[NT], s3[NT];
-#pragma unroll
-  for (int u = 0; u < NT; ++u) re[u] = im[u] = s3[u] = v4f64{0.0, 0.0, 0.0, 0.0};
-  // staging: thread -> (sample tid & 15, antenna 16 j + (tid >> 4)), j = 0 .. NB - 1; one descriptor per 16-antenna block that ends with the
-  // array's last antenna (padding antennas read as zero by the bounds check)
-  const int s_smp = tid & 15, l16 = tid >> 4;
-  __amdgpu_buffer_rsrc_t s_rs[NB];
-#pragma unroll
-  for (int j = 0; j < NB; ++j) {
-    int n_ant = A - 16 * j;
-    n_ant = n_ant < 0 ? 0 : (n_ant > 16 ? 16 : n_ant);
-    s_rs[j] = buffer_of(G + N * (long long)(n_ant > 0 ? 16 * j : 0), (unsigned)(N * n_ant * (long long)sizeof(c64)));
-  }
-  const int s_lds0 = s_smp * kCovPitch + (l16 ^ kCovSwizzle(s_smp));
-  auto voff_of = [&](long long slab) {               // samples past N / slabs past the chunk: an offset beyond every descriptor reads zero
-    const long long n = slab * 16 + s_smp;
-    return (n < N && slab < s_end) ? (unsigned)((N * l16 + n) * (long long)sizeof(c64)) : kCovOobOffset;
-  };
-  int r_off[2];
-#pragma unroll
-  for (int e = 0; e < 2; ++e) {
-    const int smp = 4 * kq + 2 * phase + e;
-    r_off[e] = smp * kCovPitch + (li ^ kCovSwizzle(smp));
-  }
-  c64 g[2][NB];                                      // staging sets: at the top of the step for slab s, g[s & 1] holds slab s + 2, the other s + 3
-  c64 ops[2][NB][2];                                 // operand sets: ops[s & 1] holds slab s
-  // One slab step.  PAR = parity of the step (compile time: register sets), rd / wr = LDS images of slab + 1 (complete) and slab + 2 (free).
-  auto step = [&](auto par_c, long long slab, int rd, int wr) {
-    constexpr int PAR = decltype(par_c)::value;
-    const c64 (&cur)[NB][2] = ops[PAR];
-    c64 (&nxt)[NB][2] = ops[PAR ^ 1];
-    c64 (&gs)[NB] = g[PAR];
-    const c64* img = lds + rd * kBuf;
-    c64* dst = lds + wr * kBuf + s_lds0;
-    const unsigned voff = voff_of(slab + 4);
-    double dm[2][NB], sp[2][NB];                     // Gr - Gi (row operand), Gr + Gi (column operand) of the 3M form
-#pragma unroll
-    for (int e = 0; e < 2; ++e)
-#pragma unroll
-      for (int b = 0; b < NB; ++b) { dm[e][b] = cur[b][e].re - cur[b][e].im; sp[e][b] = cur[b][e].re + cur[b][e].im; }
-    __builtin_amdgcn_sched_barrier(0);
-    // filler k goes into the gap behind the k-th MFMA of the step (6 NT MFMAs: 30 at NB = 4): gaps 0 .. 2 NB - 1 the operand reads of the
-    // next slab, then the NB staging writes, then the NB staging loads into the registers just written out
-    auto filler = [&](auto kc) {
-      constexpr int k = decltype(kc)::value;
-      if constexpr (k < 2 * NB) {
-        constexpr int e = k / NB, b = k % NB;
-        nxt[b][e] = img[b * kBlk + r_off[e]];        // (blocks no tile of this group touches: dead reads, dropped by the compiler)
-        __builtin_amdgcn_sched_barrier(0);
-      } else if constexpr (k < 3 * NB) {
-        constexpr int j = k - 2 * NB;
-        dst[j * kBlk] = gs[j];
-        __builtin_amdgcn_sched_barrier(0);
-      } else if constexpr (k < 4 * NB) {
-        constexpr int j = k - 3 * NB;
-        gs[j] = buffer_load_c64(s_rs[j], voff);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    };
-    static_for<0, 2>([&](auto ec) {
-      constexpr int e = decltype(ec)::value;
-      static_for<0, NT>([&](auto uc) {
-        constexpr int u = decltype(uc)::value;
-        constexpr int I = cov_tile_i(NB, T0 + u), J = cov_tile_j(NB, T0 + u);
-        re[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur[I][e].re, cur[J][e].re, re[u], 0, 0, 0);
-        filler(std::integral_constant<int, e * 3 * NT + u>{});
-      });
-      static_for<0, NT>([&](auto uc) {
-        constexpr int u = decltype(uc)::value;
-        constexpr int I = cov_tile_i(NB, T0 + u), J = cov_tile_j(NB, T0 + u);
-        if constexpr (I == J) im[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur[I][e].re, cur[J][e].im, im[u], 0, 0, 0);
-        else                  im[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur[I][e].im, cur[J][e].im, im[u], 0, 0, 0);
-        filler(std::integral_constant<int, e * 3 * NT + NT + u>{});
-      });
-      static_for<0, NT>([&](auto uc) {
-        constexpr int u = decltype(uc)::value;
-        constexpr int I = cov_tile_i(NB, T0 + u), J = cov_tile_j(NB, T0 + u);
-        if constexpr (I == J) re[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur[I][e].im, cur[J][e].im, re[u], 0, 0, 0);
-        else                  s3[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(dm[e][I], sp[e][J], s3[u], 0, 0, 0);
-        filler(std::integral_constant<int, e * 3 * NT + 2 * NT + u>{});
-      });
-    });
-    static_assert(6 * NT >= 4 * NB, "every filler has its gap");
-    __syncthreads();
-  };
-  auto fetch = [&](c64 (&gg)[NB], long long slab) {
-    const unsigned voff = voff_of(slab);
-#pragma unroll
-    for (int j = 0; j < NB; ++j) gg[j] = buffer_load_c64(s_rs[j], voff);
-  };
-  auto stash = [&](const c64 (&gg)[NB], int buf) {
-    c64* d = lds + buf * kBuf + s_lds0;
-#pragma unroll
-    for (int j = 0; j < NB; ++j) d[j * kBlk] = gg[j];
-  };
-  // prologue: slab 0 -> image 0 -> ops[0]; slab 1 -> image 1; slabs 2, 3 in flight
-  fetch(g[0], s_begin);
-  fetch(g[1], s_begin + 1);
-  stash(g[0], 0);
-  stash(g[1], 1);
-  fetch(g[0], s_begin + 2);
-  fetch(g[1], s_begin + 3);
-  __syncthreads();
-#pragma unroll
-  for (int e = 0; e < 2; ++e)
-#pragma unroll
-    for (int b = 0; b < NB; ++b) ops[0][b][e] = lds[b * kBlk + r_off[e]];
-  int rd = 1, wr = 2;                                // (uniform) image of slab + 1, image for slab + 2
-  auto rot = [&]() { rd = wr; wr = wr == kCovLdsBufs - 1 ? 0 : wr + 1; };
-  for (long long slab = s_begin; slab < s_end; slab += 2) {       // (an odd slab count runs one all-zero slab: no exit in the middle)
-    step(std::integral_constant<int, 0>{}, slab, rd, wr);
-    rot();
-    step(std::integral_constant<int, 1>{}, slab + 1, rd, wr);
-    rot();
-  }
-  // the two sample phases of a tile group are summed inside the workgroup (through the now idle slab images) before anything goes to memory: one partial per
-  // workgroup and tile instead of two -- half the partial-sum traffic of this kernel and of the reducers behind it (20 instead of 41 MB per launch at A = 64)
+  constexpr int T0 = P::first_tile(GRP);
   double* x = reinterpret_cast<double*>(lds) + GRP * (P::kPerGroup * 2 * 256);
-  static_assert(sizeof(c64) * kCovLdsBufs * kBuf >= sizeof(double) * 2 * P::kPerGroup * 2 * 256, "the phase exchange fits the slab images");
+  static_assert(sizeof(c64) * kCovLdsBufs * NB * kCovSlabBlk >= sizeof(double) * 2 * P::kPerGroup * 2 * 256, "the phase exchange fits the slab images");
   double o0[NT][4], o1[NT][4];
   static_for<0, NT>([&](auto uc) {
     constexpr int u = decltype(uc)::value;
     constexpr bool diag = cov_tile_i(NB, T0 + u) == cov_tile_j(NB, T0 + u);
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      if constexpr (!diag) {
-        o0[u][r] = re[u][r] + im[u][r];
-        o1[u][r] = (s3[u][r] - re[u][r]) + im[u][r];
-      } else {
-        o0[u][r] = re[u][r];
-        o1[u][r] = im[u][r];                                 // diagonal tile: M, antisymmetrised by cov_reduce_kernel
-      }
-    }
+    for (int r = 0; r < 4; ++r) cov_3m_out<diag>(re[u][r], im[u][r], s3[u][r], o0[u][r], o1[u][r]);
   });
   if (phase == 1) {
 #pragma unroll
@@ -745,11 +634,135 @@ __device__ __forceinline__ void cov_lds_body(const c64* __restrict__ G, long lon
   }
 }
 
+// One wave of a staged kernel: tile group GRP, sample phase `phase`, slabs s_begin .. s_end - 1 of the workgroup.  Each slab step issues its 6 NT MFMAs (30 at
+// NB = 4) on operands already in registers; filler k goes into the gap behind the k-th MFMA of the step: gaps 0 .. 2 NB - 1 the operand reads of the next slab,
+// the gaps behind them whatever the Source needs to put the slab after that into its LDS image (sched_barrier pins the positions of the first Source::kGaps).
+// A Source provides
+//   prologue(lds)                   slabs s_begin, s_begin + 1 -> images 0, 1; slabs s_begin + 2, s_begin + 3 in flight
+//   begin_step(slab)                in front of the MFMAs of `slab`
+//   gap<PAR, K>(dst_image, slab)    its share of gap K of the step for `slab` (PAR = the step's parity: register sets), building slab + 2 in dst_image
+template <int NB, int GRP, class Source>
+__device__ __forceinline__ void cov_staged_body(Source src, int phase, long long s_begin, long long s_end, int part_index, double* __restrict__ part,
+                                                c64* __restrict__ lds) {
+  using P = CovPlan<NB>;
+  static_assert(P::kGroups == 2 && P::kPhases == 2, "two tile groups x two sample phases");
+  constexpr int T0 = P::first_tile(GRP), NT = P::tiles_of(GRP);
+  constexpr int kBuf = NB * kCovSlabBlk;            // one slab image
+  static_assert(6 * NT >= Source::kGaps && Source::kGaps >= 2 * NB, "every filler has its gap");
+  const int lane = threadIdx.x & 63;
+  const int li = lane & 15, kq = lane >> 4;
+  v4f64 re[NT], im[NT], s3[NT];
+#pragma unroll
+  for (int u = 0; u < NT; ++u) re[u] = im[u] = s3[u] = v4f64{0.0, 0.0, 0.0, 0.0};
+  int r_off[2];
+#pragma unroll
+  for (int e = 0; e < 2; ++e) {
+    const int smp = 4 * kq + 2 * phase + e;
+    r_off[e] = smp * kCovPitch + (li ^ kCovSwizzle(smp));
+  }
+  c64 ops[2][NB][2];                                 // operand sets: ops[s & 1] holds slab s
+  // One slab step.  PAR = parity of the step (compile time: register sets), rd / wr = LDS images of slab + 1 (complete) and slab + 2 (free).
+  auto step = [&](auto par_c, long long slab, int rd, int wr) {
+    constexpr int PAR = decltype(par_c)::value;
+    const c64 (&cur)[NB][2] = ops[PAR];
+    c64 (&nxt)[NB][2] = ops[PAR ^ 1];
+    const c64* img = lds + rd * kBuf;
+    c64* dst = lds + wr * kBuf;
+    src.begin_step(slab);
+    double dm[2][NB], sp[2][NB];                     // Gr - Gi (row operand), Gr + Gi (column operand) of the 3M form
+#pragma unroll
+    for (int e = 0; e < 2; ++e)
+#pragma unroll
+      for (int b = 0; b < NB; ++b) { dm[e][b] = cur[b][e].re - cur[b][e].im; sp[e][b] = cur[b][e].re + cur[b][e].im; }
+    __builtin_amdgcn_sched_barrier(0);
+    static_for<0, 2>([&](auto ec) {
+      constexpr int e = decltype(ec)::value;
+      cov_3m_kstep<NB, T0, NT, e>(cur, dm[e], sp[e], re, im, s3, [&](auto kc) {
+        constexpr int k = e * 3 * NT + decltype(kc)::value;
+        if constexpr (k < 2 * NB) nxt[k % NB][k / NB] = img[(k % NB) * kCovSlabBlk + r_off[k / NB]];   // (blocks no tile of this group touches: dead reads, dropped by the compiler)
+        src.template gap<PAR, k>(dst, slab);
+        if constexpr (k < Source::kGaps) __builtin_amdgcn_sched_barrier(0);
+      });
+    });
+    __syncthreads();
+  };
+  src.prologue(lds);
+  __syncthreads();
+#pragma unroll
+  for (int e = 0; e < 2; ++e)
+#pragma unroll
+    for (int b = 0; b < NB; ++b) ops[0][b][e] = lds[b * kCovSlabBlk + r_off[e]];
+  int rd = 1, wr = 2;                                // (uniform) image of slab + 1, image for slab + 2
+  auto rot = [&]() { rd = wr; wr = wr == kCovLdsBufs - 1 ? 0 : wr + 1; };
+  for (long long slab = s_begin; slab < s_end; slab += 2) {       // (an odd slab count runs one all-zero slab: no exit in the middle)
+    step(std::integral_constant<int, 0>{}, slab, rd, wr);
+    rot();
+    step(std::integral_constant<int, 1>{}, slab + 1, rd, wr);
+    rot();
+  }
+  cov_phase_sum_store<NB, GRP>(re, im, s3, phase, lane, part_index, part, lds);
+}
+
+// The slab source of cov_mfma_lds_kernel: the grid in memory.  thread -> (sample tid & 15, antenna 16 j + (tid >> 4)), j = 0 .. NB - 1; one descriptor per
+// 16-antenna block that ends with the array's last antenna (padding antennas read as zero by the bounds check).  Gaps 2 NB .. 3 NB - 1 carry the NB staging
+// writes, gaps 3 NB .. 4 NB - 1 the NB staging loads into the registers just written out.
+template <int NB>
+struct CovArrayStager {
+  static constexpr int kGaps = 4 * NB;
+  __amdgpu_buffer_rsrc_t s_rs[NB];
+  c64 g[2][NB];                                      // staging sets: at the top of the step for slab s, g[s & 1] holds slab s + 2, the other s + 3
+  long long N, row, s_begin, s_end;                  // row = N (tid >> 4): first sample of this thread's antenna inside a block
+  int s_smp, s_lds0;
+  unsigned voff;                                     // of the loads of the running step
+  __device__ __forceinline__ CovArrayStager(const c64* __restrict__ G, long long N_, int A, long long s_begin_, long long s_end_)
+      : N(N_), row(N_ * (threadIdx.x >> 4)), s_begin(s_begin_), s_end(s_end_), s_smp(threadIdx.x & 15) {
+#pragma unroll
+    for (int j = 0; j < NB; ++j) {
+      int n_ant = A - 16 * j;
+      n_ant = n_ant < 0 ? 0 : (n_ant > 16 ? 16 : n_ant);
+      s_rs[j] = buffer_of(G + N * (long long)(n_ant > 0 ? 16 * j : 0), (unsigned)(N * n_ant * (long long)sizeof(c64)));
+    }
+    s_lds0 = s_smp * kCovPitch + ((threadIdx.x >> 4) ^ kCovSwizzle(s_smp));
+  }
+  __device__ __forceinline__ unsigned voff_of(long long slab) const {   // samples past N / slabs past the chunk: an offset beyond every descriptor reads zero
+    const long long n = slab * 16 + s_smp;
+    return (n < N && slab < s_end) ? (unsigned)((row + n) * (long long)sizeof(c64)) : kCovOobOffset;
+  }
+  __device__ __forceinline__ void fetch(c64 (&gg)[NB], long long slab) {
+    const unsigned v = voff_of(slab);
+#pragma unroll
+    for (int j = 0; j < NB; ++j) gg[j] = buffer_load_c64(s_rs[j], v);
+  }
+  __device__ __forceinline__ void stash(const c64 (&gg)[NB], c64* img) {
+    c64* d = img + s_lds0;
+#pragma unroll
+    for (int j = 0; j < NB; ++j) d[j * kCovSlabBlk] = gg[j];
+  }
+  __device__ __forceinline__ void prologue(c64* __restrict__ lds) {
+    // The loads of the two slabs in flight are issued slab by slab, as the steps re-issue them: interleaved, the vmcnt waits of every step cover both slabs.
+    // The sched_barrier holds the order only if no load is moved behind the slab loop's guard: every workgroup of a launch has a slab, said here.
+    __builtin_assume(s_begin < s_end);
+    fetch(g[0], s_begin);
+    fetch(g[1], s_begin + 1);
+    stash(g[0], lds);
+    stash(g[1], lds + NB * kCovSlabBlk);
+    fetch(g[0], s_begin + 2);
+    __builtin_amdgcn_sched_barrier(0);
+    fetch(g[1], s_begin + 3);
+  }
+  __device__ __forceinline__ void begin_step(long long slab) { voff = voff_of(slab + 4); }
+  template <int PAR, int K>
+  __device__ __forceinline__ void gap(c64* dst, long long) {
+    if constexpr (K >= 2 * NB && K < 3 * NB) dst[s_lds0 + (K - 2 * NB) * kCovSlabBlk] = g[PAR][K - 2 * NB];
+    else if constexpr (K >= 3 * NB && K < 4 * NB) g[PAR][K - 3 * NB] = buffer_load_c64(s_rs[K - 3 * NB], voff);
+  }
+};
+
 template <int NB>
 __global__ __launch_bounds__(256, 2) void cov_mfma_lds_kernel(const c64* __restrict__ G, long long N, int A, long long slabs_per_wg,
                                                               double* __restrict__ part /* [gridX][kTiles][2][256] */) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  c64* lds = reinterpret_cast<c64*>(smem_raw);      // [kCovLdsBufs][NB * 16 * kCovPitch]
+  c64* lds = reinterpret_cast<c64*>(smem_raw);      // [kCovLdsBufs][NB * kCovSlabBlk]
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int grp = wid >> 1, phase = wid & 1;
   const long long total = (N + 15) / 16;
@@ -757,8 +770,8 @@ __global__ __launch_bounds__(256, 2) void cov_mfma_lds_kernel(const c64* __restr
   long long s_end = s_begin + slabs_per_wg;
   if (s_end > total) s_end = total;
   const int pidx = blockIdx.x;                       // (one partial per workgroup: the phases are summed in the kernel)
-  if (grp == 0) cov_lds_body<NB, 0>(G, N, A, phase, s_begin, s_end, pidx, part, lds);
-  else cov_lds_body<NB, 1>(G, N, A, phase, s_begin, s_end, pidx, part, lds);
+  if (grp == 0) cov_staged_body<NB, 0>(CovArrayStager<NB>(G, N, A, s_begin, s_end), phase, s_begin, s_end, pidx, part, lds);
+  else cov_staged_body<NB, 1>(CovArrayStager<NB>(G, N, A, s_begin, s_end), phase, s_begin, s_end, pidx, part, lds);
 }
 
 // ---------------------------------------------------------------- covariance of a LAZY echo grid (round 6)
@@ -788,51 +801,46 @@ __host__ __device__ constexpr int lazy_piece_gap(int i) {       // MFMA gap (0..
   return (i * 30) / kLazyPieces;
 }
 
-template <int GRP, int QT>
-__device__ __forceinline__ void cov_lazy_body(const LazyCovArgs& a, int phase, long long s_begin, long long s_end, int part_index, double* __restrict__ part,
-                                              c64* __restrict__ lds) {
-  constexpr int NB = 4;
-  using P = CovPlan<NB>;
-  constexpr int T0 = GRP * P::kPerGroup;
-  constexpr int NT = (T0 + P::kPerGroup <= P::kTiles) ? P::kPerGroup : (P::kTiles - T0);
-  constexpr int kBuf = NB * 16 * kCovPitch;         // one slab image
-  constexpr int kBlk = 16 * kCovPitch;              // one 16-antenna block of it
-  static_assert(6 * NT == 30, "30 MFMA gaps per slab step");
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int li = lane & 15, kq = lane >> 4;
-  v4f64 re[NT], im[NT], s3[NT];
-#pragma unroll
-  for (int u = 0; u < NT; ++u) re[u] = im[u] = s3[u] = v4f64{0.0, 0.0, 0.0, 0.0};
-  // ---- generator: thread -> (pair row gp, antennas ga and ga + 32)
-  const int gp = tid & 7, ga = tid >> 3;
-  const int K = a.K;
-  const double sig = a.sig;
-  const uint32_t key0 = (uint32_t)a.seed, key1 = (uint32_t)(a.seed >> 32);
+// The slab source of cov_lazy_kernel: thread -> (pair row gp, antennas ga and ga + 32) of every slab.
+template <int QT>
+struct CovLazyGenerator {
+  static constexpr int NB = 4;
+  static constexpr int kGaps = 30;                   // the generator's pieces are spread over all 30 gaps of a step (lazy_piece_gap)
+  struct Cur { int l, sc; long long g; };            // slab g = slab sc of symbol column l
+  int gp, ga, K, s_col, g_lds0;
+  double sig;
+  uint32_t key0, key1;
+  long long s_end;
   c64 st[2][QT];
   bool ant_ok[2];
   uint64_t colbase[2];
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int ant = ga + 32 * j;
-    ant_ok[j] = ant < a.A;
-    colbase[j] = (uint64_t)a.L_out * (uint64_t)ant;
-#pragma unroll
-    for (int q = 0; q < QT; ++q) st[j][q] = ant_ok[j] ? a.steer_rq[(long long)ant * QT + q] : mk(0.0, 0.0);
-  }
   __amdgpu_buffer_rsrc_t rsD[QT];
-#pragma unroll
-  for (int q = 0; q < QT; ++q) rsD[q] = buffer_of(a.D + (long long)q * K * a.L_whole, (unsigned)((long long)K * a.L_whole * (long long)sizeof(c64)));
-  const int g_lds0 = (ga >> 4) * kBlk + gp * kCovPitch + ((ga & 15) ^ kCovSwizzle(gp));     // element (antenna ga, sample slot gp); + 2 j kBlk, + 8 h kCovPitch
-  // cursors (wave-uniform): the slab being generated and the slab whose D values are being fetched
-  struct Cur { int l, sc; long long g; };
-  auto cur_at = [&](long long g) { Cur c; c.g = g; c.l = (int)((unsigned)g / (unsigned)a.s_col); c.sc = (int)((unsigned)g - (unsigned)c.l * (unsigned)a.s_col); return c; };   // (slab counts fit 31 bits: checked by the launcher)
-  auto advance = [&](Cur& c) { ++c.g; if (++c.sc == a.s_col) { c.sc = 0; ++c.l; } };
-  auto k0_of = [&](const Cur& c) { return ((c.sc >> 6) << 10) + ((c.sc & 63) << 3) + gp; };      // subcarrier of half 0; half 1 = + 512
+  Cur cg, cd;                                        // cursors (wave-uniform): the slab being generated and the slab whose D values are being fetched
   uint32_t pc[2][4];
   float wf[2][2][2];
   bool v_half[2];
   c64 dl[2][QT][2];                                  // D values of two slabs in flight: dl[par][q][half]
-  auto gen_init = [&](const Cur& c) {
+  __device__ __forceinline__ CovLazyGenerator(const LazyCovArgs& a, long long s_begin, long long s_end_)
+      : gp(threadIdx.x & 7), ga(threadIdx.x >> 3), K(a.K), s_col(a.s_col), sig(a.sig), key0((uint32_t)a.seed), key1((uint32_t)(a.seed >> 32)), s_end(s_end_) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int ant = ga + 32 * j;
+      ant_ok[j] = ant < a.A;
+      colbase[j] = (uint64_t)a.L_out * (uint64_t)ant;
+#pragma unroll
+      for (int q = 0; q < QT; ++q) st[j][q] = ant_ok[j] ? a.steer_rq[(long long)ant * QT + q] : mk(0.0, 0.0);
+    }
+#pragma unroll
+    for (int q = 0; q < QT; ++q) rsD[q] = buffer_of(a.D + (long long)q * K * a.L_whole, (unsigned)((long long)K * a.L_whole * (long long)sizeof(c64)));
+    g_lds0 = (ga >> 4) * kCovSlabBlk + gp * kCovPitch + ((ga & 15) ^ kCovSwizzle(gp));     // element (antenna ga, sample slot gp); + 2 j kCovSlabBlk, + 8 h kCovPitch
+    cg = cd = cur_at(s_begin);
+  }
+  __device__ __forceinline__ Cur cur_at(long long g) const {   // (slab counts fit 31 bits: checked by the launcher)
+    Cur c; c.g = g; c.l = (int)((unsigned)g / (unsigned)s_col); c.sc = (int)((unsigned)g - (unsigned)c.l * (unsigned)s_col); return c;
+  }
+  __device__ __forceinline__ void advance(Cur& c) const { ++c.g; if (++c.sc == s_col) { c.sc = 0; ++c.l; } }
+  __device__ __forceinline__ int k0_of(const Cur& c) const { return ((c.sc >> 6) << 10) + ((c.sc & 63) << 3) + gp; }      // subcarrier of half 0; half 1 = + 512
+  __device__ __forceinline__ void init(const Cur& c) {
     const int k0 = k0_of(c);
     const bool in = c.g < s_end;
     v_half[0] = in && k0 < K;
@@ -843,174 +851,80 @@ __device__ __forceinline__ void cov_lazy_body(const LazyCovArgs& a, int phase, l
       const uint64_t ctr = (uint64_t)slot + (uint64_t)kSpectralSlotsPerColumn * ((uint64_t)c.l + colbase[j]);
       pc[j][0] = (uint32_t)ctr; pc[j][1] = (uint32_t)(ctr >> 32); pc[j][2] = kSpectralStream; pc[j][3] = 0u;
     }
-  };
-  auto gen_round = [&](auto rc) {
-    constexpr uint32_t r = (uint32_t)decltype(rc)::value;
+  }
+  template <int R>
+  __device__ __forceinline__ void round() {
 #pragma unroll
-    for (int j = 0; j < 2; ++j) philox4x32_round(pc[j], key0 + r * 0x9E3779B9u, key1 + r * 0xBB67AE85u);
-  };
-  auto gen_bm = [&](auto jc, auto hc) {
-    constexpr int j = decltype(jc)::value, h = decltype(hc)::value;
+    for (int j = 0; j < 2; ++j) philox4x32_round(pc[j], key0 + (uint32_t)R * 0x9E3779B9u, key1 + (uint32_t)R * 0xBB67AE85u);
+  }
+  template <int I>                                   // Box-Muller transform I = 2 j + h: antenna set j, half h
+  __device__ __forceinline__ void bm() {
+    constexpr int j = I / 2, h = I % 2;
     box_muller32_hw_f32(pc[j][2 * h], pc[j][2 * h + 1], wf[j][h][0], wf[j][h][1]);
-  };
-  auto gen_emit = [&](auto jc, auto hc, const c64 (&dv)[QT][2], c64* img) {
-    constexpr int j = decltype(jc)::value, h = decltype(hc)::value;
+  }
+  template <int I>                                   // synthesis + mask + LDS store of element I = 2 j + h
+  __device__ __forceinline__ void emit(const c64 (&dv)[QT][2], c64* img) {
+    constexpr int j = I / 2, h = I % 2;
     c64 d[QT];
 #pragma unroll
     for (int q = 0; q < QT; ++q) d[q] = dv[q][h];
     c64 v = spectral_echo_value<QT, true>(d, st[j], mk((double)wf[j][h][0], (double)wf[j][h][1]), sig);
     const bool ok = v_half[h] && ant_ok[j];
     v = mk(ok ? v.re : 0.0, ok ? v.im : 0.0);
-    img[g_lds0 + 2 * j * kBlk + 8 * h * kCovPitch] = v;
-  };
-  auto gen_loads = [&](c64 (&dv)[QT][2], const Cur& c) {
+    img[g_lds0 + 2 * j * kCovSlabBlk + 8 * h * kCovPitch] = v;
+  }
+  __device__ __forceinline__ void loads(c64 (&dv)[QT][2], const Cur& c) {
     const int k0 = k0_of(c);
     const bool in = c.g < s_end;
     const unsigned base = (unsigned)(((long long)K * c.l + k0) * (long long)sizeof(c64));
     const unsigned o0 = (in && k0 < K) ? base : kCovOobOffset, o1 = (in && k0 + 512 < K) ? base + 512u * (unsigned)sizeof(c64) : kCovOobOffset;
 #pragma unroll
     for (int q = 0; q < QT; ++q) { dv[q][0] = buffer_load_c64(rsD[q], o0); dv[q][1] = buffer_load_c64(rsD[q], o1); }
-  };
-  int r_off[2];
-#pragma unroll
-  for (int e = 0; e < 2; ++e) {
-    const int smp = 4 * kq + 2 * phase + e;
-    r_off[e] = smp * kCovPitch + (li ^ kCovSwizzle(smp));
   }
-  c64 ops[2][NB][2];                                 // operand sets: ops[s & 1] holds slab s
-  Cur cg = cur_at(s_begin), cd = cur_at(s_begin);
-  // One slab step.  PAR = parity of the step, rd / wr = LDS images of slab + 1 (complete) and slab + 2 (being generated here).
-  auto step = [&](auto par_c, int rd, int wr) {
-    constexpr int PAR = decltype(par_c)::value;
-    const c64 (&cur)[NB][2] = ops[PAR];
-    c64 (&nxt)[NB][2] = ops[PAR ^ 1];
-    const c64* img = lds + rd * kBuf;
-    c64* dst = lds + wr * kBuf;
-    double dm[2][NB], sp[2][NB];
-#pragma unroll
-    for (int e = 0; e < 2; ++e)
-#pragma unroll
-      for (int b = 0; b < NB; ++b) { dm[e][b] = cur[b][e].re - cur[b][e].im; sp[e][b] = cur[b][e].re + cur[b][e].im; }
-    __builtin_amdgcn_sched_barrier(0);
-    auto piece = [&](auto ic) {
-      constexpr int i = decltype(ic)::value;
-      if constexpr (i == 0) { gen_init(cg); gen_round(std::integral_constant<int, 0>{}); }
-      else if constexpr (i < 10) gen_round(std::integral_constant<int, i>{});
-      else if constexpr (i < 14) gen_bm(std::integral_constant<int, (i - 10) / 2>{}, std::integral_constant<int, (i - 10) % 2>{});
-      else if constexpr (i < 18) gen_emit(std::integral_constant<int, (i - 14) / 2>{}, std::integral_constant<int, (i - 14) % 2>{}, dl[PAR], dst);
-      else { gen_loads(dl[PAR], cd); advance(cg); advance(cd); }
-    };
-    auto filler = [&](auto kc) {
-      constexpr int k = decltype(kc)::value;
-      if constexpr (k < 2 * NB) {
-        constexpr int e = k / NB, b = k % NB;
-        nxt[b][e] = img[b * kBlk + r_off[e]];        // (blocks no tile of this group touches: dead reads, dropped by the compiler)
-      }
-      static_for<0, kLazyPieces>([&](auto ic) {
-        if constexpr (lazy_piece_gap(decltype(ic)::value) == k) piece(ic);
-      });
-      __builtin_amdgcn_sched_barrier(0);
-    };
-    static_for<0, 2>([&](auto ec) {
-      constexpr int e = decltype(ec)::value;
-      static_for<0, NT>([&](auto uc) {
-        constexpr int u = decltype(uc)::value;
-        constexpr int I = cov_tile_i(NB, T0 + u), J = cov_tile_j(NB, T0 + u);
-        re[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur[I][e].re, cur[J][e].re, re[u], 0, 0, 0);
-        filler(std::integral_constant<int, e * 3 * NT + u>{});
-      });
-      static_for<0, NT>([&](auto uc) {
-        constexpr int u = decltype(uc)::value;
-        constexpr int I = cov_tile_i(NB, T0 + u), J = cov_tile_j(NB, T0 + u);
-        if constexpr (I == J) im[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur[I][e].re, cur[J][e].im, im[u], 0, 0, 0);
-        else                  im[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur[I][e].im, cur[J][e].im, im[u], 0, 0, 0);
-        filler(std::integral_constant<int, e * 3 * NT + NT + u>{});
-      });
-      static_for<0, NT>([&](auto uc) {
-        constexpr int u = decltype(uc)::value;
-        constexpr int I = cov_tile_i(NB, T0 + u), J = cov_tile_j(NB, T0 + u);
-        if constexpr (I == J) re[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur[I][e].im, cur[J][e].im, re[u], 0, 0, 0);
-        else                  s3[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(dm[e][I], sp[e][J], s3[u], 0, 0, 0);
-        filler(std::integral_constant<int, e * 3 * NT + 2 * NT + u>{});
-      });
-    });
-    __syncthreads();
-  };
-  // prologue: slabs 0 and 1 generated outright into images 0 and 1; the D values of slabs 2 and 3 in flight
-  auto gen_whole = [&](c64 (&dv)[QT][2], int buf) {
-    gen_loads(dv, cg);
-    gen_init(cg);
-    static_for<0, 10>([&](auto rc) { gen_round(rc); });
-    static_for<0, 4>([&](auto ic) { gen_bm(std::integral_constant<int, decltype(ic)::value / 2>{}, std::integral_constant<int, decltype(ic)::value % 2>{}); });
-    static_for<0, 4>([&](auto ic) { gen_emit(std::integral_constant<int, decltype(ic)::value / 2>{}, std::integral_constant<int, decltype(ic)::value % 2>{}, dv, lds + buf * kBuf); });
+  __device__ __forceinline__ void whole(c64 (&dv)[QT][2], c64* img) {
+    loads(dv, cg);
+    init(cg);
+    static_for<0, 10>([&](auto rc) { round<decltype(rc)::value>(); });
+    static_for<0, 4>([&](auto ic) { bm<decltype(ic)::value>(); });
+    static_for<0, 4>([&](auto ic) { emit<decltype(ic)::value>(dv, img); });
     advance(cg);
-  };
-  gen_whole(dl[0], 0);
-  gen_whole(dl[1], 1);
-  cd = cg;                                           // slab s_begin + 2
-  gen_loads(dl[0], cd); advance(cd);
-  gen_loads(dl[1], cd); advance(cd);
-  __syncthreads();
-#pragma unroll
-  for (int e = 0; e < 2; ++e)
-#pragma unroll
-    for (int b = 0; b < NB; ++b) ops[0][b][e] = lds[b * kBlk + r_off[e]];
-  int rd = 1, wr = 2;                                // (uniform) image of slab + 1, image for slab + 2
-  auto rot = [&]() { rd = wr; wr = wr == kCovLdsBufs - 1 ? 0 : wr + 1; };
-  for (long long slab = s_begin; slab < s_end; slab += 2) {       // (an odd slab count runs one all-zero slab: no exit in the middle)
-    step(std::integral_constant<int, 0>{}, rd, wr);
-    rot();
-    step(std::integral_constant<int, 1>{}, rd, wr);
-    rot();
   }
-  // phase exchange + partial store: as cov_lds_body
-  double* x = reinterpret_cast<double*>(lds) + GRP * (P::kPerGroup * 2 * 256);
-  double o0[NT][4], o1[NT][4];
-  static_for<0, NT>([&](auto uc) {
-    constexpr int u = decltype(uc)::value;
-    constexpr bool diag = cov_tile_i(NB, T0 + u) == cov_tile_j(NB, T0 + u);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      if constexpr (!diag) {
-        o0[u][r] = re[u][r] + im[u][r];
-        o1[u][r] = (s3[u][r] - re[u][r]) + im[u][r];
-      } else {
-        o0[u][r] = re[u][r];
-        o1[u][r] = im[u][r];                                 // diagonal tile: M, antisymmetrised by cov_reduce_kernel
-      }
-    }
-  });
-  if (phase == 1) {
-#pragma unroll
-    for (int u = 0; u < NT; ++u)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) { x[(u * 2 + 0) * 256 + r * 64 + lane] = o0[u][r]; x[(u * 2 + 1) * 256 + r * 64 + lane] = o1[u][r]; }
+  // slabs 0 and 1 generated outright into images 0 and 1; the D values of slabs 2 and 3 in flight
+  __device__ __forceinline__ void prologue(c64* __restrict__ lds) {
+    whole(dl[0], lds);
+    whole(dl[1], lds + NB * kCovSlabBlk);
+    cd = cg;                                         // slab s_begin + 2
+    loads(dl[0], cd); advance(cd);
+    loads(dl[1], cd); advance(cd);
   }
-  __syncthreads();
-  if (phase == 0) {
-#pragma unroll
-    for (int u = 0; u < NT; ++u) {
-      double* o = part + (((long long)part_index * P::kTiles + (T0 + u)) * 2) * 256;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        o[0 * 256 + r * 64 + lane] = o0[u][r] + x[(u * 2 + 0) * 256 + r * 64 + lane];
-        o[1 * 256 + r * 64 + lane] = o1[u][r] + x[(u * 2 + 1) * 256 + r * 64 + lane];
-      }
-    }
+  __device__ __forceinline__ void begin_step(long long) {}
+  template <int PAR, int I>                          // generator piece I of the slab at cursor cg, into image dst
+  __device__ __forceinline__ void piece(c64* dst) {
+    if constexpr (I == 0) { init(cg); round<0>(); }
+    else if constexpr (I < 10) round<I>();
+    else if constexpr (I < 14) bm<I - 10>();
+    else if constexpr (I < 18) emit<I - 14>(dl[PAR], dst);
+    else { loads(dl[PAR], cd); advance(cg); advance(cd); }
   }
-}
+  template <int PAR, int K_>
+  __device__ __forceinline__ void gap(c64* dst, long long) {
+    static_for<0, kLazyPieces>([&](auto ic) {
+      if constexpr (lazy_piece_gap(decltype(ic)::value) == K_) piece<PAR, decltype(ic)::value>(dst);
+    });
+  }
+};
 
 template <int QT>
 __global__ __launch_bounds__(256, 2) void cov_lazy_kernel(LazyCovArgs a, long long n_slabs, long long slabs_per_wg, double* __restrict__ part /* [gridX][kTiles][2][256] */) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  c64* lds = reinterpret_cast<c64*>(smem_raw);      // [kCovLdsBufs][4 * 16 * kCovPitch]
+  c64* lds = reinterpret_cast<c64*>(smem_raw);      // [kCovLdsBufs][4 * kCovSlabBlk]
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int grp = wid >> 1, phase = wid & 1;
   const long long s_begin = (long long)blockIdx.x * slabs_per_wg;
   long long s_end = s_begin + slabs_per_wg;
   if (s_end > n_slabs) s_end = n_slabs;
-  if (grp == 0) cov_lazy_body<0, QT>(a, phase, s_begin, s_end, blockIdx.x, part, lds);
-  else cov_lazy_body<1, QT>(a, phase, s_begin, s_end, blockIdx.x, part, lds);
+  if (grp == 0) cov_staged_body<4, 0>(CovLazyGenerator<QT>(a, s_begin, s_end), phase, s_begin, s_end, blockIdx.x, part, lds);
+  else cov_staged_body<4, 1>(CovLazyGenerator<QT>(a, s_begin, s_end), phase, s_begin, s_end, blockIdx.x, part, lds);
 }
 
 __global__ __launch_bounds__(256, 2) void cov_mfma_block_kernel(const c64* __restrict__ G, long long N, int A, int n_blk,
@@ -1021,12 +935,8 @@ __global__ __launch_bounds__(256, 2) void cov_mfma_block_kernel(const c64* __res
   // (pinning the block pairs of one sample chunk to one XCD -- workgroup b runs on XCD b % 8 -- so that a chunk's slabs enter ONE L2: 3.71 ->
   // 4.11 ms at A = 256, no change at A = 128: the diagonal pairs run 1.6x faster than the off-diagonal ones and drift out of the L2 window)
   const int pair = blockIdx.x % n_pairs, chunk = blockIdx.x / n_pairs;
-  int BI = 0, BJ = 0;
-  {
-    int rem = pair;                                 // pair-th (BI <= BJ) in row-major order
-    while (rem >= n_blk - BI) { rem -= n_blk - BI; ++BI; }
-    BJ = BI + rem;
-  }
+  int BI, BJ;
+  cov_pair_blocks(n_blk, pair, BI, BJ);
   if (BI == BJ) cov_block_pair<true>(G, N, A, BI, BJ, pair, chunk, n_pairs, slabs_per_wg, part, lds);
   else cov_block_pair<false>(G, N, A, BI, BJ, pair, chunk, n_pairs, slabs_per_wg, part, lds);
 }
@@ -1036,12 +946,8 @@ __global__ __launch_bounds__(1024) void cov_block_reduce_kernel(const double* __
                                                                 int A, double inv_n, c64* __restrict__ Ra) {
   __shared__ double s_sum[2][4][256];
   const int tile = blockIdx.x, pair = blockIdx.y;
-  int BI = 0, BJ = 0;
-  {
-    int rem = pair;
-    while (rem >= n_blk - BI) { rem -= n_blk - BI; ++BI; }
-    BJ = BI + rem;
-  }
+  int BI, BJ;
+  cov_pair_blocks(n_blk, pair, BI, BJ);
   const int I = tile >> 2, J = tile & 3;
   if (BI == BJ && J < I) return;                    // never computed
   const int e = threadIdx.x, g = threadIdx.y;
@@ -1094,13 +1000,11 @@ __global__ __launch_bounds__(256) void cov_reduce_slice_kernel(const double* __r
 
 // fixed-order reduction over workgroup partials + Hermitian fill + 1/N.
 __global__ __launch_bounds__(1024) void cov_reduce_kernel(const double* __restrict__ part, int n_wg, int n_tiles, int A,
-                                                          double inv_n, c64* __restrict__ Ra /* [A x A] column-major */,
-                                                          int diag_antisym /* diagonal tiles hold M: Im = M - M^T */) {
+                                                          double inv_n, c64* __restrict__ Ra /* [A x A] column-major */) {
   __shared__ double s_sum[2][4][256];
   const int t = blockIdx.x;
   const int nb = (A + 15) / 16;
-  int I, J;
-  tile_ij(t, nb, I, J);
+  const int I = cov_tile_i(nb, t), J = cov_tile_j(nb, t);
   const int e = threadIdx.x;            // r*64 + lane
   const int g = threadIdx.y;
   const int r = e >> 6, lane = e & 63;
@@ -1120,7 +1024,7 @@ __global__ __launch_bounds__(1024) void cov_reduce_kernel(const double* __restri
   if (g != 0) return;
   sr = ((s_sum[0][0][e] + s_sum[0][1][e]) + s_sum[0][2][e]) + s_sum[0][3][e];
   si = ((s_sum[1][0][e] + s_sum[1][1][e]) + s_sum[1][2][e]) + s_sum[1][3][e];
-  if (diag_antisym && I == J) {
+  if (I == J) {                                                       // diagonal tiles hold M: Im = M - M^T
     const int et = (col >> 2) * 64 + ((col & 3) << 4) + row;          // the (col, row) entry of the same tile
     si -= ((s_sum[1][0][et] + s_sum[1][1][et]) + s_sum[1][2][et]) + s_sum[1][3][et];
   }
@@ -1154,50 +1058,71 @@ extern "C" int isac_covariance_dev(isac_ctx* ctx, const isac_c64* d_grid, int64_
 // isac_profile_enable(ctx, 2): HIP events around exactly the wide covariance launch (bench.py's roofline entry when that launch is the longest of the CPI)
 #define ISAC_PROF_COV0(st) do { if (ctx->profile_cov) ISAC_HIP(hipEventRecord(ctx->ev_k0, st)); } while (0)
 #define ISAC_PROF_COV1(st) do { if (ctx->profile_cov) { ISAC_HIP(hipEventRecord(ctx->ev_k1, st)); ctx->profile_recorded = true; } } while (0)
+// Grid of a staged launch (cov_mfma_lds_kernel, cov_lazy_kernel) over `slabs` slabs: at most 512 workgroups (2 per CU: register-limited occupancy), each
+// walking `per` slabs, in pairs.
+static void cov_staged_grid(long long slabs, long long& gx, long long& per) {
+  gx = 512 < slabs ? 512 : slabs;
+  per = (slabs + gx - 1) / gx;
+  per = (per + 1) & ~1ll;
+  gx = (slabs + per - 1) / per;
+}
+
+// Sizes cov_part for n_part workgroup partials [n_part][n_tiles][2][256] (+ the 32 slices of the first reduction level), has `launch(part)` enqueue the kernel
+// that writes them, and enqueues the two-level fixed-order reduction into Ra.
+template <class Launch>
+static int cov_partials_to_ra(isac_ctx* ctx, hipStream_t st, int n_part, int n_tiles, int A, double inv_n, c64* Ra, Launch&& launch) {
+  const int S = 32;
+  ISAC_TRY(ensure(ctx, ctx->cov_part, sizeof(double) * ((size_t)n_part + S) * n_tiles * 2 * 256));
+  double* part = (double*)ctx->cov_part.p;
+  double* part2 = part + (size_t)n_part * n_tiles * 2 * 256;
+  ISAC_TRY(launch(part));
+  hipLaunchKernelGGL(cov_reduce_slice_kernel, dim3(n_tiles, S), dim3(256), 0, st, (const double*)part, n_part, n_tiles, S, part2);
+  ISAC_HIP(hipGetLastError());
+  hipLaunchKernelGGL(cov_reduce_kernel, dim3(n_tiles), dim3(256, 4), 0, st, (const double*)part2, S, n_tiles, A, inv_n, Ra);
+  ISAC_HIP(hipGetLastError());
+  return ISAC_OK;
+}
+
 template <int NB>
 static int launch_cov_small(isac_ctx* ctx, hipStream_t st, const c64* G, long long N, int A, c64* Ra) {
   using P = CovPlan<NB>;
   const long long total = (N + 15) / 16;
   if (N * 256 >= (1ll << 32)) return fail(ctx, ISAC_ERR_UNSUPPORTED, "covariance: at most 2^24 - 1 samples per antenna");
-  long long gx = NB == 4 ? 512 : 768;       // NB = 4: 2 workgroups per CU (register-limited occupancy)
-  if (gx > total) gx = total;
-  long long per = (total + gx - 1) / gx;
   const bool staged = (NB >= 3) && N * 256 < (1ll << 31);           // two tile groups: fetch each slab once per workgroup, through LDS
-  if (staged) { gx = 512 < total ? 512 : total; per = (total + gx - 1) / gx; per = (per + 1) & ~1ll; }   // (the staged kernel walks slabs in pairs)
-  gx = (total + per - 1) / per;
-  const int n_part = (int)gx * (staged ? 1 : P::kPhases);       // (the staged kernel sums its two sample phases itself)
-  ISAC_TRY(ensure(ctx, ctx->cov_part, sizeof(double) * ((size_t)n_part + 32) * P::kTiles * 2 * 256));
-  if constexpr (NB >= 3) {
-    if (staged) {
-      const size_t lds = sizeof(c64) * kCovLdsBufs * NB * 16 * kCovPitch;
-      ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(cov_mfma_lds_kernel<NB>), lds));
-      ISAC_PROF_COV0(st);
-      hipLaunchKernelGGL((cov_mfma_lds_kernel<NB>), dim3((unsigned)gx), dim3(256), lds, st, G, N, A, per, (double*)ctx->cov_part.p);
-      ISAC_HIP(hipGetLastError());
-      ISAC_PROF_COV1(st);
-    }
+  long long gx, per;
+  if (staged) {
+    cov_staged_grid(total, gx, per);
+  } else {
+    gx = NB == 4 ? 512 : 768;                 // NB = 4: 2 workgroups per CU (register-limited occupancy)
+    if (gx > total) gx = total;
+    per = (total + gx - 1) / gx;
+    gx = (total + per - 1) / per;
   }
-  if (!staged) {
+  const int n_part = (int)gx * (staged ? 1 : P::kPhases);       // (the staged kernel sums its two sample phases itself)
+  return cov_partials_to_ra(ctx, st, n_part, P::kTiles, A, 1.0 / (double)N, Ra, [&](double* part) -> int {
+    if constexpr (NB >= 3) {
+      if (staged) {
+        const size_t lds = sizeof(c64) * kCovLdsBufs * NB * kCovSlabBlk;
+        ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(cov_mfma_lds_kernel<NB>), lds));
+        ISAC_PROF_COV0(st);
+        hipLaunchKernelGGL((cov_mfma_lds_kernel<NB>), dim3((unsigned)gx), dim3(256), lds, st, G, N, A, per, part);
+        ISAC_HIP(hipGetLastError());
+        ISAC_PROF_COV1(st);
+        return ISAC_OK;
+      }
+    }
     ISAC_PROF_COV0(st);
-    hipLaunchKernelGGL((cov_mfma_small_kernel<NB>), dim3((unsigned)gx), dim3(256), 0, st, G, N, A, per, (double*)ctx->cov_part.p);
+    hipLaunchKernelGGL((cov_mfma_small_kernel<NB>), dim3((unsigned)gx), dim3(256), 0, st, G, N, A, per, part);
     ISAC_HIP(hipGetLastError());
     ISAC_PROF_COV1(st);
-  }
-  const int S = 32;
-  double* part2 = (double*)ctx->cov_part.p + (size_t)n_part * P::kTiles * 2 * 256;
-  hipLaunchKernelGGL(cov_reduce_slice_kernel, dim3(P::kTiles, S), dim3(256), 0, st, (const double*)ctx->cov_part.p, n_part, P::kTiles, S,
-                     part2);
-  ISAC_HIP(hipGetLastError());
-  hipLaunchKernelGGL(cov_reduce_kernel, dim3(P::kTiles), dim3(256, 4), 0, st, (const double*)part2, S, P::kTiles, A,
-                     1.0 / (double)N, Ra, 1);
-  ISAC_HIP(hipGetLastError());
-  return ISAC_OK;
+    return ISAC_OK;
+  });
 }
 
 // Ra of the context's NATIVE lazy echo grid (ctx->lazy: isac_mono_static_sensing_fused_dev with d_echo_grid == NULL) -- fft2D.m:106-107 without the array.
 template <int QT>
 static int launch_cov_lazy(isac_ctx* ctx, hipStream_t st, const LazyCovArgs& a, long long n_slabs, long long per, long long gx, double* part) {
-  const size_t lds = sizeof(c64) * kCovLdsBufs * 4 * 16 * kCovPitch;
+  const size_t lds = sizeof(c64) * kCovLdsBufs * 4 * kCovSlabBlk;
   ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(cov_lazy_kernel<QT>), lds));
   ISAC_PROF_COV0(st);
   hipLaunchKernelGGL((cov_lazy_kernel<QT>), dim3((unsigned)gx), dim3(256), lds, st, a, n_slabs, per, part);
@@ -1211,28 +1136,16 @@ int isac_covariance_lazy_on(isac_ctx* ctx, hipStream_t st, isac_c64* d_Ra) {
   if (!lz.valid || !lz.native || !d_Ra) return fail(ctx, ISAC_ERR_INVALID_ARG, "no native lazy echo grid on this context");
   if (lz.A <= 48 || lz.A > 64 || lz.Q < 1 || lz.Q > 2) return fail(ctx, ISAC_ERR_UNSUPPORTED, "lazy covariance: 49..64 antennas, one or two LoS targets");
   if ((long long)lz.K * lz.L_whole * 16 >= (1ll << 31)) return fail(ctx, ISAC_ERR_UNSUPPORTED, "lazy covariance: per-target grid of 2 GB or more");
-  using P = CovPlan<4>;
   int s_col = 0;
   for (int k0 = 0; k0 < lz.K; k0 += 1024) s_col += (std::min(512, lz.K - k0) + 7) / 8;
   const long long n_slabs = (long long)lz.L_whole * s_col;
   if (n_slabs <= 0 || n_slabs >= (1ll << 31) - 4) return fail(ctx, ISAC_ERR_UNSUPPORTED, "lazy covariance: slab count out of range");
-  long long gx = 512 < n_slabs ? 512 : n_slabs;
-  long long per = (n_slabs + gx - 1) / gx;
-  per = (per + 1) & ~1ll;                             // the kernel walks slabs in pairs
-  gx = (n_slabs + per - 1) / per;
-  const int n_part = (int)gx;
-  ISAC_TRY(ensure(ctx, ctx->cov_part, sizeof(double) * ((size_t)n_part + 32) * P::kTiles * 2 * 256));
+  long long gx, per;
+  cov_staged_grid(n_slabs, gx, per);
   LazyCovArgs a{(const c64*)ctx->dgrid.p, (const c64*)ctx->steer.p + (size_t)lz.A * lz.Q, lz.sig, lz.seed, lz.K, lz.L_whole, lz.L_out, lz.A, s_col};
-  if (lz.Q == 1) ISAC_TRY(launch_cov_lazy<1>(ctx, st, a, n_slabs, per, gx, (double*)ctx->cov_part.p));
-  else ISAC_TRY(launch_cov_lazy<2>(ctx, st, a, n_slabs, per, gx, (double*)ctx->cov_part.p));
-  const int S = 32;
-  double* part2 = (double*)ctx->cov_part.p + (size_t)n_part * P::kTiles * 2 * 256;
-  hipLaunchKernelGGL(cov_reduce_slice_kernel, dim3(P::kTiles, S), dim3(256), 0, st, (const double*)ctx->cov_part.p, n_part, P::kTiles, S, part2);
-  ISAC_HIP(hipGetLastError());
-  hipLaunchKernelGGL(cov_reduce_kernel, dim3(P::kTiles), dim3(256, 4), 0, st, (const double*)part2, S, P::kTiles, lz.A,
-                     1.0 / ((double)lz.K * (double)lz.L_out), (c64*)d_Ra, 1);
-  ISAC_HIP(hipGetLastError());
-  return ISAC_OK;
+  return cov_partials_to_ra(ctx, st, (int)gx, CovPlan<4>::kTiles, lz.A, 1.0 / ((double)lz.K * (double)lz.L_out), (c64*)d_Ra, [&](double* part) -> int {
+    return lz.Q == 1 ? launch_cov_lazy<1>(ctx, st, a, n_slabs, per, gx, part) : launch_cov_lazy<2>(ctx, st, a, n_slabs, per, gx, part);
+  });
 }
 
 int isac_covariance_on(isac_ctx* ctx, hipStream_t st, const isac_c64* d_grid, int64_t N, int32_t A, isac_c64* d_Ra) {
