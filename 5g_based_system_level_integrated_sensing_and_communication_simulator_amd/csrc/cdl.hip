@@ -10,11 +10,12 @@
 // followed by the per-(t,u) FIR over the reduced signals:  y[t,u] = sum_n sum_k g_n[k] Z[t-shift_n-k, n,u].
 // Uplink (Nr > Nt: 2 -> 64): the delay filters run on the Nt transmit signals first, the contraction follows with K = n_paths*Nt.
 //
-// Round 4: everything is device resident and batched -- a call takes any number of (UE, slot) jobs that share the numerology, builds one
-// segment table (one entry per job and gain block), uploads it through pinned staging without synchronising, and issues ONE GEMM launch and ONE
-// filter launch for the whole batch.  The GEMM is in 3M form (three real MFMAs per complex tile step), reads its path gains straight from the
-// caller's [block][path][s][u] array into an LDS image in MFMA operand order (with hr + hi precomputed), streams X with coalesced 256-byte
-// runs per 16 lanes, and computes two 16-row tiles per wave against each B operand read.  The filter stages each column window in LDS once.
+// Everything is device resident and batched -- a call takes any number of (UE, slot) jobs that share the numerology, builds one segment table (one entry per
+// job and gain block) and uploads it through pinned staging without synchronising.  Three forms, all with the contraction in 3M form on fp64 MFMA
+// (cdl_3m_step) against a B image of the path gains in MFMA operand order (cdl_b_entry):
+//   fused downlink (cdl_fused_kernel) / fused uplink (cdl_fused_ul_kernel): one persistent launch, the intermediate signals never leave the CU;
+//   unfused (every shape outside the fused envelopes, and ISAC_CDL_UNFUSED): cdl_pack_kernel + cdl_gemm_kernel + cdl_fir_kernel / cdl_fir4_kernel.
+// Long waveforms take the overlap-save form of cdl_os.hip instead (ISAC_CDL_TIME_DOMAIN keeps them here); these kernels are its <= 1e-12 cross-check.
 #include <algorithm>
 #include <cstring>
 #include <type_traits>
@@ -52,25 +53,50 @@ constexpr int kCdlKChunk = 64;                      // contraction depth per LDS
 constexpr int kCdlMaxColTiles = 3;                  // 16-column tiles per workgroup (accumulators: 2 x 3 x 3 x 8 VGPRs)
 
 // C[r0:r1, cols] = scale * A[r0:r1, 0:K] * B,  B[k, col] = H[n][s][u] with  DL: k = s, col = n Nr + u;  UL: k = n Nt + s, col = u.
-// LDS image of one K chunk: [k-step 16][column tile NCT][form 3: hr, hi, hr + hi][lane 64] doubles, lane = 16 (k & 3) + (col & 15) -- exactly the
-// B-operand order of v_mfma_f64_16x16x4_f64, so every operand is one conflict-free ds_read_b64.
-// B images in LDS order, one per (segment, column group, K chunk): [k-step 16][column tile NCT][form 3: hr, hi, hr + hi][lane 64] doubles.
+// B image of one K chunk, entry i = [k-step][column tile nct][lane 64], lane = 16 (k & 3) + (col & 15) -- exactly the B-operand order of v_mfma_f64_16x16x4_f64,
+// so every operand is one conflict-free LDS read.  The gain of entry i of the image that starts at contraction index k0 and column tile ct0; beyond K or Nc the entry
+// is zero: `ok` tells, and the caller selects where it stores (selecting here costs the fused downlink kernel four registers and <3, *> 16 bytes of scratch).
+template <bool UL>
+__device__ __forceinline__ c64 cdl_b_entry(const c64* __restrict__ H, int i, int nct, int k0, int ct0, int K, int Nc, int Nt, int Nr, bool& ok) {
+  const int ks = i / (nct * 64), ct = (i >> 6) % nct, ln = i & 63;
+  const int k = k0 + 4 * ks + (ln >> 4), col = 16 * (ct0 + ct) + (ln & 15);
+  ok = k < K && col < Nc;
+  const int kk = ok ? k : 0, cc = ok ? col : 0;
+  const int n = UL ? kk / Nt : cc / Nr, s = UL ? kk % Nt : kk, u = UL ? cc : cc % Nr;
+  return H[((long long)n * Nt + s) * Nr + u];                          // unconditional load (index clamped), select afterwards
+}
+
+// One k-step of the 3M product (xr + j xi)(hr + j hi) for RT row tiles x NCT column tiles:  P1 += xr hr,  P2 += xi hi,  P3 += (xr + xi)(hr + hi);
+// issue order column tile, form, row tile.  Then  Re = P1 - P2,  Im = P3 - P1 - P2  (cdl_3m_out, element r of the f64 MFMA C/D layout).
+template <int RT, int NCT>
+__device__ __forceinline__ void cdl_3m_step(const c64 (&x)[RT], const c64 (&h)[NCT], const double (&hs)[NCT], v4f64 (&p1)[RT][NCT], v4f64 (&p2)[RT][NCT], v4f64 (&p3)[RT][NCT]) {
+  double xs[RT];
+#pragma unroll
+  for (int rt = 0; rt < RT; ++rt) xs[rt] = x[rt].re + x[rt].im;
+#pragma unroll
+  for (int ct = 0; ct < NCT; ++ct) {
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) p1[rt][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(x[rt].re, h[ct].re, p1[rt][ct], 0, 0, 0);
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) p2[rt][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(x[rt].im, h[ct].im, p2[rt][ct], 0, 0, 0);
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) p3[rt][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(xs[rt], hs[ct], p3[rt][ct], 0, 0, 0);
+  }
+}
+__device__ __forceinline__ c64 cdl_3m_out(const v4f64& p1, const v4f64& p2, const v4f64& p3, int r) { return mk(p1[r] - p2[r], (p3[r] - p1[r]) - p2[r]); }
+
+// The B images of the unfused contraction, one per (segment, column group, K chunk), each [k-step 16][column tile nct][form 3: hr, hi, hr + hi][lane 64] doubles.
 // (Built once per call by this small kernel; the contraction kernel's workgroups -- hundreds per segment -- copy them with coalesced 16-byte loads
 // instead of each gathering 3 072 path gains through index arithmetic: that gather cost about half a row tile's MFMA time.)
 template <bool UL>
 __global__ __launch_bounds__(256) void cdl_pack_kernel(const CdlSeg* __restrict__ segs, int nct, int Nt, int Nr, int K, int Nc, double* __restrict__ bimg) {
   const CdlSeg sg = segs[blockIdx.z];
   const int n_chunks = (K + kCdlKChunk - 1) / kCdlKChunk, per = 16 * nct * 3 * 64;
-  const int ct0 = blockIdx.y * nct, kc0 = blockIdx.x * kCdlKChunk;
   double* img = bimg + (((size_t)blockIdx.z * gridDim.y + blockIdx.y) * (size_t)n_chunks + blockIdx.x) * (size_t)per;
   for (int i = threadIdx.x; i < 16 * nct * 64; i += blockDim.x) {
-    const int ks = i / (nct * 64), ct = (i >> 6) % nct, ln = i & 63;
-    const int k = kc0 + 4 * ks + (ln >> 4), col = 16 * (ct0 + ct) + (ln & 15);
-    const bool ok = k < K && col < Nc;
-    const int kk = ok ? k : 0, cc = ok ? col : 0;
-    const int n = UL ? kk / Nt : cc / Nr, s = UL ? kk % Nt : kk, u = UL ? cc : cc % Nr;
-    const c64 h = sg.H[((long long)n * Nt + s) * Nr + u];             // unconditional load, select afterwards
-    double* d = img + ((ks * nct + ct) * 3) * 64 + ln;
+    bool ok;
+    const c64 h = cdl_b_entry<UL>(sg.H, i, nct, blockIdx.x * kCdlKChunk, blockIdx.y * nct, K, Nc, Nt, Nr, ok);
+    double* d = img + (i >> 6) * (3 * 64) + (i & 63);
     d[0] = ok ? h.re : 0.0;
     d[64] = ok ? h.im : 0.0;
     d[128] = ok ? h.re + h.im : 0.0;
@@ -127,45 +153,31 @@ __global__ __launch_bounds__(256, 2) void cdl_gemm_kernel(const CdlSeg* __restri
       const unsigned col_step = (unsigned)(4 * lda * (long long)sizeof(c64));          // one k-step = four columns of A
       const int k_last = K - 1 - kc0 - kq;                                              // (k-steps whose column k >= K re-read column K - 1: B is zero there)
       const unsigned col0 = (unsigned)((long long)(kc0 + kq) * lda * (long long)sizeof(c64)), col_last = (unsigned)((long long)(K - 1) * lda * (long long)sizeof(c64));
-      c64 xa[2][RT];
-      double hb[2][NCT][3];
+      c64 xa[2][RT], hp[2][NCT];
+      double hs[2][NCT];
       auto load_a = [&](int ks, c64 (&x)[RT]) {
         const unsigned co = 4 * ks <= k_last ? col0 + (unsigned)ks * col_step : col_last;
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) x[rt] = buffer_load_c64(rs_a, ro[rt] + co);
       };
-      auto load_b = [&](int ks, double (&h)[NCT][3]) {
+      auto load_b = [&](int ks, c64 (&h)[NCT], double (&hsv)[NCT]) {
         const double* bp = lds + (ks * NCT * 3) * 64 + lane;
 #pragma unroll
-        for (int ct = 0; ct < NCT; ++ct)
-#pragma unroll
-          for (int f = 0; f < 3; ++f) h[ct][f] = bp[(ct * 3 + f) * 64];
+        for (int ct = 0; ct < NCT; ++ct) { h[ct] = mk(bp[(ct * 3) * 64], bp[(ct * 3 + 1) * 64]); hsv[ct] = bp[(ct * 3 + 2) * 64]; }
       };
       load_a(0, xa[0]);
-      load_b(0, hb[0]);
+      load_b(0, hp[0], hs[0]);
       static_for<0, 16>([&](auto ksc) {
         constexpr int ks = decltype(ksc)::value, cur = ks & 1;
         if constexpr (ks + 1 < 16) {
           load_a(ks + 1, xa[cur ^ 1]);
-          load_b(ks + 1, hb[cur ^ 1]);
+          load_b(ks + 1, hp[cur ^ 1], hs[cur ^ 1]);
         }
         __builtin_amdgcn_sched_barrier(0);
-        double xs[RT];
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt) xs[rt] = xa[cur][rt].re + xa[cur][rt].im;
-#pragma unroll
-        for (int ct = 0; ct < NCT; ++ct) {
-#pragma unroll
-          for (int rt = 0; rt < RT; ++rt) p1[rt][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(xa[cur][rt].re, hb[cur][ct][0], p1[rt][ct], 0, 0, 0);
-#pragma unroll
-          for (int rt = 0; rt < RT; ++rt) p2[rt][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(xa[cur][rt].im, hb[cur][ct][1], p2[rt][ct], 0, 0, 0);
-#pragma unroll
-          for (int rt = 0; rt < RT; ++rt) p3[rt][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(xs[rt], hb[cur][ct][2], p3[rt][ct], 0, 0, 0);
-        }
+        cdl_3m_step<RT, NCT>(xa[cur], hp[cur], hs[cur], p1, p2, p3);
         __builtin_amdgcn_sched_barrier(0);
       });
     }
-    // (xr + j xi)(hr + j hi):  Re = P1 - P2,  Im = P3 - P1 - P2  with  P1 = xr hr, P2 = xi hi, P3 = (xr + xi)(hr + hi)
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
@@ -176,7 +188,7 @@ __global__ __launch_bounds__(256, 2) void cdl_gemm_kernel(const CdlSeg* __restri
         for (int r = 0; r < 4; ++r) {
           const long long row = t0 + 16 * rt + kq + 4 * r;            // f64 MFMA C/D layout
           if (row < sg.r1)
-            sg.C[row + ldc * (long long)col] = mk((p1[rt][ct][r] - p2[rt][ct][r]) * scale, ((p3[rt][ct][r] - p1[rt][ct][r]) - p2[rt][ct][r]) * scale);
+            sg.C[row + ldc * (long long)col] = cdl_3m_out(p1[rt][ct], p2[rt][ct], p3[rt][ct], r) * scale;
         }
       }
   }
@@ -231,14 +243,13 @@ __global__ __launch_bounds__(256) void cdl_fir_kernel(const CdlSeg* __restrict__
   if (t < sg.o1) (UL ? sg.C : sg.Y)[t + ld_out * (long long)oc] = acc * scale;
 }
 
-// The same filters with FOUR consecutive outputs per thread (n_taps = 16, the model's filter length).  cdl_fir_kernel reads one 16-byte window sample from LDS
+// The downlink filter with FOUR consecutive outputs per thread (n_taps = 16, the model's filter length; Nt is unused).  cdl_fir_kernel reads one 16-byte window sample from LDS
 // per tap and output -- 16 x n_paths ds_read_b128 per output: at 13-23 paths the LDS pipe, not HBM, sets its time (the Z columns stream at 3.5 TB/s).  Here a
 // thread keeps the 19 window samples of its four outputs in registers (4.75 reads per output) and applies the taps from scalar registers; the additions of an
 // output run in the same order (terms ascending, taps ascending): same bits.  Measured (profiles/r04_negative_results.txt): 62.7 -> 58.7 us per launch mix --
 // the kernel turned out to be bound by its Z reads (with the tap arithmetic and the LDS reads REMOVED it still takes 90 of 95 us = 4.2 TB/s on Z that the
 // contraction has just written, 10 loads per thread in flight), not by LDS: kept for the 6 %, the downlink only.  One workgroup = 1024 consecutive outputs of one column; window index s lives at
 // s ^ ((s >> 4) & 3): with lane i reading sample 4 i + m every ds_read_b128 touches each bank once (plain layout: 16-way conflicts -- bank model of the guide).
-template <bool UL>
 __global__ __launch_bounds__(256) void cdl_fir4_kernel(const CdlSeg* __restrict__ segs, long long ld_in, long long ld_out, int Nt, int Nr, int n_paths,
                                                        const double* __restrict__ taps, const int* __restrict__ shift, double scale) {
   constexpr int NTAPS = 16, R = 4, W = 256 * R, WIN = W + 64;
@@ -247,16 +258,12 @@ __global__ __launch_bounds__(256) void cdl_fir4_kernel(const CdlSeg* __restrict_
   const long long t0 = sg.o0 + (long long)blockIdx.x * W;
   if (t0 >= sg.o1) return;                                            // (uniform)
   const int tid = threadIdx.x;
-  const int oc = blockIdx.y;                                          // DL: receive antenna u;  UL: filtered signal n Nt + s
-  const c64* in = UL ? sg.A : sg.C;
-  const int n_terms = UL ? 1 : n_paths;
+  const int oc = blockIdx.y;                                          // receive antenna u; term j = path j
   auto swz = [](int s_) { return s_ ^ ((s_ >> 4) & 3); };
-  auto term_n = [&](int j) { return UL ? oc / Nt : j; };
   // window of term j: rows base_j .. base_j + W + 14, base_j = t0 - shift - 15; thread tid fetches rows base_j + tid + 256 q (q = 0..3) and (tid < 15) row base_j + W + tid
   auto fetch = [&](int j, c64 (&v)[R + 1]) {
-    const int n = term_n(j);
-    const c64* col = in + ld_in * (long long)(UL ? oc % Nt : n * Nr + oc);
-    const long long base = t0 - shift[n] - (NTAPS - 1);
+    const c64* col = sg.C + ld_in * (long long)(j * Nr + oc);
+    const long long base = t0 - shift[j] - (NTAPS - 1);
 #pragma unroll
     for (int q = 0; q <= R; ++q) {
       const long long i = base + 256 * q + tid;
@@ -272,7 +279,7 @@ __global__ __launch_bounds__(256) void cdl_fir4_kernel(const CdlSeg* __restrict_
   // already waits: the filter then streams Z at the rate of the one-output kernel, 3.6 TB/s, whatever the LDS traffic)
   c64 vs[2][R + 1];
   fetch(0, vs[0]);
-  if (n_terms > 1) fetch(1, vs[1]);
+  if (n_paths > 1) fetch(1, vs[1]);
   auto term = [&](auto par_c, int j) __attribute__((always_inline)) {
     constexpr int PAR = decltype(par_c)::value;
     c64 (&v)[R + 1] = vs[PAR];
@@ -280,9 +287,9 @@ __global__ __launch_bounds__(256) void cdl_fir4_kernel(const CdlSeg* __restrict_
 #pragma unroll
     for (int q = 0; q < R; ++q) w[swz(tid + 256 * q)] = v[q];
     if (tid < NTAPS - 1) w[swz(W + tid)] = v[R];
-    if (j + 2 < n_terms) fetch(j + 2, v);
+    if (j + 2 < n_paths) fetch(j + 2, v);
     __syncthreads();                                                  // (one barrier per term: this buffer was last read two terms ago)
-    const double* g = taps + term_n(j) * NTAPS;
+    const double* g = taps + j * NTAPS;
     c64 x[NTAPS + R - 1];
 #pragma unroll
     for (int m = 0; m < NTAPS + R - 1; ++m) x[m] = w[swz(R * tid + m)];
@@ -295,11 +302,11 @@ __global__ __launch_bounds__(256) void cdl_fir4_kernel(const CdlSeg* __restrict_
         acc[r].im = ::fma(g[k], x[r + NTAPS - 1 - k].im, acc[r].im);
       }
   };
-  for (int j = 0; j < n_terms; j += 2) {
+  for (int j = 0; j < n_paths; j += 2) {
     term(std::integral_constant<int, 0>{}, j);
-    if (j + 1 < n_terms) term(std::integral_constant<int, 1>{}, j + 1);
+    if (j + 1 < n_paths) term(std::integral_constant<int, 1>{}, j + 1);
   }
-  c64* out = (UL ? sg.C : sg.Y) + ld_out * (long long)oc;
+  c64* out = sg.Y + ld_out * (long long)oc;
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     const long long t = t0 + R * tid + r;
@@ -340,6 +347,25 @@ __device__ __forceinline__ void lds_barrier() {
 // rows are XOR-swizzled inside aligned groups of eight: the 16 lanes of a filter task column read rows 8 g + m -- (g & 1, (g >> 1) ^ m) is a different bank quad for every g
 __device__ __forceinline__ int fz_swz(int p) { return p ^ ((p >> 4) & 7); }
 
+// The 16-tap filter of a fused kernel's task (one component of rows 8 fg .. 8 fg + 7 of a column): a[r] = sum_k g[k] w[ORG + r - k] -- taps from LDS, the window in
+// registers, eight independent FMA chains -- stored to the task's rows of the fbuf column `fo` (XOR swizzle of fz_swz: the rows stay inside their aligned group of eight).
+template <int ORG, int NW>
+__device__ __forceinline__ void cdl_filter8(const double* tp, const double (&w)[NW], double* fo, int fg) {
+  double gk[kFzTaps];
+#pragma unroll
+  for (int k = 0; k < kFzTaps; ++k) gk[k] = tp[k];
+  double a[8];
+#pragma unroll
+  for (int r = 0; r < 8; ++r) a[r] = 0.0;
+#pragma unroll
+  for (int k = 0; k < kFzTaps; ++k)
+#pragma unroll
+    for (int r = 0; r < 8; ++r) a[r] = ::fma(gk[k], w[ORG + r - k], a[r]);
+  const int po = 8 * fg, xo = (po >> 4) & 7;
+#pragma unroll
+  for (int r = 0; r < 8; ++r) fo[2 * (po + (r ^ xo))] = a[r];
+}
+
 template <int NCT, int NSLOT>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void cdl_fused_kernel(const CdlSeg* __restrict__ segs, const CdlWork* __restrict__ works, const int* __restrict__ wg_first, long long lda, long long ldy, int Nt,
@@ -370,11 +396,8 @@ void cdl_fused_kernel(const CdlSeg* __restrict__ segs, const CdlWork* __restrict
     const __amdgpu_buffer_rsrc_t rs_y = buffer_of(sg.Y, (unsigned)(ldy * Nr * (long long)sizeof(c64)));
     lds_barrier();                                                           // the previous item's last reads of the image are done
     for (int i = tid; i < KS * NCT * 64; i += 512) {
-      const int ks = i / (NCT * 64), ct = (i >> 6) % NCT, ln = i & 63;
-      const int k = 4 * ks + (ln >> 4), col = 16 * ct + (ln & 15);
-      const bool ok = k < Nt && col < Nc;
-      const int kk = ok ? k : 0, cc = ok ? col : 0;
-      const c64 h = sg.H[((long long)(cc / Nr) * Nt + kk) * Nr + (cc % Nr)];   // unconditional load, select afterwards
+      bool ok;
+      const c64 h = cdl_b_entry<false>(sg.H, i, NCT, 0, 0, Nt, Nc, Nt, Nr, ok);
       bpair[i] = ok ? h : mk(0.0, 0.0);
       bsum[i] = ok ? h.re + h.im : 0.0;
     }
@@ -409,26 +432,20 @@ void cdl_fused_kernel(const CdlSeg* __restrict__ segs, const CdlWork* __restrict
       const long long row0 = sg.r0 + (long long)tile * kFzRows;
       ro_nxt = row_off(row0 + kFzRows);
       // ---- 1. contraction: 16 k-steps x (NCT column tiles x 3 forms) MFMAs on this wave's 16 rows
-      v4f64 p1[NCT], p2[NCT], p3[NCT];
+      v4f64 p1[1][NCT], p2[1][NCT], p3[1][NCT];
 #pragma unroll
-      for (int ct = 0; ct < NCT; ++ct) p1[ct] = p2[ct] = p3[ct] = v4f64{0.0, 0.0, 0.0, 0.0};
+      for (int ct = 0; ct < NCT; ++ct) p1[0][ct] = p2[0][ct] = p3[0][ct] = v4f64{0.0, 0.0, 0.0, 0.0};
       c64 hp[2][NCT];
       double hs[2][NCT];
       load_b(0, hp[0], hs[0]);
       static_for<0, KS>([&](auto ksc) {
         constexpr int ks = decltype(ksc)::value, cur = ks & 1, sl = ks % kFzPf;
-        const double xr = xq[sl].re, xi = xq[sl].im;
+        const c64 x[1] = {xq[sl]};
         if constexpr (ks + kFzPf < KS) xq[sl] = load_a(ro_cur, ks + kFzPf);
         else xq[sl] = load_a(ro_nxt, ks + kFzPf - KS);
         if constexpr (ks + 1 < KS) load_b(ks + 1, hp[cur ^ 1], hs[cur ^ 1]);
         __builtin_amdgcn_sched_barrier(0);
-        const double xs = xr + xi;
-#pragma unroll
-        for (int ct = 0; ct < NCT; ++ct) {
-          p1[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(xr, hp[cur][ct].re, p1[ct], 0, 0, 0);
-          p2[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(xi, hp[cur][ct].im, p2[ct], 0, 0, 0);
-          p3[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(xs, hs[cur][ct], p3[ct], 0, 0, 0);
-        }
+        cdl_3m_step<1, NCT>(x, hp[cur], hs[cur], p1, p2, p3);
         __builtin_amdgcn_sched_barrier(0);
       });
       ro_cur = ro_nxt;
@@ -439,7 +456,7 @@ void cdl_fused_kernel(const CdlSeg* __restrict__ segs, const CdlWork* __restrict
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int p = kFzHist + 16 * wid + kq + 4 * r;
-          zbuf[li * kFzLd + fz_swz(p)] = mk(p1[ct][r] - p2[ct][r], (p3[ct][r] - p1[ct][r]) - p2[ct][r]);
+          zbuf[li * kFzLd + fz_swz(p)] = cdl_3m_out(p1[0][ct], p2[0][ct], p3[0][ct], r);
         }
         if (tid < 256) zbuf[(tid >> 4) * kFzLd + fz_swz(tid & 15)] = hk[ct];
         lds_barrier();
@@ -455,21 +472,8 @@ void cdl_fused_kernel(const CdlSeg* __restrict__ segs, const CdlWork* __restrict
               if (8 * j + i > 0) w[8 * j + i] = zc[2 * (p + (i ^ x))];
           }
           if (tid < 256) hk[ct] = zbuf[(tid >> 4) * kFzLd + fz_swz(kFzRows + (tid & 15))];   // the tile's last 16 rows: the next tile's history
-          const double* tp = s_taps + (ct * kFzPpt + (fc >> 1)) * kFzTaps;
-          double gk[kFzTaps];
-#pragma unroll
-          for (int k = 0; k < kFzTaps; ++k) gk[k] = tp[k];
-          double a[8];
-#pragma unroll
-          for (int r = 0; r < 8; ++r) a[r] = 0.0;
-#pragma unroll
-          for (int k = 0; k < kFzTaps; ++k)                                  // f[t] = sum_k g[k] z[t - k]: row 8 fg + r - k  <->  w[16 + r - k]
-#pragma unroll
-            for (int r = 0; r < 8; ++r) a[r] = ::fma(gk[k], w[16 + r - k], a[r]);
-          double* fo = fwr + 2 * (fc * kFzLdF);
-          const int po = 8 * fg, xo = (po >> 4) & 7;
-#pragma unroll
-          for (int r = 0; r < 8; ++r) fo[2 * (po + (r ^ xo))] = a[r];         // (the previous tile's gather of fbuf lies in front of the barrier above)
+          // f[t] = sum_k g[k] z[t - k]: row 8 fg + r - k  <->  w[16 + r - k]  (the previous tile's gather of fbuf lies in front of the barrier above)
+          cdl_filter8<16>(s_taps + (ct * kFzPpt + (fc >> 1)) * kFzTaps, w, fwr + 2 * (fc * kFzLdF), fg);
         }
         lds_barrier();
         // ---- 4. integer delays: for every path of this column tile, the one row of the tile that lands on a row = rho (mod 128)
@@ -619,11 +623,8 @@ void cdl_fused_ul_kernel(const CdlSeg* __restrict__ segs, const CdlWork* __restr
     const __amdgpu_buffer_rsrc_t rs_y = buffer_of(sg.Y, (unsigned)(ldy * Nr * (long long)sizeof(c64)));
     lds_barrier();                                                           // the previous item's last reads of the image are done
     for (int i = tid; i < KS * NCT * 64; i += 512) {
-      const int ks = i / (NCT * 64), ct = (i >> 6) % NCT, ln = i & 63;
-      const int k = 4 * ks + (ln >> 4), col = 16 * ct + (ln & 15);          // contraction index k = 2 n + s
-      const bool ok = k < Nt * n_paths && col < Nc;
-      const int kk = ok ? k : 0, cc = ok ? col : 0;
-      const c64 h = sg.H[((long long)(kk >> 1) * Nt + (kk & 1)) * Nr + cc];  // unconditional load, select afterwards
+      bool ok;
+      const c64 h = cdl_b_entry<true>(sg.H, i, NCT, 0, 0, Nt * n_paths, Nc, Nt, Nr, ok);   // contraction index k = 2 n + s
       bpair[i] = ok ? h : mk(0.0, 0.0);
       bsum[i] = ok ? h.re + h.im : 0.0;
     }
@@ -638,9 +639,9 @@ void cdl_fused_ul_kernel(const CdlSeg* __restrict__ segs, const CdlWork* __restr
         const c64 v = buffer_load_c64(rs_x, (unsigned)((rc + ldx * s_) * (long long)sizeof(c64)));
         xwin[(s_ * 8 + (r & 7)) * xs_pitch + (r >> 3)] = (row >= 0 && row < ldx) ? v : mk(0.0, 0.0);
       }
-      v4f64 p1[NCT], p2[NCT], p3[NCT];
+      v4f64 p1[1][NCT], p2[1][NCT], p3[1][NCT];
 #pragma unroll
-      for (int ct = 0; ct < NCT; ++ct) p1[ct] = p2[ct] = p3[ct] = v4f64{0.0, 0.0, 0.0, 0.0};
+      for (int ct = 0; ct < NCT; ++ct) p1[0][ct] = p2[0][ct] = p3[0][ct] = v4f64{0.0, 0.0, 0.0, 0.0};
       lds_barrier();
       for (int ch = 0; ch < n_chunks; ++ch) {
         // ---- 2a. XF of this chunk's 16 contraction columns: the wave's path n = 8 ch + wid (both transmit elements), 23 window samples of one component in registers
@@ -655,30 +656,17 @@ void cdl_fused_ul_kernel(const CdlSeg* __restrict__ segs, const CdlWork* __restr
             const int r = base + j;                                          // (scalar) row of task 0; task fg reads row r + 8 fg: phase r & 7, entry (r >> 3) + fg
             w[j] = xc[2 * ((r & 7) * xs_pitch + (r >> 3))];
           }
-          const double* tp = s_taps + (ch * kFzPpt + wid) * kFzTaps;
-          double gk[kFzTaps];
-#pragma unroll
-          for (int k = 0; k < kFzTaps; ++k) gk[k] = n < n_paths ? tp[k] : 0.0;
-          double a[8];
-#pragma unroll
-          for (int r = 0; r < 8; ++r) a[r] = 0.0;
-#pragma unroll
-          for (int k = 0; k < kFzTaps; ++k)                                  // XF[t] = sum_k g[k] x[t - d - k]: row 8 fg + r - d - k  <->  w[15 + r - k]
-#pragma unroll
-            for (int r = 0; r < 8; ++r) a[r] = ::fma(gk[k], w[15 + r - k], a[r]);
-          double* fo = reinterpret_cast<double*>(fbuf) + part + 2 * (fc * kFzLdF);
-          const int po = 8 * fg, xo = (po >> 4) & 7;
-#pragma unroll
-          for (int r = 0; r < 8; ++r) fo[2 * (po + (r ^ xo))] = a[r];
+          // XF[t] = sum_k g[k] x[t - d - k]: row 8 fg + r - d - k  <->  w[15 + r - k]  (the taps of a path beyond n_paths are zero in s_taps)
+          cdl_filter8<15>(s_taps + n * kFzTaps, w, reinterpret_cast<double*>(fbuf) + part + 2 * (fc * kFzLdF), fg);
         }
         lds_barrier();
         // ---- 2b. four k-steps of the contraction: A operands from the XF tile (lane (li, kq): row 16 wid + li, column 4 ksl + kq), B from the image
         {
           const c64* ap = fbuf + fz_swz(16 * wid + li);
-          c64 xa[2], hp[2][NCT];
+          c64 xa[2][1], hp[2][NCT];
           double hs[2][NCT];
-          auto load_ops = [&](int ksl, c64& x, c64 (&h)[NCT], double (&hsv)[NCT]) {
-            x = ap[(4 * ksl + kq) * kFzLdF];
+          auto load_ops = [&](int ksl, c64 (&x)[1], c64 (&h)[NCT], double (&hsv)[NCT]) {
+            x[0] = ap[(4 * ksl + kq) * kFzLdF];
             const int ks = ch * KSC + ksl;
 #pragma unroll
             for (int ct = 0; ct < NCT; ++ct) { h[ct] = bpair[(ks * NCT + ct) * 64 + lane]; hsv[ct] = bsum[(ks * NCT + ct) * 64 + lane]; }
@@ -688,13 +676,7 @@ void cdl_fused_ul_kernel(const CdlSeg* __restrict__ segs, const CdlWork* __restr
             constexpr int ksl = decltype(kc)::value, cur = ksl & 1;
             if constexpr (ksl + 1 < KSC) load_ops(ksl + 1, xa[cur ^ 1], hp[cur ^ 1], hs[cur ^ 1]);
             __builtin_amdgcn_sched_barrier(0);
-            const double xr = xa[cur].re, xi = xa[cur].im, xs = xr + xi;
-#pragma unroll
-            for (int ct = 0; ct < NCT; ++ct) {
-              p1[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(xr, hp[cur][ct].re, p1[ct], 0, 0, 0);
-              p2[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(xi, hp[cur][ct].im, p2[ct], 0, 0, 0);
-              p3[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(xs, hs[cur][ct], p3[ct], 0, 0, 0);
-            }
+            cdl_3m_step<1, NCT>(xa[cur], hp[cur], hs[cur], p1, p2, p3);
             __builtin_amdgcn_sched_barrier(0);
           });
         }
@@ -709,7 +691,7 @@ void cdl_fused_ul_kernel(const CdlSeg* __restrict__ segs, const CdlWork* __restr
           const long long row = t0 + 16 * wid + kq + 4 * r;
           const bool st = col < Nc && row < sg.o1;
           const unsigned off = st ? (unsigned)((row + ldy * (long long)col) * (long long)sizeof(c64)) : 0xfffffff0u;
-          buffer_store_c64_nt(rs_y, off, mk((p1[ct][r] - p2[ct][r]) * scale, ((p3[ct][r] - p1[ct][r]) - p2[ct][r]) * scale));
+          buffer_store_c64_nt(rs_y, off, cdl_3m_out(p1[0][ct], p2[0][ct], p3[0][ct], r) * scale);
         }
       }
     }
@@ -770,6 +752,14 @@ using namespace isac;
 
 namespace {
 
+// f(integral_constant<int, v>) for 1 <= v <= MAXV (larger values take MAXV): the kernels' column-tile template parameter from the run-time count
+template <int MAXV, class F>
+int cdl_dispatch(int v, F&& f) {
+  if constexpr (MAXV > 1)
+    if (v < MAXV) return cdl_dispatch<MAXV - 1>(v, f);
+  return f(std::integral_constant<int, MAXV>{});
+}
+
 template <bool UL>
 int launch_gemm(isac_ctx* ctx, const CdlSeg* d_segs, int n_segs, long long max_rows, long long lda, long long ldc, int Nt, int Nr, int K, int Nc, double scale) {
   const int tiles = (Nc + 15) / 16, groups = (tiles + kCdlMaxColTiles - 1) / kCdlMaxColTiles, nct = (tiles + groups - 1) / groups;
@@ -785,23 +775,22 @@ int launch_gemm(isac_ctx* ctx, const CdlSeg* d_segs, int n_segs, long long max_r
   const long long n_tiles = cdiv(max_rows, rows_wg) * (long long)groups * n_segs;
   const int tpw = (int)std::min<long long>(kCdlMaxTilesPerWg, std::max<long long>(1, n_tiles / 8192));
   const dim3 grid((unsigned)cdiv(max_rows, rows_wg * tpw), (unsigned)groups, (unsigned)n_segs), block(256);
-#define ISAC_CDL_GEMM(NCT)                                                                                                   \
-  do {                                                                                                                       \
-    auto kern = cdl_gemm_kernel<NCT, UL>;                                                                                     \
-    ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(kern), img_bytes));                                                \
-    hipLaunchKernelGGL(kern, grid, block, img_bytes, ctx->stream, d_segs, (const c64*)ctx->stage_a.p, lda, ldc, K, Nc, scale, tpw, n_segs); \
-  } while (0)
-  switch (nct) { case 1: ISAC_CDL_GEMM(1); break; case 2: ISAC_CDL_GEMM(2); break; default: ISAC_CDL_GEMM(3); break; }
-#undef ISAC_CDL_GEMM
+  ISAC_TRY(cdl_dispatch<kCdlMaxColTiles>(nct, [&](auto nct_c) -> int {
+    auto kern = cdl_gemm_kernel<decltype(nct_c)::value, UL>;
+    ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(kern), img_bytes));
+    hipLaunchKernelGGL(kern, grid, block, img_bytes, ctx->stream, d_segs, (const c64*)ctx->stage_a.p, lda, ldc, K, Nc, scale, tpw, n_segs);
+    return ISAC_OK;
+  }));
   ISAC_HIP(hipGetLastError());
   return ISAC_OK;
 }
 
-// Fused downlink apply: does the shape fit the kernel's envelope?  (Everything else -- uplink, more than 64 transmit elements, more than two receive
-// antennas (or one), more than 24 paths, filters longer than 16 taps, delays beyond 895 samples -- takes the unfused kernels.)
-bool cdl_fused_ok(long long T, int Nt, int Nr, int n_paths, int n_taps, int max_shift) {
-  static const bool off = std::getenv("ISAC_CDL_UNFUSED") != nullptr;        // test hook: contraction + filter as separate launches (Z through HBM)
-  return !off && Nr == 2 && Nt >= 2 && Nt <= 64 && n_paths <= 3 * kFzPpt && n_taps <= kFzTaps && max_shift < 128 * 7 && (long long)T * Nr < (1ll << 28);
+// Do the shapes fit the fused kernels' envelopes?  Downlink: 2..64 transmit elements onto two receive antennas, delays below 896 samples; uplink: two transmit
+// elements into an array of up to 64, delays that keep the x window within LDS; both: <= 24 paths, <= 16 taps.  Everything else takes the unfused kernels.
+bool cdl_fused_ok(bool ul, long long T, int Nt, int Nr, int n_paths, int n_taps, int max_shift) {
+  static const bool off = std::getenv("ISAC_CDL_UNFUSED") != nullptr;        // test hook: contraction + filter as separate launches (Z / XF through HBM)
+  if (off || n_paths > 3 * kFzPpt || n_taps > kFzTaps || (long long)T * Nr >= (1ll << 28)) return false;
+  return ul ? Nt == 2 && Nr > Nt && Nr <= 64 && max_shift + kFzTaps <= 896 : Nr == 2 && Nt >= 2 && Nt <= 64 && max_shift < 128 * 7;
 }
 
 // The tile sequence of all segments cut into one contiguous range per workgroup; a range that starts inside a segment walks `warm` warm-up tiles first.
@@ -823,12 +812,37 @@ void cdl_work_list(const std::vector<long long>& seg_tiles, long long total, int
   wg_first[n_wg] = (int)works.size();
 }
 
+// What both fused launches need: the persistent grid (one workgroup per CU, or ISAC_CDL_FUSED_WGS) with its work list over the 128-row tiles of the segments' rows
+// [r0, r1) (the uplink's segments have r0 = o0, r1 = o1), and the staged table  segments | taps padded to 16 | work items | ranges  (the caller adds its own tables and uploads).  n_wg = 0: nothing to do.
+struct CdlGrid {
+  int n_wg = 0;
+  MetaPack meta;
+  size_t o_seg = 0, o_tap = 0, o_wk = 0, o_wf = 0;
+};
+int cdl_persistent_grid(isac_ctx* ctx, const std::vector<CdlSeg>& segs, int warm, int n_paths, const double* taps, int n_taps, CdlGrid& g) {
+  std::vector<long long> seg_tiles(segs.size());
+  long long total = 0;
+  for (size_t i = 0; i < segs.size(); ++i) { seg_tiles[i] = segs[i].o1 > segs[i].o0 ? (segs[i].r1 - segs[i].r0 + kFzRows - 1) / kFzRows : 0; total += seg_tiles[i]; }
+  if (total == 0) return ISAC_OK;
+  static const int wgs_env = std::getenv("ISAC_CDL_FUSED_WGS") ? std::atoi(std::getenv("ISAC_CDL_FUSED_WGS")) : 0;   // test hook: workgroups of the persistent grid
+  int n_cus = 0;
+  ISAC_TRY(ctx_n_cus(ctx, &n_cus));
+  g.n_wg = (int)std::min<long long>(wgs_env > 0 ? wgs_env : n_cus, total);
+  std::vector<CdlWork> works;
+  std::vector<int> wg_first;
+  cdl_work_list(seg_tiles, total, g.n_wg, warm, works, wg_first);
+  std::vector<double> taps16((size_t)n_paths * kFzTaps, 0.0);
+  for (int n = 0; n < n_paths; ++n) std::memcpy(&taps16[(size_t)n * kFzTaps], taps + (size_t)n * n_taps, sizeof(double) * (size_t)n_taps);
+  g.o_seg = g.meta.add(segs);
+  g.o_tap = g.meta.add(taps16);
+  g.o_wk = g.meta.add(works);
+  g.o_wf = g.meta.add(wg_first);
+  return ISAC_OK;
+}
+
 int launch_fused(isac_ctx* ctx, const std::vector<CdlSeg>& segs, long long T, int Nt, int Nr, int n_paths, const double* taps, int n_taps, const int32_t* shift,
                  int max_shift, double out_scale) {
   const int Nc = n_paths * Nr, nct = (Nc + 15) / 16, nslot = max_shift < 128 * 3 ? 4 : 8;
-  // ---- tables: taps padded to 16, paths in delay order, first entry of every 128-sample delay class
-  std::vector<double> taps16((size_t)n_paths * kFzTaps, 0.0);
-  for (int n = 0; n < n_paths; ++n) std::memcpy(&taps16[(size_t)n * kFzTaps], taps + (size_t)n * n_taps, sizeof(double) * (size_t)n_taps);
   // delay table: per 16-column tile its (up to 8) paths in delay order, packed  local path | (delay & 127) << 8 | (delay >> 7) << 16 | valid << 24
   std::vector<int> pmeta((size_t)nct * kFzPpt, 0);
   for (int ct = 0; ct < nct; ++ct) {
@@ -838,107 +852,48 @@ int launch_fused(isac_ctx* ctx, const std::vector<CdlSeg>& segs, long long T, in
     std::stable_sort(order.begin(), order.end(), [&](int a_, int b_) { return shift[a_] < shift[b_]; });
     for (size_t e = 0; e < order.size(); ++e) pmeta[(size_t)ct * kFzPpt + e] = (order[e] - lo) | ((shift[order[e]] & 127) << 8) | ((shift[order[e]] >> 7) << 16) | (1 << 24);
   }
-  // ---- work list: the tile sequence of all segments cut into one contiguous range per workgroup; a range that starts inside a segment walks W warm-up tiles first
-  if (ctx->n_cus <= 0) {
-    int v = 0;
-    ISAC_HIP(hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, ctx->device));
-    ctx->n_cus = v > 0 ? v : 256;
-  }
-  const int warm = (max_shift + (kFzTaps - 1) + kFzRows - 1) / kFzRows;
-  std::vector<long long> seg_tiles(segs.size());
-  long long total = 0;
-  for (size_t i = 0; i < segs.size(); ++i) { seg_tiles[i] = segs[i].o1 > segs[i].o0 ? (segs[i].r1 - segs[i].r0 + kFzRows - 1) / kFzRows : 0; total += seg_tiles[i]; }
-  if (total == 0) return ISAC_OK;
-  static const int wgs_env = std::getenv("ISAC_CDL_FUSED_WGS") ? std::atoi(std::getenv("ISAC_CDL_FUSED_WGS")) : 0;   // test hook: workgroups of the persistent grid
-  const int n_wg = (int)std::min<long long>(wgs_env > 0 ? wgs_env : ctx->n_cus, total);
-  std::vector<CdlWork> works;
-  std::vector<int> wg_first;
-  cdl_work_list(seg_tiles, total, n_wg, warm, works, wg_first);
-  // ---- one upload: segments | taps | delay table | class starts | work items | ranges
-  auto pad = [](size_t b) { return (b + 63) & ~(size_t)63; };
-  const size_t o_seg = 0, o_tap = o_seg + pad(sizeof(CdlSeg) * segs.size()), o_pm = o_tap + pad(sizeof(double) * taps16.size()), o_wk = o_pm + pad(sizeof(int) * pmeta.size()),
-               o_wf = o_wk + pad(sizeof(CdlWork) * works.size()), meta = o_wf + pad(sizeof(int) * wg_first.size());
-  std::vector<char> host(meta);
-  std::memcpy(host.data() + o_seg, segs.data(), sizeof(CdlSeg) * segs.size());
-  std::memcpy(host.data() + o_tap, taps16.data(), sizeof(double) * taps16.size());
-  std::memcpy(host.data() + o_pm, pmeta.data(), sizeof(int) * pmeta.size());
-  std::memcpy(host.data() + o_wk, works.data(), sizeof(CdlWork) * works.size());
-  std::memcpy(host.data() + o_wf, wg_first.data(), sizeof(int) * wg_first.size());
-  ISAC_TRY(ensure(ctx, ctx->stage_c, meta + 64));
-  char* dm = (char*)ctx->stage_c.p;
-  ISAC_TRY(stage_upload(ctx, dm, host.data(), meta));
+  CdlGrid g;
+  ISAC_TRY(cdl_persistent_grid(ctx, segs, (max_shift + (kFzTaps - 1) + kFzRows - 1) / kFzRows, n_paths, taps, n_taps, g));
+  if (g.n_wg == 0) return ISAC_OK;
+  const size_t o_pm = g.meta.add(pmeta);
+  ISAC_TRY(g.meta.upload(ctx, ctx->stage_c));
+  const char* dm = (const char*)ctx->stage_c.p;
   const size_t lds_bytes = sizeof(c64) * 16 * (size_t)(kFzLd + kFzLdF) + sizeof(double) * 16 * (size_t)nct * 3 * 64 + sizeof(double) * (size_t)nct * kFzPpt * kFzTaps;
-  if (ctx->profile) ISAC_HIP(hipEventRecord(ctx->ev_k0, ctx->stream));       // isac_profile_*: brackets exactly the fused launch
-#define ISAC_CDL_FUSED(NCT, NSLOT)                                                                                                                          \
-  do {                                                                                                                                                      \
-    auto kern = cdl_fused_kernel<NCT, NSLOT>;                                                                                                               \
-    ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(kern), lds_bytes));                                                                               \
-    hipLaunchKernelGGL(kern, dim3((unsigned)n_wg), dim3(512), lds_bytes, ctx->stream, (const CdlSeg*)(dm + o_seg), (const CdlWork*)(dm + o_wk),            \
-                       (const int*)(dm + o_wf), (long long)T, (long long)T, Nt, n_paths, (const double*)(dm + o_tap), (const int*)(dm + o_pm), out_scale);   \
-  } while (0)
-  if (nslot == 4) { switch (nct) { case 1: ISAC_CDL_FUSED(1, 4); break; case 2: ISAC_CDL_FUSED(2, 4); break; default: ISAC_CDL_FUSED(3, 4); break; } }
-  else { switch (nct) { case 1: ISAC_CDL_FUSED(1, 8); break; case 2: ISAC_CDL_FUSED(2, 8); break; default: ISAC_CDL_FUSED(3, 8); break; } }
-#undef ISAC_CDL_FUSED
+  auto launch = [&](auto kern) -> int {
+    ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(kern), lds_bytes));
+    hipLaunchKernelGGL(kern, dim3((unsigned)g.n_wg), dim3(512), lds_bytes, ctx->stream, (const CdlSeg*)(dm + g.o_seg), (const CdlWork*)(dm + g.o_wk),
+                       (const int*)(dm + g.o_wf), (long long)T, (long long)T, Nt, n_paths, (const double*)(dm + g.o_tap), (const int*)(dm + o_pm), out_scale);
+    return ISAC_OK;
+  };
+  ISAC_TRY(profile_begin(ctx));                                              // isac_profile_*: brackets exactly the fused launch
+  ISAC_TRY(cdl_dispatch<3>(nct, [&](auto c) -> int { return nslot == 4 ? launch(cdl_fused_kernel<decltype(c)::value, 4>) : launch(cdl_fused_kernel<decltype(c)::value, 8>); }));
   ISAC_HIP(hipGetLastError());
-  if (ctx->profile) { ISAC_HIP(hipEventRecord(ctx->ev_k1, ctx->stream)); ctx->profile_recorded = true; }
-  return ISAC_OK;
-}
-
-// Fused uplink apply: two transmit elements into an array of up to 64 elements, <= 24 paths, <= 16 taps, delays that keep the x window within LDS.
-bool cdl_fused_ul_ok(long long T, int Nt, int Nr, int n_paths, int n_taps, int max_shift) {
-  static const bool off = std::getenv("ISAC_CDL_UNFUSED") != nullptr;        // test hook (as above)
-  return !off && Nt == 2 && Nr > Nt && Nr <= 64 && n_paths <= 3 * kFzPpt && n_taps <= kFzTaps && max_shift + kFzTaps <= 896 && (long long)T * Nr < (1ll << 28);
+  return profile_end(ctx);
 }
 
 int launch_fused_ul(isac_ctx* ctx, const std::vector<CdlSeg>& segs, long long T, int Nr, int n_paths, const double* taps, int n_taps, const int32_t* shift, int max_shift,
                     double out_scale) {
   const int nct = (Nr + 15) / 16, n_chunks = (n_paths + kFzPpt - 1) / kFzPpt, KS = 4 * n_chunks;
   const int hist = (max_shift + (kFzTaps - 1) + 7) / 8 * 8;
-  std::vector<double> taps16((size_t)n_paths * kFzTaps, 0.0);
-  for (int n = 0; n < n_paths; ++n) std::memcpy(&taps16[(size_t)n * kFzTaps], taps + (size_t)n * n_taps, sizeof(double) * (size_t)n_taps);
-  if (ctx->n_cus <= 0) {
-    int v = 0;
-    ISAC_HIP(hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, ctx->device));
-    ctx->n_cus = v > 0 ? v : 256;
-  }
-  std::vector<long long> seg_tiles(segs.size());
-  long long total = 0;
-  for (size_t i = 0; i < segs.size(); ++i) { seg_tiles[i] = segs[i].o1 > segs[i].o0 ? (segs[i].o1 - segs[i].o0 + kFzRows - 1) / kFzRows : 0; total += seg_tiles[i]; }
-  if (total == 0) return ISAC_OK;
-  static const int wgs_env = std::getenv("ISAC_CDL_FUSED_WGS") ? std::atoi(std::getenv("ISAC_CDL_FUSED_WGS")) : 0;   // test hook (as above)
-  const int n_wg = (int)std::min<long long>(wgs_env > 0 ? wgs_env : ctx->n_cus, total);
-  std::vector<CdlWork> works;
-  std::vector<int> wg_first;
-  cdl_work_list(seg_tiles, total, n_wg, 0, works, wg_first);                 // tiles are independent: no warm-up
-  auto pad = [](size_t b) { return (b + 63) & ~(size_t)63; };
-  const size_t o_seg = 0, o_tap = o_seg + pad(sizeof(CdlSeg) * segs.size()), o_sh = o_tap + pad(sizeof(double) * taps16.size()), o_wk = o_sh + pad(sizeof(int) * (size_t)n_paths),
-               o_wf = o_wk + pad(sizeof(CdlWork) * works.size()), meta = o_wf + pad(sizeof(int) * wg_first.size());
-  std::vector<char> host(meta);
-  std::memcpy(host.data() + o_seg, segs.data(), sizeof(CdlSeg) * segs.size());
-  std::memcpy(host.data() + o_tap, taps16.data(), sizeof(double) * taps16.size());
-  std::memcpy(host.data() + o_sh, shift, sizeof(int) * (size_t)n_paths);
-  std::memcpy(host.data() + o_wk, works.data(), sizeof(CdlWork) * works.size());
-  std::memcpy(host.data() + o_wf, wg_first.data(), sizeof(int) * wg_first.size());
-  ISAC_TRY(ensure(ctx, ctx->stage_c, meta + 64));
-  char* dm = (char*)ctx->stage_c.p;
-  ISAC_TRY(stage_upload(ctx, dm, host.data(), meta));
+  CdlGrid g;
+  ISAC_TRY(cdl_persistent_grid(ctx, segs, 0, n_paths, taps, n_taps, g));     // tiles are independent: no warm-up
+  if (g.n_wg == 0) return ISAC_OK;
+  const size_t o_sh = g.meta.add(shift, sizeof(int) * (size_t)n_paths);
+  ISAC_TRY(g.meta.upload(ctx, ctx->stage_c));
+  const char* dm = (const char*)ctx->stage_c.p;
   const int xs_len = (hist + kFzRows) / 8 + 1, xs_pitch = (xs_len + 15) / 16 * 16 + 1;
   const size_t lds_bytes = sizeof(c64) * (16 * (size_t)kFzLdF + (size_t)KS * nct * 64 + 2 * 8 * (size_t)xs_pitch) + sizeof(double) * ((size_t)KS * nct * 64 + (size_t)n_chunks * kFzPpt * kFzTaps);
-  if (ctx->profile) ISAC_HIP(hipEventRecord(ctx->ev_k0, ctx->stream));
-#define ISAC_CDL_FUSED_UL(NCT)                                                                                                                                     \
-  do {                                                                                                                                                             \
-    auto kern = cdl_fused_ul_kernel<NCT>;                                                                                                                          \
-    ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(kern), lds_bytes));                                                                                      \
-    hipLaunchKernelGGL(kern, dim3((unsigned)n_wg), dim3(512), lds_bytes, ctx->stream, (const CdlSeg*)(dm + o_seg), (const CdlWork*)(dm + o_wk), (const int*)(dm + o_wf), \
-                       (long long)T, (long long)T, Nr, n_paths, (const double*)(dm + o_tap), (const int*)(dm + o_sh), hist, out_scale);                            \
-  } while (0)
-  switch (nct) { case 1: ISAC_CDL_FUSED_UL(1); break; case 2: ISAC_CDL_FUSED_UL(2); break; case 3: ISAC_CDL_FUSED_UL(3); break; default: ISAC_CDL_FUSED_UL(4); break; }
-#undef ISAC_CDL_FUSED_UL
+  ISAC_TRY(profile_begin(ctx));
+  ISAC_TRY(cdl_dispatch<4>(nct, [&](auto c) -> int {
+    auto kern = cdl_fused_ul_kernel<decltype(c)::value>;
+    ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(kern), lds_bytes));
+    hipLaunchKernelGGL(kern, dim3((unsigned)g.n_wg), dim3(512), lds_bytes, ctx->stream, (const CdlSeg*)(dm + g.o_seg), (const CdlWork*)(dm + g.o_wk), (const int*)(dm + g.o_wf),
+                       (long long)T, (long long)T, Nr, n_paths, (const double*)(dm + g.o_tap), (const int*)(dm + o_sh), hist, out_scale);
+    return ISAC_OK;
+  }));
   ISAC_HIP(hipGetLastError());
-  if (ctx->profile) { ISAC_HIP(hipEventRecord(ctx->ev_k1, ctx->stream)); ctx->profile_recorded = true; }
-  return ISAC_OK;
+  return profile_end(ctx);
 }
-
 
 int cdl_apply_jobs(isac_ctx* ctx, const isac_cdl_job* jobs, int n_jobs, long long T, int Nt, int Nr, int n_paths, const double* taps, int n_taps,
                    const int32_t* shift, double out_scale) {
@@ -968,7 +923,7 @@ int cdl_apply_jobs(isac_ctx* ctx, const isac_cdl_job* jobs, int n_jobs, long lon
   if (ul && cdl_os_ul_ok(T, Nt, Nr, n_paths, n_taps, max_shift))    // long uplink waveforms: the same overlap-save form, one workgroup per (job, gain block, receive element)
     return cdl_os_apply(ctx, jobs, n_jobs, T, Nt, Nr, n_paths, taps, n_taps, shift, max_shift, out_scale);
   // workspace: DL (unfused kernels only): Z [T x Ncp] per segment;  UL: prefiltered signals [T x Kc] per job;  fused DL: none
-  const bool fused = !ul && cdl_fused_ok(T, Nt, Nr, n_paths, n_taps, max_shift), fused_ul = ul && cdl_fused_ul_ok(T, Nt, Nr, n_paths, n_taps, max_shift);
+  const bool fused_any = cdl_fused_ok(ul, T, Nt, Nr, n_paths, n_taps, max_shift), fused = !ul && fused_any, fused_ul = ul && fused_any;
   const size_t ws_elems = (fused || fused_ul) ? 0 : ul ? (size_t)n_jobs * (size_t)T * Kc : n_seg_total * (size_t)T * Ncp;
   if (ws_elems) ISAC_TRY(ensure(ctx, ctx->stage_b, sizeof(c64) * ws_elems));
   c64* ws = (c64*)ctx->stage_b.p;
@@ -1009,38 +964,32 @@ int cdl_apply_jobs(isac_ctx* ctx, const isac_cdl_job* jobs, int n_jobs, long lon
       segs.push_back(s);
     }
   // ---- one upload: segments | taps | shifts
-  const size_t seg_bytes = (sizeof(CdlSeg) * segs.size() + 63) & ~(size_t)63, tap_bytes = (sizeof(double) * (size_t)n_paths * n_taps + 63) & ~(size_t)63;
-  const size_t meta = seg_bytes + tap_bytes + sizeof(int) * (size_t)n_paths;
-  std::vector<char> host(meta);
-  std::memcpy(host.data(), segs.data(), sizeof(CdlSeg) * segs.size());
-  std::memcpy(host.data() + seg_bytes, taps, sizeof(double) * (size_t)n_paths * n_taps);
-  std::memcpy(host.data() + seg_bytes + tap_bytes, shift, sizeof(int) * (size_t)n_paths);
-  ISAC_TRY(ensure(ctx, ctx->stage_c, meta + 64));
-  char* dm = (char*)ctx->stage_c.p;
-  ISAC_TRY(stage_upload(ctx, dm, host.data(), meta));
-  const CdlSeg* d_segs = (const CdlSeg*)dm;
+  MetaPack meta;
+  const size_t o_seg = meta.add(segs), o_tap = meta.add(taps, sizeof(double) * (size_t)n_paths * n_taps), o_sh = meta.add(shift, sizeof(int) * (size_t)n_paths);
+  ISAC_TRY(meta.upload(ctx, ctx->stage_c));
+  const char* dm = (const char*)ctx->stage_c.p;
+  const CdlSeg* d_segs = (const CdlSeg*)(dm + o_seg);
   static const bool fir1 = std::getenv("ISAC_CDL_FIR1") != nullptr;     // test hook: the one-output-per-thread filter kernel for every tap count
   const bool fir4 = n_taps == 16 && !fir1;
-  const double* d_taps = (const double*)(dm + seg_bytes);
-  const int* d_shift = (const int*)(dm + seg_bytes + tap_bytes);
+  const double* d_taps = (const double*)(dm + o_tap);
+  const int* d_shift = (const int*)(dm + o_sh);
   if (ul) {
     // (the uplink prefilter is ONE term per output column: nothing to pipeline across terms, the one-output kernel's 4x finer grid hides the latency better --
-    //  cdl_fir4_kernel<true> measured 71 vs 54 us)
+    //  a four-output form measured 71 vs 54 us; cdl_fir4_kernel is the downlink's alone)
     hipLaunchKernelGGL(cdl_fir_kernel<true>, dim3((unsigned)cdiv(T, 256), (unsigned)Kc, (unsigned)n_jobs), dim3(256), 0, ctx->stream, d_segs + n_gemm, (long long)T,
                        (long long)T, Nt, Nr, n_paths, n_taps, d_taps, d_shift, 1.0);
     ISAC_HIP(hipGetLastError());
-    if (ctx->profile) ISAC_HIP(hipEventRecord(ctx->ev_k0, ctx->stream));   // isac_profile_*: brackets exactly the contraction launch
+    ISAC_TRY(profile_begin(ctx));                                      // isac_profile_*: brackets exactly the contraction launch
     ISAC_TRY((launch_gemm<true>(ctx, d_segs, (int)n_gemm, max_rows, T, T, Nt, Nr, Kc, Nr, out_scale)));
-    if (ctx->profile) { ISAC_HIP(hipEventRecord(ctx->ev_k1, ctx->stream)); ctx->profile_recorded = true; }
-    return ISAC_OK;
+    return profile_end(ctx);
   }
-  if (ctx->profile) ISAC_HIP(hipEventRecord(ctx->ev_k0, ctx->stream));
+  ISAC_TRY(profile_begin(ctx));
   ISAC_TRY((launch_gemm<false>(ctx, d_segs, (int)n_gemm, max_rows, T, T, Nt, Nr, Nt, Nc_dl, 1.0)));
-  if (ctx->profile) { ISAC_HIP(hipEventRecord(ctx->ev_k1, ctx->stream)); ctx->profile_recorded = true; }
+  ISAC_TRY(profile_end(ctx));
   long long max_out = 0;
   for (size_t i = 0; i < n_gemm; ++i) max_out = std::max(max_out, segs[i].o1 - segs[i].o0);
   if (max_out > 0) {
-    if (fir4) hipLaunchKernelGGL(cdl_fir4_kernel<false>, dim3((unsigned)cdiv(max_out, 1024), (unsigned)Nr, (unsigned)n_gemm), dim3(256), 0, ctx->stream, d_segs, (long long)T,
+    if (fir4) hipLaunchKernelGGL(cdl_fir4_kernel, dim3((unsigned)cdiv(max_out, 1024), (unsigned)Nr, (unsigned)n_gemm), dim3(256), 0, ctx->stream, d_segs, (long long)T,
                                  (long long)T, Nt, Nr, n_paths, d_taps, d_shift, out_scale);
     else hipLaunchKernelGGL(cdl_fir_kernel<false>, dim3((unsigned)cdiv(max_out, 256), (unsigned)Nr, (unsigned)n_gemm), dim3(256), 0, ctx->stream, d_segs, (long long)T,
                             (long long)T, Nt, Nr, n_paths, n_taps, d_taps, d_shift, out_scale);

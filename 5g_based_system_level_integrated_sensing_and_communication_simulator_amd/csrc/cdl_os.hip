@@ -427,16 +427,19 @@ __global__ __launch_bounds__(FFT::NT, MINW) void cdl_os_ul_kernel(const OsPair* 
 
 using namespace isac;
 
-bool cdl_os_ok(long long T, int Nt, int Nr, int n_paths, int n_taps, int max_shift) {
+static bool os_switched_off() {
   static const bool off = std::getenv("ISAC_CDL_TIME_DOMAIN") != nullptr;       // test hook: the time-domain kernels for every shape
+  return off;
+}
+
+bool cdl_os_ok(long long T, int Nt, int Nr, int n_paths, int n_taps, int max_shift) {
   const int Mpad = (max_shift + n_taps - 1 + 7) / 8 * 8;
-  return !off && Nr == 2 && (Nt == 8 || Nt == 16 || Nt == 32 || Nt == 64) && n_paths >= 1 && n_paths <= 64 && Mpad <= kOsN / 4 && T >= 2 * (kOsN - Mpad);
+  return !os_switched_off() && Nr == 2 && (Nt == 8 || Nt == 16 || Nt == 32 || Nt == 64) && n_paths >= 1 && n_paths <= 64 && Mpad <= kOsN / 4 && T >= 2 * (kOsN - Mpad);
 }
 
 bool cdl_os_ul_ok(long long T, int Nt, int Nr, int n_paths, int n_taps, int max_shift) {
-  static const bool off = std::getenv("ISAC_CDL_TIME_DOMAIN") != nullptr;       // test hook (as above)
   const int Mpad = (max_shift + n_taps - 1 + 7) / 8 * 8;
-  return !off && (Nt == 1 || Nt == 2) && Nr > Nt && Nr <= 65535 && n_paths >= 1 && n_paths <= 64 && Mpad <= kOsN / 4 && T >= 2 * (kOsN - Mpad);
+  return !os_switched_off() && (Nt == 1 || Nt == 2) && Nr > Nt && Nr <= 65535 && n_paths >= 1 && n_paths <= 64 && Mpad <= kOsN / 4 && T >= 2 * (kOsN - Mpad);
 }
 
 // jobs: the batch of isac_cdl_apply_batch_dev (cdl.hip); one launch sequence for all of them.
@@ -512,19 +515,11 @@ int cdl_os_apply(isac_ctx* ctx, const isac_cdl_job* jobs, int n_jobs, long long 
   c64* d_E = (c64*)ctx->stage_b.p;
   c64* d_X = share ? (c64*)ctx->os_x.p : (c64*)((char*)ctx->stage_b.p + e_bytes);
   c64* d_Y = (c64*)((char*)ctx->stage_b.p + e_bytes + (share ? 0 : x_bytes));
-  const size_t o_pairs = 0, o_chunks = o_pairs + pad(sizeof(OsPair) * ordered.size()), o_tasks = o_chunks + pad(sizeof(OsChunk) * chunks.size()),
-               o_waves = o_tasks + pad(sizeof(OsTask) * tasks.size()), o_taps = o_waves + pad(sizeof(void*) * waves.size()), o_shift = o_taps + pad(sizeof(double) * (size_t)n_paths * n_taps),
-               meta = o_shift + pad(sizeof(int) * (size_t)n_paths);
-  std::vector<char> host(meta);
-  std::memcpy(host.data() + o_pairs, ordered.data(), sizeof(OsPair) * ordered.size());
-  std::memcpy(host.data() + o_chunks, chunks.data(), sizeof(OsChunk) * chunks.size());
-  std::memcpy(host.data() + o_tasks, tasks.data(), sizeof(OsTask) * tasks.size());
-  std::memcpy(host.data() + o_waves, waves.data(), sizeof(void*) * waves.size());
-  std::memcpy(host.data() + o_taps, taps, sizeof(double) * (size_t)n_paths * n_taps);
-  std::memcpy(host.data() + o_shift, shift, sizeof(int) * (size_t)n_paths);
-  ISAC_TRY(ensure(ctx, ctx->stage_c, meta + 64));
-  char* dm = (char*)ctx->stage_c.p;
-  ISAC_TRY(stage_upload(ctx, dm, host.data(), meta));
+  MetaPack meta(256);
+  const size_t o_pairs = meta.add(ordered), o_chunks = meta.add(chunks), o_tasks = meta.add(tasks), o_waves = meta.add(waves),
+               o_taps = meta.add(taps, sizeof(double) * (size_t)n_paths * n_taps), o_shift = meta.add(shift, sizeof(int) * (size_t)n_paths);
+  ISAC_TRY(meta.upload(ctx, ctx->stage_c));
+  const char* dm = (const char*)ctx->stage_c.p;
   const c64* tw = nullptr;
   ISAC_TRY(isac_get_twiddles(ctx, kOsN, &tw));
   const size_t lds = sizeof(c64) * Fft4096::LDS_ELEMS;
@@ -533,7 +528,7 @@ int cdl_os_apply(isac_ctx* ctx, const isac_cdl_job* jobs, int n_jobs, long long 
     hipLaunchKernelGGL(cdl_os_fwd_kernel, dim3((unsigned)n_seg, (unsigned)Nt, (unsigned)waves.size()), dim3(256), lds, ctx->stream, (const c64* const*)(dm + o_waves), T, Nt, n_seg, S,
                        Mpad, tw, 12, d_X);                                      // (one 4096-bin "tile": the plain [wave][seg][s][N] layout)
     ISAC_HIP(hipGetLastError());
-    if (ctx->profile) ISAC_HIP(hipEventRecord(ctx->ev_k0, ctx->stream));
+    ISAC_TRY(profile_begin(ctx));
     const c64* tw_ul = nullptr;
     ISAC_TRY(isac_get_w512_pack(ctx, &tw_ul));
     // (one receive element per workgroup: sharing a window's X spectra between two or four of them -- NU = 2 / 4 -- needs their C(f) in registers as well and spills (268 / 948
@@ -550,8 +545,7 @@ int cdl_os_apply(isac_ctx* ctx, const isac_cdl_job* jobs, int n_jobs, long long 
     if (Nt == 1) ISAC_OS_UL(1); else ISAC_OS_UL(2);
 #undef ISAC_OS_UL
     ISAC_HIP(hipGetLastError());
-    if (ctx->profile) { ISAC_HIP(hipEventRecord(ctx->ev_k1, ctx->stream)); ctx->profile_recorded = true; }
-    return ISAC_OK;
+    return profile_end(ctx);
   }
   hipLaunchKernelGGL(cdl_os_table_kernel, dim3(kOsN / 256, (unsigned)n_paths), dim3(256), 0, ctx->stream, (const double*)(dm + o_taps), (const int*)(dm + o_shift), n_paths, n_taps, d_E);
   ISAC_HIP(hipGetLastError());
@@ -563,7 +557,7 @@ int cdl_os_apply(isac_ctx* ctx, const isac_cdl_job* jobs, int n_jobs, long long 
     ISAC_HIP(hipGetLastError());
     if (share) { ctx->os_waves = wave_ids; ctx->os_T = T; ctx->os_nt = Nt; ctx->os_mpad = Mpad; ctx->os_tb = tb_log2; ctx->os_valid = true; }
   }
-  if (ctx->profile) ISAC_HIP(hipEventRecord(ctx->ev_k0, ctx->stream));          // isac_profile_*: brackets the mix launch (the arithmetic of the apply)
+  ISAC_TRY(profile_begin(ctx));                                                 // isac_profile_*: brackets the mix launch (the arithmetic of the apply)
   const dim3 gm(kOsN / kOsBins, (unsigned)chunks.size());
 #define ISAC_OS_MIX(HS) hipLaunchKernelGGL((cdl_os_mix_kernel<HS>), gm, dim3(256), 0, ctx->stream, (const OsPair*)(dm + o_pairs), (const OsChunk*)(dm + o_chunks), (const c64*)d_X, \
                                            (const c64*)d_E, n_paths, n_seg, d_Y)
@@ -574,7 +568,7 @@ int cdl_os_apply(isac_ctx* ctx, const isac_cdl_job* jobs, int n_jobs, long long 
     switch (Nt) { case 8: ISAC_OS_MIX(4); break; case 16: ISAC_OS_MIX(8); break; case 32: ISAC_OS_MIX(16); break; default: ISAC_OS_MIX(32); break; }
 #undef ISAC_OS_MIX
   ISAC_HIP(hipGetLastError());
-  if (ctx->profile) { ISAC_HIP(hipEventRecord(ctx->ev_k1, ctx->stream)); ctx->profile_recorded = true; }
+  ISAC_TRY(profile_end(ctx));
   hipLaunchKernelGGL(cdl_os_inv_kernel, dim3((unsigned)tasks.size(), (unsigned)Nr), dim3(256), lds, ctx->stream, (const OsPair*)(dm + o_pairs), (const OsTask*)(dm + o_tasks), T, Nr, S, Mpad,
                      tw, (const c64*)d_Y, out_scale / (double)kOsN);
   ISAC_HIP(hipGetLastError());

@@ -658,26 +658,20 @@ static int csi_report_batch(isac_ctx* ctx, int n_ue, const isac_c64* const* d_H_
   for (long long i = 0; i < n_re; ++i) if (re_l[i] >= 0 && re_l[i] < 14) sym_mask |= 1u << re_l[i];
   for (int q = 0; q < n_re; ++q) { sym_p[q] = q < ptr_p[nsp] ? re_l[idx_p[q]] : -1; sym_c[q] = q < ptr_c[nsc] ? re_l[idx_c[q]] : -1; }
   // ---- ONE staged upload: W | int tables | H pointers | noise variances
-  const size_t w_bytes = (sizeof(c64) * (size_t)P * NL * nE + 63) & ~(size_t)63, int_bytes = (sizeof(int) * ints.size() + 63) & ~(size_t)63;
-  const size_t ptr_bytes = (sizeof(void*) * (size_t)n_ue + 63) & ~(size_t)63, nv_bytes = (sizeof(double) * (size_t)n_ue + 63) & ~(size_t)63;
-  const size_t meta = w_bytes + int_bytes + ptr_bytes + nv_bytes;
-  std::vector<char> host(meta, 0);
-  std::memcpy(host.data(), W, sizeof(c64) * (size_t)P * NL * nE);
-  std::memcpy(host.data() + w_bytes, ints.data(), sizeof(int) * ints.size());
-  std::memcpy(host.data() + w_bytes + int_bytes, d_H_list, sizeof(void*) * (size_t)n_ue);
-  std::memcpy(host.data() + w_bytes + int_bytes + ptr_bytes, nvar, sizeof(double) * (size_t)n_ue);
-  ISAC_TRY(ensure(ctx, ctx->stage_c, meta + 64));
-  char* dm = (char*)ctx->stage_c.p;
-  ISAC_TRY(stage_upload(ctx, dm, host.data(), meta));
-  const c64* dW = (const c64*)dm;
-  const int* d_idx_p = (const int*)(dm + w_bytes);
+  MetaPack meta;
+  const size_t o_w = meta.add(W, sizeof(c64) * (size_t)P * NL * nE), o_int = meta.add(ints), o_h = meta.add(d_H_list, sizeof(void*) * (size_t)n_ue),
+               o_nv = meta.add(nvar, sizeof(double) * (size_t)n_ue);
+  ISAC_TRY(meta.upload(ctx, ctx->stage_c));
+  const char* dm = (const char*)ctx->stage_c.p;
+  const c64* dW = (const c64*)(dm + o_w);
+  const int* d_idx_p = (const int*)(dm + o_int);
   const int* d_idx_c = d_idx_p + n_re;
   const int* d_sym_p = d_idx_c + n_re;
   const int* d_sym_c = d_sym_p + n_re;
   const int* d_ptr_p = d_sym_c + n_re;
   const int* d_ptr_c = d_ptr_p + nsp + 1;
-  const c64* const* d_hl = (const c64* const*)(dm + w_bytes + int_bytes);
-  const double* d_nv = (const double*)(dm + w_bytes + int_bytes + ptr_bytes);
+  const c64* const* d_hl = (const c64* const*)(dm + o_h);
+  const double* d_nv = (const double*)(dm + o_nv);
   // ---- device results: per UE [total nE | sb_sinr pmi | sb_sinr cqi]; per-RE SINRs per UE
   const size_t sinr_elems = (size_t)n_re * NL * nE;
   const size_t n_sbp = (size_t)sh.pmi_sb.n * NL * nE, n_sbc = (size_t)sh.cqi_sb.n * NL * nE, res_stride = (size_t)nE + n_sbp + n_sbc;
@@ -802,18 +796,11 @@ extern "C" int isac_srs_pmi_select_batch_dev(isac_ctx* ctx, int32_t n_ue, const 
   for (int s2 = 0; s2 < n_sb; ++s2) ptr[(size_t)s2 + 1] += ptr[(size_t)s2];
   { std::vector<int> cur(ptr.begin(), ptr.end() - 1); for (long long i = 0; i < n_re; ++i) idx[(size_t)cur[(size_t)of[(size_t)i]]++] = (int)i; }
   // ---- one staged upload: W | ptr | idx | H pointers | noise variances
-  auto pad = [](size_t b) { return (b + 63) & ~(size_t)63; };
-  const size_t o_w = 0, o_ptr = o_w + pad(sizeof(isac_c64) * W.size()), o_idx = o_ptr + pad(sizeof(int) * ptr.size()), o_h = o_idx + pad(sizeof(int) * idx.size()),
-               o_nv = o_h + pad(sizeof(void*) * (size_t)n_ue), meta = o_nv + pad(sizeof(double) * (size_t)n_ue);
-  std::vector<char> host(meta, 0);
-  std::memcpy(host.data() + o_w, W.data(), sizeof(isac_c64) * W.size());
-  std::memcpy(host.data() + o_ptr, ptr.data(), sizeof(int) * ptr.size());
-  std::memcpy(host.data() + o_idx, idx.data(), sizeof(int) * idx.size());
-  std::memcpy(host.data() + o_h, d_H_list, sizeof(void*) * (size_t)n_ue);
-  std::memcpy(host.data() + o_nv, nvar, sizeof(double) * (size_t)n_ue);
-  ISAC_TRY(ensure(ctx, ctx->stage_c, meta + 64));
-  char* dm = (char*)ctx->stage_c.p;
-  ISAC_TRY(stage_upload(ctx, dm, host.data(), meta));
+  MetaPack meta;
+  const size_t o_w = meta.add(W), o_ptr = meta.add(ptr), o_idx = meta.add(idx), o_h = meta.add(d_H_list, sizeof(void*) * (size_t)n_ue),
+               o_nv = meta.add(nvar, sizeof(double) * (size_t)n_ue);
+  ISAC_TRY(meta.upload(ctx, ctx->stage_c));
+  const char* dm = (const char*)ctx->stage_c.p;
   const size_t sinr_elems = (size_t)n_re * NL * nE, res_stride = (size_t)n_sb * nE;
   ISAC_TRY(ensure(ctx, ctx->stage_a, sizeof(double) * sinr_elems * (size_t)n_ue));
   ISAC_TRY(ensure(ctx, ctx->stage_b, sizeof(double) * res_stride * (size_t)n_ue + 64));

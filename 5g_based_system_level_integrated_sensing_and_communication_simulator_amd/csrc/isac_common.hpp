@@ -378,6 +378,46 @@ inline int stage_upload(isac_ctx* ctx, void* d_dst, const void* src, size_t byte
   std::memcpy(h, src, bytes);
   return stage_commit(ctx, d_dst, bytes);
 }
+// Several small host arrays -> ONE staged upload into a device scratch buffer: add() appends an array and returns its byte offset (a multiple of `align`),
+// upload() sizes the buffer and enqueues the copy.
+struct MetaPack {
+  size_t align;
+  std::vector<char> host;
+  explicit MetaPack(size_t align_ = 64) : align(align_) {}
+  size_t add(const void* src, size_t bytes) {
+    const size_t off = host.size();
+    host.resize(off + (bytes + align - 1) / align * align, 0);
+    if (bytes) std::memcpy(host.data() + off, src, bytes);
+    return off;
+  }
+  template <class T>
+  size_t add(const std::vector<T>& v) { return add(v.data(), sizeof(T) * v.size()); }
+  int upload(isac_ctx* ctx, DevBuf& b) {
+    ISAC_TRY(ensure(ctx, b, host.size() + 64));
+    return stage_upload(ctx, b.p, host.data(), host.size());
+  }
+};
+
+// isac_profile_*: the event pair around the launch(es) a call wants timed
+inline int profile_begin(isac_ctx* ctx) {
+  if (ctx->profile) ISAC_HIP(hipEventRecord(ctx->ev_k0, ctx->stream));
+  return ISAC_OK;
+}
+inline int profile_end(isac_ctx* ctx) {
+  if (ctx->profile) { ISAC_HIP(hipEventRecord(ctx->ev_k1, ctx->stream)); ctx->profile_recorded = true; }
+  return ISAC_OK;
+}
+
+// compute units of the context's device (queried once: the persistent-grid launches size themselves by it)
+inline int ctx_n_cus(isac_ctx* ctx, int* n_cus) {
+  if (ctx->n_cus <= 0) {
+    int v = 0;
+    ISAC_HIP(hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, ctx->device));
+    ctx->n_cus = v > 0 ? v : 256;
+  }
+  *n_cus = ctx->n_cus;
+  return ISAC_OK;
+}
 
 // ---------------------------------------------------------------- OFDM numerology (TS 38.211 5.3.1)
 struct Numerology {

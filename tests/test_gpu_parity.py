@@ -748,6 +748,68 @@ def test_cdl_fused_apply_bits_do_not_depend_on_the_grid(tmp_path):
         assert runs["os"][i][1:] == runs["os"][i + 1][1:]                          # overlap-save: a job alone == the job in a batch, bit for bit
 
 
+_CDL_LONG_SNIPPET = """
+import hashlib, importlib, sys
+import numpy as np
+sys.path.insert(0, %r)
+pkg = importlib.import_module(%r)
+ctx = pkg._lib.Context(0)
+CM = pkg.communication.channelModels
+fs, t_len = 122.88e6, 3001
+UE, ARR = (1, 1, 2, 1, 1), (1, 4, 2, 1, 1)
+for tag, tx, rx in (("dl", ARR, UE), ("ul", UE, ARR)):
+    nt = int(np.prod(tx))
+    rng = np.random.default_rng(1000 + nt)
+    xh = [np.asfortranarray(rng.standard_normal((t_len, nt)) + 1j * rng.standard_normal((t_len, nt))) for _ in range(2)]
+    xs = [ctx.to_device(x) for x in xh]
+    which, seeds, t0s = [0, 0, 1, 1], [70, 71, 72, 73], [0.0, 0.0, 0.0, 1.0 / 640 - (t_len // 2) / fs]     # the last job crosses a path-gain refresh
+    def chans():
+        c = [CM.CDLChannel("CDL-A", 600e-9, 3.5e9, tx, rx, fs, Seed=s) for s in seeds]
+        for ch, t0 in zip(c, t0s):
+            ch.time = t0
+        return c
+    outs = CM.applyCDLBatch(chans(), [xs[w] for w in which], ctx=ctx)
+    print("digest batch", tag, hashlib.sha256(b"".join(o.numpy().tobytes() for o in outs)).hexdigest())
+    single = [CM.applyCDLBatch([c], [xs[w]], ctx=ctx)[0] for c, w in zip(chans(), which)]
+    print("digest single", tag, hashlib.sha256(b"".join(o.numpy().tobytes() for o in single)).hexdigest())
+    np.savez(sys.argv[1] + "_" + tag + ".npz", y=np.stack([o.numpy() for o in outs]), x=np.stack(xh), which=which, seeds=seeds, t0s=t0s, tx=tx, rx=rx)
+"""
+
+
+def test_cdl_fused_long_delays_match_oracle_and_unfused(tmp_path):
+    """The fused kernels at a 600 ns delay spread and 122.88 MHz: CDL-A's 23 paths then reach 712.1 samples back, so the downlink (8 -> 2 elements) takes
+    cdl_fused_kernel<3, 8> (eight slots per thread: delays of 384 samples and more, six warm-up tiles) and the uplink (2 -> 8) a 728-row history window --
+    no 300 ns case reaches either.  T = 3001 (ragged, 24 tiles, less than two overlap-save windows), four jobs on two waveforms, one across a path-gain
+    refresh: the same bits for 1, 7 and one-per-CU workgroups and for a job alone or in a batch; <= 1e-12 against the unfused kernels (other summation
+    order); RTOL against the oracle."""
+    import subprocess, sys
+    import oracle.cdl as OC
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    fs = 122.88e6
+    shift = np.floor(OC.path_delays(OC.cdl_config("CDL-A", 3.5e9, UE_ARRAY, UE_ARRAY, fs, delay_spread=600e-9)) * fs)
+    assert shift.size == 23 and 384 <= shift.max() and shift.max() + 16 <= 896          # the eight-slot instantiations; inside both fused envelopes
+    runs = {}
+    td = {"ISAC_CDL_TIME_DOMAIN": "1"}
+    for tag, extra in (("cu", td), ("one", dict(td, ISAC_CDL_FUSED_WGS="1")), ("seven", dict(td, ISAC_CDL_FUSED_WGS="7")), ("unfused", dict(td, ISAC_CDL_UNFUSED="1"))):
+        r = subprocess.run([sys.executable, "-c", _CDL_LONG_SNIPPET % (root, PKG_NAME), str(tmp_path / tag)], env=dict(os.environ, **extra), capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stdout + r.stderr
+        runs[tag] = [ln.split()[1:] for ln in r.stdout.splitlines() if ln.startswith("digest")]
+    assert len(runs["cu"]) == 4
+    assert runs["cu"] == runs["one"] == runs["seven"]
+    for i in (0, 2):
+        assert runs["cu"][i][1:] == runs["cu"][i + 1][1:], runs["cu"][i]                  # batch == single
+    for tag in ("dl", "ul"):
+        a, b = np.load(tmp_path / ("cu_%s.npz" % tag)), np.load(tmp_path / ("unfused_%s.npz" % tag))
+        assert rel(a["y"], b["y"]) <= 1e-12, (tag, rel(a["y"], b["y"]))
+        if tag == "dl":           # tile-major against path-major sums: other bits, so the hook really chose the other kernels (the uplink forms add in the same order)
+            assert not np.array_equal(a["y"], b["y"])
+        tx, rx = tuple(int(v) for v in a["tx"]), tuple(int(v) for v in a["rx"])
+        assert a["y"].shape == (4, 3001, int(np.prod(rx)))
+        for y, w, seed, t0 in zip(a["y"], a["which"], a["seeds"], a["t0s"]):
+            cfg = OC.cdl_config("CDL-A", 3.5e9, tx, rx, fs, delay_spread=600e-9, seed=int(seed))
+            assert rel(y, OC.apply_cdl(cfg, a["x"][w], float(t0))) < RTOL, (tag, int(seed))
+
+
 # ------------------------------------------------------------------ SINR -> CQI
 @pytest.mark.parametrize("nr,p,nl", [(2, 4, 1), (2, 4, 2), (4, 8, 4), (8, 32, 8)])
 def test_precoded_sinr_and_cqi(pkg, ctx, nr, p, nl):
