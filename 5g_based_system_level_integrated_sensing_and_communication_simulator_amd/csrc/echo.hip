@@ -545,8 +545,6 @@ extern "C" int isac_ofdm_waveform_length(const isac_carrier* carrier, int32_t L,
   return ISAC_OK;
 }
 
-static unsigned fft_grid(int n_cols) { return (unsigned)n_cols; }   // one column per workgroup (two 72 KB workgroups per CU)
-
 // Everything basicRadarChannel needs before samples can be synthesised: LoS compaction,
 // beam-sums, coefficient vectors.  Leaves coef [Q x T], phase_rx [T], steer_rq [A x Q] in ctx.
 static int prepare_echo(isac_ctx* ctx, const c64* d_tx, long long T, const isac_radar_channel_params* rp,
@@ -561,11 +559,15 @@ static int prepare_echo(isac_ctx* ctx, const c64* d_tx, long long T, const isac_
   const double Ts = 1.0 / rp->fs;                   // :15
   const double two_pi = 2.0 * M_PI;
   TargetTable tab{};
-  std::vector<c64> steer_aq, steer_rq;              // compacted LoS columns
+  std::vector<c64> steer_aq;                        // compacted LoS columns [A x Q]
   int Q = 0;
   for (int i = 0; i < rp->n_targets; ++i) {
     if (los[i] != 1) continue;                      // :40
     if (Q >= kMaxTargets) return fail(ctx, ISAC_ERR_CAPACITY, "more than 64 LoS targets");
+    for (int a = 0; a < A; ++a) {
+      const isac_c64 sv = rp->rx_steering[(size_t)a + (size_t)A * i];
+      steer_aq.push_back(mk(sv.re, sv.im));
+    }
     double path_delay = 2.0 * rp->range[i] / c0;    // :21
     tab.t[Q].shift = (long long)std::ceil(path_delay / Ts);   // :22
     double fd = 2.0 * rp->velocity[i] / lambda;     // :25
@@ -574,20 +576,9 @@ static int prepare_echo(isac_ctx* ctx, const c64* d_tx, long long T, const isac_
     ++Q;
   }
   if (Q == 0) return fail(ctx, ISAC_ERR_NO_LOS, "no LoS target: rxWaveform is empty (basicRadarChannel.m:59,64)");
-  steer_aq.resize((size_t)A * Q);
-  steer_rq.resize((size_t)A * Q);
-  {
-    int q = 0;
-    for (int i = 0; i < rp->n_targets; ++i) {
-      if (los[i] != 1) continue;
-      for (int a = 0; a < A; ++a) {
-        const isac_c64 s = rp->rx_steering[(size_t)a + (size_t)A * i];
-        steer_aq[(size_t)q * A + a] = mk(s.re, s.im);
-        steer_rq[(size_t)a * Q + q] = mk(s.re, s.im);
-      }
-      ++q;
-    }
-  }
+  std::vector<c64> steer_rq((size_t)A * Q);         // the same, transposed: row r holds a_q[r] at r * Q + q
+  for (int q = 0; q < Q; ++q)
+    for (int a = 0; a < A; ++a) steer_rq[(size_t)a * Q + q] = steer_aq[(size_t)q * A + a];
   ISAC_TRY(ensure(ctx, ctx->steer, sizeof(c64) * (size_t)A * Q * 2));
   ISAC_TRY(ensure(ctx, ctx->beam, sizeof(c64) * (size_t)Q * T));
   ISAC_TRY(ensure(ctx, ctx->coef, sizeof(c64) * (size_t)Q * T));
@@ -646,6 +637,21 @@ extern "C" int isac_basic_radar_channel_dev(isac_ctx* ctx, const isac_c64* d_tx_
   return ISAC_OK;
 }
 
+// f(std::integral_constant<int, Q>) for a LoS target count the kernels have as a compile-time constant (1..MAXQ), f(<0>) -- the run-time count -- for any other
+template <int MAXQ, class F>
+static int echo_dispatch(int Q, F&& f) {
+  if constexpr (MAXQ > 0)
+    if (Q != MAXQ) return echo_dispatch<MAXQ - 1>(Q, f);
+  return f(std::integral_constant<int, MAXQ>{});
+}
+
+// monoStaticSensing.m:19-21: the grid has at least the transmit grid's symbol count (the caller zero-fills a grid that is wider than the waveform)
+static int padded_symbols(int L_whole, int tx_dim_l, int32_t* l_out) {
+  const int L_out = L_whole < tx_dim_l ? tx_dim_l : L_whole;
+  if (l_out) *l_out = L_out;
+  return L_out;
+}
+
 template <class FFT, bool SYNTH, int QT = 0>
 static int launch_demod(isac_ctx* ctx, const OfdmGeom& g, long long T, int A, int L_whole, int L_out, const c64* tw, int Q,
                         int noise_mode, const c64* noise, double n0s, uint64_t seed, const c64* wave, c64* grid) {
@@ -654,7 +660,7 @@ static int launch_demod(isac_ctx* ctx, const OfdmGeom& g, long long T, int A, in
   ISAC_TRY(isac_get_logtab(ctx, &logtab));
   auto kern = demod_kernel<FFT, SYNTH, QT>;
   ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(kern), lds));
-  hipLaunchKernelGGL(kern, dim3(fft_grid(L_whole * A)), dim3(256), lds, ctx->stream, g, T, A, L_whole, L_out, tw, Q,
+  hipLaunchKernelGGL(kern, dim3((unsigned)(L_whole * A)) /* one column per workgroup (two 72 KB workgroups per CU) */, dim3(256), lds, ctx->stream, g, T, A, L_whole, L_out, tw, Q,
                      (const c64*)ctx->coef.p, SYNTH ? (const c64*)ctx->steer.p + (size_t)A * Q : nullptr,
                      (const c64*)ctx->phase_rx.p, noise_mode, noise, n0s, seed, wave, grid, logtab);
   ISAC_HIP(hipGetLastError());
@@ -687,12 +693,18 @@ static int launch_echo_spectral(isac_ctx* ctx, const OfdmGeom& g, int A, int L_w
   const dim3 gr((unsigned)spectral_grid_size(L_whole, A)), bl(256);
   const c64* D = (const c64*)ctx->dgrid.p;
   const c64* srq = (const c64*)ctx->steer.p + (size_t)A * Q;
-  if (noise_mode == ISAC_NOISE_PHILOX_SPECTRAL)
-    hipLaunchKernelGGL((echo_spectral_kernel<QT, 1>), gr, bl, 0, ctx->stream, g.n_sc, L_whole, L_out, A, Q, D, srq, sig, seed, noise, grid);
-  else if (noise_mode == ISAC_NOISE_INJECTED_SPECTRAL)
-    hipLaunchKernelGGL((echo_spectral_kernel<QT, 2>), gr, bl, 0, ctx->stream, g.n_sc, L_whole, L_out, A, Q, D, srq, sig, seed, noise, grid);
-  else
-    hipLaunchKernelGGL((echo_spectral_kernel<QT, 0>), gr, bl, 0, ctx->stream, g.n_sc, L_whole, L_out, A, Q, D, srq, sig, seed, noise, grid);
+  auto kern = noise_mode == ISAC_NOISE_PHILOX_SPECTRAL ? echo_spectral_kernel<QT, 1> : noise_mode == ISAC_NOISE_INJECTED_SPECTRAL ? echo_spectral_kernel<QT, 2> : echo_spectral_kernel<QT, 0>;
+  hipLaunchKernelGGL(kern, gr, bl, 0, ctx->stream, g.n_sc, L_whole, L_out, A, Q, D, srq, sig, seed, noise, grid);
+  ISAC_HIP(hipGetLastError());
+  return ISAC_OK;
+}
+
+// One launch of a fused synthesis + range kernel (echo_range_kernel / echo_range_sl_kernel: Fft4096W workgroups, one per tile-map slot)
+template <class Kern, class... Args>
+static int launch_echo_range(isac_ctx* ctx, Kern kern, int L_whole, int A, Args... args) {
+  const size_t lds = sizeof(c64) * Fft4096W::LDS_ELEMS;
+  ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(kern), lds));
+  hipLaunchKernelGGL(kern, dim3((unsigned)spectral_grid_size(L_whole, A)), dim3(Fft4096W::NT), lds, ctx->stream, args...);
   ISAC_HIP(hipGetLastError());
   return ISAC_OK;
 }
@@ -703,17 +715,10 @@ static int mono_static_spectral(isac_ctx* ctx, const c64* d_tx, long long T, int
   int Q = 0, L_whole = 0;
   ISAC_TRY(spectral_prepare(ctx, d_tx, T, rp, los, g, &Q, &L_whole));
   const int A = rp->n_ants;
-  const int L_out = L_whole < tx_dim_l ? tx_dim_l : L_whole;                          // monoStaticSensing.m:19-21
-  if (l_out) *l_out = L_out;
+  const int L_out = padded_symbols(L_whole, tx_dim_l, l_out);
   if (L_out > L_whole) ISAC_HIP(hipMemsetAsync(d_grid, 0, sizeof(c64) * (size_t)g.n_sc * L_out * A, ctx->stream));
   const double sig = std::sqrt(rp->n0 / 2.0) * std::sqrt((double)g.nfft);            // basicRadarChannel.m:67 through the unscaled FFT
-  switch (Q) {
-    case 1: return launch_echo_spectral<1>(ctx, g, A, L_whole, L_out, Q, noise_mode, d_noise, sig, seed, d_grid);
-    case 2: return launch_echo_spectral<2>(ctx, g, A, L_whole, L_out, Q, noise_mode, d_noise, sig, seed, d_grid);
-    case 3: return launch_echo_spectral<3>(ctx, g, A, L_whole, L_out, Q, noise_mode, d_noise, sig, seed, d_grid);
-    case 4: return launch_echo_spectral<4>(ctx, g, A, L_whole, L_out, Q, noise_mode, d_noise, sig, seed, d_grid);
-    default: return launch_echo_spectral<0>(ctx, g, A, L_whole, L_out, Q, noise_mode, d_noise, sig, seed, d_grid);
-  }
+  return echo_dispatch<4>(Q, [&](auto qc) { return launch_echo_spectral<decltype(qc)::value>(ctx, g, A, L_whole, L_out, Q, noise_mode, d_noise, sig, seed, d_grid); });
 }
 
 extern "C" int isac_mono_static_sensing_dev(isac_ctx* ctx, const isac_c64* d_tx_wave, int64_t T, int32_t tx_dim_l,
@@ -736,23 +741,18 @@ extern "C" int isac_mono_static_sensing_dev(isac_ctx* ctx, const isac_c64* d_tx_
   const int A = rp->n_ants;
   const int L_whole = whole_symbols(g, T);
   if (L_whole <= 0) return fail(ctx, ISAC_ERR_SHORT_WAVEFORM, "waveform shorter than one OFDM symbol");
-  const int L_out = L_whole < tx_dim_l ? tx_dim_l : L_whole;            // monoStaticSensing.m:19-21
-  if (l_out) *l_out = L_out;
-  if (L_out > L_whole)
-    ISAC_HIP(hipMemsetAsync(d_echo_grid, 0, sizeof(c64) * (size_t)g.n_sc * L_out * A, ctx->stream));
+  const int L_out = padded_symbols(L_whole, tx_dim_l, l_out);
+  if (L_out > L_whole) ISAC_HIP(hipMemsetAsync(d_echo_grid, 0, sizeof(c64) * (size_t)g.n_sc * L_out * A, ctx->stream));
   const c64* tw = nullptr;
   ISAC_TRY(isac_get_twiddles(ctx, g.nfft, &tw));
   const double n0s = std::sqrt(rp->n0 / 2.0);
-#define ISAC_DEMOD_Q(QT) ISAC_TRY((launch_demod<Fft4096, true, QT>(ctx, g, T, A, L_whole, L_out, tw, Q, noise_mode, \
-                                                                   (const c64*)d_noise_unit, n0s, seed, nullptr, (c64*)d_echo_grid)))
-  if (g.nfft == 4096 && Q >= 1 && Q <= 4) {
-    switch (Q) { case 1: ISAC_DEMOD_Q(1); break; case 2: ISAC_DEMOD_Q(2); break; case 3: ISAC_DEMOD_Q(3); break; default: ISAC_DEMOD_Q(4); break; }
-  } else {
-    ISAC_FFT_DISPATCH(g.nfft, ISAC_TRY((launch_demod<FFT, true>(ctx, g, T, A, L_whole, L_out, tw, Q, noise_mode,
-                                                                (const c64*)d_noise_unit, n0s, seed, nullptr,
-                                                                (c64*)d_echo_grid))));
-  }
-#undef ISAC_DEMOD_Q
+  if (g.nfft == 4096)      // the target count as a compile-time constant where the kernel has one (1..4)
+    return echo_dispatch<4>(Q, [&](auto qc) {
+      return launch_demod<Fft4096, true, decltype(qc)::value>(ctx, g, T, A, L_whole, L_out, tw, Q, noise_mode, (const c64*)d_noise_unit, n0s, seed, nullptr, (c64*)d_echo_grid);
+    });
+  ISAC_FFT_DISPATCH(g.nfft, ISAC_TRY((launch_demod<FFT, true>(ctx, g, T, A, L_whole, L_out, tw, Q, noise_mode,
+                                                              (const c64*)d_noise_unit, n0s, seed, nullptr,
+                                                              (c64*)d_echo_grid))));
   return ISAC_OK;
 }
 
@@ -769,9 +769,9 @@ extern "C" int isac_mono_static_sensing_fused_dev(isac_ctx* ctx, const isac_c64*
   if (!ep || !cf || !d_tx_grid || !rp) return fail(ctx, ISAC_ERR_INVALID_ARG, "NULL argument");
   if (noise_mode == ISAC_NOISE_INJECTED && !d_noise_unit) return fail(ctx, ISAC_ERR_INVALID_ARG, "noise buffer missing");
   OfdmGeom g = geom_of(carrier);
-  const int hr = cf->guard[0] + cf->train[0];
-  const int row_lo = cf->row0 - 1 - hr, row_hi = cf->row1 - 1 + hr;
-  const bool fusable = (g.nfft == 4096 && ep->n_ifft == g.nfft && row_lo >= 0 && row_hi < ep->n_ifft && cf->row1 >= cf->row0);
+  CutRows cr;
+  const bool rows_ok = cut_rows_ok(ep, cf, &cr) && cf->row1 >= cf->row0;
+  const bool fusable = g.nfft == 4096 && ep->n_ifft == g.nfft && rows_ok;
   // d_echo_grid == NULL: the echo grid stays inside the context (LazyEcho, isac_common.hpp).  Where the kernels can re-form it -- the fused spectral route with Philox noise,
   // 49..64 antennas, one or two LoS targets -- nothing is stored at all; every other shape gets a context-owned buffer and runs exactly as with a caller's array.
   const bool lazy = d_echo_grid == nullptr;
@@ -784,53 +784,36 @@ extern "C" int isac_mono_static_sensing_fused_dev(isac_ctx* ctx, const isac_c64*
     if (!lazy_native) {
       int32_t lw = 0;
       ISAC_TRY(isac_ofdm_symbol_count(carrier, T, &lw));
-      const int lo_ = lw < tx_dim_l ? tx_dim_l : lw;
+      const int lo_ = padded_symbols(lw, tx_dim_l, nullptr);
       if (lo_ <= 0) return fail(ctx, ISAC_ERR_SHORT_WAVEFORM, "waveform shorter than one OFDM symbol");
       ISAC_TRY(ensure(ctx, ctx->echo_own, sizeof(c64) * (size_t)g.n_sc * lo_ * rp->n_ants));
       d_echo_grid = (isac_c64*)ctx->echo_own.p;
     }
   }
-  auto lazy_owned_done = [&](int lo_) {                                            // the owned-buffer form: remember the shape, the data are in ctx->echo_own
-    if (!lazy) return;
-    LazyEcho& lz = ctx->lazy;
-    lz.valid = true; lz.native = false; lz.K = g.n_sc; lz.L_whole = lo_; lz.L_out = lo_; lz.A = rp->n_ants; lz.Q = 0; lz.sig = 0.0; lz.seed = 0;
-  };
-  if (!fusable) {
-    // other numerologies (Nfft != 4096 or nIFFT != Nfft): the plain synthesis, then the range stage of the following fft2D launched right
-    // behind it -- the contract (stage results cached for isac_fft2d_submit_cached_dev) holds for every carrier.  A CUT window that
-    // leaves the map is fft2D's error to report: nothing is cached then.
+  // No fused kernel: the plain synthesis, then (cache_rows) the range stage of the following fft2D launched right behind it -- the contract (stage results cached for
+  // isac_fft2d_submit_cached_dev) holds for every carrier and noise mode.
+  auto plain_then_range = [&](bool cache_rows) -> int {
     int32_t lo = 0;
     ISAC_TRY(isac_mono_static_sensing_dev(ctx, d_tx_wave, T, tx_dim_l, carrier, rp, los, noise_mode, d_noise_unit, seed, d_echo_grid, &lo));
     if (l_out) *l_out = lo;
-    lazy_owned_done(lo);
-    const bool window_ok = row_lo >= 0 && row_hi < ep->n_ifft && cf->row1 >= cf->row0 && ep->n_ifft >= g.n_sc && (ep->n_ifft & (ep->n_ifft - 1)) == 0;
-    if (!window_ok) return ISAC_OK;
+    if (lazy) ctx->lazy.set_owned(g.n_sc, lo, rp->n_ants);
+    if (!cache_rows) return ISAC_OK;
     return isac_range_stage_into_cache(ctx, ep, cf, (const c64*)d_echo_grid, (const c64*)d_tx_grid, g.n_sc, lo, rp->n_ants);
-  }
+  };
+  // other numerologies (Nfft != 4096 or nIFFT != Nfft).  A CUT window that leaves the map is fft2D's error to report: nothing is cached then.
+  if (!fusable) return plain_then_range(rows_ok && ep->n_ifft >= g.n_sc && (ep->n_ifft & (ep->n_ifft - 1)) == 0);
   if (noise_mode < ISAC_NOISE_NONE || noise_mode > ISAC_NOISE_INJECTED_SPECTRAL) return fail(ctx, ISAC_ERR_INVALID_ARG, "unknown noise mode");
   if (noise_mode == ISAC_NOISE_INJECTED_SPECTRAL && !d_noise_unit) return fail(ctx, ISAC_ERR_INVALID_ARG, "noise buffer missing");
-  const bool spectral = spectral_mode(noise_mode);
-  if (!spectral) {
-    // time-domain noise modes (NONE / INJECTED / PHILOX per sample): the per-antenna demodulation kernel, then the range stage of the
-    // following fft2D launched right behind it -- same contract (cached range rows for isac_fft2d_submit_cached_dev), no fused kernel
-    // (the 256-thread demodulator and the 512-thread range transform do not share a workgroup shape; the fused time-domain kernel of
-    // round 1 was slower than the two launches anyway).
-    int32_t lo = 0;
-    ISAC_TRY(isac_mono_static_sensing_dev(ctx, d_tx_wave, T, tx_dim_l, carrier, rp, los, noise_mode, d_noise_unit, seed, d_echo_grid, &lo));
-    if (l_out) *l_out = lo;
-    lazy_owned_done(lo);
-    return isac_range_stage_into_cache(ctx, ep, cf, (const c64*)d_echo_grid, (const c64*)d_tx_grid, g.n_sc, lo, rp->n_ants);
-  }
+  // time-domain noise modes (NONE / INJECTED / PHILOX per sample): the per-antenna demodulation kernel and the range kernel, no fused kernel (the 256-thread demodulator
+  // and the 512-thread range transform do not share a workgroup shape; the fused time-domain kernel of round 1 was slower than the two launches anyway).
+  if (!spectral_mode(noise_mode)) return plain_then_range(true);
   int Q = 0, L_whole = 0;
   // (tried in round 6 and removed: the front of the call -- beam-sum, coefficient vectors, Q x L demodulation FFTs -- on a lowest-priority third stream per context, so that it
   //  would yield to the compute-bound kernels of the CPIs ahead: 24 streams on 16 hardware queues collapse the pipelined rate to 4-5 k slots/s whatever GPU_MAX_HW_QUEUES says,
   //  and with 4-5 contexts (12-15 streams) it is 7-15 % slower than two streams per context; profiles/r06_lazy_first_measurements.txt)
   ISAC_TRY(spectral_prepare(ctx, (const c64*)d_tx_wave, T, rp, los, g, &Q, &L_whole));
-  const int A = rp->n_ants;
-  if (L_whole <= 0) return fail(ctx, ISAC_ERR_SHORT_WAVEFORM, "waveform shorter than one OFDM symbol");
-  const int L_out = L_whole < tx_dim_l ? tx_dim_l : L_whole;
-  if (l_out) *l_out = L_out;
-  const int nr = row_hi - row_lo + 1;
+  const int A = rp->n_ants, row_lo = cr.row_lo, nr = cr.nr;
+  const int L_out = padded_symbols(L_whole, tx_dim_l, l_out);
   ISAC_TRY(ensure(ctx, ctx->ymid, sizeof(c64) * (size_t)nr * L_out * A));
   if (L_out > L_whole) {
     if (!lazy_native) ISAC_HIP(hipMemsetAsync(d_echo_grid, 0, sizeof(c64) * (size_t)g.n_sc * L_out * A, ctx->stream));
@@ -840,59 +823,28 @@ extern "C" int isac_mono_static_sensing_fused_dev(isac_ctx* ctx, const isac_c64*
   const double *wk = nullptr, *wr = nullptr;
   ISAC_TRY(isac_get_w512_pack(ctx, &tw));            // Fft4096W's packed LDS tables (the fused kernel needs nothing else of the 4096 table)
   ISAC_TRY(isac_get_windows(ctx, g.n_sc, ep->n_ifft, &wk, &wr));
-  const double n0s = std::sqrt(rp->n0 / 2.0);
-  if (ctx->profile && !ctx->profile_cov) ISAC_HIP(hipEventRecord(ctx->ev_k0, ctx->stream));   // isac_profile_*: brackets exactly the fused kernel below
+  const double sig = std::sqrt(rp->n0 / 2.0) * std::sqrt((double)g.nfft);
+  if (!ctx->profile_cov) ISAC_TRY(profile_begin(ctx));   // isac_profile_*: brackets exactly the fused kernel below
   timeline_mark(ctx, 2, ctx->stream);
-  {
-    const double sig = n0s * std::sqrt((double)g.nfft);
-    const size_t lds = sizeof(c64) * Fft4096W::LDS_ELEMS;
-    const dim3 gr((unsigned)spectral_grid_size(L_whole, A)), bl(Fft4096W::NT);
-    const c64* D = (const c64*)ctx->dgrid.p;
-    const c64* srq = (const c64*)ctx->steer.p + (size_t)A * Q;
-#define ISAC_SPEC(QT, NZ)                                                                                                            \
-  do {                                                                                                                               \
-    auto kern = echo_range_kernel<QT, NZ>;                                                                                           \
-    ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(kern), lds));                                                              \
-    hipLaunchKernelGGL(kern, gr, bl, lds, ctx->stream, g.n_sc, L_whole, L_out, A, Q, D, srq, sig, seed, (const c64*)d_noise_unit, tw,   \
-                       (c64*)d_echo_grid, (const c64*)d_tx_grid, wk, wr, 1.0 / ep->n_ifft, std::sqrt((double)ep->n_ifft),   \
-                       row_lo, nr, (c64*)ctx->ymid.p);                                                                               \
-  } while (0)
-#define ISAC_SPEC_SL(QT, NZ)                                                                                                         \
-  do {                                                                                                                               \
-    auto kern = echo_range_sl_kernel<QT, NZ>;                                                                                        \
-    ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(kern), lds));                                                              \
-    hipLaunchKernelGGL(kern, gr, bl, lds, ctx->stream, g.n_sc, L_whole, L_out, A, D, srq, sig, seed, (const c64*)d_noise_unit, tw,      \
-                       (c64*)d_echo_grid, (const c64*)d_tx_grid, wk, wr, 1.0 / ep->n_ifft, std::sqrt((double)ep->n_ifft),   \
-                       row_lo, nr, (c64*)ctx->ymid.p);                                                                               \
-  } while (0)
-#define ISAC_SPEC_SL_LAZY(QT)                                                                                                        \
-  do {                                                                                                                               \
-    auto kern = echo_range_sl_kernel<QT, 1, false>;                                                                                  \
-    ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(kern), lds));                                                              \
-    hipLaunchKernelGGL(kern, gr, bl, lds, ctx->stream, g.n_sc, L_whole, L_out, A, D, srq, sig, seed, (const c64*)nullptr, tw,        \
-                       (c64*)nullptr, (const c64*)d_tx_grid, wk, wr, 1.0 / ep->n_ifft, std::sqrt((double)ep->n_ifft),                \
-                       row_lo, nr, (c64*)ctx->ymid.p);                                                                               \
-  } while (0)
-#define ISAC_SPEC_Q(QT) do { if (noise_mode == ISAC_NOISE_PHILOX_SPECTRAL) ISAC_SPEC(QT, 1); else ISAC_SPEC(QT, 2); } while (0)
-#define ISAC_SPEC_SL_Q(QT) do { if (lazy_native) ISAC_SPEC_SL_LAZY(QT); else if (noise_mode == ISAC_NOISE_PHILOX_SPECTRAL) ISAC_SPEC_SL(QT, 1); else ISAC_SPEC_SL(QT, 2); } while (0)
-    switch (Q) { case 1: ISAC_SPEC_SL_Q(1); break; case 2: ISAC_SPEC_SL_Q(2); break; case 3: ISAC_SPEC_Q(3); break; case 4: ISAC_SPEC_Q(4); break; default: ISAC_SPEC_Q(0); break; }
-#undef ISAC_SPEC_SL_LAZY
-#undef ISAC_SPEC_SL_Q
-#undef ISAC_SPEC_SL
-#undef ISAC_SPEC_Q
-#undef ISAC_SPEC
-    ISAC_HIP(hipGetLastError());
-  }
-  if (ctx->profile && !ctx->profile_cov) { ISAC_HIP(hipEventRecord(ctx->ev_k1, ctx->stream)); ctx->profile_recorded = true; }
+  // the two kernels' argument lists differ in the run-time target count `q_rt` alone (the straight-line form has none)
+  auto launch = [&](auto kern, auto... q_rt) {
+    return launch_echo_range(ctx, kern, L_whole, A, g.n_sc, L_whole, L_out, A, q_rt..., (const c64*)ctx->dgrid.p, (const c64*)ctx->steer.p + (size_t)A * Q, sig, seed,
+                             (const c64*)d_noise_unit, tw, (c64*)d_echo_grid, (const c64*)d_tx_grid, wk, wr, 1.0 / ep->n_ifft, std::sqrt((double)ep->n_ifft), row_lo, nr,
+                             (c64*)ctx->ymid.p);
+  };
+  const bool philox = noise_mode == ISAC_NOISE_PHILOX_SPECTRAL;
+  ISAC_TRY(echo_dispatch<4>(Q, [&](auto qc) {
+    constexpr int QT = decltype(qc)::value;
+    if constexpr (QT == 1 || QT == 2)       // the straight-line form; lazy_native: without the echoGrid store (d_echo_grid is NULL, the noise is Philox)
+      return launch(lazy_native ? echo_range_sl_kernel<QT, 1, false> : philox ? echo_range_sl_kernel<QT, 1> : echo_range_sl_kernel<QT, 2>);
+    else
+      return launch(philox ? echo_range_kernel<QT, 1> : echo_range_kernel<QT, 2>, Q);
+  }));
+  if (!ctx->profile_cov) ISAC_TRY(profile_end(ctx));
   timeline_mark(ctx, 3, ctx->stream);
-  RangeCache& rc = ctx->range_cache;
-  rc.rx = d_echo_grid; rc.tx = d_tx_grid; rc.K = g.n_sc; rc.L = L_out; rc.A = A; rc.n_ifft = ep->n_ifft; rc.row_lo = row_lo; rc.nr = nr;   // (rc.rx == NULL: the native lazy grid)
-  rc.valid = true;
-  if (lazy) {
-    LazyEcho& lz = ctx->lazy;
-    lz.valid = true; lz.native = lazy_native; lz.K = g.n_sc; lz.L_whole = lazy_native ? L_whole : L_out; lz.L_out = L_out; lz.A = A; lz.Q = Q;
-    lz.sig = n0s * std::sqrt((double)g.nfft); lz.seed = seed;
-  }
+  ctx->range_cache.set(d_echo_grid, d_tx_grid, g.n_sc, L_out, A, ep->n_ifft, row_lo, nr);   // (rx == NULL: the native lazy grid)
+  if (lazy_native) ctx->lazy.set_native(g.n_sc, L_whole, L_out, A, Q, sig, seed);
+  else if (lazy) ctx->lazy.set_owned(g.n_sc, L_out, A);
   return ISAC_OK;
 }
 
@@ -912,10 +864,9 @@ extern "C" int isac_echo_grid_materialize_dev(isac_ctx* ctx, isac_c64* d_echo_gr
   }
   if (lz.L_out > lz.L_whole) ISAC_HIP(hipMemsetAsync(d_echo_grid, 0, bytes, ctx->stream));
   OfdmGeom g{4096, lz.K, 0, 0, 0};
-  switch (lz.Q) {
-    case 1: return launch_echo_spectral<1>(ctx, g, lz.A, lz.L_whole, lz.L_out, lz.Q, ISAC_NOISE_PHILOX_SPECTRAL, nullptr, lz.sig, lz.seed, (c64*)d_echo_grid);
-    default: return launch_echo_spectral<2>(ctx, g, lz.A, lz.L_whole, lz.L_out, lz.Q, ISAC_NOISE_PHILOX_SPECTRAL, nullptr, lz.sig, lz.seed, (c64*)d_echo_grid);
-  }
+  return echo_dispatch<1>(lz.Q, [&](auto qc) {     // a native lazy grid has one or two LoS targets
+    return launch_echo_spectral<(decltype(qc)::value == 1 ? 1 : 2)>(ctx, g, lz.A, lz.L_whole, lz.L_out, lz.Q, ISAC_NOISE_PHILOX_SPECTRAL, nullptr, lz.sig, lz.seed, (c64*)d_echo_grid);
+  });
 }
 
 extern "C" int isac_ofdm_demodulate_dev(isac_ctx* ctx, const isac_c64* d_wave, int64_t T, int32_t A,
@@ -942,7 +893,7 @@ static int launch_mod(isac_ctx* ctx, const OfdmGeom& g, const ModIo& io, int A, 
   size_t lds = sizeof(c64) * FFT::LDS_ELEMS;
   auto kern = mod_kernel<FFT>;
   ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(kern), lds));
-  hipLaunchKernelGGL(kern, dim3(fft_grid(L * A)), dim3(256), lds, ctx->stream, g, io, A, L, tw, grid, scale, wave, head, rise);
+  hipLaunchKernelGGL(kern, dim3((unsigned)(L * A)) /* one column per workgroup */, dim3(256), lds, ctx->stream, g, io, A, L, tw, grid, scale, wave, head, rise);
   ISAC_HIP(hipGetLastError());
   return ISAC_OK;
 }

@@ -112,6 +112,9 @@ struct RangeCache {  // range rows pre-computed by the fused monoStaticSensing c
   const void* rx = nullptr;
   const void* tx = nullptr;
   int K = 0, L = 0, A = 0, n_ifft = 0, row_lo = 0, nr = 0;
+  void set(const void* rx_, const void* tx_, int K_, int L_, int A_, int n_ifft_, int row_lo_, int nr_) {   // (rx_ == NULL: the native lazy grid)
+    *this = RangeCache{true, rx_, tx_, K_, L_, A_, n_ifft_, row_lo_, nr_};
+  }
   // a write of [p, p + bytes) through the library (copy, memset, free) that touches either cached grid drops the cache
   void touch(const void* p, size_t bytes) {
     if (!valid) return;
@@ -131,6 +134,8 @@ struct LazyEcho {
   int K = 0, L_whole = 0, L_out = 0, A = 0, Q = 0;
   double sig = 0.0;
   unsigned long long seed = 0;
+  void set_owned(int K_, int L_, int A_) { *this = LazyEcho{true, false, K_, L_, L_, A_, 0, 0.0, 0}; }      // the grid is in ctx->echo_own
+  void set_native(int K_, int L_whole_, int L_out_, int A_, int Q_, double sig_, unsigned long long seed_) { *this = LazyEcho{true, true, K_, L_whole_, L_out_, A_, Q_, sig_, seed_}; }
 };
 
 // pinned host -> device parameter staging: a small ring of slots, each guarded by its own event, so that a call's uploads do not wait for the

@@ -27,6 +27,9 @@ int isac_get_windows(isac_ctx* ctx, int K, int n_ifft, const double** win_k, con
 // ---------------------------------------------------------------- rdm.hip
 int isac_rdm_power_window(isac_ctx* ctx, const isac_est_params* ep, const isac_cfar_config* cf, const isac::c64* d_rx, const isac::c64* d_tx, int K, int L, int A, int* nr_out, int* nc_out, bool use_cached_range);
 int isac_cfar_window(isac_ctx* ctx, const isac_est_params* ep, const isac_cfar_config* cf, int nr, int nc, int A, int cap);
+namespace isac { struct CutRows { int row_lo, nr; }; }   // rows [row_lo, row_lo + nr) of the range-Doppler map (0-based): the CUT rows +- (guard + training)
+bool cut_rows_ok(const isac_est_params* ep, const isac_cfar_config* cf, isac::CutRows* out);              // false: the window leaves the map
+int cut_rows(isac_ctx* ctx, const isac_est_params* ep, const isac_cfar_config* cf, isac::CutRows* out);   // ... as ISAC_ERR_CFAR_WINDOW
 int isac_range_stage_into_cache(isac_ctx* ctx, const isac_est_params* ep, const isac_cfar_config* cf, const isac::c64* d_rx, const isac::c64* d_tx, int K, int L, int A);
 // ---------------------------------------------------------------- cov.hip
 int isac_covariance_on(isac_ctx* ctx, hipStream_t st, const isac_c64* d_grid, int64_t N, int32_t A, isac_c64* d_Ra);

@@ -526,19 +526,47 @@ using namespace isac;
 
 static double cfar_alpha(int n_train, double pfa) { return n_train * (std::pow(pfa, -1.0 / n_train) - 1.0); }
 
-static unsigned fft_grid2(int n_cols) { return (unsigned)n_cols; }   // one column per workgroup
-
 template <class FFT>
-static int launch_range(isac_ctx* ctx, hipStream_t st, const c64* rx, const c64* tx, int K, int L, int A, const c64* tw,
-                        const double* wk, const double* wr, int n_ifft, int row_lo, int n_rows, c64* ymid) {
+static int launch_range(isac_ctx* ctx, const c64* rx, const c64* tx, int K, int L, int A, const c64* tw, const double* wk, const double* wr, int n_ifft,
+                        int row_lo, int n_rows, c64* ymid) {
   size_t lds = sizeof(c64) * FFT::LDS_ELEMS;
   auto kern = range_kernel<FFT>;
   ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(kern), lds));
   if (FFT::kPackedTable) ISAC_TRY(isac_get_w512_pack(ctx, &tw));          // the 512-thread transform builds everything from its packed table
-  hipLaunchKernelGGL(kern, dim3(fft_grid2(L * A)), dim3(FFT::NT), lds, st, rx, tx, K, L, A, tw, wk, wr, 1.0 / n_ifft,
+  hipLaunchKernelGGL(kern, dim3((unsigned)(L * A)) /* one column per workgroup */, dim3(FFT::NT), lds, ctx->stream, rx, tx, K, L, A, tw, wk, wr, 1.0 / n_ifft,
                      std::sqrt((double)n_ifft), row_lo, n_rows, ymid);
   ISAC_HIP(hipGetLastError());
   return ISAC_OK;
+}
+
+// The rows of the range-Doppler map the CFAR stage can touch: CUT rows +- (guard + training), 0-based.  false: the window leaves the map.
+bool cut_rows_ok(const isac_est_params* ep, const isac_cfar_config* cf, CutRows* out) {
+  const int hr = cf->guard[0] + cf->train[0];
+  const int row_lo = cf->row0 - 1 - hr, row_hi = cf->row1 - 1 + hr;   // 0-based inclusive
+  *out = CutRows{row_lo, row_hi - row_lo + 1};
+  return row_lo >= 0 && row_hi < ep->n_ifft;
+}
+int cut_rows(isac_ctx* ctx, const isac_est_params* ep, const isac_cfar_config* cf, CutRows* out) {
+  if (!cut_rows_ok(ep, cf, out)) return fail(ctx, ISAC_ERR_CFAR_WINDOW, "CUT training window exceeds the range-Doppler map");
+  return ISAC_OK;
+}
+
+// Range stage (conj-multiply + Kaiser window + nIFFT-point IFFT + row selection + range-axis window, fft2D.m:37-45) of every (symbol, antenna) column:
+// rows [row_lo, row_lo + nr) into dst [nr x L x A], sized here.
+static int range_stage(isac_ctx* ctx, const isac_est_params* ep, const c64* rx, const c64* tx, int K, int L, int A, int row_lo, int nr, DevBuf& dst) {
+  const int n_ifft = ep->n_ifft;
+  const c64* tw = nullptr;
+  const double *wk = nullptr, *wr = nullptr;
+  ISAC_TRY(isac_get_twiddles(ctx, n_ifft, &tw));
+  ISAC_TRY(isac_get_windows(ctx, K, n_ifft, &wk, &wr));
+  ISAC_TRY(ensure(ctx, dst, sizeof(c64) * (size_t)nr * L * A));
+  ISAC_FFT_DISPATCH_RANGE(n_ifft, ISAC_TRY((launch_range<FFT>(ctx, rx, tx, K, L, A, tw, wk, wr, n_ifft, row_lo, nr, (c64*)dst.p))));
+  return ISAC_OK;
+}
+// ... of the CUT rows, into ctx->ymid
+static int range_stage_cut(isac_ctx* ctx, const isac_est_params* ep, const isac_cfar_config* cf, const c64* rx, const c64* tx, int K, int L, int A, CutRows* cr) {
+  ISAC_TRY(cut_rows(ctx, ep, cf, cr));
+  return range_stage(ctx, ep, rx, tx, K, L, A, cr->row_lo, cr->nr, ctx->ymid);
 }
 
 // Range + Doppler + power window for the CUT rectangle.  Leaves pwin [nr x nc x A] in ctx->pwin.
@@ -569,19 +597,15 @@ static bool tail_fusable(isac_ctx* ctx, const isac_est_params* ep, const isac_cf
 int isac_rdm_power_window(isac_ctx* ctx, const isac_est_params* ep, const isac_cfar_config* cf, const c64* d_rx,
                           const c64* d_tx, int K, int L, int A, int* nr_out, int* nc_out, bool use_cached_range) {
   const int n_ifft = ep->n_ifft, n_fft = ep->n_fft;
-  const int hr = cf->guard[0] + cf->train[0], hc = cf->guard[1] + cf->train[1];
-  const int row_lo = cf->row0 - 1 - hr, row_hi = cf->row1 - 1 + hr;   // 0-based inclusive
-  const int col_lo = cf->col0 - 1 - hc, col_hi = cf->col1 - 1 + hc;
+  const int hc = cf->guard[1] + cf->train[1];
+  const int col_lo = cf->col0 - 1 - hc, col_hi = cf->col1 - 1 + hc;   // 0-based inclusive
   if (cf->row1 < cf->row0 || cf->col1 < cf->col0) return fail(ctx, ISAC_ERR_INVALID_ARG, "empty CUT rectangle");
-  if (row_lo < 0 || row_hi >= n_ifft || col_lo < 0 || col_hi >= n_fft)
-    return fail(ctx, ISAC_ERR_CFAR_WINDOW, "CUT training window exceeds the range-Doppler map");
-  const int nr = row_hi - row_lo + 1, nc = col_hi - col_lo + 1;
-  const c64 *tw = nullptr, *twd = nullptr;
-  const double *wk = nullptr, *wr = nullptr;
-  ISAC_TRY(isac_get_twiddles(ctx, n_ifft, &tw));
+  CutRows cr;
+  ISAC_TRY(cut_rows(ctx, ep, cf, &cr));
+  if (col_lo < 0 || col_hi >= n_fft) return fail(ctx, ISAC_ERR_CFAR_WINDOW, "CUT training window exceeds the range-Doppler map");
+  const int row_lo = cr.row_lo, nr = cr.nr, nc = col_hi - col_lo + 1;
+  const c64* twd = nullptr;
   ISAC_TRY(isac_get_twiddles(ctx, n_fft, &twd));
-  ISAC_TRY(isac_get_windows(ctx, K, n_ifft, &wk, &wr));
-  ISAC_TRY(ensure(ctx, ctx->ymid, sizeof(c64) * (size_t)nr * L * A));
   ISAC_TRY(ensure(ctx, ctx->pwin, sizeof(double) * (size_t)nr * nc * A));
   {
     // Range rows already produced by isac_mono_static_sensing_fused_dev are consumed only on the caller's explicit request
@@ -594,9 +618,7 @@ int isac_rdm_power_window(isac_ctx* ctx, const isac_est_params* ep, const isac_c
     if (use_cached_range && !hit)
       return fail(ctx, ISAC_ERR_INVALID_ARG, "fft2d_submit_cached: no range rows cached for these grids / parameters on this context "
                                               "(call isac_mono_static_sensing_fused_dev with the same echoGrid, txGrid, est and cfar blocks first)");
-    if (!use_cached_range)
-      ISAC_FFT_DISPATCH_RANGE(n_ifft, ISAC_TRY((launch_range<FFT>(ctx, ctx->stream, d_rx, d_tx, K, L, A, tw, wk, wr, n_ifft, row_lo, nr,
-                                                            (c64*)ctx->ymid.p))));
+    if (!use_cached_range) ISAC_TRY(range_stage(ctx, ep, d_rx, d_tx, K, L, A, row_lo, nr, ctx->ymid));
   }
   const int Lu = L < n_fft ? L : n_fft;
   if (n_fft == 256) {
@@ -726,48 +748,25 @@ extern "C" int isac_cfar2d_ca(isac_ctx* ctx, const double* P, int32_t n_rows, in
   return ISAC_OK;
 }
 
-// Range stage alone (conj-multiply + Kaiser window + nIFFT-point IFFT + row selection + range-axis
-// window, fft2D.m:37-45) for every (symbol, antenna) column -- the dominant HBM-bound kernel of fft2D;
-// exposed so bench.py can time exactly this launch with HIP events for the roofline entry.
 // Range stage into the context's cache (used by the fused echo entry for the time-domain noise modes): the rows the next
 // isac_fft2d_submit_cached_dev on the same grids consumes.
 int isac_range_stage_into_cache(isac_ctx* ctx, const isac_est_params* ep, const isac_cfar_config* cf, const c64* d_rx, const c64* d_tx, int K,
                                 int L, int A) {
-  const int n_ifft = ep->n_ifft;
-  const int hr = cf->guard[0] + cf->train[0];
-  const int row_lo = cf->row0 - 1 - hr, row_hi = cf->row1 - 1 + hr;
-  if (row_lo < 0 || row_hi >= n_ifft) return fail(ctx, ISAC_ERR_CFAR_WINDOW, "CUT training window exceeds the range-Doppler map");
-  const int nr = row_hi - row_lo + 1;
-  const c64* tw = nullptr;
-  const double *wk = nullptr, *wr = nullptr;
-  ISAC_TRY(isac_get_twiddles(ctx, n_ifft, &tw));
-  ISAC_TRY(isac_get_windows(ctx, K, n_ifft, &wk, &wr));
-  ISAC_TRY(ensure(ctx, ctx->ymid, sizeof(c64) * (size_t)nr * L * A));
-  ISAC_FFT_DISPATCH_RANGE(n_ifft, ISAC_TRY((launch_range<FFT>(ctx, ctx->stream, d_rx, d_tx, K, L, A, tw, wk, wr, n_ifft, row_lo, nr, (c64*)ctx->ymid.p))));
-  RangeCache& rc = ctx->range_cache;
-  rc.rx = d_rx; rc.tx = d_tx; rc.K = K; rc.L = L; rc.A = A; rc.n_ifft = n_ifft; rc.row_lo = row_lo; rc.nr = nr;
-  rc.valid = true;
+  CutRows cr;
+  ISAC_TRY(range_stage_cut(ctx, ep, cf, d_rx, d_tx, K, L, A, &cr));
+  ctx->range_cache.set(d_rx, d_tx, K, L, A, ep->n_ifft, cr.row_lo, cr.nr);
   return ISAC_OK;
 }
 
+// Range stage alone for every (symbol, antenna) column -- the dominant HBM-bound kernel of fft2D; exposed so bench.py can time exactly this launch
+// with HIP events for the roofline entry.
 extern "C" int isac_fft2d_range_stage_dev(isac_ctx* ctx, const isac_est_params* ep, const isac_cfar_config* cf,
                                           const isac_c64* d_rx_grid, const isac_c64* d_tx_grid, int32_t K, int32_t L, int32_t A) {
   ISAC_ENTER(ctx);
   if (!ep || !cf || !d_rx_grid || !d_tx_grid) return fail(ctx, ISAC_ERR_INVALID_ARG, "NULL argument");
   ctx->range_cache.valid = false;
-  const int n_ifft = ep->n_ifft;
-  const int hr = cf->guard[0] + cf->train[0];
-  const int row_lo = cf->row0 - 1 - hr, row_hi = cf->row1 - 1 + hr;
-  if (row_lo < 0 || row_hi >= n_ifft) return fail(ctx, ISAC_ERR_CFAR_WINDOW, "CUT training window exceeds the range-Doppler map");
-  const int nr = row_hi - row_lo + 1;
-  const c64* tw = nullptr;
-  const double *wk = nullptr, *wr = nullptr;
-  ISAC_TRY(isac_get_twiddles(ctx, n_ifft, &tw));
-  ISAC_TRY(isac_get_windows(ctx, K, n_ifft, &wk, &wr));
-  ISAC_TRY(ensure(ctx, ctx->ymid, sizeof(c64) * (size_t)nr * L * A));
-  ISAC_FFT_DISPATCH_RANGE(n_ifft, ISAC_TRY((launch_range<FFT>(ctx, ctx->stream, (const c64*)d_rx_grid, (const c64*)d_tx_grid, K, L, A, tw,
-                                                        wk, wr, n_ifft, row_lo, nr, (c64*)ctx->ymid.p))));
-  return ISAC_OK;
+  CutRows cr;
+  return range_stage_cut(ctx, ep, cf, (const c64*)d_rx_grid, (const c64*)d_tx_grid, K, L, A, &cr);
 }
 
 extern "C" int isac_rdm_plane_dev(isac_ctx* ctx, const isac_est_params* ep, const isac_c64* d_rx_grid,
@@ -775,16 +774,11 @@ extern "C" int isac_rdm_plane_dev(isac_ctx* ctx, const isac_est_params* ep, cons
   ISAC_ENTER(ctx);
   if (!ep || !d_rx_grid || !d_tx_grid || !d_rdm || ant < 0 || ant >= A) return fail(ctx, ISAC_ERR_INVALID_ARG, "bad arguments");
   const int n_ifft = ep->n_ifft, n_fft = ep->n_fft;
-  const c64 *tw = nullptr, *twd = nullptr;
-  const double *wk = nullptr, *wr = nullptr;
-  ISAC_TRY(isac_get_twiddles(ctx, n_ifft, &tw));
+  const c64* twd = nullptr;
   ISAC_TRY(isac_get_twiddles(ctx, n_fft, &twd));
-  ISAC_TRY(isac_get_windows(ctx, K, n_ifft, &wk, &wr));
-  ISAC_TRY(ensure(ctx, ctx->stage_a, sizeof(c64) * (size_t)n_ifft * L));
   const c64* rx = (const c64*)d_rx_grid + (size_t)K * L * ant;
   const c64* tx = (const c64*)d_tx_grid + (size_t)K * L * ant;
-  ISAC_FFT_DISPATCH_RANGE(n_ifft, ISAC_TRY((launch_range<FFT>(ctx, ctx->stream, rx, tx, K, L, 1, tw, wk, wr, n_ifft, 0, n_ifft,
-                                                        (c64*)ctx->stage_a.p))));
+  ISAC_TRY(range_stage(ctx, ep, rx, tx, K, L, 1, 0, n_ifft, ctx->stage_a));     // one antenna plane, every row
   hipLaunchKernelGGL(doppler_full_kernel, dim3(cdiv((long long)n_ifft * n_fft, 256)), dim3(256), 0, ctx->stream,
                      (const c64*)ctx->stage_a.p, n_ifft, L, n_fft, twd, std::sqrt((double)n_fft), (c64*)d_rdm);
   ISAC_HIP(hipGetLastError());

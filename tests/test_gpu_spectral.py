@@ -141,6 +141,72 @@ def test_fused_spectral_path_is_identical_and_reuse_is_explicit(pkg, ctx):
     assert np.array_equal(e3.numpy(), e4.numpy()) and np.all(e3.numpy()[:, -1, :] == 0)
 
 
+_RANGE_STAGE_TARGETS = (((100.0, 20.0, 1.5), 7.0), ((180.0, -150.0, 1.5), -4.0), ((260.0, 60.0, 1.5), 2.0), ((70.0, -30.0, 1.5), -9.0), ((330.0, -40.0, 1.5), 5.0))
+_RANGE_STAGE_ZONES = {"default": None, "straddle": ((50.0, 700.0), (-50.0, 50.0))}     # detectionArea [m; m/s]: radar.m:10, or range rows on both sides of row 512
+_range_stage_cache = {}
+
+
+def _block_of_rows(row_lo, n_rows):
+    """Fft4096W::block_of_rows (csrc/fft_lds.hpp) restated: the 512-row output block that holds all the rows, or -1."""
+    return (row_lo >> 9) if n_rows > 0 and (row_lo >> 9) == ((row_lo + n_rows - 1) >> 9) else -1
+
+
+def _range_stage_scene(q):
+    """Scene, injected noise field and the time-domain oracle's echo grid for q LoS targets: made once, shared by both windows, never written to."""
+    if q not in _range_stage_cache:
+        sc = make_scene(n_ants=2, n_slots=2, nrb=273, targets=tuple(t for t, _ in _RANGE_STAGE_TARGETS[:q]), velocity=tuple(v for _, v in _RANGE_STAGE_TARGETS[:q]),
+                        seed=13, with_noise=False, num_slots_param=2)      # nFFT = 32: the 14 live symbols resolve a target from its CFAR training ring
+        sc.tx_grid[:, 14:, :] = 0                             # the second slot as a zero-filled 'S' slot (gNBPhy.m:609-612): its columns take the `live` shortcut
+        sc.tx_wave = np.asfortranarray(O.ofdm_modulate(sc.tx_grid, sc.wave.Nfft, 30) * sc.amp)
+        w = unit_noise(sc.tx_grid.shape, 100 + q)
+        tnoise = spectral_to_time_noise(w, sc.T, 4096, 30, sc.rp.fc, sc.rp.fs)
+        want_echo = O.mono_static_sensing(sc.tx_wave, sc.tx_grid.shape, sc.carrier, sc.rp, sc.los, tnoise, nfft=4096)
+        for a in (sc.tx_grid, sc.tx_wave, w, want_echo):
+            a.setflags(write=False)
+        _range_stage_cache[q] = (sc, w, want_echo)
+    return _range_stage_cache[q]
+
+
+@pytest.mark.parametrize("zone", ["default", "straddle"])
+@pytest.mark.parametrize("q", [1, 3, 5])
+def test_fused_range_stage_equals_plain_and_oracle(pkg, ctx, q, zone):
+    """The range stage (fft2D.m:37-45) as echo_range_sl_kernel<1>, echo_range_kernel<3> and echo_range_kernel<0> run it inside the fused call, against range_kernel
+    in the plain sequence (bit for bit) and against the oracle (RTOL): with the CUT rows inside one 512-row block of the IFFT output (one output per thread) and on
+    both sides of row 512 (the full drain), live columns and the all-zero columns of a zeroed transmit slot.  The three kernels state the stage separately and
+    promise the same bits; their equality alone would not show any of them right: the oracle comparison does."""
+    import copy
+    sc, w, want_echo = _range_stage_scene(q)
+    assert sc.wave.Nfft == 4096 and sc.los.sum() == q
+    cell = copy.copy(sc.cell)
+    if _RANGE_STAGE_ZONES[zone] is not None:
+        cell.detectionArea = np.asarray(_RANGE_STAGE_ZONES[zone], dtype=np.float64)
+    rp = pkg.sensing.radarParams(cell, sc.carrier, sc.wave)
+    cf = pkg.sensing.detection.cfar2D(rp)
+    hr = cf.cfarDetector2D.GuardBandSize[0] + cf.cfarDetector2D.TrainingBandSize[0]
+    row0, row1 = int(cf.CUTIdx[0].min()), int(cf.CUTIdx[0].max())
+    blk = _block_of_rows(row0 - 1 - hr, row1 - row0 + 1 + 2 * hr)
+    assert (blk == 0) if zone == "default" else (blk < 0)
+    d_wave, d_txg = ctx.to_device(sc.tx_wave), ctx.to_device(sc.tx_grid)
+    for kw in (dict(spectral_noise=ctx.to_device(w)), dict(seed=4321 + q, noise_domain="spectral")):
+        e0 = pkg.sensing.monoStaticSensing(d_wave, sc.tx_grid.shape, sc.carrier, rp, sc.los, nfft=4096, **kw)
+        est0, dbg0 = pkg.sensing.estimation.fft2D(rp, cf, e0, d_txg, return_debug=True)
+        e1 = pkg.sensing.monoStaticSensing(d_wave, sc.tx_grid.shape, sc.carrier, rp, sc.los, nfft=4096, fuse_fft2d=(rp, cf, d_txg), **kw)
+        est1, dbg1 = pkg.sensing.estimation.fft2D(rp, cf, e1, d_txg, return_debug=True, reuse_range=True)
+        assert np.array_equal(e0.numpy(), e1.numpy())
+        assert np.array_equal(dbg0.power_window, dbg1.power_window)
+        assert len(dbg0.detections) == len(dbg1.detections) == sc.A and all(np.array_equal(a, b) for a, b in zip(dbg0.detections, dbg1.detections))
+        assert np.array_equal(est0.rngEst, est1.rngEst) and np.array_equal(est0.velEst, est1.velEst) and np.array_equal(est0.aziEst, est1.aziEst)
+        assert est0.rngEst.size >= 1
+        if "spectral_noise" in kw:
+            orp = O.radar_params(cell, sc.carrier, sc.wave)
+            _, odbg = O.fft2d(orp, O.cfar2d_config(orp), want_echo, sc.tx_grid, return_debug=True, rdm_fn=O.rdm_explicit)
+            r0, c0 = dbg0.first_row - 1, dbg0.first_col - 1
+            nr, nc, _ = dbg0.power_window.shape
+            assert nr == row1 - row0 + 1 + 2 * hr and r0 == row0 - 1 - hr
+            assert rel(e0.numpy(), want_echo) < RTOL
+            assert rel(dbg0.power_window, np.abs(odbg.rdm[r0:r0 + nr, c0:c0 + nc, :]) ** 2) < RTOL
+
+
 def test_basic_radar_channel_rejects_spectral_modes(pkg, ctx):
     import ctypes as C
     sc = make_scene(n_ants=2, n_slots=1, nrb=24, with_noise=False)
