@@ -16,6 +16,7 @@ _lock = threading.Lock()
 
 ISAC_ABI_VERSION = 8          # include/isac.h ISAC_ABI_VERSION this binding was written against (checked at load)
 ISAC_MAX_EST = 4096
+ISAC_MAX_TARGETS = 1024
 NOISE_NONE, NOISE_INJECTED, NOISE_PHILOX, NOISE_PHILOX_SPECTRAL, NOISE_INJECTED_SPECTRAL = 0, 1, 2, 3, 4
 OPT_MUSIC_ROUTE, OPT_TAIL_FUSION, OPT_WIDE_ORDER, OPT_CDL_SHARE_SPECTRA, OPT_UPA_DOA = 0, 1, 2, 3, 4   # ISAC_OPT_* of isac_ctx_set_option
 
@@ -107,11 +108,20 @@ class EstResult(C.Structure):
                 ("azi_est", C.c_double * ISAC_MAX_EST), ("ele_est", C.c_double * ISAC_MAX_EST)]
 
 
+class TargetList(C.Structure):
+    _fields_ = [("n_targets", C.c_int32), ("n_total", C.c_int32),
+                ("row", C.c_int32 * ISAC_MAX_TARGETS), ("col", C.c_int32 * ISAC_MAX_TARGETS), ("hits", C.c_int32 * ISAC_MAX_TARGETS),
+                ("rng", C.c_double * ISAC_MAX_TARGETS), ("vel", C.c_double * ISAC_MAX_TARGETS), ("azi", C.c_double * ISAC_MAX_TARGETS),
+                ("power", C.c_double * ISAC_MAX_TARGETS)]
+
+
 # The structs isac_abi_sizeof() knows, in ISAC_SIZEOF_* index order: (C name, mirror).  load() compares every size with the library's.
 ABI_STRUCTS = (("isac_est_result", EstResult), ("isac_est_params", EstParams), ("isac_cfar_config", CfarConfig),
                ("isac_radar_channel_params", RadarChannelParams), ("isac_carrier", Carrier), ("isac_music2d_params", Music2dParams),
                ("isac_csi_report", CsiReport), ("isac_sensing_job", SensingJob), ("isac_srs_report", SrsReport),
                ("isac_rx_frontend_job", RxFrontendJob), ("isac_path_loss_config", PathLossConfig))
+# ... and the ones the additive headers add (include/isac_targets.h): (selector, C name, mirror)
+ABI_STRUCTS_ADDED = ((11, "isac_target_list", TargetList),)
 
 # Every function include/isac.h declares, in the header's order: name -> (restype, argtypes).  load() sets both, so a call with a missing
 # argument (TypeError) or a float for an integer (ctypes.ArgumentError) fails instead of reaching the library, a 64-bit value arrives whole,
@@ -201,6 +211,10 @@ PROTOTYPES = {
     "isac_synth_qpsk_grid_dev": (_INT, (_P, _P, _I32, _I32, _I32, _U64, _I32)),
 }
 EXPORTS = list(PROTOTYPES)
+# What the additive headers declare under the same ABI version (include/isac_targets.h), same typing rule; load() applies both tables.
+PROTOTYPES_ADDED = {
+    "isac_fft2d_get_targets": (_INT, (_P, _P, _P, _I32)),
+}
 
 
 def library_path() -> str:
@@ -227,13 +241,13 @@ def load():
             except Exception:
                 pass
         lib = C.CDLL(_LIB_PATH, mode=C.RTLD_GLOBAL)
-        for name, (restype, argtypes) in PROTOTYPES.items():
+        for name, (restype, argtypes) in {**PROTOTYPES, **PROTOTYPES_ADDED}.items():
             fn = getattr(lib, name)  # AttributeError here = ABI drift between isac.h and the .so
             fn.restype, fn.argtypes = restype, argtypes
         # the library writes whole structs into caller memory: version AND struct sizes must match this binding's mirrors
         if lib.isac_abi_version() != ISAC_ABI_VERSION:
             raise RuntimeError(f"{_LIB_PATH}: ABI version {lib.isac_abi_version()} but this binding was written for {ISAC_ABI_VERSION}; rebuild the library")
-        for which, (name, cls) in enumerate(ABI_STRUCTS):
+        for which, name, cls in [(i, n, c) for i, (n, c) in enumerate(ABI_STRUCTS)] + list(ABI_STRUCTS_ADDED):
             if lib.isac_abi_sizeof(which) != C.sizeof(cls):
                 raise RuntimeError(f"{_LIB_PATH}: sizeof({name}) = {lib.isac_abi_sizeof(which)} in the library, {C.sizeof(cls)} in the binding")
         _lib = lib

@@ -26,6 +26,7 @@ extern "C" int isac_abi_sizeof(int32_t which) {
     case ISAC_SIZEOF_SRS_REPORT: return (int)sizeof(isac_srs_report);
     case ISAC_SIZEOF_RX_FRONTEND_JOB: return (int)sizeof(isac_rx_frontend_job);
     case ISAC_SIZEOF_PATH_LOSS_CONFIG: return (int)sizeof(isac_path_loss_config);
+    case ISAC_SIZEOF_TARGET_LIST: return (int)sizeof(isac_target_list);
     default: return -1;
   }
 }
@@ -325,6 +326,7 @@ static int fft2d_submit(isac_ctx* ctx, const isac_est_params* ep, const isac_cfa
   if (ep->n_ifft < K || (ep->n_ifft & (ep->n_ifft - 1)) || ep->n_fft <= 0 || (ep->n_fft & (ep->n_fft - 1)))
     return fail(ctx, ISAC_ERR_INVALID_ARG, "nIFFT/nFFT must be powers of two with nIFFT >= K");
   ctx->last.valid = false;
+  ctx->tgt.drop();
   const c64* rx = (const c64*)d_rx_grid;
   const c64* tx = (const c64*)d_tx_grid;
   // MUSIC branch on the second stream, concurrent with the range-Doppler/CFAR branch:
@@ -418,6 +420,11 @@ static int fft2d_submit(isac_ctx* ctx, const isac_est_params* ep, const isac_cfa
   pd.d_pcut_full = d_pcut_full; pd.d_ppow_full = d_ppow_full;
   pd.doa = pl; pd.first2d = first2d;
   pd.active = true;
+  TargetSource& ts = ctx->tgt;                        // what isac_fft2d_get_targets reads once this CPI is collected
+  ts.ep = *ep; ts.cfar = *cfar;
+  ts.A = A; ts.L = L; ts.nr = nr; ts.nc = nc; ts.cap = cap;
+  ts.d_sind = pl.d_sind; ts.n_steps = pl.n_steps;
+  ts.state = TargetSource::kSubmitted;
   return ISAC_OK;
 }
 
@@ -515,6 +522,7 @@ extern "C" int isac_fft2d_collect(isac_ctx* ctx, isac_est_result* out) {
   for (size_t i = 0; i < urow.size(); ++i) out->rng_est[i] = (double)(urow[i] - 1) * ep->r_res;               // :77,:81
   for (size_t i = 0; i < ucol.size(); ++i) out->vel_est[i] = ((double)ucol[i] - ep->n_fft / 2.0 - 1.0) * ep->v_res;   // :78,:82
   last.valid = true;
+  if (ctx->tgt.state == TargetSource::kSubmitted) ctx->tgt.state = TargetSource::kCollected;   // (dropped in between: a later call rewrote ymid / pwin / the lists)
   last.spectrum_db.clear();
   if (pd.doa.refused()) return fail(ctx, ISAC_ERR_UNSUPPORTED, kUpaRefused);
   // ---- DoA: music.m:94-104 (ULA), :65-71 (UPA) from the pack's spectrum slot
@@ -679,6 +687,7 @@ extern "C" int isac_ctx_reserve(isac_ctx* ctx, int64_t T, int32_t tx_dim_l, cons
   ctx->range_cache.valid = false;                                                          // the cached rows belong to grids that are about to be freed
   ctx->last.valid = false;                                                                 // isac_fft2d_get_* must not hand out the dry run's detections / window / Ra
   ctx->last.pow_on_device = false;
+  ctx->tgt.drop();                                                                         // nor isac_fft2d_get_targets the dry run's targets
   ctx->profile_recorded = false;                                                           // nor isac_profile_last_kernel_ms the dry run's kernel
   (void)grid.reset(); (void)wave.reset(); (void)echo.reset();
   if (elapsed_ms) *elapsed_ms = ms_since();

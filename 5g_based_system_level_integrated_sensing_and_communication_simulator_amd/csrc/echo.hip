@@ -814,6 +814,7 @@ extern "C" int isac_mono_static_sensing_fused_dev(isac_ctx* ctx, const isac_c64*
   ISAC_TRY(spectral_prepare(ctx, (const c64*)d_tx_wave, T, rp, los, g, &Q, &L_whole));
   const int A = rp->n_ants, row_lo = cr.row_lo, nr = cr.nr;
   const int L_out = padded_symbols(L_whole, tx_dim_l, l_out);
+  ctx->tgt.drop();                                     // the fused kernel rewrites the range rows isac_fft2d_get_targets reads
   ISAC_TRY(ensure(ctx, ctx->ymid, sizeof(c64) * (size_t)nr * L_out * A));
   if (L_out > L_whole) {
     if (!lazy_native) ISAC_HIP(hipMemsetAsync(d_echo_grid, 0, sizeof(c64) * (size_t)g.n_sc * L_out * A, ctx->stream));

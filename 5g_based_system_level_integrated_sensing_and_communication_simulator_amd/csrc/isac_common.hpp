@@ -157,6 +157,19 @@ struct DoaPlan {  // the direction-finding tail of one covariance: what doa_plan
   bool refused() const { return upa && !upa2d; }   // music.m:69 without the option
 };
 
+// What isac_fft2d_get_targets (targets.hip) reads: ctx->ymid, ctx->pwin and the device detection lists (det_cut / det_cnt) as the last fft2D left them, with the geometry
+// they were written for.  fft2d_submit fills it (kSubmitted), isac_fft2d_collect confirms it (kCollected), and every function that rewrites one of those buffers calls
+// drop() first -- a later range stage, echo call or submit on the context makes the target list ISAC_ERR_INVALID_ARG, never stale.
+struct TargetSource {
+  enum { kNone = 0, kSubmitted = 1, kCollected = 2 };
+  int state = kNone;
+  isac_est_params ep{};
+  isac_cfar_config cfar{};
+  int A = 0, L = 0, nr = 0, nc = 0, cap = 0;      // antennas, symbols of ymid, window dims, per-antenna capacity of det_cut
+  const double* d_sind = nullptr; int n_steps = 0;   // MUSIC's ULA scan grid (a cached table of the context)
+  void drop() { state = kNone; }
+};
+
 struct Fft2dPending {  // state between isac_fft2d_submit_dev and isac_fft2d_collect
   bool active = false;
   isac_est_params ep{};
@@ -201,6 +214,8 @@ struct isac_ctx {
   isac::PinnedBuf pinned_csi;   // results of isac_csi_report*: its own buffer, so a CSI call between submit and collect cannot clobber a pending CPI
   isac::Fft2dLast last;
   isac::Fft2dPending pending;
+  isac::TargetSource tgt;            // isac_fft2d_get_targets: validity + geometry of ymid / pwin / det_* (above)
+  isac::DevBuf tgt_scratch;          // ... and its device scratch (hits map, candidate lists, snapshots)
   isac::RangeCache range_cache;
   isac::LazyEcho lazy;               // the echo grid of the last fused monoStaticSensing call when the caller passed no array for it
   // overlap-save CDL apply (cdl_os.hip): the forward spectra of the last downlink batch, kept in a buffer of their own so that the NEXT batch on this context can reuse them when

@@ -31,6 +31,8 @@ namespace isac { struct CutRows { int row_lo, nr; }; }   // rows [row_lo, row_lo
 bool cut_rows_ok(const isac_est_params* ep, const isac_cfar_config* cf, isac::CutRows* out);              // false: the window leaves the map
 int cut_rows(isac_ctx* ctx, const isac_est_params* ep, const isac_cfar_config* cf, isac::CutRows* out);   // ... as ISAC_ERR_CFAR_WINDOW
 int isac_range_stage_into_cache(isac_ctx* ctx, const isac_est_params* ep, const isac_cfar_config* cf, const isac::c64* d_rx, const isac::c64* d_tx, int K, int L, int A);
+// ---------------------------------------------------------------- targets.hip: isac_fft2d_get_targets (include/isac_targets.h) -- the per-target list of the last completed fft2D.  It calls nothing but
+// isac_get_twiddles and is called by no other unit; what it shares with them is ctx->tgt (isac::TargetSource, isac_common.hpp): capi.hip fills it, rdm.hip / echo.hip drop it.
 // ---------------------------------------------------------------- cov.hip
 int isac_covariance_on(isac_ctx* ctx, hipStream_t st, const isac_c64* d_grid, int64_t N, int32_t A, isac_c64* d_Ra);
 int isac_covariance_lazy_on(isac_ctx* ctx, hipStream_t st, isac_c64* d_Ra);   // Ra of the context's native lazy echo grid

@@ -559,6 +559,7 @@ static int range_stage(isac_ctx* ctx, const isac_est_params* ep, const c64* rx, 
   const double *wk = nullptr, *wr = nullptr;
   ISAC_TRY(isac_get_twiddles(ctx, n_ifft, &tw));
   ISAC_TRY(isac_get_windows(ctx, K, n_ifft, &wk, &wr));
+  if (&dst == &ctx->ymid) ctx->tgt.drop();                                  // the rows isac_fft2d_get_targets reads are about to be rewritten
   ISAC_TRY(ensure(ctx, dst, sizeof(c64) * (size_t)nr * L * A));
   ISAC_FFT_DISPATCH_RANGE(n_ifft, ISAC_TRY((launch_range<FFT>(ctx, rx, tx, K, L, A, tw, wk, wr, n_ifft, row_lo, nr, (c64*)dst.p))));
   return ISAC_OK;
@@ -598,6 +599,7 @@ int isac_rdm_power_window(isac_ctx* ctx, const isac_est_params* ep, const isac_c
                           const c64* d_tx, int K, int L, int A, int* nr_out, int* nc_out, bool use_cached_range) {
   const int n_ifft = ep->n_ifft, n_fft = ep->n_fft;
   const int hc = cf->guard[1] + cf->train[1];
+  ctx->tgt.drop();                                                         // rewrites ctx->pwin
   const int col_lo = cf->col0 - 1 - hc, col_hi = cf->col1 - 1 + hc;   // 0-based inclusive
   if (cf->row1 < cf->row0 || cf->col1 < cf->col0) return fail(ctx, ISAC_ERR_INVALID_ARG, "empty CUT rectangle");
   CutRows cr;
@@ -667,6 +669,7 @@ static int launch_tail_fused(isac_ctx* ctx, const isac_est_params* ep, const isa
 }
 
 int isac_cfar_window(isac_ctx* ctx, const isac_est_params* ep, const isac_cfar_config* cf, int nr, int nc, int A, int cap) {
+  ctx->tgt.drop();                                                         // rewrites the device detection lists
   {
     TailGeom tg;
     if (tail_fusable(ctx, ep, cf, &tg)) return launch_tail_fused(ctx, ep, cf, nr, nc, A, cap);

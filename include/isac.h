@@ -318,6 +318,9 @@ int isac_fft2d_get_power_window(isac_ctx* ctx, double* P, int64_t cap_elems, int
 int isac_fft2d_get_covariance(isac_ctx* ctx, isac_c64* Ra, int32_t A);
 int isac_fft2d_get_music_spectrum(isac_ctx* ctx, double* p_db, int32_t cap, int32_t* n_steps);
 
+/* Per-target list of the last completed fft2D on this context (paired range, velocity, azimuth; project-defined): the additive part of ABI 8 -- one entry point, one
+ * struct, one isac_abi_sizeof selector -- is declared in isac_targets.h, which this header includes at its end: a host that includes isac.h has it. */
+
 /* Full range-Doppler map (fft2D.m:37-46) for one antenna plane, rdm [n_ifft x n_fft]; the
  * reference plots antenna 1 (fft2D.m:119).  Debug/plot path, not on the hot path. */
 int isac_rdm_plane_dev(isac_ctx* ctx, const isac_est_params* ep, const isac_c64* d_rx_grid,
@@ -646,4 +649,7 @@ int isac_synth_qpsk_grid_dev(isac_ctx* ctx, isac_c64* d_grid, int32_t K, int32_t
 #ifdef __cplusplus
 }
 #endif
+
+#include "isac_targets.h"   /* isac_fft2d_get_targets: additive under ABI 8 */
+
 #endif /* ISAC_H */

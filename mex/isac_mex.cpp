@@ -344,6 +344,18 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
       check(isac_music2d_dev(ctx(), &e, &m, d_rx.p, d_tx.p, K, L, A, &r));
     }
     plhs[0] = est_struct(r);
+  } else if (fn == "fft2DTargets") {
+    // targets = fft2DTargets(): the per-target list of the last completed 'fft2D' of this session (isac_fft2d_get_targets; project-defined, include/isac_targets.h):
+    // an [n x 1] struct array, strongest first, with scalar fields rng, vel, azi, power, hits, row, col (1-based bins)
+    static isac_target_list tl;                                       // (45 KB: not on the stack)
+    check(isac_fft2d_get_targets(ctx(), &tl, nullptr, 0));
+    const char* names[] = {"rng", "vel", "azi", "power", "hits", "row", "col"};
+    mxArray* s = mxCreateStructMatrix((mwSize)tl.n_targets, 1, 7, names);
+    for (int i = 0; i < tl.n_targets; ++i) {
+      const double v[7] = {tl.rng[i], tl.vel[i], tl.azi[i], tl.power[i], (double)tl.hits[i], (double)tl.row[i], (double)tl.col[i]};
+      for (int f = 0; f < 7; ++f) mxSetField(s, (mwIndex)i, names[f], mxCreateDoubleScalar(v[f]));
+    }
+    plhs[0] = s;
   } else if (fn == "music" || fn == "digitalBF" || fn == "mvdrBF") {
     // music: (numDets | [], radarEstParams, Ra) -> [L, aziEst, eleEst]                           music.m:1
     // digitalBF / mvdrBF: (numDets, radarEstParams, Ra) -> [aziEst, eleEst]                      digitalBF.m:1, mvdrBF.m:1
