@@ -18,6 +18,9 @@ ISAC_ABI_VERSION = 8          # include/isac.h ISAC_ABI_VERSION this binding was
 ISAC_MAX_EST = 4096
 ISAC_MAX_TARGETS = 1024
 NOISE_NONE, NOISE_INJECTED, NOISE_PHILOX, NOISE_PHILOX_SPECTRAL, NOISE_INJECTED_SPECTRAL = 0, 1, 2, 3, 4
+CFAR_CA, CFAR_GOCA, CFAR_SOCA, CFAR_OS = 0, 1, 2, 3      # ISAC_CFAR_* (include/isac_cfar.h)
+CFAR_METHODS = {"CA": CFAR_CA, "GOCA": CFAR_GOCA, "SOCA": CFAR_SOCA, "OS": CFAR_OS}
+ISAC_CFAR_MAX_TRAIN = 1024
 OPT_MUSIC_ROUTE, OPT_TAIL_FUSION, OPT_WIDE_ORDER, OPT_CDL_SHARE_SPECTRA, OPT_UPA_DOA = 0, 1, 2, 3, 4   # ISAC_OPT_* of isac_ctx_set_option
 
 STATUS_NAMES = {0: "OK", 1: "INVALID_ARG", 2: "HIP", 3: "NO_LOS", 4: "NO_DETECTION", 5: "CFAR_WINDOW",
@@ -115,6 +118,10 @@ class TargetList(C.Structure):
                 ("power", C.c_double * ISAC_MAX_TARGETS)]
 
 
+class CfarMethod(C.Structure):
+    _fields_ = [("method", C.c_int32), ("rank", C.c_int32), ("custom_factor", C.c_double)]
+
+
 # The structs isac_abi_sizeof() knows, in ISAC_SIZEOF_* index order: (C name, mirror).  load() compares every size with the library's.
 ABI_STRUCTS = (("isac_est_result", EstResult), ("isac_est_params", EstParams), ("isac_cfar_config", CfarConfig),
                ("isac_radar_channel_params", RadarChannelParams), ("isac_carrier", Carrier), ("isac_music2d_params", Music2dParams),
@@ -122,6 +129,7 @@ ABI_STRUCTS = (("isac_est_result", EstResult), ("isac_est_params", EstParams), (
                ("isac_rx_frontend_job", RxFrontendJob), ("isac_path_loss_config", PathLossConfig))
 # ... and the ones the additive headers add (include/isac_targets.h): (selector, C name, mirror)
 ABI_STRUCTS_ADDED = ((11, "isac_target_list", TargetList),)
+ABI_STRUCTS_CFAR = ((12, "isac_cfar_method", CfarMethod),)      # include/isac_cfar.h
 
 # Every function include/isac.h declares, in the header's order: name -> (restype, argtypes).  load() sets both, so a call with a missing
 # argument (TypeError) or a float for an integer (ctypes.ArgumentError) fails instead of reaching the library, a 64-bit value arrives whole,
@@ -215,6 +223,12 @@ EXPORTS = list(PROTOTYPES)
 PROTOTYPES_ADDED = {
     "isac_fft2d_get_targets": (_INT, (_P, _P, _P, _I32)),
 }
+# ... and include/isac_cfar.h, a table per additive header (tests/test_target_list_cpu.py pins PROTOTYPES_ADDED to isac_targets.h as tests/test_abi_cpu.py pins PROTOTYPES to isac.h)
+PROTOTYPES_CFAR = {
+    "isac_cfar_threshold_factor": (_INT, (_I32, _I32, _I32, _F64, _P)),
+    "isac_cfar2d": (_INT, (_P, _P, _I32, _I32, _P, _I32, _P, _P, _F64, _ptr(CfarMethod), _P, _I32, _P)),
+    "isac_fft2d_redetect": (_INT, (_P, _ptr(CfarMethod), _ptr(EstResult), _P, _P, _I32, _P, _P)),
+}
 
 
 def library_path() -> str:
@@ -241,13 +255,13 @@ def load():
             except Exception:
                 pass
         lib = C.CDLL(_LIB_PATH, mode=C.RTLD_GLOBAL)
-        for name, (restype, argtypes) in {**PROTOTYPES, **PROTOTYPES_ADDED}.items():
+        for name, (restype, argtypes) in {**PROTOTYPES, **PROTOTYPES_ADDED, **PROTOTYPES_CFAR}.items():
             fn = getattr(lib, name)  # AttributeError here = ABI drift between isac.h and the .so
             fn.restype, fn.argtypes = restype, argtypes
         # the library writes whole structs into caller memory: version AND struct sizes must match this binding's mirrors
         if lib.isac_abi_version() != ISAC_ABI_VERSION:
             raise RuntimeError(f"{_LIB_PATH}: ABI version {lib.isac_abi_version()} but this binding was written for {ISAC_ABI_VERSION}; rebuild the library")
-        for which, name, cls in [(i, n, c) for i, (n, c) in enumerate(ABI_STRUCTS)] + list(ABI_STRUCTS_ADDED):
+        for which, name, cls in [(i, n, c) for i, (n, c) in enumerate(ABI_STRUCTS)] + list(ABI_STRUCTS_ADDED) + list(ABI_STRUCTS_CFAR):
             if lib.isac_abi_sizeof(which) != C.sizeof(cls):
                 raise RuntimeError(f"{_LIB_PATH}: sizeof({name}) = {lib.isac_abi_sizeof(which)} in the library, {C.sizeof(cls)} in the binding")
         _lib = lib

@@ -27,6 +27,7 @@ extern "C" int isac_abi_sizeof(int32_t which) {
     case ISAC_SIZEOF_RX_FRONTEND_JOB: return (int)sizeof(isac_rx_frontend_job);
     case ISAC_SIZEOF_PATH_LOSS_CONFIG: return (int)sizeof(isac_path_loss_config);
     case ISAC_SIZEOF_TARGET_LIST: return (int)sizeof(isac_target_list);
+    case ISAC_SIZEOF_CFAR_METHOD: return (int)sizeof(isac_cfar_method);
     default: return -1;
   }
 }
@@ -437,6 +438,56 @@ extern "C" int isac_fft2d_submit_cached_dev(isac_ctx* ctx, const isac_est_params
   return fft2d_submit(ctx, ep, cfar, d_rx_grid, d_tx_grid, K, L, A, true);
 }
 
+// The host half of fft2D.m:63-99 on per-antenna detection lists in CUT order (cut: CUT ordinals cr + n_cut_rows cc, pw: the CUTs' powers, antenna a at
+// [ant_off[a], ant_off[a + 1])): det_rc = the 1-based (row, column) pairs, and in `out` the range / velocity estimates, numDets and the detection count.
+// num_dets_dev: the device's own count of distinct detected rows, which must agree.
+int fft2d_estimates(isac_ctx* ctx, const isac_est_params* ep, const isac_cfar_config* cfar, int A, const int* ant_off, const std::vector<int>& cut,
+                    const std::vector<double>& pw, int num_dets_dev, std::vector<int32_t>& det_rc, isac_est_result* out) {
+  const int n_cut_rows = cfar->row1 - cfar->row0 + 1;
+  const int total = ant_off[A];
+  det_rc.resize((size_t)2 * total);
+  std::vector<int> all_row, all_col;
+  all_row.reserve((size_t)total);
+  all_col.reserve((size_t)total);
+  std::vector<int> order;
+  for (int a = 0; a < A; ++a) {
+    const int b = ant_off[a], e = ant_off[a + 1];
+    for (int i = b; i < e; ++i) {
+      const int cr = cut[(size_t)i] % n_cut_rows, cc = cut[(size_t)i] / n_cut_rows;
+      det_rc[(size_t)2 * i] = cfar->row0 + cr;          // 1-based
+      det_rc[(size_t)2 * i + 1] = cfar->col0 + cc;
+    }
+    order.resize((size_t)(e - b));
+    std::iota(order.begin(), order.end(), b);
+    std::stable_sort(order.begin(), order.end(), [&](int p, int q) { return pw[(size_t)p] > pw[(size_t)q]; });   // :89 sort(peaks,'descend')
+    for (int i : order) {
+      all_row.push_back(det_rc[(size_t)2 * i]);
+      all_col.push_back(det_rc[(size_t)2 * i + 1]);
+    }
+  }
+  auto unique_stable = [](const std::vector<int>& v) {      // unique(x,'stable') on the integer bin indices  :99
+    std::vector<int> out_;
+    std::vector<char> seen;
+    for (int x : v) {
+      if ((size_t)x >= seen.size()) seen.resize((size_t)x + 1, 0);
+      if (!seen[(size_t)x]) { seen[(size_t)x] = 1; out_.push_back(x); }
+    }
+    return out_;
+  };
+  const std::vector<int> urow = unique_stable(all_row), ucol = unique_stable(all_col);
+  out->total_detections = total;
+  out->num_dets = (int)urow.size();                           // :110
+  if ((int)urow.size() != num_dets_dev)
+    return fail(ctx, ISAC_ERR_HIP, "internal: device numDets disagrees with host unique() count");
+  if (urow.size() > ISAC_MAX_EST || ucol.size() > ISAC_MAX_EST)
+    return fail(ctx, ISAC_ERR_CAPACITY, "more unique estimates than ISAC_MAX_EST");
+  out->n_rng = (int)urow.size();
+  out->n_vel = (int)ucol.size();
+  for (size_t i = 0; i < urow.size(); ++i) out->rng_est[i] = (double)(urow[i] - 1) * ep->r_res;               // :77,:81
+  for (size_t i = 0; i < ucol.size(); ++i) out->vel_est[i] = ((double)ucol[i] - ep->n_fft / 2.0 - 1.0) * ep->v_res;   // :78,:82
+  return ISAC_OK;
+}
+
 extern "C" int isac_fft2d_collect(isac_ctx* ctx, isac_est_result* out) {
   ISAC_ENTER_NOJOIN(ctx);                             // (waits for ev_done on the host below: no stream-side join, which would stall a shared main stream)
   if (!out) return fail(ctx, ISAC_ERR_INVALID_ARG, "NULL argument");
@@ -450,7 +501,6 @@ extern "C" int isac_fft2d_collect(isac_ctx* ctx, isac_est_result* out) {
   const size_t off_spec = pd.off_spec, off_pow = pd.off_pow, off_cut = pd.off_cut;
   int* d_pcut_full = pd.d_pcut_full;
   double* d_ppow_full = pd.d_ppow_full;
-  const int n_cut_rows = cfar->row1 - cfar->row0 + 1;
   char* h = (char*)ctx->pinned.p;
   ISAC_HIP(hipEventSynchronize(ctx->ev_done));      // (not the stream: contexts that share streams have later CPIs queued behind this one)
   ctx->tail_unjoined = false;                       // the narrow chain of this CPI has finished: nothing left for the main stream to wait for
@@ -474,53 +524,13 @@ extern "C" int isac_fft2d_collect(isac_ctx* ctx, isac_est_result* out) {
     ISAC_TRY(copy_d2h(ctx, pw.data(), d_ppow_full, sizeof(double) * (size_t)total));
   }
   const int* ant_off = hdr + 3;
-  // ---- host post-processing, fft2D.m:63-99
   Fft2dLast& last = ctx->last;
   last.A = A; last.nr = nr; last.nc = nc;
   last.first_row = cfar->row0 - (cfar->guard[0] + cfar->train[0]);
   last.first_col = cfar->col0 - (cfar->guard[1] + cfar->train[1]);
   last.ant_off.assign(ant_off, ant_off + A + 1);
-  last.det_rc.resize((size_t)2 * total);
   last.det_pow = pw;
-  std::vector<int> all_row, all_col;
-  all_row.reserve((size_t)total);
-  all_col.reserve((size_t)total);
-  std::vector<int> order;
-  for (int a = 0; a < A; ++a) {
-    const int b = ant_off[a], e = ant_off[a + 1];
-    for (int i = b; i < e; ++i) {
-      const int cr = cut[(size_t)i] % n_cut_rows, cc = cut[(size_t)i] / n_cut_rows;
-      last.det_rc[(size_t)2 * i] = cfar->row0 + cr;          // 1-based
-      last.det_rc[(size_t)2 * i + 1] = cfar->col0 + cc;
-    }
-    order.resize((size_t)(e - b));
-    std::iota(order.begin(), order.end(), b);
-    std::stable_sort(order.begin(), order.end(), [&](int p, int q) { return pw[(size_t)p] > pw[(size_t)q]; });   // :89 sort(peaks,'descend')
-    for (int i : order) {
-      all_row.push_back(last.det_rc[(size_t)2 * i]);
-      all_col.push_back(last.det_rc[(size_t)2 * i + 1]);
-    }
-  }
-  auto unique_stable = [](const std::vector<int>& v) {      // unique(x,'stable') on the integer bin indices  :99
-    std::vector<int> out_;
-    std::vector<char> seen;
-    for (int x : v) {
-      if ((size_t)x >= seen.size()) seen.resize((size_t)x + 1, 0);
-      if (!seen[(size_t)x]) { seen[(size_t)x] = 1; out_.push_back(x); }
-    }
-    return out_;
-  };
-  const std::vector<int> urow = unique_stable(all_row), ucol = unique_stable(all_col);
-  out->total_detections = total;
-  out->num_dets = (int)urow.size();                           // :110
-  if ((int)urow.size() != num_dets_dev)
-    return fail(ctx, ISAC_ERR_HIP, "internal: device numDets disagrees with host unique() count");
-  if (urow.size() > ISAC_MAX_EST || ucol.size() > ISAC_MAX_EST)
-    return fail(ctx, ISAC_ERR_CAPACITY, "more unique estimates than ISAC_MAX_EST");
-  out->n_rng = (int)urow.size();
-  out->n_vel = (int)ucol.size();
-  for (size_t i = 0; i < urow.size(); ++i) out->rng_est[i] = (double)(urow[i] - 1) * ep->r_res;               // :77,:81
-  for (size_t i = 0; i < ucol.size(); ++i) out->vel_est[i] = ((double)ucol[i] - ep->n_fft / 2.0 - 1.0) * ep->v_res;   // :78,:82
+  ISAC_TRY(fft2d_estimates(ctx, ep, cfar, A, ant_off, cut, pw, num_dets_dev, last.det_rc, out));
   last.valid = true;
   if (ctx->tgt.state == TargetSource::kSubmitted) ctx->tgt.state = TargetSource::kCollected;   // (dropped in between: a later call rewrote ymid / pwin / the lists)
   last.spectrum_db.clear();

@@ -1,0 +1,381 @@
+// The other detectors of phased.CFARDetector2D (gfx950 only): cell averaging, greatest-of / smallest-of cell averaging and ordered statistics, with the automatic or a
+// custom threshold factor (cfar2D.m:28-29 names them; include/isac_cfar.h and DESIGN.md section 5 define what the toolbox leaves open).  Entry points:
+//   isac_cfar_threshold_factor   host only: the 'Auto' factor of a method
+//   isac_cfar2d                  an arbitrary map and CUT list (isac_cfar2d_ca with the method block)
+//   isac_fft2d_redetect          the power window of the last completed fft2D, detected again; then the host half of fft2D.m:63-99 on the new lists
+// One per-CUT device function, cfar_cut<M>, serves both: K1 cfar_method_window_kernel stages a kPanelRows x pc tile of CUTs plus its halo of guard + training cells in LDS
+// and evaluates one CUT per lane into a flag per (CUT, antenna); K2 cfar_compact_kernel, one workgroup per antenna, turns the flags into the CUT-order list (rows
+// fastest, cfar2D.m:23-24) with ballots and a running base; cfar_method_list_kernel evaluates one listed CUT per lane on a map in global memory.  The CA detector of the
+// timed fft2D path (rdm.hip) is not touched; cfar_cut<CA> restates its arithmetic operation for operation.  Everything here is off the timed path.
+#include <algorithm>
+#include <cmath>
+
+#include "isac_internal.hpp"
+
+namespace isac {
+
+struct CutGeom {
+  int hr, hc;          // guard + training half sizes
+  int gr, gc;          // guard half sizes
+  int n_train;         // N
+  int rank;            // OS: 1..N
+  double alpha;
+};
+
+// ---------------------------------------------------------------- one CUT: cutp points at the CUT, the cell (dr, dc) away is cutp[dr + dc * ld].  LDS or global memory.
+// Training cells in the ORACLE-DEFINED order of the CA kernels (column offset slowest, row offset fastest, guard block skipped; oracle/cfar.py); correctly rounded
+// operations only, so the flag is a function of the map's bits.
+template <int M>
+__device__ __forceinline__ bool cfar_cut(const double* __restrict__ cutp, int ld, const CutGeom& g) {
+  double est;
+  if constexpr (M == ISAC_CFAR_CA) {
+    double acc = 0.0;
+    for (int dc = -g.hc; dc <= g.hc; ++dc) {
+      const bool guard_col = (dc >= -g.gc && dc <= g.gc);
+      const double* colp = cutp + (long long)dc * ld;
+      for (int dr = -g.hr; dr <= g.hr; ++dr) {
+        if (guard_col && dr >= -g.gr && dr <= g.gr) continue;
+        acc = __dadd_rn(acc, colp[dr]);
+      }
+    }
+    est = __ddiv_rn(acc, (double)g.n_train);
+  } else if constexpr (M == ISAC_CFAR_GOCA || M == ISAC_CFAR_SOCA) {
+    const int half = g.n_train / 2;                             // front half: the cells before the CUT in this order
+    double front = 0.0, rear = 0.0;
+    int k = 0;                                                  // (uniform over the lanes: no divergence)
+    for (int dc = -g.hc; dc <= g.hc; ++dc) {
+      const bool guard_col = (dc >= -g.gc && dc <= g.gc);
+      const double* colp = cutp + (long long)dc * ld;
+      for (int dr = -g.hr; dr <= g.hr; ++dr) {
+        if (guard_col && dr >= -g.gr && dr <= g.gr) continue;
+        if (k < half) front = __dadd_rn(front, colp[dr]);
+        else rear = __dadd_rn(rear, colp[dr]);
+        ++k;
+      }
+    }
+    front = __ddiv_rn(front, (double)half);
+    rear = __ddiv_rn(rear, (double)half);
+    est = M == ISAC_CFAR_GOCA ? (front > rear ? front : rear) : (front < rear ? front : rear);
+    if (front != front) est = front;                            // a NaN mean is the estimate (the comparisons above drop it): no detection
+    if (rear != rear) est = rear;
+  } else {
+    // the rank-th smallest: the candidate with exactly rank - 1 cells below it, ties broken by index -- a strict total order, so exactly one candidate qualifies.
+    // Both loops read the map (LDS in the window kernel); nothing is kept in a per-lane array.
+    bool has_nan = false;
+    est = 0.0;
+    int i = 0;
+    for (int dc = -g.hc; dc <= g.hc; ++dc) {
+      const bool guard_col = (dc >= -g.gc && dc <= g.gc);
+      const double* colp = cutp + (long long)dc * ld;
+      for (int dr = -g.hr; dr <= g.hr; ++dr) {
+        if (guard_col && dr >= -g.gr && dr <= g.gr) continue;
+        const double ti = colp[dr];
+        has_nan |= ti != ti;
+        int below = 0, j = 0;
+        for (int dc2 = -g.hc; dc2 <= g.hc; ++dc2) {
+          const bool guard_col2 = (dc2 >= -g.gc && dc2 <= g.gc);
+          const double* colp2 = cutp + (long long)dc2 * ld;
+          for (int dr2 = -g.hr; dr2 <= g.hr; ++dr2) {
+            if (guard_col2 && dr2 >= -g.gr && dr2 <= g.gr) continue;
+            const double tj = colp2[dr2];
+            below += ((tj < ti) | ((tj == ti) & (j < i))) ? 1 : 0;
+            ++j;
+          }
+        }
+        if (below == g.rank - 1) est = ti;
+        ++i;
+      }
+    }
+    if (has_nan) est = __builtin_nan("");                       // a rank count skips NaNs: make the rule hold
+  }
+  const double thr = __dmul_rn(g.alpha, est);
+  return *cutp > thr;                                           // strict; a NaN CUT or threshold compares false
+}
+
+// ---------------------------------------------------------------- K1: a tile of the CUT rectangle of one antenna, one lane per CUT
+constexpr int kPanelRows = 32;                                  // CUT rows per workgroup (the panel height)
+constexpr int kPanelColsMax = 8;                                // CUT columns per workgroup: 256 lanes
+
+struct WinGeom {
+  int nr, nc;                    // power window dims
+  int n_cut_rows, n_cut_cols;
+  int pc;                        // CUT columns per workgroup, 1..kPanelColsMax (from the LDS budget)
+  CutGeom c;
+};
+
+template <int M>
+__global__ __launch_bounds__(kPanelRows * kPanelColsMax) void cfar_method_window_kernel(const double* __restrict__ pwin /* [nr x nc x A] */, WinGeom g,
+                                                                                         unsigned char* __restrict__ flags /* [A][n_cut], CUT order */) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  double* s_p = reinterpret_cast<double*>(smem_raw);            // [pc + 2 hc][kPanelRows + 2 hr], rows fastest
+  constexpr int NT = kPanelRows * kPanelColsMax;
+  const int tid = threadIdx.x;
+  const int r0 = blockIdx.x * kPanelRows, c0 = blockIdx.y * g.pc, a = blockIdx.z;   // first CUT row / column of the tile = first window row / column staged
+  const int wr = kPanelRows + 2 * g.c.hr, wc = g.pc + 2 * g.c.hc;
+  {   // 8 independent loads in flight per thread (cells past the window, where the tile overhangs the zone: clamped, never used by a CUT)
+    const double* src = pwin + (long long)g.nr * g.nc * a;
+    const int n_el = wr * wc;
+    for (int i0 = tid; i0 < n_el; i0 += 8 * NT) {
+      double v[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int i = min(i0 + u * NT, n_el - 1);
+        const int pcol = i / wr, prow = i - pcol * wr;
+        v[u] = src[(long long)min(r0 + prow, g.nr - 1) + (long long)g.nr * min(c0 + pcol, g.nc - 1)];
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u) { const int i = i0 + u * NT; if (i < n_el) s_p[i] = v[u]; }
+    }
+  }
+  __syncthreads();
+  const int crl = tid % kPanelRows, ccl = tid / kPanelRows;     // lanes along a column read consecutive doubles: no bank conflict
+  const int cr = r0 + crl, cc = c0 + ccl;
+  if (ccl < g.pc && cr < g.n_cut_rows && cc < g.n_cut_cols) {
+    const bool det = cfar_cut<M>(s_p + (ccl + g.c.hc) * wr + crl + g.c.hr, wr, g.c);
+    flags[(long long)a * g.n_cut_rows * g.n_cut_cols + cr + (long long)g.n_cut_rows * cc] = det ? 1 : 0;
+  }
+}
+
+// ---------------------------------------------------------------- K2: flags of one antenna -> its list in CUT order, the CUTs' powers, the detected rows
+__global__ __launch_bounds__(256) void cfar_compact_kernel(const unsigned char* __restrict__ flags /* [A][n_cut] */, const double* __restrict__ pwin, int nr, int nc,
+                                                           int hr, int hc, int n_cut_rows, int n_cut, int* __restrict__ det_cut /* [A][n_cut] CUT ordinal */,
+                                                           double* __restrict__ det_pow /* [A][n_cut] */, int* __restrict__ det_cnt /* [A] */,
+                                                           unsigned* __restrict__ row_seen /* [n_cut_rows], zeroed */) {
+  __shared__ int s_w[4];                                        // detections of each wave in this round
+  const int a = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const unsigned char* f = flags + (long long)a * n_cut;
+  const double* p = pwin + (long long)nr * nc * a;
+  int base = 0;                                                 // detections before this round (every thread keeps the same count)
+  for (int i0 = 0; i0 < n_cut; i0 += 256) {
+    const int i = i0 + tid;
+    const bool det = i < n_cut && f[i] != 0;
+    const unsigned long long mask = __ballot(det);
+    if (lane == 0) s_w[wid] = __popcll(mask);
+    __syncthreads();
+    int off = base;
+    for (int q = 0; q < wid; ++q) off += s_w[q];
+    base += s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    if (det) {
+      const int pos = off + __popcll(mask & ((1ull << lane) - 1ull));   // < n_cut: at most one entry per CUT
+      const int cr = i % n_cut_rows, cc = i / n_cut_rows;
+      det_cut[(long long)a * n_cut + pos] = i;
+      det_pow[(long long)a * n_cut + pos] = p[(long long)(cr + hr) + (long long)nr * (cc + hc)];
+      row_seen[cr] = 1u;                                        // (every writer stores the same value)
+    }
+    __syncthreads();                                            // s_w is rewritten in the next round
+  }
+  if (tid == 0) det_cnt[a] = base;
+}
+
+// ---------------------------------------------------------------- arbitrary CUT list on an arbitrary map: one lane per listed CUT, the map in global memory
+template <int M>
+__global__ __launch_bounds__(256) void cfar_method_list_kernel(const double* __restrict__ P, int n_rows, const int* __restrict__ cut /* [2 x n_cut] 1-based */,
+                                                               int n_cut, CutGeom g, unsigned char* __restrict__ flags) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_cut) return;
+  const int r = cut[2 * i] - 1, c = cut[2 * i + 1] - 1;         // (the host has checked that the training window stays inside the map)
+  flags[i] = cfar_cut<M>(P + (long long)r + (long long)n_rows * c, n_rows, g) ? 1 : 0;
+}
+
+}  // namespace isac
+
+// ================================================================= host side
+using namespace isac;
+
+// Run the statement(s) with M = the method as a compile-time constant
+#define CFAR_METHOD_DISPATCH(method, ...)                                                \
+  switch (method) {                                                                      \
+    case ISAC_CFAR_CA: { constexpr int M = ISAC_CFAR_CA; __VA_ARGS__; } break;           \
+    case ISAC_CFAR_GOCA: { constexpr int M = ISAC_CFAR_GOCA; __VA_ARGS__; } break;       \
+    case ISAC_CFAR_SOCA: { constexpr int M = ISAC_CFAR_SOCA; __VA_ARGS__; } break;       \
+    default: { constexpr int M = ISAC_CFAR_OS; __VA_ARGS__; } break;                     \
+  }
+
+// ---------------------------------------------------------------- ThresholdFactor 'Auto': the false-alarm probability of each method at factor alpha (exponential cells)
+static double soca_sum(int n, double T) {                      // 2 sum_{k<n} C(n-1+k, k) (2+T)^-(n+k), terms by the ratio recurrence (binomials overflow)
+  double t = std::pow(2.0 + T, -(double)n), s = 0.0;
+  for (int k = 0; k < n; ++k) {
+    s += t;
+    t = t * (double)(n + k) / ((double)(k + 1) * (2.0 + T));
+  }
+  return 2.0 * s;
+}
+static double pfa_of(int method, int N, int rank, double alpha) {
+  const int n = N / 2;
+  const double T = alpha / n;
+  switch (method) {
+    case ISAC_CFAR_SOCA: return soca_sum(n, T);
+    case ISAC_CFAR_GOCA: return 2.0 * std::pow(1.0 + T, -(double)n) - soca_sum(n, T);
+    default: {                                                  // OS
+      double p = 1.0;
+      for (int i = 0; i < rank; ++i) p *= (double)(N - i) / ((double)(N - i) + alpha);
+      return p;
+    }
+  }
+}
+// the checks of isac_cfar.h on method, N and rank; *why: what was wrong
+static int check_method(int method, int N, int rank, const char** why) {
+  if (method < ISAC_CFAR_CA || method > ISAC_CFAR_OS) { *why = "unknown CFAR method"; return ISAC_ERR_INVALID_ARG; }
+  if (N < 1) { *why = "TrainingBandSize must be positive"; return ISAC_ERR_INVALID_ARG; }
+  if (method == ISAC_CFAR_CA) return ISAC_OK;
+  if (method == ISAC_CFAR_OS && (rank < 1 || rank > N)) { *why = "OS rank must lie in 1..N"; return ISAC_ERR_INVALID_ARG; }
+  if (method != ISAC_CFAR_OS && (N & 1)) { *why = "GOCA / SOCA need an even number of training cells"; return ISAC_ERR_INVALID_ARG; }
+  if (N > ISAC_CFAR_MAX_TRAIN) { *why = "GOCA / SOCA / OS: more than ISAC_CFAR_MAX_TRAIN training cells"; return ISAC_ERR_UNSUPPORTED; }
+  return ISAC_OK;
+}
+// ... and the 'Auto' factor of a method that passed them
+static int threshold_factor(int method, int N, int rank, double pfa, double* alpha, const char** why) {
+  const int st = check_method(method, N, rank, why);
+  if (st != ISAC_OK) return st;
+  if (!(pfa > 0.0 && pfa < 1.0)) { *why = "ProbabilityFalseAlarm must lie in (0, 1)"; return ISAC_ERR_INVALID_ARG; }
+  if (method == ISAC_CFAR_CA) { *alpha = cfar_alpha(N, pfa); return ISAC_OK; }
+  // the left sides fall strictly with alpha from 1 at alpha = 0: double the bracket until it holds the root, halve it until its ends are adjacent doubles
+  double lo = 0.0, hi = 1.0;
+  for (int it = 0; it < 1100 && pfa_of(method, N, rank, hi) > pfa; ++it) { lo = hi; hi *= 2.0; }
+  for (int it = 0; it < 200; ++it) {
+    const double mid = lo + (hi - lo) / 2.0;
+    if (!(mid > lo && mid < hi)) break;
+    if (pfa_of(method, N, rank, mid) > pfa) lo = mid;
+    else hi = mid;
+  }
+  *alpha = hi;
+  return ISAC_OK;
+}
+
+extern "C" int isac_cfar_threshold_factor(int32_t method, int32_t n_train, int32_t rank, double pfa, double* alpha) {
+  if (!alpha) return ISAC_ERR_INVALID_ARG;
+  const char* why = "";
+  return threshold_factor(method, n_train, rank, pfa, alpha, &why);
+}
+
+// guard / training sizes + the method block -> the per-CUT geometry with its factor
+static int cut_geom(isac_ctx* ctx, const int32_t guard[2], const int32_t train[2], double pfa, const isac_cfar_method* m, CutGeom* out) {
+  if (guard[0] < 0 || guard[1] < 0 || train[0] < 0 || train[1] < 0) return fail(ctx, ISAC_ERR_INVALID_ARG, "negative guard / training band size");
+  CutGeom g{};
+  g.gr = guard[0]; g.gc = guard[1];
+  g.hr = guard[0] + train[0]; g.hc = guard[1] + train[1];
+  const long long n_train = (2ll * g.hr + 1) * (2ll * g.hc + 1) - (2ll * g.gr + 1) * (2ll * g.gc + 1);
+  if (n_train <= 0) return fail(ctx, ISAC_ERR_INVALID_ARG, "TrainingBandSize must be positive");
+  if (n_train > (1ll << 30)) return fail(ctx, ISAC_ERR_UNSUPPORTED, "training band too large");
+  g.n_train = (int)n_train;
+  g.rank = m->rank;
+  const char* why = "";
+  int st;
+  if (m->custom_factor == 0.0) st = threshold_factor(m->method, g.n_train, m->rank, pfa, &g.alpha, &why);                  // 'Auto'
+  else if (m->custom_factor > 0.0) { st = check_method(m->method, g.n_train, m->rank, &why); g.alpha = m->custom_factor; }   // 'Custom': pfa is not used
+  else return fail(ctx, ISAC_ERR_INVALID_ARG, "custom_factor must be 0 ('Auto') or positive");                              // negative or NaN
+  if (st != ISAC_OK) return fail(ctx, st, why);
+  *out = g;
+  return ISAC_OK;
+}
+
+extern "C" int isac_cfar2d(isac_ctx* ctx, const double* P, int32_t n_rows, int32_t n_cols, const int32_t* cut_idx, int32_t n_cut, const int32_t guard[2],
+                           const int32_t train[2], double pfa, const isac_cfar_method* m, int32_t* det_idx, int32_t cap, int32_t* n_det) {
+  ISAC_ENTER(ctx);
+  if (!P || !cut_idx || !guard || !train || !m || !n_det || n_rows <= 0 || n_cols <= 0 || n_cut < 0) return fail(ctx, ISAC_ERR_INVALID_ARG, "bad arguments");
+  CutGeom g;
+  ISAC_TRY(cut_geom(ctx, guard, train, pfa, m, &g));
+  for (int i = 0; i < n_cut; ++i) {
+    const int r = cut_idx[2 * i] - 1, c = cut_idx[2 * i + 1] - 1;
+    if (r - g.hr < 0 || r + g.hr >= n_rows || c - g.hc < 0 || c + g.hc >= n_cols)
+      return fail(ctx, ISAC_ERR_CFAR_WINDOW, "CUT training window exceeds the input matrix");
+  }
+  *n_det = 0;
+  if (n_cut == 0) return ISAC_OK;
+  const size_t pb = sizeof(double) * (size_t)n_rows * n_cols, cb = sizeof(int) * 2 * (size_t)n_cut;
+  ISAC_TRY(ensure(ctx, ctx->stage_a, pb));
+  ISAC_TRY(ensure(ctx, ctx->stage_b, cb));
+  ISAC_TRY(ensure(ctx, ctx->stage_c, (size_t)n_cut));
+  ISAC_TRY(copy_h2d(ctx, ctx->stage_a.p, P, pb));
+  ISAC_TRY(copy_h2d(ctx, ctx->stage_b.p, cut_idx, cb));
+  CFAR_METHOD_DISPATCH(m->method, hipLaunchKernelGGL(cfar_method_list_kernel<M>, dim3(cdiv(n_cut, 256)), dim3(256), 0, ctx->stream, (const double*)ctx->stage_a.p,
+                                                     n_rows, (const int*)ctx->stage_b.p, n_cut, g, (unsigned char*)ctx->stage_c.p));
+  ISAC_HIP(hipGetLastError());
+  std::vector<unsigned char> flags((size_t)n_cut);
+  ISAC_TRY(copy_d2h(ctx, flags.data(), ctx->stage_c.p, (size_t)n_cut));
+  int n = 0;
+  for (int i = 0; i < n_cut; ++i)
+    if (flags[i]) {
+      if (n < cap && det_idx) {
+        det_idx[2 * n] = cut_idx[2 * i];
+        det_idx[2 * n + 1] = cut_idx[2 * i + 1];
+      }
+      ++n;
+    }
+  *n_det = n;
+  if (n > cap) return fail(ctx, ISAC_ERR_CAPACITY, "more detections than det_idx capacity");
+  return ISAC_OK;
+}
+
+extern "C" int isac_fft2d_redetect(isac_ctx* ctx, const isac_cfar_method* m, isac_est_result* out, int32_t* det_idx, double* det_pow, int32_t cap,
+                                   int32_t* ant_offsets, int32_t* n_total) {
+  ISAC_ENTER(ctx);
+  if (!m || !out || cap < 0) return fail(ctx, ISAC_ERR_INVALID_ARG, "bad arguments");
+  const TargetSource& ts = ctx->tgt;
+  if (!ctx->last.valid || ts.state != TargetSource::kCollected)
+    return fail(ctx, ISAC_ERR_INVALID_ARG, "isac_fft2d_redetect: no completed fft2D on this context whose power window is still on the device");
+  const isac_cfar_config& cf = ts.cfar;
+  WinGeom g{};
+  ISAC_TRY(cut_geom(ctx, cf.guard, cf.train, cf.pfa, m, &g.c));
+  const int A = ts.A;
+  g.nr = ts.nr; g.nc = ts.nc;
+  g.n_cut_rows = cf.row1 - cf.row0 + 1; g.n_cut_cols = cf.col1 - cf.col0 + 1;
+  if (g.n_cut_rows < 1 || g.n_cut_cols < 1 || g.nr != g.n_cut_rows + 2 * g.c.hr || g.nc != g.n_cut_cols + 2 * g.c.hc)
+    return fail(ctx, ISAC_ERR_HIP, "internal: power window geometry mismatch");
+  const long long n_cut_ll = (long long)g.n_cut_rows * g.n_cut_cols;
+  if (n_cut_ll * A > (1ll << 30)) return fail(ctx, ISAC_ERR_UNSUPPORTED, "isac_fft2d_redetect: more than 2^30 (CUT, antenna) pairs");
+  const int n_cut = (int)n_cut_ll;
+  std::memset(out, 0, sizeof(*out));
+  // CUT columns per workgroup: as many as fit ~128 KB of LDS with the panel's kPanelRows + 2 hr rows, at most one per wave quarter (kPanelColsMax)
+  const size_t budget = 128 * 1024;
+  const long long fit = (long long)(budget / (sizeof(double) * (size_t)(kPanelRows + 2 * g.c.hr))) - 2ll * g.c.hc;
+  if (fit < 1) return fail(ctx, ISAC_ERR_UNSUPPORTED, "isac_fft2d_redetect: guard + training band too large for the LDS-staged detector");
+  g.pc = (int)std::min<long long>(fit, std::min(kPanelColsMax, g.n_cut_cols));
+  const size_t lds = sizeof(double) * (size_t)(kPanelRows + 2 * g.c.hr) * (size_t)(g.pc + 2 * g.c.hc);
+  // scratch of its own, every list sized for all CUTs: [det_pow A n_cut | det_cut A n_cut | det_cnt A | row_seen n_cut_rows | flags A n_cut]
+  const size_t n_pairs = (size_t)A * n_cut;
+  const size_t off_cut = sizeof(double) * n_pairs, off_cnt = off_cut + sizeof(int) * n_pairs, off_rows = off_cnt + sizeof(int) * (size_t)A;
+  const size_t off_flags = off_rows + sizeof(unsigned) * (size_t)g.n_cut_rows;
+  ISAC_TRY(ensure(ctx, ctx->redet, off_flags + n_pairs));
+  char* d = (char*)ctx->redet.p;
+  ISAC_HIP(hipMemsetAsync(d + off_rows, 0, sizeof(unsigned) * (size_t)g.n_cut_rows, ctx->stream));
+  CFAR_METHOD_DISPATCH(m->method, {
+    auto kern = cfar_method_window_kernel<M>;
+    ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(kern), lds));
+    hipLaunchKernelGGL(kern, dim3(cdiv(g.n_cut_rows, kPanelRows), cdiv(g.n_cut_cols, g.pc), A), dim3(kPanelRows * kPanelColsMax), lds, ctx->stream,
+                       (const double*)ctx->pwin.p, g, (unsigned char*)(d + off_flags));
+  });
+  ISAC_HIP(hipGetLastError());
+  hipLaunchKernelGGL(cfar_compact_kernel, dim3(A), dim3(256), 0, ctx->stream, (const unsigned char*)(d + off_flags), (const double*)ctx->pwin.p, g.nr, g.nc, g.c.hr, g.c.hc,
+                     g.n_cut_rows, n_cut, (int*)(d + off_cut), (double*)d, (int*)(d + off_cnt), (unsigned*)(d + off_rows));
+  ISAC_HIP(hipGetLastError());
+  std::vector<int> tail((size_t)A + g.n_cut_rows);              // [det_cnt | row_seen]
+  ISAC_TRY(copy_d2h(ctx, tail.data(), d + off_cnt, sizeof(int) * tail.size()));
+  std::vector<int> ant_off((size_t)A + 1, 0);
+  long long total_ll = 0;
+  for (int a = 0; a < A; ++a) {
+    if (tail[(size_t)a] < 0 || tail[(size_t)a] > n_cut) return fail(ctx, ISAC_ERR_HIP, "internal: detection count outside 0..nCUT");
+    total_ll += tail[(size_t)a];
+    ant_off[(size_t)a + 1] = (int)total_ll;
+  }
+  const int total = (int)total_ll;
+  int num_dets_dev = 0;
+  for (int r = 0; r < g.n_cut_rows; ++r) num_dets_dev += tail[(size_t)A + r] ? 1 : 0;
+  if (n_total) *n_total = total;
+  if (ant_offsets) std::copy(ant_off.begin(), ant_off.end(), ant_offsets);
+  if (total > cap) return fail(ctx, ISAC_ERR_CAPACITY, "detection list larger than capacity");
+  std::vector<int> cut((size_t)total);
+  std::vector<double> pw((size_t)total);
+  for (int a = 0; a < A; ++a) {
+    const size_t b = (size_t)ant_off[(size_t)a], n = (size_t)tail[(size_t)a];
+    if (!n) continue;
+    ISAC_TRY(copy_d2h(ctx, cut.data() + b, d + off_cut + sizeof(int) * (size_t)a * n_cut, sizeof(int) * n));
+    ISAC_TRY(copy_d2h(ctx, pw.data() + b, d + sizeof(double) * (size_t)a * n_cut, sizeof(double) * n));
+  }
+  std::vector<int32_t> det_rc;
+  ISAC_TRY(fft2d_estimates(ctx, &ts.ep, &cf, A, ant_off.data(), cut, pw, num_dets_dev, det_rc, out));   // fft2D.m:63-99; n_azi stays 0
+  if (det_idx) std::copy(det_rc.begin(), det_rc.end(), det_idx);
+  if (det_pow) std::copy(pw.begin(), pw.end(), det_pow);
+  return ISAC_OK;
+}

@@ -160,6 +160,7 @@ struct DoaPlan {  // the direction-finding tail of one covariance: what doa_plan
 // What isac_fft2d_get_targets (targets.hip) reads: ctx->ymid, ctx->pwin and the device detection lists (det_cut / det_cnt) as the last fft2D left them, with the geometry
 // they were written for.  fft2d_submit fills it (kSubmitted), isac_fft2d_collect confirms it (kCollected), and every function that rewrites one of those buffers calls
 // drop() first -- a later range stage, echo call or submit on the context makes the target list ISAC_ERR_INVALID_ARG, never stale.
+// isac_fft2d_redetect (cfar.hip) reads ctx->pwin under the same validity.
 struct TargetSource {
   enum { kNone = 0, kSubmitted = 1, kCollected = 2 };
   int state = kNone;
@@ -216,6 +217,7 @@ struct isac_ctx {
   isac::Fft2dPending pending;
   isac::TargetSource tgt;            // isac_fft2d_get_targets: validity + geometry of ymid / pwin / det_* (above)
   isac::DevBuf tgt_scratch;          // ... and its device scratch (hits map, candidate lists, snapshots)
+  isac::DevBuf redet;                // isac_fft2d_redetect (cfar.hip): per-CUT flags, per-antenna lists sized for every CUT, counts, row flags
   isac::RangeCache range_cache;
   isac::LazyEcho lazy;               // the echo grid of the last fused monoStaticSensing call when the caller passed no array for it
   // overlap-save CDL apply (cdl_os.hip): the forward spectra of the last downlink batch, kept in a buffer of their own so that the NEXT batch on this context can reuse them when

@@ -524,7 +524,7 @@ __global__ __launch_bounds__(256) void doppler_full_kernel(const c64* __restrict
 // ================================================================= host side
 using namespace isac;
 
-static double cfar_alpha(int n_train, double pfa) { return n_train * (std::pow(pfa, -1.0 / n_train) - 1.0); }
+double cfar_alpha(int n_train, double pfa) { return n_train * (std::pow(pfa, -1.0 / n_train) - 1.0); }
 
 template <class FFT>
 static int launch_range(isac_ctx* ctx, const c64* rx, const c64* tx, int K, int L, int A, const c64* tw, const double* wk, const double* wr, int n_ifft,

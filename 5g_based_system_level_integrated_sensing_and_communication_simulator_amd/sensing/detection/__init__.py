@@ -1,1 +1,2 @@
 from .cfar2D import cfar2D, CFARDetector2D  # noqa: F401
+from .cfarDetect import cfarDetect, cfarThresholdFactor  # noqa: F401
