@@ -312,18 +312,15 @@ extern "C" int isac_fft2d_redetect(isac_ctx* ctx, const isac_cfar_method* m, isa
                                    int32_t* ant_offsets, int32_t* n_total) {
   ISAC_ENTER(ctx);
   if (!m || !out || cap < 0) return fail(ctx, ISAC_ERR_INVALID_ARG, "bad arguments");
-  const TargetSource& ts = ctx->tgt;
-  if (!ctx->last.valid || ts.state != TargetSource::kCollected)
+  const Fft2dCpi& ts = ctx->tgt;
+  if (!ctx->last.valid || ts.state != Fft2dCpi::kCollected)
     return fail(ctx, ISAC_ERR_INVALID_ARG, "isac_fft2d_redetect: no completed fft2D on this context whose power window is still on the device");
   const isac_cfar_config& cf = ts.cfar;
   WinGeom g{};
   ISAC_TRY(cut_geom(ctx, cf.guard, cf.train, cf.pfa, m, &g.c));
   const int A = ts.A;
-  g.nr = ts.nr; g.nc = ts.nc;
-  g.n_cut_rows = cf.row1 - cf.row0 + 1; g.n_cut_cols = cf.col1 - cf.col0 + 1;
-  if (g.n_cut_rows < 1 || g.n_cut_cols < 1 || g.nr != g.n_cut_rows + 2 * g.c.hr || g.nc != g.n_cut_cols + 2 * g.c.hc)
-    return fail(ctx, ISAC_ERR_HIP, "internal: power window geometry mismatch");
-  const long long n_cut_ll = (long long)g.n_cut_rows * g.n_cut_cols;
+  g.nr = ts.win.nr; g.nc = ts.win.nc; g.n_cut_rows = ts.win.n_cut_rows; g.n_cut_cols = ts.win.n_cut_cols;   // (both >= 1: the submit that left the window refuses an empty zone)
+  const long long n_cut_ll = ts.win.n_cut();
   if (n_cut_ll * A > (1ll << 30)) return fail(ctx, ISAC_ERR_UNSUPPORTED, "isac_fft2d_redetect: more than 2^30 (CUT, antenna) pairs");
   const int n_cut = (int)n_cut_ll;
   std::memset(out, 0, sizeof(*out));
@@ -374,7 +371,7 @@ extern "C" int isac_fft2d_redetect(isac_ctx* ctx, const isac_cfar_method* m, isa
     ISAC_TRY(copy_d2h(ctx, pw.data() + b, d + sizeof(double) * (size_t)a * n_cut, sizeof(double) * n));
   }
   std::vector<int32_t> det_rc;
-  ISAC_TRY(fft2d_estimates(ctx, &ts.ep, &cf, A, ant_off.data(), cut, pw, num_dets_dev, det_rc, out));   // fft2D.m:63-99; n_azi stays 0
+  ISAC_TRY(fft2d_estimates(ctx, &ts.ep, ts.win, A, ant_off.data(), cut, pw, num_dets_dev, det_rc, out));   // fft2D.m:63-99; n_azi stays 0
   if (det_idx) std::copy(det_rc.begin(), det_rc.end(), det_idx);
   if (det_pow) std::copy(pw.begin(), pw.end(), det_pow);
   return ISAC_OK;

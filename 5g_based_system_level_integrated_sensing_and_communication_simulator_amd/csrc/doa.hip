@@ -1,4 +1,4 @@
-// Direction finding on the host (gfx950 only): the one DoA back end behind the fft2D pipeline (capi.hip) and the stand-alone calls, the stand-alone
+// Direction finding on the host (gfx950 only): the one DoA back end behind the fft2D pipeline (fft2d.hip) and the stand-alone calls, the stand-alone
 // eigensolver calls, find2DPeaks and music2D.  No kernel lives here: the eigensolver is eigh.hip, the scans are music.hip (ULA) and doa2d.hip (UPA).
 #include <algorithm>
 #include <numeric>

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/isac.h"
+#include "cut_window.hpp"
 
 namespace isac {
 
@@ -97,14 +98,12 @@ struct TableKey {
   bool operator<(const TableKey& o) const { return kind != o.kind ? kind < o.kind : par < o.par; }
 };
 
-struct Fft2dLast {  // introspection of the last fft2D call (host copies)
-  bool valid = false;
-  int A = 0, nr = 0, nc = 0, first_row = 0, first_col = 0;
+struct Fft2dLast {  // introspection of the last fft2D call: the host copies (their antennas and window: Fft2dCpi)
+  bool valid = false;               // false from every submit (and isac_ctx_reserve) on, true once isac_fft2d_collect has the estimates: all the isac_fft2d_get_* calls ask for
   std::vector<int32_t> det_rc;      // [2 x total] 1-based, CUT order per antenna
   std::vector<double> det_pow;
   std::vector<int32_t> ant_off;     // [A+1]
   std::vector<double> spectrum_db;
-  bool pow_on_device = false;
 };
 
 struct RangeCache {  // range rows pre-computed by the fused monoStaticSensing call for the next fft2D
@@ -157,28 +156,40 @@ struct DoaPlan {  // the direction-finding tail of one covariance: what doa_plan
   bool refused() const { return upa && !upa2d; }   // music.m:69 without the option
 };
 
-// What isac_fft2d_get_targets (targets.hip) reads: ctx->ymid, ctx->pwin and the device detection lists (det_cut / det_cnt) as the last fft2D left them, with the geometry
-// they were written for.  fft2d_submit fills it (kSubmitted), isac_fft2d_collect confirms it (kCollected), and every function that rewrites one of those buffers calls
-// drop() first -- a later range stage, echo call or submit on the context makes the target list ISAC_ERR_INVALID_ARG, never stale.
-// isac_fft2d_redetect (cfar.hip) reads ctx->pwin under the same validity.
-struct TargetSource {
+// The one description of the context's last CPI, filled once, at the end of a successful fft2d_submit (fft2d.hip).  Readers: isac_fft2d_collect, the getters (under Fft2dLast::valid)
+// and -- with the device buffers it describes: ctx->ymid, ctx->pwin, det_cut / det_cnt -- isac_fft2d_get_targets (targets.hip) and isac_fft2d_redetect (cfar.hip).
+// A submit overwrites the record while the host copies of an OLDER CPI would otherwise still be readable: it clears Fft2dLast::valid (and the pending flag) before anything else,
+// and has to keep that order -- a getter must never pair the old lists with the new geometry.  state: are the device buffers still the ones this CPI left?  fft2d_submit sets
+// kSubmitted, isac_fft2d_collect promotes that to kCollected, and every function that rewrites one of them calls drop() first -- a later range stage, echo call or submit on the
+// context makes the target list ISAC_ERR_INVALID_ARG, never stale.
+struct Fft2dCpi {
   enum { kNone = 0, kSubmitted = 1, kCollected = 2 };
   int state = kNone;
   isac_est_params ep{};
   isac_cfar_config cfar{};
-  int A = 0, L = 0, nr = 0, nc = 0, cap = 0;      // antennas, symbols of ymid, window dims, per-antenna capacity of det_cut
+  CutWindow win{};                                   // of cfar: the dims of ctx->pwin, the rows of ctx->ymid
+  int A = 0, L = 0, cap = 0;                         // antennas, symbols of ymid, per-antenna capacity of det_cut
   const double* d_sind = nullptr; int n_steps = 0;   // MUSIC's ULA scan grid (a cached table of the context)
   void drop() { state = kNone; }
 };
 
-struct Fft2dPending {  // state between isac_fft2d_submit_dev and isac_fft2d_collect
+// The packed result of a CPI, one device -> host copy of first_bytes: [hdr 3 + A + 1 ints | 16-byte aligned spectrum slot, n_spec doubles | pow first | cut first],
+// `first` = the first pack_first detections (more: isac_fft2d_collect fetches the full lists)
+struct PackLayout {
+  static constexpr int pack_first = 4096;
+  size_t off_spec = 0, off_pow = 0, off_cut = 0, first_bytes = 0;
+  static PackLayout of(int A, int n_spec) {
+    PackLayout p;
+    p.off_spec = ((3 + (size_t)A + 1) * sizeof(int) + 15) & ~(size_t)15;
+    p.off_pow = p.off_spec + sizeof(double) * (size_t)(n_spec > 0 ? n_spec : 1);
+    p.off_cut = p.off_pow + sizeof(double) * (size_t)pack_first; p.first_bytes = p.off_cut + sizeof(int) * (size_t)pack_first;
+    return p;
+  }
+};
+struct Fft2dPending {  // state between isac_fft2d_submit_dev and isac_fft2d_collect (the CPI itself: Fft2dCpi)
   bool active = false;
-  isac_est_params ep{};
-  isac_cfar_config cfar{};
-  int A = 0, nr = 0, nc = 0, pack_first = 0;
-  size_t off_spec = 0, off_pow = 0, off_cut = 0;
-  int* d_pcut_full = nullptr;
-  double* d_ppow_full = nullptr;
+  PackLayout pack;
+  int* d_pcut_full = nullptr; double* d_ppow_full = nullptr;   // the full lists on the device, for more than pack_first detections
   DoaPlan doa; int first2d = 0;            // doa.upa2d: the pack's spectrum slot holds [counter | first2d find2DPeaks candidates]
 };
 
@@ -215,7 +226,7 @@ struct isac_ctx {
   isac::PinnedBuf pinned_csi;   // results of isac_csi_report*: its own buffer, so a CSI call between submit and collect cannot clobber a pending CPI
   isac::Fft2dLast last;
   isac::Fft2dPending pending;
-  isac::TargetSource tgt;            // isac_fft2d_get_targets: validity + geometry of ymid / pwin / det_* (above)
+  isac::Fft2dCpi tgt;                // the last submitted CPI (named for its first reader, isac_fft2d_get_targets): parameters, window, validity of ymid / pwin / det_*
   isac::DevBuf tgt_scratch;          // ... and its device scratch (hits map, candidate lists, snapshots)
   isac::DevBuf redet;                // isac_fft2d_redetect (cfar.hip): per-CUT flags, per-antenna lists sized for every CUT, counts, row flags
   isac::RangeCache range_cache;

@@ -25,20 +25,20 @@ int isac_get_logtab(isac_ctx* ctx, const isac::c64** out);
 int isac_get_rise_window(isac_ctx* ctx, int n_win, const double** out);
 int isac_get_windows(isac_ctx* ctx, int K, int n_ifft, const double** win_k, const double** win_r);
 // ---------------------------------------------------------------- rdm.hip
-int isac_rdm_power_window(isac_ctx* ctx, const isac_est_params* ep, const isac_cfar_config* cf, const isac::c64* d_rx, const isac::c64* d_tx, int K, int L, int A, int* nr_out, int* nc_out, bool use_cached_range);
-int isac_cfar_window(isac_ctx* ctx, const isac_est_params* ep, const isac_cfar_config* cf, int nr, int nc, int A, int cap);
+int isac_rdm_power_window(isac_ctx* ctx, const isac_est_params* ep, const isac_cfar_config* cf, const isac::c64* d_rx, const isac::c64* d_tx, int K, int L, int A, bool use_cached_range);   // leaves the window of isac::CutWindow::of(*cf) in ctx->pwin
+int isac_cfar_window(isac_ctx* ctx, const isac_est_params* ep, const isac_cfar_config* cf, int A, int cap);
 double cfar_alpha(int n_train, double pfa);   // CA, ThresholdFactor 'Auto': N (Pfa^(-1/N) - 1)
 namespace isac { struct CutRows { int row_lo, nr; }; }   // rows [row_lo, row_lo + nr) of the range-Doppler map (0-based): the CUT rows +- (guard + training)
 bool cut_rows_ok(const isac_est_params* ep, const isac_cfar_config* cf, isac::CutRows* out);              // false: the window leaves the map
 int cut_rows(isac_ctx* ctx, const isac_est_params* ep, const isac_cfar_config* cf, isac::CutRows* out);   // ... as ISAC_ERR_CFAR_WINDOW
 int isac_range_stage_into_cache(isac_ctx* ctx, const isac_est_params* ep, const isac_cfar_config* cf, const isac::c64* d_rx, const isac::c64* d_tx, int K, int L, int A);
 // ---------------------------------------------------------------- targets.hip: isac_fft2d_get_targets (include/isac_targets.h) -- the per-target list of the last completed fft2D.  It calls nothing but
-// isac_get_twiddles and is called by no other unit; what it shares with them is ctx->tgt (isac::TargetSource, isac_common.hpp): capi.hip fills it, rdm.hip / echo.hip drop it.
+// isac_get_twiddles and is called by no other unit; what it shares with them is ctx->tgt (isac::Fft2dCpi, isac_common.hpp): fft2d.hip fills it, rdm.hip / echo.hip drop it.
 // ---------------------------------------------------------------- cfar.hip: the GOCA / SOCA / OS detectors (include/isac_cfar.h): isac_cfar2d, isac_fft2d_redetect, isac_cfar_threshold_factor.  Reads ctx->tgt and
-// ctx->pwin, writes ctx->redet only; calls cfar_alpha (rdm.hip) and fft2d_estimates (capi.hip).
-// ---------------------------------------------------------------- capi.hip
+// ctx->pwin, writes ctx->redet only; calls cfar_alpha (rdm.hip) and fft2d_estimates (fft2d.hip).
+// ---------------------------------------------------------------- fft2d.hip: the host side of the fft2D pipeline -- submit, collect, submit_n / collect_n, the host-array call, the getters
 // host half of fft2D.m:63-99 on per-antenna CUT-order lists (callers: isac_fft2d_collect, isac_fft2d_redetect)
-int fft2d_estimates(isac_ctx* ctx, const isac_est_params* ep, const isac_cfar_config* cfar, int A, const int* ant_off, const std::vector<int>& cut, const std::vector<double>& pw, int num_dets_dev, std::vector<int32_t>& det_rc, isac_est_result* out);
+int fft2d_estimates(isac_ctx* ctx, const isac_est_params* ep, const isac::CutWindow& win, int A, const int* ant_off, const std::vector<int>& cut, const std::vector<double>& pw, int num_dets_dev, std::vector<int32_t>& det_rc, isac_est_result* out);
 // ---------------------------------------------------------------- cov.hip
 int isac_covariance_on(isac_ctx* ctx, hipStream_t st, const isac_c64* d_grid, int64_t N, int32_t A, isac_c64* d_Ra);
 int isac_covariance_lazy_on(isac_ctx* ctx, hipStream_t st, isac_c64* d_Ra);   // Ra of the context's native lazy echo grid
@@ -83,7 +83,7 @@ int isac_rx_frontend_jobs(isac_ctx* ctx, const isac_rx_frontend_job* jobs, int n
 // block gave up waiting (-2; isac_eigh_replay_recover, once the stream is idle), the signal-subspace vectors are not finite (-3), the distributed tridiagonalisation saw no progress (-4; sticky in info[6]).
 inline int* eig_info(isac_ctx* ctx, int A) { return reinterpret_cast<int*>((char*)ctx->eig_w.p + sizeof(double) * (size_t)A); }
 namespace isac {
-hipEvent_t timeline_base(hipStream_t st);   // capi.hip
+hipEvent_t timeline_base(hipStream_t st);   // fft2d.hip
 inline void timeline_mark(isac_ctx* ctx, int i, hipStream_t st) {
   static const bool on = std::getenv("ISAC_TIMELINE") != nullptr;   // diagnostic: per-stage event timeline
   if (!on) return;

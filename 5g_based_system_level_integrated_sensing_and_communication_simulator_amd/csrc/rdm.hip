@@ -541,14 +541,12 @@ static int launch_range(isac_ctx* ctx, const c64* rx, const c64* tx, int K, int 
 
 // The rows of the range-Doppler map the CFAR stage can touch: CUT rows +- (guard + training), 0-based.  false: the window leaves the map.
 bool cut_rows_ok(const isac_est_params* ep, const isac_cfar_config* cf, CutRows* out) {
-  const int hr = cf->guard[0] + cf->train[0];
-  const int row_lo = cf->row0 - 1 - hr, row_hi = cf->row1 - 1 + hr;   // 0-based inclusive
-  *out = CutRows{row_lo, row_hi - row_lo + 1};
-  return row_lo >= 0 && row_hi < ep->n_ifft;
+  const CutWindow w = CutWindow::of(*cf);
+  *out = CutRows{w.first_row - 1, w.nr};
+  return out->row_lo >= 0 && out->row_lo + out->nr <= ep->n_ifft;
 }
 int cut_rows(isac_ctx* ctx, const isac_est_params* ep, const isac_cfar_config* cf, CutRows* out) {
-  if (!cut_rows_ok(ep, cf, out)) return fail(ctx, ISAC_ERR_CFAR_WINDOW, "CUT training window exceeds the range-Doppler map");
-  return ISAC_OK;
+  return cut_rows_ok(ep, cf, out) ? ISAC_OK : fail(ctx, ISAC_ERR_CFAR_WINDOW, "CUT training window exceeds the range-Doppler map");
 }
 
 // Range stage (conj-multiply + Kaiser window + nIFFT-point IFFT + row selection + range-axis window, fft2D.m:37-45) of every (symbol, antenna) column:
@@ -575,12 +573,9 @@ static int range_stage_cut(isac_ctx* ctx, const isac_est_params* ep, const isac_
 // the LDS carves; anything else -- or ISAC_OPT_TAIL_FUSION = 0 -- takes memset + cfar_window_kernel + count.
 static bool tail_fusable(isac_ctx* ctx, const isac_est_params* ep, const isac_cfar_config* cf, TailGeom* out) {
   if (!ctx->tail_fusion) return false;
+  const CutWindow w = CutWindow::of(*cf);
   TailGeom g{};
-  g.gr = cf->guard[0]; g.gc = cf->guard[1];
-  g.hr = cf->guard[0] + cf->train[0]; g.hc = cf->guard[1] + cf->train[1];
-  g.n_cut_rows = cf->row1 - cf->row0 + 1;
-  g.n_cut_cols = cf->col1 - cf->col0 + 1;
-  g.nr = g.n_cut_rows + 2 * g.hr; g.nc = g.n_cut_cols + 2 * g.hc;
+  w.fill(g);
   g.pr = kTailRows - 2 * g.hr;
   if (g.pr < 8 || g.n_cut_rows < 1 || g.n_cut_cols < 1) return false;
   g.n_panels = (g.n_cut_rows + g.pr - 1) / g.pr;
@@ -590,22 +585,20 @@ static bool tail_fusable(isac_ctx* ctx, const isac_est_params* ep, const isac_cf
   g.alpha = cfar_alpha(n_train, cf->pfa);
   g.n_train = (double)n_train;
   g.sqrt_nfft = std::sqrt((double)ep->n_fft);
-  g.col_lo = cf->col0 - 1 - g.hc;
+  g.col_lo = w.first_col - 1;
   *out = g;
   return true;
 }
 
-int isac_rdm_power_window(isac_ctx* ctx, const isac_est_params* ep, const isac_cfar_config* cf, const c64* d_rx,
-                          const c64* d_tx, int K, int L, int A, int* nr_out, int* nc_out, bool use_cached_range) {
+int isac_rdm_power_window(isac_ctx* ctx, const isac_est_params* ep, const isac_cfar_config* cf, const c64* d_rx, const c64* d_tx, int K, int L, int A, bool use_cached_range) {
   const int n_ifft = ep->n_ifft, n_fft = ep->n_fft;
-  const int hc = cf->guard[1] + cf->train[1];
+  const CutWindow w = CutWindow::of(*cf);
   ctx->tgt.drop();                                                         // rewrites ctx->pwin
-  const int col_lo = cf->col0 - 1 - hc, col_hi = cf->col1 - 1 + hc;   // 0-based inclusive
-  if (cf->row1 < cf->row0 || cf->col1 < cf->col0) return fail(ctx, ISAC_ERR_INVALID_ARG, "empty CUT rectangle");
+  if (w.n_cut_rows < 1 || w.n_cut_cols < 1) return fail(ctx, ISAC_ERR_INVALID_ARG, "empty CUT rectangle");
   CutRows cr;
   ISAC_TRY(cut_rows(ctx, ep, cf, &cr));
-  if (col_lo < 0 || col_hi >= n_fft) return fail(ctx, ISAC_ERR_CFAR_WINDOW, "CUT training window exceeds the range-Doppler map");
-  const int row_lo = cr.row_lo, nr = cr.nr, nc = col_hi - col_lo + 1;
+  const int row_lo = cr.row_lo, nr = w.nr, col_lo = w.first_col - 1, nc = w.nc;   // 0-based
+  if (col_lo < 0 || col_lo + nc > n_fft) return fail(ctx, ISAC_ERR_CFAR_WINDOW, "CUT training window exceeds the range-Doppler map");
   const c64* twd = nullptr;
   ISAC_TRY(isac_get_twiddles(ctx, n_fft, &twd));
   ISAC_TRY(ensure(ctx, ctx->pwin, sizeof(double) * (size_t)nr * nc * A));
@@ -636,15 +629,11 @@ int isac_rdm_power_window(isac_ctx* ctx, const isac_est_params* ep, const isac_c
                        L, A, n_fft, twd, std::sqrt((double)n_fft), col_lo, nc, (double*)ctx->pwin.p, (c64*)nullptr);
     ISAC_HIP(hipGetLastError());
   }
-  *nr_out = nr;
-  *nc_out = nc;
   return ISAC_OK;
 }
 
 // CFAR over the window in ctx->pwin; leaves compact lists in ctx->det_* and numDets in ctx->misc[0].
-static int launch_tail_fused(isac_ctx* ctx, const isac_est_params* ep, const isac_cfar_config* cf, int nr, int nc, int A, int cap) {
-  TailGeom g;
-  if (!tail_fusable(ctx, ep, cf, &g) || g.nr != nr || g.nc != nc) return fail(ctx, ISAC_ERR_HIP, "internal: panel detector geometry mismatch");
+static int launch_tail_fused(isac_ctx* ctx, TailGeom g, int A, int cap) {
   g.cap = cap;
   const size_t seg_elems = (size_t)A * g.n_panels * (size_t)g.pr * g.n_cut_cols;
   const size_t n_slots = (size_t)A * g.n_panels;
@@ -668,18 +657,13 @@ static int launch_tail_fused(isac_ctx* ctx, const isac_est_params* ep, const isa
   return ISAC_OK;
 }
 
-int isac_cfar_window(isac_ctx* ctx, const isac_est_params* ep, const isac_cfar_config* cf, int nr, int nc, int A, int cap) {
+int isac_cfar_window(isac_ctx* ctx, const isac_est_params* ep, const isac_cfar_config* cf, int A, int cap) {
   ctx->tgt.drop();                                                         // rewrites the device detection lists
-  {
-    TailGeom tg;
-    if (tail_fusable(ctx, ep, cf, &tg)) return launch_tail_fused(ctx, ep, cf, nr, nc, A, cap);
-  }
+  TailGeom tg;
+  if (tail_fusable(ctx, ep, cf, &tg)) return launch_tail_fused(ctx, tg, A, cap);
+  const CutWindow w = CutWindow::of(*cf);
   CfarGeom g{};
-  g.nr = nr; g.nc = nc;
-  g.gr = cf->guard[0]; g.gc = cf->guard[1];
-  g.hr = cf->guard[0] + cf->train[0]; g.hc = cf->guard[1] + cf->train[1];
-  g.n_cut_rows = cf->row1 - cf->row0 + 1;
-  g.n_cut_cols = cf->col1 - cf->col0 + 1;
+  w.fill(g);
   g.cap = cap;
   const int n_train = (2 * g.hr + 1) * (2 * g.hc + 1) - (2 * g.gr + 1) * (2 * g.gc + 1);
   if (n_train <= 0) return fail(ctx, ISAC_ERR_INVALID_ARG, "TrainingBandSize must be positive");
@@ -687,12 +671,12 @@ int isac_cfar_window(isac_ctx* ctx, const isac_est_params* ep, const isac_cfar_c
   g.n_train = (double)n_train;
   // column panels: as many CUT columns as fit ~128 KB of LDS with full rows
   const size_t budget = 128 * 1024;
-  int panel = (int)(budget / (sizeof(double) * (size_t)nr)) - 2 * g.hc;
+  int panel = (int)(budget / (sizeof(double) * (size_t)g.nr)) - 2 * g.hc;
   if (panel < 1) return fail(ctx, ISAC_ERR_UNSUPPORTED, "CUT zone has too many rows for the LDS-staged detector");
   if (panel > g.n_cut_cols) panel = g.n_cut_cols;
   if ((long long)g.n_cut_rows * panel > 32 * 1024) panel = (32 * 1024) / g.n_cut_rows;   // <= 32 iterations of 1024 threads
   if (panel < 1) return fail(ctx, ISAC_ERR_UNSUPPORTED, "CUT zone has too many rows for the LDS-staged detector");
-  size_t lds = sizeof(double) * (size_t)nr * (panel + 2 * g.hc) + sizeof(int) * (32 * 16 + 4) + (size_t)g.n_cut_rows * panel + 16;
+  size_t lds = sizeof(double) * (size_t)g.nr * (panel + 2 * g.hc) + sizeof(int) * (32 * 16 + 4) + (size_t)g.n_cut_rows * panel + 16;
   ISAC_TRY(ensure(ctx, ctx->det_cut, sizeof(int) * (size_t)A * cap));
   ISAC_TRY(ensure(ctx, ctx->det_pow, sizeof(double) * (size_t)A * cap));
   ISAC_TRY(ensure(ctx, ctx->det_cnt, sizeof(int) * (size_t)A));

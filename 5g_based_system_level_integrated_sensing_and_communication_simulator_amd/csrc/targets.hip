@@ -160,18 +160,15 @@ using namespace isac;
 extern "C" int isac_fft2d_get_targets(isac_ctx* ctx, isac_target_list* out, isac_c64* snapshots, int32_t cap_snap) {
   ISAC_ENTER(ctx);
   if (!out || (snapshots && cap_snap < 0)) return fail(ctx, ISAC_ERR_INVALID_ARG, "NULL argument");
-  const TargetSource& ts = ctx->tgt;
-  if (!ctx->last.valid || ts.state != TargetSource::kCollected)
+  const Fft2dCpi& ts = ctx->tgt;
+  if (!ctx->last.valid || ts.state != Fft2dCpi::kCollected)
     return fail(ctx, ISAC_ERR_INVALID_ARG, "isac_fft2d_get_targets: no completed fft2D on this context whose range rows, power window and detection lists are still on the device");
   if (ts.ep.array_is_upa) return fail(ctx, ISAC_ERR_UNSUPPORTED, "isac_fft2d_get_targets: ULA only");
   const isac_est_params& ep = ts.ep;
-  const isac_cfar_config& cf = ts.cfar;
-  const int hr = cf.guard[0] + cf.train[0], hc = cf.guard[1] + cf.train[1];
+  const CutWindow& w = ts.win;
+  const int hr = w.hr, hc = w.hc;
   if (hr < 1 || hc < 1) return fail(ctx, ISAC_ERR_UNSUPPORTED, "isac_fft2d_get_targets: the local-maximum test needs a halo of at least one cell (guard + training) in both dimensions");
-  const int A = ts.A, L = ts.L, nr = ts.nr, nc = ts.nc;
-  const int n_cut_rows = cf.row1 - cf.row0 + 1, n_cut_cols = cf.col1 - cf.col0 + 1;
-  const int n_cut = n_cut_rows * n_cut_cols;
-  if (nr != n_cut_rows + 2 * hr || nc != n_cut_cols + 2 * hc) return fail(ctx, ISAC_ERR_HIP, "internal: power window geometry mismatch");
+  const int A = ts.A, L = ts.L, nr = w.nr, nc = w.nc, n_cut_rows = w.n_cut_rows, n_cut_cols = w.n_cut_cols, n_cut = (int)w.n_cut();
   std::memset(out, 0, sizeof(*out));
   // one scratch block: [hits nr x nc | count (16 ints)] zeroed, then the candidate lists, the selected cells and their results
   const size_t n_map = (size_t)nr * nc;
@@ -212,15 +209,15 @@ extern "C" int isac_fft2d_get_targets(isac_ctx* ctx, isac_target_list* out, isac
   std::vector<int> sel((size_t)2 * n);                                    // [window row | rdm column], 0-based
   for (int i = 0; i < n; ++i) {
     const int o = order[(size_t)i];
-    const int cr = ccut[(size_t)o] % n_cut_rows, cc = ccut[(size_t)o] / n_cut_rows;
-    out->row[i] = cf.row0 + cr;                                           // 1-based
-    out->col[i] = cf.col0 + cc;
+    const CutWindow::RowCol rc = w.row_col_of(ccut[(size_t)o]);           // 1-based
+    out->row[i] = rc.row;
+    out->col[i] = rc.col;
     out->hits[i] = chit[(size_t)o];
     out->power[i] = cs[(size_t)o];
-    out->rng[i] = (double)(out->row[i] - 1) * ep.r_res;                                   // fft2D.m:77,:81
-    out->vel[i] = ((double)out->col[i] - ep.n_fft / 2.0 - 1.0) * ep.v_res;                // fft2D.m:78,:82
-    sel[(size_t)i] = hr + cr;
-    sel[(size_t)n + i] = cf.col0 - 1 + cc;
+    out->rng[i] = CutWindow::range_of(rc.row, ep);
+    out->vel[i] = CutWindow::velocity_of(rc.col, ep);
+    sel[(size_t)i] = rc.row - w.first_row;
+    sel[(size_t)n + i] = rc.col - 1;
   }
   ISAC_TRY(stage_upload(ctx, d + off_sel, sel.data(), sizeof(int) * sel.size()));
   const size_t lds = sizeof(c64) * (size_t)A;
