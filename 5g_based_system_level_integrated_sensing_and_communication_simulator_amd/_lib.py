@@ -397,6 +397,15 @@ class Context:
         self.check(self.lib.isac_get_angular_spectrum2d(self.handle, _np_ptr(out), out.size, dims))
         return out
 
+    def angular_spectrum(self) -> np.ndarray:
+        """The dB spectrum [n_steps] of this context's last ULA azimuth scan -- from fft2D, doaEstimation.music, digitalBF / mvdrBF or the DoA stage of
+        music2D, whichever ran last (isac_fft2d_get_music_spectrum); IsacError(INVALID_ARG) while no such scan has completed on the context."""
+        n = C.c_int32(0)
+        self.check(self.lib.isac_fft2d_get_music_spectrum(self.handle, None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=np.float64)
+        self.check(self.lib.isac_fft2d_get_music_spectrum(self.handle, _np_ptr(out), out.size, C.byref(n)))
+        return out
+
     def share_streams(self, owner: "Context | None"):
         """Enqueue on `owner`'s two streams from now on (None: back to this context's own): isac_ctx_share_streams."""
         self.check(self.lib.isac_ctx_share_streams(self.handle, owner.handle if owner is not None else None))

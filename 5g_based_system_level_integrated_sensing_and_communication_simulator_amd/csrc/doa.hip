@@ -409,7 +409,8 @@ extern "C" int isac_music2d_dev(isac_ctx* ctx, const isac_est_params* ep, const 
   ISAC_TRY(get_sind_table(ctx, ep, &d_sind, &n_steps));
   ISAC_TRY(ensure(ctx, ctx->spec, sizeof(double) * (size_t)std::max(n_steps, std::max(r_steps, v_steps))));
   ISAC_TRY(isac_music_scan_dev(ctx, A, nullptr, Lsig, d_sind, n_steps, 0.5, (double*)ctx->spec.p, nullptr));
-  std::vector<double> spec((size_t)n_steps);
+  std::vector<double>& spec = ctx->last.spectrum_db;                    // the context's last ULA azimuth scan (isac_fft2d_get_music_spectrum)
+  spec.resize((size_t)n_steps);
   ISAC_TRY(copy_d2h(ctx, spec.data(), ctx->spec.p, sizeof(double) * (size_t)n_steps));
   ISAC_HIP(hipStreamSynchronize(ctx->stream));
   std::vector<double> azi;
@@ -450,6 +451,5 @@ extern "C" int isac_music2d_dev(isac_ctx* ctx, const isac_est_params* ep, const 
   out->n_vel = (int)std::min<size_t>(vl.size(), ISAC_MAX_EST);
   for (int i = 0; i < out->n_rng; ++i) out->rng_est[i] = rl[(size_t)i] * r_gran;                               // :122
   for (int i = 0; i < out->n_vel; ++i) out->vel_est[i] = vl[(size_t)i] * v_gran - mp->v_max / 2.0;             // :123
-  ctx->last.spectrum_db = pr;
   return ISAC_OK;
 }

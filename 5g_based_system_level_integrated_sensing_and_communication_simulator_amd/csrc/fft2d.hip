@@ -375,8 +375,8 @@ extern "C" int isac_fft2d_get_covariance(isac_ctx* ctx, isac_c64* Ra, int32_t A)
 
 extern "C" int isac_fft2d_get_music_spectrum(isac_ctx* ctx, double* p_db, int32_t cap, int32_t* n_steps) {
   ISAC_ENTER(ctx);
-  if (!ctx->last.valid) return fail(ctx, ISAC_ERR_INVALID_ARG, "no completed fft2D call on this context");
   const int n = (int)ctx->last.spectrum_db.size();
+  if (n == 0) return fail(ctx, ISAC_ERR_INVALID_ARG, "no ULA azimuth scan has completed on this context");
   if (n_steps) *n_steps = n;
   if (!p_db) return ISAC_OK;
   if (cap < n) return fail(ctx, ISAC_ERR_CAPACITY, "spectrum larger than capacity");

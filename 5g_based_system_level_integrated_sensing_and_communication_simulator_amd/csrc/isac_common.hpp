@@ -99,11 +99,11 @@ struct TableKey {
 };
 
 struct Fft2dLast {  // introspection of the last fft2D call: the host copies (their antennas and window: Fft2dCpi)
-  bool valid = false;               // false from every submit (and isac_ctx_reserve) on, true once isac_fft2d_collect has the estimates: all the isac_fft2d_get_* calls ask for
+  bool valid = false;               // false from every submit (and isac_ctx_reserve) on, true once isac_fft2d_collect has the estimates: the isac_fft2d_get_* calls ask for it, but for the spectrum's
   std::vector<int32_t> det_rc;      // [2 x total] 1-based, CUT order per antenna
   std::vector<double> det_pow;
   std::vector<int32_t> ant_off;     // [A+1]
-  std::vector<double> spectrum_db;
+  std::vector<double> spectrum_db;  // dB spectrum of the context's last ULA azimuth scan, whichever call ran it (doa_readout, isac_music2d_dev); empty: none (isac_fft2d_get_music_spectrum)
 };
 
 struct RangeCache {  // range rows pre-computed by the fused monoStaticSensing call for the next fft2D

@@ -113,8 +113,9 @@ def fft2D_collect(ctx):
 
 
 def fft2D_debug(ctx, A):
-    """Detection lists (CUT order, per antenna), the |rdm|^2 window, Ra and the MUSIC spectrum of the
-    last fft2D call on ``ctx`` -- what the parity tests compare against the oracle."""
+    """Detection lists (CUT order, per antenna), the |rdm|^2 window and Ra of the last fft2D call on ``ctx`` -- what the parity tests
+    compare against the oracle -- and ``spectrum_db``, the context's last ULA azimuth scan (``ctx.angular_spectrum()``: the fft2D's MUSIC
+    spectrum when nothing has scanned since; empty after a UPA CPI)."""
     lib = ctx.lib
     n_total = C.c_int32(0)
     off = np.zeros(A + 1, dtype=np.int32)
@@ -132,9 +133,11 @@ def fft2D_debug(ctx, A):
     ctx.check(lib.isac_fft2d_get_power_window(ctx.handle, pwin.ctypes.data_as(C.c_void_p), pwin.size, dims, C.byref(fr), C.byref(fc)))
     ra = np.zeros((A, A), dtype=np.complex128, order="F")
     ctx.check(lib.isac_fft2d_get_covariance(ctx.handle, ra.ctypes.data_as(C.c_void_p), A))
-    ns = C.c_int32(0)
-    ctx.check(lib.isac_fft2d_get_music_spectrum(ctx.handle, None, 0, C.byref(ns)))
-    spec = np.zeros(max(ns.value, 1), dtype=np.float64)
-    ctx.check(lib.isac_fft2d_get_music_spectrum(ctx.handle, spec.ctypes.data_as(C.c_void_p), spec.size, C.byref(ns)))
+    try:
+        spec = ctx.angular_spectrum()
+    except L.IsacError as e:                             # a UPA CPI runs no ULA scan: fft2D's collect left no spectrum
+        if e.name != "INVALID_ARG":
+            raise
+        spec = np.zeros(0, dtype=np.float64)
     return SimpleNamespace(detections=dets, det_pow=[pw[off[a]:off[a + 1]] for a in range(A)], power_window=pwin,
-                           first_row=int(fr.value), first_col=int(fc.value), Ra=ra, spectrum_db=spec[: ns.value])
+                           first_row=int(fr.value), first_col=int(fc.value), Ra=ra, spectrum_db=spec)

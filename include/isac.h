@@ -310,7 +310,12 @@ int isac_fft2d_range_stage_dev(isac_ctx* ctx, const isac_est_params* ep, const i
  *  - per-antenna detection indices in CUT order (before the peak sort), det_idx [2 x cap] 1-based,
  *    ant_offsets [A+1] prefix offsets into det_idx;
  *  - the |rdm|^2 window the detector saw: rows row0-hr..row1+hr, cols col0-hc..col1+hc, [nr x nc x A];
- *  - Ra [A x A], the MUSIC spectrum in dB [n_steps]. */
+ *  - Ra [A x A].
+ * isac_fft2d_get_music_spectrum: the dB spectrum [n_steps] of the context's last ULA azimuth scan -- from isac_fft2d_collect, isac_music_doa,
+ * isac_beamscan_doa or the DoA stage of isac_music2d_dev, whichever ran last (so a digitalBF / mvdrBF call leaves ITS spectrum here).  It succeeds
+ * whenever such a scan has completed on the context, an fft2D or not; ISAC_ERR_INVALID_ARG otherwise: a new context, after isac_ctx_reserve's dry
+ * run, and after an fft2D on a UPA (refused or through the 2-D scan, whose map is isac_get_angular_spectrum2d's), which clears it.  p_db == NULL:
+ * n_steps only. */
 int isac_fft2d_get_detections(isac_ctx* ctx, int32_t* det_idx, double* det_pow, int32_t cap,
                               int32_t* ant_offsets, int32_t* n_total);
 int isac_fft2d_get_power_window(isac_ctx* ctx, double* P, int64_t cap_elems, int32_t dims[3],

@@ -62,8 +62,8 @@ def music_spectrum_ula(uann, n_ants, rp):
         return mag2db(pm / pm.max())                                      # :95-96
 
 
-def music_doa(num_dets, rp, ra):
-    """[L, aziEst, eleEst] = music(numDets, radarEstParams, Ra)  (music.m:1)."""
+def music_doa(num_dets, rp, ra, return_db: bool = False):
+    """[L, aziEst, eleEst] = music(numDets, radarEstParams, Ra)  (music.m:1).  ``return_db`` appends PmusicdB (:96)."""
     ra = np.asarray(ra, dtype=np.complex128)
     n_ants = ra.shape[0]
     if num_dets is None:                                                  # :21-22
@@ -79,11 +79,20 @@ def music_doa(num_dets, rp, ra):
     _, locs = findpeaks(pdb, npeaks=n_sig, sort_descend=True)             # :102 (L = 0 raises)
     azi = locs * rp.azimuthScanGranularity - rp.azimuthScanScale / 2.0    # :103  (azi-1)*g - aMax/2, locs 0-based
     ele = np.full(azi.shape, np.nan)                                      # :104
+    if return_db:
+        return n_sig, azi.astype(np.float64), ele, pdb
     return n_sig, azi.astype(np.float64), ele
 
 
-def digital_bf(num_dets, rp, ra):
-    """digitalBF.m:55-86 (ULA)."""
+def _bf_results(pdb, num_dets, rp, return_db):
+    _, locs = findpeaks(pdb, npeaks=int(num_dets), sort_descend=True)     # digitalBF.m:84, mvdrBF.m:84
+    azi = locs * rp.azimuthScanGranularity - rp.azimuthScanScale / 2.0
+    out = (azi.astype(np.float64), np.full(azi.shape, np.nan))
+    return out + (pdb,) if return_db else out
+
+
+def digital_bf(num_dets, rp, ra, return_db: bool = False):
+    """digitalBF.m:55-86 (ULA).  ``return_db`` appends the dB spectrum (:76-78)."""
     ra = np.asarray(ra, dtype=np.complex128)
     n_ants = ra.shape[0]
     nn = np.arange(n_ants, dtype=np.float64)
@@ -91,14 +100,13 @@ def digital_bf(num_dets, rp, ra):
     p = np.array([np.vdot(aa, ra @ aa) for aa in
                   (np.exp(-2j * np.pi * nn * 0.5 * float(sind(a))) for a in angles)])   # :72
     pm = np.abs(p)
-    pdb = mag2db(pm / pm.max())
-    _, locs = findpeaks(pdb, npeaks=int(num_dets), sort_descend=True)     # :84
-    azi = locs * rp.azimuthScanGranularity - rp.azimuthScanScale / 2.0
-    return azi.astype(np.float64), np.full(azi.shape, np.nan)
+    with np.errstate(divide="ignore"):
+        pdb = mag2db(pm / pm.max())
+    return _bf_results(pdb, num_dets, rp, return_db)
 
 
-def mvdr_bf(num_dets, rp, ra):
-    """mvdrBF.m:55-86 (ULA):  1 / (a^H Ra^-1 a + eps)."""
+def mvdr_bf(num_dets, rp, ra, return_db: bool = False):
+    """mvdrBF.m:55-86 (ULA):  1 / (a^H Ra^-1 a + eps).  ``return_db`` appends the dB spectrum (:76-78)."""
     ra = np.asarray(ra, dtype=np.complex128)
     n_ants = ra.shape[0]
     nn = np.arange(n_ants, dtype=np.float64)
@@ -107,10 +115,9 @@ def mvdr_bf(num_dets, rp, ra):
     p = np.array([1.0 / (np.vdot(aa, ra_inv @ aa) + EPS) for aa in
                   (np.exp(-2j * np.pi * nn * 0.5 * float(sind(a))) for a in angles)])   # :72
     pm = np.abs(p)
-    pdb = mag2db(pm / pm.max())
-    _, locs = findpeaks(pdb, npeaks=int(num_dets), sort_descend=True)
-    azi = locs * rp.azimuthScanGranularity - rp.azimuthScanScale / 2.0
-    return azi.astype(np.float64), np.full(azi.shape, np.nan)
+    with np.errstate(divide="ignore"):
+        pdb = mag2db(pm / pm.max())
+    return _bf_results(pdb, num_dets, rp, return_db)
 
 
 def music2d(rp, scs_khz, rx_grid, tx_grid, return_debug: bool = False):

@@ -846,6 +846,7 @@ def test_music2d_matches_oracle(pkg, ctx, n_ants, targets, vel):
 
 
 def test_digital_and_mvdr_beamforming(pkg, ctx):
+    # (peak lists only, and on this covariance all three methods give the same ones: the spectra's VALUES are compared in tests/test_gpu_doa_spectra.py)
     sc = make_scene(n_ants=16, n_slots=1, nrb=24, with_noise=False)
     rp = pkg.sensing.radarParams(sc.cell, sc.carrier, sc.wave)
     m = np.arange(16)
