@@ -11,20 +11,20 @@ namespace {
 
 int eig_status(isac_ctx* ctx, int A, bool ql_ran = true /* false: the signal-subspace kernel delivered, the QL pipeline returned at once */) {
   int sweeps = 0;
-  ISAC_TRY(copy_d2h(ctx, &sweeps, eig_info(ctx, A), sizeof(int)));
+  ISAC_TRY(copy_d2h(ctx, &sweeps, &eig_info(ctx, A)->status, sizeof(int)));
   static const bool force = std::getenv("ISAC_EIG_FORCE_REPLAY_TIMEOUT") != nullptr;   // test hook: take the recovery path on every call ...
   if (force && ql_ran && sweeps >= 0 && A > 16 && ctx->eig_scratch.p) {
     ISAC_HIP(hipMemset(ctx->eig_v.p, 0xFF, sizeof(c64) * (size_t)A * A));               // ... with the eigenvectors destroyed first
-    sweeps = -2;
+    sweeps = kEighReplayTimeout;
   }
-  if (sweeps == -2) {                                // live replay blocks gave up waiting: Z and the rotations are intact, replay them offline
+  if (sweeps == kEighReplayTimeout) {                                // live replay blocks gave up waiting: Z and the rotations are intact, replay them offline
     ISAC_TRY(isac_eigh_replay_recover(ctx, A, ctx->stream));
     ISAC_HIP(hipStreamSynchronize(ctx->stream));
-    ISAC_TRY(copy_d2h(ctx, &sweeps, eig_info(ctx, A), sizeof(int)));
+    ISAC_TRY(copy_d2h(ctx, &sweeps, &eig_info(ctx, A)->status, sizeof(int)));
   }
-  if (sweeps < 0) return isac::fail(ctx, ISAC_ERR_HIP, sweeps == -1 ? "eigensolver: QL recurrence exceeded its rotation storage (no convergence)"
-                                                     : sweeps == -3 ? "eigensolver: the signal-subspace vectors are not finite (NaN / Inf in the covariance)"
-                                                     : sweeps == -4 ? "eigensolver: the distributed tridiagonalisation saw no progress for 2 s (its workgroups were not resident together)"
+  if (sweeps < 0) return isac::fail(ctx, ISAC_ERR_HIP, sweeps == kEighRotStorage ? "eigensolver: QL recurrence exceeded its rotation storage (no convergence)"
+                                                     : sweeps == kEighNotFinite ? "eigensolver: the signal-subspace vectors are not finite (NaN / Inf in the covariance)"
+                                                     : sweeps == kEighTridiagTimeout ? "eigensolver: the distributed tridiagonalisation saw no progress for 2 s (its workgroups were not resident together)"
                                                                      : "eigensolver: a replay block timed out waiting for the recurrence");
   return ISAC_OK;
 }
@@ -183,20 +183,20 @@ int sorted_eigenpairs(isac_ctx* ctx, int A, bool descending, std::vector<double>
 
 int eig_debug_print(isac_ctx* ctx, int A, int n_top /* < 0: isac_eigh */) {   // ISAC_DEBUG diagnostic: eigensolver phase counters on stderr
   if (!std::getenv("ISAC_DEBUG")) return ISAC_OK;
-  int inf[16] = {0};
-  ISAC_TRY(copy_d2h(ctx, inf, eig_info(ctx, A), sizeof(inf)));
+  EighInfo inf{};
+  ISAC_TRY(copy_d2h(ctx, &inf, eig_info(ctx, A), sizeof(inf)));
   if (n_top >= 0)
     std::fprintf(stderr, "[isac] eigh_top A=%d n_top=%d phases(x64 clk): tridiag=%d (n <= 64: reflector=%d matvec=%d matvec+update=%d) | subspace: set-up=%d solves=%d "
-                 "gram-schmidt=%d back-transform=%d\n", A, n_top, inf[1], inf[12], inf[13], inf[14], inf[8], inf[9], inf[10], inf[11]);
+                 "gram-schmidt=%d back-transform=%d\n", A, n_top, inf.cyc_a, inf.tri_a, inf.tri_b, inf.tri_c, inf.sub_setup, inf.sub_solve, inf.sub_mgs, inf.sub_back);
   else {
     if (A > 64 && A <= 256)
       std::fprintf(stderr, "[isac] eigh A=%d distributed tridiagonalisation, phases(x64 clk): column + p published=%d exchange wait=%d vector work=%d rank-2 update=%d\n", A,
-                   inf[12], inf[13], inf[14], inf[15]);
-    if (inf[5] < 0)
-      std::fprintf(stderr, "[isac] eigh A=%d Jacobi sweeps=%d phases(x64 clk): rotation parameters=%d two-sided updates=%d\n", A, inf[0], inf[1], inf[2]);
+                   inf.tri_a, inf.tri_b, inf.tri_c, inf.tri_d);
+    if (inf.rotations < 0)
+      std::fprintf(stderr, "[isac] eigh A=%d Jacobi sweeps=%d phases(x64 clk): rotation parameters=%d two-sided updates=%d\n", A, inf.status, inf.cyc_a, inf.cyc_b);
     else
-      std::fprintf(stderr, "[isac] eigh A=%d QL sweeps=%d rotations=%d phases(x64 clk): tridiag=%d formQ=%d ql-recurrence=%d replay=%d\n", A, inf[0],
-                   inf[5], inf[1], inf[2], inf[3], inf[4]);
+      std::fprintf(stderr, "[isac] eigh A=%d QL sweeps=%d rotations=%d phases(x64 clk): tridiag=%d formQ=%d ql-recurrence=%d replay=%d\n", A, inf.status,
+                   inf.rotations, inf.cyc_a, inf.cyc_b, inf.cyc_ql, inf.cyc_replay);
   }
   return ISAC_OK;
 }

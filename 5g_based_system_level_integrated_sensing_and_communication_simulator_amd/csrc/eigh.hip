@@ -10,6 +10,11 @@ namespace isac {
 // zheev-style safe scaling: when the largest |entry| lies outside [2^-400, 2^400] (squares would under/overflow), the
 // matrix is multiplied by an exact power of two on load and the eigenvalues by its inverse on output.  Returns the factor
 // (1.0 in the normal range, so ordinary inputs are untouched bit for bit).  s_red: >= 16 doubles of LDS.
+__device__ __forceinline__ double eigh_scale_of(double t /* the largest |entry| */) {
+  if (!(t > 0.0) || !(t < 1.7976931348623157e308)) return 1.0;      // zero matrix, Inf or NaN: leave as is
+  const int ex = ilogb(t);
+  return (ex < -400 || ex > 400) ? ldexp(1.0, -ex) : 1.0;
+}
 __device__ __forceinline__ double eigh_safe_scale(const c64* __restrict__ Hin, int count, double* s_red) {
   const int tid = threadIdx.x, nt = blockDim.x, lane = tid & 63, wid = tid >> 6, nw = nt >> 6;
   double mx = 0.0;
@@ -21,9 +26,7 @@ __device__ __forceinline__ double eigh_safe_scale(const c64* __restrict__ Hin, i
   double t = 0.0;
   for (int w = 0; w < nw; ++w) t = fmax(t, s_red[w]);
   __syncthreads();
-  if (!(t > 0.0) || !(t < 1.7976931348623157e308)) return 1.0;      // zero matrix, Inf or NaN: leave as is
-  const int ex = ilogb(t);
-  return (ex < -400 || ex > 400) ? ldexp(1.0, -ex) : 1.0;
+  return eigh_scale_of(t);
 }
 
 // ---------------------------------------------------------------- Hermitian eigensolver: one-workgroup cyclic Jacobi in LDS
@@ -51,17 +54,17 @@ __device__ __forceinline__ void rr_pair(int round, int k, int n /* even */, int&
 // was 99 ms at A = 256).
 __global__ __launch_bounds__(1024) void jacobi_eigh_kernel(const c64* __restrict__ Hin, int A, int max_sweeps,
                                                            double* __restrict__ w_out, c64* __restrict__ V_out,
-                                                           int* __restrict__ info /* [0]=sweeps used */) {
+                                                           EighInfo* __restrict__ info) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  const int n = (A + 1) & ~1;                      // pad to even with an isolated zero row/col
-  const int h = n / 2;
-  c64* lds0 = reinterpret_cast<c64*>(smem_raw);
-  c64* H = lds0;                                   // [n x n] column-major
-  c64* rg = lds0 + 2 * n * n;                      // [h] g_k
-  c64* V = H + n * n;                              // [n x n]
-  double* rc = reinterpret_cast<double*>(rg + h);  // [h] c_k
-  int* rp = reinterpret_cast<int*>(rc + h);        // [h] p_k
-  int* rq = rp + h;                                // [h] q_k
+  const JacobiLds lds = JacobiLds::of(A);
+  const int n = lds.n;                             // A padded to even with an isolated zero row/col
+  const int h = lds.h;
+  c64* H = reinterpret_cast<c64*>(smem_raw + lds.H);
+  c64* V = reinterpret_cast<c64*>(smem_raw + lds.V);
+  c64* rg = reinterpret_cast<c64*>(smem_raw + lds.rg);
+  double* rc = reinterpret_cast<double*>(smem_raw + lds.rc);
+  int* rp = reinterpret_cast<int*>(smem_raw + lds.rp);
+  int* rq = reinterpret_cast<int*>(smem_raw + lds.rq);
   const int tid = threadIdx.x, nt = blockDim.x;
   const double scl = eigh_safe_scale(Hin, A * A, reinterpret_cast<double*>(smem_raw));   // (LDS not in use yet; >= 128 B for n >= 2)
   for (int i = tid; i < n * n; i += nt) {
@@ -74,7 +77,7 @@ __global__ __launch_bounds__(1024) void jacobi_eigh_kernel(const c64* __restrict
   // diagonal pair, Demmel-Veselic style -- keeps the tiny noise eigen-pairs accurate next to a
   // 60 dB stronger signal eigenvalue; a Frobenius-relative test would stop far too early for them).
   const double tol2 = 1e-28;
-  int& s_dirty = rq[h];                            // lives in the dynamic LDS carve (keeps its base 16-B aligned)
+  int& s_dirty = *reinterpret_cast<int*>(smem_raw + lds.dirty);   // lives in the dynamic LDS carve (keeps its base 16-B aligned)
   int sweep = 0;
   long long cyc_p = 0, cyc_u = 0;                  // phase instrumentation (ISAC_DEBUG): cycles of thread 0
   for (; sweep < max_sweeps; ++sweep) {
@@ -161,7 +164,7 @@ __global__ __launch_bounds__(1024) void jacobi_eigh_kernel(const c64* __restrict
     int r = i % A, c = i / A;
     V_out[i] = V[r + n * c];
   }
-  if (tid == 0 && info) { info[0] = sweep; info[1] = (int)(cyc_p >> 6); info[2] = (int)(cyc_u >> 6); info[3] = 0; info[4] = 0; info[5] = -1; }
+  if (tid == 0 && info) { info->status = sweep; info->cyc_a = (int)(cyc_p >> 6); info->cyc_b = (int)(cyc_u >> 6); info->cyc_ql = 0; info->cyc_replay = 0; info->rotations = kEighRouteJacobi; }
 }
 
 // ---------------------------------------------------------------- Hermitian eigensolver II: Householder tridiagonalisation + implicit QL
@@ -187,15 +190,16 @@ __global__ __launch_bounds__(1024) void jacobi_eigh_kernel(const c64* __restrict
 //   (c) w' = tau' acc + alpha v'  becomes the pending pair of step k + 1.
 // Element for element the arithmetic is that of the two-pass form (same update expression, same partial-sum order of the product): d, e,
 // tau and the reflectors come out bit-identical.
-__global__ __launch_bounds__(1024) void eigh_tridiag_fused_kernel(const c64* __restrict__ Hin, int n, void* scratch, int* __restrict__ info) {
+__global__ __launch_bounds__(1024) void eigh_tridiag_fused_kernel(const c64* __restrict__ Hin, int n, void* scratch, EighInfo* __restrict__ info) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   EighScratch S(scratch, n);
+  const TridiagFusedLds lds = TridiagFusedLds::of(n);
   c64* M = S.M;                                     // [n x n] column-major working matrix (reflectors end up below the subdiagonal)
-  c64* sv = reinterpret_cast<c64*>(smem_raw);       // [n] pending reflector (zero before the first step)
-  c64* sw = sv + n;                                 // [n] pending w
-  c64* sn = sw + n;                                 // [n] the step's new reflector
-  c64* spart = sn + n;                              // [4][n] partial matrix-vector products
-  double* sred = reinterpret_cast<double*>(spart + 4 * n);   // [2 x 16] block-reduction scratch
+  c64* sv = reinterpret_cast<c64*>(smem_raw + lds.sv);         // pending reflector (zero before the first step)
+  c64* sw = reinterpret_cast<c64*>(smem_raw + lds.sw);
+  c64* sn = reinterpret_cast<c64*>(smem_raw + lds.sn);
+  c64* spart = reinterpret_cast<c64*>(smem_raw + lds.spart);
+  double* sred = reinterpret_cast<double*>(smem_raw + lds.sred);
   const int tid = threadIdx.x, nt = blockDim.x, lane = tid & 63, wid = tid >> 6, nw = nt >> 6;
   auto block_sum2 = [&](double a, double b, double& oa, double& ob) {   // sum over the workgroup of two values
     for (int o = 32; o > 0; o >>= 1) { a += __shfl_down(a, o); b += __shfl_down(b, o); }
@@ -227,15 +231,7 @@ __global__ __launch_bounds__(1024) void eigh_tridiag_fused_kernel(const c64* __r
     double xnorm2, unused;
     block_sum2(xn2, dummy, xnorm2, unused);
     const c64 alpha = M[k + 1 + n * k];
-    c64 tau = mk(0.0, 0.0), scale = mk(0.0, 0.0);
-    double beta = alpha.re;
-    if (xnorm2 != 0.0 || alpha.im != 0.0) {         // zlarfg
-      beta = -copysign(sqrt(alpha.re * alpha.re + alpha.im * alpha.im + xnorm2), alpha.re);
-      tau = mk((beta - alpha.re) / beta, -alpha.im / beta);
-      const c64 dlt = mk(alpha.re - beta, alpha.im);
-      const double dn = dlt.re * dlt.re + dlt.im * dlt.im;
-      scale = mk(dlt.re / dn, -dlt.im / dn);        // 1 / (alpha - beta)
-    }
+    const auto [beta, tau, scale] = zlarfg<false>(alpha, xnorm2);
     for (int i = k + 1 + tid; i < n; i += nt) {
       const c64 vi = (i == k + 1) ? mk(1.0, 0.0) : M[i + n * k] * scale;
       sn[i] = vi;
@@ -301,7 +297,7 @@ __global__ __launch_bounds__(1024) void eigh_tridiag_fused_kernel(const c64* __r
   if (tid == 0) {
     const c64 c = M[n - 1 + n * (n - 1)] - mul_conj(sv[n - 1], sw[n - 1]) - mul_conj(sw[n - 1], sv[n - 1]);   // the last pending update
     S.d[n - 1] = c.re; S.e[n - 1] = 0.0;
-    if (info) { info[1] = (int)((clock64() - t_start) >> 6); info[6] = 0; }
+    if (info) { info->cyc_a = (int)((clock64() - t_start) >> 6); info->sticky = 0; }
   }
 }
 
@@ -319,7 +315,7 @@ __global__ __launch_bounds__(1024) void eigh_tridiag_fused_kernel(const c64* __r
 // no fence, no reset between launches; the consumer re-reads the 64 bytes of each of its rows (p_i and the next column's entry) with sc1 loads until
 // all tags match.  Two parities of the area alternate: a wavefront can overwrite parity k & 1 at step k + 2 only after it has consumed every other
 // wavefront's step k + 1, which they publish after reading step k.  A wavefront returns after the step that consumed its last column; a poll that
-// sees no progress for ~2 s gives up with info[0] = -4.
+// sees no progress for ~2 s gives up with kEighTridiagTimeout.
 //   History (n = 256, profiles/r04_tridiag_dist.txt): 16 workgroups of 256 threads, agent-scope atomics + one step stamp per workgroup behind
 // s_waitcnt 1.0 ms (with __threadfence() instead 2.8 ms); tagged granules 0.9 ms -- 58 % of it the O(n) vector work, a chain of ~550 dependent
 // instructions through two workgroup-wide sums per reflector; this form: the sums stay inside the wavefront (DPP), four independent rows per lane.
@@ -343,10 +339,10 @@ __device__ __forceinline__ double row16_sum_dpp(double x) {      // every lane: 
   x += dpp_move<0x128, 0xf>(x);
   return x;
 }
-__global__ __launch_bounds__(256) void eigh_tridiag_dist_kernel(const c64* __restrict__ Hin, int n, void* scratch, int* __restrict__ info, unsigned base,
+__global__ __launch_bounds__(256) void eigh_tridiag_dist_kernel(const c64* __restrict__ Hin, int n, void* scratch, EighInfo* __restrict__ info, unsigned base,
                                                                       int stride, int slot, int far_only, int force_abort) {
   if ((int)(blockIdx.x % (unsigned)stride) != slot) return;
-  if (force_abort) { if (threadIdx.x == 0 && info) info[0] = info[6] = -4; return; }   // test hook (ISAC_EIG_FORCE_TRIDIAG_TIMEOUT): behave like an exchange that timed out
+  if (force_abort) { if (threadIdx.x == 0 && info) eigh_mark_tridiag_timeout(info); return; }   // test hook (ISAC_EIG_FORCE_TRIDIAG_TIMEOUT): behave like an exchange that timed out
   __shared__ __attribute__((aligned(16))) c64 sv[2][kTdMaxN];      // the reflector of the step, by parity   (sv, sw: every wavefront writes the same bits)
   __shared__ __attribute__((aligned(16))) c64 sw[kTdMaxN];         // w of the step
   __shared__ __attribute__((aligned(16))) c64 scol4[4][kTdMaxN];   // per wavefront: the owner's next column, row by row
@@ -400,11 +396,8 @@ __global__ __launch_bounds__(256) void eigh_tridiag_dist_kernel(const c64* __res
     }
     for (int o = 32; o > 0; o >>= 1) t = fmax(t, __shfl_xor(t, o));
     __syncthreads();
-    if (s_abort) { if (threadIdx.x == 0 && info) info[0] = info[6] = -4; return; }   // (info[6]: sticky -- the kernels behind overwrite info[0])
-    if (t > 0.0 && t < 1.7976931348623157e308) {                     // (eigh_safe_scale's rule)
-      const int ex = ilogb(t);
-      if (ex < -400 || ex > 400) scl = ldexp(1.0, -ex);
-    }
+    if (s_abort) { if (threadIdx.x == 0 && info) eigh_mark_tridiag_timeout(info); return; }
+    scl = eigh_scale_of(t);
 #pragma unroll
     for (int u = 0; u < 16; ++u) a[u] = a[u] * scl;
 #pragma unroll
@@ -421,16 +414,7 @@ __global__ __launch_bounds__(256) void eigh_tridiag_dist_kernel(const c64* __res
 #pragma unroll
     for (int r = 0; r < 4; ++r) { const int i = lane + 64 * r; if (i > k2 + 1 && i < n) xn2 += ci[r].re * ci[r].re + ci[r].im * ci[r].im; }
     xn2 = wave_sum_dpp(xn2);
-    c64 tau = mk(0.0, 0.0), scale = mk(0.0, 0.0);
-    double beta = alpha.re;
-    if (xn2 != 0.0 || alpha.im != 0.0) {                             // zlarfg (two reciprocals instead of four divisions)
-      beta = -copysign(sqrt(alpha.re * alpha.re + alpha.im * alpha.im + xn2), alpha.re);
-      const double ib = 1.0 / beta;
-      tau = mk((beta - alpha.re) * ib, -alpha.im * ib);
-      const c64 dlt = mk(alpha.re - beta, alpha.im);
-      const double idn = 1.0 / (dlt.re * dlt.re + dlt.im * dlt.im);
-      scale = mk(dlt.re * idn, -dlt.im * idn);                       // 1 / (alpha - beta)
-    }
+    const auto [beta, tau, scale] = zlarfg<true>(alpha, xn2);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int i = lane + 64 * r;
@@ -506,7 +490,7 @@ __global__ __launch_bounds__(256) void eigh_tridiag_dist_kernel(const c64* __res
       sc[par][i] = cr;
     }
     __syncthreads();
-    if (s_abort) { if (threadIdx.x == 0 && info) info[0] = info[6] = -4; return; }   // (info[6]: sticky -- the kernels behind overwrite info[0])
+    if (s_abort) { if (threadIdx.x == 0 && info) eigh_mark_tridiag_timeout(info); return; }
     c64 pi[4], ci[4];
     bool live[4];
 #pragma unroll
@@ -549,8 +533,8 @@ __global__ __launch_bounds__(256) void eigh_tridiag_dist_kernel(const c64* __res
     c_upd += clock64() - c3;
   }
   if (writer && lane == 0 && info) {
-    info[1] = (int)((clock64() - t_start) >> 6);
-    info[12] = (int)(c_pub >> 6); info[13] = (int)(c_poll >> 6); info[14] = (int)(c_vec >> 6); info[15] = (int)(c_upd >> 6);
+    info->cyc_a = (int)((clock64() - t_start) >> 6);
+    info->tri_a = (int)(c_pub >> 6); info->tri_b = (int)(c_poll >> 6); info->tri_c = (int)(c_vec >> 6); info->tri_d = (int)(c_upd >> 6);
   }
 }
 
@@ -560,19 +544,19 @@ __global__ __launch_bounds__(256) void eigh_tridiag_dist_kernel(const c64* __res
 // matrix-vector product (partials exchanged through LDS: barrier 1) and of the rank-2 update (barrier 2 before the next step reads the
 // updated column).  The matrix lives in LDS, the reflectors go straight to the scratch zungtr reads.  222 -> ~120 us at n = 64
 // (host-call time of the whole eigensolver 0.905 -> 0.807 ms).
-constexpr int kTriWaves = 4;       // wavefronts of eigh_tridiag_small_kernel (eight: the same 124 us at n = 64 -- every step is a chain of LDS round trips, DPP sums and two barriers, ~5 000 cycles whatever the column count per wave)
 // (Round 4 tried the matrix in REGISTERS: wave w owns the columns j = w (mod 4), the 63 steps unrolled, per-column operands by v_readlane, LDS only for
 // the new reflector and the partial products -- 35 000 instructions, 128.9 us against this kernel's 129.3: the step is bound by what ONE wave can issue
 // (~8 cycles per instruction: ~550 instructions per step either way) and by the serial zlarfg chain (sqrt + three fp64 divides + three DPP sums),
 // not by the LDS traffic it removed.  profiles/r04_negative_results.txt.)
-__global__ __launch_bounds__(64 * kTriWaves) void eigh_tridiag_small_kernel(const c64* __restrict__ Hin, int n, void* scratch, int* __restrict__ info) {
+__global__ __launch_bounds__(64 * kTriWaves) void eigh_tridiag_small_kernel(const c64* __restrict__ Hin, int n, void* scratch, EighInfo* __restrict__ info) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   constexpr int NW = kTriWaves;
   EighScratch S(scratch, n);
-  c64* M = reinterpret_cast<c64*>(smem_raw);                     // [n x n] column-major working matrix
-  c64* spart = M + (size_t)n * n;                                 // [NW][64] partial matrix-vector products
-  c64* svw = spart + NW * 64;                                     // [NW waves][2][64]: each wave's own copy of v and w
-  double* sred = reinterpret_cast<double*>(svw + NW * 2 * 64);    // [32] scratch of eigh_safe_scale
+  const TridiagSmallLds lds = TridiagSmallLds::of(n);
+  c64* M = reinterpret_cast<c64*>(smem_raw + lds.M);
+  c64* spart = reinterpret_cast<c64*>(smem_raw + lds.spart);
+  c64* svw = reinterpret_cast<c64*>(smem_raw + lds.svw);
+  double* sred = reinterpret_cast<double*>(smem_raw + lds.sred);
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   c64* my_v = svw + (size_t)wid * 128;
   c64* my_w = my_v + 64;
@@ -590,15 +574,7 @@ __global__ __launch_bounds__(64 * kTriWaves) void eigh_tridiag_small_kernel(cons
     const c64 xi = below ? M[lane + n * k] : mk(0.0, 0.0);
     const c64 alpha = M[k + 1 + n * k];                           // (broadcast read)
     const double xnorm2 = wave_sum(xi.re * xi.re + xi.im * xi.im);
-    c64 tau = mk(0.0, 0.0), scale = mk(0.0, 0.0);
-    double beta = alpha.re;
-    if (xnorm2 != 0.0 || alpha.im != 0.0) {                       // zlarfg
-      beta = -copysign(sqrt(alpha.re * alpha.re + alpha.im * alpha.im + xnorm2), alpha.re);
-      tau = mk((beta - alpha.re) / beta, -alpha.im / beta);
-      const c64 dlt = mk(alpha.re - beta, alpha.im);
-      const double dn = dlt.re * dlt.re + dlt.im * dlt.im;
-      scale = mk(dlt.re / dn, -dlt.im / dn);                      // 1 / (alpha - beta)
-    }
+    const auto [beta, tau, scale] = zlarfg<false>(alpha, xnorm2);
     const c64 vi = lane == k + 1 ? mk(1.0, 0.0) : (below ? xi * scale : mk(0.0, 0.0));
     my_v[lane] = vi;                                              // (wave-private: no barrier, LDS operations of a wave are in order)
     if (wid == 0) {
@@ -657,28 +633,29 @@ __global__ __launch_bounds__(64 * kTriWaves) void eigh_tridiag_small_kernel(cons
   }
   if (tid == 0) {
     S.d[n - 1] = M[n - 1 + n * (n - 1)].re; S.e[n - 1] = 0.0;
-    if (info) { info[1] = (int)((clock64() - t_start) >> 6); info[6] = 0; info[12] = (int)(c_refl >> 6); info[13] = (int)(c_mv >> 6); info[14] = (int)(c_upd >> 6); }
+    if (info) { info->cyc_a = (int)((clock64() - t_start) >> 6); info->sticky = 0; info->tri_a = (int)(c_refl >> 6); info->tri_b = (int)(c_mv >> 6); info->tri_c = (int)(c_upd >> 6); }
   }
 }
 
 template <bool LDS, bool LIVE>
 __device__ __forceinline__ void eigh_replay_body(int n, const EighScratch& S, c64* __restrict__ V_out, char* smem_raw, int block,
-                                                 int bt, int* __restrict__ info);
+                                                 int bt, EighInfo* __restrict__ info);
 
 // block 0: zungtr; block 1 (first wavefront): tql2 recurrence, rotations recorded; blocks >= 2: live replay
-__global__ __launch_bounds__(1024) void eigh_formq_ql_kernel(int n, void* scratch, double* __restrict__ w_out, int* __restrict__ info,
+__global__ __launch_bounds__(1024) void eigh_formq_ql_kernel(int n, void* scratch, double* __restrict__ w_out, EighInfo* __restrict__ info,
                                                              c64* __restrict__ V_out, int replay_bt, const int* __restrict__ ctl) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   if (ctl && ctl[0] == 1) return;                   // (grid-uniform) music_subspace_kernel has delivered the signal vectors: no full basis needed
   EighScratch S(scratch, n);
+  const FormqQlLds lds = FormqQlLds::of(n);
   const int tid = threadIdx.x, nt = blockDim.x, lane = tid & 63, wid = tid >> 6, nw = nt >> 6;
   const long long t0 = clock64();
   if (blockIdx.x == 0) {
     // ---- Q (zungtr): Z = H_0 H_1 ... H_{n-2}, accumulated backwards
     const c64* M = S.M;
     c64* Z = S.Z;
-    c64* sv = reinterpret_cast<c64*>(smem_raw);     // [n]
-    c64* sp = sv + n;                               // [n]
+    c64* sv = reinterpret_cast<c64*>(smem_raw + lds.sv);
+    c64* sp = reinterpret_cast<c64*>(smem_raw + lds.sp);
     for (int i = tid; i < n * n; i += nt) Z[i] = mk((i % n) == (i / n) ? 1.0 : 0.0, 0.0);
     __syncthreads();
     for (int k = n - 2; k >= 0; --k) {
@@ -704,7 +681,7 @@ __global__ __launch_bounds__(1024) void eigh_formq_ql_kernel(int n, void* scratc
     __syncthreads();
     if (tid == 0) {
       __hip_atomic_store(&S.cnt[3], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-      if (info) info[2] = (int)((clock64() - t0) >> 6);
+      if (info) info->cyc_b = (int)((clock64() - t0) >> 6);
     }
     return;
   }
@@ -719,9 +696,9 @@ __global__ __launch_bounds__(1024) void eigh_formq_ql_kernel(int n, void* scratc
   // recurrence from registers = 160 cycles per rotation), so the loop is written for instruction count: (d, e) are
   // interleaved in one LDS array (one 16-byte read and one 16-byte write per rotation), no per-rotation underflow test
   // (a zero r^2 turns the carried values into NaNs, tested once after the sweep).
-  c64* de = reinterpret_cast<c64*>(smem_raw);       // [n] (.re = d, .im = e)
-  c64* bde = de + n;                                // [n] backup of the sweep window (r == 0 recovery)
-  c64* rec = bde + n;                               // [n] rotations of the current sweep
+  c64* de = reinterpret_cast<c64*>(smem_raw + lds.de);     // (.re = d, .im = e)
+  c64* bde = reinterpret_cast<c64*>(smem_raw + lds.bde);   // backup of the sweep window (r == 0 recovery)
+  c64* rec = reinterpret_cast<c64*>(smem_raw + lds.rec);
   for (int i = lane; i < n; i += 64) de[i] = mk(S.d[i], S.e[i]);
   int sweeps = 0;
   long long nrot = 0;
@@ -849,13 +826,13 @@ __global__ __launch_bounds__(1024) void eigh_formq_ql_kernel(int n, void* scratc
     S.cnt[1] = (int)nrot; S.cnt[2] = overflow;
     __hip_atomic_store(&S.cnt[0], sweeps, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_store(&S.cnt[4], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    if (info) { info[0] = info[6] == -4 ? -4 : overflow ? -1 : sweeps; info[3] = (int)((clock64() - t0) >> 6); info[5] = (int)nrot; }   // (a timed-out tridiagonalisation stays reported)
+    if (info) { eigh_set_status(info, overflow ? kEighRotStorage : sweeps); info->cyc_ql = (int)((clock64() - t0) >> 6); info->rotations = (int)nrot; }
   }
 }
 
 // Replay of the recorded plane rotations on Z.  One thread per (row, real/imaginary part): the rotations are real, so
 // the two parts of a row never mix, and rows are independent.  LDS = true: the workgroup keeps its rows in LDS for the
-// whole replay (bt x n doubles, column-major over the threads: conflict-free), Z is read once and V written once.
+// whole replay (ReplayLds: bt x n doubles, column-major over the threads: conflict-free), Z is read once and V written once.
 // (Streaming the rows through global memory instead stalls on the store acknowledgements -- loads and stores share
 // vmcnt on this chip -- ~480 cycles per rotation; it remains as the fallback for n too large for LDS.)
 // LIVE = true: the block runs NEXT TO the zungtr and QL-recurrence blocks of the same launch and consumes the sweeps as
@@ -871,7 +848,7 @@ __device__ __forceinline__ int eigh_spin_until(const int* flag, int want_gt) {  
 
 template <bool LDS, bool LIVE>
 __device__ __forceinline__ void eigh_replay_body(int n, const EighScratch& S, c64* __restrict__ V_out, char* smem_raw, int block,
-                                                 int bt, int* __restrict__ info) {
+                                                 int bt, EighInfo* __restrict__ info) {
   const long long t0 = clock64();
   const int tx = threadIdx.x;
   if (tx >= bt) return;                             // (LIVE launch: 1024-thread blocks, the first bt threads work)
@@ -884,8 +861,9 @@ __device__ __forceinline__ void eigh_replay_body(int n, const EighScratch& S, c6
   long long cs;
   bool timeout = false;
   if (LIVE) timeout = eigh_spin_until(&S.cnt[3], 0) < 0;         // Z = Q complete (zungtr block)
+  const ReplayLds lds = ReplayLds::of(n, bt, LDS);
   if constexpr (LDS) {
-    Zd = reinterpret_cast<double*>(smem_raw) + tx;
+    Zd = reinterpret_cast<double*>(smem_raw + lds.rows) + tx;
     cs = bt;
     for (int c = 0; c < n; ++c) Zd[cs * c] = Zg[gs * c];
   } else {
@@ -897,7 +875,7 @@ __device__ __forceinline__ void eigh_replay_body(int n, const EighScratch& S, c6
   // The (c, s) of one sweep are staged in LDS: a direct read per rotation is a dependent L2 round trip (~330 cycles per
   // rotation measured).  Offline they are double buffered (loads of sweep q+1 issued before sweep q is replayed); live,
   // each sweep is fetched when it has been published (the replay is faster than the recurrence that feeds it).
-  c64* stage = reinterpret_cast<c64*>(smem_raw + (LDS ? (size_t)bt * n * sizeof(double) : 0));   // [2][n]
+  c64* stage = reinterpret_cast<c64*>(smem_raw + lds.stage);
   const int per_thread = (n + bt - 1) / bt;         // rotations each thread stages per sweep (<= 8 for bt >= n / 8)
   c64 pre[8];
   auto fetch = [&](long long o, int cnt) {          // unconditional loads (clamped): all eight fly together
@@ -997,11 +975,11 @@ __device__ __forceinline__ void eigh_replay_body(int n, const EighScratch& S, c6
     double* Vd = reinterpret_cast<double*>(V_out) + item;
     for (int c = 0; c < n; ++c) Vd[gs * c] = Zd[cs * c];
   }
-  if (gid == 0 && info) { info[4] = (int)((clock64() - t0) >> 6); if (timeout && info[6] != -4) info[0] = -2; }
+  if (gid == 0 && info) { info->cyc_replay = (int)((clock64() - t0) >> 6); if (timeout) eigh_set_status(info, kEighReplayTimeout); }
 }
 
 template <bool LDS>
-__global__ __launch_bounds__(256) void eigh_replay_kernel(int n, void* scratch, c64* __restrict__ V_out, int* __restrict__ info,
+__global__ __launch_bounds__(256) void eigh_replay_kernel(int n, void* scratch, c64* __restrict__ V_out, EighInfo* __restrict__ info,
                                                           const int* __restrict__ ctl) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   if (ctl && ctl[0] == 1) return;
@@ -1020,12 +998,12 @@ __global__ __launch_bounds__(256) void eigh_replay_kernel(int n, void* scratch, 
 
 // Four wavefronts per workgroup = one per SIMD: the count recurrence is a dependent chain of ~12 fp64 instructions per matrix row, and
 // a SIMD shared by four such chains runs each at a quarter of the rate (16 waves per workgroup: 70 us at n = 64) while the other CUs idle.
-constexpr int kBisectWaves = 4;                          // eigenvalues per workgroup (one wavefront each)
 __global__ __launch_bounds__(64 * kBisectWaves) void eigh_bisect_kernel(int n, void* scratch, double* __restrict__ w_out /* [n] ascending */) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   EighScratch S(scratch, n);
-  c64* de = reinterpret_cast<c64*>(smem_raw);            // [n]  (.re = d_i, .im = e_{i-1}^2 with e_{-1} = 0)
-  double* sred = reinterpret_cast<double*>(de + n);      // [3][16]
+  const BisectLds lds = BisectLds::of(n);
+  c64* de = reinterpret_cast<c64*>(smem_raw + lds.de);   // (.re = d_i, .im = e_{i-1}^2 with e_{-1} = 0)
+  double* sred = reinterpret_cast<double*>(smem_raw + lds.sred);
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   double gl = 1.7976931348623157e308, gu = -1.7976931348623157e308, e2m = 0.0;
   for (int i = tid; i < n; i += 64 * kBisectWaves) {     // Gershgorin interval
@@ -1081,7 +1059,7 @@ using namespace isac;
 static std::atomic<unsigned> td_launches{0};
 
 // Householder tridiagonalisation of H (order n >= 3) into ctx->eig_scratch, on stream st
-static int launch_tridiag(isac_ctx* ctx, const c64* d_H, int n, hipStream_t st, int* info) {
+static int launch_tridiag(isac_ctx* ctx, const c64* d_H, int n, hipStream_t st, EighInfo* info) {
   {
     const void* before = ctx->eig_scratch.p;
     const size_t cap_before = ctx->eig_scratch.cap;
@@ -1091,9 +1069,8 @@ static int launch_tridiag(isac_ctx* ctx, const c64* d_H, int n, hipStream_t st, 
   }
   void* gs = ctx->eig_scratch.p;
   if (n <= 64) {       // four waves, two barriers per step, matrix in LDS (the general kernel with its matrix in LDS: 222 us at n = 64; this one ~120)
-    const size_t ldss = sizeof(c64) * ((size_t)n * n + kTriWaves * 64 + kTriWaves * 2 * 64) + sizeof(double) * 32 + 64;
     ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(eigh_tridiag_small_kernel), (size_t)(112 * 1024)));
-    hipLaunchKernelGGL(eigh_tridiag_small_kernel, dim3(1), dim3(64 * kTriWaves), ldss, st, d_H, n, gs, info);
+    hipLaunchKernelGGL(eigh_tridiag_small_kernel, dim3(1), dim3(64 * kTriWaves), TridiagSmallLds::of(n).bytes, st, d_H, n, gs, info);
   } else {
     static const char* td_env = std::getenv("ISAC_EIG_TRIDIAG_DIST");   // test hook: "0" the one-workgroup kernels for every n; "far" write-through exchange at stride 8; "s1" stride 1
     const bool td_off = td_env && td_env[0] == '0';
@@ -1107,11 +1084,11 @@ static int launch_tridiag(isac_ctx* ctx, const c64* d_H, int n, hipStream_t st, 
       // every 8th workgroup of the grid works (the others return at once): the dispatcher deals workgroups round-robin to the 8 XCDs, so the working ones share
       // an L2 and the exchange can stay in it -- verified by the kernel (XCC ids in its first exchange), never assumed
       static const bool force_to = std::getenv("ISAC_EIG_FORCE_TRIDIAG_TIMEOUT") != nullptr;   // test hook: every distributed reduction reports a time-out
-      ISAC_HIP(hipMemsetAsync(info + 6, 0, sizeof(int), st));                        // the sticky time-out word (the one-workgroup kernels clear it themselves)
+      ISAC_HIP(hipMemsetAsync(&info->sticky, 0, sizeof(int), st));                        // the sticky time-out word (the one-workgroup kernels clear it themselves)
       hipLaunchKernelGGL(eigh_tridiag_dist_kernel, dim3((unsigned)(((n + 15) / 16) * td_stride)), dim3(256), 0, st, d_H, n, gs, info,
                          (unsigned)((ctx->eig_epoch & 0xFFFFF) << 12), td_stride, (int)(td_launches.fetch_add(1) % (unsigned)td_stride), td_far, force_to ? 1 : 0);
     } else {
-      const size_t ldsf = sizeof(c64) * 7 * (size_t)n + sizeof(double) * 32 + 64;
+      const size_t ldsf = TridiagFusedLds::of(n).bytes;
       ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(eigh_tridiag_fused_kernel), ldsf));
       hipLaunchKernelGGL(eigh_tridiag_fused_kernel, dim3(1), dim3(1024), ldsf, st, d_H, n, gs, info);
     }
@@ -1120,21 +1097,15 @@ static int launch_tridiag(isac_ctx* ctx, const c64* d_H, int n, hipStream_t st, 
   return ISAC_OK;
 }
 
-struct ReplayGeometry { int bt; size_t rows3, stage3; bool lds; };   // threads per replay workgroup, LDS bytes of its rows and of the staged rotations, "the rows fit LDS"
-static ReplayGeometry replay_geometry(int n) {
-  const int bt = (size_t)64 * n * sizeof(double) > 150 * 1024 ? 32 : 64;
-  const size_t rows3 = (size_t)bt * n * sizeof(double);
-  return {bt, rows3, sizeof(c64) * 2 * (size_t)n, rows3 <= 150 * 1024 && n <= 8 * bt};
-}
 // the recorded rotations applied to Z by a launch of its own (rows in LDS while they fit)
-static int launch_replay_offline(isac_ctx* ctx, int n, hipStream_t st, int* info, const int* ctl) {
+static int launch_replay_offline(isac_ctx* ctx, int n, hipStream_t st, EighInfo* info, const int* ctl) {
   void* gs = ctx->eig_scratch.p;
-  const auto [bt, rows3, stage3, lds_replay] = replay_geometry(n);
-  if (lds_replay) {
-    ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(eigh_replay_kernel<true>), rows3 + stage3));
-    hipLaunchKernelGGL(eigh_replay_kernel<true>, dim3((unsigned)((2 * n + bt - 1) / bt)), dim3(bt), rows3 + stage3, st, n, gs, (c64*)ctx->eig_v.p, info, ctl);
+  const ReplayLds rl = ReplayLds::of(n);
+  if (rl.rows_in_lds) {
+    ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(eigh_replay_kernel<true>), rl.bytes));
+    hipLaunchKernelGGL(eigh_replay_kernel<true>, dim3((unsigned)((2 * n + rl.bt - 1) / rl.bt)), dim3(rl.bt), rl.bytes, st, n, gs, (c64*)ctx->eig_v.p, info, ctl);
   } else {
-    hipLaunchKernelGGL(eigh_replay_kernel<false>, dim3((unsigned)((2 * n + 255) / 256)), dim3(256), stage3, st, n, gs, (c64*)ctx->eig_v.p, info, ctl);
+    hipLaunchKernelGGL(eigh_replay_kernel<false>, dim3((unsigned)((2 * n + 255) / 256)), dim3(256), ReplayLds::of(n, 256, false).bytes, st, n, gs, (c64*)ctx->eig_v.p, info, ctl);
   }
   ISAC_HIP(hipGetLastError());
   return ISAC_OK;
@@ -1144,34 +1115,33 @@ static int launch_replay_offline(isac_ctx* ctx, int n, hipStream_t st, int* info
 // kernels return at once when ctl[0] == 1 (music_subspace_kernel has already delivered what MUSIC needs).
 int isac_eigh_ql_dev(isac_ctx* ctx, int n, hipStream_t st, const int* ctl, bool allow_live) {
   void* gs = ctx->eig_scratch.p;
-  int* info = eig_info(ctx, n);
+  EighInfo* info = eig_info(ctx, n);
   // (forcing the zungtr block and the lone recurrence wavefront onto different CUs with an oversized LDS request made no
   // difference to the recurrence -- 345 vs 350 cycles per rotation at the time -- and cost CU capacity in pipelined runs)
-  const size_t lds2 = sizeof(c64) * 3 * (size_t)n + sizeof(double) * 4 * (size_t)n + 64;
-  const auto [bt, rows3, stage3, lds_replay] = replay_geometry(n);
-  const size_t lds3 = rows3 + stage3;
+  const FormqQlLds ql = FormqQlLds::of(n);
+  const ReplayLds rl = ReplayLds::of(n);
   // Replay blocks ride along with zungtr and the recurrence (they spin on flags of the same launch: co-resident workgroups are a speed
   // assumption, a bounded spin turns a violation into an error) -- except when this is the in-stream fallback of the subspace route
   // (ctl != null): there the replay is its own launch behind the recurrence, so the rare large-numDets CPI cannot fail on a spin time-out
-  const bool live = lds_replay && ctl == nullptr && allow_live;
-  const int n_replay = (2 * n + bt - 1) / bt;
+  const bool live = rl.rows_in_lds && ctl == nullptr && allow_live;
+  const int n_replay = (2 * n + rl.bt - 1) / rl.bt;
   ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(eigh_formq_ql_kernel), (size_t)(160 * 1024)));
   // (as the in-stream fallback it almost always returns at its first instruction: 256 threads then -- a 1024-thread workgroup of ~110 VGPRs needs a
   // whole CU to itself and sat 90-140 us in its queue while the next CPI's echo kernel held every CU with two workgroups, profiles/r03_device_timeline.txt)
-  hipLaunchKernelGGL(eigh_formq_ql_kernel, dim3(live ? 2 + n_replay : 2), dim3(ctl ? 256 : 1024), live ? std::max(lds2, lds3) : lds2, st, n, gs,
-                     (double*)ctx->eig_w.p, info, (c64*)ctx->eig_v.p, bt, ctl);
+  hipLaunchKernelGGL(eigh_formq_ql_kernel, dim3(live ? 2 + n_replay : 2), dim3(ctl ? 256 : 1024), live ? ql.bytes_live : ql.bytes, st, n, gs,
+                     (double*)ctx->eig_w.p, info, (c64*)ctx->eig_v.p, rl.bt, ctl);
   ISAC_HIP(hipGetLastError());
   if (!live) ISAC_TRY(launch_replay_offline(ctx, n, st, info, ctl));
   return ISAC_OK;
 }
 
-// Recovery of a CPI whose LIVE replay blocks gave up waiting (info[0] == -2; co-resident workgroups of one launch are a speed assumption
+// Recovery of a CPI whose LIVE replay blocks gave up waiting (kEighReplayTimeout; co-resident workgroups of one launch are a speed assumption
 // HIP does not guarantee): the zungtr result Z and every recorded rotation are intact once the launch has finished -- the recurrence and
 // zungtr blocks never wait for the replay blocks -- so the eigenvectors are formed by the offline replay, as on the fallback route.
 int isac_eigh_replay_recover(isac_ctx* ctx, int n, hipStream_t st) {
   if (!st) st = ctx->stream;
-  int* info = eig_info(ctx, n);
-  ISAC_HIP(hipMemsetAsync(info, 0, sizeof(int), st));                 // the time-out mark; the replay below cannot time out
+  EighInfo* info = eig_info(ctx, n);
+  ISAC_HIP(hipMemsetAsync(&info->status, 0, sizeof(int), st));                 // the time-out mark; the replay below cannot time out
   return launch_replay_offline(ctx, n, st, info, nullptr);
 }
 
@@ -1179,12 +1149,10 @@ int isac_eigh_replay_recover(isac_ctx* ctx, int n, hipStream_t st) {
 int isac_music_tridiag_bisect_dev(isac_ctx* ctx, const c64* d_H, int A, hipStream_t st) {
   if (!st) st = ctx->stream;
   const int n = A;
-  ISAC_TRY(ensure(ctx, ctx->eig_w, sizeof(double) * (size_t)A + 64));
-  ISAC_TRY(ensure(ctx, ctx->eig_v, sizeof(c64) * (size_t)A * A));
+  ISAC_TRY(ensure_eig_out(ctx, A));
   ISAC_TRY(ensure(ctx, ctx->misc, 512));
   ISAC_TRY(launch_tridiag(ctx, d_H, n, st, eig_info(ctx, A)));
-  const size_t lds = sizeof(c64) * (size_t)n + sizeof(double) * 48 + 64;
-  hipLaunchKernelGGL(eigh_bisect_kernel, dim3((unsigned)((n + kBisectWaves - 1) / kBisectWaves)), dim3(64 * kBisectWaves), lds, st, n, ctx->eig_scratch.p,
+  hipLaunchKernelGGL(eigh_bisect_kernel, dim3((unsigned)((n + kBisectWaves - 1) / kBisectWaves)), dim3(64 * kBisectWaves), BisectLds::of(n).bytes, st, n, ctx->eig_scratch.p,
                      (double*)ctx->eig_w.p);
   ISAC_HIP(hipGetLastError());
   return ISAC_OK;
@@ -1198,15 +1166,13 @@ int isac_eigh_dev(isac_ctx* ctx, const c64* d_H, int A, hipStream_t st, bool liv
   if (A > 1024) return fail(ctx, ISAC_ERR_UNSUPPORTED, "device eigensolver supports up to 1024 antennas");
   // measured host-call times (tools/_eig_sizes.py): Jacobi 0.10 / 0.16 / 0.26 / 0.35 / 0.78 / 1.41 ms at A = 8 / 16 / 24 / 32 / 48 /
   // 64, the tridiagonal pipeline 0.10 / 0.17 / 0.24 / 0.33 / 0.57 / 0.86 ms: Jacobi up to 16 antennas, the pipeline beyond
-  ISAC_TRY(ensure(ctx, ctx->eig_w, sizeof(double) * (size_t)A + 64));
-  ISAC_TRY(ensure(ctx, ctx->eig_v, sizeof(c64) * (size_t)A * A));
-  int* info = eig_info(ctx, A);
+  ISAC_TRY(ensure_eig_out(ctx, A));
+  EighInfo* info = eig_info(ctx, A);
   if (A > kJacobiMaxA) {
     ISAC_TRY(launch_tridiag(ctx, d_H, A, st, info));
     return isac_eigh_ql_dev(ctx, A, st, nullptr, live_replay);
   }
-  const int n = (A + 1) & ~1;
-  size_t lds = sizeof(c64) * ((size_t)2 * n * n + n / 2) + sizeof(double) * (n / 2) + sizeof(int) * (n + 1) + 64;
+  const size_t lds = JacobiLds::of(A).bytes;
   ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(jacobi_eigh_kernel), lds));
   hipLaunchKernelGGL(jacobi_eigh_kernel, dim3(1), dim3(1024), lds, st, d_H, A, 40, (double*)ctx->eig_w.p, (c64*)ctx->eig_v.p, info);
   ISAC_HIP(hipGetLastError());

@@ -1,39 +1,62 @@
-// Device-side pieces that the eigensolver (eigh.hip) and MUSIC (music.hip) share: the carve of ctx->eig_scratch and the wavefront reductions.
+// Device-side pieces that the eigensolver (eigh.hip) and MUSIC (music.hip) share: the pointers into ctx->eig_scratch, the status helpers, zlarfg and the
+// wavefront reductions.  The geometry behind them: eigh_layout.hpp.
 #pragma once
 #include "isac_common.hpp"
+#include "eigh_layout.hpp"
 
 namespace isac {
 
-struct EighScratch {   // carve of ctx->eig_scratch for order n
+struct EighScratch {   // pointers into ctx->eig_scratch for order n (the carve: EighScratchLayout)
   c64 *M, *Z, *tau, *rot;
   double *d, *e, *scale;
   double* wsc;         // [n] eigenvalues of the (safe-scaled) tridiagonal, ascending -- eigh_bisect_kernel
-  char* xch;           // exchange area of eigh_tridiag_dist_kernel (kTdXchBytes, 128-byte aligned)
+  char* xch;           // exchange area of eigh_tridiag_dist_kernel
   int *desc, *cnt;     // desc: (mm, l, first rotation, -) per sweep; cnt: {sweeps published, n_rot, overflow, zungtr done, QL done}
   long long rot_cap;
   int desc_cap;
-  __host__ __device__ static size_t bytes(int n) {
-    return sizeof(c64) * ((size_t)2 * n * n + n + (size_t)16 * n * n) + sizeof(double) * (3 * n + 4) + sizeof(int) * (4 * (size_t)(30 * n + 2) + 8) + 256 +
-           kXchBytes;
-  }
-  static constexpr size_t kXchBytes = 2048 + 2 * 256 * 64;               // per-wavefront (maximum, XCC id) | 2 parities x 256 rows x (p_i, next column's entry) as tagged granules: at the
-                                                                           // START of the scratch, wherever n puts the rest (the host zeroes a fresh allocation)
+  static constexpr size_t kXchBytes = EighScratchLayout::kXchBytes;
+  __host__ __device__ static size_t bytes(int n) { return EighScratchLayout::of(n).bytes; }
   __host__ __device__ EighScratch(void* base, int n) {
-    xch = reinterpret_cast<char*>(base);
-    c64* p = reinterpret_cast<c64*>(xch + kXchBytes);
-    M = p; p += (size_t)n * n;
-    Z = p; p += (size_t)n * n;
-    tau = p; p += n;
-    rot = p; rot_cap = (long long)16 * n * n; p += rot_cap;
-    d = reinterpret_cast<double*>(p);
-    e = d + n;
-    scale = e + n + (n & 1);
-    desc_cap = 30 * n + 2;
-    desc = reinterpret_cast<int*>(scale + 2);       // 16-byte aligned (rot is, and n + (n & 1) + 2 doubles follow)
-    cnt = desc + 4 * (size_t)desc_cap;
-    wsc = reinterpret_cast<double*>(cnt + 8);       // 16-byte aligned (desc is, 16 desc_cap + 32 bytes follow)
+    const EighScratchLayout l = EighScratchLayout::of(n);
+    char* b = reinterpret_cast<char*>(base);
+    xch = b + l.xch;
+    M = reinterpret_cast<c64*>(b + l.M); Z = reinterpret_cast<c64*>(b + l.Z); tau = reinterpret_cast<c64*>(b + l.tau); rot = reinterpret_cast<c64*>(b + l.rot);
+    d = reinterpret_cast<double*>(b + l.d); e = reinterpret_cast<double*>(b + l.e); scale = reinterpret_cast<double*>(b + l.scale);
+    desc = reinterpret_cast<int*>(b + l.desc); cnt = reinterpret_cast<int*>(b + l.cnt); wsc = reinterpret_cast<double*>(b + l.wsc);
+    rot_cap = l.rot_cap; desc_cap = l.desc_cap;
   }
 };
+
+// The final status of a kernel behind the tridiagonalisation: a timed-out distributed tridiagonalisation stays reported.
+__device__ __forceinline__ void eigh_set_status(EighInfo* __restrict__ info, int status) {
+  info->status = info->sticky == kEighTridiagTimeout ? kEighTridiagTimeout : status;
+}
+// eigh_tridiag_dist_kernel gave up (sticky: the kernels behind it overwrite `status`)
+__device__ __forceinline__ void eigh_mark_tridiag_timeout(EighInfo* __restrict__ info) { info->status = info->sticky = kEighTridiagTimeout; }
+
+// zlarfg: the reflector of (alpha, x) with |x|^2 = xnorm2 -- beta, tau and scale = 1 / (alpha - beta).  RCP = false: divisions (the one-workgroup kernels);
+// RCP = true: two reciprocals instead of four divisions (the distributed kernel).  The two forms round differently and both are pinned: do not unify.
+struct Zlarfg { double beta; c64 tau, scale; };
+template <bool RCP>
+__device__ __forceinline__ Zlarfg zlarfg(const c64 alpha, const double xnorm2) {
+  Zlarfg r{alpha.re, mk(0.0, 0.0), mk(0.0, 0.0)};
+  if (xnorm2 != 0.0 || alpha.im != 0.0) {
+    r.beta = -copysign(sqrt(alpha.re * alpha.re + alpha.im * alpha.im + xnorm2), alpha.re);
+    if constexpr (RCP) {
+      const double ib = 1.0 / r.beta;
+      r.tau = mk((r.beta - alpha.re) * ib, -alpha.im * ib);
+      const c64 dlt = mk(alpha.re - r.beta, alpha.im);
+      const double idn = 1.0 / (dlt.re * dlt.re + dlt.im * dlt.im);
+      r.scale = mk(dlt.re * idn, -dlt.im * idn);
+    } else {
+      r.tau = mk((r.beta - alpha.re) / r.beta, -alpha.im / r.beta);
+      const c64 dlt = mk(alpha.re - r.beta, alpha.im);
+      const double dn = dlt.re * dlt.re + dlt.im * dlt.im;
+      r.scale = mk(dlt.re / dn, -dlt.im / dn);
+    }
+  }
+  return r;
+}
 
 __device__ __forceinline__ double rcp_fast(double q) {   // 1/q: hardware estimate r0 + one third-order step  r0 (1 + h + h^2), h = 1 - q r0
   const double r0 = __builtin_amdgcn_rcp(q);

@@ -15,7 +15,7 @@ __global__ void pack_kernel(const int* __restrict__ det_cnt, const int* __restri
                             const int* __restrict__ num_dets, int A, int cap, int* __restrict__ hdr /* [3 + A+1] */,
                             int* __restrict__ full_cut, double* __restrict__ full_pow, int pack_first,
                             int* __restrict__ first_cut, double* __restrict__ first_pow, const double* __restrict__ spec,
-                            int n_steps, double* __restrict__ spec_out, const int* __restrict__ eig_info) {
+                            int n_steps, double* __restrict__ spec_out, const EighInfo* __restrict__ eig_info) {
   __shared__ int s_off[1025];
   __shared__ int s_cnt[1024];
   const int tid = threadIdx.x;
@@ -32,7 +32,7 @@ __global__ void pack_kernel(const int* __restrict__ det_cnt, const int* __restri
     s_off[A] = acc;
     hdr[0] = acc;
     hdr[1] = *num_dets;
-    hdr[2] = over | ((eig_info && eig_info[0] < 0) ? 2 : 0);
+    hdr[2] = over | ((eig_info && eig_info->status < 0) ? 2 : 0);
   }
   __syncthreads();
   for (int a = tid; a <= A; a += blockDim.x) hdr[3 + a] = s_off[a];

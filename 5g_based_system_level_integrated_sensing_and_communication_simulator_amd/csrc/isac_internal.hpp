@@ -2,6 +2,7 @@
 // included), and every .hip file includes this header -- the defining unit too, so the compiler sees both.  extern "C" entry points: include/isac.h, not here.
 #pragma once
 #include "isac_common.hpp"
+#include "eigh_layout.hpp"
 
 // ---------------------------------------------------------------- tables.hip: cached device tables
 // The one way a cached table comes to exist: `key` is looked up in ctx->tables; on a miss `build` fills a std::vector<T> on the host, which is uploaded and kept under
@@ -79,9 +80,12 @@ int cdl_os_apply(isac_ctx* ctx, const isac_cdl_job* jobs, int n_jobs, long long 
 constexpr uint32_t kRxFrontEndStream = 3u;   // Philox stream word of its time-domain AWGN (0: the echo's time-domain noise, 1: isac_synth_qpsk_grid_dev, 2: kSpectralStream)
 int isac_rx_frontend_jobs(isac_ctx* ctx, const isac_rx_frontend_job* jobs, int n_jobs, long long T, int Nr, int noise_mode);
 
-// Status words the device eigensolver leaves behind the eigenvalues (ctx->eig_w [A] | info[0..6]).  info[0] negative: the QL recurrence ran out of rotation storage (-1), a live replay
-// block gave up waiting (-2; isac_eigh_replay_recover, once the stream is idle), the signal-subspace vectors are not finite (-3), the distributed tridiagonalisation saw no progress (-4; sticky in info[6]).
-inline int* eig_info(isac_ctx* ctx, int A) { return reinterpret_cast<int*>((char*)ctx->eig_w.p + sizeof(double) * (size_t)A); }
+// The status record the device eigensolver leaves behind the eigenvalues (ctx->eig_w [A] | isac::EighInfo, eigh_layout.hpp), and the one place the two outputs are sized
+inline isac::EighInfo* eig_info(isac_ctx* ctx, int A) { return reinterpret_cast<isac::EighInfo*>((char*)ctx->eig_w.p + sizeof(double) * (size_t)A); }
+inline int ensure_eig_out(isac_ctx* ctx, int A) {   // ctx->eig_w [A] + the record, ctx->eig_v [A x A]
+  ISAC_TRY(isac::ensure(ctx, ctx->eig_w, sizeof(double) * (size_t)A + sizeof(isac::EighInfo)));
+  return isac::ensure(ctx, ctx->eig_v, sizeof(isac::c64) * (size_t)A * A);
+}
 namespace isac {
 hipEvent_t timeline_base(hipStream_t st);   // fft2d.hip
 inline void timeline_mark(isac_ctx* ctx, int i, hipStream_t st) {

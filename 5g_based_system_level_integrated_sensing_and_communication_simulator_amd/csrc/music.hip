@@ -17,12 +17,12 @@ namespace isac {
 // L >= A (empty noise space) and L <= 0 need no vectors; L beyond the LDS capacity of K3 falls back to the QL pipeline, whose kernels are
 // always enqueued behind K3 and return at once when K3 reports success in `ctl` (numDets lives on the device: no host decision).
 
-// K3.  LDS: four [n][lv] arrays (1 / pivot, the two superdiagonals of U, the vectors), lane v owns column v: consecutive lanes touch
-// consecutive doubles.  R = rows per lane in the wave-per-vector phases (n <= 64 R).
+// K3.  LDS: SubspaceLds (lane v owns column v of its planes: consecutive lanes touch consecutive doubles).  R = rows per lane in the
+// wave-per-vector phases (n <= 64 R).
 template <int R>
 __global__ __launch_bounds__(1024) void music_subspace_kernel(int n, void* scratch, const int* __restrict__ num_dets_dev, int num_dets_host,
                                                               int lmax, int lv, c64* __restrict__ U_out /* [n x L] */, int* __restrict__ ctl,
-                                                              int* __restrict__ info) {
+                                                              EighInfo* __restrict__ info) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   __shared__ int s_bad;
   __shared__ double s_red[16];
@@ -34,20 +34,20 @@ __global__ __launch_bounds__(1024) void music_subspace_kernel(int n, void* scrat
       const bool done = L <= 0 || L >= n;
       ctl[MusicCtl::kRoute] = done ? 1 : 0;
       ctl[MusicCtl::kLsub] = L <= 0 ? 0 : L;
-      if (done && info) { info[0] = info[6] == -4 ? -4 : 0; info[5] = -3; }
+      if (done && info) { eigh_set_status(info, 0); info->rotations = kEighRouteSubspace; }
     }
     return;
   }
   const long long t_k0 = clock64();
   long long t_solve = 0, t_mgs = 0;                                  // phase instrumentation (ISAC_DEBUG): cycles of thread 0
-  const size_t plane = (size_t)n * lv;
-  double* u0 = reinterpret_cast<double*>(smem_raw);                  // 1 / pivot
-  double* u1 = u0 + plane;
-  double* u2 = u1 + plane;
-  double* y = u2 + plane;                                            // right-hand sides / solutions = the vectors, [row][vector]
-  double* sd = y + plane;                                            // [n] d
-  double* se = sd + n;                                               // [n] e (e[n-1] = 0)
-  c64* s_tau = reinterpret_cast<c64*>(se + n);                       // [n] reflector scalars
+  const SubspaceLds lds = SubspaceLds::of(n, lv);
+  double* u0 = reinterpret_cast<double*>(smem_raw + lds.u0);         // 1 / pivot
+  double* u1 = reinterpret_cast<double*>(smem_raw + lds.u1);
+  double* u2 = reinterpret_cast<double*>(smem_raw + lds.u2);
+  double* y = reinterpret_cast<double*>(smem_raw + lds.y);           // right-hand sides / solutions = the vectors, [row][vector]
+  double* sd = reinterpret_cast<double*>(smem_raw + lds.sd);         // d
+  double* se = reinterpret_cast<double*>(smem_raw + lds.se);         // e (e[n-1] = 0)
+  c64* s_tau = reinterpret_cast<c64*>(smem_raw + lds.tau);           // reflector scalars
   double tn = 0.0;
   for (int i = tid; i < n; i += 1024) {
     const double d = S.d[i], e = i < n - 1 ? S.e[i] : 0.0;
@@ -243,8 +243,8 @@ __global__ __launch_bounds__(1024) void music_subspace_kernel(int n, void* scrat
     ctl[MusicCtl::kRoute] = 1;
     ctl[MusicCtl::kLsub] = L;
     if (info) {
-      info[0] = info[6] == -4 ? -4 : s_bad ? -3 : 0; info[5] = -3;
-      info[8] = (int)((t_k1 - t_k0) >> 6); info[9] = (int)(t_solve >> 6); info[10] = (int)(t_mgs >> 6); info[11] = (int)((clock64() - t_k2) >> 6);
+      eigh_set_status(info, s_bad ? kEighNotFinite : 0); info->rotations = kEighRouteSubspace;
+      info->sub_setup = (int)((t_k1 - t_k0) >> 6); info->sub_solve = (int)(t_solve >> 6); info->sub_mgs = (int)(t_mgs >> 6); info->sub_back = (int)((clock64() - t_k2) >> 6);
     }
   }
 }
@@ -395,18 +395,14 @@ bool isac_music_subspace_ok(isac_ctx* ctx, int A) {
 int isac_music_subspace_dev(isac_ctx* ctx, int A, const int* d_num_dets, int num_dets_host, hipStream_t st) {
   if (!st) st = ctx->stream;
   const int n = A;
-  int* info = eig_info(ctx, A);
+  EighInfo* info = eig_info(ctx, A);
   int* ctl = music_ctl(ctx);
-  int lmax = (int)(122880 / (32 * (size_t)n));
-  lmax = lmax > 32 ? 32 : (lmax < 1 ? 1 : lmax);
-  const int lv = lmax | 1;                           // odd pitch
-  if (n > 128 && lmax > 16) lmax = 16;               // one vector per wavefront in the back-transformation of the R = 4 instantiation
-  const size_t lds = sizeof(double) * ((size_t)4 * n * lv + 4 * (size_t)n) + 64;
+  const SubspaceLds lds = SubspaceLds::of(n);
 #define ISAC_SUBSPACE(RR)                                                                                                         \
   do {                                                                                                                            \
     ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(music_subspace_kernel<RR>), (size_t)(150 * 1024)));                     \
-    hipLaunchKernelGGL(music_subspace_kernel<RR>, dim3(1), dim3(1024), lds, st, n, ctx->eig_scratch.p, d_num_dets, num_dets_host, \
-                       lmax, lv, (c64*)ctx->eig_v.p, ctl, info);                                                                  \
+    hipLaunchKernelGGL(music_subspace_kernel<RR>, dim3(1), dim3(1024), lds.bytes, st, n, ctx->eig_scratch.p, d_num_dets,          \
+                       num_dets_host, lds.lmax, lds.lv, (c64*)ctx->eig_v.p, ctl, info);                                           \
   } while (0)
   if (n <= 64) ISAC_SUBSPACE(1); else if (n <= 128) ISAC_SUBSPACE(2); else ISAC_SUBSPACE(4);
 #undef ISAC_SUBSPACE
