@@ -21,6 +21,9 @@ NOISE_NONE, NOISE_INJECTED, NOISE_PHILOX, NOISE_PHILOX_SPECTRAL, NOISE_INJECTED_
 CFAR_CA, CFAR_GOCA, CFAR_SOCA, CFAR_OS = 0, 1, 2, 3      # ISAC_CFAR_* (include/isac_cfar.h)
 CFAR_METHODS = {"CA": CFAR_CA, "GOCA": CFAR_GOCA, "SOCA": CFAR_SOCA, "OS": CFAR_OS}
 ISAC_CFAR_MAX_TRAIN = 1024
+TARGET_SW0, TARGET_SW1 = 0, 1                            # ISAC_TARGET_* (include/isac_cfar_mc.h)
+TARGET_MODELS = {"swerling0": TARGET_SW0, "swerling1": TARGET_SW1}
+ISAC_CFAR_MC_MAX_TRAIN = 128
 OPT_MUSIC_ROUTE, OPT_TAIL_FUSION, OPT_WIDE_ORDER, OPT_CDL_SHARE_SPECTRA, OPT_UPA_DOA = 0, 1, 2, 3, 4   # ISAC_OPT_* of isac_ctx_set_option
 
 STATUS_NAMES = {0: "OK", 1: "INVALID_ARG", 2: "HIP", 3: "NO_LOS", 4: "NO_DETECTION", 5: "CFAR_WINDOW",
@@ -229,6 +232,10 @@ PROTOTYPES_CFAR = {
     "isac_cfar2d": (_INT, (_P, _P, _I32, _I32, _P, _I32, _P, _P, _F64, _ptr(CfarMethod), _P, _I32, _P)),
     "isac_fft2d_redetect": (_INT, (_P, _ptr(CfarMethod), _ptr(EstResult), _P, _P, _I32, _P, _P)),
 }
+# ... and include/isac_cfar_mc.h (tests/test_cfar_mc_cpu.py pins it)
+PROTOTYPES_CFAR_MC = {
+    "isac_cfar_monte_carlo": (_INT, (_P, _ptr(CfarMethod), _I32, _F64, _I32, _P, _I32, _U64, _U64, _P, _P)),
+}
 
 
 def library_path() -> str:
@@ -255,7 +262,7 @@ def load():
             except Exception:
                 pass
         lib = C.CDLL(_LIB_PATH, mode=C.RTLD_GLOBAL)
-        for name, (restype, argtypes) in {**PROTOTYPES, **PROTOTYPES_ADDED, **PROTOTYPES_CFAR}.items():
+        for name, (restype, argtypes) in {**PROTOTYPES, **PROTOTYPES_ADDED, **PROTOTYPES_CFAR, **PROTOTYPES_CFAR_MC}.items():
             fn = getattr(lib, name)  # AttributeError here = ABI drift between isac.h and the .so
             fn.restype, fn.argtypes = restype, argtypes
         # the library writes whole structs into caller memory: version AND struct sizes must match this binding's mirrors

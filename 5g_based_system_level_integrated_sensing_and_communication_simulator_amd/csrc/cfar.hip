@@ -3,6 +3,7 @@
 //   isac_cfar_threshold_factor   host only: the 'Auto' factor of a method
 //   isac_cfar2d                  an arbitrary map and CUT list (isac_cfar2d_ca with the method block)
 //   isac_fft2d_redetect          the power window of the last completed fft2D, detected again; then the host half of fft2D.m:63-99 on the new lists
+//   isac_cfar_monte_carlo        (include/isac_cfar_mc.h) drawn noise and a target through the same per-CUT function, counted: the detectors' Pfa / Pd as built
 // One per-CUT device function, cfar_cut<M>, serves both: K1 cfar_method_window_kernel stages a kPanelRows x pc tile of CUTs plus its halo of guard + training cells in LDS
 // and evaluates one CUT per lane into a flag per (CUT, antenna); K2 cfar_compact_kernel, one workgroup per antenna, turns the flags into the CUT-order list (rows
 // fastest, cfar2D.m:23-24) with ballots and a running base; cfar_method_list_kernel evaluates one listed CUT per lane on a map in global memory.  The CA detector of the
@@ -11,6 +12,7 @@
 #include <cmath>
 
 #include "isac_internal.hpp"
+#include "echo_dev.hpp"
 
 namespace isac {
 
@@ -176,6 +178,72 @@ __global__ __launch_bounds__(256) void cfar_method_list_kernel(const double* __r
   if (i >= n_cut) return;
   const int r = cut[2 * i] - 1, c = cut[2 * i + 1] - 1;         // (the host has checked that the training window stays inside the map)
   flags[i] = cfar_cut<M>(P + (long long)r + (long long)n_rows * c, n_rows, g) ? 1 : 0;
+}
+
+// ---------------------------------------------------------------- Monte Carlo (include/isac_cfar_mc.h): one lane per trial, the lane's 1 x (N + 1) window in LDS
+constexpr int kMcMaxSnr = 64;                                   // SNR points per call = lanes of a wave: lane i of every wave keeps the count of point i
+constexpr unsigned long long kMcLaunchTrials = 1ull << 28;      // trials per launch: the host loops, so that no kernel holds the device for long
+
+struct McGeom {
+  CutGeom c;                     // hr = 0, hc = N/2, no guard: the CUT in the middle column
+  int n_snr, model;
+  unsigned long long t0, n;      // this launch: trials t0 .. t0 + n - 1
+  unsigned long long n_trials;   // leading dimension of flags
+  unsigned long long seed;
+};
+struct McSnr { double s[kMcMaxSnr], root[kMcMaxSnr]; };         // S_i and sqrt(S_i)
+
+__device__ __forceinline__ double neg_ln_u53(uint64_t w) { return -ln_unit(((double)(w >> 11) + 1.0) * 0x1.0p-53); }   // -ln u(w), u in (0, 1]: a unit-mean exponential
+
+// Cell c of lane l at s_c[c * NT + l]: the lanes of a wave read consecutive doubles in every step of cfar_cut (ld = NT), so no bank conflict.  A lane touches its own column
+// only, so no barrier inside the trial loop; the loop bounds are uniform over the workgroup and a lane past the end repeats the launch's last trial without counting it.
+template <int M, int NT>
+__global__ __launch_bounds__(NT) void cfar_mc_kernel(McGeom g, McSnr snr, unsigned long long* __restrict__ n_det /* [n_snr], zeroed before the first launch */,
+                                                     unsigned char* __restrict__ flags /* [n_trials x n_snr] or nullptr */) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  __shared__ unsigned long long s_tot[kMcMaxSnr];
+  double* s_c = reinterpret_cast<double*>(smem_raw);            // [N + 1][NT]
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int half = g.c.n_train / 2;
+  if (tid < kMcMaxSnr) s_tot[tid] = 0ull;
+  __syncthreads();
+  double* cutp = s_c + half * NT + tid;
+  const uint32_t k0 = (uint32_t)g.seed, k1 = (uint32_t)(g.seed >> 32);
+  unsigned long long cnt = 0ull;                                // detections of SNR point `lane` seen by this wave
+  for (unsigned long long base = (unsigned long long)blockIdx.x * NT; base < g.n; base += (unsigned long long)gridDim.x * NT) {
+    const bool active = base + tid < g.n;
+    const unsigned long long t = g.t0 + (active ? base + tid : g.n - 1);
+    uint32_t o[4];
+    for (int j = 0; j < half; ++j) {                            // T_{2j+1}, T_{2j+2}: columns 0 .. half - 1 before the CUT, half + 1 .. N after it
+      philox4x32_10((uint32_t)t, (uint32_t)(t >> 32), kCfarMcStream, (uint32_t)j, k0, k1, o);
+      const int c0 = 2 * j, c1 = 2 * j + 1;
+      s_c[(c0 + (c0 >= half ? 1 : 0)) * NT + tid] = neg_ln_u53((uint64_t)o[0] | ((uint64_t)o[1] << 32));
+      s_c[(c1 + (c1 >= half ? 1 : 0)) * NT + tid] = neg_ln_u53((uint64_t)o[2] | ((uint64_t)o[3] << 32));
+    }
+    philox4x32_10((uint32_t)t, (uint32_t)(t >> 32), kCfarMcStream, (uint32_t)half, k0, k1, o);
+    const double e0 = neg_ln_u53((uint64_t)o[0] | ((uint64_t)o[1] << 32));
+    double re = 0.0, im = 0.0;                                  // the noise sample sqrt(E0) exp(j theta) of the CUT (SW0)
+    if (g.model == ISAC_TARGET_SW0) {
+      const double u2 = (double)(((uint64_t)o[2] | ((uint64_t)o[3] << 32)) >> 11) * 0x1.0p-53;
+      double sn, cs;
+      sincospi(2.0 * u2, &sn, &cs);
+      const double r = sqrt(e0);
+      re = r * cs; im = r * sn;
+    }
+    for (int i = 0; i < g.n_snr; ++i) {
+      double p;
+      if (g.model == ISAC_TARGET_SW1) p = (1.0 + snr.s[i]) * e0;
+      else { const double a = snr.root[i] + re; p = a * a + im * im; }
+      *cutp = p;
+      const bool det = cfar_cut<M>(cutp, NT, g.c) && active;
+      const unsigned long long mask = __ballot(det);
+      if (lane == i) cnt += (unsigned long long)__popcll(mask);
+      if (flags && active) flags[t + g.n_trials * (unsigned long long)i] = det ? 1 : 0;
+    }
+  }
+  if (lane < g.n_snr) atomicAdd(&s_tot[lane], cnt);             // the waves of the workgroup, in LDS
+  __syncthreads();
+  if (tid < g.n_snr) atomicAdd(&n_det[tid], s_tot[tid]);        // one 64-bit add per workgroup and SNR point
 }
 
 }  // namespace isac
@@ -374,5 +442,50 @@ extern "C" int isac_fft2d_redetect(isac_ctx* ctx, const isac_cfar_method* m, isa
   ISAC_TRY(fft2d_estimates(ctx, &ts.ep, ts.win, A, ant_off.data(), cut, pw, num_dets_dev, det_rc, out));   // fft2D.m:63-99; n_azi stays 0
   if (det_idx) std::copy(det_rc.begin(), det_rc.end(), det_idx);
   if (det_pow) std::copy(pw.begin(), pw.end(), det_pow);
+  return ISAC_OK;
+}
+
+extern "C" int isac_cfar_monte_carlo(isac_ctx* ctx, const isac_cfar_method* m, int32_t n_train, double pfa, int32_t target_model, const double* snr_db, int32_t n_snr,
+                                     uint64_t n_trials, uint64_t seed, uint64_t* n_det, uint8_t* flags) {
+  ISAC_ENTER(ctx);
+  if (!m || !snr_db || !n_det) return fail(ctx, ISAC_ERR_INVALID_ARG, "bad arguments");
+  if (n_train < 2 || (n_train & 1)) return fail(ctx, ISAC_ERR_INVALID_ARG, "isac_cfar_monte_carlo: n_train must be even and at least 2");
+  if (n_train > ISAC_CFAR_MC_MAX_TRAIN) return fail(ctx, ISAC_ERR_UNSUPPORTED, "isac_cfar_monte_carlo: more than ISAC_CFAR_MC_MAX_TRAIN training cells");
+  if (target_model != ISAC_TARGET_SW0 && target_model != ISAC_TARGET_SW1) return fail(ctx, ISAC_ERR_INVALID_ARG, "isac_cfar_monte_carlo: unknown target model");
+  if (n_snr < 1 || n_snr > kMcMaxSnr) return fail(ctx, ISAC_ERR_INVALID_ARG, "isac_cfar_monte_carlo: n_snr must lie in 1..64");
+  if (n_trials < 1 || n_trials > (1ull << 40)) return fail(ctx, ISAC_ERR_INVALID_ARG, "isac_cfar_monte_carlo: n_trials must lie in 1..2^40");
+  if (flags && n_trials > (1ull << 22)) return fail(ctx, ISAC_ERR_INVALID_ARG, "isac_cfar_monte_carlo: per-trial flags need n_trials <= 2^22");
+  McGeom g{};
+  McSnr snr{};
+  for (int i = 0; i < n_snr; ++i) {
+    if (snr_db[i] != snr_db[i] || snr_db[i] == HUGE_VAL) return fail(ctx, ISAC_ERR_INVALID_ARG, "isac_cfar_monte_carlo: snr_db must be finite or -inf");
+    snr.s[i] = std::pow(10.0, snr_db[i] / 10.0);                // -inf: 0, the false-alarm point
+    snr.root[i] = std::sqrt(snr.s[i]);
+  }
+  const int32_t guard[2] = {0, 0}, train[2] = {0, n_train / 2}; // the 1 x (N + 1) window: N/2 columns on either side of the CUT
+  ISAC_TRY(cut_geom(ctx, guard, train, pfa, m, &g.c));
+  g.n_snr = n_snr; g.model = target_model; g.n_trials = n_trials; g.seed = seed;
+  // 256 lanes while the tile of N + 1 cells per lane fits ~128 KB of LDS (N <= 62), 128 lanes beyond (N = 128: 129 KB of the CU's 160)
+  const int nt = sizeof(double) * (size_t)(n_train + 1) * 256 <= 128 * 1024 ? 256 : 128;
+  const size_t lds = sizeof(double) * (size_t)(n_train + 1) * (size_t)nt;
+  const int per_cu = (int)std::max<size_t>(1, std::min<size_t>((160 * 1024) / (lds + 1024), 2048 / nt));   // resident workgroups per CU: LDS, 32 waves
+  const size_t off_flags = sizeof(unsigned long long) * kMcMaxSnr, flag_bytes = flags ? (size_t)n_trials * (size_t)n_snr : 0;
+  ISAC_TRY(ensure(ctx, ctx->cfar_mc, off_flags + flag_bytes));
+  char* d = (char*)ctx->cfar_mc.p;
+  ISAC_HIP(hipMemsetAsync(d, 0, off_flags, ctx->stream));
+  for (unsigned long long t0 = 0; t0 < n_trials; t0 += kMcLaunchTrials) {
+    g.t0 = t0;
+    g.n = std::min<unsigned long long>(kMcLaunchTrials, n_trials - t0);
+    const unsigned grid = (unsigned)std::min<unsigned long long>((g.n + nt - 1) / nt, 256ull * per_cu * 2);   // two waves of workgroups over 256 CUs; grid-stride loop
+    CFAR_METHOD_DISPATCH(m->method, {
+      auto kern = nt == 256 ? cfar_mc_kernel<M, 256> : cfar_mc_kernel<M, 128>;
+      ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(kern), lds));
+      hipLaunchKernelGGL(kern, dim3(grid), dim3(nt), lds, ctx->stream, g, snr, (unsigned long long*)d, flags ? (unsigned char*)(d + off_flags) : (unsigned char*)nullptr);
+    });
+    ISAC_HIP(hipGetLastError());
+  }
+  static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "n_det is copied out as it is counted");
+  ISAC_TRY(copy_d2h(ctx, n_det, d, sizeof(uint64_t) * (size_t)n_snr));
+  if (flags) ISAC_TRY(copy_d2h(ctx, flags, d + off_flags, flag_bytes));
   return ISAC_OK;
 }

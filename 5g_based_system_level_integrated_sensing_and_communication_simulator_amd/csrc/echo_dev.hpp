@@ -22,11 +22,12 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
   out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
 
-// sqrt(-2 ln u) for u in (0,1], u a multiple of 2^-53: the Box-Muller radius.  Lean fp64 evaluation (the
-// generic libm log/sqrt cost ~0.2 ms per 58.7 M samples here): ln u = e ln2 + 2 atanh(t), t = (m-1)/(m+1),
-// m in [sqrt(1/2), sqrt(2)), odd series to t^19 (|t| <= 0.1716, truncation < 1e-17); reciprocal and square
-// root from the hardware estimates + Newton steps.  Max relative error ~3e-16 (not correctly rounded).
-__device__ __forceinline__ double sqrt_neg2log(double u) {
+// ln u for u in (0,1], u a multiple of 2^-53.  Lean fp64 evaluation (the generic libm log costs ~0.2 ms per
+// 58.7 M samples here): ln u = e ln2 + 2 atanh(t), t = (m-1)/(m+1), m in [sqrt(1/2), sqrt(2)), odd series to
+// t^19 (|t| <= 0.1716, truncation < 1e-17); reciprocal from the hardware estimate + Newton steps.  A few ulp
+// (not correctly rounded); <= 0, and exactly 0 at u = 1.  Callers: sqrt_neg2log below, the exponential cells
+// of the CFAR Monte Carlo (cfar.hip).
+__device__ __forceinline__ double ln_unit(double u) {
   int e;
   double m = frexp(u, &e);                                  // m in [0.5, 1)
   if (m < 0.70710678118654752440) { m *= 2.0; --e; }
@@ -39,8 +40,13 @@ __device__ __forceinline__ double sqrt_neg2log(double u) {
   p = ::fma(p, t2, 1.0 / 17.0); p = ::fma(p, t2, 1.0 / 15.0); p = ::fma(p, t2, 1.0 / 13.0); p = ::fma(p, t2, 1.0 / 11.0);
   p = ::fma(p, t2, 1.0 / 9.0);  p = ::fma(p, t2, 1.0 / 7.0);  p = ::fma(p, t2, 1.0 / 5.0);  p = ::fma(p, t2, 1.0 / 3.0);
   p = ::fma(p, t2, 1.0);
-  const double ln_u = ::fma((double)e, 0.69314718055994530942, 2.0 * t * p);
-  const double y = -2.0 * ln_u;                            // >= 0
+  return ::fma((double)e, 0.69314718055994530942, 2.0 * t * p);
+}
+
+// sqrt(-2 ln u), same u: the Box-Muller radius.  ln_unit, then the square root from the hardware estimate
+// + Newton steps.  Max relative error ~3e-16 (not correctly rounded).
+__device__ __forceinline__ double sqrt_neg2log(double u) {
+  const double y = -2.0 * ln_unit(u);                      // >= 0
   if (!(y > 0.0)) return 0.0;
   double rs = __builtin_amdgcn_rsq(y);
   double sq = y * rs;                                      // ~ sqrt(y)

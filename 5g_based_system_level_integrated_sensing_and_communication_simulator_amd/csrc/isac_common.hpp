@@ -229,6 +229,7 @@ struct isac_ctx {
   isac::Fft2dCpi tgt;                // the last submitted CPI (named for its first reader, isac_fft2d_get_targets): parameters, window, validity of ymid / pwin / det_*
   isac::DevBuf tgt_scratch;          // ... and its device scratch (hits map, candidate lists, snapshots)
   isac::DevBuf redet;                // isac_fft2d_redetect (cfar.hip): per-CUT flags, per-antenna lists sized for every CUT, counts, row flags
+  isac::DevBuf cfar_mc;              // isac_cfar_monte_carlo (cfar.hip): detection counts, per-trial flags
   isac::RangeCache range_cache;
   isac::LazyEcho lazy;               // the echo grid of the last fused monoStaticSensing call when the caller passed no array for it
   // overlap-save CDL apply (cdl_os.hip): the forward spectra of the last downlink batch, kept in a buffer of their own so that the NEXT batch on this context can reuse them when

@@ -36,7 +36,8 @@ int isac_range_stage_into_cache(isac_ctx* ctx, const isac_est_params* ep, const 
 // ---------------------------------------------------------------- targets.hip: isac_fft2d_get_targets (include/isac_targets.h) -- the per-target list of the last completed fft2D.  It calls nothing but
 // isac_get_twiddles and is called by no other unit; what it shares with them is ctx->tgt (isac::Fft2dCpi, isac_common.hpp): fft2d.hip fills it, rdm.hip / echo.hip drop it.
 // ---------------------------------------------------------------- cfar.hip: the GOCA / SOCA / OS detectors (include/isac_cfar.h): isac_cfar2d, isac_fft2d_redetect, isac_cfar_threshold_factor.  Reads ctx->tgt and
-// ctx->pwin, writes ctx->redet only; calls cfar_alpha (rdm.hip) and fft2d_estimates (fft2d.hip).
+// ctx->pwin, writes ctx->redet only; calls cfar_alpha (rdm.hip) and fft2d_estimates (fft2d.hip).  Also isac_cfar_monte_carlo (include/isac_cfar_mc.h): reads nothing of the
+// context, writes ctx->cfar_mc only.
 // ---------------------------------------------------------------- fft2d.hip: the host side of the fft2D pipeline -- submit, collect, submit_n / collect_n, the host-array call, the getters
 // host half of fft2D.m:63-99 on per-antenna CUT-order lists (callers: isac_fft2d_collect, isac_fft2d_redetect)
 int fft2d_estimates(isac_ctx* ctx, const isac_est_params* ep, const isac::CutWindow& win, int A, const int* ant_off, const std::vector<int>& cut, const std::vector<double>& pw, int num_dets_dev, std::vector<int32_t>& det_rc, isac_est_result* out);
@@ -78,6 +79,7 @@ bool cdl_os_ul_ok(long long T, int Nt, int Nr, int n_paths, int n_taps, int max_
 int cdl_os_apply(isac_ctx* ctx, const isac_cdl_job* jobs, int n_jobs, long long T, int Nt, int Nr, int n_paths, const double* taps, int n_taps, const int32_t* shift, int max_shift, double out_scale);
 // ---------------------------------------------------------------- rxfe.hip: the tail of applyChannelModel (path loss, Rx gain, thermal noise), one launch for a batch
 constexpr uint32_t kRxFrontEndStream = 3u;   // Philox stream word of its time-domain AWGN (0: the echo's time-domain noise, 1: isac_synth_qpsk_grid_dev, 2: kSpectralStream)
+constexpr uint32_t kCfarMcStream = 4u;       // ... 4: the noise cells of isac_cfar_monte_carlo (cfar.hip; include/isac_cfar_mc.h)
 int isac_rx_frontend_jobs(isac_ctx* ctx, const isac_rx_frontend_job* jobs, int n_jobs, long long T, int Nr, int noise_mode);
 
 // The status record the device eigensolver leaves behind the eigenvalues (ctx->eig_w [A] | isac::EighInfo, eigh_layout.hpp), and the one place the two outputs are sized

@@ -657,5 +657,6 @@ int isac_synth_qpsk_grid_dev(isac_ctx* ctx, isac_c64* d_grid, int32_t K, int32_t
 
 #include "isac_targets.h"   /* isac_fft2d_get_targets: additive under ABI 8 */
 #include "isac_cfar.h"      /* GOCA / SOCA / OS detectors, isac_fft2d_redetect: additive under ABI 8 */
+#include "isac_cfar_mc.h"   /* isac_cfar_monte_carlo, the detectors' Pfa / Pd by counting: additive under ABI 8 */
 
 #endif /* ISAC_H */
