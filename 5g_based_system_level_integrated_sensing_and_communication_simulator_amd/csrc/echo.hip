@@ -509,8 +509,9 @@ using namespace isac;
 
 static int check_carrier(isac_ctx* ctx, const isac_carrier* c) {
   if (!c) return fail(ctx, ISAC_ERR_INVALID_ARG, "carrier is NULL");
-  if (c->nfft < 64 || c->nfft > 4096 || (c->nfft & (c->nfft - 1)))
-    return fail(ctx, ISAC_ERR_UNSUPPORTED, "carrier.nfft must be a power of two in 64..4096");
+  // (below 128 -- nrOFDMInfo's own minimum -- the normal cyclic prefix, 9 Nfft / 128 samples, is not a whole number of samples)
+  if (c->nfft < 128 || c->nfft > 4096 || (c->nfft & (c->nfft - 1)))
+    return fail(ctx, ISAC_ERR_UNSUPPORTED, "carrier.nfft must be a power of two in 128..4096: no integral normal cyclic prefix (144 Nfft / 2048 samples) exists below 128");
   if (c->n_sc <= 0 || c->n_sc > c->nfft || (c->n_sc & 1)) return fail(ctx, ISAC_ERR_INVALID_ARG, "carrier.n_sc invalid");
   if (c->scs_khz != 15 && c->scs_khz != 30 && c->scs_khz != 60 && c->scs_khz != 120)
     return fail(ctx, ISAC_ERR_INVALID_ARG, "carrier.scs_khz must be 15/30/60/120");

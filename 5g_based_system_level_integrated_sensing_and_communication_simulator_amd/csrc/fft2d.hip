@@ -65,10 +65,8 @@ int resolve_grids(isac_ctx* ctx, const isac_est_params* ep, const isac_cfar_conf
     *lazy_native = lz.native;
     if (!lz.native) *d_rx_grid = (const isac_c64*)ctx->echo_own.p;
   }
-  if (K <= 0 || L <= 0 || A <= 0 || A > 1024) return fail(ctx, ISAC_ERR_INVALID_ARG, "bad grid dimensions");
-  if (ep->n_ifft < K || (ep->n_ifft & (ep->n_ifft - 1)) || ep->n_fft <= 0 || (ep->n_fft & (ep->n_fft - 1)))
-    return fail(ctx, ISAC_ERR_INVALID_ARG, "nIFFT/nFFT must be powers of two with nIFFT >= K");
-  return ISAC_OK;
+  if (A > 1024) return fail(ctx, ISAC_ERR_INVALID_ARG, "bad grid dimensions");   // (pack_kernel's per-antenna counters)
+  return check_rdm_dims(ctx, ep, K, L, A);
 }
 // fft2D.m:106-107 into ctx->cov, on `st`
 int enqueue_covariance(isac_ctx* ctx, hipStream_t st, bool lazy_native, const isac_c64* d_rx_grid, int K, int L, int A) {

@@ -27,6 +27,7 @@ int isac_get_rise_window(isac_ctx* ctx, int n_win, const double** out);
 int isac_get_windows(isac_ctx* ctx, int K, int n_ifft, const double** win_k, const double** win_r);
 // ---------------------------------------------------------------- rdm.hip
 int isac_rdm_power_window(isac_ctx* ctx, const isac_est_params* ep, const isac_cfar_config* cf, const isac::c64* d_rx, const isac::c64* d_tx, int K, int L, int A, bool use_cached_range);   // leaves the window of isac::CutWindow::of(*cf) in ctx->pwin
+int check_rdm_dims(isac_ctx* ctx, const isac_est_params* ep, int K, int L, int A);   // ISAC_ERR_INVALID_ARG unless K, L, A > 0 and nIFFT >= K, nFFT > 0 are powers of two: what every entry that runs the range or the Doppler stage asks of its grids
 int isac_cfar_window(isac_ctx* ctx, const isac_est_params* ep, const isac_cfar_config* cf, int A, int cap);
 double cfar_alpha(int n_train, double pfa);   // CA, ThresholdFactor 'Auto': N (Pfa^(-1/N) - 1)
 namespace isac { struct CutRows { int row_lo, nr; }; }   // rows [row_lo, row_lo + nr) of the range-Doppler map (0-based): the CUT rows +- (guard + training)

@@ -526,6 +526,15 @@ using namespace isac;
 
 double cfar_alpha(int n_train, double pfa) { return n_train * (std::pow(pfa, -1.0 / n_train) - 1.0); }
 
+// The grid dimensions and transform lengths the range and the Doppler kernels can take: range_kernel reads prx[K - 1] for the padding rows, and the Doppler
+// kernels' column <-> bin rule, (column + n_fft / 2) mod n_fft, is the fftshift of radarParams.m:69-75's power-of-two lengths only.
+int check_rdm_dims(isac_ctx* ctx, const isac_est_params* ep, int K, int L, int A) {
+  if (K <= 0 || L <= 0 || A <= 0) return fail(ctx, ISAC_ERR_INVALID_ARG, "bad grid dimensions");
+  if (ep->n_ifft < K || (ep->n_ifft & (ep->n_ifft - 1)) || ep->n_fft <= 0 || (ep->n_fft & (ep->n_fft - 1)))
+    return fail(ctx, ISAC_ERR_INVALID_ARG, "nIFFT/nFFT must be powers of two with nIFFT >= K");
+  return ISAC_OK;
+}
+
 template <class FFT>
 static int launch_range(isac_ctx* ctx, const c64* rx, const c64* tx, int K, int L, int A, const c64* tw, const double* wk, const double* wr, int n_ifft,
                         int row_lo, int n_rows, c64* ymid) {
@@ -751,6 +760,7 @@ extern "C" int isac_fft2d_range_stage_dev(isac_ctx* ctx, const isac_est_params* 
                                           const isac_c64* d_rx_grid, const isac_c64* d_tx_grid, int32_t K, int32_t L, int32_t A) {
   ISAC_ENTER(ctx);
   if (!ep || !cf || !d_rx_grid || !d_tx_grid) return fail(ctx, ISAC_ERR_INVALID_ARG, "NULL argument");
+  ISAC_TRY(check_rdm_dims(ctx, ep, K, L, A));
   ctx->range_cache.valid = false;
   CutRows cr;
   return range_stage_cut(ctx, ep, cf, (const c64*)d_rx_grid, (const c64*)d_tx_grid, K, L, A, &cr);
@@ -760,6 +770,7 @@ extern "C" int isac_rdm_plane_dev(isac_ctx* ctx, const isac_est_params* ep, cons
                                   const isac_c64* d_tx_grid, int32_t K, int32_t L, int32_t A, int32_t ant, isac_c64* d_rdm) {
   ISAC_ENTER(ctx);
   if (!ep || !d_rx_grid || !d_tx_grid || !d_rdm || ant < 0 || ant >= A) return fail(ctx, ISAC_ERR_INVALID_ARG, "bad arguments");
+  ISAC_TRY(check_rdm_dims(ctx, ep, K, L, A));
   const int n_ifft = ep->n_ifft, n_fft = ep->n_fft;
   const c64* twd = nullptr;
   ISAC_TRY(isac_get_twiddles(ctx, n_fft, &twd));

@@ -100,7 +100,8 @@ int isac_profile_last_kernel_ms(isac_ctx* ctx, double* ms);
 /* carrier = nrCarrierConfig fields monoStaticSensing.m:8-10 sets, + nrOFDMInfo() */
 typedef struct {
   int32_t n_sc;      /* 12 * NRBsDL                              */
-  int32_t nfft;      /* nrOFDMInfo.Nfft (power of two, <= 4096)  */
+  int32_t nfft;      /* nrOFDMInfo.Nfft (power of two, 128..4096: nrOFDMInfo's minimum is 128, and below it the normal cyclic
+                        prefix, 9 Nfft / 128 samples, is not a whole number: ISAC_ERR_UNSUPPORTED) */
   int32_t scs_khz;   /* 15 / 30 / 60 / 120                       */
   int32_t reserved;
 } isac_carrier;
