@@ -826,7 +826,7 @@ struct CovLazyGenerator {
     for (int j = 0; j < 2; ++j) {
       const int ant = ga + 32 * j;
       ant_ok[j] = ant < a.A;
-      colbase[j] = (uint64_t)a.L_out * (uint64_t)ant;
+      colbase[j] = (uint64_t)gp + (uint64_t)kSpectralSlotsPerColumn * ((uint64_t)a.L_out * (uint64_t)ant);   // the thread's part of the Philox counter; the slab's part (init) is wave-uniform
 #pragma unroll
       for (int q = 0; q < QT; ++q) st[j][q] = ant_ok[j] ? a.steer_rq[(long long)ant * QT + q] : mk(0.0, 0.0);
     }
@@ -845,10 +845,11 @@ struct CovLazyGenerator {
     const bool in = c.g < s_end;
     v_half[0] = in && k0 < K;
     v_half[1] = in && k0 + 512 < K;
-    const uint32_t slot = (uint32_t)(((c.sc >> 6) << 9) + ((c.sc & 63) << 3) + gp);
+    const uint32_t slot = (uint32_t)(((c.sc >> 6) << 9) + ((c.sc & 63) << 3));               // (+ gp: in colbase)
+    const uint64_t slab = (uint64_t)slot + (uint64_t)kSpectralSlotsPerColumn * (uint64_t)c.l;   // (scalar registers)
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      const uint64_t ctr = (uint64_t)slot + (uint64_t)kSpectralSlotsPerColumn * ((uint64_t)c.l + colbase[j]);
+      const uint64_t ctr = slab + colbase[j];                         // = (slot + gp) + 2048 (l + L_out ant)
       pc[j][0] = (uint32_t)ctr; pc[j][1] = (uint32_t)(ctr >> 32); pc[j][2] = kSpectralStream; pc[j][3] = 0u;
     }
   }

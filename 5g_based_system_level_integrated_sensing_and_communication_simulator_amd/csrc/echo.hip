@@ -29,6 +29,28 @@ namespace isac {
 // HBM-bound: T x A x 16 B read once (1.007 GB at the bench shape), nothing else.  Each workgroup walks blocks of 256 consecutive samples
 // (grid-stride: 1024 long-lived workgroups, four per CU) with its antenna loop unrolled UNROLL deep: 170.6 us = 5.90 TB/s, against 178 us of the
 // 8-deep one-block-per-workgroup form of rounds 1-3 (profiles/r04_beamsum_sweep.txt; a plain streaming read tops out at 6.0-6.2 TB/s, tools/gbench.hip).
+// One sample's sums over the antennas, for both kernels below: acc[q] = sum_a p[a T] s_steer[q A + a].
+template <int QT, int UNROLL>
+__device__ __forceinline__ void beam_sample(const c64* __restrict__ p /* tx + t */, long long T, int A, const c64* __restrict__ s_steer /* LDS [QT x A] */, c64 (&acc)[QT]) {
+#pragma unroll
+  for (int q = 0; q < QT; ++q) acc[q] = mk(0.0, 0.0);
+  int a = 0;
+  for (; a + UNROLL <= A; a += UNROLL) {
+    c64 v[UNROLL];
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) v[u] = p[(long long)(a + u) * T];
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u)
+#pragma unroll
+      for (int q = 0; q < QT; ++q) acc[q] = fma(v[u], s_steer[q * A + a + u], acc[q]);
+  }
+  for (; a < A; ++a) {
+    c64 v = p[(long long)a * T];
+#pragma unroll
+    for (int q = 0; q < QT; ++q) acc[q] = fma(v, s_steer[q * A + a], acc[q]);
+  }
+}
+
 template <int QT, int UNROLL>
 __global__ __launch_bounds__(256) void beamsum_kernel(const c64* __restrict__ tx, long long T, int A,
                                                       const c64* __restrict__ steer /* [A x QT] compacted LoS */,
@@ -41,24 +63,7 @@ __global__ __launch_bounds__(256) void beamsum_kernel(const c64* __restrict__ tx
     const long long t = t0 + threadIdx.x;
     const long long tc = t < T ? t : T - 1;                            // unconditional loads (clamped), one conditional store
     c64 acc[QT];
-#pragma unroll
-    for (int q = 0; q < QT; ++q) acc[q] = mk(0.0, 0.0);
-    const c64* p = tx + tc;
-    int a = 0;
-    for (; a + UNROLL <= A; a += UNROLL) {
-      c64 v[UNROLL];
-#pragma unroll
-      for (int u = 0; u < UNROLL; ++u) v[u] = p[(long long)(a + u) * T];
-#pragma unroll
-      for (int u = 0; u < UNROLL; ++u)
-#pragma unroll
-        for (int q = 0; q < QT; ++q) acc[q] = fma(v[u], s_steer[q * A + a + u], acc[q]);
-    }
-    for (; a < A; ++a) {
-      c64 v = p[(long long)a * T];
-#pragma unroll
-      for (int q = 0; q < QT; ++q) acc[q] = fma(v, s_steer[q * A + a], acc[q]);
-    }
+    beam_sample<QT, UNROLL>(tx + tc, T, A, s_steer, acc);
     if (t < T) {
 #pragma unroll
       for (int q = 0; q < QT; ++q) beam[(long long)q * T + t] = acc[q];
@@ -77,6 +82,25 @@ struct TargetTable {
   TargetDesc t[kMaxTargets];
 };
 
+// exp(-2j*pi*fc*t) at receive time tt = t Ts   basicRadarChannel.m:73
+__device__ __forceinline__ c64 rx_phase(double w /* (2*pi)*fc */, double tt) {
+  double s, c;
+  sincos(w * tt, &s, &c);
+  return mk(c, -s);
+}
+
+// coef_q[t] for t >= d = td.shift from the beam-sum sample b = beam_q[t - d]: THE expression of the coefficient vectors, shared by coef_kernel and beamsum_coef_kernel --
+// same operations in the same order, so the same bits.  tt = (double)t * Ts, prx = rx_phase(w, tt).
+__device__ __forceinline__ c64 coef_value(c64 b, long long t, const TargetDesc& td, double w, double Ts, double tt, c64 prx) {
+  double sd, cd, st, ct;
+  sincos(td.wd * tt, &sd, &cd);                                // doppler phase at receive time  :43-44
+  sincos(w * ((double)(t - td.shift) * Ts), &st, &ct);         // up-conversion phase at transmit time :29-31,42
+  c64 v = b * mk(ct, st);
+  v = v * mk(cd, sd);
+  v = v * td.lsf;
+  return v * prx;
+}
+
 __global__ __launch_bounds__(256) void coef_kernel(const c64* __restrict__ beam, long long T, int Q,
                                                    TargetTable tab, double w /* (2*pi)*fc */, double Ts,
                                                    c64* __restrict__ coef /* [Q x T] */,
@@ -84,23 +108,48 @@ __global__ __launch_bounds__(256) void coef_kernel(const c64* __restrict__ beam,
   long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= T) return;
   double tt = (double)t * Ts;
-  double s, c;
-  sincos(w * tt, &s, &c);
-  c64 prx = mk(c, -s);  // exp(-2j*pi*fc*t)   basicRadarChannel.m:73
+  c64 prx = rx_phase(w, tt);
   phase_rx[t] = prx;
   for (int q = 0; q < Q; ++q) {
     long long d = tab.t[q].shift;
     c64 out = mk(0.0, 0.0);
-    if (t >= d) {
-      double sd, cd, st, ct;
-      sincos(tab.t[q].wd * tt, &sd, &cd);                  // doppler phase at receive time  :43-44
-      sincos(w * ((double)(t - d) * Ts), &st, &ct);         // up-conversion phase at transmit time :29-31,42
-      c64 v = beam[(long long)q * T + (t - d)] * mk(ct, st);
-      v = v * mk(cd, sd);
-      v = v * tab.t[q].lsf;
-      out = v * prx;
-    }
+    if (t >= d) out = coef_value(beam[(long long)q * T + (t - d)], t, tab.t[q], w, Ts, tt, prx);
     coef[(long long)q * T + t] = out;
+  }
+}
+
+// The beam-sum that writes the coefficient vectors itself (the spectral route of isac_mono_static_sensing_fused_dev, one or two LoS targets): that route reads neither beam
+// nor phase_rx, and coef_kernel was a launch of its own on the serial chain of the CPI -- 12-13 us plus its gap, for ~300 VALU instructions per sample that fit in the shadow
+// of this kernel's loads.  The thread that has summed sample u of target q holds beam_q[u] = the only input of coef_q[u + d_q] (coef_value above: the bits of coef_kernel);
+// it also writes the zero of coef_q[u] for u < d_q, so every element of coef [QT x T] is written exactly once; samples with u + d_q >= T are dropped.
+template <int QT>
+struct CoefTargets {
+  TargetDesc t[QT];
+};
+template <int QT, int UNROLL>
+__global__ __launch_bounds__(256) void beamsum_coef_kernel(const c64* __restrict__ tx, long long T, int A,
+                                                           const c64* __restrict__ steer /* [A x QT] compacted LoS */,
+                                                           CoefTargets<QT> tab, double w /* (2*pi)*fc */, double Ts,
+                                                           c64* __restrict__ coef /* [QT x T] */) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  c64* s_steer = reinterpret_cast<c64*>(smem_raw);
+  for (int i = threadIdx.x; i < A * QT; i += blockDim.x) s_steer[i] = steer[i];
+  __syncthreads();
+  for (long long t0 = (long long)blockIdx.x * 256; t0 < T; t0 += (long long)gridDim.x * 256) {
+    const long long u = t0 + threadIdx.x;
+    const long long uc = u < T ? u : T - 1;                            // unconditional loads (clamped), conditional stores
+    c64 acc[QT];
+    beam_sample<QT, UNROLL>(tx + uc, T, A, s_steer, acc);
+#pragma unroll
+    for (int q = 0; q < QT; ++q) {
+      const long long d = tab.t[q].shift, t = u + d;
+      c64* cq = coef + (long long)q * T;
+      if (u < d && u < T) cq[u] = mk(0.0, 0.0);
+      if (u < T && t >= 0 && t < T) {
+        const double tt = (double)t * Ts;
+        cq[t] = coef_value(acc[q], t, tab.t[q], w, Ts, tt, rx_phase(w, tt));
+      }
+    }
   }
 }
 
@@ -340,13 +389,17 @@ __global__ __launch_bounds__(Fft4096W::NT, kEchoRangeWavesPerSimd) void echo_ran
 #pragma unroll
     for (int u = 0; u < GROUP; ++u) {
       const int k = tid + NT * (g * GROUP + u);
-      const int kc = k < K ? k : K - 1;                                 // unconditional loads, select afterwards
+      const int kc = k < K ? k : K - 1;                                 // unconditional loads at a clamped row
+      // every base below is uniform and the row's byte offset fits 32 bits (kc < 4096): as unsigned offsets the loads take the scalar-base + 32-bit vector-offset form --
+      // one shift per element instead of a sign extension, a 64-bit shift and a 64-bit add per pointer
+      const unsigned o16 = (unsigned)kc * (unsigned)sizeof(c64);
+      auto at = [](const auto* base, unsigned off) { return *reinterpret_cast<decltype(base)>(reinterpret_cast<const char*>(base) + off); };
       Ld& e = ld[b][u];
-      e.tx = ptx[kc];
-      e.w = win_k[kc];
-      if constexpr (NZ == 2) e.nz = nzc[kc];
+      e.tx = at(ptx, o16);
+      e.w = at(win_k, (unsigned)k * (unsigned)sizeof(double));          // the window of the zero-padded IFFT input: n_ifft entries, +0.0 from K on (isac_get_windows)
+      if constexpr (NZ == 2) e.nz = at(nzc, o16);
 #pragma unroll
-      for (int q = 0; q < QT; ++q) e.d[q] = Dl[(long long)q * d_stride + kc];
+      for (int q = 0; q < QT; ++q) e.d[q] = at(Dl + (long long)q * d_stride, o16);
     }
     asm volatile("" ::: "memory");                                      // (compiler-only) nothing of the next phase moves above these loads
   };
@@ -378,10 +431,9 @@ __global__ __launch_bounds__(Fft4096W::NT, kEchoRangeWavesPerSimd) void echo_ran
       if constexpr (STORE) buffer_store_c64_nt(rs_dst, (unsigned)k * (unsigned)sizeof(c64), v);   // echoGrid(k, l, r); k >= K: dropped by the bounds check
       else asm volatile("" ::"v"(v.re), "v"(v.im) : "memory");          // (compiler-only: the element is complete HERE, as in the storing form -- without this anchor the scheduler
                                                                         //  interleaves the eight elements and the two-target form spills 35 registers)
-      c64 y = mul_conj(v, e.tx) * e.w;                                  // fft2D.m:37,:43 (same order as range_kernel)
-      y = k < K ? y : mk(0.0, 0.0);                                     // ifft(., nIFFT, 1) zero-pads at the end
-      live |= (y.re != 0.0) | (y.im != 0.0);
-      fft.x[j] = y;
+      const c64 y = mul_conj(v, e.tx) * e.w;                            // fft2D.m:37,:43 (same order as range_kernel); k >= K: e.w = +0.0, so y is a signed zero --
+      live |= (y.re != 0.0) | (y.im != 0.0);                            // ifft(., nIFFT, 1) zero-pads at the end -- without a select per element (v, e.tx come from row K - 1:
+      fft.x[j] = y;                                                     // finite wherever that row's own product is)
     }
   };
 #pragma unroll
@@ -547,9 +599,10 @@ extern "C" int isac_ofdm_waveform_length(const isac_carrier* carrier, int32_t L,
 }
 
 // Everything basicRadarChannel needs before samples can be synthesised: LoS compaction,
-// beam-sums, coefficient vectors.  Leaves coef [Q x T], phase_rx [T], steer_rq [A x Q] in ctx.
+// beam-sums, coefficient vectors.  Leaves coef [Q x T], phase_rx [T], steer_rq [A x Q] in ctx.  coef_only: the caller reads coef and steer alone -- with one or two LoS targets
+// the beam-sum then writes coef itself (beamsum_coef_kernel) and beam / phase_rx are left as they were.
 static int prepare_echo(isac_ctx* ctx, const c64* d_tx, long long T, const isac_radar_channel_params* rp,
-                        const uint8_t* los, int* q_out) {
+                        const uint8_t* los, int* q_out, bool coef_only = false) {
   if (!d_tx || !rp || !los) return fail(ctx, ISAC_ERR_INVALID_ARG, "NULL argument");
   if (T <= 0 || rp->n_ants <= 0 || rp->n_targets < 0) return fail(ctx, ISAC_ERR_INVALID_ARG, "bad T / n_ants / n_targets");
   ctx->lazy.valid = false;                          // steer / coef / dgrid below are the inputs of a lazy echo grid of an earlier call: overwritten now
@@ -598,6 +651,21 @@ static int prepare_echo(isac_ctx* ctx, const c64* d_tx, long long T, const isac_
   const unsigned gb = cdiv(T, 256);                                   // one thread per sample (coef_kernel below)
   const unsigned gbs = (unsigned)std::min<long long>(gb, 1024);        // beam-sum: long-lived workgroups (sweep: profiles/r04_beamsum_sweep.txt)
   timeline_mark(ctx, 0, ctx->stream);
+  const double w = two_pi * rp->fc;                 // 2j*pi*fc  :30,:73
+  if (coef_only && Q <= 2) {                        // one launch: the beam-sum writes coef itself; beam and phase_rx stay unwritten (the caller reads neither)
+    auto launch = [&](auto qc) {
+      constexpr int QT = decltype(qc)::value;
+      CoefTargets<QT> ct;
+      for (int q = 0; q < QT; ++q) ct.t[q] = tab.t[q];
+      hipLaunchKernelGGL((beamsum_coef_kernel<QT, 32>), dim3(gbs), dim3(256), sizeof(c64) * A * QT, ctx->stream, d_tx, T, A, (const c64*)d_steer_aq, ct, w, Ts, (c64*)ctx->coef.p);
+    };
+    if (Q == 1) launch(std::integral_constant<int, 1>{});
+    else launch(std::integral_constant<int, 2>{});
+    ISAC_HIP(hipGetLastError());
+    timeline_mark(ctx, 1, ctx->stream);
+    *q_out = Q;
+    return ISAC_OK;
+  }
 #define ISAC_BEAMSUM(QT) \
   hipLaunchKernelGGL((beamsum_kernel<QT, (QT <= 2 ? 32 : 8)>), dim3(gbs), dim3(256), sizeof(c64) * A * QT, ctx->stream, d_tx, T, A, st, bm)
   for (int q0 = 0; q0 < Q;) {
@@ -611,7 +679,6 @@ static int prepare_echo(isac_ctx* ctx, const c64* d_tx, long long T, const isac_
   }
 #undef ISAC_BEAMSUM
   timeline_mark(ctx, 1, ctx->stream);
-  const double w = two_pi * rp->fc;                 // 2j*pi*fc  :30,:73
   hipLaunchKernelGGL(coef_kernel, dim3(gb), dim3(256), 0, ctx->stream, (const c64*)ctx->beam.p, T, Q, tab, w, Ts,
                      (c64*)ctx->coef.p, (c64*)ctx->phase_rx.p);
   ISAC_HIP(hipGetLastError());
@@ -671,9 +738,9 @@ static int launch_demod(isac_ctx* ctx, const OfdmGeom& g, long long T, int A, in
 // ---- spectral noise modes: per-target demodulated coefficient grids D [K x L_whole x Q] (the coefficient vectors
 // coef [Q x T] are, byte for byte, a [T x Q] waveform), then one synthesis kernel.
 static int spectral_prepare(isac_ctx* ctx, const c64* d_tx, long long T, const isac_radar_channel_params* rp, const uint8_t* los,
-                            const OfdmGeom& g, int* q_out, int* l_whole_out) {
+                            const OfdmGeom& g, int* q_out, int* l_whole_out, bool coef_only = false) {
   int Q = 0;
-  ISAC_TRY(prepare_echo(ctx, d_tx, T, rp, los, &Q));                                 // monoStaticSensing.m:13
+  ISAC_TRY(prepare_echo(ctx, d_tx, T, rp, los, &Q, coef_only));                      // monoStaticSensing.m:13
   const int L_whole = whole_symbols(g, T);
   if (L_whole <= 0) return fail(ctx, ISAC_ERR_SHORT_WAVEFORM, "waveform shorter than one OFDM symbol");
   ISAC_TRY(ensure(ctx, ctx->dgrid, sizeof(c64) * (size_t)g.n_sc * L_whole * Q));
@@ -812,7 +879,8 @@ extern "C" int isac_mono_static_sensing_fused_dev(isac_ctx* ctx, const isac_c64*
   // (tried in round 6 and removed: the front of the call -- beam-sum, coefficient vectors, Q x L demodulation FFTs -- on a lowest-priority third stream per context, so that it
   //  would yield to the compute-bound kernels of the CPIs ahead: 24 streams on 16 hardware queues collapse the pipelined rate to 4-5 k slots/s whatever GPU_MAX_HW_QUEUES says,
   //  and with 4-5 contexts (12-15 streams) it is 7-15 % slower than two streams per context; profiles/r06_lazy_first_measurements.txt)
-  ISAC_TRY(spectral_prepare(ctx, (const c64*)d_tx_wave, T, rp, los, g, &Q, &L_whole));
+  // (coef_only: this route reads coef and steer alone; isac_mono_static_sensing_dev keeps beamsum_kernel + coef_kernel and is the in-tree reference of the one-launch form)
+  ISAC_TRY(spectral_prepare(ctx, (const c64*)d_tx_wave, T, rp, los, g, &Q, &L_whole, true));
   const int A = rp->n_ants, row_lo = cr.row_lo, nr = cr.nr;
   const int L_out = padded_symbols(L_whole, tx_dim_l, l_out);
   ctx->tgt.drop();                                     // the fused kernel rewrites the range rows isac_fft2d_get_targets reads

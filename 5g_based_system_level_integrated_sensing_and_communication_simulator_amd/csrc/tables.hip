@@ -88,10 +88,12 @@ int isac_get_rise_window(isac_ctx* ctx, int n_win, const double** out) {
   });
 }
 
-// kaiser(K, 3) over the subcarriers and fftshift(kaiser(n_ifft, 3)) over the range bins
+// kaiser(K, 3) over the subcarriers and fftshift(kaiser(n_ifft, 3)) over the range bins.  The subcarrier window is handed out as max(K, n_ifft) entries, +0.0 beyond K: it is
+// the window of the zero-padded IFFT input (ifft(., nIFFT, 1), fft2D.m:43), so a kernel that indexes it with the unclamped input row (echo_range_sl_kernel, echo.hip) gets its
+// zero padding from the product and needs no select; range_kernel and echo_range_kernel read it below K only.
 int isac_get_windows(isac_ctx* ctx, int K, int n_ifft, const double** win_k, const double** win_r) {
-  auto get = [&](int n, bool shifted, const double** out) {
-    return cached_table(ctx, {shifted ? kKaiser3Shifted : kKaiser3, {n}}, out, [&](std::vector<double>& w) {
+  auto get = [&](int n, int n_pad, bool shifted, const double** out) {
+    return cached_table(ctx, {shifted ? kKaiser3Shifted : kKaiser3, {n, n_pad}}, out, [&](std::vector<double>& w) {
       w = kaiser_window(n, 3.0);                                // fft2D.m:135 'kaiser', beta = 3
       if (shifted) {                                            // fftshift: out[i] = in[(i + ceil(n/2)) mod n]
         std::vector<double> s((size_t)n);
@@ -99,9 +101,10 @@ int isac_get_windows(isac_ctx* ctx, int K, int n_ifft, const double** win_k, con
         for (int i = 0; i < n; ++i) s[(size_t)i] = w[(size_t)((i + sh) % n)];
         w.swap(s);
       }
+      if (n_pad > n) w.resize((size_t)n_pad, 0.0);
     });
   };
-  ISAC_TRY(get(K, false, win_k));
-  ISAC_TRY(get(n_ifft, true, win_r));
+  ISAC_TRY(get(K, K > n_ifft ? K : n_ifft, false, win_k));
+  ISAC_TRY(get(n_ifft, n_ifft, true, win_r));
   return ISAC_OK;
 }
