@@ -198,6 +198,7 @@ PROTOTYPES = {
     "isac_get_angular_spectrum2d": (_INT, (_P, _P, _I64, _P)),
     "isac_find2d_peaks": (_INT, (_P, _P, _I32, _I32, _I32, _P, _P, _P)),
     "isac_music2d_dev": (_INT, (_P, _ptr(EstParams), _ptr(Music2dParams), _P, _P, _I32, _I32, _I32, _ptr(EstResult))),
+    "isac_music2d_get_spectra": (_INT, (_P, _P, _I32, _P, _I32, _P)),
     "isac_eigh": (_INT, (_P, _P, _I32, _P, _P)),
     "isac_cdl_apply_dev": (_INT, (_P, _P, _I64, _I32, _I32, _I32, _P, _I32, _P, _P, _I32, _P, _F64, _P)),
     "isac_cdl_apply_batch_dev": (_INT, (_P, _ptr(CdlJob), _I32, _I64, _I32, _I32, _I32, _P, _I32, _P, _F64)),
@@ -412,6 +413,15 @@ class Context:
         out = np.zeros(n.value, dtype=np.float64)
         self.check(self.lib.isac_fft2d_get_music_spectrum(self.handle, _np_ptr(out), out.size, C.byref(n)))
         return out
+
+    def music2d_spectra(self):
+        """(PrdB [rSteps], PvdB [vSteps]): the dB range and velocity spectra of this context's last completed music2D (isac_music2d_get_spectra);
+        IsacError(INVALID_ARG) while there is none."""
+        n = (C.c_int32 * 2)()
+        self.check(self.lib.isac_music2d_get_spectra(self.handle, None, 0, None, 0, n))
+        pr, pv = np.zeros(n[0], dtype=np.float64), np.zeros(n[1], dtype=np.float64)
+        self.check(self.lib.isac_music2d_get_spectra(self.handle, _np_ptr(pr), pr.size, _np_ptr(pv), pv.size, n))
+        return pr, pv
 
     def share_streams(self, owner: "Context | None"):
         """Enqueue on `owner`'s two streams from now on (None: back to this context's own): isac_ctx_share_streams."""

@@ -292,6 +292,7 @@ extern "C" int isac_ctx_reserve(isac_ctx* ctx, int64_t T, int32_t tx_dim_l, cons
   ctx->range_cache.valid = false;                                                          // the cached rows belong to grids that are about to be freed
   ctx->last.valid = false;                                                                 // isac_fft2d_get_* must not hand out the dry run's detections / window / Ra
   ctx->last.spectrum_db.clear();                                                           // ... nor its azimuth spectrum (isac_fft2d_get_music_spectrum asks for a scan, not for last.valid)
+  ctx->last.range_db.clear(); ctx->last.velocity_db.clear();                               // ... nor, by the same rule, music2D spectra from before the buffers were re-planned (isac_music2d_get_spectra)
   ctx->tgt.drop();                                                                         // nor isac_fft2d_get_targets the dry run's targets
   ctx->profile_recorded = false;                                                           // nor isac_profile_last_kernel_ms the dry run's kernel
   (void)grid.reset(); (void)wave.reset(); (void)echo.reset();

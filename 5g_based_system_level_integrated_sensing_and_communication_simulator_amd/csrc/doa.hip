@@ -391,6 +391,8 @@ extern "C" int isac_music2d_dev(isac_ctx* ctx, const isac_est_params* ep, const 
   ISAC_ENTER(ctx);
   if (!ep || !mp || !d_rx_grid || !d_tx_grid || !out || K <= 0 || L <= 0 || A <= 0) return fail(ctx, ISAC_ERR_INVALID_ARG, "bad arguments");
   std::memset(out, 0, sizeof(*out));
+  ctx->last.range_db.clear();                                           // (a call that fails from here on leaves no spectra behind)
+  ctx->last.velocity_db.clear();
   const double c0 = 299792458.0;                                        // physconst('LightSpeed')  music2D.m:35
   const double lambda = c0 / mp->fc;                                    // :37
   const double r_gran = 0.5, v_gran = 0.5;                              // :43-44
@@ -425,25 +427,32 @@ extern "C" int isac_music2d_dev(isac_ctx* ctx, const isac_est_params* ep, const 
   ISAC_TRY(isac_eigh_dev(ctx, (const c64*)ctx->cov.p, L, nullptr));                                            // :77-89
   std::vector<double> wg; std::vector<int> order;
   ISAC_TRY(sorted_eigenpairs(ctx, L, true, wg, nullptr, order));                                                // sort(.,'descend')
+  // An empty noise space (Urn / Uvn of :81,:88 have no column: Lsig >= K for the range, Lsig >= L for the velocity) is a flat 0 dB spectrum without
+  // estimates, as in the ULA scan (include/isac.h).  H has rank <= L, so Rr has at most L signal vectors whatever Lsig says.
+  const bool r_empty = Lsig >= K, v_empty = Lsig >= L;
   const int Lu = std::min(Lsig, L);
   std::vector<int> top(order.begin(), order.begin() + Lu);
   ISAC_TRY(ensure(ctx, ctx->stage_b, sizeof(c64) * (size_t)K * Lu + sizeof(int) * (size_t)Lu + 64));
   c64* d_U = (c64*)ctx->stage_b.p;
   int* d_top = (int*)((char*)ctx->stage_b.p + sizeof(c64) * (size_t)K * Lu);
   ISAC_TRY(copy_h2d(ctx, d_top, top.data(), sizeof(int) * (size_t)Lu));
-  ISAC_TRY(isac_music2d_signal_vectors(ctx, d_h, K, L, d_top, Lu, d_U));
-  // range scan  ar = exp(-2j*pi*scs*2*r*n/c)                                                :92,:98-102
-  const double coef_r = ((-2.0 * M_PI) * mp->scs_hz) * 2.0;
-  ISAC_TRY(isac_music2d_scan(ctx, d_U, K, K, nullptr, Lu, 0, coef_r, c0, 0.0, r_gran, r_steps, (double*)ctx->spec.p));
-  std::vector<double> pr((size_t)r_steps), pv((size_t)v_steps);
-  ISAC_TRY(copy_d2h(ctx, pr.data(), ctx->spec.p, sizeof(double) * (size_t)r_steps));
-  ISAC_HIP(hipStreamSynchronize(ctx->stream));
-  // velocity scan  av = exp(2j*pi*T*2*v*m/lambda), Uvs = conj(V(:,top))                       :93,:104-108
-  const double coef_v = ((2.0 * M_PI) * mp->t_sri) * 2.0;
-  ISAC_TRY(isac_music2d_scan(ctx, (const c64*)ctx->eig_v.p, L, L, d_top, Lu, 1, coef_v, lambda, -mp->v_max / 2.0, v_gran, v_steps,
-                             (double*)ctx->spec.p));
-  ISAC_TRY(copy_d2h(ctx, pv.data(), ctx->spec.p, sizeof(double) * (size_t)v_steps));
-  ISAC_HIP(hipStreamSynchronize(ctx->stream));
+  std::vector<double> pr((size_t)r_steps, 1.0), pv((size_t)v_steps, 1.0);
+  if (!r_empty) {
+    ISAC_TRY(isac_music2d_signal_vectors(ctx, d_h, K, L, d_top, Lu, d_U));
+    // range scan  ar = exp(-2j*pi*scs*2*r*n/c)                                              :92,:98-102
+    const double coef_r = ((-2.0 * M_PI) * mp->scs_hz) * 2.0;
+    ISAC_TRY(isac_music2d_scan(ctx, d_U, K, K, nullptr, Lu, 0, coef_r, c0, 0.0, r_gran, r_steps, (double*)ctx->spec.p));
+    ISAC_TRY(copy_d2h(ctx, pr.data(), ctx->spec.p, sizeof(double) * (size_t)r_steps));
+    ISAC_HIP(hipStreamSynchronize(ctx->stream));
+  }
+  if (!v_empty) {
+    // velocity scan  av = exp(2j*pi*T*2*v*m/lambda), Uvs = conj(V(:,top))                     :93,:104-108
+    const double coef_v = ((2.0 * M_PI) * mp->t_sri) * 2.0;
+    ISAC_TRY(isac_music2d_scan(ctx, (const c64*)ctx->eig_v.p, L, L, d_top, Lu, 1, coef_v, lambda, -mp->v_max / 2.0, v_gran, v_steps,
+                               (double*)ctx->spec.p));
+    ISAC_TRY(copy_d2h(ctx, pv.data(), ctx->spec.p, sizeof(double) * (size_t)v_steps));
+    ISAC_HIP(hipStreamSynchronize(ctx->stream));
+  }
   to_db(pr);                                                            // :111-117
   to_db(pv);
   const std::vector<int> rl = findpeaks_desc(pr, Lsig), vl = findpeaks_desc(pv, Lsig);                          // :120-121
@@ -451,5 +460,19 @@ extern "C" int isac_music2d_dev(isac_ctx* ctx, const isac_est_params* ep, const 
   out->n_vel = (int)std::min<size_t>(vl.size(), ISAC_MAX_EST);
   for (int i = 0; i < out->n_rng; ++i) out->rng_est[i] = rl[(size_t)i] * r_gran;                               // :122
   for (int i = 0; i < out->n_vel; ++i) out->vel_est[i] = vl[(size_t)i] * v_gran - mp->v_max / 2.0;             // :123
+  ctx->last.range_db = std::move(pr);                                   // isac_music2d_get_spectra
+  ctx->last.velocity_db = std::move(pv);
+  return ISAC_OK;
+}
+
+extern "C" int isac_music2d_get_spectra(isac_ctx* ctx, double* pr_db, int32_t cap_r, double* pv_db, int32_t cap_v, int32_t n_steps[2]) {
+  ISAC_ENTER(ctx);
+  const int nr = (int)ctx->last.range_db.size(), nv = (int)ctx->last.velocity_db.size();
+  if (nr == 0 && nv == 0) return fail(ctx, ISAC_ERR_INVALID_ARG, "no music2D has completed on this context");
+  if (n_steps) { n_steps[0] = nr; n_steps[1] = nv; }
+  if (!pr_db && !pv_db) return ISAC_OK;
+  if ((pr_db && cap_r < nr) || (pv_db && cap_v < nv)) return fail(ctx, ISAC_ERR_CAPACITY, "music2D spectrum larger than capacity");
+  if (pr_db) std::copy(ctx->last.range_db.begin(), ctx->last.range_db.end(), pr_db);
+  if (pv_db) std::copy(ctx->last.velocity_db.begin(), ctx->last.velocity_db.end(), pv_db);
   return ISAC_OK;
 }

@@ -104,6 +104,7 @@ struct Fft2dLast {  // introspection of the last fft2D call: the host copies (th
   std::vector<double> det_pow;
   std::vector<int32_t> ant_off;     // [A+1]
   std::vector<double> spectrum_db;  // dB spectrum of the context's last ULA azimuth scan, whichever call ran it (doa_readout, isac_music2d_dev); empty: none (isac_fft2d_get_music_spectrum)
+  std::vector<double> range_db, velocity_db;  // dB range [r_steps] / velocity [v_steps] spectra of the context's last COMPLETED isac_music2d_dev; both empty: none (isac_music2d_get_spectra)
 };
 
 struct RangeCache {  // range rows pre-computed by the fused monoStaticSensing call for the next fft2D

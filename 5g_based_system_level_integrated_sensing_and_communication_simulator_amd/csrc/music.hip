@@ -347,37 +347,66 @@ __global__ __launch_bounds__(256) void signal_vectors_kernel(const c64* __restri
   U[n + (long long)K * i] = mk(acc.re / nrm, acc.im / nrm);
 }
 
-// P(x) = 1 / (N - sum_i |u_i^H a(x)|^2),  a(x)[n] = exp(j * ((coef * x) * n) / den)   (music2D.m:92-93,98-108)
-// conj_u = 0: y_i = sum_n conj(U[n,i]) a[n] (range, U = Urs);  conj_u = 1: y_i = sum_n U[n,i] a[n] (velocity, Uvs = conj(V))
+// Sum of v over the 256 threads of the block, in every thread (s_red: 4 doubles, free again on return)
+__device__ inline double music2d_block_sum(double v, double* s_red) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return s_red[0] + s_red[1] + s_red[2] + s_red[3];
+}
+
+// P(x) = 1 / || a(x) - sum_i e_i (e_i^H a(x)) ||^2,  a(x)[n] = exp(j * ((coef * x) * n) / den)   (music2D.m:92-93,98-108)
+// = 1 / (a^H Un Un^H a) for the orthonormal signal vectors e_i: the residual is summed term by term, so a denominator 1e-10 N (a target on the scan grid
+// at 100 dB) keeps its digits; N - sum_i |e_i^H a|^2, the same number, would lose them.
+// conj_u = 0: e_i = U[:, i] (range, U = Urs);  conj_u = 1: e_i = conj(U[:, cols[i]]) (velocity, Uvs = conj(V)).  Dynamic LDS: 4 + 2 Lsig doubles.
+constexpr int kMusic2dChunk = 4;     // projections formed per pass over a(x)
 __global__ __launch_bounds__(256) void music2d_scan_kernel(const c64* __restrict__ U, int N, int ldU, const int* __restrict__ cols,
                                                            int Lsig, int conj_u, double coef, double den, double x0, double dx,
                                                            double* __restrict__ p_out) {
-  __shared__ double s_red[4];
+  extern __shared__ __align__(16) double s_m2d[];
+  double* s_red = s_m2d;
+  c64* s_y = reinterpret_cast<c64*>(s_m2d + 4);      // y_i = e_i^H a(x)
   const double x = x0 + dx * (double)blockIdx.x;
   const double a = coef * x;
-  double tot = 0.0;
-  for (int i = 0; i < Lsig; ++i) {
-    const c64* u = U + (long long)ldU * (cols ? cols[i] : i);
-    c64 y = mk(0.0, 0.0);
+  for (int i0 = 0; i0 < Lsig; i0 += kMusic2dChunk) {
+    const int nb = min(kMusic2dChunk, Lsig - i0);
+    const c64* u[kMusic2dChunk];
+    c64 y[kMusic2dChunk];
+#pragma unroll
+    for (int j = 0; j < kMusic2dChunk; ++j) {
+      const int i = i0 + min(j, nb - 1);
+      u[j] = U + (long long)ldU * (cols ? cols[i] : i);
+      y[j] = mk(0.0, 0.0);
+    }
     for (int n = threadIdx.x; n < N; n += blockDim.x) {
       double s, c;
       sincos((a * (double)n) / den, &s, &c);
-      const c64 un = conj_u ? u[n] : conj(u[n]);
-      y = fma(un, mk(c, s), y);
+#pragma unroll
+      for (int j = 0; j < kMusic2dChunk; ++j)
+        if (j < nb) y[j] = fma(conj_u ? u[j][n] : conj(u[j][n]), mk(c, s), y[j]);
     }
-    double yr = y.re, yi = y.im;
-    for (int o = 32; o > 0; o >>= 1) { yr += __shfl_down(yr, o); yi += __shfl_down(yi, o); }
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = yr;
-    __syncthreads();
-    yr = s_red[0] + s_red[1] + s_red[2] + s_red[3];
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = yi;
-    __syncthreads();
-    yi = s_red[0] + s_red[1] + s_red[2] + s_red[3];
-    tot += yr * yr + yi * yi;
+#pragma unroll
+    for (int j = 0; j < kMusic2dChunk; ++j) {
+      if (j >= nb) break;                                        // (nb is uniform over the block)
+      const double yr = music2d_block_sum(y[j].re, s_red), yi = music2d_block_sum(y[j].im, s_red);
+      if (threadIdx.x == 0) s_y[i0 + j] = mk(yr, yi);
+    }
   }
-  if (threadIdx.x == 0) p_out[blockIdx.x] = 1.0 / ((double)N - tot);
+  __syncthreads();
+  double q = 0.0;
+  for (int n = threadIdx.x; n < N; n += blockDim.x) {
+    double s, c;
+    sincos((a * (double)n) / den, &s, &c);
+    c64 r = mk(c, s);
+    for (int i = 0; i < Lsig; ++i) {
+      const c64 un = U[(long long)ldU * (cols ? cols[i] : i) + n];
+      r = r - (conj_u ? conj(un) : un) * s_y[i];
+    }
+    q += r.re * r.re + r.im * r.im;
+  }
+  q = music2d_block_sum(q, s_red);
+  if (threadIdx.x == 0) p_out[blockIdx.x] = 1.0 / q;
 }
 
 }  // namespace isac
@@ -436,7 +465,7 @@ int isac_music2d_signal_vectors(isac_ctx* ctx, const c64* d_h, int K, int Ls, co
 }
 int isac_music2d_scan(isac_ctx* ctx, const c64* d_U, int N, int ldU, const int* d_cols, int Lsig, int conj_u, double coef, double den,
                       double x0, double dx, int n_steps, double* d_p) {
-  hipLaunchKernelGGL(music2d_scan_kernel, dim3(n_steps), dim3(256), 0, ctx->stream, d_U, N, ldU, d_cols, Lsig, conj_u, coef, den, x0, dx,
+  hipLaunchKernelGGL(music2d_scan_kernel, dim3(n_steps), dim3(256), sizeof(double) * (4 + 2 * (size_t)Lsig), ctx->stream, d_U, N, ldU, d_cols, Lsig, conj_u, coef, den, x0, dx,
                      d_p);
   ISAC_HIP(hipGetLastError());
   return ISAC_OK;

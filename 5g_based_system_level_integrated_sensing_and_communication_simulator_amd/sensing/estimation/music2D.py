@@ -11,9 +11,10 @@ from ... import _lib as L
 from .._marshal import est_block
 
 
-def music2D(rdrEstParams, bsParams, rxGrid, txGrid, *, ctx=None):
+def music2D(rdrEstParams, bsParams, rxGrid, txGrid, *, ctx=None, return_debug=False):
     """estResults = music2D(rdrEstParams, bsParams, rxGrid, txGrid) -> .aziEst .eleEst .rngEst .velEst (+ .L).
-    ``bsParams.scs`` in kHz (music2D.m:34)."""
+    ``bsParams.scs`` in kHz (music2D.m:34).  ``return_debug`` adds a second value with the spectra the estimates were read from: ``PrdB`` / ``PvdB``
+    (music2D.m:113,117; ``ctx.music2d_spectra()``) and the values they are scanned at, ``rGrid`` = (r-1) 0.5 (:99) and ``vGrid`` = (v-1) 0.5 - vMax/2 (:105)."""
     dev = isinstance(rxGrid, L.DeviceArray)
     ctx = ctx or (rxGrid.ctx if dev else L.default_context())
     K, Ls, A = (rxGrid.shape if dev else np.shape(rxGrid))
@@ -24,5 +25,9 @@ def music2D(rdrEstParams, bsParams, rxGrid, txGrid, *, ctx=None):
     ep = est_block(rdrEstParams)
     res = L.EstResult()
     ctx.check(ctx.lib.isac_music2d_dev(ctx.handle, C.byref(ep), C.byref(mp), d_rx, d_tx, K, Ls, A, C.byref(res)))
-    return SimpleNamespace(aziEst=np.array(res.azi_est[: res.n_azi]), eleEst=np.array(res.ele_est[: res.n_azi]),
-                           rngEst=np.array(res.rng_est[: res.n_rng]), velEst=np.array(res.vel_est[: res.n_vel]), L=int(res.num_dets))
+    est = SimpleNamespace(aziEst=np.array(res.azi_est[: res.n_azi]), eleEst=np.array(res.ele_est[: res.n_azi]),
+                          rngEst=np.array(res.rng_est[: res.n_rng]), velEst=np.array(res.vel_est[: res.n_vel]), L=int(res.num_dets))
+    if not return_debug:
+        return est
+    pr, pv = ctx.music2d_spectra()
+    return est, SimpleNamespace(PrdB=pr, PvdB=pv, rGrid=np.arange(pr.size) * 0.5, vGrid=np.arange(pv.size) * 0.5 - mp.v_max / 2.0)

@@ -437,6 +437,17 @@ typedef struct {
 int isac_music2d_dev(isac_ctx* ctx, const isac_est_params* ep, const isac_music2d_params* mp,
                      const isac_c64* d_rx_grid, const isac_c64* d_tx_grid,
                      int32_t K, int32_t L, int32_t A, isac_est_result* out);
+/* The two pseudo-spectra of the context's last COMPLETED isac_music2d_dev in dB, as music2D.m:111-117 leaves them (20 log10(|P| / max |P|)): the range
+ * spectrum pr_db [r_steps], point i at range 0.5 i metres, r_steps = floor((r_max + 1) / 0.5) (music2D.m:45,99), and the velocity spectrum pv_db [v_steps],
+ * point i at 0.5 i - v_max / 2 m/s, v_steps = floor((v_max + 1) / 0.5) (:46,105).  Query, then fetch: n_steps (may be NULL) receives {r_steps, v_steps};
+ * with both buffers NULL nothing else happens; a buffer that is not NULL receives its spectrum and needs its capacity (cap_r, cap_v, in doubles) to reach
+ * the length, ISAC_ERR_CAPACITY otherwise (nothing is written then).  ISAC_ERR_INVALID_ARG while no music2D has completed on the context: a new context,
+ * after an isac_music2d_dev that failed (a refused UPA, bad arguments: every isac_music2d_dev drops the previous call's spectra when it starts), and after
+ * isac_ctx_reserve's dry run -- the rule of isac_fft2d_get_music_spectrum.  Other calls (fft2D, the stand-alone DoA calls) leave the spectra alone.
+ * An EMPTY NOISE SPACE: with L = num_dets >= nSym the velocity noise vectors Uvn of music2D.m:88 have no column (L >= nSc: Urn, :81), the reference divides
+ * by zero and findpeaks sees NaN.  The library gives that spectrum the convention of the ULA scan (music.m:28 with numDets >= nAnts): flat 0 dB, no
+ * estimate (n_vel / n_rng = 0).  With nSym <= L < nSc the range spectrum uses the nSym signal vectors that H has. */
+int isac_music2d_get_spectra(isac_ctx* ctx, double* pr_db, int32_t cap_r, double* pv_db, int32_t cap_v, int32_t n_steps[2]);
 
 /* Hermitian eigendecomposition used by MUSIC (eig(Ra), music.m:19): ascending real
  * eigenvalues w [A], orthonormal eigenvectors V [A x A] column-major.  One-workgroup
