@@ -22,6 +22,7 @@
 #include "isac_internal.hpp"
 #include "fft_lds.hpp"
 #include "echo_dev.hpp"
+#include "beam_window.hpp"
 
 namespace isac {
 
@@ -121,33 +122,66 @@ __global__ __launch_bounds__(256) void coef_kernel(const c64* __restrict__ beam,
 // The beam-sum that writes the coefficient vectors itself (the spectral route of isac_mono_static_sensing_fused_dev, one or two LoS targets): that route reads neither beam
 // nor phase_rx, and coef_kernel was a launch of its own on the serial chain of the CPI -- 12-13 us plus its gap, for ~300 VALU instructions per sample that fit in the shadow
 // of this kernel's loads.  The thread that has summed sample u of target q holds beam_q[u] = the only input of coef_q[u + d_q] (coef_value above: the bits of coef_kernel);
-// it also writes the zero of coef_q[u] for u < d_q, so every element of coef [QT x T] is written exactly once; samples with u + d_q >= T are dropped.
+// a sample before the waveform (u < 0, beam_window.hpp) stands for the zero of coef_q[u + d_q]; samples with u + d_q >= T are dropped.
+//
+// It sums only the samples the demodulation windows need (beam_window.hpp: nfft + d_max - d_min per symbol, nothing of the cyclic prefix in between -- 6.6 % of the 1 GB at
+// the bench shape), so the elements of coef OUTSIDE every window stay unwritten: every element some window reads is written exactly once.  The workgroups are long-lived as
+// in beamsum_kernel, walking units (symbol, 256 samples of its range) instead of blocks of [0, T); a wave whose 64 samples lie outside its symbol's share loads nothing.
+// Measured (profiles/r08_ab_parent_vs_pr.txt): alone on the GPU the kernel takes what the walk over [0, T) took, 177-180 us -- the bytes saved buy no isolated time; with other
+// CPIs' kernels beside it the pipelined rate gains 0.8-1.3 % from the walk and 1.1-1.9 % more from the upload that is gone (below).
+//
+// The steering vectors come in the argument block where they fit (steer == nullptr: A QT <= kSteerArgMax; read by address from the constant argument segment, never copied
+// to private memory), which takes the staged upload -- a blit kernel of 4-6 us at the head of every CPI's serial chain -- off this route; workgroup 0 then writes both halves
+// of ctx->steer ([QT x A] and its transpose) for the kernels behind it in the stream.
 template <int QT>
 struct CoefTargets {
   TargetDesc t[QT];
 };
+constexpr int kSteerArgMax = 128;                   // 2 KB of the 4 KB argument block
+struct SteerArg {
+  c64 v[kSteerArgMax];
+};
 template <int QT, int UNROLL>
 __global__ __launch_bounds__(256) void beamsum_coef_kernel(const c64* __restrict__ tx, long long T, int A,
-                                                           const c64* __restrict__ steer /* [A x QT] compacted LoS */,
-                                                           CoefTargets<QT> tab, double w /* (2*pi)*fc */, double Ts,
+                                                           const c64* __restrict__ steer /* [A x QT] compacted LoS, or nullptr: steer_arg */,
+                                                           const SteerArg steer_arg, c64* __restrict__ steer_out /* [2 x A x QT], written when steer == nullptr */,
+                                                           BeamWindow bw, CoefTargets<QT> tab, double w /* (2*pi)*fc */, double Ts,
                                                            c64* __restrict__ coef /* [QT x T] */) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   c64* s_steer = reinterpret_cast<c64*>(smem_raw);
-  for (int i = threadIdx.x; i < A * QT; i += blockDim.x) s_steer[i] = steer[i];
+  if (steer) {
+    for (int i = threadIdx.x; i < A * QT; i += blockDim.x) s_steer[i] = steer[i];
+  } else {
+    for (int i = threadIdx.x; i < A * QT; i += blockDim.x) {
+      const c64 v = steer_arg.v[i];
+      s_steer[i] = v;
+      if (blockIdx.x == 0) {
+        const int q = i / A, a = i - q * A;
+        steer_out[i] = v;
+        steer_out[A * QT + a * QT + q] = v;          // row r of the transpose holds a_q[r] at r QT + q
+      }
+    }
+  }
   __syncthreads();
-  for (long long t0 = (long long)blockIdx.x * 256; t0 < T; t0 += (long long)gridDim.x * 256) {
-    const long long u = t0 + threadIdx.x;
-    const long long uc = u < T ? u : T - 1;                            // unconditional loads (clamped), conditional stores
+  const int n_units = (int)bw_units(bw);
+  for (int k = blockIdx.x; k < n_units; k += gridDim.x) {
+    const int l = k / bw.units_per_symbol, j = k - l * bw.units_per_symbol;
+    const long long lo = bw_first(bw, l), hi = bw_range_end(bw, l);
+    const long long u = bw_sample(bw, l, j, threadIdx.x);
+    const bool mine = u >= lo && u < hi;
+    if (!__any(mine)) continue;                                        // (wave-uniform; no barrier in this loop)
+    long long uc = u < lo ? lo : u < hi ? u : hi - 1;                  // unconditional loads, clamped into the symbol's share (no line beyond it) and into [0, T);
+    uc = uc < 0 ? 0 : uc < T ? uc : T - 1;                             // conditional stores
     c64 acc[QT];
     beam_sample<QT, UNROLL>(tx + uc, T, A, s_steer, acc);
+    if (!mine) continue;
 #pragma unroll
     for (int q = 0; q < QT; ++q) {
-      const long long d = tab.t[q].shift, t = u + d;
+      const long long t = u + tab.t[q].shift;
       c64* cq = coef + (long long)q * T;
-      if (u < d && u < T) cq[u] = mk(0.0, 0.0);
-      if (u < T && t >= 0 && t < T) {
+      if (t >= 0 && t < T) {
         const double tt = (double)t * Ts;
-        cq[t] = coef_value(acc[q], t, tab.t[q], w, Ts, tt, rx_phase(w, tt));
+        cq[t] = u < 0 ? mk(0.0, 0.0) : coef_value(acc[q], t, tab.t[q], w, Ts, tt, rx_phase(w, tt));
       }
     }
   }
@@ -599,10 +633,11 @@ extern "C" int isac_ofdm_waveform_length(const isac_carrier* carrier, int32_t L,
 }
 
 // Everything basicRadarChannel needs before samples can be synthesised: LoS compaction,
-// beam-sums, coefficient vectors.  Leaves coef [Q x T], phase_rx [T], steer_rq [A x Q] in ctx.  coef_only: the caller reads coef and steer alone -- with one or two LoS targets
-// the beam-sum then writes coef itself (beamsum_coef_kernel) and beam / phase_rx are left as they were.
+// beam-sums, coefficient vectors.  Leaves coef [Q x T], phase_rx [T], steer_rq [A x Q] in ctx.  coef_only != nullptr: the caller reads steer and, of coef, the demodulation
+// windows of that carrier alone -- with one or two LoS targets the beam-sum then writes coef itself (beamsum_coef_kernel), beam / phase_rx are left as they were, and so is
+// every element of coef outside those windows (beam_window.hpp).
 static int prepare_echo(isac_ctx* ctx, const c64* d_tx, long long T, const isac_radar_channel_params* rp,
-                        const uint8_t* los, int* q_out, bool coef_only = false) {
+                        const uint8_t* los, int* q_out, const OfdmGeom* coef_only = nullptr) {
   if (!d_tx || !rp || !los) return fail(ctx, ISAC_ERR_INVALID_ARG, "NULL argument");
   if (T <= 0 || rp->n_ants <= 0 || rp->n_targets < 0) return fail(ctx, ISAC_ERR_INVALID_ARG, "bad T / n_ants / n_targets");
   ctx->lazy.valid = false;                          // steer / coef / dgrid below are the inputs of a lazy echo grid of an earlier call: overwritten now
@@ -638,7 +673,9 @@ static int prepare_echo(isac_ctx* ctx, const c64* d_tx, long long T, const isac_
   ISAC_TRY(ensure(ctx, ctx->coef, sizeof(c64) * (size_t)Q * T));
   ISAC_TRY(ensure(ctx, ctx->phase_rx, sizeof(c64) * (size_t)T));
   c64* d_steer_aq = (c64*)ctx->steer.p;
-  {
+  const bool one_launch = coef_only && Q <= 2;      // beamsum_coef_kernel
+  const bool steer_by_arg = one_launch && A * Q <= kSteerArgMax;   // ... which then takes the steering vectors as an argument and writes ctx->steer itself
+  if (!steer_by_arg) {
     // pinned staging ring: the upload is truly asynchronous
     const size_t bytes = sizeof(c64) * (size_t)A * Q * 2;
     void* hst = nullptr;
@@ -652,12 +689,22 @@ static int prepare_echo(isac_ctx* ctx, const c64* d_tx, long long T, const isac_
   const unsigned gbs = (unsigned)std::min<long long>(gb, 1024);        // beam-sum: long-lived workgroups (sweep: profiles/r04_beamsum_sweep.txt)
   timeline_mark(ctx, 0, ctx->stream);
   const double w = two_pi * rp->fc;                 // 2j*pi*fc  :30,:73
-  if (coef_only && Q <= 2) {                        // one launch: the beam-sum writes coef itself; beam and phase_rx stay unwritten (the caller reads neither)
+  if (one_launch) {                                 // the beam-sum writes coef itself, inside the demodulation windows; beam and phase_rx stay unwritten (the caller reads neither)
+    long long d_min = tab.t[0].shift, d_max = d_min;
+    for (int q = 1; q < Q; ++q) { d_min = std::min(d_min, tab.t[q].shift); d_max = std::max(d_max, tab.t[q].shift); }
+    const OfdmGeom& g = *coef_only;
+    constexpr long long kSpan = 1LL << 38;          // T + d_max in 256-sample units is an int
+    if (T >= kSpan || d_max >= kSpan || d_min <= -kSpan) return fail(ctx, ISAC_ERR_CAPACITY, "waveform or target delay beyond the beam-sum's unit count");
+    const BeamWindow bw = beam_window(g.nfft, g.cp_base, g.cp_long, g.sym_per_half, whole_symbols(g, T), T, d_min, d_max);
+    const unsigned gbu = (unsigned)std::max<long long>(1, std::min<long long>(bw_units(bw), 1024));   // long-lived workgroups, as above
+    SteerArg sa{};
+    if (steer_by_arg) std::memcpy(sa.v, steer_aq.data(), sizeof(c64) * (size_t)A * Q);
     auto launch = [&](auto qc) {
       constexpr int QT = decltype(qc)::value;
       CoefTargets<QT> ct;
       for (int q = 0; q < QT; ++q) ct.t[q] = tab.t[q];
-      hipLaunchKernelGGL((beamsum_coef_kernel<QT, 32>), dim3(gbs), dim3(256), sizeof(c64) * A * QT, ctx->stream, d_tx, T, A, (const c64*)d_steer_aq, ct, w, Ts, (c64*)ctx->coef.p);
+      hipLaunchKernelGGL((beamsum_coef_kernel<QT, 32>), dim3(gbu), dim3(256), sizeof(c64) * A * QT, ctx->stream, d_tx, T, A, steer_by_arg ? nullptr : (const c64*)d_steer_aq, sa,
+                         d_steer_aq, bw, ct, w, Ts, (c64*)ctx->coef.p);
     };
     if (Q == 1) launch(std::integral_constant<int, 1>{});
     else launch(std::integral_constant<int, 2>{});
@@ -740,7 +787,7 @@ static int launch_demod(isac_ctx* ctx, const OfdmGeom& g, long long T, int A, in
 static int spectral_prepare(isac_ctx* ctx, const c64* d_tx, long long T, const isac_radar_channel_params* rp, const uint8_t* los,
                             const OfdmGeom& g, int* q_out, int* l_whole_out, bool coef_only = false) {
   int Q = 0;
-  ISAC_TRY(prepare_echo(ctx, d_tx, T, rp, los, &Q, coef_only));                      // monoStaticSensing.m:13
+  ISAC_TRY(prepare_echo(ctx, d_tx, T, rp, los, &Q, coef_only ? &g : nullptr));       // monoStaticSensing.m:13
   const int L_whole = whole_symbols(g, T);
   if (L_whole <= 0) return fail(ctx, ISAC_ERR_SHORT_WAVEFORM, "waveform shorter than one OFDM symbol");
   ISAC_TRY(ensure(ctx, ctx->dgrid, sizeof(c64) * (size_t)g.n_sc * L_whole * Q));

@@ -17,6 +17,7 @@
 
 #include "../../include/isac.h"
 #include "cut_window.hpp"
+#include "ofdm_symbol.hpp"
 
 namespace isac {
 
@@ -219,7 +220,7 @@ struct isac_ctx {
   std::string err;
   std::map<const void*, size_t> lds_allowed;                        // kernel -> dynamic LDS bytes enabled on this context's device
   std::map<isac::TableKey, isac::DevBuf> tables;                    // cached device tables: made on first use, kept until the context goes
-  // scratch
+  // scratch  (coef [Q x T]: after the fused spectral route with one or two LoS targets only the demodulation windows hold values -- echo.hip prepare_echo, beam_window.hpp)
   isac::DevBuf beam, coef, phase_rx, steer, dgrid, ymid, pwin, flags, det_cut, det_pow, det_cnt, cov_part, cov,
       eig_w, eig_v, eig_scratch, spec, misc, stage_a, stage_b, stage_c, cdl_par, seg, cdl_h, rxfe_tab;
   isac::PinnedBuf pinned;       // results of isac_fft2d_submit* (read by isac_fft2d_collect) -- no other entry point may touch it
@@ -454,29 +455,7 @@ inline int ctx_n_cus(isac_ctx* ctx, int* n_cus) {
   return ISAC_OK;
 }
 
-// ---------------------------------------------------------------- OFDM numerology (TS 38.211 5.3.1)
-struct Numerology {
-  int nfft, mu, cp_base, cp_long, sym_per_half;  // long CP every sym_per_half symbols
-};
-inline Numerology numerology(int nfft, int scs_khz) {
-  Numerology n{};
-  n.nfft = nfft;
-  n.mu = 0;
-  for (int s = scs_khz / 15; s > 1; s >>= 1) n.mu++;
-  double scale = nfft / 2048.0;
-  n.cp_base = (int)std::lround(144.0 * scale);
-  n.cp_long = n.cp_base + (int)std::lround(16.0 * scale * (1 << n.mu));
-  n.sym_per_half = 7 * (1 << n.mu);
-  return n;
-}
-__host__ __device__ inline int cp_of_symbol(int l, int cp_base, int cp_long, int sym_per_half) {
-  return (l % sym_per_half) == 0 ? cp_long : cp_base;
-}
-// start sample (of the CP) of symbol l
-__host__ __device__ inline long long symbol_start(int l, int nfft, int cp_base, int cp_long, int sym_per_half) {
-  long long n_long = (l + sym_per_half - 1) / sym_per_half;  // long-CP symbols among 0..l-1
-  return (long long)l * (nfft + cp_base) + n_long * (cp_long - cp_base);
-}
+// (OFDM numerology -- Numerology, numerology, cp_of_symbol, symbol_start: ofdm_symbol.hpp)
 
 // host-side launch geometry helper
 inline unsigned cdiv(long long a, long long b) { return (unsigned)((a + b - 1) / b); }
