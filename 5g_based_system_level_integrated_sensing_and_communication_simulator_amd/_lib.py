@@ -24,6 +24,7 @@ ISAC_CFAR_MAX_TRAIN = 1024
 TARGET_SW0, TARGET_SW1 = 0, 1                            # ISAC_TARGET_* (include/isac_cfar_mc.h)
 TARGET_MODELS = {"swerling0": TARGET_SW0, "swerling1": TARGET_SW1}
 ISAC_CFAR_MC_MAX_TRAIN = 128
+LAZY_COV_SPLIT, LAZY_COV_REGENERATE = 0, 1                   # ISAC_LAZY_COV_* (include/isac_lazy_cov.h)
 OPT_MUSIC_ROUTE, OPT_TAIL_FUSION, OPT_WIDE_ORDER, OPT_CDL_SHARE_SPECTRA, OPT_UPA_DOA = 0, 1, 2, 3, 4   # ISAC_OPT_* of isac_ctx_set_option
 
 STATUS_NAMES = {0: "OK", 1: "INVALID_ARG", 2: "HIP", 3: "NO_LOS", 4: "NO_DETECTION", 5: "CFAR_WINDOW",
@@ -237,6 +238,11 @@ PROTOTYPES_CFAR = {
 PROTOTYPES_CFAR_MC = {
     "isac_cfar_monte_carlo": (_INT, (_P, _ptr(CfarMethod), _I32, _F64, _I32, _P, _I32, _U64, _U64, _P, _P)),
 }
+# ... and include/isac_lazy_cov.h (tests/test_lazy_cov_abi_cpu.py pins it)
+PROTOTYPES_LAZY_COV = {
+    "isac_ctx_set_lazy_cov_route": (_INT, (_P, _I32)),
+    "isac_ctx_get_lazy_cov_route_used": (_INT, (_P, _P)),
+}
 
 
 def library_path() -> str:
@@ -263,7 +269,7 @@ def load():
             except Exception:
                 pass
         lib = C.CDLL(_LIB_PATH, mode=C.RTLD_GLOBAL)
-        for name, (restype, argtypes) in {**PROTOTYPES, **PROTOTYPES_ADDED, **PROTOTYPES_CFAR, **PROTOTYPES_CFAR_MC}.items():
+        for name, (restype, argtypes) in {**PROTOTYPES, **PROTOTYPES_ADDED, **PROTOTYPES_CFAR, **PROTOTYPES_CFAR_MC, **PROTOTYPES_LAZY_COV}.items():
             fn = getattr(lib, name)  # AttributeError here = ABI drift between isac.h and the .so
             fn.restype, fn.argtypes = restype, argtypes
         # the library writes whole structs into caller memory: version AND struct sizes must match this binding's mirrors
@@ -377,6 +383,17 @@ class Context:
     def set_music_route(self, route: int):
         """0 = MUSIC through the signal-subspace eigensolver (default), 1 = always the full eigendecomposition (ISAC_OPT_MUSIC_ROUTE)."""
         self.check(self.lib.isac_ctx_set_option(self.handle, OPT_MUSIC_ROUTE, int(route)))
+
+    def set_lazy_cov_route(self, route: int):
+        """isac_ctx_set_lazy_cov_route (include/isac_lazy_cov.h): LAZY_COV_SPLIT (0, default) = split covariance of a native lazy echo grid, the noise term beside the
+        beam-sum; LAZY_COV_REGENERATE (1) = the regenerating kernel.  Set before the fused monoStaticSensing call."""
+        self.check(self.lib.isac_ctx_set_lazy_cov_route(self.handle, int(route)))
+
+    def lazy_cov_route_used(self) -> int:
+        """The route this context's last covariance of a native lazy echo grid took (isac_ctx_get_lazy_cov_route_used); IsacError(INVALID_ARG) while there has been none."""
+        r = C.c_int32(-1)
+        self.check(self.lib.isac_ctx_get_lazy_cov_route_used(self.handle, C.byref(r)))
+        return int(r.value)
 
     def set_tail_fusion(self, on: bool):
         """True (default) = panel CFAR (antenna x 42-CUT-row workgroups) + per-antenna merge that also forms numDets, where the zone allows;

@@ -314,6 +314,21 @@ extern "C" int isac_ctx_set_option(isac_ctx* ctx, int32_t option, int32_t value)
   }
 }
 
+// include/isac_lazy_cov.h: the covariance route of a native lazy echo grid, read by the next isac_mono_static_sensing_fused_dev (echo.hip)
+extern "C" int isac_ctx_set_lazy_cov_route(isac_ctx* ctx, int32_t route) {
+  ISAC_ENTER(ctx);
+  if (route != ISAC_LAZY_COV_SPLIT && route != ISAC_LAZY_COV_REGENERATE) return fail(ctx, ISAC_ERR_INVALID_ARG, "lazy covariance route: ISAC_LAZY_COV_SPLIT or ISAC_LAZY_COV_REGENERATE");
+  ctx->lazy_cov_route = route;
+  return ISAC_OK;
+}
+
+extern "C" int isac_ctx_get_lazy_cov_route_used(isac_ctx* ctx, int32_t* route) {
+  ISAC_ENTER_NOJOIN(ctx);
+  if (!route || ctx->lazy_cov_used < 0) return fail(ctx, ISAC_ERR_INVALID_ARG, "no covariance of a native lazy echo grid on this context yet");
+  *route = ctx->lazy_cov_used;
+  return ISAC_OK;
+}
+
 // Several contexts on ONE pair of streams: a context is then a set of buffers / scratch, and the device executes the calls of all of them
 // in submission order -- the wide kernels (beam-sum, fused echo + range, covariance with ISAC_OPT_WIDE_ORDER) one after the other on the main
 // stream, never side by side, the narrow ones of each CPI on the second stream underneath.

@@ -10,9 +10,11 @@
 // k-steps; the k index is only a summation label, so no transposition is needed.
 // Per-workgroup partial tiles are reduced in a fixed order (deterministic).
 #include <algorithm>
+#include <cstring>
 #include <type_traits>
 #include "isac_internal.hpp"
 #include "echo_dev.hpp"
+#include "beam_stream.hpp"
 
 namespace isac {
 
@@ -802,6 +804,8 @@ __host__ __device__ constexpr int lazy_piece_gap(int i) {       // MFMA gap (0..
 }
 
 // The slab source of cov_lazy_kernel: thread -> (pair row gp, antennas ga and ga + 32) of every slab.
+// (CovNoiseBeamSource below restates its cursor, counter, mask, Philox and Box-Muller members: the noise field of the two routes is the same only while the two stay in step --
+//  tests/test_gpu_lazy_split.py compares them.  They are two texts because this struct's kernel is pinned instruction by instruction.)
 template <int QT>
 struct CovLazyGenerator {
   static constexpr int NB = 4;
@@ -926,6 +930,399 @@ __global__ __launch_bounds__(256, 2) void cov_lazy_kernel(LazyCovArgs a, long lo
   if (s_end > n_slabs) s_end = n_slabs;
   if (grp == 0) cov_staged_body<4, 0>(CovLazyGenerator<QT>(a, s_begin, s_end), phase, s_begin, s_end, blockIdx.x, part, lds);
   else cov_staged_body<4, 1>(CovLazyGenerator<QT>(a, s_begin, s_end), phase, s_begin, s_end, blockIdx.x, part, lds);
+}
+
+// ---------------------------------------------------------------- split lazy covariance: the noise term, with the beam-sum streamed beside it
+// With G[n, r] = sum_q a_q[r] d_q[n] + sig w[n, r] (n = (k, l), the lazy echo grid above) the covariance Ra[a, b] = (1/N) sum_n conj(G[n, a]) G[n, b] is
+//     N Ra = sig^2 M  +  sig sum_q ( conj(a_q[a]) c_q[b] + conj(c_q[a]) a_q[b] )  +  sum_pq conj(a_p[a]) H_pq a_q[b],
+//     M[a, b] = sum_n conj(w[n, a]) w[n, b],   c_q[r] = sum_n w[n, r] conj(d_q[n]),   H_pq = sum_n conj(d_p[n]) d_q[n].
+// M is the whole MFMA bulk and depends on the seed and the shape alone -- not on the waveform, D or the steering vectors -- so it can run at the HEAD of the CPI, in the kernel
+// that streams txWaveform for the beam-sum: cov_noise_beam_kernel is cov_lazy_kernel with the synthesis taken out of the generator (the UNIT noise value, masked, goes into the
+// LDS image; same slab order, pair rows, antenna and half masks, so the same field elements enter the sum) and the beam-sum's loads and folds in the MFMA gaps instead
+// (beam_stream.hpp: the most HBM-bound and the most MFMA-bound kernel of the CPI, each idle in what the other needs, in one instruction stream).  c_q comes from the range
+// kernel, which holds w and d in registers (echo_range_xc_kernel, echo.hip; two LoS targets: cov_cross_kernel below); cov_assemble_kernel below puts the three terms together.
+struct NoiseBeamArgs {
+  const c64* tx;              // [T x A]
+  const c64* steer;           // [A x QT] compacted LoS columns on the device, or nullptr: the argument block
+  c64* steer_out;             // ctx->steer [2 x A x QT]: written by workgroup 0 when steer == nullptr
+  c64* beam;                  // [QT x T]: written inside the BeamWindow's ranges
+  long long T;
+  unsigned long long seed;
+  int K, L_out, A, s_col;
+  BeamWindow bw;
+};
+constexpr int kBeamSteerPitch = 72;                             // steering image per target: zero from A on (>= kBeamStreamLoads * bs_steps_per_unit(64))
+// One unit of a workgroup's walk, relative to `base` (the first sample of the unit's 256, bw_sample): thread i sums sample base + i, or base + i + W when i < d_s (the
+// threads in front of the symbol's range take the samples behind its last unit); it owns the sample when d_lo <= i' < d_hi and loads at i' clamped into [c_lo, c_hi].
+// An idle entry loads beyond the descriptors and owns nothing.
+struct BeamUnitEntry {
+  unsigned base16;            // byte offset of sample `base` inside an antenna column (mod 2^32)
+  int d_s, d_lo, d_hi, c_lo, c_hi, pad0, pad1;
+};
+static_assert(sizeof(BeamUnitEntry) == 32, "two 16-byte LDS reads");
+__device__ __forceinline__ BeamUnitEntry beam_unit_entry(const BeamWindow& bw, long long k, bool active) {
+  BeamUnitEntry e{kCovOobOffset, 0, 0, 0, 0, 0, 0, 0};
+  if (!active) return e;
+  const int l = (int)(k / bw.units_per_symbol), j = (int)(k - (long long)l * bw.units_per_symbol);
+  const long long s = bw_range_start(bw, l), base = bw_floor_line(s) + (long long)j * kBeamUnit;
+  long long lo = bw_first(bw, l), hi = bw_range_end(bw, l);
+  if (lo < 0) lo = 0;                                           // samples before the waveform have no beam-sum (their coefficient is the zero coef_window_kernel writes)
+  const long long span = (long long)(bw.units_per_symbol + 2) * kBeamUnit;
+  auto rel = [&](long long x) { const long long d = x - base; return (int)(d < -span ? -span : d > span ? span : d); };
+  e.d_s = rel(s);
+  if (hi > lo) {
+    e.base16 = (unsigned)((unsigned long long)base * sizeof(c64));
+    e.d_lo = e.c_lo = rel(lo);
+    e.d_hi = rel(hi);
+    e.c_hi = rel(hi - 1);
+  }
+  return e;
+}
+
+// The slab source of cov_noise_beam_kernel: the unit noise of CovLazyGenerator's slabs (thread -> pair row gp, antennas ga and ga + 32) plus the beam pieces.  Per slab step
+// 27 pieces sit in the 30 MFMA gaps: the generator's 18 (counter set-up + 10 Philox rounds, 4 Box-Muller transforms, 4 x (widen + mask + LDS store)) and 9 of the beam-sum --
+// two folds of the six values loaded a step ago (antenna order, the additions of beam_sample: the bits beamsum_kernel produces), the store of a finished unit, the running
+// unit's offsets, six loads -- interleaved with the generator's first pieces.  The cursors (unit n of the table, step i of the unit) are wave-uniform; nothing branches.
+// init / round / bm / advance and the masks are CovLazyGenerator's, restated (that kernel is pinned instruction by instruction; a change there must be made here too).
+template <int QT>
+struct CovNoiseBeamSource {
+  static constexpr int NB = 4;
+  static constexpr int kGaps = 30;
+  static constexpr int kPieces = 27;
+  struct Cur { int l, sc; long long g; };
+  int gp, ga, K, s_col, g_lds0;
+  uint32_t key0, key1;
+  long long s_end;
+  bool ant_ok[2];
+  uint64_t colbase[2];
+  Cur cg;
+  uint32_t pc[2][4];
+  float wf[2][2][2];
+  bool v_half[2];
+  // beam pieces
+  const c64* tx;
+  long long T;
+  int A, spu, W;
+  __amdgpu_buffer_rsrc_t rs_beam[QT];
+  const c64* s_steer;                                // LDS [QT][kBeamSteerPitch]
+  const BeamUnitEntry* s_tab;                        // LDS [kBeamStreamTab]
+  int n, i, ip;                                      // unit of the table and step of the unit whose loads are issued; step of the loads in flight
+  bool fin;                                          // the loads in flight are the last of their unit
+  c64 v[kBeamStreamLoads];
+  c64 acc[QT];
+  unsigned voff, soff;
+  __device__ __forceinline__ CovNoiseBeamSource(const NoiseBeamArgs& a, long long s_begin, long long s_end_, const c64* s_steer_, const BeamUnitEntry* s_tab_)
+      : gp(threadIdx.x & 7), ga(threadIdx.x >> 3), K(a.K), s_col(a.s_col), key0((uint32_t)a.seed), key1((uint32_t)(a.seed >> 32)), s_end(s_end_), tx(a.tx), T(a.T), A(a.A),
+        spu(bs_steps_per_unit(a.A)), W(a.bw.units_per_symbol * kBeamUnit), s_steer(s_steer_), s_tab(s_tab_), n(0), i(0), ip(0), fin(false), voff(kCovOobOffset), soff(kCovOobOffset) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int ant = ga + 32 * j;
+      ant_ok[j] = ant < a.A;
+      colbase[j] = (uint64_t)gp + (uint64_t)kSpectralSlotsPerColumn * ((uint64_t)a.L_out * (uint64_t)ant);
+    }
+    g_lds0 = (ga >> 4) * kCovSlabBlk + gp * kCovPitch + ((ga & 15) ^ kCovSwizzle(gp));
+    Cur c; c.g = s_begin; c.l = (int)((unsigned)s_begin / (unsigned)s_col); c.sc = (int)((unsigned)s_begin - (unsigned)c.l * (unsigned)s_col);
+    cg = c;
+#pragma unroll
+    for (int q = 0; q < QT; ++q) { rs_beam[q] = buffer_of(a.beam + (long long)q * a.T, (unsigned)(a.T * (long long)sizeof(c64))); acc[q] = mk(0.0, 0.0); }
+#pragma unroll
+    for (int j = 0; j < kBeamStreamLoads; ++j) v[j] = mk(0.0, 0.0);
+  }
+  __device__ __forceinline__ void advance(Cur& c) const { ++c.g; if (++c.sc == s_col) { c.sc = 0; ++c.l; } }
+  __device__ __forceinline__ void init(const Cur& c) {          // (CovLazyGenerator::init)
+    const int k0 = ((c.sc >> 6) << 10) + ((c.sc & 63) << 3) + gp;
+    const bool in = c.g < s_end;
+    v_half[0] = in && k0 < K;
+    v_half[1] = in && k0 + 512 < K;
+    const uint32_t slot = (uint32_t)(((c.sc >> 6) << 9) + ((c.sc & 63) << 3));
+    const uint64_t slab = (uint64_t)slot + (uint64_t)kSpectralSlotsPerColumn * (uint64_t)c.l;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const uint64_t ctr = slab + colbase[j];
+      pc[j][0] = (uint32_t)ctr; pc[j][1] = (uint32_t)(ctr >> 32); pc[j][2] = kSpectralStream; pc[j][3] = 0u;
+    }
+  }
+  template <int R>
+  __device__ __forceinline__ void round() {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) philox4x32_round(pc[j], key0 + (uint32_t)R * 0x9E3779B9u, key1 + (uint32_t)R * 0xBB67AE85u);
+  }
+  template <int I>
+  __device__ __forceinline__ void bm() {
+    constexpr int j = I / 2, h = I % 2;
+    box_muller32_hw_f32(pc[j][2 * h], pc[j][2 * h + 1], wf[j][h][0], wf[j][h][1]);
+  }
+  template <int I>                                   // widen + mask + LDS store of unit noise element I = 2 j + h
+  __device__ __forceinline__ void emit(c64* img) {
+    constexpr int j = I / 2, h = I % 2;
+    const bool ok = v_half[h] && ant_ok[j];
+    const double re = (double)wf[j][h][0], im = (double)wf[j][h][1];
+    img[g_lds0 + 2 * j * kCovSlabBlk + 8 * h * kCovPitch] = mk(ok ? re : 0.0, ok ? im : 0.0);
+  }
+  template <int I>                                   // generator piece I of the slab at cursor cg, into image dst
+  __device__ __forceinline__ void gen(c64* dst) {
+    if constexpr (I == 0) { init(cg); round<0>(); }
+    else if constexpr (I < 10) round<I>();
+    else if constexpr (I < 14) bm<I - 10>();
+    else { emit<I - 14>(dst); if constexpr (I == 17) advance(cg); }
+  }
+  __device__ __forceinline__ void whole(c64* img) {
+    static_for<0, 18>([&](auto ic) { gen<decltype(ic)::value>(img); });
+  }
+  __device__ __forceinline__ void prologue(c64* __restrict__ lds) {   // slabs 0 and 1 generated outright into images 0 and 1
+    whole(lds);
+    whole(lds + NB * kCovSlabBlk);
+  }
+  __device__ __forceinline__ void begin_step(long long) {}
+  template <int J0>
+  __device__ __forceinline__ void fold() {           // values J0 .. J0 + 2 of the loads in flight, in antenna order
+    const c64* sp = s_steer + ip * kBeamStreamLoads;
+#pragma unroll
+    for (int j = J0; j < J0 + kBeamStreamLoads / 2; ++j)
+#pragma unroll
+      for (int q = 0; q < QT; ++q) acc[q] = fma(v[j], sp[q * kBeamSteerPitch + j], acc[q]);
+  }
+  __device__ __forceinline__ void finish() {         // behind the last fold of a unit: its sums go out (a store beyond the descriptor is dropped), the next unit starts from zero
+    const unsigned so = fin ? soff : kCovOobOffset;
+#pragma unroll
+    for (int q = 0; q < QT; ++q) {
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, acc[q]), rs_beam[q], (int)so, 0, 0);
+      acc[q] = mk(fin ? 0.0 : acc[q].re, fin ? 0.0 : acc[q].im);
+    }
+  }
+  __device__ __forceinline__ void offsets() {        // this thread's sample of unit n
+    const uint4 e0 = *reinterpret_cast<const uint4*>(s_tab + n);
+    const uint4 e1 = *(reinterpret_cast<const uint4*>(s_tab + n) + 1);
+    const int tid = threadIdx.x;
+    const int ur = tid + (tid < (int)e0.y ? W : 0);
+    const bool mine = ur >= (int)e0.z && ur < (int)e0.w;
+    int uc = ur < (int)e1.x ? (int)e1.x : ur;
+    uc = uc > (int)e1.y ? (int)e1.y : uc;
+    voff = e0.x + (unsigned)uc * (unsigned)sizeof(c64);
+    soff = mine ? voff : kCovOobOffset;
+  }
+  template <int J>
+  __device__ __forceinline__ void load() {           // antenna slot J of step i
+    const int a = bs_antenna(i, J), ac = a < A ? a : A - 1;            // (wave-uniform) a padding slot loads beyond the descriptor: a true zero, whatever the waveform holds
+    v[J] = buffer_load_c64(buffer_of(tx + (long long)ac * T, (unsigned)(T * (long long)sizeof(c64))), a < A ? voff : kCovOobOffset);
+    if constexpr (J == kBeamStreamLoads - 1) {
+      const bool last = i == spu - 1;
+      ip = i;
+      fin = last;
+      i = last ? 0 : i + 1;
+      n = (last && n < kBeamStreamTab - 1) ? n + 1 : n;
+    }
+  }
+  template <int I>
+  __device__ __forceinline__ void beam() {
+    if constexpr (I == 0) fold<0>();
+    else if constexpr (I == 1) { fold<kBeamStreamLoads / 2>(); finish(); }
+    else if constexpr (I == 2) offsets();
+    else load<I - 3>();
+  }
+  // piece P of a step: the first 18 alternate generator / beam, the last 9 are the generator's
+  template <int P>
+  __device__ __forceinline__ void piece(c64* dst) {
+    if constexpr (P >= 18) gen<P - 9>(dst);
+    else if constexpr (P % 2 == 0) gen<P / 2>(dst);
+    else beam<P / 2>();
+  }
+  static __host__ __device__ constexpr int piece_gap(int p) { return (p * 30) / kPieces; }
+  template <int PAR, int K_>
+  __device__ __forceinline__ void gap(c64* dst, long long) {
+    static_for<0, kPieces>([&](auto ic) {
+      if constexpr (piece_gap(decltype(ic)::value) == K_) piece<decltype(ic)::value>(dst);
+    });
+  }
+};
+
+template <int QT>
+__global__ __launch_bounds__(256, 2) void cov_noise_beam_kernel(NoiseBeamArgs a, const SteerArg steer_arg, long long n_slabs, long long slabs_per_wg,
+                                                                double* __restrict__ part /* [gridX][kTiles][2][256] */) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  c64* lds = reinterpret_cast<c64*>(smem_raw);      // [kCovLdsBufs][4 * kCovSlabBlk] | steering image [QT][kBeamSteerPitch] | unit table [kBeamStreamTab]
+  c64* s_steer = lds + kCovLdsBufs * 4 * kCovSlabBlk;
+  BeamUnitEntry* s_tab = reinterpret_cast<BeamUnitEntry*>(s_steer + QT * kBeamSteerPitch);
+  const int tid = threadIdx.x;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int grp = wid >> 1, phase = wid & 1;
+  const int A = a.A, wg = blockIdx.x, n_wg = gridDim.x;
+  const long long s_begin = (long long)wg * slabs_per_wg;
+  long long s_end = s_begin + slabs_per_wg;
+  if (s_end > n_slabs) s_end = n_slabs;
+  const int my_units = bs_units_of(bw_units(a.bw), n_wg, wg);
+  const int n_stream = bs_stream_units(my_units, bs_steps_of(n_slabs, slabs_per_wg, wg), bs_steps_per_unit(A));
+  for (int i = tid; i < QT * kBeamSteerPitch; i += 256) {
+    const int q = i / kBeamSteerPitch, r = i - q * kBeamSteerPitch;
+    c64 sv = mk(0.0, 0.0);
+    if (r < A) {
+      sv = a.steer ? a.steer[q * A + r] : steer_arg.v[q * A + r];
+      if (!a.steer && wg == 0) {
+        a.steer_out[q * A + r] = sv;
+        a.steer_out[A * QT + r * QT + q] = sv;       // row r of the transpose holds a_q[r] at r QT + q
+      }
+    }
+    s_steer[i] = sv;
+  }
+  if (tid < kBeamStreamTab) s_tab[tid] = beam_unit_entry(a.bw, bs_unit(n_wg, wg, tid), tid < n_stream);
+  __syncthreads();
+  if (grp == 0) cov_staged_body<4, 0>(CovNoiseBeamSource<QT>(a, s_begin, s_end, s_steer, s_tab), phase, s_begin, s_end, wg, part, lds);
+  else cov_staged_body<4, 1>(CovNoiseBeamSource<QT>(a, s_begin, s_end, s_steer, s_tab), phase, s_begin, s_end, wg, part, lds);
+  // the units the slab steps did not reach (small K against a full waveform): beamsum_coef_kernel's walk, sums only
+  for (int t = n_stream; t < my_units; ++t) {
+    const long long k = bs_unit(n_wg, wg, t);
+    const int l = (int)(k / a.bw.units_per_symbol), j = (int)(k - (long long)l * a.bw.units_per_symbol);
+    const long long lo = bw_first(a.bw, l), hi = bw_range_end(a.bw, l);
+    const long long u = bw_sample(a.bw, l, j, tid);
+    const bool mine = u >= lo && u < hi;
+    if (!__any(mine)) continue;                      // (wave-uniform; no barrier in this loop)
+    long long uc = u < lo ? lo : u < hi ? u : hi - 1;
+    uc = uc < 0 ? 0 : uc < a.T ? uc : a.T - 1;
+    const c64* p = a.tx + uc;
+    c64 acc[QT];
+#pragma unroll
+    for (int q = 0; q < QT; ++q) acc[q] = mk(0.0, 0.0);
+    constexpr int UN = 16;
+    int r = 0;
+    for (; r + UN <= A; r += UN) {
+      c64 vv[UN];
+#pragma unroll
+      for (int x = 0; x < UN; ++x) vv[x] = p[(long long)(r + x) * a.T];
+#pragma unroll
+      for (int x = 0; x < UN; ++x)
+#pragma unroll
+        for (int q = 0; q < QT; ++q) acc[q] = fma(vv[x], s_steer[q * kBeamSteerPitch + r + x], acc[q]);
+    }
+    for (; r < A; ++r) {
+      const c64 vv = p[(long long)r * a.T];
+#pragma unroll
+      for (int q = 0; q < QT; ++q) acc[q] = fma(vv, s_steer[q * kBeamSteerPitch + r], acc[q]);
+    }
+    if (mine && u >= 0) {
+#pragma unroll
+      for (int q = 0; q < QT; ++q) a.beam[(long long)q * a.T + u] = acc[q];
+    }
+  }
+}
+
+// The cross term where the range kernel cannot carry it (two LoS targets: echo_range_sl_kernel<2, 1, false, 2> sits at exactly 128 registers, echo.hip): a pass of its own over
+// w and D, in fft2D, off the serial chain of the CPI.  One workgroup per column (l, r); thread tid draws the column's Philox calls tid + 256 c -- slot s serves the rows
+// k0 = (s mod 512) + 1024 (s div 512) and k0 + 512, counter s + 2048 (l + L_out r): the field of echo_dev.hpp, box_muller32_hw's bits -- and sums w conj(d_q) over k < K;
+// the workgroup's sums are added in a fixed-order tree.  xc[(l A + r) QT + q], the layout echo_range_xc_kernel writes.
+template <int QT>
+__global__ __launch_bounds__(256) void cov_cross_kernel(const c64* __restrict__ D /* [K x L x QT] */, int K, int L, int L_out, int A, unsigned long long seed,
+                                                        c64* __restrict__ xc /* [L][A][QT] */) {
+  __shared__ c64 s_sum[QT][256];
+  const int l = blockIdx.x % L, r = blockIdx.x / L, tid = threadIdx.x;
+  const unsigned long long colg = (unsigned long long)l + (unsigned long long)L_out * (unsigned long long)r;
+  c64 acc[QT];
+#pragma unroll
+  for (int q = 0; q < QT; ++q) acc[q] = mk(0.0, 0.0);
+  for (int s = tid; s < kSpectralSlotsPerColumn; s += 256) {
+    const int k0 = (s & 511) + ((s >> 9) << 10);
+    if (k0 >= K) break;                              // (k0 grows with s)
+    const uint64_t ctr = (uint64_t)s + (uint64_t)kSpectralSlotsPerColumn * colg;
+    uint32_t o[4];
+    philox4x32_10((uint32_t)ctr, (uint32_t)(ctr >> 32), kSpectralStream, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), o);
+    const c64 w0 = box_muller32_hw(o[0], o[1]);
+#pragma unroll
+    for (int q = 0; q < QT; ++q) acc[q] = fma(w0, conj(D[(long long)K * ((long long)l + (long long)L * q) + k0]), acc[q]);
+    if (k0 + 512 < K) {
+      const c64 w1 = box_muller32_hw(o[2], o[3]);
+#pragma unroll
+      for (int q = 0; q < QT; ++q) acc[q] = fma(w1, conj(D[(long long)K * ((long long)l + (long long)L * q) + k0 + 512]), acc[q]);
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < QT; ++q) s_sum[q][tid] = acc[q];
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (tid < w) {
+#pragma unroll
+      for (int q = 0; q < QT; ++q) s_sum[q][tid] += s_sum[q][tid + w];
+    }
+    __syncthreads();
+  }
+  if (tid < QT) xc[((long long)l * A + r) * QT + tid] = s_sum[tid][0];
+}
+
+// H[l][p][q] = sum_k conj(d_p[k, l]) d_q[k, l]: one workgroup per symbol column, a fixed-order tree
+template <int QT>
+__global__ __launch_bounds__(256) void cov_dgram_kernel(const c64* __restrict__ D /* [K x L x QT] */, int K, int L, c64* __restrict__ H /* [L][QT][QT] */) {
+  __shared__ c64 s_sum[256];
+  const int l = blockIdx.x, tid = threadIdx.x;
+#pragma unroll
+  for (int p = 0; p < QT; ++p)
+#pragma unroll
+    for (int q = 0; q < QT; ++q) {
+      const c64 *dp = D + (long long)K * ((long long)l + (long long)L * p), *dq = D + (long long)K * ((long long)l + (long long)L * q);
+      c64 s = mk(0.0, 0.0);
+      for (int k = tid; k < K; k += 256) s = fma(conj(dp[k]), dq[k], s);
+      __syncthreads();
+      s_sum[tid] = s;
+      __syncthreads();
+      for (int w = 128; w > 0; w >>= 1) {
+        if (tid < w) s_sum[tid] += s_sum[tid + w];
+        __syncthreads();
+      }
+      if (tid == 0) H[((long long)l * QT + p) * QT + q] = s_sum[0];
+    }
+}
+
+// Ra = sig^2 (M / N) + ( sig sum_q (conj(a_q[a]) c_q[b] + conj(c_q[a]) a_q[b]) + sum_pq conj(a_p[a]) H_pq a_q[b] ) / N   (the split above).  One workgroup: the cross
+// partials xc[l][r][q] (echo_range_xc_kernel) and H[l] are summed over the symbols in index order; the upper triangle is computed and mirrored by conjugation, the diagonal's
+// imaginary part is set to zero -- exactly Hermitian, as cov_reduce_kernel leaves it.
+template <int QT>
+__global__ __launch_bounds__(256) void cov_assemble_kernel(const c64* __restrict__ Mn /* [A x A] = M / N */, const c64* __restrict__ xc /* [L][A][QT] */,
+                                                           const c64* __restrict__ H /* [L][QT][QT] */, const c64* __restrict__ steer_rq /* [A x QT]: a_q[r] at r QT + q */,
+                                                           int A, int L, double sig, double inv_n, c64* __restrict__ Ra) {
+  __shared__ c64 s_c[64 * QT], s_a[64 * QT], s_h[QT * QT], s_p[256];
+  const int tid = threadIdx.x;
+  // the symbol sums in kParts interleaved runs per entry (l = p, p + kParts, ...: independent loads, eight in flight), the runs then added in the order of p
+  constexpr int kParts = 256 / (64 * QT);
+  {
+    const int i = tid % (64 * QT), p = tid / (64 * QT);
+    c64 s = mk(0.0, 0.0);
+    if (i < A * QT) {
+#pragma unroll 8
+      for (int l = p; l < L; l += kParts) s += xc[(long long)l * A * QT + i];
+    }
+    s_p[tid] = s;
+  }
+  __syncthreads();
+  for (int i = tid; i < A * QT; i += 256) {
+    c64 s = s_p[i];
+#pragma unroll
+    for (int p = 1; p < kParts; ++p) s += s_p[p * 64 * QT + i];
+    s_c[i] = s;
+    s_a[i] = steer_rq[i];
+  }
+  if (tid >= 128 && tid < 128 + QT * QT) {
+    c64 s = mk(0.0, 0.0);
+#pragma unroll 8
+    for (int l = 0; l < L; ++l) s += H[(long long)l * QT * QT + (tid - 128)];
+    s_h[tid - 128] = s;
+  }
+  __syncthreads();
+  for (int e = tid; e < A * A; e += 256) {
+    const int a = e % A, b = e / A;
+    if (a > b) continue;
+    c64 x = mk(0.0, 0.0), h = mk(0.0, 0.0);
+#pragma unroll
+    for (int q = 0; q < QT; ++q) {
+      x = fma(conj(s_a[a * QT + q]), s_c[b * QT + q], x);
+      x = fma(conj(s_c[a * QT + q]), s_a[b * QT + q], x);
+      c64 hq = mk(0.0, 0.0);                          // sum_p conj(a_p[a]) H_pq
+#pragma unroll
+      for (int p = 0; p < QT; ++p) hq = fma(conj(s_a[a * QT + p]), s_h[p * QT + q], hq);
+      h = fma(hq, s_a[b * QT + q], h);
+    }
+    const c64 m = Mn[a + (long long)A * b];
+    c64 v = mk(::fma(sig * sig, m.re, (sig * x.re + h.re) * inv_n), ::fma(sig * sig, m.im, (sig * x.im + h.im) * inv_n));
+    if (a == b) v.im = 0.0;
+    Ra[a + (long long)A * b] = v;
+    if (a != b) Ra[b + (long long)A * a] = conj(v);
+  }
 }
 
 __global__ __launch_bounds__(256, 2) void cov_mfma_block_kernel(const c64* __restrict__ G, long long N, int A, int n_blk,
@@ -1132,14 +1529,87 @@ static int launch_cov_lazy(isac_ctx* ctx, hipStream_t st, const LazyCovArgs& a, 
   return ISAC_OK;
 }
 
+// slabs of a lazy grid: 8 pair rows (k, k + 512) each, one 1024-subcarrier block pair after the other (CovLazyGenerator)
+static long long lazy_slabs(int K, int L_whole, int* s_col_out) {
+  int s_col = 0;
+  for (int k0 = 0; k0 < K; k0 += 1024) s_col += (std::min(512, K - k0) + 7) / 8;
+  *s_col_out = s_col;
+  return (long long)L_whole * s_col;
+}
+
+bool isac_lazy_split_ok(long long T, int K, int L_whole) {
+  int s_col = 0;
+  const long long n_slabs = lazy_slabs(K, L_whole, &s_col);
+  return T > 0 && T * (long long)sizeof(c64) < (1ll << 31) && n_slabs > 0 && n_slabs < (1ll << 31) - 4;   // (32-bit sample offsets below kCovOobOffset)
+}
+
+// Head of a CPI on the split route (ISAC_LAZY_COV_SPLIT, include/isac_lazy_cov.h): the noise term's workgroup partials into ctx->cov_noise, the beam-sums into ctx->beam.
+int isac_cov_noise_beam_on(isac_ctx* ctx, hipStream_t st, const LazySplitFront& f) {
+  if (!isac_lazy_split_ok(f.T, f.K, f.L_whole) || f.A <= 48 || f.A > 64 || f.Q < 1 || f.Q > 2) return fail(ctx, ISAC_ERR_UNSUPPORTED, "split lazy covariance: shape outside the route (49..64 antennas, one or two LoS targets)");
+  int s_col = 0;
+  const long long n_slabs = lazy_slabs(f.K, f.L_whole, &s_col);
+  long long gx, per;
+  cov_staged_grid(n_slabs, gx, per);
+  const int S = 32, n_tiles = CovPlan<4>::kTiles;
+  ISAC_TRY(ensure(ctx, ctx->cov_noise, sizeof(double) * ((size_t)gx + S) * n_tiles * 2 * 256));
+  NoiseBeamArgs a{f.d_tx, f.steer_host ? nullptr : (const c64*)ctx->steer.p, (c64*)ctx->steer.p, (c64*)ctx->beam.p, f.T, f.seed, f.K, f.L_out, f.A, s_col, f.bw};
+  SteerArg sa{};
+  if (f.steer_host) std::memcpy(sa.v, f.steer_host, sizeof(c64) * (size_t)f.A * f.Q);
+  auto launch = [&](auto qc) -> int {
+    constexpr int QT = decltype(qc)::value;
+    const size_t lds = sizeof(c64) * (kCovLdsBufs * 4 * kCovSlabBlk + QT * kBeamSteerPitch) + sizeof(BeamUnitEntry) * kBeamStreamTab;
+    ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(cov_noise_beam_kernel<QT>), lds));
+    ISAC_PROF_COV0(st);
+    hipLaunchKernelGGL((cov_noise_beam_kernel<QT>), dim3((unsigned)gx), dim3(256), lds, st, a, sa, n_slabs, per, (double*)ctx->cov_noise.p);
+    ISAC_HIP(hipGetLastError());
+    ISAC_PROF_COV1(st);
+    return ISAC_OK;
+  };
+  ISAC_TRY(f.Q == 1 ? launch(std::integral_constant<int, 1>{}) : launch(std::integral_constant<int, 2>{}));
+  ctx->split_wg = (int)gx;
+  return ISAC_OK;
+}
+
+// The tail of the split route, where cov_lazy_kernel runs on the other: reduce the noise partials to M / N, sum D's Gram matrix per symbol, assemble Ra.
+static int covariance_lazy_split(isac_ctx* ctx, hipStream_t st, c64* Ra) {
+  const LazyEcho& lz = ctx->lazy;
+  const int S = 32, n_tiles = CovPlan<4>::kTiles, n_part = ctx->split_wg;
+  const double inv_n = 1.0 / ((double)lz.K * (double)lz.L_out);
+  double* part = (double*)ctx->cov_noise.p;
+  double* part2 = part + (size_t)n_part * n_tiles * 2 * 256;
+  c64* xc = (c64*)ctx->cov_xc.p;
+  c64* H = xc + lazy_xc_elems(lz.L_whole, lz.A, lz.Q);
+  c64* Mn = H + (size_t)lz.L_whole * lz.Q * lz.Q;
+  hipLaunchKernelGGL(cov_reduce_slice_kernel, dim3(n_tiles, S), dim3(256), 0, st, (const double*)part, n_part, n_tiles, S, part2);
+  ISAC_HIP(hipGetLastError());
+  hipLaunchKernelGGL(cov_reduce_kernel, dim3(n_tiles), dim3(256, 4), 0, st, (const double*)part2, S, n_tiles, lz.A, inv_n, Mn);
+  ISAC_HIP(hipGetLastError());
+  const c64* srq = (const c64*)ctx->steer.p + (size_t)lz.A * lz.Q;
+  auto tail = [&](auto qc) -> int {
+    constexpr int QT = decltype(qc)::value;
+    if constexpr (QT > 1) {                          // (one target: echo_range_xc_kernel has written xc)
+      hipLaunchKernelGGL((cov_cross_kernel<QT>), dim3((unsigned)(lz.L_whole * lz.A)), dim3(256), 0, st, (const c64*)ctx->dgrid.p, lz.K, lz.L_whole, lz.L_out, lz.A, lz.seed, xc);
+      ISAC_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL((cov_dgram_kernel<QT>), dim3((unsigned)lz.L_whole), dim3(256), 0, st, (const c64*)ctx->dgrid.p, lz.K, lz.L_whole, H);
+    ISAC_HIP(hipGetLastError());
+    hipLaunchKernelGGL((cov_assemble_kernel<QT>), dim3(1), dim3(256), 0, st, (const c64*)Mn, (const c64*)xc, (const c64*)H, srq, lz.A, lz.L_whole, lz.sig, inv_n, Ra);
+    ISAC_HIP(hipGetLastError());
+    return ISAC_OK;
+  };
+  ISAC_TRY(lz.Q == 1 ? tail(std::integral_constant<int, 1>{}) : tail(std::integral_constant<int, 2>{}));
+  return ISAC_OK;
+}
+
 int isac_covariance_lazy_on(isac_ctx* ctx, hipStream_t st, isac_c64* d_Ra) {
   const LazyEcho& lz = ctx->lazy;
   if (!lz.valid || !lz.native || !d_Ra) return fail(ctx, ISAC_ERR_INVALID_ARG, "no native lazy echo grid on this context");
   if (lz.A <= 48 || lz.A > 64 || lz.Q < 1 || lz.Q > 2) return fail(ctx, ISAC_ERR_UNSUPPORTED, "lazy covariance: 49..64 antennas, one or two LoS targets");
+  ctx->lazy_cov_used = lz.split ? ISAC_LAZY_COV_SPLIT : ISAC_LAZY_COV_REGENERATE;   // isac_ctx_get_lazy_cov_route_used
+  if (lz.split) return covariance_lazy_split(ctx, st, (c64*)d_Ra);
   if ((long long)lz.K * lz.L_whole * 16 >= (1ll << 31)) return fail(ctx, ISAC_ERR_UNSUPPORTED, "lazy covariance: per-target grid of 2 GB or more");
   int s_col = 0;
-  for (int k0 = 0; k0 < lz.K; k0 += 1024) s_col += (std::min(512, lz.K - k0) + 7) / 8;
-  const long long n_slabs = (long long)lz.L_whole * s_col;
+  const long long n_slabs = lazy_slabs(lz.K, lz.L_whole, &s_col);
   if (n_slabs <= 0 || n_slabs >= (1ll << 31) - 4) return fail(ctx, ISAC_ERR_UNSUPPORTED, "lazy covariance: slab count out of range");
   long long gx, per;
   cov_staged_grid(n_slabs, gx, per);

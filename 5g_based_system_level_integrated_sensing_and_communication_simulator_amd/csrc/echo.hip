@@ -137,10 +137,6 @@ template <int QT>
 struct CoefTargets {
   TargetDesc t[QT];
 };
-constexpr int kSteerArgMax = 128;                   // 2 KB of the 4 KB argument block
-struct SteerArg {
-  c64 v[kSteerArgMax];
-};
 template <int QT, int UNROLL>
 __global__ __launch_bounds__(256) void beamsum_coef_kernel(const c64* __restrict__ tx, long long T, int A,
                                                            const c64* __restrict__ steer /* [A x QT] compacted LoS, or nullptr: steer_arg */,
@@ -183,6 +179,27 @@ __global__ __launch_bounds__(256) void beamsum_coef_kernel(const c64* __restrict
         const double tt = (double)t * Ts;
         cq[t] = u < 0 ? mk(0.0, 0.0) : coef_value(acc[q], t, tab.t[q], w, Ts, tt, rx_phase(w, tt));
       }
+    }
+  }
+}
+
+// The coefficient vectors inside the demodulation windows from beam-sums that are already in memory (the split lazy covariance: cov_noise_beam_kernel, cov.hip, sums the
+// same BeamWindow units beside its MFMA stream and stores beam_q[u]): beamsum_coef_kernel's own tail, one workgroup per unit -- the same expression on the same bits, and like
+// it nothing outside the windows is read or written (coef_kernel would walk [0, T) and read the beam-sum's holes).
+template <int QT>
+__global__ __launch_bounds__(256) void coef_window_kernel(const c64* __restrict__ beam /* [QT x T] */, long long T, BeamWindow bw, CoefTargets<QT> tab, double w, double Ts,
+                                                          c64* __restrict__ coef /* [QT x T] */) {
+  const int k = blockIdx.x;
+  const int l = k / bw.units_per_symbol, j = k - l * bw.units_per_symbol;
+  const long long lo = bw_first(bw, l), hi = bw_range_end(bw, l);
+  const long long u = bw_sample(bw, l, j, threadIdx.x);
+  if (!(u >= lo && u < hi)) return;
+#pragma unroll
+  for (int q = 0; q < QT; ++q) {
+    const long long t = u + tab.t[q].shift;
+    if (t >= 0 && t < T) {
+      const double tt = (double)t * Ts;
+      coef[(long long)q * T + t] = u < 0 ? mk(0.0, 0.0) : coef_value(beam[(long long)q * T + u], t, tab.t[q], w, Ts, tt, rx_phase(w, tt));
     }
   }
 }
@@ -399,101 +416,27 @@ __global__ __launch_bounds__(Fft4096W::NT, kEchoRangeWavesPerSimd) void echo_ran
                                                             const c64* txg, const double* win_k,
                                                             const double* __restrict__ win_r, double inv_n, double sqrt_n,
                                                             int row_lo, int n_rows, c64* __restrict__ ymid) {
-  static_assert(QT >= 1 && QT <= 2, "compile-time target count");
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  c64* lds = reinterpret_cast<c64*>(smem_raw);
-  using FFT = Fft4096W;
-  constexpr int NT = FFT::NT, PER = FFT::PER, NG = PER / GROUP;
-  const int tid = threadIdx.x;
-  FFT fft;
-  int l, r;
-  if (!spectral_tile_map(blockIdx.x, L_whole, A, l, r)) return;       // padding workgroup of the tile grid (before any barrier)
-  const long long colg = (long long)l + (long long)L_out * r;
-  const c64* Dl = D + (long long)K * l;
-  const long long d_stride = (long long)K * L_whole;
-  const c64* ptx = txg + (long long)K * colg;
-  const c64* nzc = NZ == 2 ? noise + (long long)K * colg : nullptr;
-  const __amdgpu_buffer_rsrc_t rs_dst = buffer_of(grid + (long long)K * colg, (unsigned)K * (unsigned)sizeof(c64));
-  c64 s[QT];
-#pragma unroll
-  for (int q = 0; q < QT; ++q) s[q] = steer_rq[(long long)r * QT + q];   // uniform: scalar registers
-  struct Ld { c64 tx; double w; c64 d[QT]; c64 nz; };
-  Ld ld[2][GROUP];
-  auto load_group = [&](int g, int b) {
-#pragma unroll
-    for (int u = 0; u < GROUP; ++u) {
-      const int k = tid + NT * (g * GROUP + u);
-      const int kc = k < K ? k : K - 1;                                 // unconditional loads at a clamped row
-      // every base below is uniform and the row's byte offset fits 32 bits (kc < 4096): as unsigned offsets the loads take the scalar-base + 32-bit vector-offset form --
-      // one shift per element instead of a sign extension, a 64-bit shift and a 64-bit add per pointer
-      const unsigned o16 = (unsigned)kc * (unsigned)sizeof(c64);
-      auto at = [](const auto* base, unsigned off) { return *reinterpret_cast<decltype(base)>(reinterpret_cast<const char*>(base) + off); };
-      Ld& e = ld[b][u];
-      e.tx = at(ptx, o16);
-      e.w = at(win_k, (unsigned)k * (unsigned)sizeof(double));          // the window of the zero-padded IFFT input: n_ifft entries, +0.0 from K on (isac_get_windows)
-      if constexpr (NZ == 2) e.nz = at(nzc, o16);
-#pragma unroll
-      for (int q = 0; q < QT; ++q) e.d[q] = at(Dl + (long long)q * d_stride, o16);
-    }
-    asm volatile("" ::: "memory");                                      // (compiler-only) nothing of the next phase moves above these loads
-  };
-  fft.init_table(lds, tw, tid);                      // W512 (FFT twiddles); barrier inside
-  load_group(0, 0);
-  __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-  for (int j = 0; j < PER; ++j) fft.x[j] = mk(0.0, 0.0);               // unit noise first, then the range-IFFT input
-  const int wave_k0 = __builtin_amdgcn_readfirstlane(tid & ~63);
-  auto draw = [&](int c) {                                              // one Philox call: elements 2c, 2c + 1 (echo_dev.hpp pairing)
-    if constexpr (NZ == 1) {
-      const int j0 = 2 * c, j1 = j0 + 1;
-      if (wave_k0 + NT * j0 < K) {                                      // (wavefront-uniform; VALU only inside)
-        const uint64_t ctr = (uint64_t)(tid + NT * c) + (uint64_t)kSpectralSlotsPerColumn * (uint64_t)colg;
-        uint32_t o[4];
-        philox4x32_10((uint32_t)ctr, (uint32_t)(ctr >> 32), kSpectralStream, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), o);
-        fft.x[j0] = box_muller32_hw(o[0], o[1]);
-        if (wave_k0 + NT * j1 < K) fft.x[j1] = box_muller32_hw(o[2], o[3]);
-      }
-    }
-  };
-  bool live = false;                                                    // any non-zero (or NaN) matched-filter sample in this column?
-  auto consume = [&](int g, int b) {
-#pragma unroll
-    for (int u = 0; u < GROUP; ++u) {
-      const int j = g * GROUP + u, k = tid + NT * j;
-      const Ld& e = ld[b][u];
-      const c64 v = spectral_echo_value<QT, NZ != 0>(e.d, s, NZ == 2 ? e.nz : fft.x[j], sig);
-      if constexpr (STORE) buffer_store_c64_nt(rs_dst, (unsigned)k * (unsigned)sizeof(c64), v);   // echoGrid(k, l, r); k >= K: dropped by the bounds check
-      else asm volatile("" ::"v"(v.re), "v"(v.im) : "memory");          // (compiler-only: the element is complete HERE, as in the storing form -- without this anchor the scheduler
-                                                                        //  interleaves the eight elements and the two-target form spills 35 registers)
-      const c64 y = mul_conj(v, e.tx) * e.w;                            // fft2D.m:37,:43 (same order as range_kernel); k >= K: e.w = +0.0, so y is a signed zero --
-      live |= (y.re != 0.0) | (y.im != 0.0);                            // ifft(., nIFFT, 1) zero-pads at the end -- without a select per element (v, e.tx come from row K - 1:
-      fft.x[j] = y;                                                     // finite wherever that row's own product is)
-    }
-  };
-#pragma unroll
-  for (int g = 0; g < NG; ++g) {
-#pragma unroll
-    for (int c = g * GROUP / 2; c < (g + 1) * GROUP / 2; ++c) draw(c);
-    __builtin_amdgcn_sched_barrier(0);
-    if (g + 1 < NG) load_group(g + 1, (g + 1) & 1);
-    consume(g, g & 1);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  c64* yd = ymid + (long long)n_rows * colg;
-  if (!__syncthreads_or(live)) {                                        // zero-filled 'S' slot column (see echo_range_kernel)
-    for (int rr = tid; rr < n_rows; rr += NT) yd[rr] = mk(0.0, 0.0);
-    return;
-  }
-  fft.init_twiddles_lds(lds, tid);
-  const int blk = FFT::block_of_rows(row_lo, n_rows);
-  fft.template transform<+1>(lds, tw, tid, blk);
-  auto put = [&](int n, c64 v) {
-    const int rr = n - row_lo;
-    const double wr = win_r[n];
-    if (rr >= 0 && rr < n_rows) yd[rr] = ((v * inv_n) * sqrt_n) * wr;            // fft2D.m:44-45
-  };
-  if (blk >= 0) fft.drain_block(put, tid, blk);
-  else fft.drain(put, tid);
+  constexpr bool XC = false;
+  c64* const xc = nullptr;
+#include "echo_range_sl_body.inc"
+}
+
+// The lazy form (STORE = false) with the cross term of the split covariance; xc [L_whole x A x QT]; 16 c64 of dynamic LDS behind Fft4096W::LDS_ELEMS.  One LoS target only:
+// the two-target form of the kernel above sits at exactly 128 registers, and every placement of the cross term tried there spilled (24-388 B of scratch) -- with two LoS
+// targets the range kernel stays echo_range_sl_kernel<2, 1, false, 2> and the cross term is a pass of its own in fft2D (cov_cross_kernel, cov.hip).
+constexpr int kEchoXcLds = 16;
+template <int QT>
+__global__ __launch_bounds__(Fft4096W::NT, kEchoRangeWavesPerSimd) void echo_range_xc_kernel(int K, int L_whole, int L_out, int A, const c64* D,
+                                                            const c64* __restrict__ steer_rq, double sig, uint64_t seed,
+                                                            const c64* noise, const c64* __restrict__ tw,
+                                                            c64* grid,
+                                                            const c64* txg, const double* win_k,
+                                                            const double* __restrict__ win_r, double inv_n, double sqrt_n,
+                                                            int row_lo, int n_rows, c64* __restrict__ ymid, c64* __restrict__ xc) {
+  static_assert(QT == 1, "one LoS target (see above)");
+  constexpr int NZ = 1, GROUP = 4;
+  constexpr bool STORE = false, XC = true;
+#include "echo_range_sl_body.inc"
 }
 
 // ---------------------------------------------------------------- CP-OFDM modulator
@@ -636,8 +579,11 @@ extern "C" int isac_ofdm_waveform_length(const isac_carrier* carrier, int32_t L,
 // beam-sums, coefficient vectors.  Leaves coef [Q x T], phase_rx [T], steer_rq [A x Q] in ctx.  coef_only != nullptr: the caller reads steer and, of coef, the demodulation
 // windows of that carrier alone -- with one or two LoS targets the beam-sum then writes coef itself (beamsum_coef_kernel), beam / phase_rx are left as they were, and so is
 // every element of coef outside those windows (beam_window.hpp).
+// split != nullptr (with coef_only): the caller's covariance takes the split route (cov.hip) -- the beam-sums come out of cov_noise_beam_kernel, which forms the noise term of
+// that covariance in the same launch, and coef_window_kernel writes coef from them.
+struct SplitReq { int L_out; unsigned long long seed; };
 static int prepare_echo(isac_ctx* ctx, const c64* d_tx, long long T, const isac_radar_channel_params* rp,
-                        const uint8_t* los, int* q_out, const OfdmGeom* coef_only = nullptr) {
+                        const uint8_t* los, int* q_out, const OfdmGeom* coef_only = nullptr, const SplitReq* split = nullptr) {
   if (!d_tx || !rp || !los) return fail(ctx, ISAC_ERR_INVALID_ARG, "NULL argument");
   if (T <= 0 || rp->n_ants <= 0 || rp->n_targets < 0) return fail(ctx, ISAC_ERR_INVALID_ARG, "bad T / n_ants / n_targets");
   ctx->lazy.valid = false;                          // steer / coef / dgrid below are the inputs of a lazy echo grid of an earlier call: overwritten now
@@ -697,6 +643,22 @@ static int prepare_echo(isac_ctx* ctx, const c64* d_tx, long long T, const isac_
     if (T >= kSpan || d_max >= kSpan || d_min <= -kSpan) return fail(ctx, ISAC_ERR_CAPACITY, "waveform or target delay beyond the beam-sum's unit count");
     const BeamWindow bw = beam_window(g.nfft, g.cp_base, g.cp_long, g.sym_per_half, whole_symbols(g, T), T, d_min, d_max);
     const unsigned gbu = (unsigned)std::max<long long>(1, std::min<long long>(bw_units(bw), 1024));   // long-lived workgroups, as above
+    if (split) {
+      const LazySplitFront f{d_tx, T, A, Q, steer_by_arg ? steer_aq.data() : nullptr, bw, g.n_sc, whole_symbols(g, T), split->L_out, split->seed};
+      ISAC_TRY(isac_cov_noise_beam_on(ctx, ctx->stream, f));
+      timeline_mark(ctx, 1, ctx->stream);
+      auto coefs = [&](auto qc) {
+        constexpr int QT = decltype(qc)::value;
+        CoefTargets<QT> ct;
+        for (int q = 0; q < QT; ++q) ct.t[q] = tab.t[q];
+        hipLaunchKernelGGL((coef_window_kernel<QT>), dim3((unsigned)bw_units(bw)), dim3(256), 0, ctx->stream, (const c64*)ctx->beam.p, T, bw, ct, w, Ts, (c64*)ctx->coef.p);
+      };
+      if (Q == 1) coefs(std::integral_constant<int, 1>{});
+      else coefs(std::integral_constant<int, 2>{});
+      ISAC_HIP(hipGetLastError());
+      *q_out = Q;
+      return ISAC_OK;
+    }
     SteerArg sa{};
     if (steer_by_arg) std::memcpy(sa.v, steer_aq.data(), sizeof(c64) * (size_t)A * Q);
     auto launch = [&](auto qc) {
@@ -785,9 +747,9 @@ static int launch_demod(isac_ctx* ctx, const OfdmGeom& g, long long T, int A, in
 // ---- spectral noise modes: per-target demodulated coefficient grids D [K x L_whole x Q] (the coefficient vectors
 // coef [Q x T] are, byte for byte, a [T x Q] waveform), then one synthesis kernel.
 static int spectral_prepare(isac_ctx* ctx, const c64* d_tx, long long T, const isac_radar_channel_params* rp, const uint8_t* los,
-                            const OfdmGeom& g, int* q_out, int* l_whole_out, bool coef_only = false) {
+                            const OfdmGeom& g, int* q_out, int* l_whole_out, bool coef_only = false, const SplitReq* split = nullptr) {
   int Q = 0;
-  ISAC_TRY(prepare_echo(ctx, d_tx, T, rp, los, &Q, coef_only ? &g : nullptr));       // monoStaticSensing.m:13
+  ISAC_TRY(prepare_echo(ctx, d_tx, T, rp, los, &Q, coef_only ? &g : nullptr, split));       // monoStaticSensing.m:13
   const int L_whole = whole_symbols(g, T);
   if (L_whole <= 0) return fail(ctx, ISAC_ERR_SHORT_WAVEFORM, "waveform shorter than one OFDM symbol");
   ISAC_TRY(ensure(ctx, ctx->dgrid, sizeof(c64) * (size_t)g.n_sc * L_whole * Q));
@@ -816,8 +778,8 @@ static int launch_echo_spectral(isac_ctx* ctx, const OfdmGeom& g, int A, int L_w
 
 // One launch of a fused synthesis + range kernel (echo_range_kernel / echo_range_sl_kernel: Fft4096W workgroups, one per tile-map slot)
 template <class Kern, class... Args>
-static int launch_echo_range(isac_ctx* ctx, Kern kern, int L_whole, int A, Args... args) {
-  const size_t lds = sizeof(c64) * Fft4096W::LDS_ELEMS;
+static int launch_echo_range(isac_ctx* ctx, Kern kern, int L_whole, int A, size_t lds_extra, Args... args) {
+  const size_t lds = sizeof(c64) * Fft4096W::LDS_ELEMS + lds_extra;
   ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(kern), lds));
   hipLaunchKernelGGL(kern, dim3((unsigned)spectral_grid_size(L_whole, A)), dim3(Fft4096W::NT), lds, ctx->stream, args...);
   ISAC_HIP(hipGetLastError());
@@ -927,9 +889,14 @@ extern "C" int isac_mono_static_sensing_fused_dev(isac_ctx* ctx, const isac_c64*
   //  would yield to the compute-bound kernels of the CPIs ahead: 24 streams on 16 hardware queues collapse the pipelined rate to 4-5 k slots/s whatever GPU_MAX_HW_QUEUES says,
   //  and with 4-5 contexts (12-15 streams) it is 7-15 % slower than two streams per context; profiles/r06_lazy_first_measurements.txt)
   // (coef_only: this route reads coef and steer alone; isac_mono_static_sensing_dev keeps beamsum_kernel + coef_kernel and is the in-tree reference of the one-launch form)
-  ISAC_TRY(spectral_prepare(ctx, (const c64*)d_tx_wave, T, rp, los, g, &Q, &L_whole, true));
+  // the covariance of a native lazy grid on the split route (ISAC_LAZY_COV_SPLIT, cov.hip): its noise term is formed at the head of the call, beside the beam-sum
+  const int lw_pre = whole_symbols(g, T);
+  const SplitReq sreq{padded_symbols(lw_pre, tx_dim_l, nullptr), seed};
+  const bool split = lazy_native && ctx->lazy_cov_route == 0 && lw_pre > 0 && isac_lazy_split_ok(T, g.n_sc, lw_pre);
+  ISAC_TRY(spectral_prepare(ctx, (const c64*)d_tx_wave, T, rp, los, g, &Q, &L_whole, true, split ? &sreq : nullptr));
   const int A = rp->n_ants, row_lo = cr.row_lo, nr = cr.nr;
   const int L_out = padded_symbols(L_whole, tx_dim_l, l_out);
+  if (split) ISAC_TRY(ensure(ctx, ctx->cov_xc, sizeof(c64) * lazy_xc_total(L_whole, A, Q)));
   ctx->tgt.drop();                                     // the fused kernel rewrites the range rows isac_fft2d_get_targets reads
   ISAC_TRY(ensure(ctx, ctx->ymid, sizeof(c64) * (size_t)nr * L_out * A));
   if (L_out > L_whole) {
@@ -945,22 +912,27 @@ extern "C" int isac_mono_static_sensing_fused_dev(isac_ctx* ctx, const isac_c64*
   timeline_mark(ctx, 2, ctx->stream);
   // the two kernels' argument lists differ in the run-time target count `q_rt` alone (the straight-line form has none)
   auto launch = [&](auto kern, auto... q_rt) {
-    return launch_echo_range(ctx, kern, L_whole, A, g.n_sc, L_whole, L_out, A, q_rt..., (const c64*)ctx->dgrid.p, (const c64*)ctx->steer.p + (size_t)A * Q, sig, seed,
+    return launch_echo_range(ctx, kern, L_whole, A, (size_t)0, g.n_sc, L_whole, L_out, A, q_rt..., (const c64*)ctx->dgrid.p, (const c64*)ctx->steer.p + (size_t)A * Q, sig, seed,
                              (const c64*)d_noise_unit, tw, (c64*)d_echo_grid, (const c64*)d_tx_grid, wk, wr, 1.0 / ep->n_ifft, std::sqrt((double)ep->n_ifft), row_lo, nr,
                              (c64*)ctx->ymid.p);
   };
   const bool philox = noise_mode == ISAC_NOISE_PHILOX_SPECTRAL;
   ISAC_TRY(echo_dispatch<4>(Q, [&](auto qc) {
     constexpr int QT = decltype(qc)::value;
-    if constexpr (QT == 1 || QT == 2)       // the straight-line form; lazy_native: without the echoGrid store (d_echo_grid is NULL, the noise is Philox)
+    if constexpr (QT == 1 || QT == 2) {     // the straight-line form; lazy_native: without the echoGrid store (d_echo_grid is NULL, the noise is Philox)
+      if constexpr (QT == 1)
+        if (split)                          // ... and with the cross term of the split covariance (the one extra argument; two targets: cov_cross_kernel forms it in fft2D)
+          return launch_echo_range(ctx, echo_range_xc_kernel<QT>, L_whole, A, sizeof(c64) * kEchoXcLds, g.n_sc, L_whole, L_out, A, (const c64*)ctx->dgrid.p, (const c64*)ctx->steer.p + (size_t)A * Q, sig, seed,
+                                 (const c64*)d_noise_unit, tw, (c64*)d_echo_grid, (const c64*)d_tx_grid, wk, wr, 1.0 / ep->n_ifft, std::sqrt((double)ep->n_ifft), row_lo, nr,
+                                 (c64*)ctx->ymid.p, (c64*)ctx->cov_xc.p);
       return launch(lazy_native ? echo_range_sl_kernel<QT, 1, false> : philox ? echo_range_sl_kernel<QT, 1> : echo_range_sl_kernel<QT, 2>);
-    else
+    } else
       return launch(philox ? echo_range_kernel<QT, 1> : echo_range_kernel<QT, 2>, Q);
   }));
   if (!ctx->profile_cov) ISAC_TRY(profile_end(ctx));
   timeline_mark(ctx, 3, ctx->stream);
   ctx->range_cache.set(d_echo_grid, d_tx_grid, g.n_sc, L_out, A, ep->n_ifft, row_lo, nr);   // (rx == NULL: the native lazy grid)
-  if (lazy_native) ctx->lazy.set_native(g.n_sc, L_whole, L_out, A, Q, sig, seed);
+  if (lazy_native) { ctx->lazy.set_native(g.n_sc, L_whole, L_out, A, Q, sig, seed); ctx->lazy.split = split; }
   else if (lazy) ctx->lazy.set_owned(g.n_sc, L_out, A);
   return ISAC_OK;
 }

@@ -300,6 +300,12 @@ __device__ __forceinline__ void spectral_echo_column(int tid, int K, int Q_rt, c
   }
 }
 
+// Steering vectors handed to a kernel inside its argument block (beamsum_coef_kernel, echo.hip; cov_noise_beam_kernel, cov.hip): [A x QT] compacted LoS columns
+constexpr int kSteerArgMax = 128;                   // 2 KB of the 4 KB argument block
+struct SteerArg {
+  c64 v[kSteerArgMax];
+};
+
 // rx[t,r] for one sample (shared by the fused demodulator and the waveform materialiser)
 __device__ __forceinline__ c64 rx_sample(long long t, int r, long long T, int Q, const c64* __restrict__ coef,
                                          const c64* __restrict__ s_steer_r /* [Q] a_q[r] */,

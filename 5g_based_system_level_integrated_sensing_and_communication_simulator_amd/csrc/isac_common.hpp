@@ -135,6 +135,7 @@ struct LazyEcho {
   int K = 0, L_whole = 0, L_out = 0, A = 0, Q = 0;
   double sig = 0.0;
   unsigned long long seed = 0;
+  bool split = false;                      // native, ISAC_LAZY_COV_SPLIT: the noise term's partials (ctx->cov_noise) and the cross partials (ctx->cov_xc) of this grid are in the context
   void set_owned(int K_, int L_, int A_) { *this = LazyEcho{true, false, K_, L_, L_, A_, 0, 0.0, 0}; }      // the grid is in ctx->echo_own
   void set_native(int K_, int L_whole_, int L_out_, int A_, int Q_, double sig_, unsigned long long seed_) { *this = LazyEcho{true, true, K_, L_whole_, L_out_, A_, Q_, sig_, seed_}; }
 };
@@ -212,6 +213,9 @@ struct isac_ctx {
   hipEvent_t ev_k0 = nullptr, ev_k1 = nullptr;   // isac_profile_*: around the dominant kernel of the last fused echo call
   bool profile = false, profile_recorded = false;
   bool profile_cov = false;                    // isac_profile_enable(ctx, 2): the event pair brackets the wide covariance launch of fft2D instead of the fused echo kernel
+  int lazy_cov_route = 0;          // isac_ctx_set_lazy_cov_route: 0 = split covariance of a native lazy echo grid (noise term beside the beam-sum, default), 1 = the regenerating cov_lazy_kernel
+  int lazy_cov_used = -1;          // route the last covariance of a native lazy grid took (isac_ctx_get_lazy_cov_route_used); -1: none yet
+  int split_wg = 0;                // workgroup partials the last cov_noise_beam_kernel launch left in cov_noise
   int music_route = 0;             // ISAC_OPT_MUSIC_ROUTE: 0 = signal-subspace eigensolver for MUSIC (default), 1 = always the full eigendecomposition
   long long eig_epoch = 0;         // launches of eigh_tridiag_dist_kernel on this context (its exchange stamps carry the epoch: no reset between launches)
   bool tail_unjoined = false;      // wide order: ev_done of the last submit has not been waited for by the main stream (ISAC_ENTER joins lazily)
@@ -221,7 +225,7 @@ struct isac_ctx {
   std::map<const void*, size_t> lds_allowed;                        // kernel -> dynamic LDS bytes enabled on this context's device
   std::map<isac::TableKey, isac::DevBuf> tables;                    // cached device tables: made on first use, kept until the context goes
   // scratch  (coef [Q x T]: after the fused spectral route with one or two LoS targets only the demodulation windows hold values -- echo.hip prepare_echo, beam_window.hpp)
-  isac::DevBuf beam, coef, phase_rx, steer, dgrid, ymid, pwin, flags, det_cut, det_pow, det_cnt, cov_part, cov,
+  isac::DevBuf beam, coef, phase_rx, steer, dgrid, ymid, pwin, flags, det_cut, det_pow, det_cnt, cov_part, cov, cov_noise, cov_xc,
       eig_w, eig_v, eig_scratch, spec, misc, stage_a, stage_b, stage_c, cdl_par, seg, cdl_h, rxfe_tab;
   isac::PinnedBuf pinned;       // results of isac_fft2d_submit* (read by isac_fft2d_collect) -- no other entry point may touch it
   isac::PinnedBuf bounce; hipEvent_t ev_bounce[2] = {nullptr, nullptr};   // pinned bounce buffer of the host-array copies (copy_h2d / copy_d2h)

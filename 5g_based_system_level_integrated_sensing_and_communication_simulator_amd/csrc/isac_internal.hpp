@@ -3,6 +3,7 @@
 #pragma once
 #include "isac_common.hpp"
 #include "eigh_layout.hpp"
+#include "beam_window.hpp"
 
 // ---------------------------------------------------------------- tables.hip: cached device tables
 // The one way a cached table comes to exist: `key` is looked up in ctx->tables; on a miss `build` fills a std::vector<T> on the host, which is uploaded and kept under
@@ -45,6 +46,18 @@ int fft2d_estimates(isac_ctx* ctx, const isac_est_params* ep, const isac::CutWin
 // ---------------------------------------------------------------- cov.hip
 int isac_covariance_on(isac_ctx* ctx, hipStream_t st, const isac_c64* d_grid, int64_t N, int32_t A, isac_c64* d_Ra);
 int isac_covariance_lazy_on(isac_ctx* ctx, hipStream_t st, isac_c64* d_Ra);   // Ra of the context's native lazy echo grid
+// The split route of that covariance (ISAC_LAZY_COV_SPLIT): what the head of the CPI hands to cov_noise_beam_kernel
+struct LazySplitFront {
+  const isac::c64* d_tx; long long T; int A, Q;
+  const isac::c64* steer_host;   // [A x Q] compacted LoS columns for the argument block, or nullptr: they are in ctx->steer
+  isac::BeamWindow bw;
+  int K, L_whole, L_out; unsigned long long seed;
+};
+bool isac_lazy_split_ok(long long T, int K, int L_whole);
+int isac_cov_noise_beam_on(isac_ctx* ctx, hipStream_t st, const LazySplitFront& f);   // noise partials -> ctx->cov_noise, beam-sums -> ctx->beam (inside f.bw's ranges), ctx->steer
+// ctx->cov_xc: cross partials [L_whole][A][Q] (echo_range_xc_kernel) | D's Gram matrix per symbol [L_whole][Q][Q] | M / N [A x A]
+inline size_t lazy_xc_elems(int L_whole, int A, int Q) { return (size_t)L_whole * A * Q; }
+inline size_t lazy_xc_total(int L_whole, int A, int Q) { return lazy_xc_elems(L_whole, A, Q) + (size_t)L_whole * Q * Q + (size_t)A * A; }
 // ---------------------------------------------------------------- eigh.hip (the device code it shares with music.hip: eigh_dev.hpp)
 // device eig: H [A x A] (device) -> ctx->eig_w [A], ctx->eig_v [A x A] (unsorted); live_replay: see the definition
 int isac_eigh_dev(isac_ctx* ctx, const isac::c64* d_H, int A, hipStream_t st, bool live_replay = true);
