@@ -243,6 +243,10 @@ PROTOTYPES_LAZY_COV = {
     "isac_ctx_set_lazy_cov_route": (_INT, (_P, _I32)),
     "isac_ctx_get_lazy_cov_route_used": (_INT, (_P, _P)),
 }
+# ... and include/isac_targets_upa.h (tests/test_target_list_upa_cpu.py pins it)
+PROTOTYPES_TARGETS_UPA = {
+    "isac_fft2d_get_targets_upa": (_INT, (_P, _P, _P, _P, _I32)),
+}
 
 
 def library_path() -> str:
@@ -269,7 +273,7 @@ def load():
             except Exception:
                 pass
         lib = C.CDLL(_LIB_PATH, mode=C.RTLD_GLOBAL)
-        for name, (restype, argtypes) in {**PROTOTYPES, **PROTOTYPES_ADDED, **PROTOTYPES_CFAR, **PROTOTYPES_CFAR_MC, **PROTOTYPES_LAZY_COV}.items():
+        for name, (restype, argtypes) in {**PROTOTYPES, **PROTOTYPES_ADDED, **PROTOTYPES_CFAR, **PROTOTYPES_CFAR_MC, **PROTOTYPES_LAZY_COV, **PROTOTYPES_TARGETS_UPA}.items():
             fn = getattr(lib, name)  # AttributeError here = ABI drift between isac.h and the .so
             fn.restype, fn.argtypes = restype, argtypes
         # the library writes whole structs into caller memory: version AND struct sizes must match this binding's mirrors

@@ -203,6 +203,12 @@ int eig_debug_print(isac_ctx* ctx, int A, int n_top /* < 0: isac_eigh */) {   //
 
 }  // namespace
 
+// The UPA scan grid for a caller outside the DoA back end (targets.hip): nV x nH against A and the 256-element limit of the 2-D scans, then the cached table
+int isac_doa2d_grid(isac_ctx* ctx, const isac_est_params* ep, int A, const double** d_tab, int* e_steps, int* a_steps) {
+  ISAC_TRY(check_upa_dims(ctx, ep, A));
+  return get_doa2d_tables(ctx, ep, d_tab, e_steps, a_steps);
+}
+
 // ------------------------------------------------------------------ the DoA back end: plan -> first half of the eigen stage -> scan -> read-out
 // Everything both callers settle before anything is enqueued: which route, the scan tables, every buffer of the tail.
 int doa_plan(isac_ctx* ctx, const isac_est_params* ep, int A, int mode, DoaPlan* pl) {

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "isac_internal.hpp"
+#include "upa_steer.hpp"
 
 using namespace isac;
 
@@ -14,7 +15,6 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kCandHdr = 2;          // doubles in front of the candidate pairs: [0] holds the 32-bit candidate counter
-constexpr double kD = 0.5;           // element spacing / wavelength (music.m:12)
 
 // the L signal vectors of music_subspace_kernel are delivered when ctl[kRoute] == 1 (ctl[kLsub] of them)
 __device__ __forceinline__ bool subspace_delivered(const int* ctl) { return ctl && ctl[MusicCtl::kRoute] == 1; }
@@ -39,7 +39,7 @@ __global__ __launch_bounds__(kThreads) void doa2d_weights_kernel(const double* _
 }
 
 // One workgroup per tile of PT scan points (j = e + eSteps a, column-major like the reference's P(e, a)).  The steering tile [A x PT]
-// is formed in LDS from the three host tables, the phase in ONE association for every point:
+// is formed in LDS from the three host tables (upa_steer, upa_steer.hpp), the phase in ONE association for every point:
 //     arg = ((-2 pi) sind(th)) * fma(m d, cosd(ph), (n d) sind(ph)),    element r = n + nH m   (music.m:44-55)
 // so that mirror twins (ph -+ 180, -th) -- whose table entries are exact negatives -- get bitwise equal vectors.  Every point then takes
 // the same reduction order (sum over m ascending, over the thread's four vectors in order, over the vector groups in order), wherever it
@@ -58,21 +58,11 @@ __global__ __launch_bounds__(kThreads) void doa2d_scan_kernel(const double* __re
   c64* s_a = reinterpret_cast<c64*>(smem_raw);                       // [A][PT]
   double* s_part = reinterpret_cast<double*>(s_a + (size_t)A * PT);  // [VG][PT]
   c64* s_y = reinterpret_cast<c64*>(s_part + VG * PT);               // [Ls][PT] (subspace route only)
-  const double* sth = tab;
-  const double* cph = tab + eS;
-  const double* sph = tab + eS + aS;
   const int tid = threadIdx.x;
   const int j0 = blockIdx.x * PT;
   for (int t = tid; t < A * PT; t += kThreads) {
     const int p = t % PT, r = t / PT;
-    const int j = min(j0 + p, n_pts - 1);                            // (tail points repeat the last one; not stored)
-    const int e = j % eS, az = j / eS;
-    const int n = r % nH, m = r / nH;
-    const double inner = ::fma((double)m * kD, cph[az], ((double)n * kD) * sph[az]);
-    const double arg = ((-2.0 * M_PI) * sth[e]) * inner;
-    double s, c;
-    sincos(arg, &s, &c);
-    s_a[t] = mk(c, s);
+    s_a[t] = upa_steer(tab, eS, aS, nH, min(j0 + p, n_pts - 1), r);   // (tail points repeat the last one; not stored)
   }
   __syncthreads();
   double t_out = 0.0;

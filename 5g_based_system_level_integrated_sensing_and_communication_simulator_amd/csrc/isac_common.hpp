@@ -160,7 +160,7 @@ struct DoaPlan {  // the direction-finding tail of one covariance: what doa_plan
 };
 
 // The one description of the context's last CPI, filled once, at the end of a successful fft2d_submit (fft2d.hip).  Readers: isac_fft2d_collect, the getters (under Fft2dLast::valid)
-// and -- with the device buffers it describes: ctx->ymid, ctx->pwin, det_cut / det_cnt -- isac_fft2d_get_targets (targets.hip) and isac_fft2d_redetect (cfar.hip).
+// and -- with the device buffers it describes: ctx->ymid, ctx->pwin, det_cut / det_cnt -- isac_fft2d_get_targets[_upa] (targets.hip) and isac_fft2d_redetect (cfar.hip).
 // A submit overwrites the record while the host copies of an OLDER CPI would otherwise still be readable: it clears Fft2dLast::valid (and the pending flag) before anything else,
 // and has to keep that order -- a getter must never pair the old lists with the new geometry.  state: are the device buffers still the ones this CPI left?  fft2d_submit sets
 // kSubmitted, isac_fft2d_collect promotes that to kCollected, and every function that rewrites one of them calls drop() first -- a later range stage, echo call or submit on the
@@ -234,6 +234,7 @@ struct isac_ctx {
   isac::Fft2dPending pending;
   isac::Fft2dCpi tgt;                // the last submitted CPI (named for its first reader, isac_fft2d_get_targets): parameters, window, validity of ymid / pwin / det_*
   isac::DevBuf tgt_scratch;          // ... and its device scratch (hits map, candidate lists, snapshots)
+  isac::DevBuf tgt_part;             // isac_fft2d_get_targets_upa: per (scan tile, target) partial maxima of the 2-D Bartlett scan, sized once the target count is known
   isac::DevBuf redet;                // isac_fft2d_redetect (cfar.hip): per-CUT flags, per-antenna lists sized for every CUT, counts, row flags
   isac::DevBuf cfar_mc;              // isac_cfar_monte_carlo (cfar.hip): detection counts, per-trial flags
   isac::RangeCache range_cache;

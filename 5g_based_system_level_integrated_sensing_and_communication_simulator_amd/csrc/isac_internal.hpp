@@ -35,8 +35,9 @@ namespace isac { struct CutRows { int row_lo, nr; }; }   // rows [row_lo, row_lo
 bool cut_rows_ok(const isac_est_params* ep, const isac_cfar_config* cf, isac::CutRows* out);              // false: the window leaves the map
 int cut_rows(isac_ctx* ctx, const isac_est_params* ep, const isac_cfar_config* cf, isac::CutRows* out);   // ... as ISAC_ERR_CFAR_WINDOW
 int isac_range_stage_into_cache(isac_ctx* ctx, const isac_est_params* ep, const isac_cfar_config* cf, const isac::c64* d_rx, const isac::c64* d_tx, int K, int L, int A);
-// ---------------------------------------------------------------- targets.hip: isac_fft2d_get_targets (include/isac_targets.h) -- the per-target list of the last completed fft2D.  It calls nothing but
-// isac_get_twiddles and is called by no other unit; what it shares with them is ctx->tgt (isac::Fft2dCpi, isac_common.hpp): fft2d.hip fills it, rdm.hip / echo.hip drop it.
+// ---------------------------------------------------------------- targets.hip: isac_fft2d_get_targets (include/isac_targets.h) and isac_fft2d_get_targets_upa (include/isac_targets_upa.h) -- the per-target
+// list of the last completed fft2D.  It calls nothing but isac_get_twiddles and (UPA) isac_doa2d_grid and is called by no other unit; what it shares with them is ctx->tgt
+// (isac::Fft2dCpi, isac_common.hpp): fft2d.hip fills it, rdm.hip / echo.hip drop it.
 // ---------------------------------------------------------------- cfar.hip: the GOCA / SOCA / OS detectors (include/isac_cfar.h): isac_cfar2d, isac_fft2d_redetect, isac_cfar_threshold_factor.  Reads ctx->tgt and
 // ctx->pwin, writes ctx->redet only; calls cfar_alpha (rdm.hip) and fft2d_estimates (fft2d.hip).  Also isac_cfar_monte_carlo (include/isac_cfar_mc.h): reads nothing of the
 // context, writes ctx->cfar_mc only.
@@ -87,6 +88,7 @@ int doa_eig_first_half(isac_ctx* ctx, const isac::DoaPlan& pl, const isac::c64* 
 int doa_enqueue(isac_ctx* ctx, const isac::DoaPlan& pl, const int* d_num_dets, int num_dets_host, hipStream_t st);   // subspace -> scan (-> norm + peak candidates)
 int doa_readout(isac_ctx* ctx, const isac::DoaPlan& pl, const isac_est_params* ep, const double* host, int n_first, int L, const char* none_prefix, std::vector<double>& ele, std::vector<double>& azi);
 void doa_store(const std::vector<double>& ele, const std::vector<double>& azi, int n, double* ele_est, double* azi_est);   // the first n, NaN elevations for a ULA
+int isac_doa2d_grid(isac_ctx* ctx, const isac_est_params* ep, int A, const double** d_tab, int* e_steps, int* a_steps);   // UPA dims checked against A, then the cached [sind(ele) | cosd(azi) | sind(azi)] table (caller: targets.hip)
 // ---------------------------------------------------------------- cdl_os.hip: the CDL apply in the frequency domain (overlap-save, 4096-point windows) for long waveforms
 bool cdl_os_ok(long long T, int Nt, int Nr, int n_paths, int n_taps, int max_shift);      // downlink: into two receive elements
 bool cdl_os_ul_ok(long long T, int Nt, int Nr, int n_paths, int n_taps, int max_shift);   // uplink: one or two transmit elements into many receive elements

@@ -7,10 +7,17 @@
 //   5  host: sort by S descending, ties by ascending column-major index; rng / vel as fft2D.m:77-82
 // K1 target_hits_kernel scatters the lists into a zeroed hits map (its own launch: the map must be complete before any cell is tested), K2 target_cells_kernel sums, tests and
 // compacts, K3 target_doa_kernel forms snapshot and azimuth of every selected cell.  All three are latency-bound (a few MB at the bench shape) and off the timed path.
+// isac_fft2d_get_targets_upa (include/isac_targets_upa.h) is the same list for a uniform planar array: steps 1, 2, 3 and 5 are the same host function and the same device code
+// (select_cells, K1, K2, target_snapshot), and step 4 becomes
+//   4' (azimuth, elevation) = first arg-max of |a_j' x|^2 over the [eSteps x aSteps] grid of music.m:36-53, j = e + eSteps a (the table and steering element of doa2d.hip)
+// K4 target_snap_kernel writes the snapshots [A x n]; K5 target_scan2d_kernel, one workgroup per tile of PT scan points, forms the steering tile in LDS ONCE and runs every
+// snapshot over it -- eSteps aSteps A sincos in all, not that many per target -- leaving one (max, lowest j) per (tile, target); K6 target_scan2d_reduce_kernel joins each
+// target's partials in ascending tile order.  No floating-point atomics, no order that depends on arrival: the result is a function of the snapshots alone.
 #include <algorithm>
 #include <numeric>
 
 #include "isac_internal.hpp"
+#include "upa_steer.hpp"
 
 namespace isac {
 
@@ -87,17 +94,12 @@ __global__ __launch_bounds__(kCellR * kCellC) void target_cells_kernel(const dou
 // Phase 2: one lane per scan angle reads x[m] from LDS -- every lane the same address, a broadcast: no bank conflict whatever the c64 layout -- and forms
 // B = |sum_m conj(a[m]) x[m]|^2; angles with bitwise equal sind (mirror twins) run the same instructions on the same operands.  Arg-max: each lane keeps its first
 // maximum in ascending angle order, then a fixed tree on (value, lowest index).
-__global__ __launch_bounds__(256) void target_doa_kernel(const c64* __restrict__ ymid /* [n_rows x L x A] */, int n_rows, int L, int A, int n_fft,
-                                                         const c64* __restrict__ tw_d /* e^{-2 pi j m / n_fft} */, double sqrt_nfft,
-                                                         const int* __restrict__ cell_row /* window row, 0-based */, const int* __restrict__ cell_col /* rdm column, 0-based */,
-                                                         const double* __restrict__ sind_tab, int n_steps, double d_ratio,
-                                                         int* __restrict__ azi_bin /* [n] */, c64* __restrict__ snap /* [A x n] */) {
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  c64* s_x = reinterpret_cast<c64*>(smem_raw);                            // [A]
-  __shared__ double s_val[256];
-  __shared__ int s_idx[256];
-  const int tid = threadIdx.x, t = blockIdx.x;
-  const int row = cell_row[t], c = cell_col[t];
+
+// Phase 1 (step 3) for a workgroup of 256 threads, shared by K3 and K4: s_x[0 .. A) = the snapshot of cell (row, c), visible to every thread on return.
+__device__ __forceinline__ void target_snapshot(const c64* __restrict__ ymid /* [n_rows x L x A] */, int n_rows, int L, int A, int n_fft,
+                                                const c64* __restrict__ tw_d /* e^{-2 pi j m / n_fft} */, double sqrt_nfft, int row /* window row, 0-based */,
+                                                int c /* rdm column, 0-based */, c64* s_x /* LDS [A] */) {
+  const int tid = threadIdx.x;
   const int Lu = L < n_fft ? L : n_fft;                                   // fft(., nFFT, 2) truncates when L > nFFT
   const int half = L / 2;                                                 // ifftshift over the symbols
   const int kbin = (c + n_fft / 2) % n_fft;                               // fftshift: column c <-> bin (c + nFFT/2) mod nFFT
@@ -122,6 +124,19 @@ __global__ __launch_bounds__(256) void target_doa_kernel(const c64* __restrict__
     if (a < A && part == 0) s_x[a] = mk(acc.re / sqrt_nfft, acc.im / sqrt_nfft);   // fft(.)/sqrt(nFFT)  fft2D.m:46
   }
   __syncthreads();
+}
+
+__global__ __launch_bounds__(256) void target_doa_kernel(const c64* __restrict__ ymid /* [n_rows x L x A] */, int n_rows, int L, int A, int n_fft,
+                                                         const c64* __restrict__ tw_d /* e^{-2 pi j m / n_fft} */, double sqrt_nfft,
+                                                         const int* __restrict__ cell_row /* window row, 0-based */, const int* __restrict__ cell_col /* rdm column, 0-based */,
+                                                         const double* __restrict__ sind_tab, int n_steps, double d_ratio,
+                                                         int* __restrict__ azi_bin /* [n] */, c64* __restrict__ snap /* [A x n] */) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  c64* s_x = reinterpret_cast<c64*>(smem_raw);                            // [A]
+  __shared__ double s_val[256];
+  __shared__ int s_idx[256];
+  const int tid = threadIdx.x, t = blockIdx.x;
+  target_snapshot(ymid, n_rows, L, A, n_fft, tw_d, sqrt_nfft, cell_row[t], cell_col[t], s_x);
   for (int a = tid; a < A; a += 256) snap[a + (long long)A * t] = s_x[a];
   double best = -1.0;                                                     // B >= 0; NaN never wins
   int best_i = 0x7fffffff;
@@ -152,23 +167,109 @@ __global__ __launch_bounds__(256) void target_doa_kernel(const c64* __restrict__
   if (tid == 0) azi_bin[t] = s_idx[0] == 0x7fffffff ? 0 : s_idx[0];
 }
 
+// ---------------------------------------------------------------- K4: array snapshot of one target cell per workgroup (the UPA list: phase 1 of K3 alone)
+__global__ __launch_bounds__(256) void target_snap_kernel(const c64* __restrict__ ymid /* [n_rows x L x A] */, int n_rows, int L, int A, int n_fft,
+                                                          const c64* __restrict__ tw_d, double sqrt_nfft, const int* __restrict__ cell_row,
+                                                          const int* __restrict__ cell_col, c64* __restrict__ snap /* [A x n] */) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  c64* s_x = reinterpret_cast<c64*>(smem_raw);                            // [A]
+  const int t = blockIdx.x;
+  target_snapshot(ymid, n_rows, L, A, n_fft, tw_d, sqrt_nfft, cell_row[t], cell_col[t], s_x);
+  for (int a = threadIdx.x; a < A; a += 256) snap[a + (long long)A * t] = s_x[a];
+}
+
+// ---------------------------------------------------------------- K5: 2-D Bartlett scan of every snapshot over one tile of PT scan points per workgroup
+// The tile conj(a_j[r]), [A x PT] c64 (64 KB at PT = 64 / 32 / 16 for A = 64 / 128 / 256; a row of PT consecutive c64 per element, so the PT lanes of a point group read
+// consecutive 16-byte words), is formed once with doa2d_scan_kernel's steering element and then serves all n snapshots.  Thread (p, g) = (tid % PT, tid / PT): point j0 + p,
+// snapshots g, g + G, ... (G = 256 / PT).  x[r] of a snapshot is one address for the PT lanes of a group: a broadcast load out of L2 (n <= 1024 snapshots, at most 4 MB).
+// EVERY (point, snapshot) value is the same chain -- y = fma(conj(a[r]), x[r], y) over r ascending from 0, then re^2 + im^2 -- wherever the point sits in its tile: equal
+// steering vectors (the mirror twins) give bitwise equal values.  The arg-max over the tile is a butterfly on (value, lowest j) across the group's PT lanes (PT divides 64: a
+// group never straddles a wave); the operation is associative and commutative, so the butterfly's order does not matter.  Tail points (j >= eSteps aSteps) take part as
+// (-1, INT_MAX) and never win; neither does a NaN.
+template <int PT>
+__global__ __launch_bounds__(256) void target_scan2d_kernel(const double* __restrict__ tab, int eS, int aS, int nV, int nH, const c64* __restrict__ snap /* [A x n] */, int n,
+                                                            double* __restrict__ part_val /* [tiles x n] */, int* __restrict__ part_idx /* [tiles x n] */) {
+  constexpr int G = 256 / PT;
+  static_assert(64 % PT == 0, "a point group must lie inside one wave");
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  c64* s_a = reinterpret_cast<c64*>(smem_raw);                            // [A][PT], conjugated
+  const int A = nV * nH, n_pts = eS * aS;
+  const int tid = threadIdx.x, j0 = blockIdx.x * PT;
+  for (int t = tid; t < A * PT; t += 256) {
+    const int p = t % PT, r = t / PT;
+    s_a[t] = conj(upa_steer(tab, eS, aS, nH, min(j0 + p, n_pts - 1), r));   // (tail points repeat the last one; they never win)
+  }
+  __syncthreads();
+  const int p = tid % PT, g = tid / PT, j = j0 + p;
+  for (int t0 = 0; t0 < n; t0 += G) {                                     // (uniform trip count: every lane takes part in the butterfly)
+    const int t = t0 + g;
+    const c64* x = snap + (long long)A * min(t, n - 1);
+    c64 y = mk(0.0, 0.0);
+    for (int r = 0; r < A; ++r) y = fma(s_a[r * PT + p], x[r], y);        // conj(a[r]) x[r]
+    const double b = y.re * y.re + y.im * y.im;
+    double best = -1.0;                                                   // B >= 0; NaN never wins
+    int best_j = 0x7fffffff;
+    if (j < n_pts && b > best) { best = b; best_j = j; }
+    for (int o = PT / 2; o > 0; o >>= 1) {
+      const double v2 = __shfl_xor(best, o);
+      const int j2 = __shfl_xor(best_j, o);
+      if (v2 > best || (v2 == best && j2 < best_j)) { best = v2; best_j = j2; }
+    }
+    if (p == 0 && t < n) {
+      part_val[(size_t)blockIdx.x * n + t] = best;
+      part_idx[(size_t)blockIdx.x * n + t] = best_j;
+    }
+  }
+}
+
+// ---------------------------------------------------------------- K6: each target's partials joined in ascending tile order -> the first arg-max over the whole grid
+__global__ __launch_bounds__(256) void target_scan2d_reduce_kernel(const double* __restrict__ part_val, const int* __restrict__ part_idx, int n_tiles, int n,
+                                                                   int* __restrict__ best_bin /* [n]: j = e + eSteps a */) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  double best = -1.0;
+  int best_j = 0x7fffffff;
+  for (int tile = 0; tile < n_tiles; ++tile) {                            // (lanes along t: consecutive words)
+    const double v2 = part_val[(size_t)tile * n + t];
+    const int j2 = part_idx[(size_t)tile * n + t];
+    if (v2 > best || (v2 == best && j2 < best_j)) { best = v2; best_j = j2; }
+  }
+  best_bin[t] = best_j == 0x7fffffff ? 0 : best_j;
+}
+
 }  // namespace isac
 
 // ================================================================= host side
 using namespace isac;
 
-extern "C" int isac_fft2d_get_targets(isac_ctx* ctx, isac_target_list* out, isac_c64* snapshots, int32_t cap_snap) {
-  ISAC_ENTER(ctx);
+namespace {
+
+// What both entry points ask first: the caller's arguments, and a completed fft2D whose device state is still the one it left.  who: the entry point, for the message.
+int cpi_ready(isac_ctx* ctx, const char* who, const isac_target_list* out, const isac_c64* snapshots, int32_t cap_snap) {
   if (!out || (snapshots && cap_snap < 0)) return fail(ctx, ISAC_ERR_INVALID_ARG, "NULL argument");
+  if (!ctx->last.valid || ctx->tgt.state != Fft2dCpi::kCollected)
+    return fail(ctx, ISAC_ERR_INVALID_ARG, std::string(who) + ": no completed fft2D on this context whose range rows, power window and detection lists are still on the device");
+  return ISAC_OK;
+}
+
+// The selected cells on the device: n of them (0: none, the list is complete), [window row | rdm column] at d + off_sel; room for a scan bin per target at d + off_bin and
+// for the snapshots [A x n] at d + off_snap (d = ctx->tgt_scratch)
+struct SelectedCells {
+  int n = 0;
+  char* d = nullptr;
+  size_t off_sel = 0, off_bin = 0, off_snap = 0;
+};
+
+// Steps 1, 2 and 5 of both lists -- they do not know the array type: K1, K2, the sort, the ISAC_MAX_TARGETS cut, every field of *out but azi and n_targets, and the upload of
+// the selected cells for the kernels of steps 3 and 4.
+int select_cells(isac_ctx* ctx, const char* who, isac_target_list* out, const isac_c64* snapshots, int32_t cap_snap, SelectedCells* sc) {
   const Fft2dCpi& ts = ctx->tgt;
-  if (!ctx->last.valid || ts.state != Fft2dCpi::kCollected)
-    return fail(ctx, ISAC_ERR_INVALID_ARG, "isac_fft2d_get_targets: no completed fft2D on this context whose range rows, power window and detection lists are still on the device");
-  if (ts.ep.array_is_upa) return fail(ctx, ISAC_ERR_UNSUPPORTED, "isac_fft2d_get_targets: ULA only");
   const isac_est_params& ep = ts.ep;
   const CutWindow& w = ts.win;
   const int hr = w.hr, hc = w.hc;
-  if (hr < 1 || hc < 1) return fail(ctx, ISAC_ERR_UNSUPPORTED, "isac_fft2d_get_targets: the local-maximum test needs a halo of at least one cell (guard + training) in both dimensions");
-  const int A = ts.A, L = ts.L, nr = w.nr, nc = w.nc, n_cut_rows = w.n_cut_rows, n_cut_cols = w.n_cut_cols, n_cut = (int)w.n_cut();
+  if (hr < 1 || hc < 1) return fail(ctx, ISAC_ERR_UNSUPPORTED, std::string(who) + ": the local-maximum test needs a halo of at least one cell (guard + training) in both dimensions");
+  const int A = ts.A, nr = w.nr, nc = w.nc, n_cut_rows = w.n_cut_rows, n_cut_cols = w.n_cut_cols, n_cut = (int)w.n_cut();
+  *sc = SelectedCells{};
   std::memset(out, 0, sizeof(*out));
   // one scratch block: [hits nr x nc | count (16 ints)] zeroed, then the candidate lists, the selected cells and their results
   const size_t n_map = (size_t)nr * nc;
@@ -177,8 +278,6 @@ extern "C" int isac_fft2d_get_targets(isac_ctx* ctx, isac_target_list* out, isac
   const size_t off_azi = off_sel + sizeof(int) * 2 * ISAC_MAX_TARGETS, off_snap = (off_azi + sizeof(int) * ISAC_MAX_TARGETS + 15) & ~(size_t)15;
   ISAC_TRY(ensure(ctx, ctx->tgt_scratch, off_snap + sizeof(c64) * (size_t)A * ISAC_MAX_TARGETS));
   char* d = (char*)ctx->tgt_scratch.p;
-  const c64* twd = nullptr;
-  ISAC_TRY(isac_get_twiddles(ctx, ep.n_fft, &twd));
   ISAC_HIP(hipMemsetAsync(d, 0, off_ccut, ctx->stream));
   hipLaunchKernelGGL(target_hits_kernel, dim3(std::min(cdiv(ts.cap, 256), 8u), A), dim3(256), 0, ctx->stream, (const int*)ctx->det_cut.p, (const int*)ctx->det_cnt.p, ts.cap,
                      n_cut_rows, n_cut, hr, hc, nr, (int*)d);
@@ -205,7 +304,7 @@ extern "C" int isac_fft2d_get_targets(isac_ctx* ctx, isac_target_list* out, isac
     return ccut[(size_t)p] < ccut[(size_t)q];
   });
   const int n = std::min(n_total, (int)ISAC_MAX_TARGETS);
-  if (snapshots && n > cap_snap) return fail(ctx, ISAC_ERR_CAPACITY, "isac_fft2d_get_targets: more targets than snapshot columns");
+  if (snapshots && n > cap_snap) return fail(ctx, ISAC_ERR_CAPACITY, std::string(who) + ": more targets than snapshot columns");
   std::vector<int> sel((size_t)2 * n);                                    // [window row | rdm column], 0-based
   for (int i = 0; i < n; ++i) {
     const int o = order[(size_t)i];
@@ -220,15 +319,92 @@ extern "C" int isac_fft2d_get_targets(isac_ctx* ctx, isac_target_list* out, isac
     sel[(size_t)n + i] = rc.col - 1;
   }
   ISAC_TRY(stage_upload(ctx, d + off_sel, sel.data(), sizeof(int) * sel.size()));
+  *sc = SelectedCells{n, d, off_sel, off_azi, off_snap};
+  return ISAC_OK;
+}
+
+// The scan bins of the n selected cells and, when asked for, their snapshots: complete when it returns
+int fetch_bins(isac_ctx* ctx, const SelectedCells& sc, int A, std::vector<int>& bins, isac_c64* snapshots) {
+  bins.resize((size_t)sc.n);
+  ISAC_TRY(copy_d2h(ctx, bins.data(), sc.d + sc.off_bin, sizeof(int) * (size_t)sc.n));
+  if (snapshots) ISAC_TRY(copy_d2h(ctx, snapshots, sc.d + sc.off_snap, sizeof(c64) * (size_t)A * sc.n));
+  return ISAC_OK;
+}
+
+}  // namespace
+
+extern "C" int isac_fft2d_get_targets(isac_ctx* ctx, isac_target_list* out, isac_c64* snapshots, int32_t cap_snap) {
+  ISAC_ENTER(ctx);
+  ISAC_TRY(cpi_ready(ctx, "isac_fft2d_get_targets", out, snapshots, cap_snap));
+  const Fft2dCpi& ts = ctx->tgt;
+  if (ts.ep.array_is_upa) return fail(ctx, ISAC_ERR_UNSUPPORTED, "isac_fft2d_get_targets: ULA only");
+  const isac_est_params& ep = ts.ep;
+  const int A = ts.A;
+  SelectedCells sc;
+  ISAC_TRY(select_cells(ctx, "isac_fft2d_get_targets", out, snapshots, cap_snap, &sc));
+  if (sc.n == 0) return ISAC_OK;
+  const int n = sc.n;
+  const c64* twd = nullptr;
+  ISAC_TRY(isac_get_twiddles(ctx, ep.n_fft, &twd));
   const size_t lds = sizeof(c64) * (size_t)A;
   ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(target_doa_kernel), lds));
-  hipLaunchKernelGGL(target_doa_kernel, dim3(n), dim3(256), lds, ctx->stream, (const c64*)ctx->ymid.p, nr, L, A, ep.n_fft, twd, std::sqrt((double)ep.n_fft),
-                     (const int*)(d + off_sel), (const int*)(d + off_sel) + n, ts.d_sind, ts.n_steps, 0.5, (int*)(d + off_azi), (c64*)(d + off_snap));
+  hipLaunchKernelGGL(target_doa_kernel, dim3(n), dim3(256), lds, ctx->stream, (const c64*)ctx->ymid.p, ts.win.nr, ts.L, A, ep.n_fft, twd, std::sqrt((double)ep.n_fft),
+                     (const int*)(sc.d + sc.off_sel), (const int*)(sc.d + sc.off_sel) + n, ts.d_sind, ts.n_steps, 0.5, (int*)(sc.d + sc.off_bin), (c64*)(sc.d + sc.off_snap));
   ISAC_HIP(hipGetLastError());
-  std::vector<int> bins((size_t)n);
-  ISAC_TRY(copy_d2h(ctx, bins.data(), d + off_azi, sizeof(int) * (size_t)n));
-  if (snapshots) ISAC_TRY(copy_d2h(ctx, snapshots, d + off_snap, sizeof(c64) * (size_t)A * n));
+  std::vector<int> bins;
+  ISAC_TRY(fetch_bins(ctx, sc, A, bins, snapshots));
   for (int i = 0; i < n; ++i) out->azi[i] = bins[(size_t)i] * ep.azimuth_scan_granularity - ep.azimuth_scan_scale / 2.0;   // music.m:103
+  out->n_targets = n;
+  return ISAC_OK;
+}
+
+extern "C" int isac_fft2d_get_targets_upa(isac_ctx* ctx, isac_target_list* out, double* ele, isac_c64* snapshots, int32_t cap_snap) {
+  ISAC_ENTER(ctx);
+  if (!ele) return fail(ctx, ISAC_ERR_INVALID_ARG, "NULL argument");
+  ISAC_TRY(cpi_ready(ctx, "isac_fft2d_get_targets_upa", out, snapshots, cap_snap));
+  const Fft2dCpi& ts = ctx->tgt;
+  if (!ts.ep.array_is_upa) return fail(ctx, ISAC_ERR_UNSUPPORTED, "isac_fft2d_get_targets_upa: a planar array only; isac_fft2d_get_targets is the list of a ULA");
+  const isac_est_params& ep = ts.ep;
+  const int A = ts.A;
+  const double* d_tab = nullptr;
+  int e_steps = 0, a_steps = 0;
+  ISAC_TRY(isac_doa2d_grid(ctx, &ep, A, &d_tab, &e_steps, &a_steps));     // n_ants_x n_ants_y != A: ISAC_ERR_INVALID_ARG; A > 256: ISAC_ERR_UNSUPPORTED
+  SelectedCells sc;
+  ISAC_TRY(select_cells(ctx, "isac_fft2d_get_targets_upa", out, snapshots, cap_snap, &sc));
+  if (sc.n == 0) return ISAC_OK;
+  const int n = sc.n;
+  const c64* twd = nullptr;
+  ISAC_TRY(isac_get_twiddles(ctx, ep.n_fft, &twd));
+  const int pt = A <= 64 ? 64 : A <= 128 ? 32 : 16;                       // the steering tile [A x pt] c64 fits 64 KB of LDS
+  const long long n_pts = (long long)e_steps * a_steps;
+  const unsigned n_tiles = cdiv(n_pts, pt);
+  ISAC_TRY(ensure(ctx, ctx->tgt_part, (sizeof(double) + sizeof(int)) * (size_t)n_tiles * n));
+  double* part_val = (double*)ctx->tgt_part.p;
+  int* part_idx = (int*)(part_val + (size_t)n_tiles * n);
+  c64* d_snap = (c64*)(sc.d + sc.off_snap);
+  ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(target_snap_kernel), sizeof(c64) * (size_t)A));
+  hipLaunchKernelGGL(target_snap_kernel, dim3(n), dim3(256), sizeof(c64) * (size_t)A, ctx->stream, (const c64*)ctx->ymid.p, ts.win.nr, ts.L, A, ep.n_fft, twd,
+                     std::sqrt((double)ep.n_fft), (const int*)(sc.d + sc.off_sel), (const int*)(sc.d + sc.off_sel) + n, d_snap);
+  ISAC_HIP(hipGetLastError());
+#define ISAC_TARGET_SCAN2D(PT_)                                                                                                                          \
+  do {                                                                                                                                                   \
+    const size_t lds = sizeof(c64) * (size_t)A * PT_;                                                                                                    \
+    ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(target_scan2d_kernel<PT_>), lds));                                                             \
+    hipLaunchKernelGGL(target_scan2d_kernel<PT_>, dim3(n_tiles), dim3(256), lds, ctx->stream, d_tab, e_steps, a_steps, ep.n_ants_x, ep.n_ants_y,         \
+                       (const c64*)d_snap, n, part_val, part_idx);                                                                                       \
+  } while (0)
+  if (pt == 64) ISAC_TARGET_SCAN2D(64); else if (pt == 32) ISAC_TARGET_SCAN2D(32); else ISAC_TARGET_SCAN2D(16);
+#undef ISAC_TARGET_SCAN2D
+  ISAC_HIP(hipGetLastError());
+  hipLaunchKernelGGL(target_scan2d_reduce_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ctx->stream, (const double*)part_val, (const int*)part_idx, (int)n_tiles, n,
+                     (int*)(sc.d + sc.off_bin));
+  ISAC_HIP(hipGetLastError());
+  std::vector<int> bins;
+  ISAC_TRY(fetch_bins(ctx, sc, A, bins, snapshots));
+  for (int i = 0; i < n; ++i) {                                           // j = e + eSteps a   music.m:70-71
+    out->azi[i] = (bins[(size_t)i] / e_steps) * ep.azimuth_scan_granularity - ep.azimuth_scan_scale / 2.0;
+    ele[i] = (bins[(size_t)i] % e_steps) * ep.elevation_scan_granularity - ep.elevation_scan_scale / 2.0;
+  }
   out->n_targets = n;
   return ISAC_OK;
 }

@@ -20,7 +20,7 @@ def getRMSE(radarEstResults, radarEstParams):
     resolution cell of it, and of the velocity / azimuth (/ elevation, UPA only) estimates at the same index (getRMSE.m:42-61).
 
     ``radarEstResults``: the estResults of sensing.estimation.fft2D / music2D / redetect (``rngEst, velEst, aziEst, eleEst``), or the dict of
-    sensing.estimation.targetList (``rng, vel, azi``).  The reference indexes the three estimate lists with one index r although fft2D forms them independently
+    sensing.estimation.targetList (``rng, vel, azi``) or, for a UPA, of sensing.estimation.targetListUPA (which adds ``ele``).  The reference indexes the three estimate lists with one index r although fft2D forms them independently
     (fft2D.m:96-99); the target list pairs them per detection, which makes it the meaningful input.  ``radarEstParams``: ``rRes``, ``antennaType`` and
     ``targetRealPos`` of sensing.radarParams -- the reference reads ``tgtRealPos``, a field radarParams.m never sets (radarParams.m:137-144 names it targetRealPos), and
     tests the array's MATLAB class; here the UPA test is ``antennaType.kind == "upa"``.
@@ -33,9 +33,10 @@ def getRMSE(radarEstResults, radarEstParams):
     truth = _field(radarEstParams, "targetRealPos")
     rng_real, vel_real, ele_real, azi_real = (_vec([t[k] for t in truth]) for k in ("Range", "Velocity", "Elevation", "Azimuth"))   # :17-20
     if isinstance(radarEstResults, dict) and "rng" in radarEstResults:                                # sensing.estimation.targetList
-        if is_upa:
+        if is_upa and "ele" not in radarEstResults:                                                   # targetList's dict; targetListUPA's carries ele
             raise ValueError("getRMSE: the target list carries no elevation (it is refused for a UPA)")
-        rng_est, vel_est, azi_est, ele_est = _vec(radarEstResults["rng"]), _vec(radarEstResults["vel"]), _vec(radarEstResults["azi"]), None
+        rng_est, vel_est, azi_est = _vec(radarEstResults["rng"]), _vec(radarEstResults["vel"]), _vec(radarEstResults["azi"])
+        ele_est = _vec(radarEstResults["ele"]) if is_upa else None
     else:
         rng_est, vel_est, azi_est = (_vec(_field(radarEstResults, k)) for k in ("rngEst", "velEst", "aziEst"))   # :22-29
         ele_est = _vec(_field(radarEstResults, "eleEst")) if is_upa else None
