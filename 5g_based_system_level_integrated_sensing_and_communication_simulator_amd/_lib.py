@@ -17,6 +17,7 @@ _lock = threading.Lock()
 ISAC_ABI_VERSION = 8          # include/isac.h ISAC_ABI_VERSION this binding was written against (checked at load)
 ISAC_MAX_EST = 4096
 ISAC_MAX_TARGETS = 1024
+ISAC_MAX_BEAMS = 1024
 NOISE_NONE, NOISE_INJECTED, NOISE_PHILOX, NOISE_PHILOX_SPECTRAL, NOISE_INJECTED_SPECTRAL = 0, 1, 2, 3, 4
 CFAR_CA, CFAR_GOCA, CFAR_SOCA, CFAR_OS = 0, 1, 2, 3      # ISAC_CFAR_* (include/isac_cfar.h)
 CFAR_METHODS = {"CA": CFAR_CA, "GOCA": CFAR_GOCA, "SOCA": CFAR_SOCA, "OS": CFAR_OS}
@@ -247,6 +248,11 @@ PROTOTYPES_LAZY_COV = {
 PROTOTYPES_TARGETS_UPA = {
     "isac_fft2d_get_targets_upa": (_INT, (_P, _P, _P, _P, _I32)),
 }
+# ... and include/isac_beams.h (tests/test_beam_detect_cpu.py pins it)
+PROTOTYPES_BEAMS = {
+    "isac_fft2d_get_rdm_window": (_INT, (_P, _P, _I64, _P, _P, _P)),
+    "isac_fft2d_beam_detect": (_INT, (_P, _P, _I32, _P, _ptr(CfarMethod), _P, _P, _P, _P, _I32, _P, _P, _P)),
+}
 
 
 def library_path() -> str:
@@ -273,7 +279,7 @@ def load():
             except Exception:
                 pass
         lib = C.CDLL(_LIB_PATH, mode=C.RTLD_GLOBAL)
-        for name, (restype, argtypes) in {**PROTOTYPES, **PROTOTYPES_ADDED, **PROTOTYPES_CFAR, **PROTOTYPES_CFAR_MC, **PROTOTYPES_LAZY_COV, **PROTOTYPES_TARGETS_UPA}.items():
+        for name, (restype, argtypes) in {**PROTOTYPES, **PROTOTYPES_ADDED, **PROTOTYPES_CFAR, **PROTOTYPES_CFAR_MC, **PROTOTYPES_LAZY_COV, **PROTOTYPES_TARGETS_UPA, **PROTOTYPES_BEAMS}.items():
             fn = getattr(lib, name)  # AttributeError here = ABI drift between isac.h and the .so
             fn.restype, fn.argtypes = restype, argtypes
         # the library writes whole structs into caller memory: version AND struct sizes must match this binding's mirrors

@@ -3,6 +3,7 @@
 //   isac_cfar_threshold_factor   host only: the 'Auto' factor of a method
 //   isac_cfar2d                  an arbitrary map and CUT list (isac_cfar2d_ca with the method block)
 //   isac_fft2d_redetect          the power window of the last completed fft2D, detected again; then the host half of fft2D.m:63-99 on the new lists
+//   cfar_detect_planes           (internal) the device half of isac_fft2d_redetect on any planes with the window's geometry: also the detector of isac_fft2d_beam_detect (beams.hip)
 //   isac_cfar_monte_carlo        (include/isac_cfar_mc.h) drawn noise and a target through the same per-CUT function, counted: the detectors' Pfa / Pd as built
 // One per-CUT device function, cfar_cut<M>, serves both: K1 cfar_method_window_kernel stages a kPanelRows x pc tile of CUTs plus its halo of guard + training cells in LDS
 // and evaluates one CUT per lane into a flag per (CUT, antenna); K2 cfar_compact_kernel, one workgroup per antenna, turns the flags into the CUT-order list (rows
@@ -376,6 +377,70 @@ extern "C" int isac_cfar2d(isac_ctx* ctx, const double* P, int32_t n_rows, int32
   return ISAC_OK;
 }
 
+// The device half of isac_fft2d_redetect, on any planes [nr x nc x n_planes] with the geometry of the CPI's power window: detector m with the CPI's stored guard / training
+// bands and pfa on every plane over the stored CUT rectangle, the flags compacted into per-plane CUT-order lists.  Everything stays in `scratch` (described by *pl); the
+// counts and offsets are on the host when it returns.  who: the entry point, for the messages.
+int cfar_detect_planes(isac_ctx* ctx, const char* who, const isac_cfar_method* m, const double* d_planes, int n_planes, DevBuf& scratch, PlaneLists* pl) {
+  const Fft2dCpi& ts = ctx->tgt;
+  const isac_cfar_config& cf = ts.cfar;
+  WinGeom g{};
+  ISAC_TRY(cut_geom(ctx, cf.guard, cf.train, cf.pfa, m, &g.c));
+  g.nr = ts.win.nr; g.nc = ts.win.nc; g.n_cut_rows = ts.win.n_cut_rows; g.n_cut_cols = ts.win.n_cut_cols;   // (both >= 1: the submit that left the window refuses an empty zone)
+  const long long n_cut_ll = ts.win.n_cut();
+  if (n_cut_ll * n_planes > (1ll << 30)) return fail(ctx, ISAC_ERR_UNSUPPORTED, std::string(who) + ": more than 2^30 (CUT, plane) pairs");
+  const int n_cut = (int)n_cut_ll;
+  // CUT columns per workgroup: as many as fit ~128 KB of LDS with the panel's kPanelRows + 2 hr rows, at most one per wave quarter (kPanelColsMax)
+  const size_t budget = 128 * 1024;
+  const long long fit = (long long)(budget / (sizeof(double) * (size_t)(kPanelRows + 2 * g.c.hr))) - 2ll * g.c.hc;
+  if (fit < 1) return fail(ctx, ISAC_ERR_UNSUPPORTED, std::string(who) + ": guard + training band too large for the LDS-staged detector");
+  g.pc = (int)std::min<long long>(fit, std::min(kPanelColsMax, g.n_cut_cols));
+  const size_t lds = sizeof(double) * (size_t)(kPanelRows + 2 * g.c.hr) * (size_t)(g.pc + 2 * g.c.hc);
+  // every list sized for all CUTs: [det_pow n_planes n_cut | det_cut n_planes n_cut | det_cnt n_planes | row_seen n_cut_rows | flags n_planes n_cut]
+  const size_t n_pairs = (size_t)n_planes * n_cut;
+  const size_t off_cut = sizeof(double) * n_pairs, off_cnt = off_cut + sizeof(int) * n_pairs, off_rows = off_cnt + sizeof(int) * (size_t)n_planes;
+  const size_t off_flags = off_rows + sizeof(unsigned) * (size_t)g.n_cut_rows;
+  ISAC_TRY(ensure(ctx, scratch, off_flags + n_pairs));
+  char* d = (char*)scratch.p;
+  ISAC_HIP(hipMemsetAsync(d + off_rows, 0, sizeof(unsigned) * (size_t)g.n_cut_rows, ctx->stream));
+  CFAR_METHOD_DISPATCH(m->method, {
+    auto kern = cfar_method_window_kernel<M>;
+    ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(kern), lds));
+    hipLaunchKernelGGL(kern, dim3(cdiv(g.n_cut_rows, kPanelRows), cdiv(g.n_cut_cols, g.pc), n_planes), dim3(kPanelRows * kPanelColsMax), lds, ctx->stream,
+                       d_planes, g, (unsigned char*)(d + off_flags));
+  });
+  ISAC_HIP(hipGetLastError());
+  hipLaunchKernelGGL(cfar_compact_kernel, dim3(n_planes), dim3(256), 0, ctx->stream, (const unsigned char*)(d + off_flags), d_planes, g.nr, g.nc, g.c.hr, g.c.hc,
+                     g.n_cut_rows, n_cut, (int*)(d + off_cut), (double*)d, (int*)(d + off_cnt), (unsigned*)(d + off_rows));
+  ISAC_HIP(hipGetLastError());
+  std::vector<int> tail((size_t)n_planes + g.n_cut_rows);       // [det_cnt | row_seen]
+  ISAC_TRY(copy_d2h(ctx, tail.data(), d + off_cnt, sizeof(int) * tail.size()));
+  pl->off.assign((size_t)n_planes + 1, 0);
+  long long total_ll = 0;
+  for (int a = 0; a < n_planes; ++a) {
+    if (tail[(size_t)a] < 0 || tail[(size_t)a] > n_cut) return fail(ctx, ISAC_ERR_HIP, "internal: detection count outside 0..nCUT");
+    total_ll += tail[(size_t)a];
+    pl->off[(size_t)a + 1] = (int)total_ll;
+  }
+  pl->rows_seen = 0;
+  for (int r = 0; r < g.n_cut_rows; ++r) pl->rows_seen += tail[(size_t)n_planes + r] ? 1 : 0;
+  pl->n_planes = n_planes; pl->n_cut = n_cut;
+  pl->d_pow = (const double*)d; pl->d_cut = (const int*)(d + off_cut); pl->d_cnt = (const int*)(d + off_cnt);
+  return ISAC_OK;
+}
+
+// ... and its lists on the host, plane after plane: cut [total] CUT ordinals, pw [total] the CUTs' powers
+int cfar_fetch_lists(isac_ctx* ctx, const PlaneLists& pl, std::vector<int>& cut, std::vector<double>& pw) {
+  cut.resize((size_t)pl.total());
+  pw.resize((size_t)pl.total());
+  for (int a = 0; a < pl.n_planes; ++a) {
+    const size_t b = (size_t)pl.off[(size_t)a], n = (size_t)(pl.off[(size_t)a + 1] - pl.off[(size_t)a]);
+    if (!n) continue;
+    ISAC_TRY(copy_d2h(ctx, cut.data() + b, pl.d_cut + (size_t)a * pl.n_cut, sizeof(int) * n));
+    ISAC_TRY(copy_d2h(ctx, pw.data() + b, pl.d_pow + (size_t)a * pl.n_cut, sizeof(double) * n));
+  }
+  return ISAC_OK;
+}
+
 extern "C" int isac_fft2d_redetect(isac_ctx* ctx, const isac_cfar_method* m, isac_est_result* out, int32_t* det_idx, double* det_pow, int32_t cap,
                                    int32_t* ant_offsets, int32_t* n_total) {
   ISAC_ENTER(ctx);
@@ -383,63 +448,18 @@ extern "C" int isac_fft2d_redetect(isac_ctx* ctx, const isac_cfar_method* m, isa
   const Fft2dCpi& ts = ctx->tgt;
   if (!ctx->last.valid || ts.state != Fft2dCpi::kCollected)
     return fail(ctx, ISAC_ERR_INVALID_ARG, "isac_fft2d_redetect: no completed fft2D on this context whose power window is still on the device");
-  const isac_cfar_config& cf = ts.cfar;
-  WinGeom g{};
-  ISAC_TRY(cut_geom(ctx, cf.guard, cf.train, cf.pfa, m, &g.c));
   const int A = ts.A;
-  g.nr = ts.win.nr; g.nc = ts.win.nc; g.n_cut_rows = ts.win.n_cut_rows; g.n_cut_cols = ts.win.n_cut_cols;   // (both >= 1: the submit that left the window refuses an empty zone)
-  const long long n_cut_ll = ts.win.n_cut();
-  if (n_cut_ll * A > (1ll << 30)) return fail(ctx, ISAC_ERR_UNSUPPORTED, "isac_fft2d_redetect: more than 2^30 (CUT, antenna) pairs");
-  const int n_cut = (int)n_cut_ll;
+  PlaneLists pl;
+  ISAC_TRY(cfar_detect_planes(ctx, "isac_fft2d_redetect", m, (const double*)ctx->pwin.p, A, ctx->redet, &pl));
   std::memset(out, 0, sizeof(*out));
-  // CUT columns per workgroup: as many as fit ~128 KB of LDS with the panel's kPanelRows + 2 hr rows, at most one per wave quarter (kPanelColsMax)
-  const size_t budget = 128 * 1024;
-  const long long fit = (long long)(budget / (sizeof(double) * (size_t)(kPanelRows + 2 * g.c.hr))) - 2ll * g.c.hc;
-  if (fit < 1) return fail(ctx, ISAC_ERR_UNSUPPORTED, "isac_fft2d_redetect: guard + training band too large for the LDS-staged detector");
-  g.pc = (int)std::min<long long>(fit, std::min(kPanelColsMax, g.n_cut_cols));
-  const size_t lds = sizeof(double) * (size_t)(kPanelRows + 2 * g.c.hr) * (size_t)(g.pc + 2 * g.c.hc);
-  // scratch of its own, every list sized for all CUTs: [det_pow A n_cut | det_cut A n_cut | det_cnt A | row_seen n_cut_rows | flags A n_cut]
-  const size_t n_pairs = (size_t)A * n_cut;
-  const size_t off_cut = sizeof(double) * n_pairs, off_cnt = off_cut + sizeof(int) * n_pairs, off_rows = off_cnt + sizeof(int) * (size_t)A;
-  const size_t off_flags = off_rows + sizeof(unsigned) * (size_t)g.n_cut_rows;
-  ISAC_TRY(ensure(ctx, ctx->redet, off_flags + n_pairs));
-  char* d = (char*)ctx->redet.p;
-  ISAC_HIP(hipMemsetAsync(d + off_rows, 0, sizeof(unsigned) * (size_t)g.n_cut_rows, ctx->stream));
-  CFAR_METHOD_DISPATCH(m->method, {
-    auto kern = cfar_method_window_kernel<M>;
-    ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(kern), lds));
-    hipLaunchKernelGGL(kern, dim3(cdiv(g.n_cut_rows, kPanelRows), cdiv(g.n_cut_cols, g.pc), A), dim3(kPanelRows * kPanelColsMax), lds, ctx->stream,
-                       (const double*)ctx->pwin.p, g, (unsigned char*)(d + off_flags));
-  });
-  ISAC_HIP(hipGetLastError());
-  hipLaunchKernelGGL(cfar_compact_kernel, dim3(A), dim3(256), 0, ctx->stream, (const unsigned char*)(d + off_flags), (const double*)ctx->pwin.p, g.nr, g.nc, g.c.hr, g.c.hc,
-                     g.n_cut_rows, n_cut, (int*)(d + off_cut), (double*)d, (int*)(d + off_cnt), (unsigned*)(d + off_rows));
-  ISAC_HIP(hipGetLastError());
-  std::vector<int> tail((size_t)A + g.n_cut_rows);              // [det_cnt | row_seen]
-  ISAC_TRY(copy_d2h(ctx, tail.data(), d + off_cnt, sizeof(int) * tail.size()));
-  std::vector<int> ant_off((size_t)A + 1, 0);
-  long long total_ll = 0;
-  for (int a = 0; a < A; ++a) {
-    if (tail[(size_t)a] < 0 || tail[(size_t)a] > n_cut) return fail(ctx, ISAC_ERR_HIP, "internal: detection count outside 0..nCUT");
-    total_ll += tail[(size_t)a];
-    ant_off[(size_t)a + 1] = (int)total_ll;
-  }
-  const int total = (int)total_ll;
-  int num_dets_dev = 0;
-  for (int r = 0; r < g.n_cut_rows; ++r) num_dets_dev += tail[(size_t)A + r] ? 1 : 0;
-  if (n_total) *n_total = total;
-  if (ant_offsets) std::copy(ant_off.begin(), ant_off.end(), ant_offsets);
-  if (total > cap) return fail(ctx, ISAC_ERR_CAPACITY, "detection list larger than capacity");
-  std::vector<int> cut((size_t)total);
-  std::vector<double> pw((size_t)total);
-  for (int a = 0; a < A; ++a) {
-    const size_t b = (size_t)ant_off[(size_t)a], n = (size_t)tail[(size_t)a];
-    if (!n) continue;
-    ISAC_TRY(copy_d2h(ctx, cut.data() + b, d + off_cut + sizeof(int) * (size_t)a * n_cut, sizeof(int) * n));
-    ISAC_TRY(copy_d2h(ctx, pw.data() + b, d + sizeof(double) * (size_t)a * n_cut, sizeof(double) * n));
-  }
+  if (n_total) *n_total = pl.total();
+  if (ant_offsets) std::copy(pl.off.begin(), pl.off.end(), ant_offsets);
+  if (pl.total() > cap) return fail(ctx, ISAC_ERR_CAPACITY, "detection list larger than capacity");
+  std::vector<int> cut;
+  std::vector<double> pw;
+  ISAC_TRY(cfar_fetch_lists(ctx, pl, cut, pw));
   std::vector<int32_t> det_rc;
-  ISAC_TRY(fft2d_estimates(ctx, &ts.ep, ts.win, A, ant_off.data(), cut, pw, num_dets_dev, det_rc, out));   // fft2D.m:63-99; n_azi stays 0
+  ISAC_TRY(fft2d_estimates(ctx, &ts.ep, ts.win, A, pl.off.data(), cut, pw, pl.rows_seen, det_rc, out));   // fft2D.m:63-99; n_azi stays 0
   if (det_idx) std::copy(det_rc.begin(), det_rc.end(), det_idx);
   if (det_pow) std::copy(pw.begin(), pw.end(), det_pow);
   return ISAC_OK;

@@ -36,11 +36,37 @@ bool cut_rows_ok(const isac_est_params* ep, const isac_cfar_config* cf, isac::Cu
 int cut_rows(isac_ctx* ctx, const isac_est_params* ep, const isac_cfar_config* cf, isac::CutRows* out);   // ... as ISAC_ERR_CFAR_WINDOW
 int isac_range_stage_into_cache(isac_ctx* ctx, const isac_est_params* ep, const isac_cfar_config* cf, const isac::c64* d_rx, const isac::c64* d_tx, int K, int L, int A);
 // ---------------------------------------------------------------- targets.hip: isac_fft2d_get_targets (include/isac_targets.h) and isac_fft2d_get_targets_upa (include/isac_targets_upa.h) -- the per-target
-// list of the last completed fft2D.  It calls nothing but isac_get_twiddles and (UPA) isac_doa2d_grid and is called by no other unit; what it shares with them is ctx->tgt
-// (isac::Fft2dCpi, isac_common.hpp): fft2d.hip fills it, rdm.hip / echo.hip drop it.
+// list of the last completed fft2D.  It calls nothing but isac_get_twiddles and (UPA) isac_doa2d_grid; beams.hip calls its target_cells_of_planes (below).  What it shares with the
+// other units is ctx->tgt (isac::Fft2dCpi, isac_common.hpp): fft2d.hip fills it, rdm.hip / echo.hip drop it.
 // ---------------------------------------------------------------- cfar.hip: the GOCA / SOCA / OS detectors (include/isac_cfar.h): isac_cfar2d, isac_fft2d_redetect, isac_cfar_threshold_factor.  Reads ctx->tgt and
-// ctx->pwin, writes ctx->redet only; calls cfar_alpha (rdm.hip) and fft2d_estimates (fft2d.hip).  Also isac_cfar_monte_carlo (include/isac_cfar_mc.h): reads nothing of the
+// ctx->pwin, writes ctx->redet only; calls cfar_alpha (rdm.hip) and fft2d_estimates (fft2d.hip).  cfar_detect_planes (below) is its device half, shared with beams.hip.  Also isac_cfar_monte_carlo (include/isac_cfar_mc.h): reads nothing of the
 // context, writes ctx->cfar_mc only.
+// the detector of isac_fft2d_redetect on any planes with the power window's geometry (callers: isac_fft2d_redetect, isac_fft2d_beam_detect): per-plane CUT-order lists in `scratch`
+namespace isac {
+struct PlaneLists {
+  int n_planes = 0, n_cut = 0;             // every plane's list has room for all n_cut CUTs: plane a at d_cut + a n_cut, d_pow + a n_cut
+  const double* d_pow = nullptr; const int* d_cut = nullptr; const int* d_cnt = nullptr;   // device: the CUTs' powers, CUT ordinals, counts [n_planes]
+  std::vector<int> off;                    // host [n_planes + 1]: offsets of the concatenated lists
+  int rows_seen = 0;                       // distinct CUT rows with a detection (numDets)
+  int total() const { return off.empty() ? 0 : off.back(); }
+};
+}
+int cfar_detect_planes(isac_ctx* ctx, const char* who, const isac_cfar_method* m, const double* d_planes, int n_planes, isac::DevBuf& scratch, isac::PlaneLists* pl);
+int cfar_fetch_lists(isac_ctx* ctx, const isac::PlaneLists& pl, std::vector<int>& cut, std::vector<double>& pw);
+// ---------------------------------------------------------------- targets.hip, for beams.hip: steps 1, 2 and 5 of the lists (hits, local maxima of the map, order, every field of *out but azi and n_targets) on the
+// planes [nr x nc x n_planes] and per-plane lists of `src`
+namespace isac {
+struct PlaneCells {
+  const double* planes; int n_planes;
+  const int* det_cut; const int* det_cnt; int cap;   // device: CUT ordinals [n_planes x cap], counts [n_planes]
+  bool take_max;                           // false: the map is the sum over the planes; true: their maximum, and best_plane[i] (host, [ISAC_MAX_TARGETS], 0-based) its first plane
+  DevBuf* scratch;
+  int32_t* best_plane;
+};
+}
+int target_cells_of_planes(isac_ctx* ctx, const char* who, const isac::PlaneCells& src, isac_target_list* out);
+// ---------------------------------------------------------------- beams.hip: isac_fft2d_get_rdm_window, isac_fft2d_beam_detect (include/isac_beams.h) -- the complex window of the last completed fft2D and CFAR on
+// beam planes of it.  Reads ctx->tgt and ctx->ymid, writes ctx->beam_y / beam_p / beam_det / beam_sel only; calls isac_get_twiddles, cfar_detect_planes and target_cells_of_planes.
 // ---------------------------------------------------------------- fft2d.hip: the host side of the fft2D pipeline -- submit, collect, submit_n / collect_n, the host-array call, the getters
 // host half of fft2D.m:63-99 on per-antenna CUT-order lists (callers: isac_fft2d_collect, isac_fft2d_redetect)
 int fft2d_estimates(isac_ctx* ctx, const isac_est_params* ep, const isac::CutWindow& win, int A, const int* ant_off, const std::vector<int>& cut, const std::vector<double>& pw, int num_dets_dev, std::vector<int32_t>& det_rc, isac_est_result* out);

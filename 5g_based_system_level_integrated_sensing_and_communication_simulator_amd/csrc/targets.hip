@@ -13,10 +13,13 @@
 // K4 target_snap_kernel writes the snapshots [A x n]; K5 target_scan2d_kernel, one workgroup per tile of PT scan points, forms the steering tile in LDS ONCE and runs every
 // snapshot over it -- eSteps aSteps A sincos in all, not that many per target -- leaving one (max, lowest j) per (tile, target); K6 target_scan2d_reduce_kernel joins each
 // target's partials in ascending tile order.  No floating-point atomics, no order that depends on arrival: the result is a function of the snapshots alone.
+// isac_fft2d_beam_detect (include/isac_beams.h, beams.hip) runs steps 1, 2 and 5 on its beam planes and per-beam lists through target_cells_of_planes: the same host function
+// (select_cells) and K1, K2 with the map M = the maximum over the planes in place of their sum (target_cells_kernel<true>); step 3's chain is csrc/rdm_cell.hpp, shared with it.
 #include <algorithm>
 #include <numeric>
 
 #include "isac_internal.hpp"
+#include "rdm_cell.hpp"
 #include "upa_steer.hpp"
 
 namespace isac {
@@ -41,12 +44,16 @@ __global__ __launch_bounds__(256) void target_hits_kernel(const int* __restrict_
 // and one atomicAdd per wave; their order is whatever the waves arrive in -- the host sorts.
 constexpr int kCellR = 32, kCellC = 8;
 
+// MAX (isac_fft2d_beam_detect, whose planes are beams): the map is M = the maximum over the planes instead of their sum, and each candidate carries the plane of its
+// maximum -- the first one in ascending plane order; a NaN never wins, and M is NaN only where every plane is.
+template <bool MAX>
 __global__ __launch_bounds__(kCellR * kCellC) void target_cells_kernel(const double* __restrict__ pwin /* [nr x nc x A] */, int nr, int nc, int A, int hr, int hc,
                                                                        int n_cut_rows, int n_cut_cols, const int* __restrict__ hits,
                                                                        unsigned* __restrict__ count, int* __restrict__ cand_cut /* [n_cut] CUT ordinal */,
-                                                                       int* __restrict__ cand_hits, double* __restrict__ cand_s) {
+                                                                       int* __restrict__ cand_hits, double* __restrict__ cand_s, int* __restrict__ cand_plane /* MAX only */) {
   constexpr int SR = kCellR + 2, SC = kCellC + 2;
   __shared__ double s_s[SC * SR];                                         // column-major tile + rim
+  __shared__ int s_plane[MAX ? SC * SR : 1];
   const int tid = threadIdx.x;
   const int r0 = blockIdx.x * kCellR, c0 = blockIdx.y * kCellC;           // first CUT row / column of the tile (0-based)
   const long long plane = (long long)nr * nc;
@@ -56,8 +63,17 @@ __global__ __launch_bounds__(kCellR * kCellC) void target_cells_kernel(const dou
     double s = __builtin_nan("");                                          // past the window (a tile that overhangs the zone): never a valid cell's neighbour
     if (wr < nr && wc < nc) {
       const double* p = pwin + wr + (long long)nr * wc;
-      s = 0.0;
-      for (int a = 0; a < A; ++a) s = __dadd_rn(s, p[plane * a]);         // ascending antenna order, from 0.0
+      if constexpr (MAX) {
+        int best = 0;
+        for (int a = 0; a < A; ++a) {
+          const double v = p[plane * a];
+          if (v > s || (s != s && v == v)) { s = v; best = a; }           // strictly greater: the first maximum stays
+        }
+        s_plane[lc * SR + lr] = best;
+      } else {
+        s = 0.0;
+        for (int a = 0; a < A; ++a) s = __dadd_rn(s, p[plane * a]);       // ascending antenna order, from 0.0
+      }
     }
     s_s[lc * SR + lr] = s;
   }
@@ -84,6 +100,7 @@ __global__ __launch_bounds__(kCellR * kCellC) void target_cells_kernel(const dou
       cand_cut[pos] = cr + n_cut_rows * cc;
       cand_hits[pos] = h;
       cand_s[pos] = v;
+      if constexpr (MAX) cand_plane[pos] = s_plane[(lc + 1) * SR + (lr + 1)];
     }
   }
 }
@@ -100,28 +117,14 @@ __device__ __forceinline__ void target_snapshot(const c64* __restrict__ ymid /* 
                                                 const c64* __restrict__ tw_d /* e^{-2 pi j m / n_fft} */, double sqrt_nfft, int row /* window row, 0-based */,
                                                 int c /* rdm column, 0-based */, c64* s_x /* LDS [A] */) {
   const int tid = threadIdx.x;
-  const int Lu = L < n_fft ? L : n_fft;                                   // fft(., nFFT, 2) truncates when L > nFFT
-  const int half = L / 2;                                                 // ifftshift over the symbols
-  const int kbin = (c + n_fft / 2) % n_fft;                               // fftshift: column c <-> bin (c + nFFT/2) mod nFFT
-  const int chunk = (Lu + 3) / 4;
+  const int kbin = rdm_bin_of_column(c, n_fft);
   for (int base = 0; base < 4 * A; base += 256) {                         // (256 = 64 quads: a quad is inside one wave and all of it active or none)
     const int a = (base + tid) >> 2, part = tid & 3;
     c64 acc = mk(0.0, 0.0);
-    if (a < A) {
-      const int li0 = part * chunk, li1 = min(li0 + chunk, Lu);
-      int m = (int)(((long long)li0 * kbin) % n_fft);
-      const c64* col = ymid + row + (long long)n_rows * L * a;
-      for (int li = li0; li < li1; ++li) {
-        int lsrc = li + half;
-        if (lsrc >= L) lsrc -= L;
-        acc = fma(col[(long long)n_rows * lsrc], tw_d[m], acc);
-        m += kbin;
-        if (m >= n_fft) m -= n_fft;
-      }
-    }
+    if (a < A) acc = rdm_cell_quarter(ymid + row + (long long)n_rows * L * a, n_rows, L, n_fft, kbin, part, tw_d);   // the chain of a cell: rdm_cell.hpp
     acc.re += __shfl_xor(acc.re, 1); acc.im += __shfl_xor(acc.im, 1);
     acc.re += __shfl_xor(acc.re, 2); acc.im += __shfl_xor(acc.im, 2);
-    if (a < A && part == 0) s_x[a] = mk(acc.re / sqrt_nfft, acc.im / sqrt_nfft);   // fft(.)/sqrt(nFFT)  fft2D.m:46
+    if (a < A && part == 0) s_x[a] = rdm_cell_scale(acc, sqrt_nfft);
   }
   __syncthreads();
 }
@@ -260,30 +263,34 @@ struct SelectedCells {
   size_t off_sel = 0, off_bin = 0, off_snap = 0;
 };
 
-// Steps 1, 2 and 5 of both lists -- they do not know the array type: K1, K2, the sort, the ISAC_MAX_TARGETS cut, every field of *out but azi and n_targets, and the upload of
-// the selected cells for the kernels of steps 3 and 4.
-int select_cells(isac_ctx* ctx, const char* who, isac_target_list* out, const isac_c64* snapshots, int32_t cap_snap, SelectedCells* sc) {
+// Steps 1, 2 and 5 of both lists -- they do not know the array type: K1, K2, the sort, the ISAC_MAX_TARGETS cut, every field of *out but azi and n_targets, and (sc != NULL)
+// the upload of the selected cells for the kernels of steps 3 and 4.  src: the planes and per-plane lists the cells are taken from -- the power window and the CFAR lists of
+// the CPI for the two lists, the beam planes and per-beam lists for isac_fft2d_beam_detect (take_max: the map is the maximum over the planes, best_plane[i] its first plane).
+int select_cells(isac_ctx* ctx, const char* who, const PlaneCells& src, isac_target_list* out, const isac_c64* snapshots, int32_t cap_snap, SelectedCells* sc) {
   const Fft2dCpi& ts = ctx->tgt;
   const isac_est_params& ep = ts.ep;
   const CutWindow& w = ts.win;
   const int hr = w.hr, hc = w.hc;
   if (hr < 1 || hc < 1) return fail(ctx, ISAC_ERR_UNSUPPORTED, std::string(who) + ": the local-maximum test needs a halo of at least one cell (guard + training) in both dimensions");
   const int A = ts.A, nr = w.nr, nc = w.nc, n_cut_rows = w.n_cut_rows, n_cut_cols = w.n_cut_cols, n_cut = (int)w.n_cut();
-  *sc = SelectedCells{};
+  if (sc) *sc = SelectedCells{};
   std::memset(out, 0, sizeof(*out));
   // one scratch block: [hits nr x nc | count (16 ints)] zeroed, then the candidate lists, the selected cells and their results
   const size_t n_map = (size_t)nr * nc;
   const size_t off_cnt = sizeof(int) * n_map, off_ccut = off_cnt + 64, off_chit = off_ccut + sizeof(int) * (size_t)n_cut;
-  const size_t off_cs = (off_chit + sizeof(int) * (size_t)n_cut + 15) & ~(size_t)15, off_sel = off_cs + sizeof(double) * (size_t)n_cut;
+  const size_t off_cpl = off_chit + sizeof(int) * (size_t)n_cut;          // the candidates' planes: take_max only
+  const size_t off_cs = (off_cpl + (src.take_max ? sizeof(int) * (size_t)n_cut : 0) + 15) & ~(size_t)15, off_sel = off_cs + sizeof(double) * (size_t)n_cut;
   const size_t off_azi = off_sel + sizeof(int) * 2 * ISAC_MAX_TARGETS, off_snap = (off_azi + sizeof(int) * ISAC_MAX_TARGETS + 15) & ~(size_t)15;
-  ISAC_TRY(ensure(ctx, ctx->tgt_scratch, off_snap + sizeof(c64) * (size_t)A * ISAC_MAX_TARGETS));
-  char* d = (char*)ctx->tgt_scratch.p;
+  ISAC_TRY(ensure(ctx, *src.scratch, off_snap + (sc ? sizeof(c64) * (size_t)A * ISAC_MAX_TARGETS : 0)));
+  char* d = (char*)src.scratch->p;
   ISAC_HIP(hipMemsetAsync(d, 0, off_ccut, ctx->stream));
-  hipLaunchKernelGGL(target_hits_kernel, dim3(std::min(cdiv(ts.cap, 256), 8u), A), dim3(256), 0, ctx->stream, (const int*)ctx->det_cut.p, (const int*)ctx->det_cnt.p, ts.cap,
+  hipLaunchKernelGGL(target_hits_kernel, dim3(std::min(cdiv(src.cap, 256), 8u), src.n_planes), dim3(256), 0, ctx->stream, src.det_cut, src.det_cnt, src.cap,
                      n_cut_rows, n_cut, hr, hc, nr, (int*)d);
   ISAC_HIP(hipGetLastError());
-  hipLaunchKernelGGL(target_cells_kernel, dim3(cdiv(n_cut_rows, kCellR), cdiv(n_cut_cols, kCellC)), dim3(kCellR * kCellC), 0, ctx->stream, (const double*)ctx->pwin.p, nr, nc,
-                     A, hr, hc, n_cut_rows, n_cut_cols, (const int*)d, (unsigned*)(d + off_cnt), (int*)(d + off_ccut), (int*)(d + off_chit), (double*)(d + off_cs));
+  auto cells = src.take_max ? target_cells_kernel<true> : target_cells_kernel<false>;
+  hipLaunchKernelGGL(cells, dim3(cdiv(n_cut_rows, kCellR), cdiv(n_cut_cols, kCellC)), dim3(kCellR * kCellC), 0, ctx->stream, src.planes, nr, nc,
+                     src.n_planes, hr, hc, n_cut_rows, n_cut_cols, (const int*)d, (unsigned*)(d + off_cnt), (int*)(d + off_ccut), (int*)(d + off_chit), (double*)(d + off_cs),
+                     src.take_max ? (int*)(d + off_cpl) : (int*)nullptr);
   ISAC_HIP(hipGetLastError());
   unsigned count = 0;
   ISAC_TRY(copy_d2h(ctx, &count, d + off_cnt, sizeof(count)));
@@ -291,11 +298,15 @@ int select_cells(isac_ctx* ctx, const char* who, isac_target_list* out, const is
   const int n_total = (int)count;
   out->n_total = n_total;
   if (n_total == 0) return ISAC_OK;
-  std::vector<int> ccut((size_t)n_total), chit((size_t)n_total);
+  std::vector<int> ccut((size_t)n_total), chit((size_t)n_total), cpl;
   std::vector<double> cs((size_t)n_total);
   ISAC_TRY(copy_d2h(ctx, ccut.data(), d + off_ccut, sizeof(int) * (size_t)n_total));
   ISAC_TRY(copy_d2h(ctx, chit.data(), d + off_chit, sizeof(int) * (size_t)n_total));
   ISAC_TRY(copy_d2h(ctx, cs.data(), d + off_cs, sizeof(double) * (size_t)n_total));
+  if (src.take_max) {
+    cpl.resize((size_t)n_total);
+    ISAC_TRY(copy_d2h(ctx, cpl.data(), d + off_cpl, sizeof(int) * (size_t)n_total));
+  }
   // S descending, ties by ascending column-major index r + nIFFT (c - 1) -- the order of the CUT ordinal cr + n_cut_rows cc (column first, then row)
   std::vector<int> order((size_t)n_total);
   std::iota(order.begin(), order.end(), 0);
@@ -315,12 +326,19 @@ int select_cells(isac_ctx* ctx, const char* who, isac_target_list* out, const is
     out->power[i] = cs[(size_t)o];
     out->rng[i] = CutWindow::range_of(rc.row, ep);
     out->vel[i] = CutWindow::velocity_of(rc.col, ep);
+    if (src.take_max) src.best_plane[i] = cpl[(size_t)o];
     sel[(size_t)i] = rc.row - w.first_row;
     sel[(size_t)n + i] = rc.col - 1;
   }
+  if (!sc) return ISAC_OK;
   ISAC_TRY(stage_upload(ctx, d + off_sel, sel.data(), sizeof(int) * sel.size()));
   *sc = SelectedCells{n, d, off_sel, off_azi, off_snap};
   return ISAC_OK;
+}
+
+// the planes and lists of the two per-target lists: the CPI's own
+PlaneCells cpi_cells(isac_ctx* ctx) {
+  return PlaneCells{(const double*)ctx->pwin.p, ctx->tgt.A, (const int*)ctx->det_cut.p, (const int*)ctx->det_cnt.p, ctx->tgt.cap, false, &ctx->tgt_scratch, nullptr};
 }
 
 // The scan bins of the n selected cells and, when asked for, their snapshots: complete when it returns
@@ -333,6 +351,8 @@ int fetch_bins(isac_ctx* ctx, const SelectedCells& sc, int A, std::vector<int>& 
 
 }  // namespace
 
+int target_cells_of_planes(isac_ctx* ctx, const char* who, const PlaneCells& src, isac_target_list* out) { return select_cells(ctx, who, src, out, nullptr, 0, nullptr); }
+
 extern "C" int isac_fft2d_get_targets(isac_ctx* ctx, isac_target_list* out, isac_c64* snapshots, int32_t cap_snap) {
   ISAC_ENTER(ctx);
   ISAC_TRY(cpi_ready(ctx, "isac_fft2d_get_targets", out, snapshots, cap_snap));
@@ -341,7 +361,7 @@ extern "C" int isac_fft2d_get_targets(isac_ctx* ctx, isac_target_list* out, isac
   const isac_est_params& ep = ts.ep;
   const int A = ts.A;
   SelectedCells sc;
-  ISAC_TRY(select_cells(ctx, "isac_fft2d_get_targets", out, snapshots, cap_snap, &sc));
+  ISAC_TRY(select_cells(ctx, "isac_fft2d_get_targets", cpi_cells(ctx), out, snapshots, cap_snap, &sc));
   if (sc.n == 0) return ISAC_OK;
   const int n = sc.n;
   const c64* twd = nullptr;
@@ -370,7 +390,7 @@ extern "C" int isac_fft2d_get_targets_upa(isac_ctx* ctx, isac_target_list* out, 
   int e_steps = 0, a_steps = 0;
   ISAC_TRY(isac_doa2d_grid(ctx, &ep, A, &d_tab, &e_steps, &a_steps));     // n_ants_x n_ants_y != A: ISAC_ERR_INVALID_ARG; A > 256: ISAC_ERR_UNSUPPORTED
   SelectedCells sc;
-  ISAC_TRY(select_cells(ctx, "isac_fft2d_get_targets_upa", out, snapshots, cap_snap, &sc));
+  ISAC_TRY(select_cells(ctx, "isac_fft2d_get_targets_upa", cpi_cells(ctx), out, snapshots, cap_snap, &sc));
   if (sc.n == 0) return ISAC_OK;
   const int n = sc.n;
   const c64* twd = nullptr;

@@ -2,5 +2,8 @@ from .fft2D import fft2D, fft2D_submit, fft2D_collect  # noqa: F401
 from .targetList import targetList  # noqa: F401
 from .targetListUPA import targetListUPA  # noqa: F401
 from .redetect import redetect  # noqa: F401
+from .rdmWindow import rdmWindow  # noqa: F401
+from .beamWeights import beamWeights  # noqa: F401
+from .beamDetect import beamDetect  # noqa: F401
 from . import doaEstimation  # noqa: F401
 from .music2D import music2D  # noqa: F401

@@ -32,6 +32,17 @@ def cosd(x):
     return sind(90.0 - np.fmod(np.abs(np.asarray(x, dtype=np.float64)), 360.0))
 
 
+def steeringVector(arr, nAnts, lam, azi, ele=0.0):
+    """The receive steering vector [nAnts] radarParams.m:81-118 forms for the direction (azi, ele) in degrees: the one expression behind RxSteeringVec and
+    sensing.estimation.beamWeights."""
+    if getattr(arr, "kind", "ula") == "upa":                                        # :84-100
+        antX = np.arange(arr.nV) * arr.dV
+        antY = (np.arange(arr.nH) * arr.dH)[:, None]
+        return np.exp(2j * np.pi * sind(ele) * (antX * cosd(azi) + antY * sind(azi)) / lam).reshape(nAnts, order="F")
+    ant = np.arange(nAnts) * arr.d                                                  # :102-114  (spacing in wavelengths / lambda in metres, as written)
+    return np.exp(2j * np.pi * ant * sind(azi) / lam)
+
+
 def radarParams(cellSimuParams, carrierInfo, waveInfo):
     """radarParams = sensing.radarParams(cellSimuParams, carrierInfo, waveInfo)  (radarParams.m:1)."""
     p = SimpleNamespace()
@@ -86,14 +97,7 @@ def radarParams(cellSimuParams, carrierInfo, waveInfo):
     p.vMax = lam / (2 * (Tsri * ut))
 
     arr = c.gNBSenAntenna                                                           # :81
-    if getattr(arr, "kind", "ula") == "upa":                                        # :84-100
-        antX = np.arange(arr.nV) * arr.dV
-        antY = (np.arange(arr.nH) * arr.dH)[:, None]
-        cols = [np.exp(2j * np.pi * sind(ele[t]) * (antX * cosd(azi[t]) + antY * sind(azi[t])) / lam).reshape(nTxAnts, order="F")
-                for t in range(nTargets)]
-    else:                                                                           # :102-114  (spacing in wavelengths / lambda in metres, as written)
-        ant = np.arange(nTxAnts) * arr.d
-        cols = [np.exp(2j * np.pi * ant * sind(azi[t]) / lam) for t in range(nTargets)]
+    cols = [steeringVector(arr, nTxAnts, lam, azi[t], ele[t]) for t in range(nTargets)]   # :84-114
     p.antennaType = arr                                                             # :120
     p.azimuthScanScale, p.elevationScanScale = 360, 180                             # :121-122
     p.azimuthScanGranularity = p.elevationScanGranularity = 1                       # :123-124
