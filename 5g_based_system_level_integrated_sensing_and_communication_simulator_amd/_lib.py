@@ -253,6 +253,10 @@ PROTOTYPES_BEAMS = {
     "isac_fft2d_get_rdm_window": (_INT, (_P, _P, _I64, _P, _P, _P)),
     "isac_fft2d_beam_detect": (_INT, (_P, _P, _I32, _P, _ptr(CfarMethod), _P, _P, _P, _P, _I32, _P, _P, _P)),
 }
+# ... and include/isac_refine.h (tests/test_refine_cpu.py pins it)
+PROTOTYPES_REFINE = {
+    "isac_fft2d_refine_targets": (_INT, (_P, _P, _P, _I32, _F64, _I32, _F64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P)),
+}
 
 
 def library_path() -> str:
@@ -279,7 +283,7 @@ def load():
             except Exception:
                 pass
         lib = C.CDLL(_LIB_PATH, mode=C.RTLD_GLOBAL)
-        for name, (restype, argtypes) in {**PROTOTYPES, **PROTOTYPES_ADDED, **PROTOTYPES_CFAR, **PROTOTYPES_CFAR_MC, **PROTOTYPES_LAZY_COV, **PROTOTYPES_TARGETS_UPA, **PROTOTYPES_BEAMS}.items():
+        for name, (restype, argtypes) in {**PROTOTYPES, **PROTOTYPES_ADDED, **PROTOTYPES_CFAR, **PROTOTYPES_CFAR_MC, **PROTOTYPES_LAZY_COV, **PROTOTYPES_TARGETS_UPA, **PROTOTYPES_BEAMS, **PROTOTYPES_REFINE}.items():
             fn = getattr(lib, name)  # AttributeError here = ABI drift between isac.h and the .so
             fn.restype, fn.argtypes = restype, argtypes
         # the library writes whole structs into caller memory: version AND struct sizes must match this binding's mirrors

@@ -65,6 +65,11 @@ struct PlaneCells {
 };
 }
 int target_cells_of_planes(isac_ctx* ctx, const char* who, const isac::PlaneCells& src, isac_target_list* out);
+// ... and for refine.hip: step 4 (ULA) / 4' (UPA, by ctx->tgt.ep) of the lists on n snapshots [A x n] that are on the device: the scan bins into d_bin [n], azi [n] (and ele [n],
+// UPA only) on the host; complete when it returns.  UPA: the checks of isac_doa2d_grid; the scan's partials go to ctx->tgt_part.
+int target_scan_snapshots(isac_ctx* ctx, const isac::c64* d_snap, int n, int* d_bin, double* azi, double* ele);
+// ---------------------------------------------------------------- refine.hip: isac_fft2d_refine_targets (include/isac_refine.h) -- off-grid Doppler, split-lobe merge and sidelobe flags for listed cells of the
+// last completed fft2D.  Reads ctx->tgt and ctx->ymid, writes ctx->refine (and ctx->tgt_part through target_scan_snapshots) only.
 // ---------------------------------------------------------------- beams.hip: isac_fft2d_get_rdm_window, isac_fft2d_beam_detect (include/isac_beams.h) -- the complex window of the last completed fft2D and CFAR on
 // beam planes of it.  Reads ctx->tgt and ctx->ymid, writes ctx->beam_y / beam_p / beam_det / beam_sel only; calls isac_get_twiddles, cfar_detect_planes and target_cells_of_planes.
 // ---------------------------------------------------------------- fft2d.hip: the host side of the fft2D pipeline -- submit, collect, submit_n / collect_n, the host-array call, the getters

@@ -15,6 +15,8 @@
 // target's partials in ascending tile order.  No floating-point atomics, no order that depends on arrival: the result is a function of the snapshots alone.
 // isac_fft2d_beam_detect (include/isac_beams.h, beams.hip) runs steps 1, 2 and 5 on its beam planes and per-beam lists through target_cells_of_planes: the same host function
 // (select_cells) and K1, K2 with the map M = the maximum over the planes in place of their sum (target_cells_kernel<true>); step 3's chain is csrc/rdm_cell.hpp, shared with it.
+// isac_fft2d_refine_targets (include/isac_refine.h, refine.hip) runs step 4 / 4' on its refined snapshots through target_scan_snapshots: K3' target_azi_kernel is phase 2 of
+// K3 by itself (one device function, target_bartlett_ula, serves both), K5 and K6 are launched by the one host function (enqueue_scan2d) the UPA list launches them with.
 #include <algorithm>
 #include <numeric>
 
@@ -129,18 +131,10 @@ __device__ __forceinline__ void target_snapshot(const c64* __restrict__ ymid /* 
   __syncthreads();
 }
 
-__global__ __launch_bounds__(256) void target_doa_kernel(const c64* __restrict__ ymid /* [n_rows x L x A] */, int n_rows, int L, int A, int n_fft,
-                                                         const c64* __restrict__ tw_d /* e^{-2 pi j m / n_fft} */, double sqrt_nfft,
-                                                         const int* __restrict__ cell_row /* window row, 0-based */, const int* __restrict__ cell_col /* rdm column, 0-based */,
-                                                         const double* __restrict__ sind_tab, int n_steps, double d_ratio,
-                                                         int* __restrict__ azi_bin /* [n] */, c64* __restrict__ snap /* [A x n] */) {
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  c64* s_x = reinterpret_cast<c64*>(smem_raw);                            // [A]
-  __shared__ double s_val[256];
-  __shared__ int s_idx[256];
-  const int tid = threadIdx.x, t = blockIdx.x;
-  target_snapshot(ymid, n_rows, L, A, n_fft, tw_d, sqrt_nfft, cell_row[t], cell_col[t], s_x);
-  for (int a = tid; a < A; a += 256) snap[a + (long long)A * t] = s_x[a];
+// Phase 2 (step 4) for a workgroup of 256 threads, shared by K3 and K3': *out_bin = the first arg-max of the scan of the snapshot s_x (LDS [A], visible to every thread).
+__device__ __forceinline__ void target_bartlett_ula(const c64* s_x, int A, const double* __restrict__ sind_tab, int n_steps, double d_ratio,
+                                                    double* s_val /* LDS [256] */, int* s_idx /* LDS [256] */, int* __restrict__ out_bin) {
+  const int tid = threadIdx.x;
   double best = -1.0;                                                     // B >= 0; NaN never wins
   int best_i = 0x7fffffff;
   for (int i = tid; i < n_steps; i += 256) {
@@ -167,7 +161,35 @@ __global__ __launch_bounds__(256) void target_doa_kernel(const c64* __restrict__
     }
     __syncthreads();
   }
-  if (tid == 0) azi_bin[t] = s_idx[0] == 0x7fffffff ? 0 : s_idx[0];
+  if (tid == 0) *out_bin = s_idx[0] == 0x7fffffff ? 0 : s_idx[0];
+}
+
+__global__ __launch_bounds__(256) void target_doa_kernel(const c64* __restrict__ ymid /* [n_rows x L x A] */, int n_rows, int L, int A, int n_fft,
+                                                         const c64* __restrict__ tw_d /* e^{-2 pi j m / n_fft} */, double sqrt_nfft,
+                                                         const int* __restrict__ cell_row /* window row, 0-based */, const int* __restrict__ cell_col /* rdm column, 0-based */,
+                                                         const double* __restrict__ sind_tab, int n_steps, double d_ratio,
+                                                         int* __restrict__ azi_bin /* [n] */, c64* __restrict__ snap /* [A x n] */) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  c64* s_x = reinterpret_cast<c64*>(smem_raw);                            // [A]
+  __shared__ double s_val[256];
+  __shared__ int s_idx[256];
+  const int tid = threadIdx.x, t = blockIdx.x;
+  target_snapshot(ymid, n_rows, L, A, n_fft, tw_d, sqrt_nfft, cell_row[t], cell_col[t], s_x);
+  for (int a = tid; a < A; a += 256) snap[a + (long long)A * t] = s_x[a];
+  target_bartlett_ula(s_x, A, sind_tab, n_steps, d_ratio, s_val, s_idx, azi_bin + t);
+}
+
+// ---------------------------------------------------------------- K3': phase 2 of K3 on snapshots that are already there (isac_fft2d_refine_targets: the refined snapshots)
+__global__ __launch_bounds__(256) void target_azi_kernel(const c64* __restrict__ snap /* [A x n] */, int A, const double* __restrict__ sind_tab, int n_steps, double d_ratio,
+                                                         int* __restrict__ azi_bin /* [n] */) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  c64* s_x = reinterpret_cast<c64*>(smem_raw);                            // [A]
+  __shared__ double s_val[256];
+  __shared__ int s_idx[256];
+  const int t = blockIdx.x;
+  for (int a = threadIdx.x; a < A; a += 256) s_x[a] = snap[a + (long long)A * t];
+  __syncthreads();
+  target_bartlett_ula(s_x, A, sind_tab, n_steps, d_ratio, s_val, s_idx, azi_bin + t);
 }
 
 // ---------------------------------------------------------------- K4: array snapshot of one target cell per workgroup (the UPA list: phase 1 of K3 alone)
@@ -349,7 +371,60 @@ int fetch_bins(isac_ctx* ctx, const SelectedCells& sc, int A, std::vector<int>& 
   return ISAC_OK;
 }
 
+// Step 4' on the device: K5 + K6 over n snapshots [A x n] -> d_bin [n], j = e + eSteps a.  Enqueued on the context's stream; the partials live in ctx->tgt_part.
+int enqueue_scan2d(isac_ctx* ctx, const isac_est_params& ep, int A, const double* d_tab, int e_steps, int a_steps, const c64* d_snap, int n, int* d_bin) {
+  const int pt = A <= 64 ? 64 : A <= 128 ? 32 : 16;                       // the steering tile [A x pt] c64 fits 64 KB of LDS
+  const long long n_pts = (long long)e_steps * a_steps;
+  const unsigned n_tiles = cdiv(n_pts, pt);
+  ISAC_TRY(ensure(ctx, ctx->tgt_part, (sizeof(double) + sizeof(int)) * (size_t)n_tiles * n));
+  double* part_val = (double*)ctx->tgt_part.p;
+  int* part_idx = (int*)(part_val + (size_t)n_tiles * n);
+#define ISAC_TARGET_SCAN2D(PT_)                                                                                                                          \
+  do {                                                                                                                                                   \
+    const size_t lds = sizeof(c64) * (size_t)A * PT_;                                                                                                    \
+    ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(target_scan2d_kernel<PT_>), lds));                                                             \
+    hipLaunchKernelGGL(target_scan2d_kernel<PT_>, dim3(n_tiles), dim3(256), lds, ctx->stream, d_tab, e_steps, a_steps, ep.n_ants_x, ep.n_ants_y,         \
+                       d_snap, n, part_val, part_idx);                                                                                                   \
+  } while (0)
+  if (pt == 64) ISAC_TARGET_SCAN2D(64); else if (pt == 32) ISAC_TARGET_SCAN2D(32); else ISAC_TARGET_SCAN2D(16);
+#undef ISAC_TARGET_SCAN2D
+  ISAC_HIP(hipGetLastError());
+  hipLaunchKernelGGL(target_scan2d_reduce_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ctx->stream, (const double*)part_val, (const int*)part_idx, (int)n_tiles, n, d_bin);
+  ISAC_HIP(hipGetLastError());
+  return ISAC_OK;
+}
+
+// scan bin -> degrees: music.m:103 (ULA), music.m:70-71 with j = e + eSteps a (UPA)
+double azi_of_bin(int bin, const isac_est_params& ep) { return bin * ep.azimuth_scan_granularity - ep.azimuth_scan_scale / 2.0; }
+double azi_of_bin2d(int j, int e_steps, const isac_est_params& ep) { return (j / e_steps) * ep.azimuth_scan_granularity - ep.azimuth_scan_scale / 2.0; }
+double ele_of_bin2d(int j, int e_steps, const isac_est_params& ep) { return (j % e_steps) * ep.elevation_scan_granularity - ep.elevation_scan_scale / 2.0; }
+
 }  // namespace
+
+int target_scan_snapshots(isac_ctx* ctx, const c64* d_snap, int n, int* d_bin, double* azi, double* ele) {
+  const Fft2dCpi& ts = ctx->tgt;
+  const isac_est_params& ep = ts.ep;
+  const int A = ts.A;
+  int e_steps = 0;
+  if (ep.array_is_upa) {
+    const double* d_tab = nullptr;
+    int a_steps = 0;
+    ISAC_TRY(isac_doa2d_grid(ctx, &ep, A, &d_tab, &e_steps, &a_steps));
+    ISAC_TRY(enqueue_scan2d(ctx, ep, A, d_tab, e_steps, a_steps, d_snap, n, d_bin));
+  } else {
+    const size_t lds = sizeof(c64) * (size_t)A;
+    ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(target_azi_kernel), lds));
+    hipLaunchKernelGGL(target_azi_kernel, dim3(n), dim3(256), lds, ctx->stream, d_snap, A, ts.d_sind, ts.n_steps, 0.5, d_bin);
+    ISAC_HIP(hipGetLastError());
+  }
+  std::vector<int> bins((size_t)n);
+  ISAC_TRY(copy_d2h(ctx, bins.data(), d_bin, sizeof(int) * (size_t)n));
+  for (int i = 0; i < n; ++i) {
+    azi[i] = ep.array_is_upa ? azi_of_bin2d(bins[(size_t)i], e_steps, ep) : azi_of_bin(bins[(size_t)i], ep);
+    if (ep.array_is_upa) ele[i] = ele_of_bin2d(bins[(size_t)i], e_steps, ep);
+  }
+  return ISAC_OK;
+}
 
 int target_cells_of_planes(isac_ctx* ctx, const char* who, const PlaneCells& src, isac_target_list* out) { return select_cells(ctx, who, src, out, nullptr, 0, nullptr); }
 
@@ -373,7 +448,7 @@ extern "C" int isac_fft2d_get_targets(isac_ctx* ctx, isac_target_list* out, isac
   ISAC_HIP(hipGetLastError());
   std::vector<int> bins;
   ISAC_TRY(fetch_bins(ctx, sc, A, bins, snapshots));
-  for (int i = 0; i < n; ++i) out->azi[i] = bins[(size_t)i] * ep.azimuth_scan_granularity - ep.azimuth_scan_scale / 2.0;   // music.m:103
+  for (int i = 0; i < n; ++i) out->azi[i] = azi_of_bin(bins[(size_t)i], ep);
   out->n_targets = n;
   return ISAC_OK;
 }
@@ -395,35 +470,17 @@ extern "C" int isac_fft2d_get_targets_upa(isac_ctx* ctx, isac_target_list* out, 
   const int n = sc.n;
   const c64* twd = nullptr;
   ISAC_TRY(isac_get_twiddles(ctx, ep.n_fft, &twd));
-  const int pt = A <= 64 ? 64 : A <= 128 ? 32 : 16;                       // the steering tile [A x pt] c64 fits 64 KB of LDS
-  const long long n_pts = (long long)e_steps * a_steps;
-  const unsigned n_tiles = cdiv(n_pts, pt);
-  ISAC_TRY(ensure(ctx, ctx->tgt_part, (sizeof(double) + sizeof(int)) * (size_t)n_tiles * n));
-  double* part_val = (double*)ctx->tgt_part.p;
-  int* part_idx = (int*)(part_val + (size_t)n_tiles * n);
   c64* d_snap = (c64*)(sc.d + sc.off_snap);
   ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(target_snap_kernel), sizeof(c64) * (size_t)A));
   hipLaunchKernelGGL(target_snap_kernel, dim3(n), dim3(256), sizeof(c64) * (size_t)A, ctx->stream, (const c64*)ctx->ymid.p, ts.win.nr, ts.L, A, ep.n_fft, twd,
                      std::sqrt((double)ep.n_fft), (const int*)(sc.d + sc.off_sel), (const int*)(sc.d + sc.off_sel) + n, d_snap);
   ISAC_HIP(hipGetLastError());
-#define ISAC_TARGET_SCAN2D(PT_)                                                                                                                          \
-  do {                                                                                                                                                   \
-    const size_t lds = sizeof(c64) * (size_t)A * PT_;                                                                                                    \
-    ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(target_scan2d_kernel<PT_>), lds));                                                             \
-    hipLaunchKernelGGL(target_scan2d_kernel<PT_>, dim3(n_tiles), dim3(256), lds, ctx->stream, d_tab, e_steps, a_steps, ep.n_ants_x, ep.n_ants_y,         \
-                       (const c64*)d_snap, n, part_val, part_idx);                                                                                       \
-  } while (0)
-  if (pt == 64) ISAC_TARGET_SCAN2D(64); else if (pt == 32) ISAC_TARGET_SCAN2D(32); else ISAC_TARGET_SCAN2D(16);
-#undef ISAC_TARGET_SCAN2D
-  ISAC_HIP(hipGetLastError());
-  hipLaunchKernelGGL(target_scan2d_reduce_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ctx->stream, (const double*)part_val, (const int*)part_idx, (int)n_tiles, n,
-                     (int*)(sc.d + sc.off_bin));
-  ISAC_HIP(hipGetLastError());
+  ISAC_TRY(enqueue_scan2d(ctx, ep, A, d_tab, e_steps, a_steps, d_snap, n, (int*)(sc.d + sc.off_bin)));
   std::vector<int> bins;
   ISAC_TRY(fetch_bins(ctx, sc, A, bins, snapshots));
-  for (int i = 0; i < n; ++i) {                                           // j = e + eSteps a   music.m:70-71
-    out->azi[i] = (bins[(size_t)i] / e_steps) * ep.azimuth_scan_granularity - ep.azimuth_scan_scale / 2.0;
-    ele[i] = (bins[(size_t)i] % e_steps) * ep.elevation_scan_granularity - ep.elevation_scan_scale / 2.0;
+  for (int i = 0; i < n; ++i) {
+    out->azi[i] = azi_of_bin2d(bins[(size_t)i], e_steps, ep);
+    ele[i] = ele_of_bin2d(bins[(size_t)i], e_steps, ep);
   }
   out->n_targets = n;
   return ISAC_OK;
