@@ -257,6 +257,10 @@ PROTOTYPES_BEAMS = {
 PROTOTYPES_REFINE = {
     "isac_fft2d_refine_targets": (_INT, (_P, _P, _P, _I32, _F64, _I32, _F64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P)),
 }
+# ... and include/isac_clean.h (tests/test_clean_cpu.py pins it)
+PROTOTYPES_CLEAN = {
+    "isac_fft2d_clean_targets": (_INT, (_P, _ptr(CfarMethod), _I32, _I32, _F64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P)),
+}
 
 
 def library_path() -> str:
@@ -283,7 +287,7 @@ def load():
             except Exception:
                 pass
         lib = C.CDLL(_LIB_PATH, mode=C.RTLD_GLOBAL)
-        for name, (restype, argtypes) in {**PROTOTYPES, **PROTOTYPES_ADDED, **PROTOTYPES_CFAR, **PROTOTYPES_CFAR_MC, **PROTOTYPES_LAZY_COV, **PROTOTYPES_TARGETS_UPA, **PROTOTYPES_BEAMS, **PROTOTYPES_REFINE}.items():
+        for name, (restype, argtypes) in {**PROTOTYPES, **PROTOTYPES_ADDED, **PROTOTYPES_CFAR, **PROTOTYPES_CFAR_MC, **PROTOTYPES_LAZY_COV, **PROTOTYPES_TARGETS_UPA, **PROTOTYPES_BEAMS, **PROTOTYPES_REFINE, **PROTOTYPES_CLEAN}.items():
             fn = getattr(lib, name)  # AttributeError here = ABI drift between isac.h and the .so
             fn.restype, fn.argtypes = restype, argtypes
         # the library writes whole structs into caller memory: version AND struct sizes must match this binding's mirrors

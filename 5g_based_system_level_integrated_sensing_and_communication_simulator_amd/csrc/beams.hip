@@ -83,6 +83,14 @@ int cpi_ready(isac_ctx* ctx, const char* who) {
 
 // step 1 into ctx->beam_y
 int enqueue_rdm_window(isac_ctx* ctx, const char* who) {
+  const CutWindow& w = ctx->tgt.win;
+  ISAC_TRY(ensure(ctx, ctx->beam_y, sizeof(c64) * (size_t)w.nr * w.nc * ctx->tgt.A));
+  return rdm_window_enqueue(ctx, who, (const c64*)ctx->ymid.p, (c64*)ctx->beam_y.p);
+}
+
+}  // namespace
+
+int rdm_window_enqueue(isac_ctx* ctx, const char* who, const c64* d_rows, c64* d_Y) {
   const Fft2dCpi& ts = ctx->tgt;
   const CutWindow& w = ts.win;
   const int A = ts.A, L = ts.L, n_fft = ts.ep.n_fft;
@@ -90,16 +98,12 @@ int enqueue_rdm_window(isac_ctx* ctx, const char* who) {
   while (R > 1 && sizeof(c64) * (size_t)R * L > 64 * 1024) R >>= 1;
   const size_t lds = sizeof(c64) * (size_t)R * L;                          // (R was halved until the tile fits the 64 KB every kernel may take: no allow_lds)
   if (lds > 64 * 1024) return fail(ctx, ISAC_ERR_UNSUPPORTED, std::string(who) + ": more than 4096 symbols");
-  ISAC_TRY(ensure(ctx, ctx->beam_y, sizeof(c64) * (size_t)w.nr * w.nc * A));
   const c64* twd = nullptr;
   ISAC_TRY(isac_get_twiddles(ctx, n_fft, &twd));
-  hipLaunchKernelGGL(rdm_window_kernel, dim3(cdiv(w.nr, R), A), dim3(256), lds, ctx->stream, (const c64*)ctx->ymid.p, w.nr, L, n_fft, twd, std::sqrt((double)n_fft),
-                     w.first_col - 1, w.nc, R, (c64*)ctx->beam_y.p);
+  hipLaunchKernelGGL(rdm_window_kernel, dim3(cdiv(w.nr, R), A), dim3(256), lds, ctx->stream, d_rows, w.nr, L, n_fft, twd, std::sqrt((double)n_fft), w.first_col - 1, w.nc, R, d_Y);
   ISAC_HIP(hipGetLastError());
   return ISAC_OK;
 }
-
-}  // namespace
 
 extern "C" int isac_fft2d_get_rdm_window(isac_ctx* ctx, isac_c64* Y, int64_t cap_elems, int32_t dims[3], int32_t* first_row, int32_t* first_col) {
   ISAC_ENTER(ctx);

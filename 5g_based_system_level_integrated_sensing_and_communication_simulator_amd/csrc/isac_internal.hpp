@@ -70,8 +70,18 @@ int target_cells_of_planes(isac_ctx* ctx, const char* who, const isac::PlaneCell
 int target_scan_snapshots(isac_ctx* ctx, const isac::c64* d_snap, int n, int* d_bin, double* azi, double* ele);
 // ---------------------------------------------------------------- refine.hip: isac_fft2d_refine_targets (include/isac_refine.h) -- off-grid Doppler, split-lobe merge and sidelobe flags for listed cells of the
 // last completed fft2D.  Reads ctx->tgt and ctx->ymid, writes ctx->refine (and ctx->tgt_part through target_scan_snapshots) only.
+// For clean.hip: steps 1-3 of isac_refine.h on n cells of the range rows d_rows [nr x L x A] (ctx->ymid, or a residual copy of it): refine_plan sizes the probes for
+// the CPI (ISAC_ERR_UNSUPPORTED: they do not fit the LDS), refine_enqueue launches refine_kernel on the context's stream.  d_cell_row: window rows, 0-based; d_cell_k: col - nFFT/2 - 1.
+namespace isac { struct RefinePlan { double W = 0.0; int M = 0; size_t lds = 0; }; }
+int refine_plan(isac_ctx* ctx, const char* who, isac::RefinePlan* plan);
+int refine_enqueue(isac_ctx* ctx, const isac::RefinePlan& plan, const isac::c64* d_rows, const int* d_cell_row, const int* d_cell_k, int n, int* d_status, double* d_nu, double* d_pow, isac::c64* d_snap /* [A x n] */);
 // ---------------------------------------------------------------- beams.hip: isac_fft2d_get_rdm_window, isac_fft2d_beam_detect (include/isac_beams.h) -- the complex window of the last completed fft2D and CFAR on
 // beam planes of it.  Reads ctx->tgt and ctx->ymid, writes ctx->beam_y / beam_p / beam_det / beam_sel only; calls isac_get_twiddles, cfar_detect_planes and target_cells_of_planes.
+// For clean.hip: step 1 of isac_beams.h: rdm_window_kernel on the range rows d_rows [nr x L x A] into d_Y [nr x nc x A] (both sized by the caller), enqueued on the context's stream
+int rdm_window_enqueue(isac_ctx* ctx, const char* who, const isac::c64* d_rows, isac::c64* d_Y);
+// ---------------------------------------------------------------- clean.hip: isac_fft2d_clean_targets (include/isac_clean.h) -- successive cancellation on a residual copy of the range rows of the last completed
+// fft2D.  Reads ctx->tgt and ctx->ymid, writes ctx->clean / clean_det / clean_sel (and ctx->tgt_part through target_scan_snapshots) only; calls rdm_window_enqueue, cfar_detect_planes,
+// target_cells_of_planes, refine_plan / refine_enqueue and target_scan_snapshots.
 // ---------------------------------------------------------------- fft2d.hip: the host side of the fft2D pipeline -- submit, collect, submit_n / collect_n, the host-array call, the getters
 // host half of fft2D.m:63-99 on per-antenna CUT-order lists (callers: isac_fft2d_collect, isac_fft2d_redetect)
 int fft2d_estimates(isac_ctx* ctx, const isac_est_params* ep, const isac::CutWindow& win, int A, const int* ant_off, const std::vector<int>& cut, const std::vector<double>& pw, int num_dets_dev, std::vector<int32_t>& det_rc, isac_est_result* out);

@@ -5,7 +5,7 @@
 //   3  nu* = the zero of P' in [nu_{g-1}, nu_{g+1}] by kRefineBisect halvings on the sign of P'; power = P(nu*), snapshot X(nu*) / sqrt(nFFT); azimuth (elevation): the
 //      scan of the lists on the snapshot (targets.hip: target_scan_snapshots)
 //   4  merge and 5 sidelobe flags on the host
-// refine_kernel: one workgroup of 256 threads per entry runs steps 1-3 in one launch.  Every evaluation of (P, P') at one nu is refine_eval: the thread map of
+// refine_kernel: one workgroup of 256 threads per entry runs steps 1-3 in one launch.  Every evaluation of (P, P') at one nu is refine_eval (refine_dev.hpp, shared with clean.hip): the thread map of
 // target_snapshot -- four lanes per antenna, each a quarter of the symbols in ascending order, joined (q0 + q1) + (q2 + q3) -- with the phasors e^{-2 pi j nu l} read from
 // LDS (every antenna's lanes of a quarter read the same word: broadcasts), the per-antenna terms |X_a|^2 and Im(conj(X_a) D_a), D_a = sum_l l y e^{..} (X_a' = -2 pi j D_a,
 // so P' = (4 pi / nFFT) sum_a Im(conj(X_a) D_a)), left in LDS and summed by EVERY thread in ascending antenna order: all 256 threads hold the same (P, P') bits and take the
@@ -17,51 +17,11 @@
 #include <vector>
 
 #include "isac_internal.hpp"
+#include "refine_dev.hpp"
 
 namespace isac {
 
 constexpr int kRefineBisect = 40;                                         // the bracket 2 W / M shrinks by 2^-40: |nu - nu*| L <= 2.3e-13 where nFFT >= L, every entry the same count
-
-struct RefineSums { double p, d; };                                        // sum_a |X_a|^2, sum_a Im(conj(X_a) D_a)
-
-__device__ __forceinline__ c64 refine_phasor(double nu, int l) {           // e^{-2 pi j nu l}: sincos of the full argument
-  double s, co;
-  sincos(((-2.0 * M_PI) * nu) * (double)l, &s, &co);
-  return mk(co, s);
-}
-
-// (P nFFT, P' nFFT / 4 pi) at the nu whose phasors are s_ph [L]; on return every thread holds the same sums and s_x [A] = X_a(nu).  Ends with a barrier: s_ph, s_p, s_d may
-// be rewritten right away.
-__device__ __forceinline__ RefineSums refine_eval(const c64* __restrict__ row /* ymid + window row */, long long n_rows, int L, int A, const c64* s_ph, c64* s_x, double* s_p,
-                                                  double* s_d) {
-  const int tid = threadIdx.x;
-  const int chunk = (L + 3) / 4;
-  for (int base = 0; base < 4 * A; base += 256) {                         // (256 = 64 quads: a quad is inside one wave and all of it active or none)
-    const int a = (base + tid) >> 2, part = tid & 3;
-    c64 x = mk(0.0, 0.0), dx = mk(0.0, 0.0);
-    if (a < A) {
-      const c64* y = row + n_rows * L * a;
-      const int l0 = part * chunk, l1 = min(l0 + chunk, L);
-      for (int l = l0; l < l1; ++l) {
-        const c64 z = y[n_rows * l] * s_ph[l];
-        x += z;
-        dx = mk(::fma((double)l, z.re, dx.re), ::fma((double)l, z.im, dx.im));
-      }
-    }
-    x.re += __shfl_xor(x.re, 1); x.im += __shfl_xor(x.im, 1); dx.re += __shfl_xor(dx.re, 1); dx.im += __shfl_xor(dx.im, 1);
-    x.re += __shfl_xor(x.re, 2); x.im += __shfl_xor(x.im, 2); dx.re += __shfl_xor(dx.re, 2); dx.im += __shfl_xor(dx.im, 2);
-    if (a < A && part == 0) {
-      s_x[a] = x;
-      s_p[a] = x.re * x.re + x.im * x.im;
-      s_d[a] = x.re * dx.im - x.im * dx.re;
-    }
-  }
-  __syncthreads();
-  RefineSums r{0.0, 0.0};
-  for (int a = 0; a < A; ++a) { r.p += s_p[a]; r.d += s_d[a]; }           // ascending antenna order from 0.0; every lane the same address: broadcasts
-  __syncthreads();
-  return r;
-}
 
 __global__ __launch_bounds__(256) void refine_kernel(const c64* __restrict__ ymid /* [n_rows x L x A] */, int n_rows, int L, int A, int n_fft,
                                                      const int* __restrict__ cell_row /* window row, 0-based */, const int* __restrict__ cell_k /* col - nFFT/2 - 1 */,
@@ -129,6 +89,26 @@ double dirichlet2(double delta, int L) {
 
 }  // namespace
 
+int refine_plan(isac_ctx* ctx, const char* who, RefinePlan* plan) {
+  const int A = ctx->tgt.A, L = ctx->tgt.L, n_fft = ctx->tgt.ep.n_fft;
+  const bool wide = n_fft >= L;                                            // W = max(1/L, 1/nFFT), M = ceil(8 L W)
+  plan->W = wide ? 1.0 / L : 1.0 / n_fft;
+  plan->M = wide ? 8 : (8 * L + n_fft - 1) / n_fft;
+  plan->lds = sizeof(c64) * ((size_t)(2 * plan->M + 2) * L + A) + sizeof(double) * 2 * (size_t)A;
+  if (plan->lds > 160 * 1024) return fail(ctx, ISAC_ERR_UNSUPPORTED, std::string(who) + ": the probe phasors of this many symbols do not fit the LDS");
+  return ISAC_OK;
+}
+
+int refine_enqueue(isac_ctx* ctx, const RefinePlan& plan, const c64* d_rows, const int* d_cell_row, const int* d_cell_k, int n, int* d_status, double* d_nu, double* d_pow,
+                   c64* d_snap) {
+  const Fft2dCpi& ts = ctx->tgt;
+  ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(refine_kernel), plan.lds));
+  hipLaunchKernelGGL(refine_kernel, dim3(n), dim3(256), plan.lds, ctx->stream, d_rows, ts.win.nr, ts.L, ts.A, ts.ep.n_fft, d_cell_row, d_cell_k, plan.W, plan.M, d_status, d_nu,
+                     d_pow, d_snap);
+  ISAC_HIP(hipGetLastError());
+  return ISAC_OK;
+}
+
 extern "C" int isac_fft2d_refine_targets(isac_ctx* ctx, const int32_t* row, const int32_t* col, int32_t n, double merge_tol, int32_t merge_rows, double sidelobe_margin,
                                          int32_t* n_kept, int32_t* status, int32_t* parent, int32_t* sidelobe_of, double* nu, double* vel, double* power, double* azi, double* ele,
                                          isac_c64* snapshots) {
@@ -154,21 +134,16 @@ extern "C" int isac_fft2d_refine_targets(isac_ctx* ctx, const int32_t* row, cons
     sel[(size_t)i] = row[i] - w.first_row;
     sel[(size_t)n + i] = col[i] - n_fft / 2 - 1;
   }
-  const bool wide = n_fft >= L;                                            // W = max(1/L, 1/nFFT), M = ceil(8 L W)
-  const double W = wide ? 1.0 / L : 1.0 / n_fft;
-  const int M = wide ? 8 : (8 * L + n_fft - 1) / n_fft;
-  const size_t lds = sizeof(c64) * ((size_t)(2 * M + 2) * L + A) + sizeof(double) * 2 * (size_t)A;
-  if (lds > 160 * 1024) return fail(ctx, ISAC_ERR_UNSUPPORTED, std::string(who) + ": the probe phasors of this many symbols do not fit the LDS");
+  RefinePlan plan;
+  ISAC_TRY(refine_plan(ctx, who, &plan));
   // one scratch block: [row | k | status | scan bin] ints, [nu | power] doubles, the snapshots [A x n]
   const size_t off_st = sizeof(int) * 2 * (size_t)n, off_bin = off_st + sizeof(int) * (size_t)n, off_nu = (off_bin + sizeof(int) * (size_t)n + 15) & ~(size_t)15;
   const size_t off_pw = off_nu + sizeof(double) * (size_t)n, off_snap = (off_pw + sizeof(double) * (size_t)n + 15) & ~(size_t)15;
   ISAC_TRY(ensure(ctx, ctx->refine, off_snap + sizeof(c64) * (size_t)A * n));
   char* d = (char*)ctx->refine.p;
   ISAC_TRY(stage_upload(ctx, d, sel.data(), sizeof(int) * sel.size()));
-  ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(refine_kernel), lds));
-  hipLaunchKernelGGL(refine_kernel, dim3(n), dim3(256), lds, ctx->stream, (const c64*)ctx->ymid.p, w.nr, L, A, n_fft, (const int*)d, (const int*)d + n, W, M, (int*)(d + off_st),
-                     (double*)(d + off_nu), (double*)(d + off_pw), (c64*)(d + off_snap));
-  ISAC_HIP(hipGetLastError());
+  ISAC_TRY(refine_enqueue(ctx, plan, (const c64*)ctx->ymid.p, (const int*)d, (const int*)d + n, n, (int*)(d + off_st), (double*)(d + off_nu), (double*)(d + off_pw),
+                          (c64*)(d + off_snap)));
   ISAC_TRY(target_scan_snapshots(ctx, (const c64*)(d + off_snap), n, (int*)(d + off_bin), azi, ele));
   ISAC_TRY(copy_d2h(ctx, status, d + off_st, sizeof(int) * (size_t)n));
   ISAC_TRY(copy_d2h(ctx, nu, d + off_nu, sizeof(double) * (size_t)n));

@@ -1,0 +1,49 @@
+// The evaluation refine_kernel (refine.hip) and clean_cancel_kernel (clean.hip) share: X_a(nu) = sum_l y[l, a] e^{-2 pi j nu l} of one range row for every antenna, with the
+// phasors of nu in LDS.  In ONE place so that the tone a cancellation fits is the sum the refinement maximised, bit for bit.
+#pragma once
+#include "isac_common.hpp"
+
+namespace isac {
+
+struct RefineSums { double p, d; };                                        // sum_a |X_a|^2, sum_a Im(conj(X_a) D_a)
+
+__device__ __forceinline__ c64 refine_phasor(double nu, int l) {           // e^{-2 pi j nu l}: sincos of the full argument
+  double s, co;
+  sincos(((-2.0 * M_PI) * nu) * (double)l, &s, &co);
+  return mk(co, s);
+}
+
+// (P nFFT, P' nFFT / 4 pi) at the nu whose phasors are s_ph [L]; on return every thread holds the same sums and s_x [A] = X_a(nu).  Ends with a barrier: s_ph, s_p, s_d may
+// be rewritten right away.
+__device__ __forceinline__ RefineSums refine_eval(const c64* __restrict__ row /* ymid + window row */, long long n_rows, int L, int A, const c64* s_ph, c64* s_x, double* s_p,
+                                                  double* s_d) {
+  const int tid = threadIdx.x;
+  const int chunk = (L + 3) / 4;
+  for (int base = 0; base < 4 * A; base += 256) {                         // (256 = 64 quads: a quad is inside one wave and all of it active or none)
+    const int a = (base + tid) >> 2, part = tid & 3;
+    c64 x = mk(0.0, 0.0), dx = mk(0.0, 0.0);
+    if (a < A) {
+      const c64* y = row + n_rows * L * a;
+      const int l0 = part * chunk, l1 = min(l0 + chunk, L);
+      for (int l = l0; l < l1; ++l) {
+        const c64 z = y[n_rows * l] * s_ph[l];
+        x += z;
+        dx = mk(::fma((double)l, z.re, dx.re), ::fma((double)l, z.im, dx.im));
+      }
+    }
+    x.re += __shfl_xor(x.re, 1); x.im += __shfl_xor(x.im, 1); dx.re += __shfl_xor(dx.re, 1); dx.im += __shfl_xor(dx.im, 1);
+    x.re += __shfl_xor(x.re, 2); x.im += __shfl_xor(x.im, 2); dx.re += __shfl_xor(dx.re, 2); dx.im += __shfl_xor(dx.im, 2);
+    if (a < A && part == 0) {
+      s_x[a] = x;
+      s_p[a] = x.re * x.re + x.im * x.im;
+      s_d[a] = x.re * dx.im - x.im * dx.re;
+    }
+  }
+  __syncthreads();
+  RefineSums r{0.0, 0.0};
+  for (int a = 0; a < A; ++a) { r.p += s_p[a]; r.d += s_d[a]; }           // ascending antenna order from 0.0; every lane the same address: broadcasts
+  __syncthreads();
+  return r;
+}
+
+}  // namespace isac

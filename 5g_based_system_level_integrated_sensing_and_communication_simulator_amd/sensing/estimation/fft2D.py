@@ -63,6 +63,7 @@ def fft2D(radarEstParams, cfar, rxGrid, txGrid, *, ctx=None, return_debug=False,
     res = L.EstResult()
     lib = ctx.lib
     ctx.fft2d_radar_params = radarEstParams              # sensing.estimation.redetect scans with the same grid
+    ctx.fft2d_grid_shape = (int(K), int(Lsym), int(A))   # sensing.estimation.cleanTargets sizes its symbol arrays by it
     if dev and reuse_range:
         st = lib.isac_fft2d_submit_cached_dev(ctx.handle, C.byref(ep), C.byref(cf), rxGrid, txGrid, K, Lsym, A)
         if st == 0:
@@ -99,6 +100,7 @@ def fft2D_submit(radarEstParams, cfar, rxGrid, txGrid, *, ctx=None, reuse_range=
     cf = _cfar_block(cfar)
     ep = est_block(radarEstParams)
     ctx.fft2d_radar_params = radarEstParams
+    ctx.fft2d_grid_shape = (int(K), int(Lsym), int(A))
     fn = ctx.lib.isac_fft2d_submit_cached_dev if reuse_range else ctx.lib.isac_fft2d_submit_dev
     ctx.check(fn(ctx.handle, C.byref(ep), C.byref(cf), rxGrid, txGrid, K, Lsym, A))
     return ctx
