@@ -261,6 +261,11 @@ PROTOTYPES_REFINE = {
 PROTOTYPES_CLEAN = {
     "isac_fft2d_clean_targets": (_INT, (_P, _ptr(CfarMethod), _I32, _I32, _F64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P)),
 }
+# ... and include/isac_directions.h (tests/test_directions_cpu.py pins it)
+ISAC_DIR_MAX_SOURCES = 8
+PROTOTYPES_DIRECTIONS = {
+    "isac_resolve_directions": (_INT, (_P, _ptr(EstParams), _P, _I32, _I32, _I32, _I32, _F64, _F64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P)),
+}
 
 
 def library_path() -> str:
@@ -287,7 +292,7 @@ def load():
             except Exception:
                 pass
         lib = C.CDLL(_LIB_PATH, mode=C.RTLD_GLOBAL)
-        for name, (restype, argtypes) in {**PROTOTYPES, **PROTOTYPES_ADDED, **PROTOTYPES_CFAR, **PROTOTYPES_CFAR_MC, **PROTOTYPES_LAZY_COV, **PROTOTYPES_TARGETS_UPA, **PROTOTYPES_BEAMS, **PROTOTYPES_REFINE, **PROTOTYPES_CLEAN}.items():
+        for name, (restype, argtypes) in {**PROTOTYPES, **PROTOTYPES_ADDED, **PROTOTYPES_CFAR, **PROTOTYPES_CFAR_MC, **PROTOTYPES_LAZY_COV, **PROTOTYPES_TARGETS_UPA, **PROTOTYPES_BEAMS, **PROTOTYPES_REFINE, **PROTOTYPES_CLEAN, **PROTOTYPES_DIRECTIONS}.items():
             fn = getattr(lib, name)  # AttributeError here = ABI drift between isac.h and the .so
             fn.restype, fn.argtypes = restype, argtypes
         # the library writes whole structs into caller memory: version AND struct sizes must match this binding's mirrors
