@@ -261,6 +261,11 @@ PROTOTYPES_REFINE = {
 PROTOTYPES_CLEAN = {
     "isac_fft2d_clean_targets": (_INT, (_P, _ptr(CfarMethod), _I32, _I32, _F64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P)),
 }
+# ... and include/isac_relax.h (tests/test_relax_cpu.py pins it)
+ISAC_RELAX_MAX_TONES = 64
+PROTOTYPES_RELAX = {
+    "isac_fft2d_relax_targets": (_INT, (_P, _P, _P, _I32, _I32, _I32, _F64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P)),
+}
 # ... and include/isac_directions.h (tests/test_directions_cpu.py pins it)
 ISAC_DIR_MAX_SOURCES = 8
 PROTOTYPES_DIRECTIONS = {
@@ -292,7 +297,7 @@ def load():
             except Exception:
                 pass
         lib = C.CDLL(_LIB_PATH, mode=C.RTLD_GLOBAL)
-        for name, (restype, argtypes) in {**PROTOTYPES, **PROTOTYPES_ADDED, **PROTOTYPES_CFAR, **PROTOTYPES_CFAR_MC, **PROTOTYPES_LAZY_COV, **PROTOTYPES_TARGETS_UPA, **PROTOTYPES_BEAMS, **PROTOTYPES_REFINE, **PROTOTYPES_CLEAN, **PROTOTYPES_DIRECTIONS}.items():
+        for name, (restype, argtypes) in {**PROTOTYPES, **PROTOTYPES_ADDED, **PROTOTYPES_CFAR, **PROTOTYPES_CFAR_MC, **PROTOTYPES_LAZY_COV, **PROTOTYPES_TARGETS_UPA, **PROTOTYPES_BEAMS, **PROTOTYPES_REFINE, **PROTOTYPES_CLEAN, **PROTOTYPES_RELAX, **PROTOTYPES_DIRECTIONS}.items():
             fn = getattr(lib, name)  # AttributeError here = ABI drift between isac.h and the .so
             fn.restype, fn.argtypes = restype, argtypes
         # the library writes whole structs into caller memory: version AND struct sizes must match this binding's mirrors

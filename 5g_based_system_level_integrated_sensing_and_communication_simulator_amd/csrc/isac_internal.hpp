@@ -82,6 +82,8 @@ int rdm_window_enqueue(isac_ctx* ctx, const char* who, const isac::c64* d_rows, 
 // ---------------------------------------------------------------- clean.hip: isac_fft2d_clean_targets (include/isac_clean.h) -- successive cancellation on a residual copy of the range rows of the last completed
 // fft2D.  Reads ctx->tgt and ctx->ymid, writes ctx->clean / clean_det / clean_sel (and ctx->tgt_part through target_scan_snapshots) only; calls rdm_window_enqueue, cfar_detect_planes,
 // target_cells_of_planes, refine_plan / refine_enqueue and target_scan_snapshots.
+// ---------------------------------------------------------------- relax.hip: isac_fft2d_relax_targets (include/isac_relax.h) -- joint re-fit of Doppler tones on a residual copy of the range rows of the last
+// completed fft2D.  Reads ctx->tgt and ctx->ymid, writes ctx->relax (and ctx->tgt_part through target_scan_snapshots) only; calls refine_plan, isac_doa2d_grid and target_scan_snapshots.
 // ---------------------------------------------------------------- directions.hip: isac_resolve_directions (include/isac_directions.h) -- off-grid direction finding with several sources per array snapshot.
 // Reads nothing of the context, writes ctx->directions only; calls and is called by no other unit (its steering spacing: upa_steer.hpp).
 // ---------------------------------------------------------------- fft2d.hip: the host side of the fft2D pipeline -- submit, collect, submit_n / collect_n, the host-array call, the getters

@@ -1,5 +1,5 @@
-// The evaluation refine_kernel (refine.hip) and clean_cancel_kernel (clean.hip) share: X_a(nu) = sum_l y[l, a] e^{-2 pi j nu l} of one range row for every antenna, with the
-// phasors of nu in LDS.  In ONE place so that the tone a cancellation fits is the sum the refinement maximised, bit for bit.
+// The evaluation refine_kernel (refine.hip), clean_cancel_kernel (clean.hip) and the two kernels of relax.hip share: X_a(nu) = sum_l y[l, a] e^{-2 pi j nu l} of one range
+// row for every antenna, with the phasors of nu in LDS.  In ONE place so that the tone a cancellation fits is the sum the refinement maximised, bit for bit.
 #pragma once
 #include "isac_common.hpp"
 
@@ -15,8 +15,12 @@ __device__ __forceinline__ c64 refine_phasor(double nu, int l) {           // e^
 
 // (P nFFT, P' nFFT / 4 pi) at the nu whose phasors are s_ph [L]; on return every thread holds the same sums and s_x [A] = X_a(nu).  Ends with a barrier: s_ph, s_p, s_d may
 // be rewritten right away.
+// AddBack (relax.hip): the sample is y[l, a] + c_back[a] conj(s_back[l]) -- the row with one subtracted tone restored, formed on the fly and never written back; c_back [A]
+// (LDS or device memory) holds the tone's amplitudes on this row, s_back [L] (LDS) its phasors, zero at the inactive symbols.  The plain instantiation is the code that
+// stood here before the parameter existed: refine_kernel and clean_cancel_kernel keep their bits.
+template <bool AddBack = false>
 __device__ __forceinline__ RefineSums refine_eval(const c64* __restrict__ row /* ymid + window row */, long long n_rows, int L, int A, const c64* s_ph, c64* s_x, double* s_p,
-                                                  double* s_d) {
+                                                  double* s_d, const c64* s_back = nullptr, const c64* c_back = nullptr) {
   const int tid = threadIdx.x;
   const int chunk = (L + 3) / 4;
   for (int base = 0; base < 4 * A; base += 256) {                         // (256 = 64 quads: a quad is inside one wave and all of it active or none)
@@ -25,8 +29,12 @@ __device__ __forceinline__ RefineSums refine_eval(const c64* __restrict__ row /*
     if (a < A) {
       const c64* y = row + n_rows * L * a;
       const int l0 = part * chunk, l1 = min(l0 + chunk, L);
+      c64 cb = mk(0.0, 0.0);
+      if constexpr (AddBack) cb = c_back[a];
       for (int l = l0; l < l1; ++l) {
-        const c64 z = y[n_rows * l] * s_ph[l];
+        c64 v = y[n_rows * l];
+        if constexpr (AddBack) v = v + cb * conj(s_back[l]);
+        const c64 z = v * s_ph[l];
         x += z;
         dx = mk(::fma((double)l, z.re, dx.re), ::fma((double)l, z.im, dx.im));
       }

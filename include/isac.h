@@ -675,6 +675,7 @@ int isac_synth_qpsk_grid_dev(isac_ctx* ctx, isac_c64* d_grid, int32_t K, int32_t
 #include "isac_beams.h"  /* the complex window of the last fft2D and CFAR on beam planes of it: additive under ABI 8 */
 #include "isac_refine.h"  /* isac_fft2d_refine_targets: off-grid Doppler, split-lobe merge and sidelobe flags for a target list: additive under ABI 8 */
 #include "isac_clean.h"  /* isac_fft2d_clean_targets: successive target cancellation (CLEAN) on the range rows of the last fft2D: additive under ABI 8 */
+#include "isac_relax.h"  /* isac_fft2d_relax_targets: joint re-fit (RELAX) of Doppler tones on the range rows of the last fft2D: additive under ABI 8 */
 #include "isac_directions.h"  /* isac_resolve_directions: off-grid direction finding with several sources per array snapshot (greedy search + RELAX): additive under ABI 8 */
 
 #endif /* ISAC_H */

@@ -46,8 +46,8 @@
  * ULA and UPA alike.  Runs on the context's stream and returns when complete; a pending submit and its result buffer stay untouched.  Off the timed path: every pass
  * recomputes the whole window.
  *
- * OUT OF SCOPE: a MEX command; deriving sym_active inside the library; a joint re-fit of all extracted tones (RELAX); cancellation on beam planes; a range-sidelobe model
- * beyond the row span.
+ * A joint re-fit of all extracted tones (RELAX) is a call of its own on this call's entries: isac_fft2d_relax_targets (isac_relax.h).
+ * OUT OF SCOPE: a MEX command; deriving sym_active inside the library; cancellation on beam planes; a range-sidelobe model beyond the row span.
  */
 #ifndef ISAC_CLEAN_H
 #define ISAC_CLEAN_H
