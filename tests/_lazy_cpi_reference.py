@@ -3,7 +3,8 @@ cov_lazy_kernel<Q>, the one-launch beam-sum), written from the oracle alone -- n
 
   * `build_scene`: test_gpu_valu_diet._scene's recipe (Nfft = nIFFT = 4096 at every K; nrOFDMInfo would pick less below 3276 subcarriers) returning the oracle's
     radar_params and, where the caller hands in the library's radarParams function, the library's -- both from ONE cell / carrier / waveform description and with the same
-    overrides (nIFFT = 4096, rRes), so that O.fft2d and the library see one parameter set;
+    overrides (nIFFT = 4096, rRes), so that O.fft2d and the library see one parameter set; the subcarrier spacing is the case's (`scs`: 30 kHz for the whole table,
+    120 kHz for the one case of tests/test_gpu_numerology.py);
   * `reference_echo`: O.mono_static_sensing (the per-antenna time-domain chain, monoStaticSensing.m:1-23) fed the time-domain noise that demodulates to the restated Philox
     field (oracle/philox.py), zero-padded to L_out by the oracle itself;
   * `reference_covariance`: Ra = G^H G / (K L_out) (fft2D.m:106-107) and the per-antenna mean magnitudes of the element-error bound;
@@ -30,9 +31,9 @@ NEAR, MID, FAR = (100.0, 20.0, 1.5), (-250.0, 80.0, 1.5), (470.0, 60.0, 1.5)    
 RTOL = 1e-10                                                                      # test_gpu_fullsize.RTOL
 
 
-def _case(name, nrb, n_ants, targets, velocity, los, n_sym, cut=0, silent=(), zero_from=None, grid_seed=1, noise_seed=1, pfa=1e-9, rcs=1.0):
+def _case(name, nrb, n_ants, targets, velocity, los, n_sym, cut=0, silent=(), zero_from=None, grid_seed=1, noise_seed=1, pfa=1e-9, rcs=1.0, scs=SCS_KHZ):
     return SimpleNamespace(name=name, nrb=nrb, n_ants=n_ants, targets=tuple(targets), velocity=tuple(velocity), los=tuple(los), n_sym=n_sym, cut=cut,
-                           silent=tuple(silent), zero_from=zero_from, grid_seed=grid_seed, noise_seed=noise_seed, pfa=pfa, rcs=rcs)
+                           silent=tuple(silent), zero_from=zero_from, grid_seed=grid_seed, noise_seed=noise_seed, pfa=pfa, rcs=rcs, scs=scs)
 
 
 # `cut`: samples dropped from the waveform's end (the last symbol becomes incomplete: L_whole = L_out - 1); `silent`: transmit-silent columns (txGrid zero: rx .* conj(0));
@@ -109,8 +110,9 @@ def slab_plan(case):
 def build_scene(case, lib_radar_params=None):
     """QPSK txGrid on every antenna plane, CP-OFDM waveform at Nfft = 4096 scaled by signalAmp (gNBPhy.m:592), the oracle's radar_params (`orp`) and -- with the library's
     radarParams function handed in -- the library's (`rp`), both with nIFFT = 4096 and the rRes that goes with it (radarParams.m:69,71)."""
-    ci = SimpleNamespace(NRBsDL=case.nrb, SubcarrierSpacing=SCS_KHZ)
-    wi = SimpleNamespace(Nfft=NFFT, SampleRate=NFFT * SCS_KHZ * 1e3, SymbolsPerSlot=14, SlotsPerSubframe=2)
+    scs = case.scs                                                         # [kHz]; the table's cases are at SCS_KHZ
+    ci = SimpleNamespace(NRBsDL=case.nrb, SubcarrierSpacing=scs)
+    wi = SimpleNamespace(Nfft=NFFT, SampleRate=NFFT * scs * 1e3, SymbolsPerSlot=14, SlotsPerSubframe=scs // 15)
     cell = O.default_cell_params(n_ants=case.n_ants, target_pos=case.targets, velocity=case.velocity, rcs=np.full(len(case.targets), case.rcs))
     # the CPI is one or two slots: numSlots (radarParams.m:18-21,75) says so, nFFT = 32 / 64 -- with the default 20 the 14 live symbols sit in a 256-point Doppler transform
     # whose main lobe covers the CFAR training ring, and no scene of the table could have a detection (test_gpu_spectral._range_stage_scene does the same)
@@ -125,16 +127,16 @@ def build_scene(case, lib_radar_params=None):
     if case.zero_from is not None:
         tx_grid[:, case.zero_from:, :] = 0
     amp = float(O.db2mag(cell.gNBTxPower - 30)) * np.sqrt(NFFT ** 2 / (k * a))
-    tx_wave = O.ofdm_modulate(tx_grid, NFFT, SCS_KHZ) * amp
+    tx_wave = O.ofdm_modulate(tx_grid, NFFT, scs) * amp
     tx_wave = np.asfortranarray(tx_wave[:tx_wave.shape[0] - case.cut])
 
     def overridden(fn):
         p = fn(cell, ci, wi)
         p.nIFFT = NFFT
-        p.rRes = LIGHTSPEED / (2 * SCS_KHZ * 1e3 * p.nIFFT)
+        p.rRes = LIGHTSPEED / (2 * scs * 1e3 * p.nIFFT)
         return p
 
-    starts, cps = O.symbol_starts(NFFT, SCS_KHZ, case.n_sym)
+    starts, cps = O.symbol_starts(NFFT, scs, case.n_sym)
     l_whole = int(sum(int(starts[s]) + int(cps[s]) + NFFT <= tx_wave.shape[0] for s in range(case.n_sym)))
     for arr in (tx_grid, tx_wave):
         arr.setflags(write=False)
@@ -153,7 +155,7 @@ def reference_echo(sc, with_noise=True):
     tnoise = None
     if with_noise:
         w = O.philox_spectral_noise(sc.K, sc.L_out, sc.A, sc.case.noise_seed)[:, :sc.L_whole, :]
-        tnoise = spectral_to_time_noise(w, sc.T, NFFT, SCS_KHZ, sc.orp.fc, sc.orp.fs)
+        tnoise = spectral_to_time_noise(w, sc.T, NFFT, sc.case.scs, sc.orp.fc, sc.orp.fs)
     e = O.mono_static_sensing(sc.tx_wave, (sc.K, sc.L_out, sc.A), sc.carrier, sc.orp, sc.los, tnoise, nfft=NFFT)
     e = np.asfortranarray(e)
     e.setflags(write=False)

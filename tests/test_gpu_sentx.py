@@ -1,5 +1,6 @@
 """senTxGrid / senTxWave accumulation (gNBPhy.m:591-612) and the windowed CP-OFDM modulator (nrOFDMModulate, gNBPhy.m:599) on the
-device against the oracle restatement (oracle/sentx.py, oracle/ofdm.py): <= 1e-10 relative, zero blocks exactly zero."""
+device against the oracle restatement (oracle/sentx.py, oracle/ofdm.py): <= 1e-10 relative, zero blocks exactly zero.  Slots inside a subframe: the slot offset
+sym0 = (slot mod (scs / 15)) 14 decides which symbols carry the long cyclic prefix -- at 120 kHz only slots 0 and 4 of the eight begin with one."""
 from __future__ import annotations
 
 from types import SimpleNamespace
@@ -28,7 +29,9 @@ def qpsk(shape, seed):
 
 
 @pytest.mark.parametrize("nrb,scs,nfft,n_slot,win", [(24, 30, 512, 0, 0), (24, 30, 512, 1, 18), (273, 30, 4096, 3, 144), (52, 15, 1024, 2, 36),
-                                                    (66, 60, 1024, 1, 8), (66, 60, 1024, 2, 72)])
+                                                    (66, 60, 1024, 1, 8), (66, 60, 1024, 2, 72),
+                                                    # 120 kHz: of the eight slots of a subframe only 0 and 4 begin with a long CP; 60 kHz: the last slot of a subframe
+                                                    (66, 120, 1024, 0, 0), (66, 120, 1024, 3, 8), (66, 120, 1024, 4, 72), (66, 120, 1024, 7, 36), (24, 60, 512, 3, 18)])
 def test_windowed_modulator_matches_oracle(pkg, nrb, scs, nfft, n_slot, win):
     ci = SimpleNamespace(NRBsDL=nrb, SubcarrierSpacing=scs)
     g = qpsk((12 * nrb, 14, 3), nrb + n_slot)
@@ -42,12 +45,11 @@ def test_windowed_modulator_matches_oracle(pkg, nrb, scs, nfft, n_slot, win):
         pkg.communication.phyLayer.nrOFDMModulate(ci, g, windowing=10 ** 6, nfft=nfft)
 
 
-@pytest.mark.parametrize("nrb,nfft,n_ants,win", [(24, 512, 4, 0), (273, 4096, 2, 144)])
-def test_sentx_accumulation_matches_oracle(pkg, nrb, nfft, n_ants, win):
-    ci = SimpleNamespace(NRBsDL=nrb, SubcarrierSpacing=30)
+def _sentx_case(pkg, nrb, scs, nfft, n_ants, win, candidates):
+    ci = SimpleNamespace(NRBsDL=nrb, SubcarrierSpacing=scs)
     tdd, pw = "DDDSU", 46.0
-    ref = O.sentx.SenTx(nfft, 30, tdd, pw, windowing=win)
-    slots = [s for s in range(10) if tdd[s % 5] != "U"]             # PDSCH goes out in D and S slots; U slots never reach phyTx's PDSCH branch
+    ref = O.sentx.SenTx(nfft, scs, tdd, pw, windowing=win)
+    slots = [s for s in candidates if tdd[s % 5] != "U"]            # PDSCH goes out in D and S slots; U slots never reach phyTx's PDSCH branch
     acc = pkg.communication.phyLayer.SenTx(ci, n_ants, len(slots), tdd, pw, windowing=win, nfft=nfft)
     for s in slots:
         g = qpsk((12 * nrb, 14, n_ants), 100 + s)
@@ -68,3 +70,16 @@ def test_sentx_accumulation_matches_oracle(pkg, nrb, nfft, n_ants, win):
         return
     d_grid, d_wave = acc.device_arrays()
     assert np.array_equal(d_grid.numpy(), ref.grid) and rel(d_wave.numpy(), ref.wave) < 1e-10
+
+
+@pytest.mark.parametrize("nrb,nfft,n_ants,win", [(24, 512, 4, 0), (273, 4096, 2, 144)])
+def test_sentx_accumulation_matches_oracle(pkg, nrb, nfft, n_ants, win):
+    _sentx_case(pkg, nrb, 30, nfft, n_ants, win, range(10))
+
+
+def test_sentx_accumulation_at_120_khz_slots(pkg):
+    """Slots 8, 11, 12, 15 sit at positions 0, 3, 4, 7 of their subframes (eight slots at 120 kHz; only positions 0 and 4 begin with a long CP) and are S, D, D, D slots of
+    the TDD pattern: the slot offset sym0 = (slot mod 8) 14 of isac_sentx_append_dev against oracle/sentx.py."""
+    slots = (8, 11, 12, 15)
+    assert [s % 8 for s in slots] == [0, 3, 4, 7] and ["DDDSU"[s % 5] for s in slots] == ["S", "D", "D", "D"]
+    _sentx_case(pkg, 66, 120, 1024, 3, 8, slots)
