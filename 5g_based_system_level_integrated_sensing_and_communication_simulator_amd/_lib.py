@@ -271,6 +271,10 @@ ISAC_DIR_MAX_SOURCES = 8
 PROTOTYPES_DIRECTIONS = {
     "isac_resolve_directions": (_INT, (_P, _ptr(EstParams), _P, _I32, _I32, _I32, _I32, _F64, _F64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P)),
 }
+# ... and include/isac_beam_clean.h (tests/test_beam_clean_cpu.py pins it)
+PROTOTYPES_BEAM_CLEAN = {
+    "isac_fft2d_beam_clean_targets": (_INT, (_P, _P, _I32, _P, _ptr(CfarMethod), _I32, _I32, _F64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P)),
+}
 
 
 def library_path() -> str:
@@ -297,7 +301,7 @@ def load():
             except Exception:
                 pass
         lib = C.CDLL(_LIB_PATH, mode=C.RTLD_GLOBAL)
-        for name, (restype, argtypes) in {**PROTOTYPES, **PROTOTYPES_ADDED, **PROTOTYPES_CFAR, **PROTOTYPES_CFAR_MC, **PROTOTYPES_LAZY_COV, **PROTOTYPES_TARGETS_UPA, **PROTOTYPES_BEAMS, **PROTOTYPES_REFINE, **PROTOTYPES_CLEAN, **PROTOTYPES_RELAX, **PROTOTYPES_DIRECTIONS}.items():
+        for name, (restype, argtypes) in {**PROTOTYPES, **PROTOTYPES_ADDED, **PROTOTYPES_CFAR, **PROTOTYPES_CFAR_MC, **PROTOTYPES_LAZY_COV, **PROTOTYPES_TARGETS_UPA, **PROTOTYPES_BEAMS, **PROTOTYPES_REFINE, **PROTOTYPES_CLEAN, **PROTOTYPES_RELAX, **PROTOTYPES_DIRECTIONS, **PROTOTYPES_BEAM_CLEAN}.items():
             fn = getattr(lib, name)  # AttributeError here = ABI drift between isac.h and the .so
             fn.restype, fn.argtypes = restype, argtypes
         # the library writes whole structs into caller memory: version AND struct sizes must match this binding's mirrors

@@ -12,6 +12,7 @@
 #include <cmath>
 
 #include "isac_internal.hpp"
+#include "beam_cell.hpp"
 #include "rdm_cell.hpp"
 
 namespace isac {
@@ -39,8 +40,6 @@ __global__ __launch_bounds__(256) void rdm_window_kernel(const c64* __restrict__
   }
 }
 
-constexpr int kBeamTile = 8;
-
 __global__ __launch_bounds__(256) void beam_planes_kernel(const c64* __restrict__ Y /* [n_cells x A] */, long long n_cells, int A, const c64* __restrict__ W /* [A x B] */,
                                                           const double* __restrict__ norm /* [B]: n_b */, int B, double* __restrict__ Pb /* [n_cells x B] */) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -64,7 +63,7 @@ __global__ __launch_bounds__(256) void beam_planes_kernel(const c64* __restrict_
   }
 #pragma unroll
   for (int j = 0; j < kBeamTile; ++j)
-    if (j < nb) Pb[i + n_cells * (b0 + j)] = __ddiv_rn(__dadd_rn(__dmul_rn(z[j].re, z[j].re), __dmul_rn(z[j].im, z[j].im)), norm[b0 + j]);   // re^2 + im^2: two rounded products, one rounded sum -- never contracted
+    if (j < nb) Pb[i + n_cells * (b0 + j)] = beam_cell_power(z[j], norm[b0 + j]);   // beam_cell.hpp: re^2 + im^2 as two rounded products and one rounded sum, never contracted
 }
 
 }  // namespace isac
@@ -105,6 +104,26 @@ int rdm_window_enqueue(isac_ctx* ctx, const char* who, const c64* d_rows, c64* d
   return ISAC_OK;
 }
 
+int beam_weight_norms(isac_ctx* ctx, const char* who, const isac_c64* W, int A, int B, std::vector<double>& norm) {
+  norm.resize((size_t)B);
+  for (int b = 0; b < B; ++b) {                                           // n_b in fp64, ascending a from 0.0
+    double n = 0.0;
+    for (int a = 0; a < A; ++a) { const isac_c64& v = W[a + (size_t)A * b]; n += v.re * v.re + v.im * v.im; }
+    if (!(n > 0.0) || !std::isfinite(n)) return fail(ctx, ISAC_ERR_INVALID_ARG, std::string(who) + ": a column of W has a zero or non-finite norm");
+    norm[(size_t)b] = n;
+  }
+  return ISAC_OK;
+}
+
+int beam_planes_enqueue(isac_ctx* ctx, const c64* d_Y, long long n_cells, const c64* d_W, const double* d_norm, int B, double* d_Pb) {
+  const int A = ctx->tgt.A;
+  const size_t lds = sizeof(c64) * (size_t)A * kBeamTile;
+  ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(beam_planes_kernel), lds));
+  hipLaunchKernelGGL(beam_planes_kernel, dim3(cdiv(n_cells, 256), cdiv(B, kBeamTile)), dim3(256), lds, ctx->stream, d_Y, n_cells, A, d_W, d_norm, B, d_Pb);
+  ISAC_HIP(hipGetLastError());
+  return ISAC_OK;
+}
+
 extern "C" int isac_fft2d_get_rdm_window(isac_ctx* ctx, isac_c64* Y, int64_t cap_elems, int32_t dims[3], int32_t* first_row, int32_t* first_col) {
   ISAC_ENTER(ctx);
   ISAC_TRY(cpi_ready(ctx, "isac_fft2d_get_rdm_window"));
@@ -133,13 +152,8 @@ extern "C" int isac_fft2d_beam_detect(isac_ctx* ctx, const isac_c64* W, int32_t 
   if (B > ISAC_MAX_BEAMS) return fail(ctx, ISAC_ERR_UNSUPPORTED, std::string(who) + ": more than ISAC_MAX_BEAMS beams");
   if (n_cells * B >= (1ll << 31)) return fail(ctx, ISAC_ERR_UNSUPPORTED, std::string(who) + ": the beam planes hold 2^31 cells or more");
   if (w.hr < 1 || w.hc < 1) return fail(ctx, ISAC_ERR_UNSUPPORTED, std::string(who) + ": the local-maximum test needs a halo of at least one cell (guard + training) in both dimensions");
-  std::vector<double> norm((size_t)B);
-  for (int b = 0; b < B; ++b) {                                           // n_b in fp64, ascending a from 0.0
-    double n = 0.0;
-    for (int a = 0; a < A; ++a) { const isac_c64& v = W[a + (size_t)A * b]; n += v.re * v.re + v.im * v.im; }
-    if (!(n > 0.0) || !std::isfinite(n)) return fail(ctx, ISAC_ERR_INVALID_ARG, std::string(who) + ": a column of W has a zero or non-finite norm");
-    norm[(size_t)b] = n;
-  }
+  std::vector<double> norm;
+  ISAC_TRY(beam_weight_norms(ctx, who, W, A, B, norm));
   // ---- steps 1, 2: ctx->beam_y = [Y nr nc A | W A B | n_b B], ctx->beam_p = the beam planes
   const size_t off_w = sizeof(c64) * (size_t)n_cells * A, off_n = off_w + sizeof(c64) * (size_t)A * B;
   ISAC_TRY(ensure(ctx, ctx->beam_y, off_n + sizeof(double) * (size_t)B));
@@ -148,11 +162,7 @@ extern "C" int isac_fft2d_beam_detect(isac_ctx* ctx, const isac_c64* W, int32_t 
   ISAC_TRY(copy_h2d(ctx, dy + off_w, W, sizeof(c64) * (size_t)A * B));
   ISAC_TRY(copy_h2d(ctx, dy + off_n, norm.data(), sizeof(double) * (size_t)B));
   ISAC_TRY(enqueue_rdm_window(ctx, who));                                  // (beam_y is large enough already: ensure keeps it)
-  const size_t lds = sizeof(c64) * (size_t)A * kBeamTile;
-  ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(beam_planes_kernel), lds));
-  hipLaunchKernelGGL(beam_planes_kernel, dim3(cdiv(n_cells, 256), cdiv(B, kBeamTile)), dim3(256), lds, ctx->stream, (const c64*)dy, n_cells, A, (const c64*)(dy + off_w),
-                     (const double*)(dy + off_n), B, (double*)ctx->beam_p.p);
-  ISAC_HIP(hipGetLastError());
+  ISAC_TRY(beam_planes_enqueue(ctx, (const c64*)dy, n_cells, (const c64*)(dy + off_w), (const double*)(dy + off_n), B, (double*)ctx->beam_p.p));
   // ---- step 3: the detector of isac_fft2d_redetect on the beam planes
   PlaneLists pl;
   ISAC_TRY(cfar_detect_planes(ctx, who, m, (const double*)ctx->beam_p.p, B, ctx->beam_det, &pl));

@@ -102,6 +102,7 @@ constexpr int kPanelColsMax = 8;                                // CUT columns p
 struct WinGeom {
   int nr, nc;                    // power window dims
   int n_cut_rows, n_cut_cols;
+  int cut_row_lo, cut_row_hi;    // the CUT rows this launch evaluates: [cut_row_lo, cut_row_hi) of 0 .. n_cut_rows (all of them, or the band of isac_fft2d_beam_clean_targets)
   int pc;                        // CUT columns per workgroup, 1..kPanelColsMax (from the LDS budget)
   CutGeom c;
 };
@@ -113,7 +114,7 @@ __global__ __launch_bounds__(kPanelRows * kPanelColsMax) void cfar_method_window
   double* s_p = reinterpret_cast<double*>(smem_raw);            // [pc + 2 hc][kPanelRows + 2 hr], rows fastest
   constexpr int NT = kPanelRows * kPanelColsMax;
   const int tid = threadIdx.x;
-  const int r0 = blockIdx.x * kPanelRows, c0 = blockIdx.y * g.pc, a = blockIdx.z;   // first CUT row / column of the tile = first window row / column staged
+  const int r0 = g.cut_row_lo + blockIdx.x * kPanelRows, c0 = blockIdx.y * g.pc, a = blockIdx.z;   // first CUT row / column of the tile = first window row / column staged
   const int wr = kPanelRows + 2 * g.c.hr, wc = g.pc + 2 * g.c.hc;
   {   // 8 independent loads in flight per thread (cells past the window, where the tile overhangs the zone: clamped, never used by a CUT)
     const double* src = pwin + (long long)g.nr * g.nc * a;
@@ -133,7 +134,7 @@ __global__ __launch_bounds__(kPanelRows * kPanelColsMax) void cfar_method_window
   __syncthreads();
   const int crl = tid % kPanelRows, ccl = tid / kPanelRows;     // lanes along a column read consecutive doubles: no bank conflict
   const int cr = r0 + crl, cc = c0 + ccl;
-  if (ccl < g.pc && cr < g.n_cut_rows && cc < g.n_cut_cols) {
+  if (ccl < g.pc && cr < g.cut_row_hi && cc < g.n_cut_cols) {
     const bool det = cfar_cut<M>(s_p + (ccl + g.c.hc) * wr + crl + g.c.hr, wr, g.c);
     flags[(long long)a * g.n_cut_rows * g.n_cut_cols + cr + (long long)g.n_cut_rows * cc] = det ? 1 : 0;
   }
@@ -380,21 +381,40 @@ extern "C" int isac_cfar2d(isac_ctx* ctx, const double* P, int32_t n_rows, int32
 // The device half of isac_fft2d_redetect, on any planes [nr x nc x n_planes] with the geometry of the CPI's power window: detector m with the CPI's stored guard / training
 // bands and pfa on every plane over the stored CUT rectangle, the flags compacted into per-plane CUT-order lists.  Everything stays in `scratch` (described by *pl); the
 // counts and offsets are on the host when it returns.  who: the entry point, for the messages.
-int cfar_detect_planes(isac_ctx* ctx, const char* who, const isac_cfar_method* m, const double* d_planes, int n_planes, DevBuf& scratch, PlaneLists* pl) {
+// K1 alone: the flags [n_planes][n_cut] (CUT order) of the CUT rows [cut_row_lo, cut_row_hi) of every plane into d_flags (sized by the caller: n_planes n_cut bytes); the
+// flags of every other CUT row keep what they hold.  A flag is a function of the bits of its own guard + training window and of nothing else, so a band of rows evaluated
+// again after the planes changed inside it gives the flags a run over every row would.  An empty range checks the method block and the limits and launches nothing.
+int cfar_flag_planes(isac_ctx* ctx, const char* who, const isac_cfar_method* m, const double* d_planes, int n_planes, int cut_row_lo, int cut_row_hi, unsigned char* d_flags) {
   const Fft2dCpi& ts = ctx->tgt;
   const isac_cfar_config& cf = ts.cfar;
   WinGeom g{};
   ISAC_TRY(cut_geom(ctx, cf.guard, cf.train, cf.pfa, m, &g.c));
   g.nr = ts.win.nr; g.nc = ts.win.nc; g.n_cut_rows = ts.win.n_cut_rows; g.n_cut_cols = ts.win.n_cut_cols;   // (both >= 1: the submit that left the window refuses an empty zone)
-  const long long n_cut_ll = ts.win.n_cut();
-  if (n_cut_ll * n_planes > (1ll << 30)) return fail(ctx, ISAC_ERR_UNSUPPORTED, std::string(who) + ": more than 2^30 (CUT, plane) pairs");
-  const int n_cut = (int)n_cut_ll;
+  g.cut_row_lo = std::max(cut_row_lo, 0); g.cut_row_hi = std::min(cut_row_hi, g.n_cut_rows);
+  if (ts.win.n_cut() * n_planes > (1ll << 30)) return fail(ctx, ISAC_ERR_UNSUPPORTED, std::string(who) + ": more than 2^30 (CUT, plane) pairs");
   // CUT columns per workgroup: as many as fit ~128 KB of LDS with the panel's kPanelRows + 2 hr rows, at most one per wave quarter (kPanelColsMax)
   const size_t budget = 128 * 1024;
   const long long fit = (long long)(budget / (sizeof(double) * (size_t)(kPanelRows + 2 * g.c.hr))) - 2ll * g.c.hc;
   if (fit < 1) return fail(ctx, ISAC_ERR_UNSUPPORTED, std::string(who) + ": guard + training band too large for the LDS-staged detector");
   g.pc = (int)std::min<long long>(fit, std::min(kPanelColsMax, g.n_cut_cols));
   const size_t lds = sizeof(double) * (size_t)(kPanelRows + 2 * g.c.hr) * (size_t)(g.pc + 2 * g.c.hc);
+  if (g.cut_row_hi <= g.cut_row_lo) return ISAC_OK;
+  CFAR_METHOD_DISPATCH(m->method, {
+    auto kern = cfar_method_window_kernel<M>;
+    ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(kern), lds));
+    hipLaunchKernelGGL(kern, dim3(cdiv(g.cut_row_hi - g.cut_row_lo, kPanelRows), cdiv(g.n_cut_cols, g.pc), n_planes), dim3(kPanelRows * kPanelColsMax), lds, ctx->stream,
+                       d_planes, g, d_flags);
+  });
+  ISAC_HIP(hipGetLastError());
+  return ISAC_OK;
+}
+
+int cfar_detect_planes(isac_ctx* ctx, const char* who, const isac_cfar_method* m, const double* d_planes, int n_planes, DevBuf& scratch, PlaneLists* pl) {
+  const Fft2dCpi& ts = ctx->tgt;
+  const CutWindow& g = ts.win;
+  const long long n_cut_ll = g.n_cut();
+  ISAC_TRY(cfar_flag_planes(ctx, who, m, d_planes, n_planes, 0, 0, nullptr));   // the method block and the limits, before the scratch is sized
+  const int n_cut = (int)n_cut_ll;
   // every list sized for all CUTs: [det_pow n_planes n_cut | det_cut n_planes n_cut | det_cnt n_planes | row_seen n_cut_rows | flags n_planes n_cut]
   const size_t n_pairs = (size_t)n_planes * n_cut;
   const size_t off_cut = sizeof(double) * n_pairs, off_cnt = off_cut + sizeof(int) * n_pairs, off_rows = off_cnt + sizeof(int) * (size_t)n_planes;
@@ -402,14 +422,8 @@ int cfar_detect_planes(isac_ctx* ctx, const char* who, const isac_cfar_method* m
   ISAC_TRY(ensure(ctx, scratch, off_flags + n_pairs));
   char* d = (char*)scratch.p;
   ISAC_HIP(hipMemsetAsync(d + off_rows, 0, sizeof(unsigned) * (size_t)g.n_cut_rows, ctx->stream));
-  CFAR_METHOD_DISPATCH(m->method, {
-    auto kern = cfar_method_window_kernel<M>;
-    ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(kern), lds));
-    hipLaunchKernelGGL(kern, dim3(cdiv(g.n_cut_rows, kPanelRows), cdiv(g.n_cut_cols, g.pc), n_planes), dim3(kPanelRows * kPanelColsMax), lds, ctx->stream,
-                       d_planes, g, (unsigned char*)(d + off_flags));
-  });
-  ISAC_HIP(hipGetLastError());
-  hipLaunchKernelGGL(cfar_compact_kernel, dim3(n_planes), dim3(256), 0, ctx->stream, (const unsigned char*)(d + off_flags), d_planes, g.nr, g.nc, g.c.hr, g.c.hc,
+  ISAC_TRY(cfar_flag_planes(ctx, who, m, d_planes, n_planes, 0, g.n_cut_rows, (unsigned char*)(d + off_flags)));
+  hipLaunchKernelGGL(cfar_compact_kernel, dim3(n_planes), dim3(256), 0, ctx->stream, (const unsigned char*)(d + off_flags), d_planes, g.nr, g.nc, g.hr, g.hc,
                      g.n_cut_rows, n_cut, (int*)(d + off_cut), (double*)d, (int*)(d + off_cnt), (unsigned*)(d + off_rows));
   ISAC_HIP(hipGetLastError());
   std::vector<int> tail((size_t)n_planes + g.n_cut_rows);       // [det_cnt | row_seen]

@@ -52,6 +52,15 @@ __global__ __launch_bounds__(256) void clean_cancel_kernel(c64* R /* [nr x L x A
 // ================================================================= host side
 using namespace isac;
 
+int clean_cancel_enqueue(isac_ctx* ctx, c64* d_R, int row_lo, int row_hi, double nu, const unsigned char* d_active, int n_active) {
+  const Fft2dCpi& ts = ctx->tgt;
+  const size_t lds = sizeof(c64) * ((size_t)ts.L + ts.A) + sizeof(double) * 2 * (size_t)ts.A;   // (<= the refinement's, which refine_plan has bounded by 160 KB)
+  ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(clean_cancel_kernel), lds));
+  hipLaunchKernelGGL(clean_cancel_kernel, dim3(row_hi - row_lo + 1), dim3(256), lds, ctx->stream, d_R, ts.win.nr, ts.L, ts.A, row_lo, nu, d_active, (double)n_active);
+  ISAC_HIP(hipGetLastError());
+  return ISAC_OK;
+}
+
 extern "C" int isac_fft2d_clean_targets(isac_ctx* ctx, const isac_cfar_method* m, int32_t max_iter, int32_t span_rows, double merge_tol, const uint8_t* sym_active, int32_t* n_iter,
                                         int32_t* n_kept, int32_t* n_left, int32_t* row, int32_t* col, int32_t* hits, int32_t* status, int32_t* parent, double* map_power, double* nu,
                                         double* vel, double* rng, double* power, double* azi, double* ele, isac_c64* snapshots, isac_c64* residual_rows) {
@@ -98,8 +107,6 @@ extern "C" int isac_fft2d_clean_targets(isac_ctx* ctx, const isac_cfar_method* m
   int* d_rec = (int*)(d + off_rec);
   ISAC_HIP(hipMemcpyAsync(d_R, ctx->ymid.p, sizeof(c64) * n_rows_el, hipMemcpyDeviceToDevice, ctx->stream));
   ISAC_TRY(copy_h2d(ctx, d + off_act, act.data(), (size_t)L));
-  const size_t lds_cancel = sizeof(c64) * ((size_t)L + A) + sizeof(double) * 2 * (size_t)A;   // (<= the refinement's, which refine_plan has bounded by 160 KB)
-  ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(clean_cancel_kernel), lds_cancel));
   std::unique_ptr<isac_target_list> tl(new isac_target_list);
   int kept = 0;
   for (int i = 0;; ++i) {
@@ -137,8 +144,7 @@ extern "C" int isac_fft2d_clean_targets(isac_ctx* ctx, const isac_cfar_method* m
     // ---- step 8
     const int wr = sel[0];                                                 // 0 <= wr < nr: a CUT row of the window
     const int lo = (int)std::max<long long>((long long)wr - span_rows, 0), hi = (int)std::min<long long>((long long)wr + span_rows, w.nr - 1);
-    hipLaunchKernelGGL(clean_cancel_kernel, dim3(hi - lo + 1), dim3(256), lds_cancel, ctx->stream, d_R, w.nr, L, A, lo, nu[i], (const unsigned char*)(d + off_act), (double)n_active);
-    ISAC_HIP(hipGetLastError());
+    ISAC_TRY(clean_cancel_enqueue(ctx, d_R, lo, hi, nu[i], (const unsigned char*)(d + off_act), n_active));
   }
   *n_kept = kept;
   if (snapshots && *n_iter > 0) ISAC_TRY(copy_d2h(ctx, snapshots, d + off_snap, sizeof(c64) * (size_t)A * *n_iter));

@@ -53,6 +53,9 @@ struct PlaneLists {
 }
 int cfar_detect_planes(isac_ctx* ctx, const char* who, const isac_cfar_method* m, const double* d_planes, int n_planes, isac::DevBuf& scratch, isac::PlaneLists* pl);
 int cfar_fetch_lists(isac_ctx* ctx, const isac::PlaneLists& pl, std::vector<int>& cut, std::vector<double>& pw);
+// ... and its first kernel alone, for beam_clean.hip: the per-CUT flags [n_planes][n_cut] of the CUT rows [cut_row_lo, cut_row_hi) (0-based inside the zone, clipped to it)
+// into d_flags, the other rows' flags untouched; an empty range checks the method block and the detector's limits and launches nothing
+int cfar_flag_planes(isac_ctx* ctx, const char* who, const isac_cfar_method* m, const double* d_planes, int n_planes, int cut_row_lo, int cut_row_hi, unsigned char* d_flags);
 // ---------------------------------------------------------------- targets.hip, for beams.hip: steps 1, 2 and 5 of the lists (hits, local maxima of the map, order, every field of *out but azi and n_targets) on the
 // planes [nr x nc x n_planes] and per-plane lists of `src`
 namespace isac {
@@ -79,9 +82,20 @@ int refine_enqueue(isac_ctx* ctx, const isac::RefinePlan& plan, const isac::c64*
 // beam planes of it.  Reads ctx->tgt and ctx->ymid, writes ctx->beam_y / beam_p / beam_det / beam_sel only; calls isac_get_twiddles, cfar_detect_planes and target_cells_of_planes.
 // For clean.hip: step 1 of isac_beams.h: rdm_window_kernel on the range rows d_rows [nr x L x A] into d_Y [nr x nc x A] (both sized by the caller), enqueued on the context's stream
 int rdm_window_enqueue(isac_ctx* ctx, const char* who, const isac::c64* d_rows, isac::c64* d_Y);
+// For beam_clean.hip: n_b of every column of the host weights W [A x B] (ISAC_ERR_INVALID_ARG: a zero or non-finite norm), and step 2 of isac_beams.h: beam_planes_kernel on
+// d_Y [n_cells x A] with the weights d_W [A x B] and norms d_norm [B] into d_Pb [n_cells x B] (all on the device, sized by the caller), enqueued on the context's stream
+int beam_weight_norms(isac_ctx* ctx, const char* who, const isac_c64* W, int A, int B, std::vector<double>& norm);
+int beam_planes_enqueue(isac_ctx* ctx, const isac::c64* d_Y, long long n_cells, const isac::c64* d_W, const double* d_norm, int B, double* d_Pb);
 // ---------------------------------------------------------------- clean.hip: isac_fft2d_clean_targets (include/isac_clean.h) -- successive cancellation on a residual copy of the range rows of the last completed
 // fft2D.  Reads ctx->tgt and ctx->ymid, writes ctx->clean / clean_det / clean_sel (and ctx->tgt_part through target_scan_snapshots) only; calls rdm_window_enqueue, cfar_detect_planes,
 // target_cells_of_planes, refine_plan / refine_enqueue and target_scan_snapshots.
+// For beam_clean.hip: step 8 of isac_clean.h -- clean_cancel_kernel on the window rows row_lo .. row_hi (0-based, clipped by the caller) of d_R [nr x L x A] at nu, over the
+// symbols d_active [L] names (n_active of them), enqueued on the context's stream
+int clean_cancel_enqueue(isac_ctx* ctx, isac::c64* d_R, int row_lo, int row_hi, double nu, const unsigned char* d_active, int n_active);
+// ---------------------------------------------------------------- beam_clean.hip: isac_fft2d_beam_clean_targets (include/isac_beam_clean.h) -- successive cancellation with the detector on beam planes of a
+// residual copy of the range rows of the last completed fft2D; planes, flags and the map over the beams stay on the device across the passes and are updated by row band.  Reads
+// ctx->tgt and ctx->ymid, writes ctx->beam_clean (and ctx->tgt_part through target_scan_snapshots) only; calls rdm_window_enqueue, beam_weight_norms / beam_planes_enqueue,
+// cfar_flag_planes, refine_plan / refine_enqueue, clean_cancel_enqueue and target_scan_snapshots.
 // ---------------------------------------------------------------- relax.hip: isac_fft2d_relax_targets (include/isac_relax.h) -- joint re-fit of Doppler tones on a residual copy of the range rows of the last
 // completed fft2D.  Reads ctx->tgt and ctx->ymid, writes ctx->relax (and ctx->tgt_part through target_scan_snapshots) only; calls refine_plan, isac_doa2d_grid and target_scan_snapshots.
 // ---------------------------------------------------------------- directions.hip: isac_resolve_directions (include/isac_directions.h) -- off-grid direction finding with several sources per array snapshot.

@@ -21,6 +21,7 @@
 #include <numeric>
 
 #include "isac_internal.hpp"
+#include "beam_cell.hpp"
 #include "rdm_cell.hpp"
 #include "upa_steer.hpp"
 
@@ -67,10 +68,7 @@ __global__ __launch_bounds__(kCellR * kCellC) void target_cells_kernel(const dou
       const double* p = pwin + wr + (long long)nr * wc;
       if constexpr (MAX) {
         int best = 0;
-        for (int a = 0; a < A; ++a) {
-          const double v = p[plane * a];
-          if (v > s || (s != s && v == v)) { s = v; best = a; }           // strictly greater: the first maximum stays
-        }
+        s = planes_first_max(p, plane, A, &best);                         // beam_cell.hpp: strictly greater, the first maximum stays
         s_plane[lc * SR + lr] = best;
       } else {
         s = 0.0;

@@ -7,6 +7,7 @@ from .beamWeights import beamWeights  # noqa: F401
 from .beamDetect import beamDetect  # noqa: F401
 from .refineTargets import refineTargets  # noqa: F401
 from .cleanTargets import cleanTargets  # noqa: F401
+from .beamClean import beamClean  # noqa: F401
 from .relaxTargets import relaxTargets  # noqa: F401
 from .resolveDirections import resolveDirections  # noqa: F401
 from . import doaEstimation  # noqa: F401
