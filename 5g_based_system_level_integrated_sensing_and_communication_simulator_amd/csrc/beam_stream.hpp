@@ -14,7 +14,7 @@
 
 namespace isac {
 
-constexpr int kBeamStreamLoads = 6;   // antenna loads per thread and slab step: 8 units x 11 steps fit the 96 steps of a workgroup at the bench shape, 12.6 MB in flight device-wide
+constexpr int kBeamStreamLoads = 6;   // antenna loads per thread and slab step: 7 units x 11 steps fit the 84 steps of a workgroup at the bench shape (the full slabs: noise_walk.hpp), 12.6 MB in flight device-wide
 constexpr int kBeamStreamTab = 32;    // unit table entries per workgroup (LDS)
 
 ISAC_HD inline int bs_steps_per_unit(int A) { return (A + kBeamStreamLoads - 1) / kBeamStreamLoads; }

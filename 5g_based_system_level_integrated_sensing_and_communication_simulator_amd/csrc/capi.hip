@@ -79,6 +79,7 @@ extern "C" int isac_ctx_destroy(isac_ctx* ctx) {
   (void)hipStreamSynchronize(ctx->stream);
   (void)hipStreamSynchronize(ctx->stream2);
   for (auto& e : ctx->ev_bounce) if (e) (void)hipEventDestroy(e);
+  for (auto& e : ctx->ev_tail) if (e) (void)hipEventDestroy(e);
   (void)hipEventDestroy(ctx->ev_fork);
   (void)hipEventDestroy(ctx->ev_join);
   (void)hipEventDestroy(ctx->ev_cfar);

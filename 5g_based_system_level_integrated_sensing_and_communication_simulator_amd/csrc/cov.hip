@@ -10,11 +10,13 @@
 // k-steps; the k index is only a summation label, so no transposition is needed.
 // Per-workgroup partial tiles are reduced in a fixed order (deterministic).
 #include <algorithm>
+#include <cstdlib>
 #include <cstring>
 #include <type_traits>
 #include "isac_internal.hpp"
 #include "echo_dev.hpp"
 #include "beam_stream.hpp"
+#include "noise_walk.hpp"
 
 namespace isac {
 
@@ -938,7 +940,8 @@ __global__ __launch_bounds__(256, 2) void cov_lazy_kernel(LazyCovArgs a, long lo
 //     M[a, b] = sum_n conj(w[n, a]) w[n, b],   c_q[r] = sum_n w[n, r] conj(d_q[n]),   H_pq = sum_n conj(d_p[n]) d_q[n].
 // M is the whole MFMA bulk and depends on the seed and the shape alone -- not on the waveform, D or the steering vectors -- so it can run at the HEAD of the CPI, in the kernel
 // that streams txWaveform for the beam-sum: cov_noise_beam_kernel is cov_lazy_kernel with the synthesis taken out of the generator (the UNIT noise value, masked, goes into the
-// LDS image; same slab order, pair rows, antenna and half masks, so the same field elements enter the sum) and the beam-sum's loads and folds in the MFMA gaps instead
+// LDS image; same pair rows, antenna and half masks, and the slab order of that kernel's FULL slabs -- the half slabs, whose partner rows all lie beyond K, are
+// cov_noise_tail_kernel's, below -- so the same field elements enter the sum) and the beam-sum's loads and folds in the MFMA gaps instead
 // (beam_stream.hpp: the most HBM-bound and the most MFMA-bound kernel of the CPI, each idle in what the other needs, in one instruction stream).  c_q comes from the range
 // kernel, which holds w and d in registers (echo_range_xc_kernel, echo.hip; two LoS targets: cov_cross_kernel below); cov_assemble_kernel below puts the three terms together.
 struct NoiseBeamArgs {
@@ -948,7 +951,7 @@ struct NoiseBeamArgs {
   c64* beam;                  // [QT x T]: written inside the BeamWindow's ranges
   long long T;
   unsigned long long seed;
-  int K, L_out, A, s_col;
+  int K, L_out, A, s_col;     // s_col: FULL slabs per symbol column (noise_walk.hpp)
   BeamWindow bw;
 };
 constexpr int kBeamSteerPitch = 72;                             // steering image per target: zero from A on (>= kBeamStreamLoads * bs_steps_per_unit(64))
@@ -979,11 +982,22 @@ __device__ __forceinline__ BeamUnitEntry beam_unit_entry(const BeamWindow& bw, l
   return e;
 }
 
+// box_muller32_hw_f32 (echo_dev.hpp: the same expressions, so an unmasked element has its bits) with the mask applied once, to the radius, in front of the two products
+__device__ __forceinline__ void cov_noise_bm_masked(uint32_t ur, uint32_t ua, bool ok, float& re, float& im) {
+  const float u = __builtin_fmaf((float)ur, 0x1.0p-32f, 0x1.0p-33f);
+  const float rad = __builtin_amdgcn_sqrtf(__builtin_amdgcn_logf(u) * -1.3862943611198906f);
+  const float turns = (float)ua * 0x1.0p-32f;
+  const float rm = ok ? rad : 0.0f;
+  re = rm * __builtin_amdgcn_cosf(turns);
+  im = rm * __builtin_amdgcn_sinf(turns);
+}
+
 // The slab source of cov_noise_beam_kernel: the unit noise of CovLazyGenerator's slabs (thread -> pair row gp, antennas ga and ga + 32) plus the beam pieces.  Per slab step
 // 27 pieces sit in the 30 MFMA gaps: the generator's 18 (counter set-up + 10 Philox rounds, 4 Box-Muller transforms, 4 x (widen + mask + LDS store)) and 9 of the beam-sum --
 // two folds of the six values loaded a step ago (antenna order, the additions of beam_sample: the bits beamsum_kernel produces), the store of a finished unit, the running
 // unit's offsets, six loads -- interleaved with the generator's first pieces.  The cursors (unit n of the table, step i of the unit) are wave-uniform; nothing branches.
-// init / round / bm / advance and the masks are CovLazyGenerator's, restated (that kernel is pinned instruction by instruction; a change there must be made here too).
+// init / round / advance and the masks are CovLazyGenerator's, restated (that kernel is pinned instruction by instruction; a change there must be made here too); bm is its
+// transform with the element's mask on the radius, emit only widens.
 template <int QT>
 struct CovNoiseBeamSource {
   static constexpr int NB = 4;
@@ -1000,9 +1014,10 @@ struct CovNoiseBeamSource {
   float wf[2][2][2];
   bool v_half[2];
   // beam pieces
-  const c64* tx;
-  long long T;
   int A, spu, W;
+  __amdgpu_buffer_rsrc_t rs_tx;                      // the whole waveform [T x A]: the antenna is the load's scalar offset (T A 16 < 2^31: isac_lazy_split_ok)
+  unsigned T16, s_ant;                               // bytes of an antenna column; scalar offset of the next load = T16 x its antenna
+  int rem;                                           // antennas the running unit has left at the top of step i: A - kBeamStreamLoads i
   __amdgpu_buffer_rsrc_t rs_beam[QT];
   const c64* s_steer;                                // LDS [QT][kBeamSteerPitch]
   const BeamUnitEntry* s_tab;                        // LDS [kBeamStreamTab]
@@ -1012,8 +1027,9 @@ struct CovNoiseBeamSource {
   c64 acc[QT];
   unsigned voff, soff;
   __device__ __forceinline__ CovNoiseBeamSource(const NoiseBeamArgs& a, long long s_begin, long long s_end_, const c64* s_steer_, const BeamUnitEntry* s_tab_)
-      : gp(threadIdx.x & 7), ga(threadIdx.x >> 3), K(a.K), s_col(a.s_col), key0((uint32_t)a.seed), key1((uint32_t)(a.seed >> 32)), s_end(s_end_), tx(a.tx), T(a.T), A(a.A),
-        spu(bs_steps_per_unit(a.A)), W(a.bw.units_per_symbol * kBeamUnit), s_steer(s_steer_), s_tab(s_tab_), n(0), i(0), ip(0), fin(false), voff(kCovOobOffset), soff(kCovOobOffset) {
+      : gp(threadIdx.x & 7), ga(threadIdx.x >> 3), K(a.K), s_col(a.s_col), key0((uint32_t)a.seed), key1((uint32_t)(a.seed >> 32)), s_end(s_end_), A(a.A),
+        spu(bs_steps_per_unit(a.A)), W(a.bw.units_per_symbol * kBeamUnit), rs_tx(buffer_of(a.tx, (unsigned)(a.T * (long long)a.A * (long long)sizeof(c64)))),
+        T16(__builtin_amdgcn_readfirstlane((unsigned)(a.T * (long long)sizeof(c64)))), s_ant(0u), rem(a.A), s_steer(s_steer_), s_tab(s_tab_), n(0), i(0), ip(0), fin(false), voff(kCovOobOffset), soff(kCovOobOffset) {
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int ant = ga + 32 * j;
@@ -1047,17 +1063,15 @@ struct CovNoiseBeamSource {
 #pragma unroll
     for (int j = 0; j < 2; ++j) philox4x32_round(pc[j], key0 + (uint32_t)R * 0x9E3779B9u, key1 + (uint32_t)R * 0xBB67AE85u);
   }
-  template <int I>
+  template <int I>                                   // box_muller32_hw_f32 with the element's mask on the radius: a masked element is (+-0, +-0), which changes no sum
   __device__ __forceinline__ void bm() {
     constexpr int j = I / 2, h = I % 2;
-    box_muller32_hw_f32(pc[j][2 * h], pc[j][2 * h + 1], wf[j][h][0], wf[j][h][1]);
+    cov_noise_bm_masked(pc[j][2 * h], pc[j][2 * h + 1], v_half[h] && ant_ok[j], wf[j][h][0], wf[j][h][1]);
   }
-  template <int I>                                   // widen + mask + LDS store of unit noise element I = 2 j + h
+  template <int I>                                   // widen + LDS store of unit noise element I = 2 j + h (masked in bm)
   __device__ __forceinline__ void emit(c64* img) {
     constexpr int j = I / 2, h = I % 2;
-    const bool ok = v_half[h] && ant_ok[j];
-    const double re = (double)wf[j][h][0], im = (double)wf[j][h][1];
-    img[g_lds0 + 2 * j * kCovSlabBlk + 8 * h * kCovPitch] = mk(ok ? re : 0.0, ok ? im : 0.0);
+    img[g_lds0 + 2 * j * kCovSlabBlk + 8 * h * kCovPitch] = mk((double)wf[j][h][0], (double)wf[j][h][1]);
   }
   template <int I>                                   // generator piece I of the slab at cursor cg, into image dst
   __device__ __forceinline__ void gen(c64* dst) {
@@ -1103,13 +1117,17 @@ struct CovNoiseBeamSource {
   }
   template <int J>
   __device__ __forceinline__ void load() {           // antenna slot J of step i
-    const int a = bs_antenna(i, J), ac = a < A ? a : A - 1;            // (wave-uniform) a padding slot loads beyond the descriptor: a true zero, whatever the waveform holds
-    v[J] = buffer_load_c64(buffer_of(tx + (long long)ac * T, (unsigned)(T * (long long)sizeof(c64))), a < A ? voff : kCovOobOffset);
+    // (wave-uniform) antenna bs_antenna(i, J) = slot J of the rem left: a padding slot loads beyond the descriptor -- a true zero, whatever the waveform holds.  voff stays
+    // inside the antenna's column, so voff + s_ant is inside the descriptor; the antennas of a step ascend, the scalar offset moves on by a column per load.
+    v[J] = __builtin_bit_cast(c64, __builtin_amdgcn_raw_buffer_load_b128(rs_tx, (int)(J < rem ? voff : kCovOobOffset), (int)s_ant, 0));
+    s_ant += T16;
     if constexpr (J == kBeamStreamLoads - 1) {
       const bool last = i == spu - 1;
       ip = i;
       fin = last;
       i = last ? 0 : i + 1;
+      s_ant = last ? 0u : s_ant;
+      rem = last ? A : rem - kBeamStreamLoads;
       n = (last && n < kBeamStreamTab - 1) ? n + 1 : n;
     }
   }
@@ -1203,6 +1221,115 @@ __global__ __launch_bounds__(256, 2) void cov_noise_beam_kernel(NoiseBeamArgs a,
       for (int q = 0; q < QT; ++q) a.beam[(long long)q * a.T + u] = acc[q];
     }
   }
+}
+
+// ---------------------------------------------------------------- the half slabs of the noise term, packed two to a slab (noise_walk.hpp)
+// Where K is no multiple of 1024 the last block pair of every symbol column has rows whose partner k + 512 lies beyond K: slabs whose sample slots 8..15 are all masked, a
+// full step each in the regenerating route's walk (26 of 218 per column at K = 3276).  cov_noise_beam_kernel walks the full slabs alone; cov_noise_tail_kernel forms the half
+// slabs two to a slab -- sample slots 0..7 the first halves of one Philox slot group, 8..15 those of another: four calls per thread and step, outputs 0-1 of each -- so the
+// same field elements enter M in half the steps; only their order in the sum changes.  It carries no beam-sum, appends its partials behind the main kernel's and runs off the
+// CPI's serial chain (isac_cov_noise_beam_on).
+struct NoiseTailArgs {
+  unsigned long long seed;
+  int K, L_out, A;
+  NoiseWalk w;
+};
+
+// The slab source of cov_noise_tail_kernel: thread -> (row gp of both half slabs, antennas ga and ga + 32).  18 pieces per step (counter set-up + 10 Philox rounds of the four
+// calls, 4 Box-Muller transforms, 4 x (widen + LDS store)), spread over the 30 MFMA gaps.  Counter, masks and transform as in CovNoiseBeamSource.
+struct CovNoiseTailSource {
+  static constexpr int NB = 4;
+  static constexpr int kGaps = 30;
+  static constexpr int kPieces = 18;
+  struct Cur { int l, u; long long g; };             // packed slab g = packed slab u of symbol column l
+  int gp, ga, K, g_lds0;
+  NoiseWalk w;
+  uint32_t key0, key1;
+  long long s_end;
+  bool ant_ok[2];
+  uint64_t colbase[2];
+  Cur cg;
+  uint32_t pc[2][2][4];                              // [antenna set j][half h]
+  float wf[2][2][2];
+  bool v_half[2];
+  __device__ __forceinline__ CovNoiseTailSource(const NoiseTailArgs& a, long long s_begin, long long s_end_)
+      : gp(threadIdx.x & 7), ga(threadIdx.x >> 3), K(a.K), w(a.w), key0((uint32_t)a.seed), key1((uint32_t)(a.seed >> 32)), s_end(s_end_) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int ant = ga + 32 * j;
+      ant_ok[j] = ant < a.A;
+      colbase[j] = (uint64_t)gp + (uint64_t)kSpectralSlotsPerColumn * ((uint64_t)a.L_out * (uint64_t)ant);
+    }
+    g_lds0 = (ga >> 4) * kCovSlabBlk + gp * kCovPitch + ((ga & 15) ^ kCovSwizzle(gp));
+    Cur c; c.g = s_begin; c.l = (int)((unsigned)s_begin / (unsigned)w.n_packed); c.u = (int)((unsigned)s_begin - (unsigned)c.l * (unsigned)w.n_packed);   // (n_packed >= 1: the launcher)
+    cg = c;
+  }
+  __device__ __forceinline__ void advance(Cur& c) const { ++c.g; if (++c.u == w.n_packed) { c.u = 0; ++c.l; } }
+  __device__ __forceinline__ void init(const Cur& c) {
+    const bool in = c.g < s_end;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      v_half[h] = in && nw_tail_has(w, c.u, h) && nw_tail_row(w, c.u, h, gp) < K;
+      const uint64_t slab = (uint64_t)(uint32_t)nw_tail_slot(w, c.u, h, 0) + (uint64_t)kSpectralSlotsPerColumn * (uint64_t)c.l;   // (+ gp: in colbase)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const uint64_t ctr = slab + colbase[j];
+        pc[j][h][0] = (uint32_t)ctr; pc[j][h][1] = (uint32_t)(ctr >> 32); pc[j][h][2] = kSpectralStream; pc[j][h][3] = 0u;
+      }
+    }
+  }
+  template <int R>
+  __device__ __forceinline__ void round() {
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int h = 0; h < 2; ++h) philox4x32_round(pc[j][h], key0 + (uint32_t)R * 0x9E3779B9u, key1 + (uint32_t)R * 0xBB67AE85u);
+  }
+  template <int I>                                   // element I = 2 j + h: outputs 0-1 of its call, masked on the radius
+  __device__ __forceinline__ void bm() {
+    constexpr int j = I / 2, h = I % 2;
+    cov_noise_bm_masked(pc[j][h][0], pc[j][h][1], v_half[h] && ant_ok[j], wf[j][h][0], wf[j][h][1]);
+  }
+  template <int I>
+  __device__ __forceinline__ void emit(c64* img) {
+    constexpr int j = I / 2, h = I % 2;
+    img[g_lds0 + 2 * j * kCovSlabBlk + 8 * h * kCovPitch] = mk((double)wf[j][h][0], (double)wf[j][h][1]);
+  }
+  template <int I>
+  __device__ __forceinline__ void gen(c64* dst) {
+    if constexpr (I == 0) { init(cg); round<0>(); }
+    else if constexpr (I < 10) round<I>();
+    else if constexpr (I < 14) bm<I - 10>();
+    else { emit<I - 14>(dst); if constexpr (I == 17) advance(cg); }
+  }
+  __device__ __forceinline__ void whole(c64* img) {
+    static_for<0, kPieces>([&](auto ic) { gen<decltype(ic)::value>(img); });
+  }
+  __device__ __forceinline__ void prologue(c64* __restrict__ lds) {
+    whole(lds);
+    whole(lds + NB * kCovSlabBlk);
+  }
+  __device__ __forceinline__ void begin_step(long long) {}
+  static __host__ __device__ constexpr int piece_gap(int p) { return (p * 30) / kPieces; }
+  template <int PAR, int K_>
+  __device__ __forceinline__ void gap(c64* dst, long long) {
+    static_for<0, kPieces>([&](auto ic) {
+      if constexpr (piece_gap(decltype(ic)::value) == K_) gen<decltype(ic)::value>(dst);
+    });
+  }
+};
+
+__global__ __launch_bounds__(256, 2) void cov_noise_tail_kernel(NoiseTailArgs a, long long n_slabs, long long slabs_per_wg, int part0,
+                                                                double* __restrict__ part /* [part0 + gridX][kTiles][2][256] */) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  c64* lds = reinterpret_cast<c64*>(smem_raw);      // [kCovLdsBufs][4 * kCovSlabBlk]
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int grp = wid >> 1, phase = wid & 1;
+  const long long s_begin = (long long)blockIdx.x * slabs_per_wg;
+  long long s_end = s_begin + slabs_per_wg;
+  if (s_end > n_slabs) s_end = n_slabs;
+  if (grp == 0) cov_staged_body<4, 0>(CovNoiseTailSource(a, s_begin, s_end), phase, s_begin, s_end, part0 + (int)blockIdx.x, part, lds);
+  else cov_staged_body<4, 1>(CovNoiseTailSource(a, s_begin, s_end), phase, s_begin, s_end, part0 + (int)blockIdx.x, part, lds);
 }
 
 // The cross term where the range kernel cannot carry it (two LoS targets: echo_range_sl_kernel<2, 1, false, 2> sits at exactly 128 registers, echo.hip): a pass of its own over
@@ -1540,19 +1667,34 @@ static long long lazy_slabs(int K, int L_whole, int* s_col_out) {
 bool isac_lazy_split_ok(long long T, int K, int L_whole) {
   int s_col = 0;
   const long long n_slabs = lazy_slabs(K, L_whole, &s_col);
-  return T > 0 && T * (long long)sizeof(c64) < (1ll << 31) && n_slabs > 0 && n_slabs < (1ll << 31) - 4;   // (32-bit sample offsets below kCovOobOffset)
+  // (32-bit sample offsets below kCovOobOffset; the beam-sum's descriptor spans the whole waveform of up to 64 antennas -- the route's widest array -- and must end below it too)
+  return T > 0 && T * 64 * (long long)sizeof(c64) < (1ll << 31) && n_slabs > 0 && n_slabs < (1ll << 31) - 4;
 }
 
 // Head of a CPI on the split route (ISAC_LAZY_COV_SPLIT, include/isac_lazy_cov.h): the noise term's workgroup partials into ctx->cov_noise, the beam-sums into ctx->beam.
 int isac_cov_noise_beam_on(isac_ctx* ctx, hipStream_t st, const LazySplitFront& f) {
   if (!isac_lazy_split_ok(f.T, f.K, f.L_whole) || f.A <= 48 || f.A > 64 || f.Q < 1 || f.Q > 2) return fail(ctx, ISAC_ERR_UNSUPPORTED, "split lazy covariance: shape outside the route (49..64 antennas, one or two LoS targets)");
-  int s_col = 0;
-  const long long n_slabs = lazy_slabs(f.K, f.L_whole, &s_col);
-  long long gx, per;
-  cov_staged_grid(n_slabs, gx, per);
+  // The main kernel walks the full slabs (noise_walk.hpp), the tail kernel the half slabs, packed; a shape without full slabs (K <= 512) still launches the main kernel,
+  // for the beam-sum: its workgroups walk no slab, sum their units in the loop behind the slabs and leave zero partials.
+  const NoiseWalk w = noise_walk(f.K);
+  const long long n_slabs = (long long)f.L_whole * w.s_full, n_tail = (long long)f.L_whole * w.n_packed;
+  long long gx, per, gt = 0, per_t = 0;
+  if (n_slabs > 0) cov_staged_grid(n_slabs, gx, per);
+  else { gx = std::max<long long>(1, std::min<long long>(bw_units(f.bw), 512)); per = 2; }
+  if (n_tail > 0) noise_tail_grid(n_tail, gt, per_t);
   const int S = 32, n_tiles = CovPlan<4>::kTiles;
-  ISAC_TRY(ensure(ctx, ctx->cov_noise, sizeof(double) * ((size_t)gx + S) * n_tiles * 2 * 256));
-  NoiseBeamArgs a{f.d_tx, f.steer_host ? nullptr : (const c64*)ctx->steer.p, (c64*)ctx->steer.p, (c64*)ctx->beam.p, f.T, f.seed, f.K, f.L_out, f.A, s_col, f.bw};
+  ISAC_TRY(ensure(ctx, ctx->cov_noise, sizeof(double) * ((size_t)(gx + gt) + S) * n_tiles * 2 * 256));
+  // The tail kernel depends on the seed and the shape alone: it goes to the second stream, behind everything the main stream holds so far (the last reader of cov_noise among
+  // it) and beside everything from here on; covariance_lazy_split waits for it in front of the reduction.  ISAC_SINGLE_STREAM (fft2d.hip): in line, behind the main kernel.
+  static const bool single_stream = std::getenv("ISAC_SINGLE_STREAM") != nullptr;
+  hipStream_t st_tail = (single_stream || !ctx->stream2) ? st : ctx->stream2;
+  if (gt > 0 && st_tail != st) {
+    for (auto& e : ctx->ev_tail)
+      if (!e) ISAC_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    ISAC_HIP(hipEventRecord(ctx->ev_tail[0], st));
+    ISAC_HIP(hipStreamWaitEvent(st_tail, ctx->ev_tail[0], 0));
+  }
+  NoiseBeamArgs a{f.d_tx, f.steer_host ? nullptr : (const c64*)ctx->steer.p, (c64*)ctx->steer.p, (c64*)ctx->beam.p, f.T, f.seed, f.K, f.L_out, f.A, std::max(w.s_full, 1), f.bw};
   SteerArg sa{};
   if (f.steer_host) std::memcpy(sa.v, f.steer_host, sizeof(c64) * (size_t)f.A * f.Q);
   auto launch = [&](auto qc) -> int {
@@ -1566,7 +1708,19 @@ int isac_cov_noise_beam_on(isac_ctx* ctx, hipStream_t st, const LazySplitFront& 
     return ISAC_OK;
   };
   ISAC_TRY(f.Q == 1 ? launch(std::integral_constant<int, 1>{}) : launch(std::integral_constant<int, 2>{}));
-  ctx->split_wg = (int)gx;
+  ctx->split_tail_joined = true;
+  if (gt > 0) {
+    const NoiseTailArgs ta{f.seed, f.K, f.L_out, f.A, w};
+    const size_t lds = sizeof(c64) * kCovLdsBufs * 4 * kCovSlabBlk;
+    ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(cov_noise_tail_kernel), lds));
+    hipLaunchKernelGGL(cov_noise_tail_kernel, dim3((unsigned)gt), dim3(256), lds, st_tail, ta, n_tail, per_t, (int)gx, (double*)ctx->cov_noise.p);
+    ISAC_HIP(hipGetLastError());
+    if (st_tail != st) {
+      ISAC_HIP(hipEventRecord(ctx->ev_tail[1], st_tail));
+      ctx->split_tail_joined = false;
+    }
+  }
+  ctx->split_wg = (int)(gx + gt);
   return ISAC_OK;
 }
 
@@ -1580,6 +1734,10 @@ static int covariance_lazy_split(isac_ctx* ctx, hipStream_t st, c64* Ra) {
   c64* xc = (c64*)ctx->cov_xc.p;
   c64* H = xc + lazy_xc_elems(lz.L_whole, lz.A, lz.Q);
   c64* Mn = H + (size_t)lz.L_whole * lz.Q * lz.Q;
+  if (!ctx->split_tail_joined) {                     // cov_noise_tail_kernel's partials (isac_cov_noise_beam_on)
+    ISAC_HIP(hipStreamWaitEvent(st, ctx->ev_tail[1], 0));
+    ctx->split_tail_joined = true;
+  }
   hipLaunchKernelGGL(cov_reduce_slice_kernel, dim3(n_tiles, S), dim3(256), 0, st, (const double*)part, n_part, n_tiles, S, part2);
   ISAC_HIP(hipGetLastError());
   hipLaunchKernelGGL(cov_reduce_kernel, dim3(n_tiles), dim3(256, 4), 0, st, (const double*)part2, S, n_tiles, lz.A, inv_n, Mn);

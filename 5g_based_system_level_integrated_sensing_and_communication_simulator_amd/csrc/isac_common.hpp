@@ -215,7 +215,9 @@ struct isac_ctx {
   bool profile_cov = false;                    // isac_profile_enable(ctx, 2): the event pair brackets the wide covariance launch of fft2D instead of the fused echo kernel
   int lazy_cov_route = 0;          // isac_ctx_set_lazy_cov_route: 0 = split covariance of a native lazy echo grid (noise term beside the beam-sum, default), 1 = the regenerating cov_lazy_kernel
   int lazy_cov_used = -1;          // route the last covariance of a native lazy grid took (isac_ctx_get_lazy_cov_route_used); -1: none yet
-  int split_wg = 0;                // workgroup partials the last cov_noise_beam_kernel launch left in cov_noise
+  int split_wg = 0;                // workgroup partials the last cov_noise_beam_kernel launch and its cov_noise_tail_kernel left in cov_noise
+  hipEvent_t ev_tail[2] = {nullptr, nullptr};   // cov_noise_tail_kernel on the second stream: fork behind the main stream, completion (made on first use)
+  bool split_tail_joined = true;   // false: the covariance's reduction has yet to wait for ev_tail[1]
   int music_route = 0;             // ISAC_OPT_MUSIC_ROUTE: 0 = signal-subspace eigensolver for MUSIC (default), 1 = always the full eigendecomposition
   long long eig_epoch = 0;         // launches of eigh_tridiag_dist_kernel on this context (its exchange stamps carry the epoch: no reset between launches)
   bool tail_unjoined = false;      // wide order: ev_done of the last submit has not been waited for by the main stream (ISAC_ENTER joins lazily)
