@@ -232,11 +232,15 @@ __global__ __launch_bounds__(256, 2) void demod_kernel(OfdmGeom g, long long T, 
                                                        uint64_t seed,
                                                        // SYNTH = false: read them
                                                        const c64* __restrict__ wave,
-                                                       c64* __restrict__ grid, const c64* __restrict__ logtab_g) {
+                                                       c64* __restrict__ grid, const c64* __restrict__ logtab_g,
+                                                       // SYNTH = false, optional: zero_flag[column] = 1 where every value stored for the column is +-0, else 0
+                                                       // (NaN counts as non-zero) -- the D half of echo_range_xc_kernel's dead-column test
+                                                       int* __restrict__ zero_flag) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   c64* lds = reinterpret_cast<c64*>(smem_raw);
   const int tid = threadIdx.x;
   FFT fft;
+  bool stored_nz = false;
   constexpr bool kTables = SYNTH && QT > 0 && std::is_same<FFT, Fft4096>::value;   // LDS tables for the Philox Box-Muller
   const int Q = QT ? QT : Q_rt;
   {
@@ -290,9 +294,16 @@ __global__ __launch_bounds__(256, 2) void demod_kernel(OfdmGeom g, long long T, 
             const c64 o = v * ph;
             __builtin_nontemporal_store(o.re, &dst[row].re);
             __builtin_nontemporal_store(o.im, &dst[row].im);
+            if constexpr (!SYNTH) stored_nz |= (o.re != 0.0) | (o.im != 0.0);
           }
         },
         tid);
+    if constexpr (!SYNTH) {
+      if (zero_flag) {                                                   // (uniform)
+        const int any = __syncthreads_or(stored_nz);
+        if (tid == 0) zero_flag[col] = any ? 0 : 1;
+      }
+    }
   }
 }
 
@@ -432,10 +443,42 @@ __global__ __launch_bounds__(Fft4096W::NT, kEchoRangeWavesPerSimd) void echo_ran
                                                             c64* grid,
                                                             const c64* txg, const double* win_k,
                                                             const double* __restrict__ win_r, double inv_n, double sqrt_n,
-                                                            int row_lo, int n_rows, c64* __restrict__ ymid, c64* __restrict__ xc) {
+                                                            int row_lo, int n_rows, c64* __restrict__ ymid, c64* __restrict__ xc,
+                                                            const int* __restrict__ d_zero) {
   static_assert(QT == 1, "one LoS target (see above)");
   constexpr int NZ = 1, GROUP = 4;
   constexpr bool STORE = false, XC = true;
+  // A DEAD column is decided before anything is drawn for it:  tx[k, l, r] == 0 and D[k, l] == 0 (both parts, floating-point compares: +-0 is zero, NaN and Inf are not)
+  // for every k < K, and sig finite.  Its matched-filter samples are all signed zeros, so the text below would write +0.0 to its range rows, and its cross term is a sum of
+  // signed zeros, which cov_assemble_kernel adds to a sum it starts at +0.0 (cov.hip): +0.0 serves.  A silent 'S' slot (isac_synth_qpsk_grid_dev zero_s_slots, gNBPhy.m:609-612)
+  // is such a column for every antenna wherever the echo delays stay inside the cyclic prefix: a quarter of the bench's columns, each of which cost four Philox calls,
+  // eight Box-Muller transforms and the synthesis for nothing.
+  //   * The D half is ONE FLAG PER SYMBOL, d_zero[l], written by the demod_kernel launch that forms D (it has every value of the column in registers), not peek loads here:
+  //     a live symbol -- three quarters of the columns -- then pays one scalar load and a uniform branch, no vector load, no barrier and no exposed latency.
+  //   * Only where D[., l] is zero are the column's tx samples peeked (eight loads per thread in flight together, one workgroup-wide OR).  A column with tx != 0 there, or
+  //     with tx == 0 but D != 0, takes the text below unchanged.
+  {
+    int l, r;
+    if (!spectral_tile_map(blockIdx.x, L_whole, A, l, r)) return;       // padding workgroup of the tile grid (before any barrier)
+    if (d_zero[l] != 0 && isfinite(sig)) {                              // (uniform)
+      const int tid = threadIdx.x;
+      const long long colg = (long long)l + (long long)L_out * r;
+      const c64* ptx = txg + (long long)K * colg;
+      bool nz = false;
+#pragma unroll
+      for (int j = 0; j < Fft4096W::PER; ++j) {
+        const int k = tid + Fft4096W::NT * j;
+        const c64 v = ptx[k < K ? k : K - 1];
+        nz |= (v.re != 0.0) | (v.im != 0.0);
+      }
+      if (!__syncthreads_or(nz)) {
+        c64* yd = ymid + (long long)n_rows * colg;
+        for (int rr = tid; rr < n_rows; rr += Fft4096W::NT) yd[rr] = mk(0.0, 0.0);
+        if (tid < QT) xc[((long long)l * A + r) * QT + tid] = mk(0.0, 0.0);
+        return;
+      }
+    }
+  }
 #include "echo_range_sl_body.inc"
 }
 
@@ -731,7 +774,7 @@ static int padded_symbols(int L_whole, int tx_dim_l, int32_t* l_out) {
 
 template <class FFT, bool SYNTH, int QT = 0>
 static int launch_demod(isac_ctx* ctx, const OfdmGeom& g, long long T, int A, int L_whole, int L_out, const c64* tw, int Q,
-                        int noise_mode, const c64* noise, double n0s, uint64_t seed, const c64* wave, c64* grid) {
+                        int noise_mode, const c64* noise, double n0s, uint64_t seed, const c64* wave, c64* grid, int* zero_flag = nullptr) {
   size_t lds = sizeof(c64) * (FFT::LDS_ELEMS + kLogTabSize);
   const c64* logtab = nullptr;
   ISAC_TRY(isac_get_logtab(ctx, &logtab));
@@ -739,24 +782,27 @@ static int launch_demod(isac_ctx* ctx, const OfdmGeom& g, long long T, int A, in
   ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(kern), lds));
   hipLaunchKernelGGL(kern, dim3((unsigned)(L_whole * A)) /* one column per workgroup (two 72 KB workgroups per CU) */, dim3(256), lds, ctx->stream, g, T, A, L_whole, L_out, tw, Q,
                      (const c64*)ctx->coef.p, SYNTH ? (const c64*)ctx->steer.p + (size_t)A * Q : nullptr,
-                     (const c64*)ctx->phase_rx.p, noise_mode, noise, n0s, seed, wave, grid, logtab);
+                     (const c64*)ctx->phase_rx.p, noise_mode, noise, n0s, seed, wave, grid, logtab, zero_flag);
   ISAC_HIP(hipGetLastError());
   return ISAC_OK;
 }
 
 // ---- spectral noise modes: per-target demodulated coefficient grids D [K x L_whole x Q] (the coefficient vectors
 // coef [Q x T] are, byte for byte, a [T x Q] waveform), then one synthesis kernel.
+static int* dgrid_zero_flags(isac_ctx* ctx, int K, int L_whole, int Q) { return reinterpret_cast<int*>((c64*)ctx->dgrid.p + (size_t)K * L_whole * Q); }
+
 static int spectral_prepare(isac_ctx* ctx, const c64* d_tx, long long T, const isac_radar_channel_params* rp, const uint8_t* los,
                             const OfdmGeom& g, int* q_out, int* l_whole_out, bool coef_only = false, const SplitReq* split = nullptr) {
   int Q = 0;
   ISAC_TRY(prepare_echo(ctx, d_tx, T, rp, los, &Q, coef_only ? &g : nullptr, split));       // monoStaticSensing.m:13
   const int L_whole = whole_symbols(g, T);
   if (L_whole <= 0) return fail(ctx, ISAC_ERR_SHORT_WAVEFORM, "waveform shorter than one OFDM symbol");
-  ISAC_TRY(ensure(ctx, ctx->dgrid, sizeof(c64) * (size_t)g.n_sc * L_whole * Q));
+  // D, and behind it one zero flag per column of D (demod_kernel's zero_flag: the D half of echo_range_xc_kernel's dead-column test)
+  ISAC_TRY(ensure(ctx, ctx->dgrid, sizeof(c64) * (size_t)g.n_sc * L_whole * Q + sizeof(int) * (size_t)L_whole * Q));
   const c64* tw = nullptr;
   ISAC_TRY(isac_get_twiddles(ctx, g.nfft, &tw));
   ISAC_FFT_DISPATCH(g.nfft, ISAC_TRY((launch_demod<FFT, false>(ctx, g, T, Q, L_whole, L_whole, tw, 0, 0, nullptr, 0.0, 0,
-                                                               (const c64*)ctx->coef.p, (c64*)ctx->dgrid.p))));
+                                                               (const c64*)ctx->coef.p, (c64*)ctx->dgrid.p, dgrid_zero_flags(ctx, g.n_sc, L_whole, Q)))));
   *q_out = Q;
   *l_whole_out = L_whole;
   return ISAC_OK;
@@ -924,7 +970,7 @@ extern "C" int isac_mono_static_sensing_fused_dev(isac_ctx* ctx, const isac_c64*
         if (split)                          // ... and with the cross term of the split covariance (the one extra argument; two targets: cov_cross_kernel forms it in fft2D)
           return launch_echo_range(ctx, echo_range_xc_kernel<QT>, L_whole, A, sizeof(c64) * kEchoXcLds, g.n_sc, L_whole, L_out, A, (const c64*)ctx->dgrid.p, (const c64*)ctx->steer.p + (size_t)A * Q, sig, seed,
                                  (const c64*)d_noise_unit, tw, (c64*)d_echo_grid, (const c64*)d_tx_grid, wk, wr, 1.0 / ep->n_ifft, std::sqrt((double)ep->n_ifft), row_lo, nr,
-                                 (c64*)ctx->ymid.p, (c64*)ctx->cov_xc.p);
+                                 (c64*)ctx->ymid.p, (c64*)ctx->cov_xc.p, (const int*)dgrid_zero_flags(ctx, g.n_sc, L_whole, Q));
       return launch(lazy_native ? echo_range_sl_kernel<QT, 1, false> : philox ? echo_range_sl_kernel<QT, 1> : echo_range_sl_kernel<QT, 2>);
     } else
       return launch(philox ? echo_range_kernel<QT, 1> : echo_range_kernel<QT, 2>, Q);
