@@ -275,6 +275,13 @@ PROTOTYPES_DIRECTIONS = {
 PROTOTYPES_BEAM_CLEAN = {
     "isac_fft2d_beam_clean_targets": (_INT, (_P, _P, _I32, _P, _ptr(CfarMethod), _I32, _I32, _F64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P)),
 }
+# ... and include/isac_multistatic.h (tests/test_multistatic_cpu.py pins it)
+ISAC_MULTISTATIC_MAX_PATHS, ISAC_MULTISTATIC_MAX_SOURCES, ISAC_MULTISTATIC_MAX_ANTS = 64, 32, 256
+_MULTISTATIC_ARGS = (_P, _P, _P, _I32, _I64, _F64, _F64, _F64, _I32, _I32, _P, _P, _P, _P, _P, _P, _I32, _P, _U64)   # ctx .. seed: what the two calls share
+PROTOTYPES_MULTISTATIC = {
+    "isac_multi_static_channel_dev": (_INT, _MULTISTATIC_ARGS + (_P,)),
+    "isac_multi_static_sensing_dev": (_INT, _MULTISTATIC_ARGS + (_I32, _ptr(Carrier), _P, _P)),
+}
 
 
 def library_path() -> str:
@@ -301,7 +308,7 @@ def load():
             except Exception:
                 pass
         lib = C.CDLL(_LIB_PATH, mode=C.RTLD_GLOBAL)
-        for name, (restype, argtypes) in {**PROTOTYPES, **PROTOTYPES_ADDED, **PROTOTYPES_CFAR, **PROTOTYPES_CFAR_MC, **PROTOTYPES_LAZY_COV, **PROTOTYPES_TARGETS_UPA, **PROTOTYPES_BEAMS, **PROTOTYPES_REFINE, **PROTOTYPES_CLEAN, **PROTOTYPES_RELAX, **PROTOTYPES_DIRECTIONS, **PROTOTYPES_BEAM_CLEAN}.items():
+        for name, (restype, argtypes) in {**PROTOTYPES, **PROTOTYPES_ADDED, **PROTOTYPES_CFAR, **PROTOTYPES_CFAR_MC, **PROTOTYPES_LAZY_COV, **PROTOTYPES_TARGETS_UPA, **PROTOTYPES_BEAMS, **PROTOTYPES_REFINE, **PROTOTYPES_CLEAN, **PROTOTYPES_RELAX, **PROTOTYPES_DIRECTIONS, **PROTOTYPES_BEAM_CLEAN, **PROTOTYPES_MULTISTATIC}.items():
             fn = getattr(lib, name)  # AttributeError here = ABI drift between isac.h and the .so
             fn.restype, fn.argtypes = restype, argtypes
         # the library writes whole structs into caller memory: version AND struct sizes must match this binding's mirrors

@@ -30,28 +30,7 @@ namespace isac {
 // HBM-bound: T x A x 16 B read once (1.007 GB at the bench shape), nothing else.  Each workgroup walks blocks of 256 consecutive samples
 // (grid-stride: 1024 long-lived workgroups, four per CU) with its antenna loop unrolled UNROLL deep: 170.6 us = 5.90 TB/s, against 178 us of the
 // 8-deep one-block-per-workgroup form of rounds 1-3 (profiles/r04_beamsum_sweep.txt; a plain streaming read tops out at 6.0-6.2 TB/s, tools/gbench.hip).
-// One sample's sums over the antennas, for both kernels below: acc[q] = sum_a p[a T] s_steer[q A + a].
-template <int QT, int UNROLL>
-__device__ __forceinline__ void beam_sample(const c64* __restrict__ p /* tx + t */, long long T, int A, const c64* __restrict__ s_steer /* LDS [QT x A] */, c64 (&acc)[QT]) {
-#pragma unroll
-  for (int q = 0; q < QT; ++q) acc[q] = mk(0.0, 0.0);
-  int a = 0;
-  for (; a + UNROLL <= A; a += UNROLL) {
-    c64 v[UNROLL];
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) v[u] = p[(long long)(a + u) * T];
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u)
-#pragma unroll
-      for (int q = 0; q < QT; ++q) acc[q] = fma(v[u], s_steer[q * A + a + u], acc[q]);
-  }
-  for (; a < A; ++a) {
-    c64 v = p[(long long)a * T];
-#pragma unroll
-    for (int q = 0; q < QT; ++q) acc[q] = fma(v, s_steer[q * A + a], acc[q]);
-  }
-}
-
+// One sample's sums over the antennas: beam_sample (echo_dev.hpp).
 template <int QT, int UNROLL>
 __global__ __launch_bounds__(256) void beamsum_kernel(const c64* __restrict__ tx, long long T, int A,
                                                       const c64* __restrict__ steer /* [A x QT] compacted LoS */,
@@ -72,35 +51,10 @@ __global__ __launch_bounds__(256) void beamsum_kernel(const c64* __restrict__ tx
   }
 }
 
-// ---------------------------------------------------------------- per-target coefficient vectors
-struct TargetDesc {
-  double wd;      // (2*pi)*fd          basicRadarChannel.m:25,44
-  double lsf;     // largeScaleFading   basicRadarChannel.m:48
-  long long shift;  // ceil(pathDelay/Ts) basicRadarChannel.m:22
-};
-constexpr int kMaxTargets = 64;
+// ---------------------------------------------------------------- per-target coefficient vectors (TargetDesc, rx_phase, coef_value: echo_dev.hpp)
 struct TargetTable {
   TargetDesc t[kMaxTargets];
 };
-
-// exp(-2j*pi*fc*t) at receive time tt = t Ts   basicRadarChannel.m:73
-__device__ __forceinline__ c64 rx_phase(double w /* (2*pi)*fc */, double tt) {
-  double s, c;
-  sincos(w * tt, &s, &c);
-  return mk(c, -s);
-}
-
-// coef_q[t] for t >= d = td.shift from the beam-sum sample b = beam_q[t - d]: THE expression of the coefficient vectors, shared by coef_kernel and beamsum_coef_kernel --
-// same operations in the same order, so the same bits.  tt = (double)t * Ts, prx = rx_phase(w, tt).
-__device__ __forceinline__ c64 coef_value(c64 b, long long t, const TargetDesc& td, double w, double Ts, double tt, c64 prx) {
-  double sd, cd, st, ct;
-  sincos(td.wd * tt, &sd, &cd);                                // doppler phase at receive time  :43-44
-  sincos(w * ((double)(t - td.shift) * Ts), &st, &ct);         // up-conversion phase at transmit time :29-31,42
-  c64 v = b * mk(ct, st);
-  v = v * mk(cd, sd);
-  v = v * td.lsf;
-  return v * prx;
-}
 
 __global__ __launch_bounds__(256) void coef_kernel(const c64* __restrict__ beam, long long T, int Q,
                                                    TargetTable tab, double w /* (2*pi)*fc */, double Ts,
@@ -738,6 +692,16 @@ static int prepare_echo(isac_ctx* ctx, const c64* d_tx, long long T, const isac_
   return ISAC_OK;
 }
 
+// rxWaveform [T x A] from what prepare_echo / isac_path_coefs_on left in the context (coef [Q x T], phase_rx [T], steer): the tail of both time-domain channel calls
+static int waveform_from_coefs(isac_ctx* ctx, long long T, int A, int Q, double n0, int noise_mode, const c64* d_noise_unit, uint64_t seed, c64* d_rx_wave) {
+  const double n0s = std::sqrt(n0 / 2.0);           // basicRadarChannel.m:67
+  hipLaunchKernelGGL(radar_waveform_kernel, dim3(cdiv(T, 256), A), dim3(256), 0, ctx->stream, T, A, Q,
+                     (const c64*)ctx->coef.p, (const c64*)ctx->steer.p + (size_t)A * Q, (const c64*)ctx->phase_rx.p,
+                     noise_mode, d_noise_unit, n0s, seed, d_rx_wave);
+  ISAC_HIP(hipGetLastError());
+  return ISAC_OK;
+}
+
 extern "C" int isac_basic_radar_channel_dev(isac_ctx* ctx, const isac_c64* d_tx_wave, int64_t T,
                                             const isac_radar_channel_params* rp, const uint8_t* los, int noise_mode,
                                             const isac_c64* d_noise_unit, uint64_t seed, isac_c64* d_rx_wave) {
@@ -748,13 +712,7 @@ extern "C" int isac_basic_radar_channel_dev(isac_ctx* ctx, const isac_c64* d_tx_
     return fail(ctx, ISAC_ERR_INVALID_ARG, "basicRadarChannel returns a time-domain waveform: noise modes NONE / INJECTED / PHILOX only");
   int Q = 0;
   ISAC_TRY(prepare_echo(ctx, (const c64*)d_tx_wave, T, rp, los, &Q));
-  const int A = rp->n_ants;
-  const double n0s = std::sqrt(rp->n0 / 2.0);       // basicRadarChannel.m:67
-  hipLaunchKernelGGL(radar_waveform_kernel, dim3(cdiv(T, 256), A), dim3(256), 0, ctx->stream, (long long)T, A, Q,
-                     (const c64*)ctx->coef.p, (const c64*)ctx->steer.p + (size_t)A * Q, (const c64*)ctx->phase_rx.p,
-                     noise_mode, (const c64*)d_noise_unit, n0s, seed, (c64*)d_rx_wave);
-  ISAC_HIP(hipGetLastError());
-  return ISAC_OK;
+  return waveform_from_coefs(ctx, T, rp->n_ants, Q, rp->n0, noise_mode, (const c64*)d_noise_unit, seed, (c64*)d_rx_wave);
 }
 
 // f(std::integral_constant<int, Q>) for a LoS target count the kernels have as a compile-time constant (1..MAXQ), f(<0>) -- the run-time count -- for any other
@@ -791,18 +749,24 @@ static int launch_demod(isac_ctx* ctx, const OfdmGeom& g, long long T, int A, in
 // coef [Q x T] are, byte for byte, a [T x Q] waveform), then one synthesis kernel.
 static int* dgrid_zero_flags(isac_ctx* ctx, int K, int L_whole, int Q) { return reinterpret_cast<int*>((c64*)ctx->dgrid.p + (size_t)K * L_whole * Q); }
 
-static int spectral_prepare(isac_ctx* ctx, const c64* d_tx, long long T, const isac_radar_channel_params* rp, const uint8_t* los,
-                            const OfdmGeom& g, int* q_out, int* l_whole_out, bool coef_only = false, const SplitReq* split = nullptr) {
-  int Q = 0;
-  ISAC_TRY(prepare_echo(ctx, d_tx, T, rp, los, &Q, coef_only ? &g : nullptr, split));       // monoStaticSensing.m:13
-  const int L_whole = whole_symbols(g, T);
-  if (L_whole <= 0) return fail(ctx, ISAC_ERR_SHORT_WAVEFORM, "waveform shorter than one OFDM symbol");
+// D = OFDM-demodulate(coef as a [T x Q] waveform) -> ctx->dgrid
+static int demod_coefs(isac_ctx* ctx, const OfdmGeom& g, long long T, int Q, int L_whole) {
   // D, and behind it one zero flag per column of D (demod_kernel's zero_flag: the D half of echo_range_xc_kernel's dead-column test)
   ISAC_TRY(ensure(ctx, ctx->dgrid, sizeof(c64) * (size_t)g.n_sc * L_whole * Q + sizeof(int) * (size_t)L_whole * Q));
   const c64* tw = nullptr;
   ISAC_TRY(isac_get_twiddles(ctx, g.nfft, &tw));
   ISAC_FFT_DISPATCH(g.nfft, ISAC_TRY((launch_demod<FFT, false>(ctx, g, T, Q, L_whole, L_whole, tw, 0, 0, nullptr, 0.0, 0,
                                                                (const c64*)ctx->coef.p, (c64*)ctx->dgrid.p, dgrid_zero_flags(ctx, g.n_sc, L_whole, Q)))));
+  return ISAC_OK;
+}
+
+static int spectral_prepare(isac_ctx* ctx, const c64* d_tx, long long T, const isac_radar_channel_params* rp, const uint8_t* los,
+                            const OfdmGeom& g, int* q_out, int* l_whole_out, bool coef_only = false, const SplitReq* split = nullptr) {
+  int Q = 0;
+  ISAC_TRY(prepare_echo(ctx, d_tx, T, rp, los, &Q, coef_only ? &g : nullptr, split));       // monoStaticSensing.m:13
+  const int L_whole = whole_symbols(g, T);
+  if (L_whole <= 0) return fail(ctx, ISAC_ERR_SHORT_WAVEFORM, "waveform shorter than one OFDM symbol");
+  ISAC_TRY(demod_coefs(ctx, g, T, Q, L_whole));
   *q_out = Q;
   *l_whole_out = L_whole;
   return ISAC_OK;
@@ -832,16 +796,29 @@ static int launch_echo_range(isac_ctx* ctx, Kern kern, int L_whole, int A, size_
   return ISAC_OK;
 }
 
-static int mono_static_spectral(isac_ctx* ctx, const c64* d_tx, long long T, int tx_dim_l, const OfdmGeom& g,
-                                const isac_radar_channel_params* rp, const uint8_t* los, int noise_mode, const c64* d_noise,
-                                uint64_t seed, c64* d_grid, int32_t* l_out) {
-  int Q = 0, L_whole = 0;
-  ISAC_TRY(spectral_prepare(ctx, d_tx, T, rp, los, g, &Q, &L_whole));
-  const int A = rp->n_ants;
+// echoGrid [n_sc x L_out x A] from what prepare_echo / isac_path_coefs_on left in the context (coef [Q x T], phase_rx [T], steer): OFDM demodulation of the synthesised
+// samples (monoStaticSensing.m:16), or -- spectral noise modes -- of the Q coefficient vectors and the spectral synthesis; zero-padding up to tx_dim_l symbols (:19-21).
+// The tail of isac_mono_static_sensing_dev and isac_multi_static_sensing_dev.
+static int grid_from_coefs(isac_ctx* ctx, const OfdmGeom& g, long long T, int A, int Q, double n0, int tx_dim_l, int noise_mode, const c64* d_noise,
+                           uint64_t seed, c64* d_grid, int32_t* l_out) {
+  const int L_whole = whole_symbols(g, T);
+  if (L_whole <= 0) return fail(ctx, ISAC_ERR_SHORT_WAVEFORM, "waveform shorter than one OFDM symbol");
+  if (spectral_mode(noise_mode)) ISAC_TRY(demod_coefs(ctx, g, T, Q, L_whole));
   const int L_out = padded_symbols(L_whole, tx_dim_l, l_out);
   if (L_out > L_whole) ISAC_HIP(hipMemsetAsync(d_grid, 0, sizeof(c64) * (size_t)g.n_sc * L_out * A, ctx->stream));
-  const double sig = std::sqrt(rp->n0 / 2.0) * std::sqrt((double)g.nfft);            // basicRadarChannel.m:67 through the unscaled FFT
-  return echo_dispatch<4>(Q, [&](auto qc) { return launch_echo_spectral<decltype(qc)::value>(ctx, g, A, L_whole, L_out, Q, noise_mode, d_noise, sig, seed, d_grid); });
+  if (spectral_mode(noise_mode)) {
+    const double sig = std::sqrt(n0 / 2.0) * std::sqrt((double)g.nfft);              // basicRadarChannel.m:67 through the unscaled FFT
+    return echo_dispatch<4>(Q, [&](auto qc) { return launch_echo_spectral<decltype(qc)::value>(ctx, g, A, L_whole, L_out, Q, noise_mode, d_noise, sig, seed, d_grid); });
+  }
+  const c64* tw = nullptr;
+  ISAC_TRY(isac_get_twiddles(ctx, g.nfft, &tw));
+  const double n0s = std::sqrt(n0 / 2.0);
+  if (g.nfft == 4096)      // the target count as a compile-time constant where the kernel has one (1..4)
+    return echo_dispatch<4>(Q, [&](auto qc) {
+      return launch_demod<Fft4096, true, decltype(qc)::value>(ctx, g, T, A, L_whole, L_out, tw, Q, noise_mode, d_noise, n0s, seed, nullptr, d_grid);
+    });
+  ISAC_FFT_DISPATCH(g.nfft, ISAC_TRY((launch_demod<FFT, true>(ctx, g, T, A, L_whole, L_out, tw, Q, noise_mode, d_noise, n0s, seed, nullptr, d_grid))));
+  return ISAC_OK;
 }
 
 extern "C" int isac_mono_static_sensing_dev(isac_ctx* ctx, const isac_c64* d_tx_wave, int64_t T, int32_t tx_dim_l,
@@ -855,28 +832,67 @@ extern "C" int isac_mono_static_sensing_dev(isac_ctx* ctx, const isac_c64* d_tx_
   if ((noise_mode == ISAC_NOISE_INJECTED || noise_mode == ISAC_NOISE_INJECTED_SPECTRAL) && !d_noise_unit)
     return fail(ctx, ISAC_ERR_INVALID_ARG, "noise buffer missing");
   if (noise_mode < ISAC_NOISE_NONE || noise_mode > ISAC_NOISE_INJECTED_SPECTRAL) return fail(ctx, ISAC_ERR_INVALID_ARG, "unknown noise mode");
-  if (spectral_mode(noise_mode))
-    return mono_static_spectral(ctx, (const c64*)d_tx_wave, T, tx_dim_l, geom_of(carrier), rp, los, noise_mode, (const c64*)d_noise_unit,
-                                seed, (c64*)d_echo_grid, l_out);
   int Q = 0;
   ISAC_TRY(prepare_echo(ctx, (const c64*)d_tx_wave, T, rp, los, &Q));   // monoStaticSensing.m:13
-  OfdmGeom g = geom_of(carrier);
-  const int A = rp->n_ants;
-  const int L_whole = whole_symbols(g, T);
-  if (L_whole <= 0) return fail(ctx, ISAC_ERR_SHORT_WAVEFORM, "waveform shorter than one OFDM symbol");
-  const int L_out = padded_symbols(L_whole, tx_dim_l, l_out);
-  if (L_out > L_whole) ISAC_HIP(hipMemsetAsync(d_echo_grid, 0, sizeof(c64) * (size_t)g.n_sc * L_out * A, ctx->stream));
-  const c64* tw = nullptr;
-  ISAC_TRY(isac_get_twiddles(ctx, g.nfft, &tw));
-  const double n0s = std::sqrt(rp->n0 / 2.0);
-  if (g.nfft == 4096)      // the target count as a compile-time constant where the kernel has one (1..4)
-    return echo_dispatch<4>(Q, [&](auto qc) {
-      return launch_demod<Fft4096, true, decltype(qc)::value>(ctx, g, T, A, L_whole, L_out, tw, Q, noise_mode, (const c64*)d_noise_unit, n0s, seed, nullptr, (c64*)d_echo_grid);
-    });
-  ISAC_FFT_DISPATCH(g.nfft, ISAC_TRY((launch_demod<FFT, true>(ctx, g, T, A, L_whole, L_out, tw, Q, noise_mode,
-                                                              (const c64*)d_noise_unit, n0s, seed, nullptr,
-                                                              (c64*)d_echo_grid))));
+  return grid_from_coefs(ctx, geom_of(carrier), T, rp->n_ants, Q, rp->n0, tx_dim_l, noise_mode, (const c64*)d_noise_unit, seed, (c64*)d_echo_grid, l_out);
+}
+
+// ---------------------------------------------------------------- multi-static echo (include/isac_multistatic.h): paths from several source arrays.  The checks and the
+// two entry points; the coefficient vectors: multistatic.hip; everything behind them: the tails above.
+static int check_paths(isac_ctx* ctx, const PathCoefJob& j, int n_sources) {
+  if (!j.d_tx || !j.n_ants_src) return fail(ctx, ISAC_ERR_INVALID_ARG, "NULL argument");
+  if (j.T <= 0 || j.n_ants <= 0 || n_sources <= 0 || j.n_paths < 0) return fail(ctx, ISAC_ERR_INVALID_ARG, "bad T / n_ants / n_sources / n_paths");
+  if (!(j.fs > 0)) return fail(ctx, ISAC_ERR_INVALID_ARG, "fs must be positive");
+  if (j.n_paths == 0) return fail(ctx, ISAC_ERR_NO_LOS, "no path: rxWaveform is empty (basicRadarChannel.m:59,64)");
+  if (j.n_paths > ISAC_MULTISTATIC_MAX_PATHS) return fail(ctx, ISAC_ERR_CAPACITY, "more than 64 paths");
+  if (n_sources > ISAC_MULTISTATIC_MAX_SOURCES) return fail(ctx, ISAC_ERR_CAPACITY, "more than 32 sources");
+  if (j.n_ants > ISAC_MULTISTATIC_MAX_ANTS) return fail(ctx, ISAC_ERR_CAPACITY, "more than 256 receive elements");
+  if (!j.path_source || !j.path_shift || !j.path_doppler_hz || !j.path_gain || !j.path_tx_steering || !j.path_rx_steering) return fail(ctx, ISAC_ERR_INVALID_ARG, "NULL argument");
+  for (int p = 0; p < j.n_paths; ++p) {
+    const int s = j.path_source[p];
+    if (s < 0 || s >= n_sources) return fail(ctx, ISAC_ERR_INVALID_ARG, "path_source outside 0 .. n_sources - 1");
+    if (j.path_shift[p] < 0) return fail(ctx, ISAC_ERR_INVALID_ARG, "negative path_shift");
+    if (!j.d_tx[s] || j.n_ants_src[s] <= 0) return fail(ctx, ISAC_ERR_INVALID_ARG, "a path names a source without a waveform");
+    if (j.n_ants_src[s] > ISAC_MULTISTATIC_MAX_ANTS) return fail(ctx, ISAC_ERR_CAPACITY, "more than 256 elements on a source array");
+  }
   return ISAC_OK;
+}
+
+extern "C" int isac_multi_static_channel_dev(isac_ctx* ctx, const isac_c64* const* d_tx_waves, const int32_t* n_ants_src, int32_t n_sources, int64_t T, double fc, double fs,
+                                             double n0, int32_t n_ants, int32_t n_paths, const int32_t* path_source, const int64_t* path_shift, const double* path_doppler_hz,
+                                             const double* path_gain, const isac_c64* path_tx_steering, const isac_c64* path_rx_steering, int noise_mode,
+                                             const isac_c64* d_noise_unit, uint64_t seed, isac_c64* d_rx_wave) {
+  ISAC_ENTER(ctx);
+  if (!d_rx_wave) return fail(ctx, ISAC_ERR_INVALID_ARG, "rx_wave is NULL");
+  if (noise_mode == ISAC_NOISE_INJECTED && !d_noise_unit) return fail(ctx, ISAC_ERR_INVALID_ARG, "noise buffer missing");
+  if (noise_mode < ISAC_NOISE_NONE || noise_mode > ISAC_NOISE_PHILOX)
+    return fail(ctx, ISAC_ERR_INVALID_ARG, "a time-domain waveform: noise modes NONE / INJECTED / PHILOX only");
+  const PathCoefJob j{(const c64* const*)d_tx_waves, n_ants_src, T, fc, fs, n_ants, n_paths, path_source, path_shift, path_doppler_hz, path_gain, path_tx_steering, path_rx_steering};
+  ISAC_TRY(check_paths(ctx, j, n_sources));
+  ctx->range_cache.valid = false;
+  ctx->lazy.valid = false;                          // steer / coef below are the inputs of a lazy echo grid of an earlier call
+  ISAC_TRY(isac_path_coefs_on(ctx, ctx->stream, j));
+  return waveform_from_coefs(ctx, T, n_ants, n_paths, n0, noise_mode, (const c64*)d_noise_unit, seed, (c64*)d_rx_wave);
+}
+
+extern "C" int isac_multi_static_sensing_dev(isac_ctx* ctx, const isac_c64* const* d_tx_waves, const int32_t* n_ants_src, int32_t n_sources, int64_t T, double fc, double fs,
+                                             double n0, int32_t n_ants, int32_t n_paths, const int32_t* path_source, const int64_t* path_shift, const double* path_doppler_hz,
+                                             const double* path_gain, const isac_c64* path_tx_steering, const isac_c64* path_rx_steering, int noise_mode,
+                                             const isac_c64* d_noise_unit, uint64_t seed, int32_t tx_dim_l, const isac_carrier* carrier, isac_c64* d_echo_grid, int32_t* l_out) {
+  ISAC_ENTER(ctx);
+  ISAC_TRY(check_carrier(ctx, carrier));
+  if (!d_echo_grid) return fail(ctx, ISAC_ERR_INVALID_ARG, "echo_grid is NULL");
+  if ((noise_mode == ISAC_NOISE_INJECTED || noise_mode == ISAC_NOISE_INJECTED_SPECTRAL) && !d_noise_unit)
+    return fail(ctx, ISAC_ERR_INVALID_ARG, "noise buffer missing");
+  if (noise_mode < ISAC_NOISE_NONE || noise_mode > ISAC_NOISE_INJECTED_SPECTRAL) return fail(ctx, ISAC_ERR_INVALID_ARG, "unknown noise mode");
+  const PathCoefJob j{(const c64* const*)d_tx_waves, n_ants_src, T, fc, fs, n_ants, n_paths, path_source, path_shift, path_doppler_hz, path_gain, path_tx_steering, path_rx_steering};
+  ISAC_TRY(check_paths(ctx, j, n_sources));
+  const OfdmGeom g = geom_of(carrier);
+  if (whole_symbols(g, T) <= 0) return fail(ctx, ISAC_ERR_SHORT_WAVEFORM, "waveform shorter than one OFDM symbol");   // (before any launch: a refused call writes nothing)
+  ctx->range_cache.valid = false;
+  ctx->lazy.valid = false;
+  ISAC_TRY(isac_path_coefs_on(ctx, ctx->stream, j));
+  return grid_from_coefs(ctx, g, T, n_ants, n_paths, n0, tx_dim_l, noise_mode, (const c64*)d_noise_unit, seed, (c64*)d_echo_grid, l_out);
 }
 
 extern "C" int isac_mono_static_sensing_fused_dev(isac_ctx* ctx, const isac_c64* d_tx_wave, int64_t T, int32_t tx_dim_l,

@@ -306,6 +306,56 @@ struct SteerArg {
   c64 v[kSteerArgMax];
 };
 
+// ---------------------------------------------------------------- beam-sum and coefficient vectors (echo.hip: beamsum_kernel, coef_kernel, beamsum_coef_kernel, coef_window_kernel;
+// multistatic.hip: path_coef_kernel)
+// One sample's sums over the antennas: acc[q] = sum_a p[a T] s_steer[q A + a], antennas in ascending order, one complex fma each -- whatever QT and UNROLL, the same bits.
+template <int QT, int UNROLL>
+__device__ __forceinline__ void beam_sample(const c64* __restrict__ p /* tx + t */, long long T, int A, const c64* __restrict__ s_steer /* LDS [QT x A] */, c64 (&acc)[QT]) {
+#pragma unroll
+  for (int q = 0; q < QT; ++q) acc[q] = mk(0.0, 0.0);
+  int a = 0;
+  for (; a + UNROLL <= A; a += UNROLL) {
+    c64 v[UNROLL];
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) v[u] = p[(long long)(a + u) * T];
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u)
+#pragma unroll
+      for (int q = 0; q < QT; ++q) acc[q] = fma(v[u], s_steer[q * A + a + u], acc[q]);
+  }
+  for (; a < A; ++a) {
+    c64 v = p[(long long)a * T];
+#pragma unroll
+    for (int q = 0; q < QT; ++q) acc[q] = fma(v, s_steer[q * A + a], acc[q]);
+  }
+}
+
+struct TargetDesc {
+  double wd;      // (2*pi)*fd          basicRadarChannel.m:25,44
+  double lsf;     // largeScaleFading   basicRadarChannel.m:48
+  long long shift;  // ceil(pathDelay/Ts) basicRadarChannel.m:22
+};
+constexpr int kMaxTargets = 64;
+
+// exp(-2j*pi*fc*t) at receive time tt = t Ts   basicRadarChannel.m:73
+__device__ __forceinline__ c64 rx_phase(double w /* (2*pi)*fc */, double tt) {
+  double s, c;
+  sincos(w * tt, &s, &c);
+  return mk(c, -s);
+}
+
+// coef_q[t] for t >= d = td.shift from the beam-sum sample b = beam_q[t - d]: THE expression of the coefficient vectors, shared by coef_kernel, beamsum_coef_kernel and
+// path_coef_kernel -- same operations in the same order, so the same bits.  tt = (double)t * Ts, prx = rx_phase(w, tt).
+__device__ __forceinline__ c64 coef_value(c64 b, long long t, const TargetDesc& td, double w, double Ts, double tt, c64 prx) {
+  double sd, cd, st, ct;
+  sincos(td.wd * tt, &sd, &cd);                                // doppler phase at receive time  :43-44
+  sincos(w * ((double)(t - td.shift) * Ts), &st, &ct);         // up-conversion phase at transmit time :29-31,42
+  c64 v = b * mk(ct, st);
+  v = v * mk(cd, sd);
+  v = v * td.lsf;
+  return v * prx;
+}
+
 // rx[t,r] for one sample (shared by the fused demodulator and the waveform materialiser)
 __device__ __forceinline__ c64 rx_sample(long long t, int r, long long T, int Q, const c64* __restrict__ coef,
                                          const c64* __restrict__ s_steer_r /* [Q] a_q[r] */,

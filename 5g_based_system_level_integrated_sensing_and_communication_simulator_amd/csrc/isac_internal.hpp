@@ -118,6 +118,15 @@ int isac_cov_noise_beam_on(isac_ctx* ctx, hipStream_t st, const LazySplitFront& 
 // ctx->cov_xc: cross partials [L_whole][A][Q] (echo_range_xc_kernel) | D's Gram matrix per symbol [L_whole][Q][Q] | M / N [A x A]
 inline size_t lazy_xc_elems(int L_whole, int A, int Q) { return (size_t)L_whole * A * Q; }
 inline size_t lazy_xc_total(int L_whole, int A, int Q) { return lazy_xc_elems(L_whole, A, Q) + (size_t)L_whole * Q * Q + (size_t)A * A; }
+// ---------------------------------------------------------------- multistatic.hip: the coefficient vectors of a multi-static echo (include/isac_multistatic.h), for echo.hip's two entry points
+// The arguments of those calls, checked by the caller (limits, indices, shifts >= 0, the named sources' waveforms and element counts); every array is a host array.
+struct PathCoefJob {
+  const isac::c64* const* d_tx; const int32_t* n_ants_src;   // [S] device pointers, element counts
+  long long T; double fc, fs; int n_ants, n_paths;
+  const int32_t* path_source; const int64_t* path_shift; const double* path_doppler_hz; const double* path_gain;
+  const isac_c64* path_tx_steering; const isac_c64* path_rx_steering;
+};
+int isac_path_coefs_on(isac_ctx* ctx, hipStream_t st, const PathCoefJob& j);   // coef [P x T] -> ctx->coef, phase_rx [T] -> ctx->phase_rx, rx steering [A x P] and its transpose -> ctx->steer
 // ---------------------------------------------------------------- eigh.hip (the device code it shares with music.hip: eigh_dev.hpp)
 // device eig: H [A x A] (device) -> ctx->eig_w [A], ctx->eig_v [A x A] (unsorted); live_replay: see the definition
 int isac_eigh_dev(isac_ctx* ctx, const isac::c64* d_H, int A, hipStream_t st, bool live_replay = true);

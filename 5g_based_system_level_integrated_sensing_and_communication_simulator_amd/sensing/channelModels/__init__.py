@@ -1,1 +1,2 @@
 from .basicRadarChannel import basicRadarChannel  # noqa: F401
+from .multiStaticChannel import multiStaticChannel, multiStaticPaths  # noqa: F401

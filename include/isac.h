@@ -678,5 +678,6 @@ int isac_synth_qpsk_grid_dev(isac_ctx* ctx, isac_c64* d_grid, int32_t K, int32_t
 #include "isac_relax.h"  /* isac_fft2d_relax_targets: joint re-fit (RELAX) of Doppler tones on the range rows of the last fft2D: additive under ABI 8 */
 #include "isac_directions.h"  /* isac_resolve_directions: off-grid direction finding with several sources per array snapshot (greedy search + RELAX): additive under ABI 8 */
 #include "isac_beam_clean.h"  /* isac_fft2d_beam_clean_targets: successive target cancellation (CLEAN) with the detector on beam planes of the last fft2D: additive under ABI 8 */
+#include "isac_multistatic.h"  /* isac_multi_static_channel_dev / isac_multi_static_sensing_dev: echo synthesis with paths from other cells' transmitters: additive under ABI 8 */
 
 #endif /* ISAC_H */
