@@ -1,8 +1,8 @@
 // Successive target cancellation with the detector on beam planes of the last completed fft2D (gfx950 only): isac_fft2d_beam_clean_targets (include/isac_beam_clean.h;
 // project-defined).  On a copy R of the range rows ymid [nr x L x A], pass after pass:
 //   1  Y = rdm on the power window of R, Pb = the beam planes of Y and W      2  detector m on every beam plane      3  hits, M = max over the beams, b*, local maxima, order
-//   4  the first cell      5  its off-grid tone and direction: refine_enqueue (refine.hip), target_scan_snapshots (targets.hip)      6  parent (host)
-//   7  clean_cancel_enqueue (clean.hip): the tone subtracted from the rows r +- span_rows
+//   4  the first cell      5  its off-grid tone and direction      6  parent (host)      7  the tone subtracted from the rows r +- span_rows: steps 4-8 of isac_clean.h,
+//      cancel_pass (clean.hip)
 // The definition recomputes the window in every pass.  Here Pb [nr x nc x B], the per-CUT flags [B x n_cut], M / b* / hits [nr x nc] STAY on the device: pass 0 fills them
 // whole with the kernels of isac_fft2d_beam_detect (rdm_window_enqueue, beam_planes_enqueue: beams.hip) and of the detector (cfar_flag_planes: cfar.hip); after a subtraction
 // on the window rows lo .. hi only what those rows reach is formed again:
@@ -211,34 +211,23 @@ extern "C" int isac_fft2d_beam_clean_targets(isac_ctx* ctx, const isac_c64* W, i
     return fail(ctx, ISAC_ERR_INVALID_ARG, std::string(who) + ": NULL argument");
   if (n_beams < 1 || max_iter < 1 || max_iter > ISAC_MAX_TARGETS || span_rows < 0 || !std::isfinite(merge_tol) || merge_tol < 0.0)
     return fail(ctx, ISAC_ERR_INVALID_ARG, std::string(who) + ": n_beams must be positive, max_iter must lie in 1..ISAC_MAX_TARGETS, span_rows and merge_tol must be finite and not negative");
-  if (!ctx->last.valid || ctx->tgt.state != Fft2dCpi::kCollected)       // the rule of isac_fft2d_get_targets
-    return fail(ctx, ISAC_ERR_INVALID_ARG, std::string(who) + ": no completed fft2D on this context whose range rows are still on the device");
+  ISAC_TRY(cpi_ready(ctx, who));
   const Fft2dCpi& ts = ctx->tgt;
   const isac_est_params& ep = ts.ep;
   const CutWindow& w = ts.win;
-  const int A = ts.A, L = ts.L, n_fft = ep.n_fft, B = n_beams;
+  const int A = ts.A, L = ts.L, B = n_beams;
   if (ep.array_is_upa && !ele) return fail(ctx, ISAC_ERR_INVALID_ARG, std::string(who) + ": a planar array needs ele");
-  std::vector<unsigned char> act((size_t)L, 1);
-  int n_active = L;
-  if (sym_active) {
-    n_active = 0;
-    for (int l = 0; l < L; ++l) { act[(size_t)l] = sym_active[l] ? 1 : 0; n_active += act[(size_t)l]; }
-    if (n_active == 0) return fail(ctx, ISAC_ERR_INVALID_ARG, std::string(who) + ": sym_active names no active symbol");
-  }
+  SymbolMask mask;
+  ISAC_TRY(symbol_mask(ctx, who, sym_active, L, &mask));
   const long long n_win = (long long)w.nr * w.nc;
   if (B > ISAC_MAX_BEAMS) return fail(ctx, ISAC_ERR_UNSUPPORTED, std::string(who) + ": more than ISAC_MAX_BEAMS beams");
   if (n_win * B >= (1ll << 31)) return fail(ctx, ISAC_ERR_UNSUPPORTED, std::string(who) + ": the beam planes hold 2^31 cells or more");
   if (n_win * A >= (1ll << 31)) return fail(ctx, ISAC_ERR_UNSUPPORTED, std::string(who) + ": the antenna planes hold 2^31 cells or more");
-  if (w.hr < 1 || w.hc < 1) return fail(ctx, ISAC_ERR_UNSUPPORTED, std::string(who) + ": the local-maximum test needs a halo of at least one cell (guard + training) in both dimensions");
+  ISAC_TRY(needs_halo(ctx, who));
   std::vector<double> norm;
   ISAC_TRY(beam_weight_norms(ctx, who, W, A, B, norm));
-  RefinePlan plan;
-  ISAC_TRY(refine_plan(ctx, who, &plan));
-  if (ep.array_is_upa) {                                                   // n_ants_x n_ants_y != A: ISAC_ERR_INVALID_ARG; A > 256: ISAC_ERR_UNSUPPORTED -- before any work
-    const double* d_tab = nullptr;
-    int e_steps = 0, a_steps = 0;
-    ISAC_TRY(isac_doa2d_grid(ctx, &ep, A, &d_tab, &e_steps, &a_steps));
-  }
+  CancelLoop loop{who, {}, nullptr, nullptr, nullptr, nullptr, mask.n_active, span_rows, merge_tol, n_iter, row, col, status, parent, nu, vel, power, azi, ele};
+  ISAC_TRY(tone_plan(ctx, who, &loop.plan));
   BeamCleanState s{};
   s.who = who; s.m = m; s.B = B;
   // K1's tile: TC window columns with Y [A x TC] within 64 KB of LDS, the weights of 256 / TC beam groups in chunks of AC antennas within 32 KB
@@ -249,74 +238,53 @@ extern "C" int isac_fft2d_beam_clean_targets(isac_ctx* ctx, const isac_c64* W, i
   // one scratch block
   const int n_cut = (int)w.n_cut();
   const size_t n_rows_el = (size_t)w.nr * L * A, n_map = (size_t)n_win;
-  size_t off = 0;
-  auto take = [&off](size_t bytes) { const size_t o = off; off = (off + bytes + 15) & ~(size_t)15; return o; };
-  const size_t off_r = take(sizeof(c64) * n_rows_el), off_y = take(sizeof(c64) * n_map * A), off_w = take(sizeof(c64) * (size_t)A * B), off_snap = take(sizeof(c64) * (size_t)A * max_iter);
-  const size_t off_pb = take(sizeof(double) * n_map * B), off_n = take(sizeof(double) * (size_t)B), off_m = take(sizeof(double) * n_map);
-  const size_t off_cnt = take(16 + sizeof(BeamCand) * (size_t)n_cut), off_rec = take(16), off_nu = take(16), off_bs = take(sizeof(int) * n_map), off_h = take(sizeof(int) * n_map);   // (the pass's record [window row | k | status | scan bin] and [nu | power] side by side: one copy)
-  const size_t off_flags = take((size_t)B * n_cut), off_act = take((size_t)L);
-  ISAC_TRY(ensure(ctx, ctx->beam_clean, off));
+  Carver cv;
+  const size_t off_r = cv.take(sizeof(c64) * n_rows_el), off_y = cv.take(sizeof(c64) * n_map * A), off_w = cv.take(sizeof(c64) * (size_t)A * B), off_snap = cv.take(sizeof(c64) * (size_t)A * max_iter);
+  const size_t off_pb = cv.take(sizeof(double) * n_map * B), off_n = cv.take(sizeof(double) * (size_t)B), off_m = cv.take(sizeof(double) * n_map);
+  const size_t off_cnt = cv.take(16 + sizeof(BeamCand) * (size_t)n_cut), off_rec = cv.take(sizeof(CancelRecord)), off_bs = cv.take(sizeof(int) * n_map), off_h = cv.take(sizeof(int) * n_map);
+  const size_t off_flags = cv.take((size_t)B * n_cut), off_act = cv.take((size_t)L);
+  ISAC_TRY(ensure(ctx, ctx->beam_clean, cv.total));
   char* d = (char*)ctx->beam_clean.p;
   s.d_R = (c64*)(d + off_r); s.d_W = (c64*)(d + off_w);
   s.d_Pb = (double*)(d + off_pb); s.d_norm = (double*)(d + off_n); s.d_M = (double*)(d + off_m);
   s.d_bstar = (int*)(d + off_bs); s.d_hits = (int*)(d + off_h);
   s.d_count = (unsigned*)(d + off_cnt); s.d_flags = (unsigned char*)(d + off_flags);
-  int* d_rec = (int*)(d + off_rec);
+  loop.d_R = s.d_R; loop.d_rec = (CancelRecord*)(d + off_rec); loop.d_snap = (c64*)(d + off_snap); loop.d_act = (const unsigned char*)(d + off_act);
   ISAC_HIP(hipMemcpyAsync(s.d_R, ctx->ymid.p, sizeof(c64) * n_rows_el, hipMemcpyDeviceToDevice, ctx->stream));
   ISAC_TRY(copy_h2d(ctx, s.d_W, W, sizeof(c64) * (size_t)A * B));
   ISAC_TRY(copy_h2d(ctx, s.d_norm, norm.data(), sizeof(double) * (size_t)B));
-  ISAC_TRY(copy_h2d(ctx, d + off_act, act.data(), (size_t)L));
+  ISAC_TRY(copy_h2d(ctx, d + off_act, mask.act.data(), (size_t)L));
   // ---- steps 1-3 of pass 0, whole: the kernels of isac_fft2d_beam_detect and of the detector (a detector block the detector refuses is refused here, before any output)
   ISAC_TRY(rdm_window_enqueue(ctx, who, s.d_R, (c64*)(d + off_y)));
   ISAC_TRY(beam_planes_enqueue(ctx, (const c64*)(d + off_y), n_win, s.d_W, s.d_norm, B, s.d_Pb));
   ISAC_TRY(enqueue_flags_and_maps(ctx, s, 0, w.nr - 1));
   *n_iter = 0; *n_kept = 0; *n_left = 0;
-  static_assert(sizeof(int) * 4 == 16, "the record and [nu | power] are fetched as one block of 32 bytes");
   std::vector<BeamCand> cells;
-  int kept = 0;
-  for (int i = 0;; ++i) {
+  for (;;) {
     ISAC_TRY(list_cells(ctx, s, cells));
     *n_left = (int)cells.size();
+    const int i = *n_iter;
     if (cells.empty() || i == max_iter) break;
-    // ---- step 4
+    // ---- step 4: the first cell; steps 5-7
     const BeamCand c0 = cells[0];
     const CutWindow::RowCol rc = w.row_col_of(c0.cut);                    // 1-based
-    row[i] = rc.row; col[i] = rc.col; hits[i] = c0.hits; beam[i] = c0.plane + 1; map_power[i] = c0.m; rng[i] = CutWindow::range_of(rc.row, ep);
+    hits[i] = c0.hits; beam[i] = c0.plane + 1; map_power[i] = c0.m; rng[i] = CutWindow::range_of(rc.row, ep);
     beam_label[i] = beam_azi ? beam_azi[c0.plane] : (double)(c0.plane + 1);
-    // ---- step 5
-    const int sel[2] = {rc.row - w.first_row, rc.col - n_fft / 2 - 1};
-    ISAC_TRY(stage_upload(ctx, d_rec, sel, sizeof(sel)));
-    c64* d_snap = (c64*)(d + off_snap) + (size_t)A * i;
-    ISAC_TRY(refine_enqueue(ctx, plan, s.d_R, d_rec, d_rec + 1, 1, d_rec + 2, (double*)(d + off_nu), (double*)(d + off_nu) + 1, d_snap));
-    ISAC_TRY(target_scan_snapshots(ctx, d_snap, 1, d_rec + 3, azi + i, ele ? ele + i : nullptr));
-    struct { int rec[4]; double nu, pow; } got;
-    ISAC_TRY(copy_d2h(ctx, &got, d_rec, sizeof(got)));
-    status[i] = got.rec[2]; nu[i] = got.nu; power[i] = got.pow;
-    vel[i] = status[i] == 0 ? nu[i] * n_fft * ep.v_res : CutWindow::velocity_of(col[i], ep);
-    parent[i] = i;
-    *n_iter = i + 1;
-    if (status[i] != 0) { ++kept; break; }
-    // ---- step 6 (merge_tol == 0: every entry is kept)
-    if (merge_tol != 0.0)
-      for (int k = 0; k < i; ++k)
-        if (parent[k] == k && std::abs(row[i] - row[k]) <= span_rows && std::fabs(nu[i] - nu[k]) * L <= merge_tol) { parent[i] = k; break; }
-    kept += parent[i] == i ? 1 : 0;
-    // ---- step 7, then steps 1-3 of the next pass on what the band reaches
-    const int wr = sel[0];                                                 // 0 <= wr < nr: a CUT row of the window
-    const int lo = (int)std::max<long long>((long long)wr - span_rows, 0), hi = (int)std::min<long long>((long long)wr + span_rows, w.nr - 1);
-    ISAC_TRY(clean_cancel_enqueue(ctx, s.d_R, lo, hi, nu[i], (const unsigned char*)(d + off_act), n_active));
-    ISAC_TRY(enqueue_band_planes(ctx, s, lo, hi));
-    ISAC_TRY(enqueue_flags_and_maps(ctx, s, lo, hi));
+    RowSpan span;
+    bool stop = false;
+    ISAC_TRY(cancel_pass(ctx, loop, rc.row, rc.col, &span, &stop));
+    if (stop) break;
+    // ---- steps 1-3 of the next pass on what the band reaches
+    ISAC_TRY(enqueue_band_planes(ctx, s, span.lo, span.hi));
+    ISAC_TRY(enqueue_flags_and_maps(ctx, s, span.lo, span.hi));
   }
-  *n_kept = kept;
   if (left_cells)
     for (size_t i = 0; i < std::min(cells.size(), (size_t)ISAC_MAX_TARGETS); ++i) {
       const CutWindow::RowCol rc = w.row_col_of(cells[i].cut);
       left_cells[2 * i] = rc.row;
       left_cells[2 * i + 1] = rc.col;
     }
-  if (snapshots && *n_iter > 0) ISAC_TRY(copy_d2h(ctx, snapshots, d + off_snap, sizeof(c64) * (size_t)A * *n_iter));
-  if (residual_rows) ISAC_TRY(copy_d2h(ctx, residual_rows, s.d_R, sizeof(c64) * n_rows_el));
+  ISAC_TRY(cancel_finish(ctx, loop, n_kept, snapshots, residual_rows));
   if (beam_pow) ISAC_TRY(copy_d2h(ctx, beam_pow, s.d_Pb, sizeof(double) * n_map * B));
   return ISAC_OK;
 }

@@ -71,14 +71,19 @@ __global__ __launch_bounds__(256) void beam_planes_kernel(const c64* __restrict_
 // ================================================================= host side
 using namespace isac;
 
-namespace {
-
-// a completed fft2D whose range rows are still the ones it left (the rule of isac_fft2d_get_targets)
 int cpi_ready(isac_ctx* ctx, const char* who) {
   if (!ctx->last.valid || ctx->tgt.state != Fft2dCpi::kCollected)
     return fail(ctx, ISAC_ERR_INVALID_ARG, std::string(who) + ": no completed fft2D on this context whose range rows are still on the device");
   return ISAC_OK;
 }
+
+int needs_halo(isac_ctx* ctx, const char* who) {
+  if (ctx->tgt.win.hr < 1 || ctx->tgt.win.hc < 1)
+    return fail(ctx, ISAC_ERR_UNSUPPORTED, std::string(who) + ": the local-maximum test needs a halo of at least one cell (guard + training) in both dimensions");
+  return ISAC_OK;
+}
+
+namespace {
 
 // step 1 into ctx->beam_y
 int enqueue_rdm_window(isac_ctx* ctx, const char* who) {
@@ -151,18 +156,19 @@ extern "C" int isac_fft2d_beam_detect(isac_ctx* ctx, const isac_c64* W, int32_t 
   const long long n_cells = (long long)w.nr * w.nc;
   if (B > ISAC_MAX_BEAMS) return fail(ctx, ISAC_ERR_UNSUPPORTED, std::string(who) + ": more than ISAC_MAX_BEAMS beams");
   if (n_cells * B >= (1ll << 31)) return fail(ctx, ISAC_ERR_UNSUPPORTED, std::string(who) + ": the beam planes hold 2^31 cells or more");
-  if (w.hr < 1 || w.hc < 1) return fail(ctx, ISAC_ERR_UNSUPPORTED, std::string(who) + ": the local-maximum test needs a halo of at least one cell (guard + training) in both dimensions");
+  ISAC_TRY(needs_halo(ctx, who));
   std::vector<double> norm;
   ISAC_TRY(beam_weight_norms(ctx, who, W, A, B, norm));
   // ---- steps 1, 2: ctx->beam_y = [Y nr nc A | W A B | n_b B], ctx->beam_p = the beam planes
-  const size_t off_w = sizeof(c64) * (size_t)n_cells * A, off_n = off_w + sizeof(c64) * (size_t)A * B;
-  ISAC_TRY(ensure(ctx, ctx->beam_y, off_n + sizeof(double) * (size_t)B));
+  Carver cv;
+  const size_t off_y = cv.take(sizeof(c64) * (size_t)n_cells * A), off_w = cv.take(sizeof(c64) * (size_t)A * B), off_n = cv.take(sizeof(double) * (size_t)B);   // (off_y = 0: where enqueue_rdm_window writes)
+  ISAC_TRY(ensure(ctx, ctx->beam_y, cv.total));
   ISAC_TRY(ensure(ctx, ctx->beam_p, sizeof(double) * (size_t)n_cells * B));
   char* dy = (char*)ctx->beam_y.p;
   ISAC_TRY(copy_h2d(ctx, dy + off_w, W, sizeof(c64) * (size_t)A * B));
   ISAC_TRY(copy_h2d(ctx, dy + off_n, norm.data(), sizeof(double) * (size_t)B));
   ISAC_TRY(enqueue_rdm_window(ctx, who));                                  // (beam_y is large enough already: ensure keeps it)
-  ISAC_TRY(beam_planes_enqueue(ctx, (const c64*)dy, n_cells, (const c64*)(dy + off_w), (const double*)(dy + off_n), B, (double*)ctx->beam_p.p));
+  ISAC_TRY(beam_planes_enqueue(ctx, (const c64*)(dy + off_y), n_cells, (const c64*)(dy + off_w), (const double*)(dy + off_n), B, (double*)ctx->beam_p.p));
   // ---- step 3: the detector of isac_fft2d_redetect on the beam planes
   PlaneLists pl;
   ISAC_TRY(cfar_detect_planes(ctx, who, m, (const double*)ctx->beam_p.p, B, ctx->beam_det, &pl));

@@ -10,6 +10,8 @@
 // X_a sums the active ones only; then thread i subtracts (X_a / n_active) conj(p_l) from sample (l, a) = (i % L, i / L) of the row, read and written at stride nr.  The
 // phasors, one sincos of the full argument each, are formed once per workgroup and serve the fit and the subtraction.  fp64, no atomics; a workgroup owns its row.
 // The loop is host-driven (every pass reads the detector's counts and the first cell back) and recomputes the whole window each pass: off the timed path.
+// Steps 4-8 do not depend on how the cell was found: they are cancel_pass, which the loop of isac_fft2d_beam_clean_targets (beam_clean.hip) runs as well; the fit and the
+// subtraction are tone_fit_subtract (refine_dev.hpp), which relax_refit_kernel (relax.hip) shares.
 #include <cmath>
 #include <memory>
 #include <vector>
@@ -33,18 +35,10 @@ __global__ __launch_bounds__(256) void clean_cancel_kernel(c64* R /* [nr x L x A
   c64* s_x = s_ph + L;                                                    // [A]
   double* s_p = reinterpret_cast<double*>(s_x + A);                       // [A]
   double* s_d = s_p + A;                                                  // [A]
-  const int tid = threadIdx.x;
   c64* row = R + row_lo + blockIdx.x;                                     // (the host clips the span to 0 .. nr - 1)
-  for (int l = tid; l < L; l += 256) s_ph[l] = active[l] ? refine_phasor(nu, l) : mk(0.0, 0.0);
+  tone_phasors(s_ph, nu, L, active);
   __syncthreads();
-  (void)refine_eval(row, nr, L, A, s_ph, s_x, s_p, s_d);                  // s_x[a] = sum over the active symbols; ends with a barrier: every read of the row is done
-  for (int i = tid; i < L * A; i += 256) {
-    const int l = i % L, a = i / L;
-    if (!active[l]) continue;
-    const c64 c = mk(s_x[a].re / n_active, s_x[a].im / n_active);
-    c64* y = row + (long long)nr * (l + (long long)L * a);
-    *y = *y - c * conj(s_ph[l]);
-  }
+  tone_fit_subtract<false>(row, nr, L, A, active, n_active, s_ph, s_x, s_p, s_d);
 }
 
 }  // namespace isac
@@ -52,12 +46,54 @@ __global__ __launch_bounds__(256) void clean_cancel_kernel(c64* R /* [nr x L x A
 // ================================================================= host side
 using namespace isac;
 
-int clean_cancel_enqueue(isac_ctx* ctx, c64* d_R, int row_lo, int row_hi, double nu, const unsigned char* d_active, int n_active) {
+int symbol_mask(isac_ctx* ctx, const char* who, const uint8_t* sym_active, int L, SymbolMask* mask) {
+  mask->act.assign((size_t)L, 1);
+  mask->n_active = L;
+  if (sym_active) {
+    mask->n_active = 0;
+    for (int l = 0; l < L; ++l) { mask->act[(size_t)l] = sym_active[l] ? 1 : 0; mask->n_active += mask->act[(size_t)l]; }
+    if (mask->n_active == 0) return fail(ctx, ISAC_ERR_INVALID_ARG, std::string(who) + ": sym_active names no active symbol");
+  }
+  return ISAC_OK;
+}
+
+int cancel_pass(isac_ctx* ctx, CancelLoop& s, int row, int col, RowSpan* span, bool* stop) {
   const Fft2dCpi& ts = ctx->tgt;
-  const size_t lds = sizeof(c64) * ((size_t)ts.L + ts.A) + sizeof(double) * 2 * (size_t)ts.A;   // (<= the refinement's, which refine_plan has bounded by 160 KB)
+  const isac_est_params& ep = ts.ep;
+  const int A = ts.A, L = ts.L, n_fft = ep.n_fft, i = *s.n_iter;
+  // ---- step 4
+  s.row[i] = row; s.col[i] = col;
+  // ---- steps 5, 6
+  const int sel[2] = {row - ts.win.first_row, col - n_fft / 2 - 1};
+  ISAC_TRY(stage_upload(ctx, s.d_rec, sel, sizeof(sel)));
+  c64* d_snap = s.d_snap + (size_t)A * i;
+  ISAC_TRY(refine_enqueue(ctx, s.plan, s.d_R, &s.d_rec->wr, &s.d_rec->k, 1, &s.d_rec->status, &s.d_rec->nu, &s.d_rec->power, d_snap));
+  ISAC_TRY(target_scan_snapshots(ctx, d_snap, 1, &s.d_rec->bin, s.azi + i, s.ele ? s.ele + i : nullptr));
+  CancelRecord got;
+  ISAC_TRY(copy_d2h(ctx, &got, s.d_rec, sizeof(got)));
+  s.status[i] = got.status; s.nu[i] = got.nu; s.power[i] = got.power;
+  s.vel[i] = got.status == 0 ? got.nu * n_fft * ep.v_res : CutWindow::velocity_of(col, ep);
+  s.parent[i] = i;
+  *s.n_iter = i + 1;
+  *stop = got.status != 0;
+  if (*stop) { ++s.kept; return ISAC_OK; }
+  // ---- step 7
+  s.parent[i] = merge_parent(i, s.row, s.nu, s.parent, nullptr, s.span_rows, s.merge_tol, L);
+  s.kept += s.parent[i] == i ? 1 : 0;
+  // ---- step 8
+  *span = span_of(sel[0], s.span_rows, ts.win.nr);                        // 0 <= sel[0] < nr: a CUT row of the window
+  const size_t lds = sizeof(c64) * ((size_t)L + A) + sizeof(double) * 2 * (size_t)A;   // (<= the refinement's, which tone_plan has bounded by 160 KB)
   ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(clean_cancel_kernel), lds));
-  hipLaunchKernelGGL(clean_cancel_kernel, dim3(row_hi - row_lo + 1), dim3(256), lds, ctx->stream, d_R, ts.win.nr, ts.L, ts.A, row_lo, nu, d_active, (double)n_active);
+  hipLaunchKernelGGL(clean_cancel_kernel, dim3(span->len()), dim3(256), lds, ctx->stream, s.d_R, ts.win.nr, L, A, span->lo, got.nu, s.d_act, (double)s.n_active);
   ISAC_HIP(hipGetLastError());
+  return ISAC_OK;
+}
+
+int cancel_finish(isac_ctx* ctx, const CancelLoop& s, int32_t* n_kept, isac_c64* snapshots, isac_c64* residual_rows) {
+  const Fft2dCpi& ts = ctx->tgt;
+  *n_kept = s.kept;
+  if (snapshots && *s.n_iter > 0) ISAC_TRY(copy_d2h(ctx, snapshots, s.d_snap, sizeof(c64) * (size_t)ts.A * *s.n_iter));
+  if (residual_rows) ISAC_TRY(copy_d2h(ctx, residual_rows, s.d_R, sizeof(c64) * (size_t)ts.win.nr * ts.L * ts.A));
   return ISAC_OK;
 }
 
@@ -70,48 +106,34 @@ extern "C" int isac_fft2d_clean_targets(isac_ctx* ctx, const isac_cfar_method* m
     return fail(ctx, ISAC_ERR_INVALID_ARG, std::string(who) + ": NULL argument");
   if (max_iter < 1 || max_iter > ISAC_MAX_TARGETS || span_rows < 0 || !std::isfinite(merge_tol) || merge_tol < 0.0)
     return fail(ctx, ISAC_ERR_INVALID_ARG, std::string(who) + ": max_iter must lie in 1..ISAC_MAX_TARGETS, span_rows and merge_tol must be finite and not negative");
-  if (!ctx->last.valid || ctx->tgt.state != Fft2dCpi::kCollected)       // the rule of isac_fft2d_get_targets
-    return fail(ctx, ISAC_ERR_INVALID_ARG, std::string(who) + ": no completed fft2D on this context whose range rows are still on the device");
+  ISAC_TRY(cpi_ready(ctx, who));
   const Fft2dCpi& ts = ctx->tgt;
-  const isac_est_params& ep = ts.ep;
   const CutWindow& w = ts.win;
-  const int A = ts.A, L = ts.L, n_fft = ep.n_fft;
-  if (ep.array_is_upa && !ele) return fail(ctx, ISAC_ERR_INVALID_ARG, std::string(who) + ": a planar array needs ele");
-  std::vector<unsigned char> act((size_t)L, 1);
-  int n_active = L;
-  if (sym_active) {
-    n_active = 0;
-    for (int l = 0; l < L; ++l) { act[(size_t)l] = sym_active[l] ? 1 : 0; n_active += act[(size_t)l]; }
-    if (n_active == 0) return fail(ctx, ISAC_ERR_INVALID_ARG, std::string(who) + ": sym_active names no active symbol");
-  }
-  if (w.hr < 1 || w.hc < 1) return fail(ctx, ISAC_ERR_UNSUPPORTED, std::string(who) + ": the local-maximum test needs a halo of at least one cell (guard + training) in both dimensions");
-  RefinePlan plan;
-  ISAC_TRY(refine_plan(ctx, who, &plan));
-  if (ep.array_is_upa) {                                                   // n_ants_x n_ants_y != A: ISAC_ERR_INVALID_ARG; A > 256: ISAC_ERR_UNSUPPORTED -- before any work
-    const double* d_tab = nullptr;
-    int e_steps = 0, a_steps = 0;
-    ISAC_TRY(isac_doa2d_grid(ctx, &ep, A, &d_tab, &e_steps, &a_steps));
-  }
+  const int A = ts.A, L = ts.L;
+  if (ts.ep.array_is_upa && !ele) return fail(ctx, ISAC_ERR_INVALID_ARG, std::string(who) + ": a planar array needs ele");
+  SymbolMask mask;
+  ISAC_TRY(symbol_mask(ctx, who, sym_active, L, &mask));
+  ISAC_TRY(needs_halo(ctx, who));
+  CancelLoop s{who, {}, nullptr, nullptr, nullptr, nullptr, mask.n_active, span_rows, merge_tol, n_iter, row, col, status, parent, nu, vel, power, azi, ele};
+  ISAC_TRY(tone_plan(ctx, who, &s.plan));
   *n_iter = 0; *n_kept = 0; *n_left = 0;
-  // one scratch block: [R nr L A | Y nr nc A] c64, [P nr nc A] doubles, the pass's record [window row | k | status | scan bin] ints, [nu | power] doubles, the snapshots
-  // [A x max_iter], the symbol mask [L]
   const long long n_cells = (long long)w.nr * w.nc * A;
   if (n_cells >= (1ll << 31)) return fail(ctx, ISAC_ERR_UNSUPPORTED, std::string(who) + ": the antenna planes hold 2^31 cells or more");
+  // one scratch block: [R nr L A | Y nr nc A] c64, [P nr nc A] doubles, the pass's record, the snapshots [A x max_iter], the symbol mask [L]
   const size_t n_rows_el = (size_t)w.nr * L * A;
-  const size_t off_y = sizeof(c64) * n_rows_el, off_p = off_y + sizeof(c64) * (size_t)n_cells, off_rec = (off_p + sizeof(double) * (size_t)n_cells + 15) & ~(size_t)15;
-  const size_t off_nu = off_rec + 16, off_snap = off_nu + 16, off_act = off_snap + sizeof(c64) * (size_t)A * max_iter;
-  ISAC_TRY(ensure(ctx, ctx->clean, off_act + (size_t)L));
+  Carver cv;
+  const size_t off_r = cv.take(sizeof(c64) * n_rows_el), off_y = cv.take(sizeof(c64) * (size_t)n_cells), off_p = cv.take(sizeof(double) * (size_t)n_cells);
+  const size_t off_rec = cv.take(sizeof(CancelRecord)), off_snap = cv.take(sizeof(c64) * (size_t)A * max_iter), off_act = cv.take((size_t)L);
+  ISAC_TRY(ensure(ctx, ctx->clean, cv.total));
   char* d = (char*)ctx->clean.p;
-  c64* d_R = (c64*)d;
+  s.d_R = (c64*)(d + off_r); s.d_rec = (CancelRecord*)(d + off_rec); s.d_snap = (c64*)(d + off_snap); s.d_act = (const unsigned char*)(d + off_act);
   double* d_P = (double*)(d + off_p);
-  int* d_rec = (int*)(d + off_rec);
-  ISAC_HIP(hipMemcpyAsync(d_R, ctx->ymid.p, sizeof(c64) * n_rows_el, hipMemcpyDeviceToDevice, ctx->stream));
-  ISAC_TRY(copy_h2d(ctx, d + off_act, act.data(), (size_t)L));
+  ISAC_HIP(hipMemcpyAsync(s.d_R, ctx->ymid.p, sizeof(c64) * n_rows_el, hipMemcpyDeviceToDevice, ctx->stream));
+  ISAC_TRY(copy_h2d(ctx, d + off_act, mask.act.data(), (size_t)L));
   std::unique_ptr<isac_target_list> tl(new isac_target_list);
-  int kept = 0;
-  for (int i = 0;; ++i) {
+  for (bool stop = false; !stop;) {
     // ---- steps 1-3
-    ISAC_TRY(rdm_window_enqueue(ctx, who, d_R, (c64*)(d + off_y)));
+    ISAC_TRY(rdm_window_enqueue(ctx, who, s.d_R, (c64*)(d + off_y)));
     hipLaunchKernelGGL(clean_power_kernel, dim3(cdiv(n_cells, 256)), dim3(256), 0, ctx->stream, (const c64*)(d + off_y), n_cells, d_P);
     ISAC_HIP(hipGetLastError());
     PlaneLists pl;
@@ -119,35 +141,12 @@ extern "C" int isac_fft2d_clean_targets(isac_ctx* ctx, const isac_cfar_method* m
     const PlaneCells src{d_P, A, pl.d_cut, pl.d_cnt, pl.n_cut, false, &ctx->clean_sel, nullptr};
     ISAC_TRY(target_cells_of_planes(ctx, who, src, tl.get()));
     *n_left = tl->n_total;
+    const int i = *n_iter;
     if (tl->n_total == 0 || i == max_iter) break;
-    // ---- step 4
-    row[i] = tl->row[0]; col[i] = tl->col[0]; hits[i] = tl->hits[0]; map_power[i] = tl->power[0]; rng[i] = tl->rng[0];
-    // ---- steps 5, 6
-    const int sel[2] = {row[i] - w.first_row, col[i] - n_fft / 2 - 1};
-    ISAC_TRY(stage_upload(ctx, d_rec, sel, sizeof(sel)));
-    c64* d_snap = (c64*)(d + off_snap) + (size_t)A * i;
-    ISAC_TRY(refine_enqueue(ctx, plan, d_R, d_rec, d_rec + 1, 1, d_rec + 2, (double*)(d + off_nu), (double*)(d + off_nu) + 1, d_snap));
-    ISAC_TRY(target_scan_snapshots(ctx, d_snap, 1, d_rec + 3, azi + i, ele ? ele + i : nullptr));
-    double np[2];
-    ISAC_TRY(copy_d2h(ctx, status + i, d_rec + 2, sizeof(int)));
-    ISAC_TRY(copy_d2h(ctx, np, d + off_nu, sizeof(np)));
-    nu[i] = np[0]; power[i] = np[1];
-    vel[i] = status[i] == 0 ? nu[i] * n_fft * ep.v_res : CutWindow::velocity_of(col[i], ep);
-    parent[i] = i;
-    *n_iter = i + 1;
-    if (status[i] != 0) { ++kept; break; }
-    // ---- step 7 (merge_tol == 0: every entry is kept)
-    if (merge_tol != 0.0)
-      for (int k = 0; k < i; ++k)
-        if (parent[k] == k && std::abs(row[i] - row[k]) <= span_rows && std::fabs(nu[i] - nu[k]) * L <= merge_tol) { parent[i] = k; break; }
-    kept += parent[i] == i ? 1 : 0;
-    // ---- step 8
-    const int wr = sel[0];                                                 // 0 <= wr < nr: a CUT row of the window
-    const int lo = (int)std::max<long long>((long long)wr - span_rows, 0), hi = (int)std::min<long long>((long long)wr + span_rows, w.nr - 1);
-    ISAC_TRY(clean_cancel_enqueue(ctx, d_R, lo, hi, nu[i], (const unsigned char*)(d + off_act), n_active));
+    // ---- step 4: the first cell; steps 5-8
+    hits[i] = tl->hits[0]; map_power[i] = tl->power[0]; rng[i] = tl->rng[0];
+    RowSpan span;
+    ISAC_TRY(cancel_pass(ctx, s, tl->row[0], tl->col[0], &span, &stop));
   }
-  *n_kept = kept;
-  if (snapshots && *n_iter > 0) ISAC_TRY(copy_d2h(ctx, snapshots, d + off_snap, sizeof(c64) * (size_t)A * *n_iter));
-  if (residual_rows) ISAC_TRY(copy_d2h(ctx, residual_rows, d_R, sizeof(c64) * n_rows_el));
-  return ISAC_OK;
+  return cancel_finish(ctx, s, n_kept, snapshots, residual_rows);
 }

@@ -240,8 +240,8 @@ struct isac_ctx {
   isac::DevBuf redet;                // isac_fft2d_redetect (cfar.hip): per-CUT flags, per-antenna lists sized for every CUT, counts, row flags
   isac::DevBuf beam_y, beam_p, beam_det, beam_sel;   // isac_fft2d_get_rdm_window / isac_fft2d_beam_detect (beams.hip): complex window [nr x nc x A] (+ W), beam planes [nr x nc x B], the detector's scratch, the cells'
   isac::DevBuf refine;               // isac_fft2d_refine_targets (refine.hip): the cells, their status / scan bin / nu / power, the refined snapshots [A x n]
-  isac::DevBuf clean, clean_det, clean_sel;   // isac_fft2d_clean_targets (clean.hip): [residual rows | complex window | power planes | per-pass records | snapshots], the detector's scratch, the cells'
-  isac::DevBuf beam_clean;           // isac_fft2d_beam_clean_targets (beam_clean.hip): [residual rows | complex window | W | snapshots] c64, [beam planes | n_b | M] doubles, [count | the listed cells' records], the pass's record, b*, hits, the per-CUT flags [B x n_cut], the symbol mask
+  isac::DevBuf clean, clean_det, clean_sel;   // isac_fft2d_clean_targets (clean.hip): [residual rows | complex window] c64, the power planes, the pass's record (CancelRecord), the snapshots, the symbol mask -- carved by isac::Carver (cpi_post.hpp), as the next two are; the detector's scratch, the cells'
+  isac::DevBuf beam_clean;           // isac_fft2d_beam_clean_targets (beam_clean.hip): [residual rows | complex window | W | snapshots] c64, [beam planes | n_b | M] doubles, [count | the listed cells' records], the pass's record (CancelRecord), b*, hits, the per-CUT flags [B x n_cut], the symbol mask
   isac::DevBuf relax;                // isac_fft2d_relax_targets (relax.hip): [residual rows | tone amplitudes n x span x A | snapshots] c64, [nu | previous nu | power], the entries' rows, spans and schedule, the symbol mask
   isac::DevBuf directions;           // isac_resolve_directions (directions.hip): the snapshots [A x n], the sources' amplitudes and directions [K x n], residuals, counts
   isac::DevBuf cfar_mc;             // isac_cfar_monte_carlo (cfar.hip): detection counts, per-trial flags

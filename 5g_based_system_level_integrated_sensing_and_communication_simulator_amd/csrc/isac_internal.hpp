@@ -4,6 +4,7 @@
 #include "isac_common.hpp"
 #include "eigh_layout.hpp"
 #include "beam_window.hpp"
+#include "cpi_post.hpp"
 
 // ---------------------------------------------------------------- tables.hip: cached device tables
 // The one way a cached table comes to exist: `key` is looked up in ctx->tables; on a miss `build` fills a std::vector<T> on the host, which is uploaded and kept under
@@ -73,14 +74,21 @@ int target_cells_of_planes(isac_ctx* ctx, const char* who, const isac::PlaneCell
 int target_scan_snapshots(isac_ctx* ctx, const isac::c64* d_snap, int n, int* d_bin, double* azi, double* ele);
 // ---------------------------------------------------------------- refine.hip: isac_fft2d_refine_targets (include/isac_refine.h) -- off-grid Doppler, split-lobe merge and sidelobe flags for listed cells of the
 // last completed fft2D.  Reads ctx->tgt and ctx->ymid, writes ctx->refine (and ctx->tgt_part through target_scan_snapshots) only.
-// For clean.hip: steps 1-3 of isac_refine.h on n cells of the range rows d_rows [nr x L x A] (ctx->ymid, or a residual copy of it): refine_plan sizes the probes for
-// the CPI (ISAC_ERR_UNSUPPORTED: they do not fit the LDS), refine_enqueue launches refine_kernel on the context's stream.  d_cell_row: window rows, 0-based; d_cell_k: col - nFFT/2 - 1.
+// For clean.hip and relax.hip: steps 1-3 of isac_refine.h on n cells of the range rows d_rows [nr x L x A] (ctx->ymid, or a residual copy of it): tone_plan sizes the probes
+// for the CPI (ISAC_ERR_UNSUPPORTED: they do not fit the LDS) and, for a planar array, runs the checks of isac_doa2d_grid that target_scan_snapshots would meet only after
+// the work (n_ants_x n_ants_y != A: ISAC_ERR_INVALID_ARG; A > 256: ISAC_ERR_UNSUPPORTED); refine_enqueue launches refine_kernel on the context's stream.  d_cell_row: window
+// rows, 0-based; d_cell_k: col - nFFT/2 - 1.
 namespace isac { struct RefinePlan { double W = 0.0; int M = 0; size_t lds = 0; }; }
-int refine_plan(isac_ctx* ctx, const char* who, isac::RefinePlan* plan);
+int tone_plan(isac_ctx* ctx, const char* who, isac::RefinePlan* plan);
 int refine_enqueue(isac_ctx* ctx, const isac::RefinePlan& plan, const isac::c64* d_rows, const int* d_cell_row, const int* d_cell_k, int n, int* d_status, double* d_nu, double* d_pow, isac::c64* d_snap /* [A x n] */);
 // ---------------------------------------------------------------- beams.hip: isac_fft2d_get_rdm_window, isac_fft2d_beam_detect (include/isac_beams.h) -- the complex window of the last completed fft2D and CFAR on
 // beam planes of it.  Reads ctx->tgt and ctx->ymid, writes ctx->beam_y / beam_p / beam_det / beam_sel only; calls isac_get_twiddles, cfar_detect_planes and target_cells_of_planes.
-// For clean.hip: step 1 of isac_beams.h: rdm_window_kernel on the range rows d_rows [nr x L x A] into d_Y [nr x nc x A] (both sized by the caller), enqueued on the context's stream
+// What every call on "the last completed fft2D" asks first (the rule of isac_fft2d_get_targets): a completed fft2D whose range rows are still the ones it left, else
+// ISAC_ERR_INVALID_ARG; and what every local-maximum test asks of the CFAR window: a halo of at least one cell in both dimensions, else ISAC_ERR_UNSUPPORTED.  who: the
+// entry point, for the message.
+int cpi_ready(isac_ctx* ctx, const char* who);
+int needs_halo(isac_ctx* ctx, const char* who);
+// For clean.hip and beam_clean.hip: step 1 of isac_beams.h: rdm_window_kernel on the range rows d_rows [nr x L x A] into d_Y [nr x nc x A] (both sized by the caller), enqueued on the context's stream
 int rdm_window_enqueue(isac_ctx* ctx, const char* who, const isac::c64* d_rows, isac::c64* d_Y);
 // For beam_clean.hip: n_b of every column of the host weights W [A x B] (ISAC_ERR_INVALID_ARG: a zero or non-finite norm), and step 2 of isac_beams.h: beam_planes_kernel on
 // d_Y [n_cells x A] with the weights d_W [A x B] and norms d_norm [B] into d_Pb [n_cells x B] (all on the device, sized by the caller), enqueued on the context's stream
@@ -88,16 +96,33 @@ int beam_weight_norms(isac_ctx* ctx, const char* who, const isac_c64* W, int A, 
 int beam_planes_enqueue(isac_ctx* ctx, const isac::c64* d_Y, long long n_cells, const isac::c64* d_W, const double* d_norm, int B, double* d_Pb);
 // ---------------------------------------------------------------- clean.hip: isac_fft2d_clean_targets (include/isac_clean.h) -- successive cancellation on a residual copy of the range rows of the last completed
 // fft2D.  Reads ctx->tgt and ctx->ymid, writes ctx->clean / clean_det / clean_sel (and ctx->tgt_part through target_scan_snapshots) only; calls rdm_window_enqueue, cfar_detect_planes,
-// target_cells_of_planes, refine_plan / refine_enqueue and target_scan_snapshots.
-// For beam_clean.hip: step 8 of isac_clean.h -- clean_cancel_kernel on the window rows row_lo .. row_hi (0-based, clipped by the caller) of d_R [nr x L x A] at nu, over the
-// symbols d_active [L] names (n_active of them), enqueued on the context's stream
-int clean_cancel_enqueue(isac_ctx* ctx, isac::c64* d_R, int row_lo, int row_hi, double nu, const unsigned char* d_active, int n_active);
+// target_cells_of_planes, tone_plan / refine_enqueue and target_scan_snapshots.
+// For relax.hip and beam_clean.hip: the caller's sym_active [L] (NULL: every symbol) as the mask the kernels read and the number of active symbols
+// (ISAC_ERR_INVALID_ARG: none)
+namespace isac { struct SymbolMask { std::vector<unsigned char> act; int n_active = 0; }; }
+int symbol_mask(isac_ctx* ctx, const char* who, const uint8_t* sym_active, int L, isac::SymbolMask* mask);
+// For beam_clean.hip: what a cancellation loop carries across its passes, and steps 4-8 of isac_clean.h -- all of a pass that does not depend on how its cell was found.
+// The entry point fills the first two lines; the loop owns n_iter's target and kept.
+namespace isac {
+struct CancelRecord { int wr, k, status, bin; double nu, power; };   // device, one copy back per pass: the picked cell [window row | k], refine_kernel's and the scan's results
+static_assert(sizeof(CancelRecord) == 32, "the record and [nu | power] are fetched as one block of 32 bytes");
+struct CancelLoop {
+  const char* who; RefinePlan plan; c64* d_R /* [nr x L x A] */; CancelRecord* d_rec; c64* d_snap /* [A x max_iter] */; const unsigned char* d_act /* [L] */; int n_active, span_rows; double merge_tol;
+  int32_t *n_iter, *row, *col, *status, *parent; double *nu, *vel, *power, *azi, *ele /* or NULL */;   // the caller's outputs
+  int kept = 0;
+};
+}
+// entry i = *n_iter at the 1-based cell (row, col): its tone (refine_kernel on d_R), direction, velocity and parent into the outputs, *n_iter = i + 1; then either *stop
+// (status 1: nothing is subtracted) or clean_cancel_kernel enqueued on the window rows *span
+int cancel_pass(isac_ctx* ctx, isac::CancelLoop& s, int row, int col, isac::RowSpan* span, bool* stop);
+// behind the last pass: *n_kept, the first *n_iter snapshots and the residual rows (either may be NULL)
+int cancel_finish(isac_ctx* ctx, const isac::CancelLoop& s, int32_t* n_kept, isac_c64* snapshots, isac_c64* residual_rows);
 // ---------------------------------------------------------------- beam_clean.hip: isac_fft2d_beam_clean_targets (include/isac_beam_clean.h) -- successive cancellation with the detector on beam planes of a
 // residual copy of the range rows of the last completed fft2D; planes, flags and the map over the beams stay on the device across the passes and are updated by row band.  Reads
 // ctx->tgt and ctx->ymid, writes ctx->beam_clean (and ctx->tgt_part through target_scan_snapshots) only; calls rdm_window_enqueue, beam_weight_norms / beam_planes_enqueue,
-// cfar_flag_planes, refine_plan / refine_enqueue, clean_cancel_enqueue and target_scan_snapshots.
+// cfar_flag_planes, symbol_mask, tone_plan and cancel_pass / cancel_finish.
 // ---------------------------------------------------------------- relax.hip: isac_fft2d_relax_targets (include/isac_relax.h) -- joint re-fit of Doppler tones on a residual copy of the range rows of the last
-// completed fft2D.  Reads ctx->tgt and ctx->ymid, writes ctx->relax (and ctx->tgt_part through target_scan_snapshots) only; calls refine_plan, isac_doa2d_grid and target_scan_snapshots.
+// completed fft2D.  Reads ctx->tgt and ctx->ymid, writes ctx->relax (and ctx->tgt_part through target_scan_snapshots) only; calls symbol_mask, tone_plan and target_scan_snapshots.
 // ---------------------------------------------------------------- directions.hip: isac_resolve_directions (include/isac_directions.h) -- off-grid direction finding with several sources per array snapshot.
 // Reads nothing of the context, writes ctx->directions only; calls and is called by no other unit (its steering spacing: upa_steer.hpp).
 // ---------------------------------------------------------------- fft2d.hip: the host side of the fft2D pipeline -- submit, collect, submit_n / collect_n, the host-array call, the getters

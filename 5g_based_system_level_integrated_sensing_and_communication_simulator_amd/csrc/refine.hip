@@ -87,15 +87,26 @@ double dirichlet2(double delta, int L) {
   return d * d;
 }
 
-}  // namespace
-
+// W = max(1/L, 1/nFFT), M = ceil(8 L W) probes a side, and their LDS
 int refine_plan(isac_ctx* ctx, const char* who, RefinePlan* plan) {
   const int A = ctx->tgt.A, L = ctx->tgt.L, n_fft = ctx->tgt.ep.n_fft;
-  const bool wide = n_fft >= L;                                            // W = max(1/L, 1/nFFT), M = ceil(8 L W)
+  const bool wide = n_fft >= L;
   plan->W = wide ? 1.0 / L : 1.0 / n_fft;
   plan->M = wide ? 8 : (8 * L + n_fft - 1) / n_fft;
   plan->lds = sizeof(c64) * ((size_t)(2 * plan->M + 2) * L + A) + sizeof(double) * 2 * (size_t)A;
   if (plan->lds > 160 * 1024) return fail(ctx, ISAC_ERR_UNSUPPORTED, std::string(who) + ": the probe phasors of this many symbols do not fit the LDS");
+  return ISAC_OK;
+}
+
+}  // namespace
+
+int tone_plan(isac_ctx* ctx, const char* who, RefinePlan* plan) {
+  ISAC_TRY(refine_plan(ctx, who, plan));
+  if (ctx->tgt.ep.array_is_upa) {                                          // n_ants_x n_ants_y != A: ISAC_ERR_INVALID_ARG; A > 256: ISAC_ERR_UNSUPPORTED -- before any work
+    const double* d_tab = nullptr;
+    int e_steps = 0, a_steps = 0;
+    ISAC_TRY(isac_doa2d_grid(ctx, &ctx->tgt.ep, ctx->tgt.A, &d_tab, &e_steps, &a_steps));
+  }
   return ISAC_OK;
 }
 
@@ -118,8 +129,7 @@ extern "C" int isac_fft2d_refine_targets(isac_ctx* ctx, const int32_t* row, cons
     return fail(ctx, ISAC_ERR_INVALID_ARG, std::string(who) + ": bad arguments");
   if (!std::isfinite(merge_tol) || merge_tol < 0.0 || !std::isfinite(sidelobe_margin) || sidelobe_margin < 0.0 || merge_rows < 0)
     return fail(ctx, ISAC_ERR_INVALID_ARG, std::string(who) + ": merge_tol, merge_rows and sidelobe_margin must be finite and not negative");
-  if (!ctx->last.valid || ctx->tgt.state != Fft2dCpi::kCollected)       // the rule of isac_fft2d_get_targets
-    return fail(ctx, ISAC_ERR_INVALID_ARG, std::string(who) + ": no completed fft2D on this context whose range rows are still on the device");
+  ISAC_TRY(cpi_ready(ctx, who));
   const Fft2dCpi& ts = ctx->tgt;
   const isac_est_params& ep = ts.ep;
   const CutWindow& w = ts.win;
@@ -136,28 +146,25 @@ extern "C" int isac_fft2d_refine_targets(isac_ctx* ctx, const int32_t* row, cons
   }
   RefinePlan plan;
   ISAC_TRY(refine_plan(ctx, who, &plan));
-  // one scratch block: [row | k | status | scan bin] ints, [nu | power] doubles, the snapshots [A x n]
-  const size_t off_st = sizeof(int) * 2 * (size_t)n, off_bin = off_st + sizeof(int) * (size_t)n, off_nu = (off_bin + sizeof(int) * (size_t)n + 15) & ~(size_t)15;
-  const size_t off_pw = off_nu + sizeof(double) * (size_t)n, off_snap = (off_pw + sizeof(double) * (size_t)n + 15) & ~(size_t)15;
-  ISAC_TRY(ensure(ctx, ctx->refine, off_snap + sizeof(c64) * (size_t)A * n));
+  // one scratch block: [row | k], status, scan bin: ints; nu, power: doubles; the snapshots [A x n]
+  Carver cv;
+  const size_t off_sel = cv.take(sizeof(int) * 2 * (size_t)n), off_st = cv.take(sizeof(int) * (size_t)n), off_bin = cv.take(sizeof(int) * (size_t)n);
+  const size_t off_nu = cv.take(sizeof(double) * (size_t)n), off_pw = cv.take(sizeof(double) * (size_t)n), off_snap = cv.take(sizeof(c64) * (size_t)A * n);
+  ISAC_TRY(ensure(ctx, ctx->refine, cv.total));
   char* d = (char*)ctx->refine.p;
-  ISAC_TRY(stage_upload(ctx, d, sel.data(), sizeof(int) * sel.size()));
-  ISAC_TRY(refine_enqueue(ctx, plan, (const c64*)ctx->ymid.p, (const int*)d, (const int*)d + n, n, (int*)(d + off_st), (double*)(d + off_nu), (double*)(d + off_pw),
-                          (c64*)(d + off_snap)));
+  ISAC_TRY(stage_upload(ctx, d + off_sel, sel.data(), sizeof(int) * sel.size()));
+  ISAC_TRY(refine_enqueue(ctx, plan, (const c64*)ctx->ymid.p, (const int*)(d + off_sel), (const int*)(d + off_sel) + n, n, (int*)(d + off_st), (double*)(d + off_nu),
+                          (double*)(d + off_pw), (c64*)(d + off_snap)));
   ISAC_TRY(target_scan_snapshots(ctx, (const c64*)(d + off_snap), n, (int*)(d + off_bin), azi, ele));
   ISAC_TRY(copy_d2h(ctx, status, d + off_st, sizeof(int) * (size_t)n));
   ISAC_TRY(copy_d2h(ctx, nu, d + off_nu, sizeof(double) * (size_t)n));
   ISAC_TRY(copy_d2h(ctx, power, d + off_pw, sizeof(double) * (size_t)n));
   if (snapshots) ISAC_TRY(copy_d2h(ctx, snapshots, d + off_snap, sizeof(c64) * (size_t)A * n));
   for (int i = 0; i < n; ++i) vel[i] = status[i] == 0 ? nu[i] * n_fft * ep.v_res : CutWindow::velocity_of(col[i], ep);
-  // ---- step 4: in input order, the first earlier kept entry within merge_rows rows and merge_tol / L of nu absorbs (merge_tol == 0: nothing is merged -- two lobes of one
-  // tone can bisect to the very same bits, and a tolerance of zero must not depend on that)
+  // ---- step 4: in input order, the first earlier kept entry with status 0 within merge_rows rows and merge_tol / L of nu absorbs (merge_parent, cpi_post.hpp)
   for (int i = 0; i < n; ++i) {
-    parent[i] = i;
+    parent[i] = status[i] != 0 ? i : merge_parent(i, row, nu, parent, status, merge_rows, merge_tol, L);
     sidelobe_of[i] = -1;
-    if (status[i] != 0 || merge_tol == 0.0) continue;
-    for (int k = 0; k < i; ++k)
-      if (parent[k] == k && status[k] == 0 && std::abs(row[i] - row[k]) <= merge_rows && std::fabs(nu[i] - nu[k]) * L <= merge_tol) { parent[i] = k; break; }
   }
   // ---- step 5: a kept entry that a stronger kept entry's Doppler response explains is flagged
   int kept = 0;

@@ -1,5 +1,6 @@
 // The evaluation refine_kernel (refine.hip), clean_cancel_kernel (clean.hip) and the two kernels of relax.hip share: X_a(nu) = sum_l y[l, a] e^{-2 pi j nu l} of one range
-// row for every antenna, with the phasors of nu in LDS.  In ONE place so that the tone a cancellation fits is the sum the refinement maximised, bit for bit.
+// row for every antenna, with the phasors of nu in LDS.  In ONE place so that the tone a cancellation fits is the sum the refinement maximised, bit for bit.  And what a
+// cancellation does with it: the phasors that are zero at the inactive symbols (tone_phasors), the least-squares fit and its subtraction from the row (tone_fit_subtract).
 #pragma once
 #include "isac_common.hpp"
 
@@ -52,6 +53,31 @@ __device__ __forceinline__ RefineSums refine_eval(const c64* __restrict__ row /*
   for (int a = 0; a < A; ++a) { r.p += s_p[a]; r.d += s_d[a]; }           // ascending antenna order from 0.0; every lane the same address: broadcasts
   __syncthreads();
   return r;
+}
+
+// p_nu [L] into s (LDS): e^{-2 pi j nu l}, one sincos of the full argument each, 0 where the symbol is inactive -- a sum over all symbols is then the sum over the active
+// ones.  The caller places the barrier.
+__device__ __forceinline__ void tone_phasors(c64* s, double nu, int L, const unsigned char* __restrict__ active) {
+  for (int l = threadIdx.x; l < L; l += 256) s[l] = active[l] ? refine_phasor(nu, l) : mk(0.0, 0.0);
+}
+
+// Step 8 of include/isac_clean.h on one row, by one workgroup of 256 threads: refine_eval<AddBack> with the masked phasors s_ph leaves s_x[a] = X_a summed over the active
+// symbols; thread i then rewrites sample (l, a) = (i % L, i / L) of the row, read and written at stride nr, the inactive symbols untouched:
+//   plain    y - c conj(p),                               c = X_a / n_active
+//   AddBack  (y + C conj(p_old)) - c_new conj(p_new),     C = c_back[a], p_old = s_back: the tone this row held is restored, fitted anew and subtracted in one pass
+// s_x stays valid on return (relax_refit_kernel stores the new C from it); no barrier behind the subtraction.
+template <bool AddBack>
+__device__ __forceinline__ void tone_fit_subtract(c64* row, int nr, int L, int A, const unsigned char* __restrict__ active, double n_active, const c64* s_ph, c64* s_x,
+                                                  double* s_p, double* s_d, const c64* s_back = nullptr, const c64* c_back = nullptr) {
+  (void)refine_eval<AddBack>(row, nr, L, A, s_ph, s_x, s_p, s_d, s_back, c_back);   // ends with a barrier: every read of the row is done
+  for (int i = threadIdx.x; i < L * A; i += 256) {
+    const int l = i % L, a = i / L;
+    if (!active[l]) continue;
+    const c64 c = mk(s_x[a].re / n_active, s_x[a].im / n_active);
+    c64* y = row + (long long)nr * (l + (long long)L * a);
+    if constexpr (AddBack) *y = (*y + c_back[a] * conj(s_back[l])) - c * conj(s_ph[l]);
+    else *y = *y - c * conj(s_ph[l]);
+  }
 }
 
 }  // namespace isac

@@ -4,8 +4,8 @@
 //   1  `cycles` times, in input order: (a, b) relax_nu_kernel: the zero of P' of the centre row with tone j restored, inside nu_j +- box / L; (c) relax_refit_kernel: on every
 //      row of the span, restore tone j at its old frequency, fit it at the new one, subtract it -- one read-modify-write of the row
 //   2  relax_out_kernel: power and snapshot from C_j on the centre row; direction: target_scan_snapshots (targets.hip)
-// Step 0 IS relax_refit_kernel with C = 0 and old = new frequency: y + 0 conj(p) = y, so the fit and the subtraction are clean_cancel_kernel's.
-// Both kernels evaluate through refine_eval<true> (refine_dev.hpp): the thread map and the order of summation of refine_kernel, the sample being y + C conj(p_old) formed
+// Step 0 IS relax_refit_kernel with C = 0 and old = new frequency: y + 0 conj(p) = y, so the fit and the subtraction are clean_cancel_kernel's -- both are
+// tone_fit_subtract (refine_dev.hpp), which differs between them only as refine_eval<AddBack> does.  Both kernels evaluate through refine_eval<true> (refine_dev.hpp): the thread map and the order of summation of refine_kernel, the sample being y + C conj(p_old) formed
 // on the fly.  relax_nu_kernel: one workgroup of 256 threads per entry, reads only, writes nu_new (and keeps nu_old beside it for the re-fit).  relax_refit_kernel: one
 // workgroup per row of the span, as clean_cancel_kernel is laid out; a workgroup owns its row and its C_j row.
 // Entries whose spans overlap (transitively) form a cluster; clusters share no row.  blockIdx.y runs over the clusters and one launch pair handles the k-th entry (input
@@ -29,10 +29,6 @@ struct RelaxLds {                                                         // the
   static size_t bytes(int L, int A) { return sizeof(c64) * (2 * (size_t)L + A) + sizeof(double) * 2 * (size_t)A; }
 };
 
-__device__ __forceinline__ void relax_phasors(c64* s, double nu, int L, const unsigned char* __restrict__ active) {   // p_nu [L]; the caller places the barrier
-  for (int l = threadIdx.x; l < L; l += 256) s[l] = active[l] ? refine_phasor(nu, l) : mk(0.0, 0.0);
-}
-
 // sched [n_clusters x max_len]: the entries of cluster blockIdx.y in input order, -1 behind the last
 __global__ __launch_bounds__(256) void relax_nu_kernel(const c64* __restrict__ R /* [nr x L x A] */, int nr, int L, int A, int S, const int* __restrict__ sched, int max_len, int k,
                                                        const int* __restrict__ wr /* centre window row, 0-based */, const int* __restrict__ lo /* first window row of the span */,
@@ -47,11 +43,11 @@ __global__ __launch_bounds__(256) void relax_nu_kernel(const c64* __restrict__ R
   const c64* c_row = C + ((size_t)j * S + (wr[j] - lo[j])) * A;
   const double nu_j = nu[j];
   auto dp_at = [&](double v) {                                            // the sign carrier of P_j'(v)
-    relax_phasors(s.ph, v, L, active);
+    tone_phasors(s.ph, v, L, active);
     __syncthreads();
     return refine_eval<true>(row, nr, L, A, s.ph, s.x, s.p, s.d, s.back, c_row).d;
   };
-  relax_phasors(s.back, nu_j, L, active);                                 // (the barrier of the first dp_at covers it)
+  tone_phasors(s.back, nu_j, L, active);                                 // (the barrier of the first dp_at covers it)
   const double d_lo = dp_at(nu_j - h), d_hi = dp_at(nu_j + h);
   const bool ok = d_lo > 0.0 && d_hi < 0.0;                               // NaN and an all-zero row: never
   double a = nu_j, b = nu_j;                                              // no bracket: the loop leaves them there
@@ -78,17 +74,10 @@ __global__ __launch_bounds__(256) void relax_refit_kernel(c64* R /* [nr x L x A]
   const int tid = threadIdx.x;
   c64* row = R + lo[j] + blockIdx.x;                                      // (the host clips the span to 0 .. nr - 1)
   c64* c_row = C + ((size_t)j * S + blockIdx.x) * A;
-  relax_phasors(s.back, nu_prev[j], L, active);
-  relax_phasors(s.ph, nu[j], L, active);
+  tone_phasors(s.back, nu_prev[j], L, active);
+  tone_phasors(s.ph, nu[j], L, active);
   __syncthreads();
-  (void)refine_eval<true>(row, nr, L, A, s.ph, s.x, s.p, s.d, s.back, c_row);   // s.x[a] = sum over the active symbols of (y + C conj(p_old)) p_new; ends with a barrier
-  for (int i = tid; i < L * A; i += 256) {
-    const int l = i % L, a = i / L;
-    if (!active[l]) continue;
-    const c64 c_new = mk(s.x[a].re / n_active, s.x[a].im / n_active);
-    c64* y = row + (long long)nr * (l + (long long)L * a);
-    *y = (*y + c_row[a] * conj(s.back[l])) - c_new * conj(s.ph[l]);
-  }
+  tone_fit_subtract<true>(row, nr, L, A, active, n_active, s.ph, s.x, s.p, s.d, s.back, c_row);   // s.x[a] = sum over the active symbols of (y + C conj(p_old)) p_new
   __syncthreads();                                                        // every read of the old C_j row is done
   for (int a = tid; a < A; a += 256) c_row[a] = mk(s.x[a].re / n_active, s.x[a].im / n_active);
 }
@@ -126,8 +115,7 @@ extern "C" int isac_fft2d_relax_targets(isac_ctx* ctx, const int32_t* row, const
     return fail(ctx, ISAC_ERR_INVALID_ARG, std::string(who) + ": cycles must lie in 0..64, span_rows must not be negative, box must lie in (0, 2]");
   for (int i = 0; i < n; ++i)
     if (!std::isfinite(nu_in[i])) return fail(ctx, ISAC_ERR_INVALID_ARG, std::string(who) + ": a frequency that is not finite");
-  if (!ctx->last.valid || ctx->tgt.state != Fft2dCpi::kCollected)       // the rule of isac_fft2d_get_targets
-    return fail(ctx, ISAC_ERR_INVALID_ARG, std::string(who) + ": no completed fft2D on this context whose range rows are still on the device");
+  ISAC_TRY(cpi_ready(ctx, who));
   const Fft2dCpi& ts = ctx->tgt;
   const isac_est_params& ep = ts.ep;
   const CutWindow& w = ts.win;
@@ -135,32 +123,24 @@ extern "C" int isac_fft2d_relax_targets(isac_ctx* ctx, const int32_t* row, const
   if (ep.array_is_upa && n > 0 && !ele) return fail(ctx, ISAC_ERR_INVALID_ARG, std::string(who) + ": a planar array needs ele");
   for (int i = 0; i < n; ++i)
     if (row[i] < w.row0 || row[i] >= w.row0 + w.n_cut_rows) return fail(ctx, ISAC_ERR_INVALID_ARG, std::string(who) + ": a row outside the CUT zone of the CPI");
-  std::vector<unsigned char> act((size_t)L, 1);
-  int n_active = L;
-  if (sym_active) {
-    n_active = 0;
-    for (int l = 0; l < L; ++l) { act[(size_t)l] = sym_active[l] ? 1 : 0; n_active += act[(size_t)l]; }
-    if (n_active == 0) return fail(ctx, ISAC_ERR_INVALID_ARG, std::string(who) + ": sym_active names no active symbol");
-  }
+  SymbolMask mask;
+  ISAC_TRY(symbol_mask(ctx, who, sym_active, L, &mask));
+  const int n_active = mask.n_active;
   const size_t n_rows_el = (size_t)w.nr * L * A;
   if (n == 0) {                                                            // nothing to fit: R is the copy of the range rows
     if (residual_rows) ISAC_TRY(copy_d2h(ctx, residual_rows, ctx->ymid.p, sizeof(c64) * n_rows_el));
     return ISAC_OK;
   }
   RefinePlan plan;
-  ISAC_TRY(refine_plan(ctx, who, &plan));                                  // the LDS refusal of the refinement; both kernels here need less (2 L + A values against (2 M + 2) L + A, M >= 8)
-  if (ep.array_is_upa) {                                                   // n_ants_x n_ants_y != A: ISAC_ERR_INVALID_ARG; A > 256: ISAC_ERR_UNSUPPORTED -- before any work
-    const double* d_tab = nullptr;
-    int e_steps = 0, a_steps = 0;
-    ISAC_TRY(isac_doa2d_grid(ctx, &ep, A, &d_tab, &e_steps, &a_steps));
-  }
+  ISAC_TRY(tone_plan(ctx, who, &plan));                                    // the LDS refusal of the refinement; both kernels here need less (2 L + A values against (2 M + 2) L + A, M >= 8)
   // ---- spans and clusters: entries whose spans share a row, transitively; the k-th entry (input order) of every cluster goes into launch pair k
   std::vector<int> wr((size_t)n), lo((size_t)n), len((size_t)n), cl((size_t)n);
   int S = 1;
   for (int i = 0; i < n; ++i) {
     wr[(size_t)i] = row[i] - w.first_row;                                  // 0 <= wr < nr: a CUT row of the window
-    lo[(size_t)i] = (int)std::max<long long>((long long)wr[(size_t)i] - span_rows, 0);
-    len[(size_t)i] = (int)std::min<long long>((long long)wr[(size_t)i] + span_rows, w.nr - 1) - lo[(size_t)i] + 1;
+    const RowSpan sp = span_of(wr[(size_t)i], span_rows, w.nr);
+    lo[(size_t)i] = sp.lo;
+    len[(size_t)i] = sp.len();
     S = std::max(S, len[(size_t)i]);
     cl[(size_t)i] = i;
   }
@@ -184,15 +164,16 @@ extern "C" int isac_fft2d_relax_targets(isac_ctx* ctx, const int32_t* row, const
   for (int c = 0; c < n_cl; ++c)
     for (size_t k = 0; k < members[(size_t)c].size(); ++k) sched[(size_t)c * max_len + k] = members[(size_t)c][k];
   // ---- one scratch block: [R nr L A | C n S A | snapshots A n] c64, [nu | nu_prev | power] doubles, [wr | lo | len | flag | scan bin | sched] ints, the symbol mask [L]
-  const size_t off_c = sizeof(c64) * n_rows_el, off_snap = off_c + sizeof(c64) * (size_t)n * S * A, off_nu = off_snap + sizeof(c64) * (size_t)A * n;
-  const size_t off_int = off_nu + sizeof(double) * 3 * (size_t)n, n_int = 5 * (size_t)n + sched.size(), off_act = off_int + sizeof(int) * n_int;
-  ISAC_TRY(ensure(ctx, ctx->relax, off_act + (size_t)L));
+  Carver cv;
+  const size_t off_r = cv.take(sizeof(c64) * n_rows_el), off_c = cv.take(sizeof(c64) * (size_t)n * S * A), off_snap = cv.take(sizeof(c64) * (size_t)A * n);
+  const size_t off_nu = cv.take(sizeof(double) * 3 * (size_t)n), off_int = cv.take(sizeof(int) * (5 * (size_t)n + sched.size())), off_act = cv.take((size_t)L);
+  ISAC_TRY(ensure(ctx, ctx->relax, cv.total));
   char* d = (char*)ctx->relax.p;
-  c64 *d_R = (c64*)d, *d_C = (c64*)(d + off_c), *d_snap = (c64*)(d + off_snap);
+  c64 *d_R = (c64*)(d + off_r), *d_C = (c64*)(d + off_c), *d_snap = (c64*)(d + off_snap);
   double *d_nu = (double*)(d + off_nu), *d_prev = d_nu + n, *d_pow = d_prev + n;
   int *d_wr = (int*)(d + off_int), *d_lo = d_wr + n, *d_len = d_lo + n, *d_flag = d_len + n, *d_bin = d_flag + n, *d_sched = d_bin + n;
   const unsigned char* d_act = (const unsigned char*)(d + off_act);
-  std::vector<char> meta(off_act + (size_t)L - off_nu, 0);                 // (power, flag and scan bin start as zeros)
+  std::vector<char> meta(cv.total - off_nu, 0);                            // everything behind the snapshots in one upload (power, flag and scan bin start as zeros)
   std::memcpy(meta.data(), nu_in, sizeof(double) * (size_t)n);
   std::memcpy(meta.data() + sizeof(double) * (size_t)n, nu_in, sizeof(double) * (size_t)n);
   int* m_int = (int*)(meta.data() + (off_int - off_nu));
@@ -200,11 +181,11 @@ extern "C" int isac_fft2d_relax_targets(isac_ctx* ctx, const int32_t* row, const
   std::memcpy(m_int + n, lo.data(), sizeof(int) * (size_t)n);
   std::memcpy(m_int + 2 * (size_t)n, len.data(), sizeof(int) * (size_t)n);
   std::memcpy(m_int + 5 * (size_t)n, sched.data(), sizeof(int) * sched.size());
-  std::memcpy(meta.data() + (off_act - off_nu), act.data(), (size_t)L);
+  std::memcpy(meta.data() + (off_act - off_nu), mask.act.data(), (size_t)L);
   ISAC_HIP(hipMemcpyAsync(d_R, ctx->ymid.p, sizeof(c64) * n_rows_el, hipMemcpyDeviceToDevice, ctx->stream));
   ISAC_HIP(hipMemsetAsync(d_C, 0, sizeof(c64) * (size_t)n * S * A, ctx->stream));
   ISAC_TRY(copy_h2d(ctx, d + off_nu, meta.data(), meta.size()));
-  const size_t lds = RelaxLds::bytes(L, A);                                // (<= the refinement's, which refine_plan has bounded by 160 KB)
+  const size_t lds = RelaxLds::bytes(L, A);                                // (<= the refinement's, which tone_plan has bounded by 160 KB)
   ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(relax_nu_kernel), lds));
   ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(relax_refit_kernel), lds));
   const double h = box / (double)L;

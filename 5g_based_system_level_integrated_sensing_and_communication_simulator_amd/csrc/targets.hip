@@ -291,7 +291,7 @@ int select_cells(isac_ctx* ctx, const char* who, const PlaneCells& src, isac_tar
   const isac_est_params& ep = ts.ep;
   const CutWindow& w = ts.win;
   const int hr = w.hr, hc = w.hc;
-  if (hr < 1 || hc < 1) return fail(ctx, ISAC_ERR_UNSUPPORTED, std::string(who) + ": the local-maximum test needs a halo of at least one cell (guard + training) in both dimensions");
+  ISAC_TRY(needs_halo(ctx, who));
   const int A = ts.A, nr = w.nr, nc = w.nc, n_cut_rows = w.n_cut_rows, n_cut_cols = w.n_cut_cols, n_cut = (int)w.n_cut();
   if (sc) *sc = SelectedCells{};
   std::memset(out, 0, sizeof(*out));

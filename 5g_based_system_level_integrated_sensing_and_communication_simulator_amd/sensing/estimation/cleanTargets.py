@@ -8,6 +8,7 @@ import numpy as np
 
 from ... import _lib as L
 from ..detection.cfarDetect import method_block
+from ._cpi_post import add_optional, cpi_dims, kept_entries, ptr as p, symbol_count, symbol_mask
 
 
 def cleanTargets(ctx, maxIter=16, spanRows=2, mergeTol=0.5, Method="CA", Rank=1, ThresholdFactor="Auto", CustomThresholdFactor=None, symActive=None, snapshots=False,
@@ -37,51 +38,20 @@ def cleanTargets(ctx, maxIter=16, spanRows=2, mergeTol=0.5, Method="CA", Rank=1,
     lib = ctx.lib
     m = method_block(Method, Rank, ThresholdFactor, CustomThresholdFactor)
     n_max = int(maxIter)
-    dims = (C.c_int32 * 3)()
-    ctx.check(lib.isac_fft2d_get_power_window(ctx.handle, None, 0, dims, None, None))
-    nr, A = int(dims[0]), int(dims[2])
+    nr, _, A = cpi_dims(ctx)
     cap = min(max(n_max, 1), L.ISAC_MAX_TARGETS)
     row, col, hits, status, parent = (np.zeros(cap, dtype=np.int32) for _ in range(5))
     map_power, nu, vel, rng, power, azi = (np.zeros(cap, dtype=np.float64) for _ in range(6))
     ele = np.full(cap, np.nan)
-    act = None
-    if symActive is not None:
-        act = np.ascontiguousarray(np.asarray(symActive).ravel() != 0, dtype=np.uint8)
+    act = symbol_mask(symActive)
     snap = np.zeros((A, cap), dtype=np.complex128, order="F") if snapshots else None
-    res_rows = None
-    shape = getattr(ctx, "fft2d_grid_shape", None)                         # (K, L, A) of the last sensing.estimation.fft2D / fft2D_submit on this context
-    n_sym = int(shape[1]) if shape is not None and int(shape[2]) == A else None
-    if nSymbols is not None:
-        if n_sym is not None and int(nSymbols) != n_sym:
-            raise ValueError(f"nSymbols = {int(nSymbols)}, but the CPI on this context has {n_sym} symbols")
-        n_sym = int(nSymbols)
-    if (act is not None or residual) and n_sym is None:
-        raise ValueError("symActive and residual need the CPI's symbol count: this context ran no sensing.estimation.fft2D, pass nSymbols")
-    if act is not None and act.size != n_sym:
-        raise ValueError(f"symActive needs one entry per symbol of the CPI ({n_sym})")
-    if residual:
-        res_rows = np.zeros((nr, n_sym, A), dtype=np.complex128, order="F")
+    n_sym = symbol_count(ctx, A, nSymbols, act, residual)
+    res_rows = np.zeros((nr, n_sym, A), dtype=np.complex128, order="F") if residual else None
     n_iter, n_kept, n_left = C.c_int32(0), C.c_int32(0), C.c_int32(0)
-    p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)     # noqa: E731
     ctx.check(lib.isac_fft2d_clean_targets(ctx.handle, C.byref(m), n_max, int(spanRows), float(mergeTol), p(act), C.byref(n_iter), C.byref(n_kept), C.byref(n_left), p(row), p(col),
                                            p(hits), p(status), p(parent), p(map_power), p(nu), p(vel), p(rng), p(power), p(azi), p(ele), p(snap), p(res_rows)))
     n = int(n_iter.value)
-    parent = parent[:n]
-    kept = np.flatnonzero(parent == np.arange(n))
-    assert kept.size == int(n_kept.value)
-    out_of_in = np.full(n, -1, dtype=np.int32)
-    out_of_in[kept] = np.arange(kept.size, dtype=np.int32)
-    res = {"rng": rng[:n][kept], "vel": vel[:n][kept], "azi": azi[:n][kept], "power": power[:n][kept], "hits": hits[:n][kept], "row": row[:n][kept], "col": col[:n][kept],
-           "n_total": n, "nu": nu[:n][kept], "status": status[:n][kept], "parent": out_of_in[parent[kept]],
-           "n_merged": np.bincount(parent, minlength=n)[kept].astype(np.int32) if n else np.zeros(0, dtype=np.int32), "map_power": map_power[:n][kept],
-           "n_left": int(n_left.value)}
-    rp = getattr(ctx, "fft2d_radar_params", None)                          # the array type, where the context knows it; else: the library writes ele for a planar array only
-    kind = getattr(rp.get("antennaType") if isinstance(rp, dict) else getattr(rp, "antennaType", None), "kind", None)
-    upa = kind == "upa" if rp is not None else not np.isnan(ele[:n]).all()
-    if upa:
-        res["ele"] = ele[:n][kept]
-    if snap is not None:
-        res["snapshots"] = np.asfortranarray(snap[:, :n][:, kept])
-    if res_rows is not None:
-        res["residual"] = res_rows
+    res, kept = kept_entries(n, int(n_kept.value), int(n_left.value), dict(rng=rng, vel=vel, azi=azi, power=power, hits=hits, row=row, col=col, nu=nu, status=status,
+                                                                           parent=parent, map_power=map_power))
+    add_optional(res, ctx, ele, n, kept, snap, res_rows)
     return res

@@ -8,6 +8,7 @@ import numpy as np
 
 from ... import _lib as L
 from ..detection.cfarDetect import method_block
+from ._cpi_post import cpi_dims
 from .doaEstimation.music import music
 
 
@@ -23,9 +24,7 @@ def redetect(ctx, Method="CA", Rank=1, ThresholdFactor="Auto", CustomThresholdFa
     if radarEstParams is None:
         raise ValueError("redetect: this context has run no fft2D through sensing.estimation.fft2D; pass radarEstParams")
     m = method_block(Method, Rank, ThresholdFactor, CustomThresholdFactor)
-    dims = (C.c_int32 * 3)()
-    ctx.check(lib.isac_fft2d_get_power_window(ctx.handle, None, 0, dims, None, None))
-    A = int(dims[2])
+    A = cpi_dims(ctx)[2]
     res = L.EstResult()
     off = np.zeros(A + 1, dtype=np.int32)
     n_total = C.c_int32(0)

@@ -6,7 +6,7 @@ import ctypes as C
 
 import numpy as np
 
-from ... import _lib as L
+from ._cpi_post import cpi_dims
 
 
 def refineTargets(ctx, tl, mergeTol=0.5, mergeRows=1, sidelobeMargin=2.0, snapshots=False):
@@ -31,9 +31,7 @@ def refineTargets(ctx, tl, mergeTol=0.5, mergeRows=1, sidelobeMargin=2.0, snapsh
     if row.size != col.size:
         raise ValueError("row and col must have one entry per cell")
     n = int(row.size)
-    dims = (C.c_int32 * 3)()
-    ctx.check(lib.isac_fft2d_get_power_window(ctx.handle, None, 0, dims, None, None))
-    A = int(dims[2])
+    A = cpi_dims(ctx)[2]
     m = max(n, 1)
     status, parent, side = (np.zeros(m, dtype=np.int32) for _ in range(3))
     nu, vel, power, azi = (np.zeros(m, dtype=np.float64) for _ in range(4))

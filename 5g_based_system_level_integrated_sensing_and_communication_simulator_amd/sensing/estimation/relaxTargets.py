@@ -2,9 +2,9 @@
 include/isac_relax.h, isac_fft2d_relax_targets)."""
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
+
+from ._cpi_post import add_optional, cpi_dims, ptr as p, symbol_count, symbol_mask
 
 
 def relaxTargets(ctx, cl, cycles=16, spanRows=2, box=0.5, symActive=None, snapshots=False, residual=False, nSymbols=None):
@@ -30,31 +30,15 @@ def relaxTargets(ctx, cl, cycles=16, spanRows=2, box=0.5, symActive=None, snapsh
     if row.size != nu_in.size:
         raise ValueError("row and nu need one entry per target")
     n = int(row.size)
-    dims = (C.c_int32 * 3)()
-    ctx.check(lib.isac_fft2d_get_power_window(ctx.handle, None, 0, dims, None, None))
-    nr, A = int(dims[0]), int(dims[2])
+    nr, _, A = cpi_dims(ctx)
     cap = max(n, 1)
     status = np.zeros(cap, dtype=np.int32)
     nu, vel, power, shift, last_step, azi = (np.zeros(cap, dtype=np.float64) for _ in range(6))
     ele = np.full(cap, np.nan)
-    act = None
-    if symActive is not None:
-        act = np.ascontiguousarray(np.asarray(symActive).ravel() != 0, dtype=np.uint8)
+    act = symbol_mask(symActive)
     snap = np.zeros((A, cap), dtype=np.complex128, order="F") if snapshots else None
-    res_rows = None
-    shape = getattr(ctx, "fft2d_grid_shape", None)                         # (K, L, A) of the last sensing.estimation.fft2D / fft2D_submit on this context
-    n_sym = int(shape[1]) if shape is not None and int(shape[2]) == A else None
-    if nSymbols is not None:
-        if n_sym is not None and int(nSymbols) != n_sym:
-            raise ValueError(f"nSymbols = {int(nSymbols)}, but the CPI on this context has {n_sym} symbols")
-        n_sym = int(nSymbols)
-    if (act is not None or residual) and n_sym is None:
-        raise ValueError("symActive and residual need the CPI's symbol count: this context ran no sensing.estimation.fft2D, pass nSymbols")
-    if act is not None and act.size != n_sym:
-        raise ValueError(f"symActive needs one entry per symbol of the CPI ({n_sym})")
-    if residual:
-        res_rows = np.zeros((nr, n_sym, A), dtype=np.complex128, order="F")
-    p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)     # noqa: E731
+    n_sym = symbol_count(ctx, A, nSymbols, act, residual)
+    res_rows = np.zeros((nr, n_sym, A), dtype=np.complex128, order="F") if residual else None
     ctx.check(lib.isac_fft2d_relax_targets(ctx.handle, p(row), p(nu_in), n, int(cycles), int(spanRows), float(box), p(act), p(status), p(nu), p(vel), p(power), p(shift),
                                            p(last_step), p(azi), p(ele), p(snap), p(res_rows)))
     rng = get("rng")
@@ -62,13 +46,5 @@ def relaxTargets(ctx, cl, cycles=16, spanRows=2, box=0.5, symActive=None, snapsh
            "nu": nu[:n], "status": status[:n], "shift": shift[:n], "last_step": last_step[:n]}
     if get("col") is not None:
         res["col"] = np.array(np.asarray(get("col")).ravel(), dtype=np.int32)
-    rp = getattr(ctx, "fft2d_radar_params", None)                          # the array type, where the context knows it; else: the library writes ele for a planar array only
-    kind = getattr(rp.get("antennaType") if isinstance(rp, dict) else getattr(rp, "antennaType", None), "kind", None)
-    upa = kind == "upa" if rp is not None else not np.isnan(ele[:n]).all()
-    if upa:
-        res["ele"] = ele[:n]
-    if snap is not None:
-        res["snapshots"] = np.asfortranarray(snap[:, :n])
-    if res_rows is not None:
-        res["residual"] = res_rows
+    add_optional(res, ctx, ele, n, slice(None), snap, res_rows)
     return res
