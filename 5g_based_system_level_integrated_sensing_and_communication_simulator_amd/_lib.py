@@ -282,6 +282,11 @@ PROTOTYPES_MULTISTATIC = {
     "isac_multi_static_channel_dev": (_INT, _MULTISTATIC_ARGS + (_P,)),
     "isac_multi_static_sensing_dev": (_INT, _MULTISTATIC_ARGS + (_I32, _ptr(Carrier), _P, _P)),
 }
+# ... and include/isac_cancel_paths.h (tests/test_cancel_cpu.py pins it)
+ISAC_CANCEL_PATHS_MAX_REFS = 32
+PROTOTYPES_CANCEL_PATHS = {
+    "isac_cancel_paths_dev": (_INT, (_P, _P, _P, _I32, _I64, _F64, _F64, _I32, _I32, _P, _P, _P, _P, _F64, _P, _P, _P, _P, _P)),
+}
 
 
 def library_path() -> str:
@@ -308,7 +313,7 @@ def load():
             except Exception:
                 pass
         lib = C.CDLL(_LIB_PATH, mode=C.RTLD_GLOBAL)
-        for name, (restype, argtypes) in {**PROTOTYPES, **PROTOTYPES_ADDED, **PROTOTYPES_CFAR, **PROTOTYPES_CFAR_MC, **PROTOTYPES_LAZY_COV, **PROTOTYPES_TARGETS_UPA, **PROTOTYPES_BEAMS, **PROTOTYPES_REFINE, **PROTOTYPES_CLEAN, **PROTOTYPES_RELAX, **PROTOTYPES_DIRECTIONS, **PROTOTYPES_BEAM_CLEAN, **PROTOTYPES_MULTISTATIC}.items():
+        for name, (restype, argtypes) in {**PROTOTYPES, **PROTOTYPES_ADDED, **PROTOTYPES_CFAR, **PROTOTYPES_CFAR_MC, **PROTOTYPES_LAZY_COV, **PROTOTYPES_TARGETS_UPA, **PROTOTYPES_BEAMS, **PROTOTYPES_REFINE, **PROTOTYPES_CLEAN, **PROTOTYPES_RELAX, **PROTOTYPES_DIRECTIONS, **PROTOTYPES_BEAM_CLEAN, **PROTOTYPES_MULTISTATIC, **PROTOTYPES_CANCEL_PATHS}.items():
             fn = getattr(lib, name)  # AttributeError here = ABI drift between isac.h and the .so
             fn.restype, fn.argtypes = restype, argtypes
         # the library writes whole structs into caller memory: version AND struct sizes must match this binding's mirrors

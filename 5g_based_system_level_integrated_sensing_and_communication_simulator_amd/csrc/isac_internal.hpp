@@ -152,6 +152,9 @@ struct PathCoefJob {
   const isac_c64* path_tx_steering; const isac_c64* path_rx_steering;
 };
 int isac_path_coefs_on(isac_ctx* ctx, hipStream_t st, const PathCoefJob& j);   // coef [P x T] -> ctx->coef, phase_rx [T] -> ctx->phase_rx, rx steering [A x P] and its transpose -> ctx->steer
+// ---------------------------------------------------------------- cancel_paths.hip: isac_cancel_paths_dev (include/isac_cancel_paths.h) -- known reference signals projected out of a received waveform.  Calls
+// isac_path_coefs_on (unit gains, one receive element: the reference columns R [M x T] in ctx->coef; ctx->steer and ctx->phase_rx are rewritten with them) and is called by no
+// other unit; its own scratch is ctx->cancel_paths.
 // ---------------------------------------------------------------- eigh.hip (the device code it shares with music.hip: eigh_dev.hpp)
 // device eig: H [A x A] (device) -> ctx->eig_w [A], ctx->eig_v [A x A] (unsorted); live_replay: see the definition
 int isac_eigh_dev(isac_ctx* ctx, const isac::c64* d_H, int A, hipStream_t st, bool live_replay = true);

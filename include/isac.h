@@ -679,5 +679,6 @@ int isac_synth_qpsk_grid_dev(isac_ctx* ctx, isac_c64* d_grid, int32_t K, int32_t
 #include "isac_directions.h"  /* isac_resolve_directions: off-grid direction finding with several sources per array snapshot (greedy search + RELAX): additive under ABI 8 */
 #include "isac_beam_clean.h"  /* isac_fft2d_beam_clean_targets: successive target cancellation (CLEAN) with the detector on beam planes of the last fft2D: additive under ABI 8 */
 #include "isac_multistatic.h"  /* isac_multi_static_channel_dev / isac_multi_static_sensing_dev: echo synthesis with paths from other cells' transmitters: additive under ABI 8 */
+#include "isac_cancel_paths.h"  /* isac_cancel_paths_dev: known reference signals projected out of a received waveform (ECA): additive under ABI 8 */
 
 #endif /* ISAC_H */
