@@ -127,166 +127,163 @@ class CfarMethod(C.Structure):
     _fields_ = [("method", C.c_int32), ("rank", C.c_int32), ("custom_factor", C.c_double)]
 
 
-# The structs isac_abi_sizeof() knows, in ISAC_SIZEOF_* index order: (C name, mirror).  load() compares every size with the library's.
+# The structs isac_abi_sizeof() knows: (C name, mirror), the position being the selector.  0 .. 10 are the ISAC_SIZEOF_* enumerators of include/isac.h, 11 is
+# ISAC_SIZEOF_TARGET_LIST (include/isac_targets.h), 12 is ISAC_SIZEOF_CFAR_METHOD (include/isac_cfar.h).  load() compares every size with the library's.
 ABI_STRUCTS = (("isac_est_result", EstResult), ("isac_est_params", EstParams), ("isac_cfar_config", CfarConfig),
                ("isac_radar_channel_params", RadarChannelParams), ("isac_carrier", Carrier), ("isac_music2d_params", Music2dParams),
                ("isac_csi_report", CsiReport), ("isac_sensing_job", SensingJob), ("isac_srs_report", SrsReport),
-               ("isac_rx_frontend_job", RxFrontendJob), ("isac_path_loss_config", PathLossConfig))
-# ... and the ones the additive headers add (include/isac_targets.h): (selector, C name, mirror)
-ABI_STRUCTS_ADDED = ((11, "isac_target_list", TargetList),)
-ABI_STRUCTS_CFAR = ((12, "isac_cfar_method", CfarMethod),)      # include/isac_cfar.h
+               ("isac_rx_frontend_job", RxFrontendJob), ("isac_path_loss_config", PathLossConfig), ("isac_target_list", TargetList),
+               ("isac_cfar_method", CfarMethod))
 
-# Every function include/isac.h declares, in the header's order: name -> (restype, argtypes).  load() sets both, so a call with a missing
-# argument (TypeError) or a float for an integer (ctypes.ArgumentError) fails instead of reaching the library, a 64-bit value arrives whole,
-# and call sites pass plain Python numbers, DeviceArrays and None.  ONE typing rule, no exceptions (tests/test_abi_cpu.py re-derives it from the header):
+# Limits of the additive headers (include/isac_relax.h, isac_directions.h, isac_multistatic.h, isac_cancel_paths.h)
+ISAC_RELAX_MAX_TONES = 64
+ISAC_DIR_MAX_SOURCES = 8
+ISAC_MULTISTATIC_MAX_PATHS, ISAC_MULTISTATIC_MAX_SOURCES, ISAC_MULTISTATIC_MAX_ANTS = 64, 32, 256
+ISAC_CANCEL_PATHS_MAX_REFS = 32
+
+# Every function of the C ABI: header file -> {name: (restype, argtypes)}.  include/isac.h first, then the additive headers in the order of the #include lines at its
+# end; inside a header, the header's own order.  load() sets both on the library, so a call with a missing argument (TypeError) or a float for an integer
+# (ctypes.ArgumentError) fails instead of reaching the library, a 64-bit value arrives whole, and call sites pass plain Python numbers, DeviceArrays and None.
+# ONE typing rule, no exceptions (tests/_abi_header.py restates it and tests/test_abi_cpu.py re-derives every line from its header):
 #   int, int32_t -> c_int32    int64_t -> c_int64    uint64_t -> c_uint64    size_t -> c_size_t    double -> c_double
-#   pointer to a struct that has a mirror above (isac_c64 excepted: it is array data) -> POINTER(mirror): takes byref(x), an array of the mirror, None
+#   pointer to a struct of the MIRROR SET -> POINTER(mirror): takes byref(x), an array of the mirror, None.  The mirror set is
+#       isac_carrier, isac_est_params, isac_cfar_config, isac_radar_channel_params, isac_music2d_params, isac_est_result, isac_csi_report, isac_srs_report,
+#       isac_cdl_job, isac_sensing_job, isac_rx_frontend_job, isac_path_loss_config, isac_cfar_method.
+#       Outside it although mirrored above: isac_c64 (array data) and isac_target_list (its three functions -- isac_fft2d_get_targets, isac_fft2d_get_targets_upa,
+#       isac_fft2d_beam_detect -- take it as c_void_p; the wrappers pass byref(TargetList())).
 #   every other pointer (data, out-scalars, T[] parameters, isac_ctx*, void*, pointer to pointer) -> c_void_p: takes byref(x), ctypes arrays,
 #       ndarray.ctypes.data_as(c_void_p), a DeviceArray, ctx.handle, None
 #   returns: c_char_p for isac_last_error, c_int (an isac_status) for everything else.
+# A new entry point = one line under its header's key here (a new header: a new key, where isac.h includes it) and one row (name, argument count) in the HEADERS table
+# of tests/test_abi_cpu.py, which fails if the line disagrees with the header.
 _INT, _I32, _I64, _U64, _SZ, _F64, _P, _ptr = C.c_int, C.c_int32, C.c_int64, C.c_uint64, C.c_size_t, C.c_double, C.c_void_p, C.POINTER
-PROTOTYPES = {
-    "isac_abi_version": (_INT, ()),
-    "isac_abi_sizeof": (_INT, (_I32,)),
-    "isac_device_count": (_INT, (_P,)),
-    "isac_ctx_create": (_INT, (_I32, _P)),
-    "isac_ctx_destroy": (_INT, (_P,)),
-    "isac_last_error": (C.c_char_p, (_P,)),
-    "isac_ctx_get_stream": (_INT, (_P, _P)),
-    "isac_sync": (_INT, (_P,)),
-    "isac_dev_alloc": (_INT, (_P, _SZ, _P)),
-    "isac_dev_free": (_INT, (_P, _P)),
-    "isac_memcpy_h2d": (_INT, (_P, _P, _P, _SZ)),
-    "isac_memcpy_d2h": (_INT, (_P, _P, _P, _SZ)),
-    "isac_memcpy_d2d": (_INT, (_P, _P, _P, _SZ)),
-    "isac_memset_dev": (_INT, (_P, _P, _I32, _SZ)),
-    "isac_timer_start": (_INT, (_P,)),
-    "isac_timer_stop_ms": (_INT, (_P, _P)),
-    "isac_profile_enable": (_INT, (_P, _I32)),
-    "isac_profile_last_kernel_ms": (_INT, (_P, _P)),
-    "isac_basic_radar_channel_dev": (_INT, (_P, _P, _I64, _ptr(RadarChannelParams), _P, _I32, _P, _U64, _P)),
-    "isac_basic_radar_channel": (_INT, (_P, _P, _I64, _ptr(RadarChannelParams), _P, _I32, _P, _U64, _P)),
-    "isac_mono_static_sensing_dev": (_INT, (_P, _P, _I64, _I32, _ptr(Carrier), _ptr(RadarChannelParams), _P, _I32, _P, _U64, _P, _P)),
-    "isac_mono_static_sensing": (_INT, (_P, _P, _I64, _I32, _ptr(Carrier), _ptr(RadarChannelParams), _P, _I32, _P, _U64, _P, _P)),
-    "isac_mono_static_sensing_fused_dev": (_INT, (_P, _P, _I64, _I32, _ptr(Carrier), _ptr(RadarChannelParams), _P, _I32, _P, _U64, _P, _P, _ptr(EstParams), _ptr(CfarConfig), _P)),
-    "isac_echo_grid_materialize_dev": (_INT, (_P, _P, _P)),
-    "isac_ofdm_symbol_count": (_INT, (_ptr(Carrier), _I64, _P)),
-    "isac_ofdm_demodulate_dev": (_INT, (_P, _P, _I64, _I32, _ptr(Carrier), _P, _I32)),
-    "isac_ofdm_modulate_dev": (_INT, (_P, _P, _I32, _I32, _ptr(Carrier), _F64, _P, _I64)),
-    "isac_ofdm_waveform_length": (_INT, (_ptr(Carrier), _I32, _P)),
-    "isac_ofdm_modulate_windowed_dev": (_INT, (_P, _P, _I32, _I32, _ptr(Carrier), _F64, _I32, _I32, _P, _I64)),
-    "isac_sentx_append_dev": (_INT, (_P, _ptr(Carrier), _I32, _I32, _I32, _P, _F64, _I32, _P, _I32, _I32, _P, _I64, _I64, _P)),
-    "isac_cfar2d_ca": (_INT, (_P, _P, _I32, _I32, _P, _I32, _P, _P, _F64, _P, _I32, _P)),
-    "isac_fft2d_dev": (_INT, (_P, _ptr(EstParams), _ptr(CfarConfig), _P, _P, _I32, _I32, _I32, _ptr(EstResult))),
-    "isac_fft2d": (_INT, (_P, _ptr(EstParams), _ptr(CfarConfig), _P, _P, _I32, _I32, _I32, _ptr(EstResult))),
-    "isac_fft2d_submit_dev": (_INT, (_P, _ptr(EstParams), _ptr(CfarConfig), _P, _P, _I32, _I32, _I32)),
-    "isac_fft2d_collect": (_INT, (_P, _ptr(EstResult))),
-    "isac_fft2d_submit_cached_dev": (_INT, (_P, _ptr(EstParams), _ptr(CfarConfig), _P, _P, _I32, _I32, _I32)),
-    "isac_sensing_submit_n": (_INT, (_P, _I32, _ptr(SensingJob), _I64, _I32, _ptr(Carrier), _ptr(EstParams), _ptr(CfarConfig), _F64, _P)),
-    "isac_sensing_collect_n": (_INT, (_P, _I32, _ptr(EstResult), _P)),
-    "isac_fft2d_range_stage_dev": (_INT, (_P, _ptr(EstParams), _ptr(CfarConfig), _P, _P, _I32, _I32, _I32)),
-    "isac_fft2d_get_detections": (_INT, (_P, _P, _P, _I32, _P, _P)),
-    "isac_fft2d_get_power_window": (_INT, (_P, _P, _I64, _P, _P, _P)),
-    "isac_fft2d_get_covariance": (_INT, (_P, _P, _I32)),
-    "isac_fft2d_get_music_spectrum": (_INT, (_P, _P, _I32, _P)),
-    "isac_rdm_plane_dev": (_INT, (_P, _ptr(EstParams), _P, _P, _I32, _I32, _I32, _I32, _P)),
-    "isac_covariance_dev": (_INT, (_P, _P, _I64, _I32, _P)),
-    "isac_eigh_top": (_INT, (_P, _P, _I32, _I32, _P, _P)),
-    "isac_ctx_set_option": (_INT, (_P, _I32, _I32)),
-    "isac_ctx_share_streams": (_INT, (_P, _P)),
-    "isac_ctx_reserve": (_INT, (_P, _I64, _I32, _ptr(Carrier), _ptr(RadarChannelParams), _ptr(EstParams), _ptr(CfarConfig), _F64, _P)),
-    "isac_music_doa": (_INT, (_P, _I32, _ptr(EstParams), _P, _I32, _P, _P, _P, _I32, _P)),
-    "isac_beamscan_doa": (_INT, (_P, _I32, _I32, _ptr(EstParams), _P, _I32, _P, _P, _I32, _P)),
-    "isac_get_angular_spectrum2d": (_INT, (_P, _P, _I64, _P)),
-    "isac_find2d_peaks": (_INT, (_P, _P, _I32, _I32, _I32, _P, _P, _P)),
-    "isac_music2d_dev": (_INT, (_P, _ptr(EstParams), _ptr(Music2dParams), _P, _P, _I32, _I32, _I32, _ptr(EstResult))),
-    "isac_music2d_get_spectra": (_INT, (_P, _P, _I32, _P, _I32, _P)),
-    "isac_eigh": (_INT, (_P, _P, _I32, _P, _P)),
-    "isac_cdl_apply_dev": (_INT, (_P, _P, _I64, _I32, _I32, _I32, _P, _I32, _P, _P, _I32, _P, _F64, _P)),
-    "isac_cdl_apply_batch_dev": (_INT, (_P, _ptr(CdlJob), _I32, _I64, _I32, _I32, _I32, _P, _I32, _P, _F64)),
-    "isac_cdl_path_gains_dev": (_INT, (_P, _P, _P, _I32, _I32, _I32, _I32, _P, _F64, _P, _I32, _P)),
-    "isac_prg_precode_dev": (_INT, (_P, _P, _I32, _I32, _I32, _P, _I32, _I32, _I32, _P)),
-    "isac_cdl_freq_response_dev": (_INT, (_P, _P, _I32, _I32, _I32, _I32, _P, _P, _I64, _P)),
-    "isac_cdl_csi_estimate_batch_dev": (_INT, (_P, _I32, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _I64, _P)),
-    "isac_path_loss_38901": (_INT, (_I32, _F64, _I32, _P, _P, _ptr(PathLossConfig), _P)),
-    "isac_path_loss_fspl": (_INT, (_F64, _P, _P, _P)),
-    "isac_thermal_noise_power": (_INT, (_F64, _F64, _F64, _P)),
-    "isac_dft_channel_matrix": (_INT, (_I32, _I32, _P)),
-    "isac_rx_frontend_batch_dev": (_INT, (_P, _ptr(RxFrontendJob), _I32, _I64, _I32, _I32)),
-    "isac_rx_frontend_dev": (_INT, (_P, _P, _I64, _I32, _F64, _F64, _F64, _I32, _P, _U64)),
-    "isac_precoded_sinr_cqi_dev": (_INT, (_P, _P, _I64, _I32, _I32, _P, _I32, _F64, _P, _I32, _P, _P, _P)),
-    "isac_type1sp_codebook": (_INT, (_I32, _I32, _I32, _I32, _I32, _P, _I64, _P)),
-    "isac_csi_report_dev": (_INT, (_P, _P, _I64, _I32, _I32, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _I32, _P, _F64, _P, _I32, _ptr(CsiReport), _P, _P)),
-    "isac_csi_report_batch_dev": (_INT, (_P, _I32, _P, _I64, _I32, _I32, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _I32, _P, _P, _P, _I32, _ptr(CsiReport), _P)),
-    "isac_pusch_codebook": (_INT, (_I32, _I32, _P, _I64, _P)),
-    "isac_srs_pmi_select_batch_dev": (_INT, (_P, _I32, _P, _I64, _I32, _I32, _P, _I32, _I32, _I32, _P, _P, _I32, _ptr(SrsReport))),
-    "isac_los_check_dev": (_INT, (_P, _P, _P, _I64, _P, _P, _P, _P, _I32, _P, _P)),
-    "isac_winding_number_dev": (_INT, (_P, _P, _I64, _P, _P, _P, _I32, _P)),
-    "isac_synth_qpsk_grid_dev": (_INT, (_P, _P, _I32, _I32, _I32, _U64, _I32)),
+_MULTISTATIC_ARGS = (_P, _P, _P, _I32, _I64, _F64, _F64, _F64, _I32, _I32, _P, _P, _P, _P, _P, _P, _I32, _P, _U64)   # ctx .. seed: what the two isac_multistatic.h calls share
+HEADER_PROTOTYPES = {
+    "isac.h": {
+        "isac_abi_version": (_INT, ()),
+        "isac_abi_sizeof": (_INT, (_I32,)),
+        "isac_device_count": (_INT, (_P,)),
+        "isac_ctx_create": (_INT, (_I32, _P)),
+        "isac_ctx_destroy": (_INT, (_P,)),
+        "isac_last_error": (C.c_char_p, (_P,)),
+        "isac_ctx_get_stream": (_INT, (_P, _P)),
+        "isac_sync": (_INT, (_P,)),
+        "isac_dev_alloc": (_INT, (_P, _SZ, _P)),
+        "isac_dev_free": (_INT, (_P, _P)),
+        "isac_memcpy_h2d": (_INT, (_P, _P, _P, _SZ)),
+        "isac_memcpy_d2h": (_INT, (_P, _P, _P, _SZ)),
+        "isac_memcpy_d2d": (_INT, (_P, _P, _P, _SZ)),
+        "isac_memset_dev": (_INT, (_P, _P, _I32, _SZ)),
+        "isac_timer_start": (_INT, (_P,)),
+        "isac_timer_stop_ms": (_INT, (_P, _P)),
+        "isac_profile_enable": (_INT, (_P, _I32)),
+        "isac_profile_last_kernel_ms": (_INT, (_P, _P)),
+        "isac_basic_radar_channel_dev": (_INT, (_P, _P, _I64, _ptr(RadarChannelParams), _P, _I32, _P, _U64, _P)),
+        "isac_basic_radar_channel": (_INT, (_P, _P, _I64, _ptr(RadarChannelParams), _P, _I32, _P, _U64, _P)),
+        "isac_mono_static_sensing_dev": (_INT, (_P, _P, _I64, _I32, _ptr(Carrier), _ptr(RadarChannelParams), _P, _I32, _P, _U64, _P, _P)),
+        "isac_mono_static_sensing": (_INT, (_P, _P, _I64, _I32, _ptr(Carrier), _ptr(RadarChannelParams), _P, _I32, _P, _U64, _P, _P)),
+        "isac_mono_static_sensing_fused_dev": (_INT, (_P, _P, _I64, _I32, _ptr(Carrier), _ptr(RadarChannelParams), _P, _I32, _P, _U64, _P, _P, _ptr(EstParams), _ptr(CfarConfig), _P)),
+        "isac_echo_grid_materialize_dev": (_INT, (_P, _P, _P)),
+        "isac_ofdm_symbol_count": (_INT, (_ptr(Carrier), _I64, _P)),
+        "isac_ofdm_demodulate_dev": (_INT, (_P, _P, _I64, _I32, _ptr(Carrier), _P, _I32)),
+        "isac_ofdm_modulate_dev": (_INT, (_P, _P, _I32, _I32, _ptr(Carrier), _F64, _P, _I64)),
+        "isac_ofdm_waveform_length": (_INT, (_ptr(Carrier), _I32, _P)),
+        "isac_ofdm_modulate_windowed_dev": (_INT, (_P, _P, _I32, _I32, _ptr(Carrier), _F64, _I32, _I32, _P, _I64)),
+        "isac_sentx_append_dev": (_INT, (_P, _ptr(Carrier), _I32, _I32, _I32, _P, _F64, _I32, _P, _I32, _I32, _P, _I64, _I64, _P)),
+        "isac_cfar2d_ca": (_INT, (_P, _P, _I32, _I32, _P, _I32, _P, _P, _F64, _P, _I32, _P)),
+        "isac_fft2d_dev": (_INT, (_P, _ptr(EstParams), _ptr(CfarConfig), _P, _P, _I32, _I32, _I32, _ptr(EstResult))),
+        "isac_fft2d": (_INT, (_P, _ptr(EstParams), _ptr(CfarConfig), _P, _P, _I32, _I32, _I32, _ptr(EstResult))),
+        "isac_fft2d_submit_dev": (_INT, (_P, _ptr(EstParams), _ptr(CfarConfig), _P, _P, _I32, _I32, _I32)),
+        "isac_fft2d_collect": (_INT, (_P, _ptr(EstResult))),
+        "isac_fft2d_submit_cached_dev": (_INT, (_P, _ptr(EstParams), _ptr(CfarConfig), _P, _P, _I32, _I32, _I32)),
+        "isac_sensing_submit_n": (_INT, (_P, _I32, _ptr(SensingJob), _I64, _I32, _ptr(Carrier), _ptr(EstParams), _ptr(CfarConfig), _F64, _P)),
+        "isac_sensing_collect_n": (_INT, (_P, _I32, _ptr(EstResult), _P)),
+        "isac_fft2d_range_stage_dev": (_INT, (_P, _ptr(EstParams), _ptr(CfarConfig), _P, _P, _I32, _I32, _I32)),
+        "isac_fft2d_get_detections": (_INT, (_P, _P, _P, _I32, _P, _P)),
+        "isac_fft2d_get_power_window": (_INT, (_P, _P, _I64, _P, _P, _P)),
+        "isac_fft2d_get_covariance": (_INT, (_P, _P, _I32)),
+        "isac_fft2d_get_music_spectrum": (_INT, (_P, _P, _I32, _P)),
+        "isac_rdm_plane_dev": (_INT, (_P, _ptr(EstParams), _P, _P, _I32, _I32, _I32, _I32, _P)),
+        "isac_covariance_dev": (_INT, (_P, _P, _I64, _I32, _P)),
+        "isac_eigh_top": (_INT, (_P, _P, _I32, _I32, _P, _P)),
+        "isac_ctx_set_option": (_INT, (_P, _I32, _I32)),
+        "isac_ctx_share_streams": (_INT, (_P, _P)),
+        "isac_ctx_reserve": (_INT, (_P, _I64, _I32, _ptr(Carrier), _ptr(RadarChannelParams), _ptr(EstParams), _ptr(CfarConfig), _F64, _P)),
+        "isac_music_doa": (_INT, (_P, _I32, _ptr(EstParams), _P, _I32, _P, _P, _P, _I32, _P)),
+        "isac_beamscan_doa": (_INT, (_P, _I32, _I32, _ptr(EstParams), _P, _I32, _P, _P, _I32, _P)),
+        "isac_get_angular_spectrum2d": (_INT, (_P, _P, _I64, _P)),
+        "isac_find2d_peaks": (_INT, (_P, _P, _I32, _I32, _I32, _P, _P, _P)),
+        "isac_music2d_dev": (_INT, (_P, _ptr(EstParams), _ptr(Music2dParams), _P, _P, _I32, _I32, _I32, _ptr(EstResult))),
+        "isac_music2d_get_spectra": (_INT, (_P, _P, _I32, _P, _I32, _P)),
+        "isac_eigh": (_INT, (_P, _P, _I32, _P, _P)),
+        "isac_cdl_apply_dev": (_INT, (_P, _P, _I64, _I32, _I32, _I32, _P, _I32, _P, _P, _I32, _P, _F64, _P)),
+        "isac_cdl_apply_batch_dev": (_INT, (_P, _ptr(CdlJob), _I32, _I64, _I32, _I32, _I32, _P, _I32, _P, _F64)),
+        "isac_cdl_path_gains_dev": (_INT, (_P, _P, _P, _I32, _I32, _I32, _I32, _P, _F64, _P, _I32, _P)),
+        "isac_prg_precode_dev": (_INT, (_P, _P, _I32, _I32, _I32, _P, _I32, _I32, _I32, _P)),
+        "isac_cdl_freq_response_dev": (_INT, (_P, _P, _I32, _I32, _I32, _I32, _P, _P, _I64, _P)),
+        "isac_cdl_csi_estimate_batch_dev": (_INT, (_P, _I32, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _I64, _P)),
+        "isac_path_loss_38901": (_INT, (_I32, _F64, _I32, _P, _P, _ptr(PathLossConfig), _P)),
+        "isac_path_loss_fspl": (_INT, (_F64, _P, _P, _P)),
+        "isac_thermal_noise_power": (_INT, (_F64, _F64, _F64, _P)),
+        "isac_dft_channel_matrix": (_INT, (_I32, _I32, _P)),
+        "isac_rx_frontend_batch_dev": (_INT, (_P, _ptr(RxFrontendJob), _I32, _I64, _I32, _I32)),
+        "isac_rx_frontend_dev": (_INT, (_P, _P, _I64, _I32, _F64, _F64, _F64, _I32, _P, _U64)),
+        "isac_precoded_sinr_cqi_dev": (_INT, (_P, _P, _I64, _I32, _I32, _P, _I32, _F64, _P, _I32, _P, _P, _P)),
+        "isac_type1sp_codebook": (_INT, (_I32, _I32, _I32, _I32, _I32, _P, _I64, _P)),
+        "isac_csi_report_dev": (_INT, (_P, _P, _I64, _I32, _I32, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _I32, _P, _F64, _P, _I32, _ptr(CsiReport), _P, _P)),
+        "isac_csi_report_batch_dev": (_INT, (_P, _I32, _P, _I64, _I32, _I32, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _I32, _P, _P, _P, _I32, _ptr(CsiReport), _P)),
+        "isac_pusch_codebook": (_INT, (_I32, _I32, _P, _I64, _P)),
+        "isac_srs_pmi_select_batch_dev": (_INT, (_P, _I32, _P, _I64, _I32, _I32, _P, _I32, _I32, _I32, _P, _P, _I32, _ptr(SrsReport))),
+        "isac_los_check_dev": (_INT, (_P, _P, _P, _I64, _P, _P, _P, _P, _I32, _P, _P)),
+        "isac_winding_number_dev": (_INT, (_P, _P, _I64, _P, _P, _P, _I32, _P)),
+        "isac_synth_qpsk_grid_dev": (_INT, (_P, _P, _I32, _I32, _I32, _U64, _I32)),
+    },
+    "isac_targets.h": {
+        "isac_fft2d_get_targets": (_INT, (_P, _P, _P, _I32)),
+    },
+    "isac_cfar.h": {
+        "isac_cfar_threshold_factor": (_INT, (_I32, _I32, _I32, _F64, _P)),
+        "isac_cfar2d": (_INT, (_P, _P, _I32, _I32, _P, _I32, _P, _P, _F64, _ptr(CfarMethod), _P, _I32, _P)),
+        "isac_fft2d_redetect": (_INT, (_P, _ptr(CfarMethod), _ptr(EstResult), _P, _P, _I32, _P, _P)),
+    },
+    "isac_cfar_mc.h": {
+        "isac_cfar_monte_carlo": (_INT, (_P, _ptr(CfarMethod), _I32, _F64, _I32, _P, _I32, _U64, _U64, _P, _P)),
+    },
+    "isac_lazy_cov.h": {
+        "isac_ctx_set_lazy_cov_route": (_INT, (_P, _I32)),
+        "isac_ctx_get_lazy_cov_route_used": (_INT, (_P, _P)),
+    },
+    "isac_targets_upa.h": {
+        "isac_fft2d_get_targets_upa": (_INT, (_P, _P, _P, _P, _I32)),
+    },
+    "isac_beams.h": {
+        "isac_fft2d_get_rdm_window": (_INT, (_P, _P, _I64, _P, _P, _P)),
+        "isac_fft2d_beam_detect": (_INT, (_P, _P, _I32, _P, _ptr(CfarMethod), _P, _P, _P, _P, _I32, _P, _P, _P)),
+    },
+    "isac_refine.h": {
+        "isac_fft2d_refine_targets": (_INT, (_P, _P, _P, _I32, _F64, _I32, _F64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P)),
+    },
+    "isac_clean.h": {
+        "isac_fft2d_clean_targets": (_INT, (_P, _ptr(CfarMethod), _I32, _I32, _F64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P)),
+    },
+    "isac_relax.h": {
+        "isac_fft2d_relax_targets": (_INT, (_P, _P, _P, _I32, _I32, _I32, _F64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P)),
+    },
+    "isac_directions.h": {
+        "isac_resolve_directions": (_INT, (_P, _ptr(EstParams), _P, _I32, _I32, _I32, _I32, _F64, _F64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P)),
+    },
+    "isac_beam_clean.h": {
+        "isac_fft2d_beam_clean_targets": (_INT, (_P, _P, _I32, _P, _ptr(CfarMethod), _I32, _I32, _F64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P)),
+    },
+    "isac_multistatic.h": {
+        "isac_multi_static_channel_dev": (_INT, _MULTISTATIC_ARGS + (_P,)),
+        "isac_multi_static_sensing_dev": (_INT, _MULTISTATIC_ARGS + (_I32, _ptr(Carrier), _P, _P)),
+    },
+    "isac_cancel_paths.h": {
+        "isac_cancel_paths_dev": (_INT, (_P, _P, _P, _I32, _I64, _F64, _F64, _I32, _I32, _P, _P, _P, _P, _F64, _P, _P, _P, _P, _P)),
+    },
 }
-EXPORTS = list(PROTOTYPES)
-# What the additive headers declare under the same ABI version (include/isac_targets.h), same typing rule; load() applies both tables.
-PROTOTYPES_ADDED = {
-    "isac_fft2d_get_targets": (_INT, (_P, _P, _P, _I32)),
-}
-# ... and include/isac_cfar.h, a table per additive header (tests/test_target_list_cpu.py pins PROTOTYPES_ADDED to isac_targets.h as tests/test_abi_cpu.py pins PROTOTYPES to isac.h)
-PROTOTYPES_CFAR = {
-    "isac_cfar_threshold_factor": (_INT, (_I32, _I32, _I32, _F64, _P)),
-    "isac_cfar2d": (_INT, (_P, _P, _I32, _I32, _P, _I32, _P, _P, _F64, _ptr(CfarMethod), _P, _I32, _P)),
-    "isac_fft2d_redetect": (_INT, (_P, _ptr(CfarMethod), _ptr(EstResult), _P, _P, _I32, _P, _P)),
-}
-# ... and include/isac_cfar_mc.h (tests/test_cfar_mc_cpu.py pins it)
-PROTOTYPES_CFAR_MC = {
-    "isac_cfar_monte_carlo": (_INT, (_P, _ptr(CfarMethod), _I32, _F64, _I32, _P, _I32, _U64, _U64, _P, _P)),
-}
-# ... and include/isac_lazy_cov.h (tests/test_lazy_cov_abi_cpu.py pins it)
-PROTOTYPES_LAZY_COV = {
-    "isac_ctx_set_lazy_cov_route": (_INT, (_P, _I32)),
-    "isac_ctx_get_lazy_cov_route_used": (_INT, (_P, _P)),
-}
-# ... and include/isac_targets_upa.h (tests/test_target_list_upa_cpu.py pins it)
-PROTOTYPES_TARGETS_UPA = {
-    "isac_fft2d_get_targets_upa": (_INT, (_P, _P, _P, _P, _I32)),
-}
-# ... and include/isac_beams.h (tests/test_beam_detect_cpu.py pins it)
-PROTOTYPES_BEAMS = {
-    "isac_fft2d_get_rdm_window": (_INT, (_P, _P, _I64, _P, _P, _P)),
-    "isac_fft2d_beam_detect": (_INT, (_P, _P, _I32, _P, _ptr(CfarMethod), _P, _P, _P, _P, _I32, _P, _P, _P)),
-}
-# ... and include/isac_refine.h (tests/test_refine_cpu.py pins it)
-PROTOTYPES_REFINE = {
-    "isac_fft2d_refine_targets": (_INT, (_P, _P, _P, _I32, _F64, _I32, _F64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P)),
-}
-# ... and include/isac_clean.h (tests/test_clean_cpu.py pins it)
-PROTOTYPES_CLEAN = {
-    "isac_fft2d_clean_targets": (_INT, (_P, _ptr(CfarMethod), _I32, _I32, _F64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P)),
-}
-# ... and include/isac_relax.h (tests/test_relax_cpu.py pins it)
-ISAC_RELAX_MAX_TONES = 64
-PROTOTYPES_RELAX = {
-    "isac_fft2d_relax_targets": (_INT, (_P, _P, _P, _I32, _I32, _I32, _F64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P)),
-}
-# ... and include/isac_directions.h (tests/test_directions_cpu.py pins it)
-ISAC_DIR_MAX_SOURCES = 8
-PROTOTYPES_DIRECTIONS = {
-    "isac_resolve_directions": (_INT, (_P, _ptr(EstParams), _P, _I32, _I32, _I32, _I32, _F64, _F64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P)),
-}
-# ... and include/isac_beam_clean.h (tests/test_beam_clean_cpu.py pins it)
-PROTOTYPES_BEAM_CLEAN = {
-    "isac_fft2d_beam_clean_targets": (_INT, (_P, _P, _I32, _P, _ptr(CfarMethod), _I32, _I32, _F64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P)),
-}
-# ... and include/isac_multistatic.h (tests/test_multistatic_cpu.py pins it)
-ISAC_MULTISTATIC_MAX_PATHS, ISAC_MULTISTATIC_MAX_SOURCES, ISAC_MULTISTATIC_MAX_ANTS = 64, 32, 256
-_MULTISTATIC_ARGS = (_P, _P, _P, _I32, _I64, _F64, _F64, _F64, _I32, _I32, _P, _P, _P, _P, _P, _P, _I32, _P, _U64)   # ctx .. seed: what the two calls share
-PROTOTYPES_MULTISTATIC = {
-    "isac_multi_static_channel_dev": (_INT, _MULTISTATIC_ARGS + (_P,)),
-    "isac_multi_static_sensing_dev": (_INT, _MULTISTATIC_ARGS + (_I32, _ptr(Carrier), _P, _P)),
-}
-# ... and include/isac_cancel_paths.h (tests/test_cancel_cpu.py pins it)
-ISAC_CANCEL_PATHS_MAX_REFS = 32
-PROTOTYPES_CANCEL_PATHS = {
-    "isac_cancel_paths_dev": (_INT, (_P, _P, _P, _I32, _I64, _F64, _F64, _I32, _I32, _P, _P, _P, _P, _F64, _P, _P, _P, _P, _P)),
-}
+PROTOTYPES = {name: line for table in HEADER_PROTOTYPES.values() for name, line in table.items()}
 
 
 def library_path() -> str:
@@ -313,13 +310,13 @@ def load():
             except Exception:
                 pass
         lib = C.CDLL(_LIB_PATH, mode=C.RTLD_GLOBAL)
-        for name, (restype, argtypes) in {**PROTOTYPES, **PROTOTYPES_ADDED, **PROTOTYPES_CFAR, **PROTOTYPES_CFAR_MC, **PROTOTYPES_LAZY_COV, **PROTOTYPES_TARGETS_UPA, **PROTOTYPES_BEAMS, **PROTOTYPES_REFINE, **PROTOTYPES_CLEAN, **PROTOTYPES_RELAX, **PROTOTYPES_DIRECTIONS, **PROTOTYPES_BEAM_CLEAN, **PROTOTYPES_MULTISTATIC, **PROTOTYPES_CANCEL_PATHS}.items():
-            fn = getattr(lib, name)  # AttributeError here = ABI drift between isac.h and the .so
+        for name, (restype, argtypes) in PROTOTYPES.items():
+            fn = getattr(lib, name)  # AttributeError here = ABI drift between the headers and the .so
             fn.restype, fn.argtypes = restype, argtypes
         # the library writes whole structs into caller memory: version AND struct sizes must match this binding's mirrors
         if lib.isac_abi_version() != ISAC_ABI_VERSION:
             raise RuntimeError(f"{_LIB_PATH}: ABI version {lib.isac_abi_version()} but this binding was written for {ISAC_ABI_VERSION}; rebuild the library")
-        for which, name, cls in [(i, n, c) for i, (n, c) in enumerate(ABI_STRUCTS)] + list(ABI_STRUCTS_ADDED) + list(ABI_STRUCTS_CFAR):
+        for which, (name, cls) in enumerate(ABI_STRUCTS):
             if lib.isac_abi_sizeof(which) != C.sizeof(cls):
                 raise RuntimeError(f"{_LIB_PATH}: sizeof({name}) = {lib.isac_abi_sizeof(which)} in the library, {C.sizeof(cls)} in the binding")
         _lib = lib

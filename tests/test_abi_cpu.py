@@ -11,8 +11,9 @@ from types import SimpleNamespace
 import numpy as np
 import pytest
 
+import _abi_header as H
 import oracle as O
-from conftest import ROOT, load_pkg, make_scene
+from conftest import load_pkg, make_scene
 
 
 @pytest.fixture(scope="module")
@@ -25,80 +26,80 @@ def lib_path():
 
 
 def test_header_symbols_all_exported(lib_path):
-    hdr = open(os.path.join(ROOT, "include", "isac.h")).read()
+    hdr = H.text("isac.h")
     declared = set(re.findall(r"\b(isac_[a-z0-9_]+)\s*\(", hdr))
     declared -= {"isac_status"}
     lib = ctypes.CDLL(lib_path)
     missing = [s for s in sorted(declared) if not hasattr(lib, s)]
     assert not missing, f"declared in isac.h but not exported: {missing}"
     pkg = load_pkg()
-    assert set(pkg._lib.EXPORTS) == declared
+    assert set(pkg._lib.HEADER_PROTOTYPES["isac.h"]) == declared
     m = re.search(r"#define ISAC_ABI_VERSION (\d+)", hdr)
     assert lib.isac_abi_version() == int(m.group(1)) == pkg._lib.ISAC_ABI_VERSION >= 3
-    # struct sizes as the library was built == the ctypes mirrors (the loader refuses a mismatch; ADVICE r2)
+    # struct sizes as the library was built == the ctypes mirrors (the loader refuses a mismatch): every ISAC_SIZEOF_* of every header, enum or #define
     L = pkg._lib
-    selectors = {int(v): n for n, v in re.findall(r"\bISAC_SIZEOF_(\w+) = (\d+)", hdr)}
-    assert [name for name, _ in L.ABI_STRUCTS] == ["isac_" + selectors[i].lower() for i in range(len(selectors))] and len(selectors) == 11
+    selectors = H.sizeof_selectors()
+    assert sorted(selectors) == list(range(13)) and sorted(i for i, (header, _) in selectors.items() if header == "isac.h") == list(range(11))
+    assert len(re.findall(r"\bISAC_SIZEOF_\w+ = \d+", H.without_comments("isac.h"))) == 11                           # ... those eleven in the enum form
+    assert selectors[11] == ("isac_targets.h", "TARGET_LIST") and selectors[12] == ("isac_cfar.h", "CFAR_METHOD")
+    assert [name for name, _ in L.ABI_STRUCTS] == ["isac_" + selectors[i][1].lower() for i in range(13)]
     for which, (name, cls) in enumerate(L.ABI_STRUCTS):
         assert lib.isac_abi_sizeof(ctypes.c_int32(which)) == ctypes.sizeof(cls), name
+    assert lib.isac_abi_sizeof(ctypes.c_int32(13)) == -1
     assert lib.isac_abi_sizeof(ctypes.c_int32(99)) == -1
 
 
-# ---- the prototype table of _lib.py against include/isac.h.  The typing rule is restated here, not imported from the binding:
-#      by-value scalars by their C type, a pointer to a struct the binding mirrors -> POINTER(mirror), every other pointer (T[] parameters included) -> c_void_p.
-_SCALARS = {"int": ctypes.c_int32, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64, "size_t": ctypes.c_size_t,
-            "double": ctypes.c_double}
-_MIRRORS = {"isac_carrier": "Carrier", "isac_est_params": "EstParams", "isac_cfar_config": "CfarConfig", "isac_radar_channel_params": "RadarChannelParams",
-            "isac_music2d_params": "Music2dParams", "isac_est_result": "EstResult", "isac_csi_report": "CsiReport", "isac_srs_report": "SrsReport",
-            "isac_cdl_job": "CdlJob", "isac_sensing_job": "SensingJob", "isac_rx_frontend_job": "RxFrontendJob", "isac_path_loss_config": "PathLossConfig"}
-_RETURNS = {"int": ctypes.c_int, "const char*": ctypes.c_char_p}
+# ---- the prototype table of _lib.py against the headers, by the parser and the typing rule of tests/_abi_header.py.  One row per header: its functions in the
+#      header's order, each with its argument count; None = isac.h proper, whose 77 names come from the header.  A new entry point adds one row (or one pair) here.
+HEADERS = {
+    "isac.h": None,
+    "isac_targets.h": [("isac_fft2d_get_targets", 4)],
+    "isac_cfar.h": [("isac_cfar_threshold_factor", 5), ("isac_cfar2d", 13), ("isac_fft2d_redetect", 8)],
+    "isac_cfar_mc.h": [("isac_cfar_monte_carlo", 11)],
+    "isac_lazy_cov.h": [("isac_ctx_set_lazy_cov_route", 2), ("isac_ctx_get_lazy_cov_route_used", 2)],
+    "isac_targets_upa.h": [("isac_fft2d_get_targets_upa", 5)],
+    "isac_beams.h": [("isac_fft2d_get_rdm_window", 6), ("isac_fft2d_beam_detect", 13)],
+    "isac_refine.h": [("isac_fft2d_refine_targets", 17)],
+    "isac_clean.h": [("isac_fft2d_clean_targets", 23)],
+    "isac_relax.h": [("isac_fft2d_relax_targets", 18)],
+    "isac_directions.h": [("isac_resolve_directions", 19)],
+    "isac_beam_clean.h": [("isac_fft2d_beam_clean_targets", 30)],
+    "isac_multistatic.h": [("isac_multi_static_channel_dev", 20), ("isac_multi_static_sensing_dev", 23)],
+    "isac_cancel_paths.h": [("isac_cancel_paths_dev", 19)],
+}
 
 
-def _header_without_comments():
-    hdr = open(os.path.join(ROOT, "include", "isac.h")).read()
-    return re.sub(r"//[^\n]*", " ", re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S))
-
-
-def _header_prototypes():
-    """[(return type, name, [parameter type, ...])] of every function include/isac.h declares; `T name[n]` is the pointer `T*`."""
-    out = []
-    for ret, name, params in re.findall(r"\b(int|const char\s*\*)\s+(isac_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", _header_without_comments()):
-        types = []
-        for p in ([] if params.strip() == "void" else params.split(",")):
-            m = re.fullmatch(r"(.*?)\s*\b\w+\s*(\[\d*\])?", " ".join(p.split()))
-            types.append(re.sub(r"\s*\*", "*", m.group(1)) + ("*" if m.group(2) else ""))
-        out.append((re.sub(r"\s*\*", "*", ret), name, types))
-    return out
-
-
-def _rule(c_type, L):
-    if "*" not in c_type:
-        return _SCALARS[c_type]
-    m = re.fullmatch(r"(?:const )?(isac_\w+)\*", c_type)
-    return ctypes.POINTER(getattr(L, _MIRRORS[m.group(1)])) if m and m.group(1) in _MIRRORS else ctypes.c_void_p
-
-
-def test_prototype_table_matches_the_header(lib_path):
+@pytest.mark.parametrize("header", list(HEADERS))
+def test_prototype_table_matches_the_header(lib_path, header):
     L = load_pkg()._lib
-    protos = _header_prototypes()
-    hdr = open(os.path.join(ROOT, "include", "isac.h")).read()
-    assert len(protos) == 77 == len(set(re.findall(r"\b(isac_[a-z0-9_]+)\s*\(", hdr)) - {"isac_status"})      # the regex found every declaration
-    assert [name for _, name, _ in protos] == list(L.PROTOTYPES) == list(L.EXPORTS)                              # same names, in the header's order
+    protos = H.prototypes(header)
+    table = L.HEADER_PROTOTYPES[header]
+    if header == "isac.h":
+        assert len(protos) == 77 == len(set(re.findall(r"\b(isac_[a-z0-9_]+)\s*\(", H.text(header))) - {"isac_status"})   # the regex found every declaration
+        counts = {name: len(types) for _, name, types in protos}
+        # once, over all headers: the keys are isac.h and its #include lines in order, and no name stands under two headers
+        assert list(L.HEADER_PROTOTYPES) == ["isac.h"] + H.includes() == list(HEADERS)
+        assert sum(len(t) for t in L.HEADER_PROTOTYPES.values()) == len(L.PROTOTYPES) == 95 and len(table) == 77
+    else:
+        assert header in H.includes()                                                                                 # isac.h includes it
+        assert [name for _, name, _ in protos] == [name for name, _ in HEADERS[header]]
+        counts = dict(HEADERS[header])
+    assert [name for _, name, _ in protos] == list(table)                                                             # same names, in the header's order
     for ret, name, types in protos:
-        restype, argtypes = L.PROTOTYPES[name]
-        assert restype is _RETURNS[ret], name
-        assert len(argtypes) == len(types), name
+        restype, argtypes = table[name]
+        assert restype is H.RETURNS[ret], name
+        assert len(argtypes) == len(types) == counts[name], name
         for i, (got, c_type) in enumerate(zip(argtypes, types)):
-            assert got is _rule(c_type, L), f"{name} argument {i}: {c_type}"
+            assert got is H.rule(c_type, L), f"{name} argument {i}: {c_type}"
     lib = L.load()
-    for name, (restype, argtypes) in L.PROTOTYPES.items():                                                       # and load() applied the table
+    for name, (restype, argtypes) in table.items():                                                                  # and load() applied the table
         fn = getattr(lib, name)
         assert fn.restype is restype and tuple(fn.argtypes) == tuple(argtypes), name
 
 
 def test_option_and_status_constants_match_the_header():
     L = load_pkg()._lib
-    hdr = _header_without_comments()
+    hdr = H.without_comments("isac.h")
     opts = {n: int(v) for n, v in re.findall(r"\bISAC_OPT_(\w+) = (\d+)", hdr)}
     assert len(opts) == 5 and opts == {n[4:]: getattr(L, n) for n in dir(L) if n.startswith("OPT_")}
     body = re.search(r"typedef enum \{([^}]*)\} isac_status;", hdr).group(1)

@@ -3,7 +3,6 @@ tests/test_gpu_beam_detect.py runs, the matched gain of the two-way weight, the 
 beamWeights and the binding's prototype lines.  The device library is not asked for anything but its symbol table."""
 from __future__ import annotations
 
-import ctypes
 import os
 import re
 
@@ -12,6 +11,7 @@ import pytest
 
 from conftest import ROOT, load_pkg
 
+import _abi_header as H
 import _beam_detect_restatement as R
 
 
@@ -118,35 +118,21 @@ def test_beam_weights_are_the_squared_steering_vectors_of_radar_params():
 
 
 def test_binding_has_the_prototypes_and_the_abi_is_unchanged():
-    """include/isac_beams.h is additive under ABI 8 and included by isac.h; it declares exactly two functions, which are exported and carry their lines in PROTOTYPES_BEAMS
-    and in no other table -- re-derived here from the header by the typing rule of tests/test_abi_cpu.py (scalars by their C type, isac_cfar_method* by its mirror, as in
-    PROTOTYPES_CFAR, every other pointer -> c_void_p).  No new struct, no new isac_abi_sizeof selector, ABI version 8, the older tables as they were."""
+    """include/isac_beams.h is additive under ABI 8: no new struct, no new isac_abi_sizeof selector; isac_fft2d_get_rdm_window takes the arguments of
+    isac_fft2d_get_power_window, and both functions refuse a NULL context.  (Their prototype lines are compared with the header by tests/test_abi_cpu.py, row
+    "isac_beams.h".)"""
     import __graft_entry__ as g
     g.build()
     L = load_pkg()._lib
     hdr = open(os.path.join(ROOT, "include", "isac_beams.h")).read()
-    assert '#include "isac_beams.h"' in open(os.path.join(ROOT, "include", "isac.h")).read()
     plain = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
-    protos = re.findall(r"\bint\s+(isac_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", plain)
-    assert [n for n, _ in protos] == list(L.PROTOTYPES_BEAMS) == ["isac_fft2d_get_rdm_window", "isac_fft2d_beam_detect"]
     assert "typedef" not in plain and "ISAC_SIZEOF" not in plain
     assert int(re.search(r"#define ISAC_MAX_BEAMS (\d+)", plain).group(1)) == L.ISAC_MAX_BEAMS
-    scal = {"int": ctypes.c_int32, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "double": ctypes.c_double}
-    lib = L.load()                                                             # (needs no GPU) load() applied the lines
-    for name, params in protos:
-        types = []
-        for p in params.split(","):
-            m = re.fullmatch(r"(.*?)\s*\b\w+\s*(\[\d*\])?", " ".join(p.split()))
-            types.append(re.sub(r"\s*\*", "*", m.group(1)) + ("*" if m.group(2) else ""))
-        want = tuple(ctypes.POINTER(L.CfarMethod) if t == "const isac_cfar_method*" else ctypes.c_void_p if "*" in t else scal[t] for t in types)
-        assert L.PROTOTYPES_BEAMS[name] == (ctypes.c_int, want), name
-        assert all(name not in tab for tab in (L.PROTOTYPES, L.PROTOTYPES_ADDED, L.PROTOTYPES_CFAR, L.PROTOTYPES_CFAR_MC, L.PROTOTYPES_LAZY_COV, L.PROTOTYPES_TARGETS_UPA))
-        fn = getattr(lib, name)
-        assert fn.restype is ctypes.c_int and tuple(fn.argtypes) == want
-    a, b = re.findall(r"\bint\s+isac_fft2d_get_power_window\s*\(([^()]*)\)", open(os.path.join(ROOT, "include", "isac.h")).read())[0], protos[0][1]
-    assert " ".join(a.split()).replace("double* P", "isac_c64* Y") == " ".join(b.split())     # arguments exactly as isac_fft2d_get_power_window, with isac_c64 for double
+    lib = L.load()                                                             # (needs no GPU)
+    a = {name: params for _, name, params in H.declarations("isac.h")}["isac_fft2d_get_power_window"]
+    b = {name: params for _, name, params in H.declarations("isac_beams.h")}["isac_fft2d_get_rdm_window"]
+    assert a.replace("double* P", "isac_c64* Y") == b                          # arguments exactly as isac_fft2d_get_power_window, with isac_c64 for double
     assert lib.isac_abi_version() == 8 == L.ISAC_ABI_VERSION and lib.isac_abi_sizeof(13) == -1
-    assert len(L.PROTOTYPES) == 77 and list(L.PROTOTYPES_TARGETS_UPA) == ["isac_fft2d_get_targets_upa"]
     assert lib.isac_fft2d_get_rdm_window(None, None, 0, None, None, None) == 1   # refused before anything touches a device: no context (ISAC_ERR_INVALID_ARG)
     assert lib.isac_fft2d_beam_detect(None, None, 0, None, None, None, None, None, None, 0, None, None, None) == 1
     est = load_pkg().sensing.estimation

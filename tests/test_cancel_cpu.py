@@ -3,7 +3,6 @@ scene of tests/_multistatic_restatement.py before and after cancellation on the 
 edge cases tests/test_gpu_cancel.py runs, and the header and the binding's prototype line.  The device library is not asked for anything but its symbol table."""
 from __future__ import annotations
 
-import ctypes
 import os
 import re
 from types import SimpleNamespace
@@ -125,34 +124,20 @@ def test_reference_paths_is_its_restatement():
 
 # ---------------------------------------------------------------- (d) header and binding
 def test_binding_has_the_prototype_and_the_abi_is_unchanged(binding):
-    """include/isac_cancel_paths.h is additive under ABI 8 and included by isac.h; it declares exactly one function, which is exported and carries its line in
-    PROTOTYPES_CANCEL_PATHS and in no other table -- re-derived from the header by the typing rule of tests/test_abi_cpu.py."""
+    """include/isac_cancel_paths.h is additive under ABI 8: no new struct, enum or isac_abi_sizeof selector; the header states the limits, the refusals and what is out of
+    scope, and its one function refuses a NULL context.  (Its prototype line is compared with the header by tests/test_abi_cpu.py, row "isac_cancel_paths.h".)"""
     L = binding
     hdr = open(os.path.join(ROOT, "include", "isac_cancel_paths.h")).read()
-    assert '#include "isac_cancel_paths.h"' in open(os.path.join(ROOT, "include", "isac.h")).read()
     plain = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
-    protos = re.findall(r"\bint\s+(isac_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", plain)
-    assert [n for n, _ in protos] == list(L.PROTOTYPES_CANCEL_PATHS) == ["isac_cancel_paths_dev"]
     assert "typedef" not in plain and "struct" not in plain and "enum" not in plain and "ISAC_SIZEOF" not in plain
     assert int(re.search(r"#define ISAC_CANCEL_PATHS_MAX_REFS (\d+)", plain).group(1)) == 32 == L.ISAC_CANCEL_PATHS_MAX_REFS
     for word in ("OUT OF SCOPE", "MEX", "LIMITS", "n_refs 1 .. 32", "n_sources 1 .. 32", "1 .. 256", "DEPENDENT", "1e-10", "leaves d_out untouched", "*dependent = -1",
                  "ISAC_ERR_INVALID_ARG", "ISAC_ERR_CAPACITY", "launches nothing and writes nothing", "partially overlapping", "the same bits every time",
                  "cached range rows and lazy echo grid", "status record has been read back"):
         assert word in hdr, word
-    scal = {"int": ctypes.c_int32, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64, "double": ctypes.c_double}
-    lib = L.load()                                                             # (needs no GPU) load() applied the line
-    (name, params), = protos
-    want = []
-    for p in params.split(","):
-        m = re.fullmatch(r"(.*?)\s*\b\w+\s*(\[\d*\])?", " ".join(p.split()))
-        t = re.sub(r"\s*\*", "*", m.group(1)) + ("*" if m.group(2) else "")
-        want.append(scal[t] if "*" not in t else ctypes.c_void_p)
-    want = tuple(want)
-    assert len(want) == 19 and L.PROTOTYPES_CANCEL_PATHS[name] == (ctypes.c_int, want)
-    assert all(name not in tab for tab in (L.PROTOTYPES, L.PROTOTYPES_ADDED, L.PROTOTYPES_MULTISTATIC, L.PROTOTYPES_BEAM_CLEAN))
-    fn = getattr(lib, name)
-    assert fn.restype is ctypes.c_int and tuple(fn.argtypes) == want
+    lib = L.load()                                                             # (needs no GPU)
     assert lib.isac_abi_version() == 8 == L.ISAC_ABI_VERSION and lib.isac_abi_sizeof(13) == -1
+    fn = lib.isac_cancel_paths_dev
     assert fn(*([None] * 3), 1, 1, 1.0, 1.0, 1, 1, *([None] * 4), 0.0, *([None] * 5)) == 1      # refused before anything touches a device: no context
     pkg = load_pkg()
     assert callable(pkg.sensing.cancelPaths) and callable(pkg.sensing.ofdmDemodulate) and callable(pkg.sensing.channelModels.referencePaths)

@@ -3,7 +3,6 @@ the conditioning of those scenes (one local maximum per box), degenerate snapsho
 and the binding's prototype line.  The device library is not asked for anything but its symbol table."""
 from __future__ import annotations
 
-import ctypes
 import os
 import re
 from importlib import import_module
@@ -130,38 +129,19 @@ def test_wrapper_rows_and_twin():
 
 
 def test_binding_has_the_prototype_and_the_abi_is_unchanged():
-    """include/isac_directions.h is additive under ABI 8 and included by isac.h; it declares exactly one function, which is exported and carries its line in
-    PROTOTYPES_DIRECTIONS and in no other table -- re-derived here from the header by the typing rule of tests/test_abi_cpu.py.  No new struct, no new isac_abi_sizeof
-    selector, ABI version 8; the header carries the defaults."""
+    """include/isac_directions.h is additive under ABI 8: no new struct, no new isac_abi_sizeof selector; the header carries the defaults, and its one function refuses a
+    NULL context.  (Its prototype line is compared with the header by tests/test_abi_cpu.py, row "isac_directions.h".)"""
     import __graft_entry__ as g
     g.build()
     L = load_pkg()._lib
     hdr = open(os.path.join(ROOT, "include", "isac_directions.h")).read()
-    assert '#include "isac_directions.h"' in open(os.path.join(ROOT, "include", "isac.h")).read()
     plain = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
-    protos = re.findall(r"\bint\s+(isac_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", plain)
-    assert [n for n, _ in protos] == list(L.PROTOTYPES_DIRECTIONS) == ["isac_resolve_directions"]
     assert "typedef" not in plain and "ISAC_SIZEOF" not in plain
     for macro, want in (("MAX_SOURCES", 8), ("CYCLES", 16), ("MIN_RATIO", 0.01)):
         assert float(re.search(rf"#define ISAC_DIR_{macro} ([0-9.]+)", plain).group(1)) == want
     assert L.ISAC_DIR_MAX_SOURCES == 8 == R.MAX_SOURCES
-    mirrors = {"isac_est_params": L.EstParams}
-    scal = {"int": ctypes.c_int32, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "double": ctypes.c_double}
-    lib = L.load()                                                             # (needs no GPU) load() applied the lines
-    name, params = protos[0]
-    want = []
-    for p in params.split(","):
-        m = re.fullmatch(r"(.*?)\s*\b\w+\s*(\[\d*\])?", " ".join(p.split()))
-        t = re.sub(r"\s*\*", "*", m.group(1)) + ("*" if m.group(2) else "")
-        base = t.replace("const ", "").rstrip("*").strip()
-        want.append(ctypes.POINTER(mirrors[base]) if "*" in t and base in mirrors else ctypes.c_void_p if "*" in t else scal[t])
-    want = tuple(want)
-    assert len(want) == 19 and L.PROTOTYPES_DIRECTIONS[name] == (ctypes.c_int, want)
-    assert all(name not in tab for tab in (L.PROTOTYPES, L.PROTOTYPES_ADDED, L.PROTOTYPES_CFAR, L.PROTOTYPES_CFAR_MC, L.PROTOTYPES_LAZY_COV, L.PROTOTYPES_TARGETS_UPA,
-                                           L.PROTOTYPES_BEAMS, L.PROTOTYPES_REFINE, L.PROTOTYPES_CLEAN))
-    fn = getattr(lib, name)
-    assert fn.restype is ctypes.c_int and tuple(fn.argtypes) == want
+    lib = L.load()                                                             # (needs no GPU)
     assert lib.isac_abi_version() == 8 == L.ISAC_ABI_VERSION and lib.isac_abi_sizeof(13) == -1
-    assert len(L.PROTOTYPES) == 77
+    fn = lib.isac_resolve_directions
     assert fn(None, None, None, 4, 0, 1, 16, 0.01, 0.0, None, None, None, None, None, None, None, None, None, None) == 1   # refused before anything touches a device: no context
     assert callable(load_pkg().sensing.estimation.resolveDirections)

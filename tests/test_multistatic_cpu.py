@@ -4,7 +4,6 @@ device library is not asked for anything but its symbol table."""
 from __future__ import annotations
 
 import copy
-import ctypes
 import os
 import re
 from types import SimpleNamespace
@@ -106,16 +105,11 @@ def test_bistatic_and_direct_paths_follow_their_formulas():
 
 # ---------------------------------------------------------------- (c) header and binding
 def test_binding_has_the_prototypes_and_the_abi_is_unchanged(binding):
-    """include/isac_multistatic.h is additive under ABI 8 and included by isac.h; it declares exactly two functions, which are exported and carry their lines in
-    PROTOTYPES_MULTISTATIC and in no other table -- re-derived here from the header by the typing rule of tests/test_abi_cpu.py (scalars by their C type, a pointer to a struct
-    with a mirror -> POINTER(mirror), every other pointer -> c_void_p).  No new struct, no new isac_abi_sizeof selector, ABI version 8; the header states the limits, the
-    refusals and what is out of scope."""
+    """include/isac_multistatic.h is additive under ABI 8: no new struct, no new isac_abi_sizeof selector; the header states the limits, the refusals and what is out of
+    scope, and its two functions refuse a NULL context.  (Their prototype lines are compared with the header by tests/test_abi_cpu.py, row "isac_multistatic.h".)"""
     L = binding
     hdr = open(os.path.join(ROOT, "include", "isac_multistatic.h")).read()
-    assert '#include "isac_multistatic.h"' in open(os.path.join(ROOT, "include", "isac.h")).read()
     plain = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
-    protos = re.findall(r"\bint\s+(isac_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", plain)
-    assert [n for n, _ in protos] == list(L.PROTOTYPES_MULTISTATIC) == ["isac_multi_static_channel_dev", "isac_multi_static_sensing_dev"]
     assert "typedef" not in plain and "struct" not in plain and "ISAC_SIZEOF" not in plain
     for macro, want in (("PATHS", 64), ("SOURCES", 32), ("ANTS", 256)):
         assert int(re.search(rf"#define ISAC_MULTISTATIC_MAX_{macro} (\d+)", plain).group(1)) == want == getattr(L, f"ISAC_MULTISTATIC_MAX_{macro}")
@@ -123,26 +117,8 @@ def test_binding_has_the_prototypes_and_the_abi_is_unchanged(binding):
                  "ISAC_ERR_INVALID_ARG", "ISAC_ERR_CAPACITY", "a refused call launches nothing and writes nothing", "bit for bit", "the same seed gives the noise bits",
                  "cached range rows and lazy echo grid"):
         assert word in hdr, word
-    scal = {"int": ctypes.c_int32, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64, "double": ctypes.c_double}
-    mirrors = {"const isac_carrier*": ctypes.POINTER(L.Carrier)}
-    lib = L.load()                                                             # (needs no GPU) load() applied the lines
-    counts = {}
-    for name, params in protos:
-        want = []
-        for p in params.split(","):
-            m = re.fullmatch(r"(.*?)\s*\b\w+\s*(\[\d*\])?", " ".join(p.split()))
-            t = re.sub(r"\s*\*", "*", m.group(1)) + ("*" if m.group(2) else "")
-            want.append(scal[t] if "*" not in t else mirrors.get(t, ctypes.c_void_p))
-        want = tuple(want)
-        counts[name] = len(want)
-        assert L.PROTOTYPES_MULTISTATIC[name] == (ctypes.c_int, want), name
-        assert all(name not in tab for tab in (L.PROTOTYPES, L.PROTOTYPES_ADDED, L.PROTOTYPES_CFAR, L.PROTOTYPES_CFAR_MC, L.PROTOTYPES_LAZY_COV, L.PROTOTYPES_TARGETS_UPA,
-                                               L.PROTOTYPES_BEAMS, L.PROTOTYPES_REFINE, L.PROTOTYPES_CLEAN, L.PROTOTYPES_RELAX, L.PROTOTYPES_DIRECTIONS, L.PROTOTYPES_BEAM_CLEAN))
-        fn = getattr(lib, name)
-        assert fn.restype is ctypes.c_int and tuple(fn.argtypes) == want
-    assert counts == {"isac_multi_static_channel_dev": 20, "isac_multi_static_sensing_dev": 23}
+    lib = L.load()                                                             # (needs no GPU)
     assert lib.isac_abi_version() == 8 == L.ISAC_ABI_VERSION and lib.isac_abi_sizeof(13) == -1
-    assert len(L.PROTOTYPES) == 77
     assert lib.isac_multi_static_channel_dev(*([None] * 3), 1, 1, 1.0, 1.0, 0.0, 1, 1, *([None] * 6), 0, None, 0, None) == 1      # refused before anything touches a device: no context
     assert lib.isac_multi_static_sensing_dev(*([None] * 3), 1, 1, 1.0, 1.0, 0.0, 1, 1, *([None] * 6), 0, None, 0, 1, None, None, None) == 1
     pkg = load_pkg()

@@ -76,9 +76,8 @@ def test_known_snapshots_kat5(n_ants):
 
 
 def test_binding_has_the_prototype_and_the_abi_version_is_unchanged():
-    """The entry point is additive under ABI 8: it is declared in include/isac_targets.h (which isac.h includes), and the binding carries its line in PROTOTYPES_ADDED and
-    its struct in ABI_STRUCTS_ADDED -- PROTOTYPES / ABI_STRUCTS stay the image of isac.h's own declarations that tests/test_abi_cpu.py compares them with.  The line is
-    re-derived here from the header by that test's typing rule: scalars by their C type, every pointer without a POINTER(mirror) rule -> c_void_p."""
+    """The entry point is additive under ABI 8: it is declared in include/isac_targets.h, and the binding carries its struct as selector 11 of ABI_STRUCTS.  (Its
+    prototype line is compared with the header by tests/test_abi_cpu.py, row "isac_targets.h".)"""
     import os
     import re
     import __graft_entry__ as g
@@ -87,23 +86,11 @@ def test_binding_has_the_prototype_and_the_abi_version_is_unchanged():
     L = load_pkg()._lib
     assert L.ISAC_ABI_VERSION == 8
     hdr = open(os.path.join(ROOT, "include", "isac_targets.h")).read()
-    assert '#include "isac_targets.h"' in open(os.path.join(ROOT, "include", "isac.h")).read()
-    plain = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
-    protos = re.findall(r"\bint\s+(isac_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", plain)
-    assert [n for n, _ in protos] == list(L.PROTOTYPES_ADDED) == ["isac_fft2d_get_targets"]
-    scal = {"int": ctypes.c_int32, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "double": ctypes.c_double}
-    for name, params in protos:
-        types = [re.fullmatch(r"(.*?)\s*\b\w+", " ".join(p.split())).group(1) for p in params.split(",")]
-        want = tuple(ctypes.c_void_p if "*" in t else scal[t] for t in types)
-        assert L.PROTOTYPES_ADDED[name] == (ctypes.c_int, want)
-        assert name not in L.PROTOTYPES
     sel = int(re.search(r"#define ISAC_SIZEOF_TARGET_LIST (\d+)", hdr).group(1))
-    assert L.ABI_STRUCTS_ADDED == ((sel, "isac_target_list", L.TargetList),) and sel == len(L.ABI_STRUCTS)
+    assert sel == 11 and L.ABI_STRUCTS[sel] == ("isac_target_list", L.TargetList)
     assert int(re.search(r"#define ISAC_MAX_TARGETS (\d+)", hdr).group(1)) == L.ISAC_MAX_TARGETS == 1024
     assert ctypes.sizeof(L.TargetList) == 8 + 1024 * (3 * 4 + 4 * 8)
-    lib = L.load()                                                             # (needs no GPU) load() applied the line and checked the struct size
-    fn = lib.isac_fft2d_get_targets
-    assert fn.restype is ctypes.c_int and tuple(fn.argtypes) == want
+    lib = L.load()                                                             # (needs no GPU) load() checked the struct size
     assert lib.isac_abi_sizeof(sel) == ctypes.sizeof(L.TargetList) and lib.isac_abi_version() == 8
 
 

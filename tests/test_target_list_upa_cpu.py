@@ -3,7 +3,6 @@ tests/test_gpu_target_list_upa.py uses, the restatement of step 4 against a brut
 elevations."""
 from __future__ import annotations
 
-import ctypes
 import math
 import os
 import re
@@ -14,6 +13,7 @@ import pytest
 
 from conftest import ROOT, load_pkg
 
+import _abi_header as H
 import _target_list_upa_restatement as R
 import _upa_restatement as U
 
@@ -61,30 +61,17 @@ def test_restatement_against_brute_force(n_v, n_h):
 
 
 def test_binding_has_the_prototype_and_the_abi_is_unchanged():
-    """include/isac_targets_upa.h is additive under ABI 8 and included by isac.h; it declares exactly one function, which is exported and carries its line in
-    PROTOTYPES_TARGETS_UPA and in no other table -- re-derived here from the header by the typing rule of tests/test_abi_cpu.py (scalars by their C type, a pointer without
-    a POINTER(mirror) rule -> c_void_p).  No new struct, no new isac_abi_sizeof selector, ABI version 8, the older tables as they were."""
+    """include/isac_targets_upa.h is additive under ABI 8: no new struct, no new isac_abi_sizeof selector; its one function takes the C types below and refuses a NULL
+    context.  (Its prototype line is compared with the header by tests/test_abi_cpu.py, row "isac_targets_upa.h".)"""
     import __graft_entry__ as g
     g.build()
     L = load_pkg()._lib
     hdr = open(os.path.join(ROOT, "include", "isac_targets_upa.h")).read()
-    assert '#include "isac_targets_upa.h"' in open(os.path.join(ROOT, "include", "isac.h")).read()
     plain = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
-    protos = re.findall(r"\bint\s+(isac_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", plain)
-    assert [n for n, _ in protos] == list(L.PROTOTYPES_TARGETS_UPA) == ["isac_fft2d_get_targets_upa"]
     assert "typedef" not in plain and "ISAC_SIZEOF" not in plain
-    scal = {"int": ctypes.c_int32, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "double": ctypes.c_double}
-    lib = L.load()                                                             # (needs no GPU) load() applied the line
-    for name, params in protos:
-        types = [re.sub(r"\s*\*", "*", re.fullmatch(r"(.*?)\s*\b\w+", " ".join(p.split())).group(1)) for p in params.split(",")]
-        assert types == ["isac_ctx*", "isac_target_list*", "double*", "isac_c64*", "int32_t"]
-        want = tuple(ctypes.c_void_p if "*" in t else scal[t] for t in types)
-        assert L.PROTOTYPES_TARGETS_UPA[name] == (ctypes.c_int, want)
-        assert all(name not in tab for tab in (L.PROTOTYPES, L.PROTOTYPES_ADDED, L.PROTOTYPES_CFAR, L.PROTOTYPES_CFAR_MC, L.PROTOTYPES_LAZY_COV))
-        fn = getattr(lib, name)
-        assert fn.restype is ctypes.c_int and tuple(fn.argtypes) == want
+    assert [types for _, _, types in H.prototypes("isac_targets_upa.h")] == [["isac_ctx*", "isac_target_list*", "double*", "isac_c64*", "int32_t"]]
+    lib = L.load()                                                             # (needs no GPU)
     assert lib.isac_abi_version() == 8 == L.ISAC_ABI_VERSION and lib.isac_abi_sizeof(13) == -1
-    assert len(L.PROTOTYPES) == 77 and list(L.PROTOTYPES_ADDED) == ["isac_fft2d_get_targets"]
     assert lib.isac_fft2d_get_targets_upa(None, None, None, None, 0) == 1      # refused before anything touches a device: no context (ISAC_ERR_INVALID_ARG)
     est = load_pkg().sensing.estimation
     assert callable(est.targetListUPA) and est.targetListUPA is not est.targetList
