@@ -154,8 +154,9 @@ ISAC_CANCEL_PATHS_MAX_REFS = 32
 #   every other pointer (data, out-scalars, T[] parameters, isac_ctx*, void*, pointer to pointer) -> c_void_p: takes byref(x), ctypes arrays,
 #       ndarray.ctypes.data_as(c_void_p), a DeviceArray, ctx.handle, None
 #   returns: c_char_p for isac_last_error, c_int (an isac_status) for everything else.
-# A new entry point = one line under its header's key here (a new header: a new key, where isac.h includes it) and one row (name, argument count) in the HEADERS table
-# of tests/test_abi_cpu.py, which fails if the line disagrees with the header.
+# HEADER_PROTOTYPES is include/isac.h and the headers it includes, and tests/test_abi_cpu.py pins its keys and counts (95 functions, 77 of them in isac.h).  A new entry
+# point goes into a header that includes isac.h and is not included by it: one line under that header's key in STANDALONE_PROTOTYPES below, and a test of its own that
+# re-derives the line from the header with tests/_abi_header.py (tests/test_subsample_cpu.py is the pattern).
 _INT, _I32, _I64, _U64, _SZ, _F64, _P, _ptr = C.c_int, C.c_int32, C.c_int64, C.c_uint64, C.c_size_t, C.c_double, C.c_void_p, C.POINTER
 _MULTISTATIC_ARGS = (_P, _P, _P, _I32, _I64, _F64, _F64, _F64, _I32, _I32, _P, _P, _P, _P, _P, _P, _I32, _P, _U64)   # ctx .. seed: what the two isac_multistatic.h calls share
 HEADER_PROTOTYPES = {
@@ -284,6 +285,14 @@ HEADER_PROTOTYPES = {
     },
 }
 PROTOTYPES = {name: line for table in HEADER_PROTOTYPES.values() for name, line in table.items()}
+# The stand-alone headers: they include isac.h and are not included by it (a host that wants their calls includes them).  Same typing rule; load() applies the table after
+# PROTOTYPES.  tests/test_subsample_cpu.py re-derives these lines from the header.
+STANDALONE_PROTOTYPES = {
+    "isac_subsample.h": {
+        "isac_multi_static_sensing_frac_dev": (_INT, _MULTISTATIC_ARGS[:12] + (_P,) + _MULTISTATIC_ARGS[12:] + (_I32, _ptr(Carrier), _P, _P)),
+        "isac_range_refine_dev": (_INT, (_P, _ptr(EstParams), _P, _P, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _P)),
+    },
+}
 
 
 def library_path() -> str:
@@ -310,7 +319,7 @@ def load():
             except Exception:
                 pass
         lib = C.CDLL(_LIB_PATH, mode=C.RTLD_GLOBAL)
-        for name, (restype, argtypes) in PROTOTYPES.items():
+        for name, (restype, argtypes) in list(PROTOTYPES.items()) + [line for table in STANDALONE_PROTOTYPES.values() for line in table.items()]:
             fn = getattr(lib, name)  # AttributeError here = ABI drift between the headers and the .so
             fn.restype, fn.argtypes = restype, argtypes
         # the library writes whole structs into caller memory: version AND struct sizes must match this binding's mirrors

@@ -22,6 +22,7 @@
 #include "isac_internal.hpp"
 #include "fft_lds.hpp"
 #include "echo_dev.hpp"
+#include "../../include/isac_subsample.h"
 #include "beam_window.hpp"
 
 namespace isac {
@@ -800,10 +801,11 @@ static int launch_echo_range(isac_ctx* ctx, Kern kern, int L_whole, int A, size_
 // samples (monoStaticSensing.m:16), or -- spectral noise modes -- of the Q coefficient vectors and the spectral synthesis; zero-padding up to tx_dim_l symbols (:19-21).
 // The tail of isac_mono_static_sensing_dev and isac_multi_static_sensing_dev.
 static int grid_from_coefs(isac_ctx* ctx, const OfdmGeom& g, long long T, int A, int Q, double n0, int tx_dim_l, int noise_mode, const c64* d_noise,
-                           uint64_t seed, c64* d_grid, int32_t* l_out) {
+                           uint64_t seed, c64* d_grid, int32_t* l_out, const PathFrac* frac = nullptr /* spectral modes: fractional delays of the Q paths (include/isac_subsample.h) */) {
   const int L_whole = whole_symbols(g, T);
   if (L_whole <= 0) return fail(ctx, ISAC_ERR_SHORT_WAVEFORM, "waveform shorter than one OFDM symbol");
   if (spectral_mode(noise_mode)) ISAC_TRY(demod_coefs(ctx, g, T, Q, L_whole));
+  if (frac) ISAC_TRY(isac_path_frac_ramp_on(ctx, ctx->stream, *frac, g.n_sc, g.nfft, L_whole, Q));
   const int L_out = padded_symbols(L_whole, tx_dim_l, l_out);
   if (L_out > L_whole) ISAC_HIP(hipMemsetAsync(d_grid, 0, sizeof(c64) * (size_t)g.n_sc * L_out * A, ctx->stream));
   if (spectral_mode(noise_mode)) {
@@ -875,10 +877,11 @@ extern "C" int isac_multi_static_channel_dev(isac_ctx* ctx, const isac_c64* cons
   return waveform_from_coefs(ctx, T, n_ants, n_paths, n0, noise_mode, (const c64*)d_noise_unit, seed, (c64*)d_rx_wave);
 }
 
-extern "C" int isac_multi_static_sensing_dev(isac_ctx* ctx, const isac_c64* const* d_tx_waves, const int32_t* n_ants_src, int32_t n_sources, int64_t T, double fc, double fs,
-                                             double n0, int32_t n_ants, int32_t n_paths, const int32_t* path_source, const int64_t* path_shift, const double* path_doppler_hz,
-                                             const double* path_gain, const isac_c64* path_tx_steering, const isac_c64* path_rx_steering, int noise_mode,
-                                             const isac_c64* d_noise_unit, uint64_t seed, int32_t tx_dim_l, const isac_carrier* carrier, isac_c64* d_echo_grid, int32_t* l_out) {
+// The body of isac_multi_static_sensing_dev and isac_multi_static_sensing_frac_dev (include/isac_subsample.h); path_frac == NULL: the former
+static int multi_static_sensing(isac_ctx* ctx, const isac_c64* const* d_tx_waves, const int32_t* n_ants_src, int32_t n_sources, int64_t T, double fc, double fs,
+                                double n0, int32_t n_ants, int32_t n_paths, const int32_t* path_source, const int64_t* path_shift, const double* path_frac, const double* path_doppler_hz,
+                                const double* path_gain, const isac_c64* path_tx_steering, const isac_c64* path_rx_steering, int noise_mode,
+                                const isac_c64* d_noise_unit, uint64_t seed, int32_t tx_dim_l, const isac_carrier* carrier, isac_c64* d_echo_grid, int32_t* l_out) {
   ISAC_ENTER(ctx);
   ISAC_TRY(check_carrier(ctx, carrier));
   if (!d_echo_grid) return fail(ctx, ISAC_ERR_INVALID_ARG, "echo_grid is NULL");
@@ -887,12 +890,36 @@ extern "C" int isac_multi_static_sensing_dev(isac_ctx* ctx, const isac_c64* cons
   if (noise_mode < ISAC_NOISE_NONE || noise_mode > ISAC_NOISE_INJECTED_SPECTRAL) return fail(ctx, ISAC_ERR_INVALID_ARG, "unknown noise mode");
   const PathCoefJob j{(const c64* const*)d_tx_waves, n_ants_src, T, fc, fs, n_ants, n_paths, path_source, path_shift, path_doppler_hz, path_gain, path_tx_steering, path_rx_steering};
   ISAC_TRY(check_paths(ctx, j, n_sources));
+  bool any_frac = false;                                                 // include/isac_subsample.h: every delta in [0, 1); a non-zero one needs a spectral mode
+  for (int p = 0; path_frac && p < n_paths; ++p) {
+    if (!(path_frac[p] >= 0.0 && path_frac[p] < 1.0)) return fail(ctx, ISAC_ERR_INVALID_ARG, "a path_frac outside [0, 1) or not finite");
+    any_frac |= path_frac[p] != 0.0;
+  }
+  if (any_frac && !spectral_mode(noise_mode)) return fail(ctx, ISAC_ERR_UNSUPPORTED, "a fractional path delay needs a spectral noise mode: the waveform route would need an interpolation filter");
   const OfdmGeom g = geom_of(carrier);
   if (whole_symbols(g, T) <= 0) return fail(ctx, ISAC_ERR_SHORT_WAVEFORM, "waveform shorter than one OFDM symbol");   // (before any launch: a refused call writes nothing)
   ctx->range_cache.valid = false;
   ctx->lazy.valid = false;
   ISAC_TRY(isac_path_coefs_on(ctx, ctx->stream, j));
-  return grid_from_coefs(ctx, g, T, n_ants, n_paths, n0, tx_dim_l, noise_mode, (const c64*)d_noise_unit, seed, (c64*)d_echo_grid, l_out);
+  const PathFrac pf{path_frac, fc, fs};
+  return grid_from_coefs(ctx, g, T, n_ants, n_paths, n0, tx_dim_l, noise_mode, (const c64*)d_noise_unit, seed, (c64*)d_echo_grid, l_out, any_frac ? &pf : nullptr);
+}
+
+extern "C" int isac_multi_static_sensing_dev(isac_ctx* ctx, const isac_c64* const* d_tx_waves, const int32_t* n_ants_src, int32_t n_sources, int64_t T, double fc, double fs,
+                                             double n0, int32_t n_ants, int32_t n_paths, const int32_t* path_source, const int64_t* path_shift, const double* path_doppler_hz,
+                                             const double* path_gain, const isac_c64* path_tx_steering, const isac_c64* path_rx_steering, int noise_mode,
+                                             const isac_c64* d_noise_unit, uint64_t seed, int32_t tx_dim_l, const isac_carrier* carrier, isac_c64* d_echo_grid, int32_t* l_out) {
+  return multi_static_sensing(ctx, d_tx_waves, n_ants_src, n_sources, T, fc, fs, n0, n_ants, n_paths, path_source, path_shift, nullptr, path_doppler_hz, path_gain, path_tx_steering,
+                              path_rx_steering, noise_mode, d_noise_unit, seed, tx_dim_l, carrier, d_echo_grid, l_out);
+}
+
+extern "C" int isac_multi_static_sensing_frac_dev(isac_ctx* ctx, const isac_c64* const* d_tx_waves, const int32_t* n_ants_src, int32_t n_sources, int64_t T, double fc, double fs,
+                                                  double n0, int32_t n_ants, int32_t n_paths, const int32_t* path_source, const int64_t* path_shift, const double* path_frac,
+                                                  const double* path_doppler_hz, const double* path_gain, const isac_c64* path_tx_steering, const isac_c64* path_rx_steering,
+                                                  int noise_mode, const isac_c64* d_noise_unit, uint64_t seed, int32_t tx_dim_l, const isac_carrier* carrier, isac_c64* d_echo_grid,
+                                                  int32_t* l_out) {
+  return multi_static_sensing(ctx, d_tx_waves, n_ants_src, n_sources, T, fc, fs, n0, n_ants, n_paths, path_source, path_shift, path_frac, path_doppler_hz, path_gain, path_tx_steering,
+                              path_rx_steering, noise_mode, d_noise_unit, seed, tx_dim_l, carrier, d_echo_grid, l_out);
 }
 
 extern "C" int isac_mono_static_sensing_fused_dev(isac_ctx* ctx, const isac_c64* d_tx_wave, int64_t T, int32_t tx_dim_l,

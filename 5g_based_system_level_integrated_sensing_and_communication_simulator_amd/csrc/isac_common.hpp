@@ -245,6 +245,7 @@ struct isac_ctx {
   isac::DevBuf relax;                // isac_fft2d_relax_targets (relax.hip): [residual rows | tone amplitudes n x span x A | snapshots] c64, [nu | previous nu | power], the entries' rows, spans and schedule, the symbol mask
   isac::DevBuf directions;           // isac_resolve_directions (directions.hip): the snapshots [A x n], the sources' amplitudes and directions [K x n], residuals, counts
   isac::DevBuf cancel_paths;         // isac_cancel_paths_dev (cancel_paths.hip): the Gram pass's partial tiles and power partials, [G | B] and C, the subtract pass's power partials, the status record
+  isac::DevBuf range_refine;         // isac_range_refine_dev (range_refine.hip): a chunk's contracted planes [16][A][K] and Doppler phasors [L x 16], the chunk's nu / rows, the entries' status / rho / power / snapshots
   isac::DevBuf cfar_mc;             // isac_cfar_monte_carlo (cfar.hip): detection counts, per-trial flags
   isac::RangeCache range_cache;
   isac::LazyEcho lazy;               // the echo grid of the last fused monoStaticSensing call when the caller passed no array for it

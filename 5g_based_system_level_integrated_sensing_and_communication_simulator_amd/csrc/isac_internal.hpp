@@ -152,6 +152,12 @@ struct PathCoefJob {
   const isac_c64* path_tx_steering; const isac_c64* path_rx_steering;
 };
 int isac_path_coefs_on(isac_ctx* ctx, hipStream_t st, const PathCoefJob& j);   // coef [P x T] -> ctx->coef, phase_rx [T] -> ctx->phase_rx, rx steering [A x P] and its transpose -> ctx->steer
+// The fractional delays of include/isac_subsample.h on the demodulated coefficient grids D [n_sc x L_whole x P] in ctx->dgrid: D_p <- D_p exp(-2 pi j (frac(fc delta_p / fs) +
+// m_k delta_p / Nfft)), one element-wise launch on st; a path with delta_p == 0 keeps its bits.  frac [P]: host, every value in [0, 1), at least one not zero (checked by the caller).
+struct PathFrac { const double* frac; double fc, fs; };
+int isac_path_frac_ramp_on(isac_ctx* ctx, hipStream_t st, const PathFrac& f, int n_sc, int nfft, int L_whole, int n_paths);
+// ---------------------------------------------------------------- range_refine.hip: isac_range_refine_dev (include/isac_subsample.h) -- off-grid range of listed targets from the two grids of a CPI.  Reads
+// nothing of the context but the cached Kaiser window (isac_get_windows), writes ctx->range_refine only; calls and is called by no other unit.
 // ---------------------------------------------------------------- cancel_paths.hip: isac_cancel_paths_dev (include/isac_cancel_paths.h) -- known reference signals projected out of a received waveform.  Calls
 // isac_path_coefs_on (unit gains, one receive element: the reference columns R [M x T] in ctx->coef; ctx->steer and ctx->phase_rx are rewritten with them) and is called by no
 // other unit; its own scratch is ctx->cancel_paths.

@@ -69,9 +69,41 @@ __global__ __launch_bounds__(256) void path_coef_kernel(const PathTile* __restri
   }
 }
 
+// The fractional delays of include/isac_subsample.h: D_p[k, l] <- D_p[k, l] exp(-2 pi j (c_p + (k - n_sc/2) delta_p / Nfft)), c_p = frac(fc delta_p / fs) formed on the
+// host.  One thread per element of a path's grid (blockIdx.y = p), k fastest; the turn count is reduced modulo 1 before one sincospi.  delta_p == 0: the path's workgroups
+// return at once (uniform) and its values keep their bits.
+struct PathFracArg { double carrier[ISAC_MULTISTATIC_MAX_PATHS], delta[ISAC_MULTISTATIC_MAX_PATHS]; };
+__global__ __launch_bounds__(256) void path_frac_ramp_kernel(c64* __restrict__ D /* [n_sc x L_whole x P] */, int n_sc, long long per_path /* n_sc L_whole */, double nfft, PathFracArg f) {
+  const int p = blockIdx.y;
+  const double delta = f.delta[p];
+  if (delta == 0.0) return;
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= per_path) return;
+  const int k = (int)(i % n_sc);
+  double t = f.carrier[p] + ((double)(k - n_sc / 2) * delta) / nfft;     // turns
+  t -= rint(t);
+  double s, co;
+  sincospi(-2.0 * t, &s, &co);
+  c64* d = D + per_path * p + i;
+  *d = *d * mk(co, s);
+}
+
 }  // namespace isac
 
 using namespace isac;
+
+int isac_path_frac_ramp_on(isac_ctx* ctx, hipStream_t st, const PathFrac& f, int n_sc, int nfft, int L_whole, int n_paths) {
+  PathFracArg arg{};
+  for (int p = 0; p < n_paths; ++p) {
+    const double turns = f.fc * f.frac[p] / f.fs;
+    arg.carrier[p] = turns - std::floor(turns);
+    arg.delta[p] = f.frac[p];
+  }
+  const long long per_path = (long long)n_sc * L_whole;
+  hipLaunchKernelGGL(path_frac_ramp_kernel, dim3(cdiv(per_path, 256), (unsigned)n_paths), dim3(256), 0, st, (c64*)ctx->dgrid.p, n_sc, per_path, (double)nfft, arg);
+  ISAC_HIP(hipGetLastError());
+  return ISAC_OK;
+}
 
 constexpr int kPathTile = 8;
 

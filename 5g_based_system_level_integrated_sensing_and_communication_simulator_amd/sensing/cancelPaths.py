@@ -8,7 +8,7 @@ from types import SimpleNamespace
 import numpy as np
 
 from .. import _lib as L
-from .channelModels.multiStaticChannel import PathBlock
+from .channelModels.multiStaticChannel import PathBlock, whole_sample_paths
 
 
 def cancelPaths(rxWaveform, txWaveforms, radarParams, refs, *, loading=0.0, out=None, ctx=None, return_info=False):
@@ -23,6 +23,7 @@ def cancelPaths(rxWaveform, txWaveforms, radarParams, refs, *, loading=0.0, out=
 
     ``return_info``: also a namespace with coef [nRefs x nAnts], power_in, power_out [nAnts] (sum |.|^2 before and after) and removed_dB = 10 log10(power_in / power_out)."""
     dev = isinstance(rxWaveform, L.DeviceArray)
+    whole_sample_paths(refs, "cancelPaths")                                 # a multiStaticPaths(subSample=True) record handed over as it is
     src = np.ascontiguousarray(np.asarray(refs.source).reshape(-1), dtype=np.int32)
     M = int(src.size)
     A = int(radarParams.nTxAnts)

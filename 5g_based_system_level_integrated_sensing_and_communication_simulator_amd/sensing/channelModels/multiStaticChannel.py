@@ -13,9 +13,19 @@ from ... import _lib as L
 from ..radarParams import LIGHTSPEED, _db2pow, radarParams, steeringVector
 
 
+def whole_sample_paths(paths, who):
+    """ValueError for a record of multiStaticPaths(subSample=True) with a non-zero fraction, in a call whose model is the reference's whole-sample delay: the record's
+    shift is floor(tau / Ts), one sample short of the ceil(tau / Ts) those calls document, and taking it silently would mis-round every path."""
+    frac = getattr(paths, "frac", None)
+    if frac is not None and np.any(np.asarray(frac, dtype=np.float64) != 0.0):
+        raise ValueError(f"{who} delays by whole samples (ceil(tau / Ts)): a record with fractional delays (multiStaticPaths(subSample=True): shift = floor(tau / Ts)) is "
+                         "served by multiStaticSensing in the spectral noise modes only")
+
+
 class PathBlock:
     """The flat arrays of the two multi-static entry points, from (txWaveforms, radarParams, paths); keeps every host buffer alive for the call.  ``args``: ctx .. seed
-    without the three noise arguments, in include/isac_multistatic.h's order."""
+    without the three noise arguments, in include/isac_multistatic.h's order.  A record with ``frac`` (multiStaticPaths(subSample=True)): ``frac`` [P] and ``args_frac``, the
+    same with path_frac behind path_shift -- include/isac_subsample.h's order; ``frac`` is None for a record without it."""
 
     def __init__(self, ctx, txWaveforms, rp, paths):
         waves = list(txWaveforms)
@@ -50,6 +60,11 @@ class PathBlock:
         p_ = lambda a: a.ctypes.data_as(C.c_void_p)
         self.args = (self.ctx.handle, self.ptrs, p_(self.n_ants_src), len(waves), self.T, float(rp.fc), float(rp.fs), float(rp.N0), self.A, P,
                      p_(self.source), p_(self.shift), p_(self.doppler), p_(self.gain), p_(self.tx), p_(self.rx))
+        self.frac = L.as_f64(paths.frac) if getattr(paths, "frac", None) is not None else None
+        if self.frac is not None:
+            if self.frac.size != P:
+                raise ValueError("paths.frac must have one value per path")
+            self.args_frac = self.args[:12] + (p_(self.frac),) + self.args[12:]
 
     def noise(self, noise):
         """The noise argument on the device (kept alive with the block)."""
@@ -64,6 +79,7 @@ def multiStaticChannel(txWaveforms, radarParams, paths, *, noise=None, seed=None
     ``txWaveforms``: one [T x nAnts_s] array per source -- DeviceArrays (the result stays in HBM) or NumPy arrays (NumPy result); None for a source no path names.
     ``radarParams``: fc, fs, N0 and nTxAnts (the receive array) of the receiving cell.  ``paths``: the record ``multiStaticPaths`` returns (source, shift, doppler [Hz], gain,
     txSteering, rxSteering).  ``noise`` / ``seed`` as in basicRadarChannel.  No path -> IsacError NO_LOS."""
+    whole_sample_paths(paths, "multiStaticChannel")
     b = PathBlock(ctx, txWaveforms, radarParams, paths)
     mode = L.NOISE_INJECTED if noise is not None else (L.NOISE_PHILOX if seed is not None else L.NOISE_NONE)
     out = b.ctx.empty((b.T, b.A))
@@ -77,7 +93,7 @@ def _direction(frm, to):
     return np.rad2deg(np.arctan2(y, x)), np.rad2deg(np.arctan2(z, np.hypot(x, y))), np.sqrt(x * x + y * y + z * z)
 
 
-def multiStaticPaths(rxCell, sources, targets, *, carrierInfo, waveInfo, directLoS=None, targetLoS=None, directLossdB=0.0):
+def multiStaticPaths(rxCell, sources, targets, *, carrierInfo, waveInfo, directLoS=None, targetLoS=None, directLossdB=0.0, subSample=False):
     """The path list of one receiving cell from geometry (host helper; radarParams.py's own expressions: steeringVector with its lambda quirk, ceil(tau / Ts)).
 
     ``rxCell``: the receiving cell's parameters (what sensing.radarParams takes).  ``sources``: one cell-parameter record per transmitter, in the order of the waveform list
@@ -89,6 +105,10 @@ def multiStaticPaths(rxCell, sources, targets, *, carrierInfo, waveInfo, directL
     ``directLoS`` [S] and ``targetLoS`` [S x Q] are line-of-sight flags as isac_los_check_dev produces them (1 = LoS; None = all): a blocked path is left out.  The receiver's
     own row of ``targetLoS`` is that of the source at its position; where it is not among the sources, ``targetLoS`` has one more row, the receiver's, at the end.
     ``directLossdB``: a scalar or one value per source (a wall in an otherwise direct path).
+
+    ``subSample`` (include/isac_subsample.h): True = no path is rounded up to a whole sample: shift = floor(tau / Ts) and the record gains ``frac`` = tau / Ts - shift in
+    [0, 1), for every path, the receiver's own echoes included (tau = 2 R / c of sensing.radarParams' range); multiStaticSensing then takes the fractional-delay entry
+    point.  False: the record of the reference's ceil, without ``frac``.
 
     Returns a namespace: source, shift, doppler, gain [P], txSteering (list of P vectors), rxSteering [nAnts x P], kind (per path: ("direct", j) or ("target", j, k))."""
     S, Q = len(sources), len(targets)
@@ -119,7 +139,11 @@ def multiStaticPaths(rxCell, sources, targets, *, carrierInfo, waveInfo, directL
         mono = radarParams(c, carrierInfo, waveInfo)
     out = SimpleNamespace(source=[], shift=[], doppler=[], gain=[], txSteering=[], rxSteering=[], kind=[])
 
-    def add(j, shift, f, g, b, a, kind):
+    frac = []
+
+    def add(j, delay, f, g, b, a, kind):                                    # delay: tau / Ts
+        shift = np.floor(delay) if subSample else np.ceil(delay)
+        frac.append(float(delay - shift) if subSample else 0.0)
         out.source.append(j); out.shift.append(int(shift)); out.doppler.append(float(f)); out.gain.append(float(g))
         out.txSteering.append(np.asarray(b, dtype=np.complex128)); out.rxSteering.append(np.asarray(a, dtype=np.complex128)); out.kind.append(kind)
 
@@ -129,20 +153,22 @@ def multiStaticPaths(rxCell, sources, targets, *, carrierInfo, waveInfo, directL
             azi_ij, ele_ij, R = _direction(pos_i, pos_j)
             azi_ji, ele_ji, _ = _direction(pos_j, pos_i)
             g = math.sqrt(At * Ar * lam ** 2 / ((4.0 * np.pi) ** 2 * R ** 2)) * 10.0 ** (-float(loss[j]) / 20.0)
-            add(j, np.ceil(R / LIGHTSPEED / Ts), 0.0, g, steeringVector(arr_j, A_j, lam, azi_ji, ele_ji), steeringVector(arr_i, A, lam, azi_ij, ele_ij), ("direct", j))
+            add(j, R / LIGHTSPEED / Ts, 0.0, g, steeringVector(arr_j, A_j, lam, azi_ji, ele_ji), steeringVector(arr_i, A, lam, azi_ij, ele_ij), ("direct", j))
         for k in range(Q):
             if not (t_los[j, k] and t_los[rx_row, k]):
                 continue
             if own[j]:
-                add(j, np.ceil(2.0 * mono.range[k] / LIGHTSPEED / Ts), 2.0 * mono.velocity[k] / lam, mono.largeScaleFading[k], mono.RxSteeringVec[:, k], mono.RxSteeringVec[:, k],
+                add(j, 2.0 * mono.range[k] / LIGHTSPEED / Ts, 2.0 * mono.velocity[k] / lam, mono.largeScaleFading[k], mono.RxSteeringVec[:, k], mono.RxSteeringVec[:, k],
                     ("target", j, k))
                 continue
             azi_j, ele_j, R_j = _direction(pos_j, t_pos[k])
             azi_i, ele_i, R_i = _direction(pos_i, t_pos[k])
             g = math.sqrt(At * Ar * lam ** 2 * float(targets[k].rcs) / ((4.0 * np.pi) ** 3 * (R_j * R_i) ** 2))   # (R_j R_i)^2: the same bits with j and i exchanged
             f = (speed_towards(k, pos_j) + speed_towards(k, pos_i)) / lam
-            add(j, np.ceil((R_j + R_i) / LIGHTSPEED / Ts), f, g, steeringVector(arr_j, A_j, lam, azi_j, ele_j), steeringVector(arr_i, A, lam, azi_i, ele_i), ("target", j, k))
+            add(j, (R_j + R_i) / LIGHTSPEED / Ts, f, g, steeringVector(arr_j, A_j, lam, azi_j, ele_j), steeringVector(arr_i, A, lam, azi_i, ele_i), ("target", j, k))
     out.source, out.shift = np.asarray(out.source, dtype=np.int32), np.asarray(out.shift, dtype=np.int64)
     out.doppler, out.gain = np.asarray(out.doppler, dtype=np.float64), np.asarray(out.gain, dtype=np.float64)
     out.rxSteering = np.stack(out.rxSteering, axis=1) if out.rxSteering else np.zeros((A, 0), dtype=np.complex128)
+    if subSample:
+        out.frac = np.asarray(frac, dtype=np.float64)
     return out

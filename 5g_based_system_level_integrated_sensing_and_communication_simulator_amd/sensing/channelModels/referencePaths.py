@@ -5,13 +5,18 @@ from types import SimpleNamespace
 
 import numpy as np
 
+from .multiStaticChannel import whole_sample_paths
+
 
 def referencePaths(paths, kinds=("direct",), taps=0):
     """The references ``sensing.cancelPaths`` takes, from a ``multiStaticPaths`` record: the paths whose ``kind`` starts with one of ``kinds`` ("direct", "target"), in the
     record's order, each expanded to the shifts d - taps .. d + taps (ascending, clipped at 0); a reference that repeats an earlier one exactly -- same source, shift, Doppler
     and steering bits -- is left out, since a repeated column makes the fit singular.  Gains and receive steering vectors are not carried over: the fit finds them.
 
+    A record with fractional delays (multiStaticPaths(subSample=True)) is refused with ValueError: the references are delayed by whole samples.
+
     Returns a namespace: source, shift, doppler [M], txSteering (list of M vectors), kind (per reference, the kind of the path it came from)."""
+    whole_sample_paths(paths, "referencePaths")
     taps = int(taps)
     if taps < 0:
         raise ValueError("taps must be >= 0")

@@ -17,7 +17,9 @@ def multiStaticSensing(txWaveforms, txDimension, carrierInfo, radarParams, paths
 
     ``txWaveforms``: one [T x nAnts_s] array per source, DeviceArrays (DeviceArray out) or NumPy arrays (NumPy out); None for a source no path names.  ``radarParams``: fc, fs,
     N0 and nTxAnts (the receive array) of the receiving cell.  ``paths``: sensing.channelModels.multiStaticPaths' record.  ``noise`` / ``seed`` / ``spectral_noise`` /
-    ``noise_domain`` / ``nfft`` / ``out``: as in monoStaticSensing; the noise field is that of the mono-static call with the same seed."""
+    ``noise_domain`` / ``nfft`` / ``out``: as in monoStaticSensing; the noise field is that of the mono-static call with the same seed.  A record with ``frac``
+    (multiStaticPaths(subSample=True)) goes to isac_multi_static_sensing_frac_dev (include/isac_subsample.h): non-zero fractions need a spectral noise mode
+    (``spectral_noise`` or ``seed`` with ``noise_domain="spectral"``), else IsacError UNSUPPORTED."""
     b = PathBlock(ctx, txWaveforms, radarParams, paths)
     car = carrier_block(carrierInfo, nfft)
     if spectral_noise is not None:
@@ -43,5 +45,9 @@ def multiStaticSensing(txWaveforms, txDimension, carrierInfo, radarParams, paths
     elif tuple(out.shape) != shape:
         raise ValueError(f"out must have shape {shape}")
     lo = C.c_int32(0)
-    b.ctx.check(lib.isac_multi_static_sensing_dev(*b.args, mode, b.noise(noise), seed or 0, int(txDimension[1]), C.byref(car), out, C.byref(lo)))
+    tail = (mode, b.noise(noise), seed or 0, int(txDimension[1]), C.byref(car), out, C.byref(lo))
+    if b.frac is not None:                                                  # a record of multiStaticPaths(subSample=True): include/isac_subsample.h
+        b.ctx.check(lib.isac_multi_static_sensing_frac_dev(*b.args_frac, *tail))
+    else:
+        b.ctx.check(lib.isac_multi_static_sensing_dev(*b.args, *tail))
     return out if b.dev else out.numpy()

@@ -36,7 +36,8 @@
  * ULA and UPA alike, the UPA with ISAC_OPT_UPA_DOA on or off.  Runs on the context's stream in scratch of its own and returns when complete; every other getter's answer, a
  * pending submit and its result buffer stay untouched.
  *
- * OUT OF SCOPE: off-grid range (only a window of range rows is kept: band-limited interpolation would be approximate); off-grid direction (a call of its own on the snapshots this one returns: isac_resolve_directions, isac_directions.h); merging of range sidelobes (the
+ * OUT OF SCOPE: off-grid range (only a window of range rows is kept: band-limited interpolation would be approximate -- a call of its own on the two grids:
+ * isac_range_refine_dev, isac_subsample.h); off-grid direction (a call of its own on the snapshots this one returns: isac_resolve_directions, isac_directions.h); merging of range sidelobes (the
  * Kaiser range window leaves none in the project's scenes); a MEX command.
  */
 #ifndef ISAC_REFINE_H
