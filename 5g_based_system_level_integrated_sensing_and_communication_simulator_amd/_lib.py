@@ -295,6 +295,18 @@ STANDALONE_PROTOTYPES = {
 }
 
 
+# include/isac_localize.h, stand-alone like isac_subsample.h (tests/test_subsample_cpu.py pins the keys of the table above, so this header has a table of its own).  Same
+# typing rule; load() applies it after the other two.  tests/test_localize_cpu.py re-derives these lines from the header.
+_LOCALIZE_SCENE = (_P, _P, _I32, _P, _P, _I32, _P, _P, _P, _P, _P, _P, _P, _I32, _F64, _F64, _I32, _F64, _F64, _I32, _F64, _P)   # ctx .. the map: what the two calls share
+LOCALIZE_PROTOTYPES = {
+    "isac_localize.h": {
+        "isac_position_map_dev": (_INT, _LOCALIZE_SCENE),
+        "isac_localize_dev": (_INT, _LOCALIZE_SCENE + (_F64, _I32, _I32, _F64, _I32, _F64, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P)),
+    },
+}
+ISAC_LOCALIZE_MAX_NODES, ISAC_LOCALIZE_MAX_LINKS, ISAC_LOCALIZE_MAX_MEAS, ISAC_LOCALIZE_MAX_CAND = 64, 256, 4096, 256
+
+
 def library_path() -> str:
     return _LIB_PATH
 
@@ -319,7 +331,7 @@ def load():
             except Exception:
                 pass
         lib = C.CDLL(_LIB_PATH, mode=C.RTLD_GLOBAL)
-        for name, (restype, argtypes) in list(PROTOTYPES.items()) + [line for table in STANDALONE_PROTOTYPES.values() for line in table.items()]:
+        for name, (restype, argtypes) in list(PROTOTYPES.items()) + [line for tables in (STANDALONE_PROTOTYPES, LOCALIZE_PROTOTYPES) for table in tables.values() for line in table.items()]:
             fn = getattr(lib, name)  # AttributeError here = ABI drift between the headers and the .so
             fn.restype, fn.argtypes = restype, argtypes
         # the library writes whole structs into caller memory: version AND struct sizes must match this binding's mirrors

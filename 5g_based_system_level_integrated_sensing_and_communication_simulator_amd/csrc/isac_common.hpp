@@ -246,7 +246,7 @@ struct isac_ctx {
   isac::DevBuf directions;           // isac_resolve_directions (directions.hip): the snapshots [A x n], the sources' amplitudes and directions [K x n], residuals, counts
   isac::DevBuf cancel_paths;         // isac_cancel_paths_dev (cancel_paths.hip): the Gram pass's partial tiles and power partials, [G | B] and C, the subtract pass's power partials, the status record
   isac::DevBuf range_refine;         // isac_range_refine_dev (range_refine.hip): a chunk's contracted planes [16][A][K] and Doppler phasors [L x 16], the chunk's nu / rows, the entries' status / rho / power / snapshots
-  isac::DevBuf cfar_mc;             // isac_cfar_monte_carlo (cfar.hip): detection counts, per-trial flags
+  isac::DevBuf cfar_mc;            // isac_cfar_monte_carlo (cfar.hip): detection counts, per-trial flags
   isac::RangeCache range_cache;
   isac::LazyEcho lazy;               // the echo grid of the last fused monoStaticSensing call when the caller passed no array for it
   // overlap-save CDL apply (cdl_os.hip): the forward spectra of the last downlink batch, kept in a buffer of their own so that the NEXT batch on this context can reuse them when
@@ -262,6 +262,7 @@ struct isac_ctx {
   int doa2d_rows = 0, doa2d_cols = 0;   // dims of the dB map in doa2d_db (0: none yet)
   isac::StageSlot stage_ring[isac::kStageSlots];   // pinned->device parameter uploads (stage_acquire / stage_commit)
   int stage_next = 0;
+  isac::DevBuf localize;             // isac_position_map_dev / isac_localize_dev (localize.hip): the scene's tables, the blocks' candidate lists [blocks][256], the candidates, the outputs' device copies
 };
 
 namespace isac {

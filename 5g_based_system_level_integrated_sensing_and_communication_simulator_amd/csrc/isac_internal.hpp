@@ -158,6 +158,8 @@ struct PathFrac { const double* frac; double fc, fs; };
 int isac_path_frac_ramp_on(isac_ctx* ctx, hipStream_t st, const PathFrac& f, int n_sc, int nfft, int L_whole, int n_paths);
 // ---------------------------------------------------------------- range_refine.hip: isac_range_refine_dev (include/isac_subsample.h) -- off-grid range of listed targets from the two grids of a CPI.  Reads
 // nothing of the context but the cached Kaiser window (isac_get_windows), writes ctx->range_refine only; calls and is called by no other unit.
+// ---------------------------------------------------------------- localize.hip: isac_position_map_dev, isac_localize_dev (include/isac_localize.h) -- per-link lists fused into positions.  Reads nothing of the
+// context, writes ctx->localize only; calls and is called by no other unit.
 // ---------------------------------------------------------------- cancel_paths.hip: isac_cancel_paths_dev (include/isac_cancel_paths.h) -- known reference signals projected out of a received waveform.  Calls
 // isac_path_coefs_on (unit gains, one receive element: the reference columns R [M x T] in ctx->coef; ctx->steer and ctx->phase_rx are rewritten with them) and is called by no
 // other unit; its own scratch is ctx->cancel_paths.

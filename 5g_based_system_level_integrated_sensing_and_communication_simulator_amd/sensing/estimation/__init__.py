@@ -7,6 +7,8 @@ from .beamWeights import beamWeights  # noqa: F401
 from .beamDetect import beamDetect  # noqa: F401
 from .refineTargets import refineTargets  # noqa: F401
 from .refineRange import refineRange  # noqa: F401
+from .linkMeasurements import linkMeasurements  # noqa: F401
+from .localizeTargets import localizeTargets  # noqa: F401
 from .cleanTargets import cleanTargets  # noqa: F401
 from .beamClean import beamClean  # noqa: F401
 from .relaxTargets import relaxTargets  # noqa: F401

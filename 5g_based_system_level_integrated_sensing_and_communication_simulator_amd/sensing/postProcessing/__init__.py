@@ -1,1 +1,2 @@
 from .getRMSE import getRMSE  # noqa: F401
+from .getPositionRMSE import getPositionRMSE  # noqa: F401
