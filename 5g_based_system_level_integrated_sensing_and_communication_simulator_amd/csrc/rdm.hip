@@ -123,67 +123,102 @@ __global__ __launch_bounds__(512) void doppler_pow_kernel(const c64* __restrict_
 }
 
 // ---------------------------------------------------------------- Doppler, nFFT = 256: two radix-16 passes per row
-// Same staging as doppler_pow_kernel, but each row's zero-padded slow-time sequence goes through a 256-point
-// FFT held by 16 threads (16 points each) instead of a 224-term direct sum per needed bin: ~10x fewer LDS
-// operations.  16 rows x 16 threads = 256 threads per workgroup; the exchange image overlays the staging slab.
-__global__ __launch_bounds__(256, 2) void doppler_fft256_kernel(const c64* __restrict__ ymid, int n_rows, int L, int A,
+// Each row's zero-padded slow-time sequence goes through a 256-point FFT held by 16 threads (16 points each) instead of a 224-term direct sum per needed bin.
+// 16 rows x 16 threads = 256 threads per workgroup; thread (rr = tid & 15, j = tid >> 4) holds x[q] = y[row r0 + rr, (j + 16 q + L/2) mod L, a].
+//   * No staging slab: a thread loads its own inputs straight into the registers dft16 works on, all ceil(Lu / 16) of them in flight together (14 at L = 224; zero
+//     beyond Lu) -- the 16 threads of a (j, q) are 16 consecutive rows of one range column, one 256-byte run.  The kernel has almost no arithmetic for its bytes; the
+//     staged form kept four loads per thread in flight and paid 3.5 dependent round trips per slab.
+//   * The exchange between the passes moves the real and the imaginary plane one after the other through ONE image of doubles, [16 rows][16 k1][17] (+ 1 per row,
+//     kDopPlane below), 35 KB; with the twiddles 39 KB, so four workgroups share a compute unit's LDS (the slab + complex image took 74 KB: two), at <= 128 VGPRs.
+//   * K2MASK: the outputs k2 of the second pass (x[k2] = X[k1 + 16 k2]) that can lie in the power window.  The CFAR window of the default scene reads bins -14 .. 14,
+//     i.e. k2 in {0, 15}: the host launches that instantiation where the window allows it, the other fourteen outputs of the inlined dft16 fall away as dead code, and
+//     the two that stay keep their operations and their order -- the same bits as the full instantiation (kDopAllK2), which every other window takes.
+constexpr unsigned kDopAllK2 = 0xFFFFu, kDopCentreK2 = 0x8001u;
+constexpr int kDopPlane = 16 * 17 + 1;                          // doubles per row of the exchange image.  17 mod 32 repeats the k1 stride: reading [j][d], lanes with equal
+                                                                //  rr + j meet on a bank (up to four where two is the least for 64-bit accesses).  16 * 17 + 4 (20 mod 32: every
+                                                                //  bank twice, both ways) was measured and is SLOWER, 21.8 against 18.1 us (profiles/r14_ab_parent_vs_pr.txt)
+constexpr size_t kDopFft256Lds = sizeof(c64) * 256 + sizeof(double) * kDopRows * kDopPlane;
+static_assert(4 * kDopFft256Lds <= 160 * 1024, "four workgroups per compute unit");
+
+// the k2 set of a window of n_cols columns from col_lo (column c <-> bin (c + 128) mod 256, bin = k1 + 16 k2)
+inline unsigned doppler_k2_mask(int col_lo, int n_cols) {
+  unsigned m = 0u;
+  for (int c = col_lo; c < col_lo + n_cols; ++c) m |= 1u << (((c + 128) & 255) >> 4);
+  return m;
+}
+
+template <unsigned K2MASK>
+__global__ __launch_bounds__(256, 4) void doppler_fft256_kernel(const c64* __restrict__ ymid, int n_rows, int L, int A,
                                                                 const c64* __restrict__ tw_d /* e^{-2 pi j m / 256} */,
                                                                 double sqrt_nfft, int col_lo, int n_cols,
                                                                 double* __restrict__ pwin) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   constexpr int NF = 256, RT = kDopRows;
   c64* s_tw = reinterpret_cast<c64*>(smem_raw);                 // [256]
-  c64* s_y = s_tw + NF;                                         // staging [Lu][RT+1]   /   exchange [RT][16][17]
-  const int Lu = L < NF ? L : NF;
+  double* s_z = reinterpret_cast<double*>(s_tw + NF);           // exchange [RT][kDopPlane]: one plane (re, then im) of [16 k1][17]
+  const int Lu = L < NF ? L : NF;                               // fft(., nFFT, 2) truncates when L > nFFT
   const int a = blockIdx.y;
   const int r0 = blockIdx.x * RT;
   const int tid = threadIdx.x;
-  s_tw[tid] = tw_d[tid];
-  const int half = L / 2;
-  for (int i0 = tid; i0 < Lu * RT; i0 += 4 * blockDim.x) {     // 4 independent loads in flight per thread
-    c64 v[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int i = i0 + u * blockDim.x;
-      const int ii = i < Lu * RT ? i : 0;
-      const int rr = ii % RT, li = ii / RT;
-      int lsrc = li + half;
-      if (lsrc >= L) lsrc -= L;
-      const int row = min(r0 + rr, n_rows - 1);
-      v[u] = ymid[(long long)row + (long long)n_rows * ((long long)lsrc + (long long)L * a)];
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int i = i0 + u * blockDim.x;
-      if (i < Lu * RT) s_y[(i / RT) * (RT + 1) + (i % RT)] = v[u];
-    }
-  }
-  __syncthreads();
-  const int rr = tid >> 4, j = tid & 15;
+  const int rr = tid & 15, j = tid >> 4;
+  const c64 twv = tw_d[tid];
+  const int half = L / 2;                                       // ifftshift: out[i] = in[(i + floor(L/2)) mod L]
+  const c64* src = ymid + min(r0 + rr, n_rows - 1) + (long long)n_rows * L * a;
   c64 x[16];
 #pragma unroll
   for (int q = 0; q < 16; ++q) {
     const int i = j + 16 * q;
-    x[q] = i < Lu ? s_y[i * (RT + 1) + rr] : mk(0.0, 0.0);      // zero-pad L -> 256
+    int lsrc = i + half;
+    if (lsrc >= L) lsrc -= L;
+    x[q] = mk(0.0, 0.0);                                        // zero-pad L -> 256
+    if (i < Lu) x[q] = src[(long long)n_rows * lsrc];
   }
+  s_tw[tid] = twv;
   dft16<-1>(x);
-  __syncthreads();                                              // staging fully consumed: overlay the exchange image
-  c64* s_z = s_y + rr * (16 * 17);
+  __syncthreads();                                              // the twiddles
 #pragma unroll
-  for (int k1 = 0; k1 < 16; ++k1) s_z[k1 * 17 + j] = k1 ? x[k1] * s_tw[j * k1] : x[0];
+  for (int k1 = 1; k1 < 16; ++k1) x[k1] = x[k1] * s_tw[j * k1];
+  double* zw = s_z + rr * kDopPlane + j;                        // thread (rr, j) writes [k1][j]
+  const double* zr = s_z + rr * kDopPlane + j * 17;             // thread (rr, k1 = j) reads [j][d]
+#pragma unroll
+  for (int k1 = 0; k1 < 16; ++k1) zw[k1 * 17] = x[k1].re;
   __syncthreads();
 #pragma unroll
-  for (int d = 0; d < 16; ++d) x[d] = s_z[j * 17 + d];          // thread (rr, k1 = j)
-  dft16<-1>(x);                                                  // x[k2] = X[k1 + 16 k2]
-  const int row = r0 + rr;
+  for (int d = 0; d < 16; ++d) x[d].re = zr[d];
+  __syncthreads();                                              // the real plane is read: the imaginary one takes its place
+#pragma unroll
+  for (int k1 = 0; k1 < 16; ++k1) zw[k1 * 17] = x[k1].im;
+  __syncthreads();
+#pragma unroll
+  for (int d = 0; d < 16; ++d) x[d].im = zr[d];
+  dft16<-1>(x);                                                  // x[k2] = X[k1 + 16 k2], k1 = j
+  // All sixteen outputs live beside the divides and the hypot of the first ones do not fit 128 registers (the compiler spilt six doubles to scratch): the full
+  // instantiation parks its last four in the image -- the 16 doubles at zr are read by this thread alone, and it has read them -- until their turn.
+  constexpr bool PARK = K2MASK == kDopAllK2;
+  double* zp = s_z + rr * kDopPlane + j * 17;
+  if constexpr (PARK) {
+#pragma unroll
+    for (int m = 0; m < 4; ++m) { zp[2 * m] = x[12 + m].re; zp[2 * m + 1] = x[12 + m].im; }
+  }
+  int row = r0 + rr, k1 = j;
+  double sq = sqrt_nfft;
+  asm volatile("" : "+v"(row), "+v"(k1), "+s"(sq));              // (compiler-only) the outputs' columns, addresses and the divisor's reciprocal are formed HERE, not held in
+                                                                 //  registers across the passes: with them the full instantiation does not fit 128 registers
   if (row < n_rows) {
 #pragma unroll
     for (int k2 = 0; k2 < 16; ++k2) {
-      const int kbin = j + 16 * k2;
+      if (!((K2MASK >> k2) & 1u)) continue;                      // (compile time)
+      if constexpr (PARK) {
+        if (k2 == 12) {
+#pragma unroll
+          for (int m = 0; m < 4; ++m) x[12 + m] = mk(zp[2 * m], zp[2 * m + 1]);
+        }
+      }
+      const int kbin = k1 + 16 * k2;
       const int c = (kbin + NF / 2) & (NF - 1);                  // fftshift: column c <-> bin (c + 128) mod 256
       const int cc = c - col_lo;
       if (cc >= 0 && cc < n_cols) {
-        const double re = x[k2].re / sqrt_nfft, im = x[k2].im / sqrt_nfft;
+        const double re = x[k2].re / sq, im = x[k2].im / sq;
         const double h = hypot(re, im);
         pwin[(long long)row + (long long)n_rows * ((long long)cc + (long long)n_cols * a)] = h * h;
       }
@@ -626,9 +661,11 @@ int isac_rdm_power_window(isac_ctx* ctx, const isac_est_params* ep, const isac_c
   }
   const int Lu = L < n_fft ? L : n_fft;
   if (n_fft == 256) {
-    size_t lds = sizeof(c64) * (256 + std::max((size_t)Lu * (kDopRows + 1), (size_t)kDopRows * 16 * 17));
-    ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(doppler_fft256_kernel), lds));
-    hipLaunchKernelGGL(doppler_fft256_kernel, dim3(cdiv(nr, kDopRows), A), dim3(256), lds, ctx->stream, (const c64*)ctx->ymid.p, nr, L,
+    // the window's bins all among the outputs k2 = 0 and 15 of the second pass (bins -16 .. 15): the instantiation that forms only those; any other window: all 16
+    const bool centre = (doppler_k2_mask(col_lo, nc) & ~kDopCentreK2) == 0u;
+    auto kern = centre ? doppler_fft256_kernel<kDopCentreK2> : doppler_fft256_kernel<kDopAllK2>;
+    ISAC_TRY(allow_lds(ctx, reinterpret_cast<const void*>(kern), kDopFft256Lds));
+    hipLaunchKernelGGL(kern, dim3(cdiv(nr, kDopRows), A), dim3(256), kDopFft256Lds, ctx->stream, (const c64*)ctx->ymid.p, nr, L,
                        A, twd, std::sqrt((double)n_fft), col_lo, nc, (double*)ctx->pwin.p);
     ISAC_HIP(hipGetLastError());
   } else {
