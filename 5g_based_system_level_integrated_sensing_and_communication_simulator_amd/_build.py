@@ -14,8 +14,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(HERE, "libisac_hip.so")
-SOURCES = ["capi.hip", "fft2d.hip", "tables.hip", "echo.hip", "rdm.hip", "cov.hip", "eigh.hip", "music.hip", "cdl.hip", "cdl_os.hip", "cqi.hip", "los.hip", "doa2d.hip", "doa.hip", "rxfe.hip", "targets.hip", "cfar.hip", "beams.hip", "refine.hip", "clean.hip", "relax.hip", "directions.hip", "beam_clean.hip", "multistatic.hip", "cancel_paths.hip", "range_refine.hip", "localize.hip"]
-HEADERS = ["isac_common.hpp", "isac_internal.hpp", "cut_window.hpp", "ofdm_symbol.hpp", "beam_window.hpp", "beam_stream.hpp", "noise_walk.hpp", "echo_range_sl_body.inc", "fft_lds.hpp", "echo_dev.hpp", "eigh_dev.hpp", "eigh_layout.hpp", os.path.join("..", "..", "include", "isac.h"), os.path.join("..", "..", "include", "isac_targets.h"), os.path.join("..", "..", "include", "isac_cfar.h"), os.path.join("..", "..", "include", "isac_cfar_mc.h"), os.path.join("..", "..", "include", "isac_lazy_cov.h"), os.path.join("..", "..", "include", "isac_targets_upa.h"), os.path.join("..", "..", "include", "isac_beams.h"), os.path.join("..", "..", "include", "isac_refine.h"), os.path.join("..", "..", "include", "isac_clean.h"), os.path.join("..", "..", "include", "isac_relax.h"), os.path.join("..", "..", "include", "isac_directions.h"), os.path.join("..", "..", "include", "isac_beam_clean.h"), os.path.join("..", "..", "include", "isac_multistatic.h"), os.path.join("..", "..", "include", "isac_cancel_paths.h"), os.path.join("..", "..", "include", "isac_subsample.h"), os.path.join("..", "..", "include", "isac_localize.h"),"upa_steer.hpp", "rdm_cell.hpp", "refine_dev.hpp", "beam_cell.hpp", "cpi_post.hpp"]
+SOURCES = ["capi.hip", "fft2d.hip", "tables.hip", "echo.hip", "rdm.hip", "cov.hip", "eigh.hip", "music.hip", "cdl.hip", "cdl_os.hip", "cqi.hip", "los.hip", "doa2d.hip", "doa.hip", "rxfe.hip", "targets.hip", "cfar.hip", "beams.hip", "refine.hip", "clean.hip", "relax.hip", "directions.hip", "beam_clean.hip", "multistatic.hip", "cancel_paths.hip", "range_refine.hip", "localize.hip", "track.hip"]
+HEADERS = ["isac_common.hpp", "isac_internal.hpp", "cut_window.hpp", "ofdm_symbol.hpp", "beam_window.hpp", "beam_stream.hpp", "noise_walk.hpp", "echo_range_sl_body.inc", "fft_lds.hpp", "echo_dev.hpp", "eigh_dev.hpp", "eigh_layout.hpp", os.path.join("..", "..", "include", "isac.h"), os.path.join("..", "..", "include", "isac_targets.h"), os.path.join("..", "..", "include", "isac_cfar.h"), os.path.join("..", "..", "include", "isac_cfar_mc.h"), os.path.join("..", "..", "include", "isac_lazy_cov.h"), os.path.join("..", "..", "include", "isac_targets_upa.h"), os.path.join("..", "..", "include", "isac_beams.h"), os.path.join("..", "..", "include", "isac_refine.h"), os.path.join("..", "..", "include", "isac_clean.h"), os.path.join("..", "..", "include", "isac_relax.h"), os.path.join("..", "..", "include", "isac_directions.h"), os.path.join("..", "..", "include", "isac_beam_clean.h"), os.path.join("..", "..", "include", "isac_multistatic.h"), os.path.join("..", "..", "include", "isac_cancel_paths.h"), os.path.join("..", "..", "include", "isac_subsample.h"), os.path.join("..", "..", "include", "isac_localize.h"), os.path.join("..", "..", "include", "isac_track.h"), "upa_steer.hpp", "rdm_cell.hpp", "refine_dev.hpp", "beam_cell.hpp", "cpi_post.hpp"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function",
          "-Wno-unused-variable", "-Wno-unused-value", "-Wno-unused-result", "-ffp-contract=on"]

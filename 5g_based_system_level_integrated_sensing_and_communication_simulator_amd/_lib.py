@@ -306,6 +306,19 @@ LOCALIZE_PROTOTYPES = {
 }
 ISAC_LOCALIZE_MAX_NODES, ISAC_LOCALIZE_MAX_LINKS, ISAC_LOCALIZE_MAX_MEAS, ISAC_LOCALIZE_MAX_CAND = 64, 256, 4096, 256
 
+# include/isac_track.h, stand-alone like the two above and with a table of its own for the same reason (tests/test_localize_cpu.py pins the keys of LOCALIZE_PROTOTYPES).  Same
+# typing rule, plus int64_t as a return type (isac_track_state_bytes is a host-only size query); load() applies it last.  tests/test_track_cpu.py re-derives these lines.
+_TRACK_TABLE = (_P,) * 9                                                    # status, id, age, hits, misses, x, P, nis, dof
+TRACK_PROTOTYPES = {
+    "isac_track.h": {
+        "isac_track_state_bytes": (_I64, (_I32, _I32)),
+        "isac_track_reset_dev": (_INT, (_P, _P, _I32, _I32)),
+        "isac_track_step_dev": (_INT, (_P, _P, _I32, _I32, _P, _I32, _P, _P, _I32, _F64, _F64, _F64, _F64, _I32, _I32, _I32, _F64, _P, _P, _P, _P, _P, _P) + _TRACK_TABLE + (_P, _P, _P)),
+        "isac_track_get_dev": (_INT, (_P, _P, _I32, _I32) + _TRACK_TABLE),
+    },
+}
+ISAC_TRACK_MAX_BANKS, ISAC_TRACK_MAX_TRACKS, ISAC_TRACK_MAX_GROUPS, ISAC_TRACK_MAX_GROUP_MEAS, ISAC_TRACK_MAX_MEAS, ISAC_TRACK_MAX_NODES, ISAC_TRACK_MAX_LINKS = 1024, 256, 256, 256, 1 << 20, 64, 256
+
 
 def library_path() -> str:
     return _LIB_PATH
@@ -331,7 +344,7 @@ def load():
             except Exception:
                 pass
         lib = C.CDLL(_LIB_PATH, mode=C.RTLD_GLOBAL)
-        for name, (restype, argtypes) in list(PROTOTYPES.items()) + [line for tables in (STANDALONE_PROTOTYPES, LOCALIZE_PROTOTYPES) for table in tables.values() for line in table.items()]:
+        for name, (restype, argtypes) in list(PROTOTYPES.items()) + [line for tables in (STANDALONE_PROTOTYPES, LOCALIZE_PROTOTYPES, TRACK_PROTOTYPES) for table in tables.values() for line in table.items()]:
             fn = getattr(lib, name)  # AttributeError here = ABI drift between the headers and the .so
             fn.restype, fn.argtypes = restype, argtypes
         # the library writes whole structs into caller memory: version AND struct sizes must match this binding's mirrors

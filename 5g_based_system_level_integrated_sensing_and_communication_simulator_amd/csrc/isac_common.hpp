@@ -263,6 +263,7 @@ struct isac_ctx {
   isac::StageSlot stage_ring[isac::kStageSlots];   // pinned->device parameter uploads (stage_acquire / stage_commit)
   int stage_next = 0;
   isac::DevBuf localize;             // isac_position_map_dev / isac_localize_dev (localize.hip): the scene's tables, the blocks' candidate lists [blocks][256], the candidates, the outputs' device copies
+  isac::DevBuf track;                // isac_track_step_dev (track.hip): [nodes | links | the banks' group ranges | the groups | the measurements], one staged upload; assoc, assoc_kind [M], n_confirmed [B]
 };
 
 namespace isac {

@@ -160,6 +160,8 @@ int isac_path_frac_ramp_on(isac_ctx* ctx, hipStream_t st, const PathFrac& f, int
 // nothing of the context but the cached Kaiser window (isac_get_windows), writes ctx->range_refine only; calls and is called by no other unit.
 // ---------------------------------------------------------------- localize.hip: isac_position_map_dev, isac_localize_dev (include/isac_localize.h) -- per-link lists fused into positions.  Reads nothing of the
 // context, writes ctx->localize only; calls and is called by no other unit.
+// ---------------------------------------------------------------- track.hip: isac_track_state_bytes, isac_track_reset_dev, isac_track_step_dev, isac_track_get_dev (include/isac_track.h) -- Kalman track banks
+// across CPIs.  Reads nothing of the context, writes ctx->track (and the caller's state block) only; calls and is called by no other unit.
 // ---------------------------------------------------------------- cancel_paths.hip: isac_cancel_paths_dev (include/isac_cancel_paths.h) -- known reference signals projected out of a received waveform.  Calls
 // isac_path_coefs_on (unit gains, one receive element: the reference columns R [M x T] in ctx->coef; ctx->steer and ctx->phase_rx are rewritten with them) and is called by no
 // other unit; its own scratch is ctx->cancel_paths.

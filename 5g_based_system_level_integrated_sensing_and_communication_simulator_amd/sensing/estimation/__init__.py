@@ -9,6 +9,8 @@ from .refineTargets import refineTargets  # noqa: F401
 from .refineRange import refineRange  # noqa: F401
 from .linkMeasurements import linkMeasurements  # noqa: F401
 from .localizeTargets import localizeTargets  # noqa: F401
+from .trackMeasurements import trackMeasurements  # noqa: F401
+from .trackTargets import Tracker, trackTargets  # noqa: F401
 from .cleanTargets import cleanTargets  # noqa: F401
 from .beamClean import beamClean  # noqa: F401
 from .relaxTargets import relaxTargets  # noqa: F401
