@@ -145,6 +145,9 @@ CASES = {
     "a6_24prb": ("a6_24prb", "b5", {}),
     "a16_24prb_b1": ("a16_24prb", "b1", {}), "a16_24prb_b16": ("a16_24prb", "b16", {}),
     "upa2x4_24prb": ("upa2x4_24prb", "b5", {}),
+    # the asymmetric guard / training bands T.READER_BANDS (hr = 4, hc = 5, gr = 1, gc = 3, N = 78) on the beam planes' detector and on the rows the passes cancel on
+    "bands_b5": (T.BAND_SCENE, "b5", {}), "bands_b16_goca": (T.BAND_SCENE, "b16", dict(method="GOCA")), "bands_b5_soca": (T.BAND_SCENE, "b5", dict(method="SOCA")),
+    "bands_b5_os": (T.BAND_SCENE, "b5", dict(method="OS", rank=58)),
 }
 SCENES = tuple(dict.fromkeys(s for s, _, _ in CASES.values()))
 
@@ -162,7 +165,7 @@ def oracle_rows(scene):
     """Oracle only: O.mono_static_sensing -> the window's range rows and the geometry.  Computed once per scene and shared; callers must not modify it."""
     sc = make(scene)
     rp = sc.rp
-    cf = O.cfar2d_config(rp)
+    cf = T.oracle_config(scene, rp)                                        # the default bands for every scene but T.BAND_SCENE
     g = K.geometry(rp, cf)
     echo = O.mono_static_sensing(sc.tx_wave, sc.tx_grid.shape, sc.carrier, rp, sc.los, sc.noise, nfft=sc.wave.Nfft)
     rows = R.range_rows(echo, sc.tx_grid, g.n_ifft)[g.first_row - 1:g.first_row - 1 + g.n_rows].copy()

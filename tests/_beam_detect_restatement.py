@@ -151,7 +151,12 @@ SCENES = {
     "upa2x4_24prb": dict(kind="upa", **U.SCENES["upa2x4_24prb"]),
     WEAK: dict(kind="ula", rcs=(1.0, 0.01), **T.SCENES["a8_273prb"]),
 }
-GUARD, TRAIN = C.GUARD, C.TRAIN                                    # cfar2D.m:32-33
+GUARD, TRAIN = C.GUARD, C.TRAIN                                    # cfar2D.m:32-33: every scene but T.BAND_SCENE
+
+
+def bands_of(name):
+    """(guard, train) of a scene: T.READER_BANDS for T.BAND_SCENE, (GUARD, TRAIN) for every other one."""
+    return T.bands_of(name)
 
 
 @functools.lru_cache(maxsize=None)
@@ -221,6 +226,8 @@ CASES = (
     ("a16_24prb", "b1", "CA", 1), ("a16_24prb", "b16", "CA", 1),
     ("upa2x4_24prb", "b5", "CA", 1), ("upa2x4_24prb", "b16", "CA", 1),
     (WEAK, "b1_t2", "CA", 1), (WEAK, "b37", "CA", 1),
+    # the asymmetric bands (hr = 4, hc = 5, gr = 1, gc = 3, N = 78): every method, OS at rank 3N/4
+    (T.BAND_SCENE, "b5", "CA", 1), (T.BAND_SCENE, "b16", "GOCA", 1), (T.BAND_SCENE, "b5", "SOCA", 1), (T.BAND_SCENE, "b16", "OS", 58),
 )
 
 
@@ -229,13 +236,13 @@ def oracle_window(name):
     """Oracle stages of a scene: the complex window, its geometry, the per-antenna CA detections and their range list.  Computed once and shared; not to be modified."""
     sc = make(name)
     rp = sc.rp
-    cf = O.cfar2d_config(rp)
+    cf = T.oracle_config(name, rp)
     echo = O.mono_static_sensing(sc.tx_wave, sc.tx_grid.shape, sc.carrier, rp, sc.los, sc.noise, nfft=sc.wave.Nfft)
     rdm = O.rdm_explicit(echo, sc.tx_grid, int(rp.nIFFT), int(rp.nFFT))
     dets, all_rng, _ = detect_per_antenna(rdm, cf, rp.rRes, rp.vRes, int(rp.nFFT))
     rect = (cf.rowRange[0], cf.rowRange[1], cf.colRange[0], cf.colRange[1])
     hr, hc = cf.GuardBandSize[0] + cf.TrainingBandSize[0], cf.GuardBandSize[1] + cf.TrainingBandSize[1]
-    assert (tuple(cf.GuardBandSize), tuple(cf.TrainingBandSize)) == (GUARD, TRAIN)
+    assert (tuple(cf.GuardBandSize), tuple(cf.TrainingBandSize)) == bands_of(name) and (name == T.BAND_SCENE or bands_of(name) == (GUARD, TRAIN))
     fr, fc = rect[0] - hr, rect[2] - hc
     win = rdm[fr - 1:rect[1] + hr, fc - 1:rect[3] + hc, :].copy()          # the full map is not kept
     return SimpleNamespace(win=win, rect=rect, first_row=fr, first_col=fc, detections=dets, rng_est=np.unique(all_rng), rdm_max=float(np.abs(rdm).max()))
@@ -246,7 +253,7 @@ def oracle_beam_detect(name, beams, method, rank):
     """The oracle-only result of a case.  Computed once and shared; callers must not modify it."""
     sc, w = make(name), oracle_window(name)
     W, azi = weights(sc, beams)
-    t = beam_detect(w.win, W, w.first_row, w.first_col, w.rect, GUARD, TRAIN, method, rank, sc.rp)
+    t = beam_detect(w.win, W, w.first_row, w.first_col, w.rect, *bands_of(name), method, rank, sc.rp)
     t.W, t.beam_azi = W, azi
     t.azi = azi[t.beam - 1]
     return t

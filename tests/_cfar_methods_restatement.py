@@ -144,6 +144,13 @@ GUARD, TRAIN = (2, 2), (1, 1)                                                  #
 CHAIN_METHODS = (("CA", 1), ("GOCA", 1), ("SOCA", 1), ("OS", 18))              # N = 24; rank 18 = 3N/4
 
 
+def chain_methods(name):
+    """CHAIN_METHODS at the scene's bands (tests/_target_list_restatement.py: bands_of): the OS rank is 3N/4 of the scene's N, 18 of 24 at the default bands."""
+    import _target_list_restatement as R
+    n = n_train(*R.bands_of(name))
+    return tuple((m, 3 * n // 4 if m == "OS" else k) for m, k in CHAIN_METHODS)
+
+
 @functools.lru_cache(maxsize=None)
 def oracle_redetect(name, method, rank):
     """Oracle chain (tests/_target_list_restatement.py: oracle_targets) -> |rdm|^2 window -> the restatement.  Computed once and shared; callers must not modify it."""
@@ -153,8 +160,9 @@ def oracle_redetect(name, method, rank):
     nr, nc = t.S.shape
     rr, cc = np.arange(t.first_row, t.first_row + nr), np.arange(t.first_col, t.first_col + nc)
     win = np.transpose(t.rdm_at(rr[:, None], cc[None, :]), (2, 1, 0))          # rdm_at gives [A x nc x nr]
-    alpha = threshold_factor(method, n_train(GUARD, TRAIN), float(rp.Pfa), rank)
-    return redetect(np.abs(win) ** 2, t.first_row, t.first_col, t.rect, GUARD, TRAIN, method, alpha, rank, rp.rRes, rp.vRes, int(rp.nFFT), return_margin=True)
+    guard, train = R.bands_of(name)
+    alpha = threshold_factor(method, n_train(guard, train), float(rp.Pfa), rank)
+    return redetect(np.abs(win) ** 2, t.first_row, t.first_col, t.rect, guard, train, method, alpha, rank, rp.rRes, rp.vRes, int(rp.nFFT), return_margin=True)
 
 
 def chain_pairs():
@@ -162,6 +170,6 @@ def chain_pairs():
     import _target_list_restatement as R
     cleared, dropped = [], []
     for name in R.SCENES:
-        for method, rank in CHAIN_METHODS:
+        for method, rank in chain_methods(name):
             (cleared if oracle_redetect(name, method, rank).margin > GUARD_BAND else dropped).append((name, method, rank))
     return cleared, dropped

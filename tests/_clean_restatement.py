@@ -125,7 +125,12 @@ def replay(rows, g, row, nu, span_rows, sym_active=None):
 _MASKED = dict(n_ants=4, n_slots=4, seed=21, targets=((100.0, 20.0, 1.5), (100.0, -20.0, 1.5)), velocity=(T._V273, -T._V273))
 OWN = {"masked": dict(zero_s_slots=False, **_MASKED), "masked_gap": dict(zero_s_slots=True, **_MASKED)}
 RCS = (1.0, 0.01)
-SCENES = ("masked", "masked_gap", "split273", "a4_273prb", "a8_273prb", "a4_24prb_generic", "a4_24prb_truncated", "split24", "upa2x2_24prb", "upa8x16_24prb")
+# BANDS_SCENE: "masked" once more (another seed) at the asymmetric guard / training bands T.READER_BANDS -- the passes' detector, their list and the rows they cancel on all
+# take the window's geometry (hr = 4 rows, hc = 5 columns around the CUT zone, a 3 x 7 guard block) from the CPI
+BANDS_SCENE = "masked_g13_t32"
+OWN[BANDS_SCENE] = dict(zero_s_slots=False, **{**_MASKED, "seed": 27})
+T.BANDS[BANDS_SCENE] = T.READER_BANDS
+SCENES = ("masked", "masked_gap", "split273", "a4_273prb", "a8_273prb", "a4_24prb_generic", "a4_24prb_truncated", "split24", "upa2x2_24prb", "upa8x16_24prb", BANDS_SCENE)
 MASKED_CELL = (88, 124)                                                    # the weak target's cell
 GAP_MASK = np.r_[np.ones(42, dtype=np.uint8), np.zeros(14, dtype=np.uint8)]
 # the cases of tests/test_clean_cpu.py and tests/test_gpu_clean.py: name -> (scene, keywords of ``clean``)
@@ -135,6 +140,8 @@ CASES = {**{s: (s, {}) for s in SCENES if s != "masked_gap"},
          "masked_bigtol": ("masked", dict(merge_tol=1e6)),                  # the second entry lies 1.96 / L from the first: a tolerance that wide makes it a residue (step 7 taken)
          "masked_tol0": ("masked", dict(merge_tol=0.0)),                    # step 7 switched off
          "split273_one": ("split273", dict(max_iter=1)),                    # the closing pass after max_iter entries: n_left = the 3 cells of the second pass's list
+         BANDS_SCENE + "_goca": (BANDS_SCENE, dict(method="GOCA")), BANDS_SCENE + "_soca": (BANDS_SCENE, dict(method="SOCA")),
+         BANDS_SCENE + "_os": (BANDS_SCENE, dict(method="OS", rank=58)),      # rank 3N/4 of the N = 78 training cells
          "masked_goca": ("masked", dict(method="GOCA")), "split24_soca": ("split24", dict(method="SOCA")), "a4_24prb_generic_os": ("a4_24prb_generic", dict(method="OS", rank=18))}
 
 
@@ -168,7 +175,7 @@ def oracle_rows(scene):
     list's cells), as tests/_refine_restatement.py:oracle_scene forms it.  Computed once per scene and shared; callers must not modify it."""
     sc = make(scene)
     rp = sc.rp
-    cf = O.cfar2d_config(rp)
+    cf = T.oracle_config(scene, rp)                                        # the default bands for every scene but BANDS_SCENE
     g = geometry(rp, cf)
     echo = O.mono_static_sensing(sc.tx_wave, sc.tx_grid.shape, sc.carrier, rp, sc.los, sc.noise, nfft=sc.wave.Nfft)
     rows = R.range_rows(echo, sc.tx_grid, g.n_ifft)[g.first_row - 1:g.first_row - 1 + g.n_rows].copy()

@@ -31,9 +31,13 @@ NEAR, MID, FAR = (100.0, 20.0, 1.5), (-250.0, 80.0, 1.5), (470.0, 60.0, 1.5)    
 RTOL = 1e-10                                                                      # test_gpu_fullsize.RTOL
 
 
-def _case(name, nrb, n_ants, targets, velocity, los, n_sym, cut=0, silent=(), zero_from=None, grid_seed=1, noise_seed=1, pfa=1e-9, rcs=1.0, scs=SCS_KHZ):
+DEFAULT_BANDS = ((2, 2), (1, 1))                                                  # cfar2D.m:32-33: GuardBandSize, TrainingBandSize
+
+
+def _case(name, nrb, n_ants, targets, velocity, los, n_sym, cut=0, silent=(), zero_from=None, grid_seed=1, noise_seed=1, pfa=1e-9, rcs=1.0, scs=SCS_KHZ, bands=DEFAULT_BANDS):
     return SimpleNamespace(name=name, nrb=nrb, n_ants=n_ants, targets=tuple(targets), velocity=tuple(velocity), los=tuple(los), n_sym=n_sym, cut=cut,
-                           silent=tuple(silent), zero_from=zero_from, grid_seed=grid_seed, noise_seed=noise_seed, pfa=pfa, rcs=rcs, scs=scs)
+                           silent=tuple(silent), zero_from=zero_from, grid_seed=grid_seed, noise_seed=noise_seed, pfa=pfa, rcs=rcs, scs=scs,
+                           bands=(tuple(bands[0]), tuple(bands[1])))
 
 
 # `cut`: samples dropped from the waveform's end (the last symbol becomes incomplete: L_whole = L_out - 1); `silent`: transmit-silent columns (txGrid zero: rx .* conj(0));
@@ -54,6 +58,11 @@ NEIGHBOURS = (
     _case("k516_a48_owned", 43, 48, (MID,), (-6.0,), (1,), 14, grid_seed=111, noise_seed=0x1B01),
     _case("k516_a65_owned", 43, 65, (MID,), (-6.0,), (1,), 14, grid_seed=112, noise_seed=0x1B02),
 )
+# one CPI at other guard / training bands than the default, at the smallest shape the lazy tests use (tests/test_gpu_range_dead_columns.py: 25 PRB, 49 antennas, one target):
+# hr = 16 != hc = 4 and gr = 10 != gc = 1 -- the row window the lazy range kernel takes (CutRows) and the Doppler kernel's col_lo / nc differ from every other lazy case's.
+# The ten guard rows step over the range main lobe, which is what lets a K = 300 scene detect at all; RCS = 1e-4 keeps the eigenvalue gap at the signal / noise split three
+# decades above its guard (tests/test_lazy_cpi_reference_cpu.py)
+BAND_CASE = _case("k300_a49_bands_g10_1_t6_3", 25, 49, (NEAR,), (7.0,), (1,), 14, grid_seed=131, noise_seed=0x1D01, rcs=1e-4, bands=((10, 1), (6, 3)))
 SWEEP_SEEDS = (9001, 9008, 9009, 9019, 9032, 9034)
 SWEEP_NRB = (24, 43, 86, 129, 273)
 SWEEP_RCS = 1e-2
@@ -180,11 +189,19 @@ def covariance_bound(eta, m, ra_ref):
 
 
 # ---------------------------------------------------------------- the oracle's fft2D on a grid, with the suitability margins
+def cfar_config(sc):
+    """O.cfar2d_config(orp) at the case's bands (the default ones for every case that does not name others)."""
+    ocf = O.cfar2d_config(sc.orp)
+    ocf.GuardBandSize, ocf.TrainingBandSize = sc.case.bands
+    return ocf
+
+
 def oracle_chain(sc, grid):
-    """O.fft2d(orp, cfar2d_config(orp), grid, txGrid) with rdm_explicit -> namespace(est | None, rdm, detections, Ra, n_det, cfar_margin, eig_gap).
+    """O.fft2d(orp, cfar_config(sc), grid, txGrid) with rdm_explicit -> namespace(est | None, rdm, detections, Ra, n_det, cfar_margin, eig_gap).
     cfar_margin: smallest relative distance of a CUT cell's power from its threshold, over every antenna; eig_gap: (w[L-1] - w[L]) / w[0] at the signal / noise split
     L = numel(rngEst) of the descending eigenvalues (inf where there is no split: no detection, or L >= A)."""
-    ocf = O.cfar2d_config(sc.orp)
+    ocf = cfar_config(sc)
+    guard, train = ocf.GuardBandSize, ocf.TrainingBandSize
     keep = {}
 
     def rdm_fn(*args):
@@ -196,12 +213,12 @@ def oracle_chain(sc, grid):
         rdm, dets, ra = dbg.rdm, dbg.detections, dbg.Ra
     except ValueError:                                                     # findpeaks with NPeaks = 0 (music.m:102): no CUT detected
         est, rdm, ra = None, keep["rdm"], O.covariance(grid)
-        dets = [O.ca_cfar2d(np.abs(rdm[:, :, a]) ** 2, ocf.CUTIdx, ocf.Pfa) for a in range(sc.A)]
+        dets = [O.ca_cfar2d(np.abs(rdm[:, :, a]) ** 2, ocf.CUTIdx, ocf.Pfa, guard, train) for a in range(sc.A)]
         assert not any(d.shape[1] for d in dets)
     margin = np.inf
     for a in range(sc.A):
         p = np.abs(rdm[:, :, a]) ** 2
-        _, thr = O.ca_cfar2d(p, ocf.CUTIdx, ocf.Pfa, return_threshold=True)
+        _, thr = O.ca_cfar2d(p, ocf.CUTIdx, ocf.Pfa, guard, train, return_threshold=True)
         pc = p[ocf.CUTIdx[0] - 1, ocf.CUTIdx[1] - 1]
         margin = min(margin, float(np.min(np.abs(pc - thr) / np.maximum(np.abs(thr), 1e-300))))
     gap = np.inf

@@ -168,7 +168,7 @@ def oracle_scene(name):
     Computed once per scene and shared; callers must not modify it.  Only the rows of the window are kept (``rows_of``)."""
     sc = make(name)
     rp = sc.rp
-    cf = O.cfar2d_config(rp)
+    cf = T.oracle_config(name, rp)                                        # the default bands for every scene but T.BAND_SCENE
     n_ifft, n_fft = int(rp.nIFFT), int(rp.nFFT)
     echo = O.mono_static_sensing(sc.tx_wave, sc.tx_grid.shape, sc.carrier, rp, sc.los, sc.noise, nfft=sc.wave.Nfft)
     rows = range_rows(echo, sc.tx_grid, n_ifft)

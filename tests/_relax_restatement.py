@@ -16,6 +16,7 @@ import oracle as O
 
 import _clean_restatement as K
 import _refine_restatement as R
+import _target_list_restatement as T
 
 _LD = np.longdouble
 _PI_LD = 4 * np.arctan(_LD(1))
@@ -173,6 +174,11 @@ SCENES = {
     "upa2x2_L28": _scene(4, 2, 6, seed=65, upa=(2, 2)),
     "a4_L56_gap": _scene(4, 4, 6, seed=66, zero_s=True),                   # the 'S' slot (symbols 42 .. 55) silent
 }
+# "a4_L28" once more (another seed) at the asymmetric guard / training bands T.READER_BANDS: the rows the context holds are the CUT rows +- hr = 4, not 3, and every row
+# index of the call (the entries' rows, the spans, the edge rows) is taken against that window
+BANDS_SCENE = "a4_L28_g13_t32"
+SCENES[BANDS_SCENE] = _scene(4, 2, 6, seed=67)
+T.BANDS[BANDS_SCENE] = T.READER_BANDS
 GAP_MASK = K.GAP_MASK
 # ... and the end-to-end scene of tests/test_relax_cpu.py (oracle only): 16 elements, the tones 1.8 lobes apart
 OTHER = {"e2e_a16": _scene(16, 2, 6, lobes=0.9, seed=71)}
@@ -219,7 +225,7 @@ def oracle_rows(scene):
     """Oracle only: O.mono_static_sensing -> the window's range rows and the geometry (tests/_clean_restatement.py: geometry).  Shared; callers must not modify it."""
     sc = make(scene)
     rp = sc.rp
-    g = K.geometry(rp, O.cfar2d_config(rp))
+    g = K.geometry(rp, T.oracle_config(scene, rp))                         # the default bands for every scene but BANDS_SCENE
     echo = O.mono_static_sensing(sc.tx_wave, sc.tx_grid.shape, sc.carrier, rp, sc.los, sc.noise, nfft=sc.wave.Nfft)
     rows = R.range_rows(echo, sc.tx_grid, g.n_ifft)[g.first_row - 1:g.first_row - 1 + g.n_rows].copy()
     return SimpleNamespace(sc=sc, rp=rp, g=g, rows=rows, L=rows.shape[1], nu=true_nu(sc))
@@ -269,6 +275,9 @@ CASES = {
     "upa2x2": ("upa2x2_L28", lambda sc, g: _pair(sc), {}),
     "gap_mask": ("a4_L56_gap", lambda sc, g: _pair(sc), dict(sym_active=GAP_MASK)),
     "gap_nomask": ("a4_L56_gap", lambda sc, g: _pair(sc), dict(cycles=4)),
+    "bands_pair": (BANDS_SCENE, lambda sc, g: _pair(sc), {}),
+    "bands_three_clusters": (BANDS_SCENE, _three_clusters, {}),
+    "bands_edge_rows": (BANDS_SCENE, lambda sc, g: ([g.rect[0], g.rect[1], TARGET_ROW], [0.4 / sc.L, -0.2 / sc.L, true_nu(sc)[0]]), dict(span_rows=4)),   # spans that end on the window's first and last row
 }
 
 

@@ -113,6 +113,33 @@ SCENES = {
     "a4_24prb_truncated": dict(n_ants=4, n_slots=2, nrb=24, num_slots_param=1, seed=24, **_TWO24),  # nFFT = 16 < L = 28: truncation
 }
 
+# The same two targets at CFAR bands other than the default GuardBandSize (2, 2), TrainingBandSize (1, 1): hr = 4 != hc = 5 (neither the default 3) and gr = 1 != gc = 3, so every reader of the CPI's
+# window (the re-detection, this list, the refinement, the beam planes, the cancellation passes) sees a window whose row and column halves differ, a guard block that is not
+# square and -- GOCA / SOCA -- a front / rear split of 78 training cells.  The three guard columns step over the Doppler main lobe, so the default Pfa still detects.
+READER_BANDS = ((1, 3), (3, 2))
+DEFAULT_BANDS = ((2, 2), (1, 1))                                                              # cfar2D.m:32-33
+BAND_SCENE = "a4_273prb_g13_t32"
+SCENES[BAND_SCENE] = dict(n_ants=4, n_slots=4, seed=26, **_TWO)
+BANDS = {BAND_SCENE: READER_BANDS}                                                            # scene name -> (guard, train); every other scene: the default
+
+
+def bands_of(name):
+    return BANDS.get(name, DEFAULT_BANDS)
+
+
+def oracle_config(name, rp):
+    """O.cfar2d_config at the scene's bands."""
+    cf = O.cfar2d_config(rp)
+    cf.GuardBandSize, cf.TrainingBandSize = bands_of(name)
+    return cf
+
+
+def with_bands(name, cfar):
+    """The library's cfarConfig with the scene's bands set on its detector (the user setting: cf.cfarDetector2D.GuardBandSize = ...)."""
+    cfar.cfarDetector2D.GuardBandSize, cfar.cfarDetector2D.TrainingBandSize = bands_of(name)
+    return cfar
+
+
 # One target, 8 elements: only the conditioning test runs it (ORACLE_ONLY), to record that the Bartlett azimuth of the list is NOT fft2D's aziEst.
 ORACLE_ONLY = {"a8_single": dict(n_ants=8, n_slots=4, seed=25, targets=(_POS[0],), velocity=(_V273,), zero_s_slots=False)}
 
@@ -126,7 +153,7 @@ def make(name):
 def oracle_targets(name):
     """The oracle-only result: O.mono_static_sensing -> rdm -> the oracle CFAR -> the restatement.  Computed once per scene and shared; callers must not modify it."""
     sc = make(name)
-    cf = O.cfar2d_config(sc.rp)
+    cf = oracle_config(name, sc.rp)
     echo = O.mono_static_sensing(sc.tx_wave, sc.tx_grid.shape, sc.carrier, sc.rp, sc.los, sc.noise, nfft=sc.wave.Nfft)
     est, dbg = O.fft2d(sc.rp, cf, echo, sc.tx_grid, return_debug=True, rdm_fn=O.rdm_explicit)
     rect = (cf.rowRange[0], cf.rowRange[1], cf.colRange[0], cf.colRange[1])

@@ -76,6 +76,10 @@ SCENES = {
     "upa8x16_24prb": dict(nV=8, nH=16, seed=46, **_S24),
     "upa16x16_24prb": dict(nV=16, nH=16, seed=47, **_S24),
 }
+# ... and the 273-PRB scene at the asymmetric bands every reader of the CPI's window is run at (tests/_target_list_restatement.py: READER_BANDS)
+BAND_SCENE = "upa4x4_273prb_g13_t32"
+SCENES[BAND_SCENE] = dict(nV=4, nH=4, seed=48, n_slots=4, targets=_POS, velocity=(_V273, -_V273), zero_s_slots=False)
+T.BANDS[BAND_SCENE] = T.READER_BANDS
 
 
 def make(name):
@@ -95,7 +99,7 @@ def oracle_targets(name):
     """The oracle-only result, from the stage functions.  Computed once per scene and shared; callers must not modify it."""
     sc = make(name)
     rp = sc.rp
-    cf = O.cfar2d_config(rp)
+    cf = T.oracle_config(name, rp)
     echo = O.mono_static_sensing(sc.tx_wave, sc.tx_grid.shape, sc.carrier, rp, sc.los, sc.noise, nfft=sc.wave.Nfft)
     rdm = O.rdm_explicit(echo, sc.tx_grid, int(rp.nIFFT), int(rp.nFFT))
     dets, _, _ = detect_per_antenna(rdm, cf, rp.rRes, rp.vRes, int(rp.nFFT))

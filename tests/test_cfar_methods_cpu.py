@@ -194,6 +194,13 @@ def test_chain_pairs_clear_the_guard_band():
         print(f"{name} {method}: margin {r.margin:.3e}, {r.totalDetections} detections, numDets {r.numDets}{'  DROPPED' if (name, method, rank) in dropped else ''}")
     assert len(cleared) + len(dropped) == len(R.SCENES) * len(M.CHAIN_METHODS)
     assert len(dropped) <= 1, dropped
+    # the scene at other bands than the default: every method cleared (nothing of it is dropped at run time), asymmetric, 78 training cells that split into halves
+    guard, train = R.bands_of(R.BAND_SCENE)
+    assert (guard, train) == R.READER_BANDS != R.DEFAULT_BANDS == (M.GUARD, M.TRAIN) and M.n_train(guard, train) == 78
+    assert guard[0] != guard[1] and guard[0] + train[0] != guard[1] + train[1] and min(guard[0] + train[0], guard[1] + train[1]) >= 1
+    assert [p for p in cleared if p[0] == R.BAND_SCENE] == [(R.BAND_SCENE, m, k) for m, k in M.chain_methods(R.BAND_SCENE)] and M.chain_methods(R.BAND_SCENE)[3] == ("OS", 58)
+    assert all(M.chain_methods(n) == M.CHAIN_METHODS for n in R.SCENES if n != R.BAND_SCENE)
+    assert all(M.oracle_redetect(R.BAND_SCENE, m, k).totalDetections > 0 for m, k in M.chain_methods(R.BAND_SCENE))
     # CA on the oracle window is the oracle's own fft2D
     for name in R.SCENES:
         t, r = R.oracle_targets(name), M.oracle_redetect(name, "CA", 1)

@@ -109,6 +109,7 @@ def runs(pkg):
         if scene not in _runs:
             sc = BC.make(scene)
             rp, cf = _blocks(pkg, sc)
+            cf = T.with_bands(scene, cf)                                     # the default bands for every scene but T.BAND_SCENE
             est_mod = pkg.sensing.estimation
             c = pkg.Context()
             c.set_upa_doa(True)

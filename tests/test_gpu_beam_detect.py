@@ -61,6 +61,7 @@ def runs(pkg):
         if name not in _scenes:
             sc = R.make(name)
             rp, cf = _blocks(pkg, sc)
+            cf.cfarDetector2D.GuardBandSize, cf.cfarDetector2D.TrainingBandSize = R.bands_of(name)     # the default bands for every scene but the asymmetric one
             ctx = pkg.Context()
             d_txg, d_wave = ctx.to_device(sc.tx_grid), ctx.to_device(sc.tx_wave)
             echo = pkg.sensing.monoStaticSensing(d_wave, sc.tx_grid.shape, sc.carrier, rp, sc.los, noise=sc.noise, nfft=sc.wave.Nfft, ctx=ctx)
@@ -122,8 +123,9 @@ def test_lists_equal_the_restatement_on_the_devices_own_planes(pkg, runs, case):
     """Kernel level, exact: steps 3 and 4 of the restatement on the device's own beam planes give the device's per-beam lists, hits, row, col, beam and power (bytes)."""
     c = _case(pkg, runs, case)
     r, (_, _, method, rank) = c.r, case
-    alpha = M.threshold_factor(method, M.n_train(R.GUARD, R.TRAIN), float(r.rp.Pfa), rank)
-    want = R.beam_detect_on_planes(c.dbg.beam_pow, r.first_row, r.first_col, r.rect, R.GUARD, R.TRAIN, method, alpha, rank, r.rp)
+    guard, train = R.bands_of(case[0])
+    alpha = M.threshold_factor(method, M.n_train(guard, train), float(r.rp.Pfa), rank)
+    want = R.beam_detect_on_planes(c.dbg.beam_pow, r.first_row, r.first_col, r.rect, guard, train, method, alpha, rank, r.rp)
     res = c.res
     print(f"{case}: {res['n_total']} targets, {c.dbg.totalDetections} detections; rows {res['row'][:6].tolist()} cols {res['col'][:6].tolist()} beam {res['beam'][:6].tolist()}")
     assert len(c.dbg.detections) == len(want.detections) == c.W.shape[1]

@@ -165,12 +165,13 @@ def _run(pkg, ctx, name, rect=None):
     if key not in _runs:
         sc = R.make(name)
         rp, cf = _blocks(pkg, sc)
+        cf = R.with_bands(name, cf)                                            # the default bands for every scene but R.BAND_SCENE
         if rect is not None:
             cf = SimpleNamespace(CUTIdx=M.rectangle_cuts(rect), cfarDetector2D=cf.cfarDetector2D)
         d_txg, d_wave = ctx.to_device(sc.tx_grid), ctx.to_device(sc.tx_wave)
         echo = pkg.sensing.monoStaticSensing(d_wave, sc.tx_grid.shape, sc.carrier, rp, sc.los, noise=sc.noise, nfft=sc.wave.Nfft, ctx=ctx)
         est, dbg = pkg.sensing.estimation.fft2D(rp, cf, echo, d_txg, return_debug=True, ctx=ctx)
-        _runs[key] = SimpleNamespace(sc=sc, rp=rp, cf=cf, est=est, dbg=dbg, rect=_fft2d_mod(pkg)._cut_rectangle(cf.CUTIdx), grids=(echo, d_txg, d_wave))
+        _runs[key] = SimpleNamespace(name=name, sc=sc, rp=rp, cf=cf, est=est, dbg=dbg, rect=_fft2d_mod(pkg)._cut_rectangle(cf.CUTIdx), grids=(echo, d_txg, d_wave))
     return _runs[key]
 
 
@@ -180,8 +181,8 @@ def _again(pkg, ctx, r):
 
 
 def _check_against_restatement(pkg, ctx, r, method, rank, custom=0.0):
-    g, t = M.GUARD, M.TRAIN
-    alpha = custom if custom else _alpha(pkg, method, 24, float(r.rp.Pfa), rank)
+    g, t = R.bands_of(r.name)
+    alpha = custom if custom else _alpha(pkg, method, M.n_train(g, t), float(r.rp.Pfa), rank)
     want = M.redetect(r.dbg.power_window, r.dbg.first_row, r.dbg.first_col, r.rect, g, t, method, alpha, rank, r.rp.rRes, r.rp.vRes, int(r.rp.nFFT))
     st, got = _redetect_raw(pkg, ctx, r.sc.A, method, rank, custom)
     assert st == 0
@@ -195,12 +196,24 @@ def _check_against_restatement(pkg, ctx, r, method, rank, custom=0.0):
 METHOD_CASES = [("CA", 1, 0.0), ("GOCA", 1, 0.0), ("SOCA", 1, 0.0), ("OS", 1, 0.0), ("OS", 18, 0.0), ("OS", 24, 0.0), ("SOCA", 1, 20.0)]
 
 
+def _method_cases(name):
+    """METHOD_CASES at the scene's N: the OS ranks 1, 3N/4 and N (18 and 24 of the default 24 cells)."""
+    n = M.n_train(*R.bands_of(name))
+    return [(m, {18: 3 * n // 4, 24: n}.get(k, k) if m == "OS" else k, c) for m, k, c in METHOD_CASES]
+
+
 @pytest.mark.parametrize("name", list(R.SCENES))
 def test_redetect_equals_the_restatement_on_the_devices_own_window(pkg, ctx, name):
     r = _run(pkg, ctx, name)
     _again(pkg, ctx, r)
     seen = 0
-    for method, rank, custom in METHOD_CASES:
+    assert _method_cases("a4_273prb") == METHOD_CASES
+    if name == R.BAND_SCENE:                                                   # hr != hc, gr != gc, and a window cut accordingly
+        (gr, gc), (tr, tc) = R.bands_of(name)
+        assert gr != gc and gr + tr != gc + tc and M.n_train(*R.bands_of(name)) == 78
+        assert r.dbg.power_window.shape[:2] == (r.rect[1] - r.rect[0] + 1 + 2 * (gr + tr), r.rect[3] - r.rect[2] + 1 + 2 * (gc + tc))
+        assert (r.dbg.first_row, r.dbg.first_col) == (r.rect[0] - gr - tr, r.rect[2] - gc - tc)
+    for method, rank, custom in _method_cases(name):
         got = _check_against_restatement(pkg, ctx, r, method, rank, custom)
         seen += got.n_total
         print(f"{name} {method} rank {rank} custom {custom}: {got.n_total} detections, numDets {got.res.num_dets}")

@@ -95,6 +95,7 @@ def _scene(pkg, ctx, scene):
     if scene not in _runs:
         sc = K.make(scene)
         rp, cf = _blocks(pkg, sc)
+        cf = T.with_bands(scene, cf)                                         # the default bands for every scene but K.BANDS_SCENE
         est_mod = pkg.sensing.estimation
         d_txg, d_wave = ctx.to_device(sc.tx_grid), ctx.to_device(sc.tx_wave)
         echo = pkg.sensing.monoStaticSensing(d_wave, sc.tx_grid.shape, sc.carrier, rp, sc.los, noise=sc.noise, nfft=sc.wave.Nfft, ctx=ctx)

@@ -41,6 +41,8 @@ def _lazy_cpi(pkg, sc):
     ctx = pkg.Context()
     try:
         cf = pkg.sensing.detection.cfar2D(sc.rp)
+        assert (cf.cfarDetector2D.GuardBandSize, cf.cfarDetector2D.TrainingBandSize) == R.DEFAULT_BANDS
+        cf.cfarDetector2D.GuardBandSize, cf.cfarDetector2D.TrainingBandSize = sc.case.bands
         d_wave, d_txg = ctx.to_device(sc.tx_wave), ctx.to_device(sc.tx_grid)
         lz = pkg.sensing.monoStaticSensing(d_wave, sc.tx_grid.shape, sc.carrier, sc.rp, sc.los, nfft=4096, ctx=ctx, lazy=True, fuse_fft2d=(sc.rp, cf, d_txg),
                                            seed=sc.case.noise_seed, noise_domain="spectral")
@@ -109,6 +111,18 @@ def test_lazy_cpi_against_the_oracle(pkg, case, record_property):
     est, dbg, g = _lazy_cpi(pkg, sc)
     _compare_independent_field(sc, dbg, g, e, ra_ref, m, eta, record_property)
     _compare_same_field(sc, est, dbg, g, record_property)
+
+
+def test_lazy_cpi_at_asymmetric_bands(pkg, record_property):
+    """GuardBandSize (10, 1), TrainingBandSize (6, 3): the lazy range kernel's row window (CUT rows +- 16) and the Doppler kernel's columns (+- 4) at half sizes that differ
+    from each other and from the default 3; both comparisons, at the bounds every other case is held to."""
+    case = R.BAND_CASE
+    sc, e, ra_ref, m, eta = R.reference_of(case, pkg.sensing.radarParams)
+    est, dbg, g = _lazy_cpi(pkg, sc)
+    _compare_independent_field(sc, dbg, g, e, ra_ref, m, eta, record_property)
+    o = _compare_same_field(sc, est, dbg, g, record_property)
+    assert dbg.power_window.shape[:2] == (o.cfg.rowRange[1] - o.cfg.rowRange[0] + 1 + 32, o.cfg.colRange[1] - o.cfg.colRange[0] + 1 + 8)
+    assert o.n_det > sc.A and est is not None
 
 
 @pytest.mark.parametrize("seed", R.SWEEP_SEEDS)

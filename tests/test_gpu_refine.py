@@ -62,6 +62,7 @@ def _plain(pkg, ctx, name):
     if name not in _runs:
         sc = R.make(name)
         rp, cf = _blocks(pkg, sc)
+        cf = T.with_bands(name, cf)                                          # the default bands for every scene but T.BAND_SCENE
         est_mod = pkg.sensing.estimation
         d_txg, d_wave = ctx.to_device(sc.tx_grid), ctx.to_device(sc.tx_wave)
         echo = pkg.sensing.monoStaticSensing(d_wave, sc.tx_grid.shape, sc.carrier, rp, sc.los, noise=sc.noise, nfft=sc.wave.Nfft, ctx=ctx)

@@ -109,6 +109,7 @@ def _scene(pkg, ctx, scene):
     if scene not in _runs:
         sc = X.make(scene)
         rp, cf = _blocks(pkg, sc)
+        cf = T.with_bands(scene, cf)                                         # the default bands for every scene but X.BANDS_SCENE
         est_mod = pkg.sensing.estimation
         bufs = _fft2d(pkg, ctx, sc, rp, cf)
         before = _lists(pkg, ctx, X.is_upa(scene))

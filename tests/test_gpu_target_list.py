@@ -52,9 +52,13 @@ def _plain(pkg, ctx, name):
     if name not in _runs:
         sc = R.make(name)
         rp, cf = _blocks(pkg, sc)
+        cf = R.with_bands(name, cf)                                          # the default bands for every scene but R.BAND_SCENE
         d_txg, d_wave = ctx.to_device(sc.tx_grid), ctx.to_device(sc.tx_wave)
         echo = pkg.sensing.monoStaticSensing(d_wave, sc.tx_grid.shape, sc.carrier, rp, sc.los, noise=sc.noise, nfft=sc.wave.Nfft, ctx=ctx)
         est, dbg = pkg.sensing.estimation.fft2D(rp, cf, echo, d_txg, return_debug=True, ctx=ctx)
+        if name == R.BAND_SCENE:
+            (gr, gc), (tr, tc) = R.bands_of(name)
+            assert dbg.power_window.shape[:2] == (cf.CUTIdx[0].max() - cf.CUTIdx[0].min() + 1 + 2 * (gr + tr), cf.CUTIdx[1].max() - cf.CUTIdx[1].min() + 1 + 2 * (gc + tc))
         tl = pkg.sensing.estimation.targetList(ctx, snapshots=True)
         dbg2 = import_module(pkg.__name__ + ".sensing.estimation.fft2D").fft2D_debug(ctx, sc.A)
         for d in (echo, d_txg, d_wave):

@@ -57,10 +57,14 @@ def _plain(pkg, ctx, name):
     if name not in _runs:
         sc = R.make(name)
         rp, cf = _blocks(pkg, sc)
+        cf = T.with_bands(name, cf)                                          # the default bands for every scene but R.BAND_SCENE
         est_mod = pkg.sensing.estimation
         d_txg, d_wave = ctx.to_device(sc.tx_grid), ctx.to_device(sc.tx_wave)
         echo = pkg.sensing.monoStaticSensing(d_wave, sc.tx_grid.shape, sc.carrier, rp, sc.los, noise=sc.noise, nfft=sc.wave.Nfft, ctx=ctx)
         est, dbg = est_mod.fft2D(rp, cf, echo, d_txg, return_debug=True, ctx=ctx)
+        if name == R.BAND_SCENE:
+            (gr, gc), (tr, tc) = T.bands_of(name)
+            assert (gr + tr, gc + tc) == (4, 5) and dbg.power_window.shape[:2] == (np.ptp(cf.CUTIdx[0]) + 1 + 2 * (gr + tr), np.ptp(cf.CUTIdx[1]) + 1 + 2 * (gc + tc))
         tl = est_mod.targetListUPA(ctx, snapshots=True)
         map_after = ctx.angular_spectrum2d()
         with pytest.raises(pkg.IsacError) as e:                              # the ULA entry point keeps refusing a UPA

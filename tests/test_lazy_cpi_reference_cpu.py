@@ -19,7 +19,7 @@ import oracle as O
 import _lazy_cpi_reference as R
 from conftest import load_pkg
 
-ALL_CASES = tuple(R.TABLE) + tuple(R.NEIGHBOURS) + tuple(R.sweep_case(s) for s in R.SWEEP_SEEDS)
+ALL_CASES = tuple(R.TABLE) + tuple(R.NEIGHBOURS) + tuple(R.sweep_case(s) for s in R.SWEEP_SEEDS) + (R.BAND_CASE,)
 _chain = {}
 
 
@@ -62,7 +62,7 @@ def test_shape_table_reaches_the_slab_and_mask_cases():
 
 def test_scene_builder_parameter_sets_agree():
     pkg = load_pkg()
-    for case in tuple(R.TABLE) + tuple(R.NEIGHBOURS):
+    for case in tuple(R.TABLE) + tuple(R.NEIGHBOURS) + (R.BAND_CASE,):
         sc = R.build_scene(case, pkg.sensing.radarParams)
         got, want = sc.rp, sc.orp
         assert got.nIFFT == want.nIFFT == 4096 and got.nFFT == want.nFFT == (32 if case.n_sym == 14 else 64) and got.Pfa == want.Pfa == case.pfa
@@ -73,6 +73,7 @@ def test_scene_builder_parameter_sets_agree():
         cg, cw = pkg.sensing.detection.cfar2D(got), O.cfar2d_config(want)
         assert np.array_equal(cg.CUTIdx, cw.CUTIdx) and cg.cfarDetector2D.ProbabilityFalseAlarm == cw.Pfa
         assert cg.cfarDetector2D.GuardBandSize == cw.GuardBandSize and cg.cfarDetector2D.TrainingBandSize == cw.TrainingBandSize
+        assert (R.cfar_config(sc).GuardBandSize, R.cfar_config(sc).TrainingBandSize) == case.bands and (case.bands == R.DEFAULT_BANDS) == (case is not R.BAND_CASE)
         plan = R.slab_plan(case)
         assert (sc.K, sc.L_whole, sc.L_out, sc.A) == (plan.K, plan.L_whole, plan.L_out, case.n_ants) and sc.tx_grid.shape == (sc.K, sc.L_out, sc.A)
 
@@ -109,6 +110,20 @@ def test_guards_hold_on_the_reference_grid_with_a_decade_to_spare(case):
     assert o.cfar_margin > 1e-6, f"{case.name}: a CUT cell within {o.cfar_margin:.2e} of its threshold"
     assert o.eig_gap > 1e-8, f"{case.name}: eigenvalue gap {o.eig_gap:.2e} w[0] at the signal / noise split"
     assert (o.est is None) == (o.n_det == 0)
+
+
+def test_band_case_is_asymmetric_and_detects():
+    """The one lazy CPI at other bands: the default-band instance of every assertion above stays (the table, the neighbours, the sweep); this case differs from them in both
+    half sizes, in both dimensions' order, keeps its window inside the map and has detections on most antennas."""
+    case = R.BAND_CASE
+    assert all(c.bands == R.DEFAULT_BANDS == ((2, 2), (1, 1)) for c in ALL_CASES if c is not case)
+    (gr, gc), (tr, tc) = case.bands
+    hr, hc = gr + tr, gc + tc
+    assert (case.nrb, case.n_ants, len(case.targets), case.n_sym) == (25, 49, 1, 14) and gr != gc and hr != hc and min(gr, gc, tr, tc) >= 1 and hr != 3 and hc != 3
+    o = _oracle_on_reference(case)
+    sc = R.reference_of(case)[0]
+    assert o.cfg.rowRange[0] - hr >= 1 and o.cfg.rowRange[1] + hr <= 4096 and o.cfg.colRange[0] - hc >= 1 and o.cfg.colRange[1] + hc <= sc.orp.nFFT
+    assert sum(d.shape[1] > 0 for d in o.detections) > sc.A // 2 and o.n_det > sc.A and o.est is not None and 1 <= o.est.rngEst.size < sc.A
 
 
 def test_enough_scenes_have_a_detection():
